@@ -12,9 +12,13 @@ public outputs over RCCL after every launch, pipelined with the next launch.
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...      (the launcher form works too)
 
 Prints ONE JSON line on rank 0 (see the driver contract) with `roofline` (HBM-write bound kernel: algorithmic
-bytes / HIP-event kernel time) and, at N = 1, `cpu_baseline` (the C oracle timed on all host cores on a bounded
-sample of the same workload, with the reference WASM's all-core rate beside it: live when --reference-dir holds the
-reference, else as recorded in the build container by tools/wasm_baseline.py).
+bytes / HIP-event kernel time).  A plain run does only what that line's headline needs: set-up (placement, autotune),
+warm-up, the K timed steps, `--dump-outputs DIR` (the last step's outputs as .npy files) and the line.  `--full` adds
+the rest, as before: the counter passes of the HBM traffic, the on-device checks of the last step's bodies, the
+plain-buffer and store-ceiling legs, the collective alone (N > 1), the commit-count pass of the chain roofline and, at
+N = 1, `cpu_baseline` (the C oracle timed on all host cores on a bounded sample of the same workload, with the
+reference WASM's all-core rate beside it: live when --reference-dir holds the reference, else the rate recorded by
+tools/wasm_baseline.py in profiles/wasm_baseline.json).
 """
 import argparse
 import contextlib
@@ -318,6 +322,46 @@ def native_stdout_to_stderr():
         os.close(saved)
 
 
+DUMP_BODIES = 16                 # --dump-outputs: witnesses of the last step whose whole bodies are written
+DUMP_LIMIT = 64 << 20            # ... and the bytes of all the .npy files together
+
+
+def sample_rows(n, k, seed=20261016):
+    """a fixed, seeded choice of k of n row indices, ascending (all n when n <= k)"""
+    import numpy as np
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+
+def u32_words(t):
+    """a device or host array of 32-bit words (int32 / uint32 tensors; uint8 ones are read as little-endian u32 words) as uint32"""
+    import numpy as np
+    a = t.detach().contiguous().cpu().numpy() if hasattr(t, "detach") else np.ascontiguousarray(t)
+    return a.view(np.uint32)
+
+
+def write_outputs(d, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64, which holds every u32 word exactly (None: not written)"""
+    import numpy as np
+    out = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items() if v is not None}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT}")
+    os.makedirs(d, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+
+
+def rows_within(name, a, limit):
+    """{name: a} when a (2-D or 1-D, as float64) fits in `limit` bytes, else a fixed, seeded sample of its rows and their indices"""
+    rb = 8 * (a.size // max(a.shape[0], 1))
+    if a.shape[0] * rb <= limit:
+        return {name: a}
+    rows = sample_rows(a.shape[0], max(1, limit // rb))
+    return {name: a[rows], name + "_rows": rows}
+
+
 def placement_cost(ctx, before=None):
     c = ctx.placement_cost()
     if before:
@@ -420,10 +464,20 @@ def bench_chain(args, m, torch, dist, dev, world, rank, local_rank, devices=None
             sig = f"{int(w64.sum().item())}:{int((w64 * pos).sum().item())}:{out['root'].cpu().tolist()}"
             sigs = gather_strings(dist, world, sig)
             assert len(set(sigs)) == 1, f"the ranks disagree about the gathered h_out or the root: {sigs}"
-    # untimed: one more pass over the first MiB (at most) of the preimage whose consumer checks EVERY step witness against the
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        arrays = {"root": u32_words(out["root"])}
+        for name in ("public", "status", "h_out_all", "h_out_parents_all", "chunk_cvs_local", "records", "violations"):
+            if out.get(name) is not None:
+                arrays.update(rows_within(name, u32_words(out[name]).astype(np.float64), 6 << 20))
+        if key is not None:
+            arrays.update(rows_within("commitments", u32_words(d_pts[:local_steps]).astype(np.float64), 6 << 20))
+        write_outputs(args.dump_outputs, arrays)
+    # untimed, --full: one more pass over the first MiB (at most) of the preimage whose consumer checks EVERY step witness against the
     # step circuit's rank-1 constraints while it sits in the ring
-    verification = "none"
-    if circuit in m.BUILTIN_R1CS and commit_only is None and r1cs_t is None:
+    verification = "none" if args.full or circuit not in m.BUILTIN_R1CS or commit_only is not None or r1cs_t is not None else \
+        "not checked: the untimed constraint pass runs with --full"
+    if args.full and circuit in m.BUILTIN_R1CS and commit_only is None and r1cs_t is None:
         r1cs = m.R1cs(ctx)
         vsteps = [0]
         d_viol = torch.zeros(16384, dtype=torch.int32, device=dev)
@@ -441,7 +495,7 @@ def bench_chain(args, m, torch, dist, dev, world, rank, local_rank, devices=None
         r1cs.close()
     if key is not None:
         assert int(d_st[:local_steps].abs().sum().item()) == 0 and int(d_pts[:local_steps].max(dim=1).values.min().item()) > 0
-        if commit_records is not None and r1cs_t is not None:
+        if args.full and commit_records is not None and r1cs_t is not None:
             # the commitments of the fold-shaped pass against the kernel that READS bodies: the first 256 leaf steps' bodies, regenerated
             kk = min(256, local_steps)
             d_b = torch.empty((kk, ctx.body_bytes), dtype=torch.uint8, device=dev)
@@ -475,6 +529,10 @@ def bench_chain(args, m, torch, dist, dev, world, rank, local_rank, devices=None
                 "algorithmic_bytes_per_step": per,
                 "note": ("bytes per step = body written + record read" + (" + body read back by the constraint check" if r1cs_t is not None else "")
                          + "; end-to-end per-GPU rate incl. planner, H2D and launch gaps")}
+    elif not args.full:
+        peak, src = valu_ceiling()
+        roof = {"bound": "valu", "achieved": None, "peak": peak, "unit": "G field mul/s", "frac": None, "traffic": None, "peak_source": src,
+                "note": "the point additions of the commit kernel are counted in an untimed pass of their own: with --full"}
     else:
         key.count(True)
         run()
@@ -492,7 +550,7 @@ def bench_chain(args, m, torch, dist, dev, world, rank, local_rank, devices=None
                         + ("" if commit_only is not None else ", witness generation" + (" and constraint check" if r1cs_t is not None else "") + " included in the time"
                            + ("" if commit_records is not None else "; this consumer also reads every body back"))}
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if rank == 0 and world == 1 and args.full and args.cpu_seconds > 0:
         import numpy as np
         cpu = cpu_baseline(circuit, recs16.view(np.uint32), args.cpu_seconds, args.reference_dir, args.reference_seconds)
     if rank == 0:
@@ -544,7 +602,7 @@ def main():
     ap.add_argument("--circuit", default="compression")
     ap.add_argument("--variant", type=int, default=None, help="kernel tuning variant (B3W_VARIANT)")
     ap.add_argument("--pitch", type=int, default=0, help="body pitch in bytes (0 = contiguous bodies)")
-    ap.add_argument("--cpu-seconds", type=float, default=5.0, help="budget of the cpu_baseline leg (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=5.0, help="budget of the cpu_baseline leg of --full (0 = skip)")
     ap.add_argument("--reference-dir", default="/root/reference",
                     help="cpu_baseline: where the reference checkout lies.  When it is there (the build container) its WASM witness generator "
                          "is timed live on all host cores (tools/wasm_baseline.py); when not (the GPU box: the reference cannot travel) the "
@@ -590,16 +648,24 @@ def main():
                     help="batch workload with --inner 0: how long the K timed steps should last together (the driver's busy "
                          "sampler needs seconds, not a 9 ms burst)")
     ap.add_argument("--traffic", default="auto", choices=["auto", "quoted"],
-                    help="roofline.traffic of the batch line at N = 1: auto = measured by this invocation (two rocprofv3 --pmc child passes of 8 "
-                         "launches, before anything else; a few seconds) where rocprofv3 is there and this run is not itself profiled, "
+                    help="roofline.traffic of the batch line at N = 1: auto = with --full, measured by this invocation (two rocprofv3 --pmc child "
+                         "passes of 8 launches, before anything else; a few seconds) where rocprofv3 is there and this run is not itself profiled, "
                          "else — and with `quoted` — the figure of the recorded passes (profiles/traffic_latest.json), said so in traffic_source")
     ap.add_argument("--traffic-child", default=None, help=argparse.SUPPRESS)      # (internal: what --traffic auto runs under rocprofv3)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure as well: the counter passes of --traffic auto, the on-device checks of the "
+                         "last step's bodies, the plain-buffer and store-ceiling legs, the collective alone (N > 1), the commit-count pass "
+                         "of the chain roofline and cpu_baseline.  Without it a run sets up, warms up, times the steps, writes "
+                         "--dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float64: every u32 "
+                         "word exactly; whole bodies for a fixed, seeded sample of the witnesses; 64 MB at most in all)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args.gpus, sys.argv[1:], args.launch_timeout))      # nothing above has loaded torch or HIP
-    measured_traffic, traffic_why_not = None, "--traffic quoted"
-    if args.traffic == "auto" and args.traffic_child is None and args.workload == "batch" and "WORLD_SIZE" not in os.environ:
+    measured_traffic, traffic_why_not = None, "--traffic quoted" if args.traffic == "quoted" else "the counter passes run with --full"
+    if args.full and args.traffic == "auto" and args.traffic_child is None and args.workload == "batch" and "WORLD_SIZE" not in os.environ:
         measured_traffic, traffic_why_not = live_traffic(args)      # (children of a process that has not touched the GPU yet)
 
     rank = int(os.environ.get("RANK", "0"))
@@ -707,8 +773,10 @@ def main():
                 return None if self.last is None else self.outs[self.last]
         ex = NativeExchange()
 
+    last_pub = [None]                                       # the public outputs of the latest launch (--dump-outputs)
+
     def launch(post=None):
-        pub = ex.next_buffer()
+        pub = last_pub[0] = ex.next_buffer()
         ctx.run_device(d_recs.data_ptr(), n, d_bodies.data_ptr(), pitch, pub.data_ptr(), d_status.data_ptr(),
                        stream.cuda_stream)
         if post if post is not None else args.exchange == "every":
@@ -812,7 +880,13 @@ def main():
     launches = args.steps * inner
     kern_ms = ev0.elapsed_time(ev1) / launches                        # HIP events on the launch stream
     assert int(d_status.abs().sum().item()) == 0, "a witness reported a non-zero status"
-    if world > 1 and args.exchange != "none":               # the gathered buffer of the last launch: every rank's outputs
+    if args.dump_outputs and rank == 0:
+        rows = sample_rows(n, max(1, min(DUMP_BODIES, (DUMP_LIMIT // 2) // (2 * ctx.body_bytes))))
+        body_rows = d_bodies.tensor().view(n, pitch)[torch.from_numpy(rows).to(dev), :ctx.body_bytes]
+        write_outputs(args.dump_outputs, {"public_outputs": u32_words(last_pub[0]), "status": u32_words(d_status),
+                                          "bodies_sample": u32_words(body_rows), "bodies_sample_rows": rows,
+                                          "public_outputs_all": u32_words(allpub) if world > 1 and allpub is not None else None})
+    if args.full and world > 1 and args.exchange != "none":   # the gathered buffer of the last launch: every rank's outputs
         assert allpub.shape == (world * n, npub) and int((allpub[:, :npub].abs().sum(dim=1) == 0).sum().item()) == 0
         assert torch.equal(allpub[rank * n:(rank + 1) * n], ex.bufs[ex.last]), "this rank's share of the gathered outputs differs from what it sent"
         # ... and the OTHER ranks' shares against what this rank computes itself for their first records (the inputs are a function of the
@@ -829,15 +903,17 @@ def main():
             ctx.run_device(d_rq.data_ptr(), k, d_k_bodies.data_ptr(), 0, d_k_pub.data_ptr(), d_k_status.data_ptr(), stream.cuda_stream)
             torch.cuda.synchronize()
             assert torch.equal(allpub[q * n:q * n + k, :npub].to(torch.int32), d_k_pub), f"rank {q}'s share of the gathered outputs is not what its inputs give"
-    # untimed: every body of the last launch is checked on the device: the rank-1 constraint check
+    # untimed, --full: every body of the last launch is checked on the device: the rank-1 constraint check
     # Az*Bz = Cz with the constraint system derived from the circuit text where there is one (blake3_compression), and the
     # recompute-and-compare tamper check
-    d_mm = torch.full((n,), -1, dtype=torch.int32, device=dev)
-    ctx.verify_device(d_bodies.data_ptr(), n, pitch, d_mm.data_ptr(), stream.cuda_stream)
-    torch.cuda.synchronize()
-    assert int(d_mm.abs().sum().item()) == 0, "on-device verification found a body that is not a valid witness"
-    verified = "recomputed from own inputs"
-    if circuit in m.BUILTIN_R1CS:
+    verified = "not checked: the on-device checks of the last launch's bodies run with --full"
+    if args.full:
+        d_mm = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        ctx.verify_device(d_bodies.data_ptr(), n, pitch, d_mm.data_ptr(), stream.cuda_stream)
+        torch.cuda.synchronize()
+        assert int(d_mm.abs().sum().item()) == 0, "on-device verification found a body that is not a valid witness"
+        verified = "recomputed from own inputs"
+    if args.full and circuit in m.BUILTIN_R1CS:
         r1cs = m.R1cs(ctx)
         d_viol = torch.full((n,), -1, dtype=torch.int32, device=dev)
         r1cs.check_device(d_bodies.data_ptr(), n, pitch, d_viol.data_ptr(), 0, stream.cuda_stream)
@@ -846,11 +922,11 @@ def main():
         verified = f"r1cs: 0 of {r1cs.n_constraints} constraints violated by any of the {n} bodies; " + verified
         r1cs.close()
 
-    # untimed, N = 1: (1) the same kernel, same variant, on a plain hipMalloc buffer — what a caller who brings its own buffer gets;
+    # untimed, N = 1, --full: (1) the same kernel, same variant, on a plain hipMalloc buffer — what a caller who brings its own buffer gets;
     # (2) the pure-store ceilings of both buffers (b3w_bodies_store_rate: nothing but the stores, in the witness kernels' two shapes):
     # what `achieved` is a fraction of on THIS chip, next to the 8 TB/s of the data sheet.  (The bodies are overwritten: checks are done.)
     plain, ceiling = None, None
-    if world == 1:
+    if world == 1 and args.full:
         # (a baseline leg never fails the bench: the measurement is done; an out-of-memory here — the second buffer is 49 GB for config 3 —
         # or a B3WError must not cost the driver its JSON line)
         d_plain = ctx_plain = None
@@ -891,9 +967,9 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     kern_per_rank = [float(x) for x in gather_strings(dist, world, repr(kern_ms))]     # every rank's own HIP-event average
-    # the collective alone (N > 1): 20 all-gathers of the public outputs back to back, nothing else on the device, HIP events
+    # the collective alone (N > 1, --full): 20 all-gathers of the public outputs back to back, nothing else on the device, HIP events
     ex_ms = 0.0
-    if world > 1:
+    if world > 1 and args.full:
         torch.cuda.synchronize()
         dist.barrier()
         ev0.record(stream)
@@ -956,7 +1032,7 @@ def main():
                        "circuit": circuit, "batch_per_gpu": n, "launches_per_step": inner, "witnesses_per_step": world * n * inner,
                        "timed_region_s": elapsed, "witness_bytes": ctx.body_bytes, "pitch": pitch,
                        "kernel_variant": variant_name(chosen),
-                       "verified_on_device": True, "verification": verified,
+                       "verified_on_device": args.full, "verification": verified,
                        "placement": placements[0], "placement_per_rank": placements,
                        "exchange": "none" if world == 1 else
                                    f"--exchange {args.exchange}: " + {
@@ -969,7 +1045,8 @@ def main():
                        "exchange_impl": ("native b3w_comm (" + comm.transport + ")" if comm is not None else "torch.distributed") if world > 1 else "none",
                        "comm_size": (int(m.lib().b3w_comm_size(comm.handle)) if comm is not None else dist.get_world_size()) if world > 1 else 1,
                        "exchange_ms_per_rank": {"public_outputs": ex_per_rank,
-                                                "what": "one all-gather of the batch's public outputs with nothing else on the device: HIP events around 20, after the timed region"},
+                                                "what": "one all-gather of the batch's public outputs with nothing else on the device: HIP events around 20, after the timed region"
+                                                        + ("" if args.full or world == 1 else " (measured with --full; 0 here)")},
                        "devices_per_rank": devices, **place_cost},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source, "traffic_measured": traffic_parts,
@@ -986,7 +1063,7 @@ def main():
                 out["roofline"]["of_measured_ceiling"] = achieved / best       # of the best store-only shape on the SAME (placed) buffer
                 if "achieved" in plain:
                     out["roofline"]["plain_of_measured_ceiling"] = plain["achieved"] / max(ceiling["plain"].values())
-        if args.cpu_seconds > 0 and world == 1:
+        if args.full and args.cpu_seconds > 0 and world == 1:
             out["cpu_baseline"] = cpu_baseline(circuit, recs, args.cpu_seconds, args.reference_dir, args.reference_seconds)
         print(json.dumps(out), flush=True)
     if comm is not None:

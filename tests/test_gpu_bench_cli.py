@@ -22,7 +22,7 @@ def _bench(*args, env=None):
 
 
 def test_default_line_has_the_contract_fields():
-    d = _bench("--batch", "512", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1")
+    d = _bench("--batch", "512", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1", "--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -62,6 +62,46 @@ def test_default_line_has_the_contract_fields():
     assert 0.995 < r["traffic"] / r["algorithmic_bytes_per_launch"] < 1.03, (r["traffic"], r["algorithmic_bytes_per_launch"])
 
 
+def test_plain_run_is_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """without --full: the contract fields, none of the extra legs; --dump-outputs writes the last step's outputs — the public outputs,
+    the statuses and whole bodies of a fixed sample of the witnesses — as float64 .npy files, the same in every run with the same arguments"""
+    import numpy as np
+    args = ("--batch", "512", "--steps", "2", "--warmup", "1", "--inner", "2", "--placement", "plain")
+    d = _bench(*args, "--dump-outputs", str(tmp_path / "a"))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["config"]["launches_per_step"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert abs(d["value"] - d["config"]["witnesses_per_step"] / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert "cpu_baseline" not in d and "plain" not in d["roofline"] and d["roofline"]["traffic_measured"] is None
+    assert d["config"]["verified_on_device"] is False and "--full" in d["config"]["verification"]
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == {"public_outputs", "status", "bodies_sample", "bodies_sample_rows"}
+    assert all(a.dtype == np.float64 for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert got["status"].shape == (512,) and (got["status"] == 0).all() and got["public_outputs"].shape[0] == 512
+    rows = got["bodies_sample_rows"].astype(np.int64)
+    assert len(rows) == 16 and (np.diff(rows) > 0).all()
+    m = T.pkg()
+    recs = m.workloads.config2_compression(512)
+    bad, want = T.oracle_batch_u32("compression", recs[rows])
+    assert bad == 0 and np.array_equal(got["bodies_sample"].astype(np.uint32).view(np.uint8), want)
+    _bench(*args, "--dump-outputs", str(tmp_path / "b"))
+    for k, a in got.items():
+        assert np.array_equal(np.load(tmp_path / "b" / (k + ".npy")), a), k
+
+
+def test_chain_run_dumps_the_last_pass(tmp_path):
+    import numpy as np
+    import blake3_ref as B
+    d = _bench("--workload", "chain", "--preimage-mib", "0.25", "--steps", "1", "--warmup", "1", "--placement", "plain",
+               "--dump-outputs", str(tmp_path))
+    assert "cpu_baseline" not in d and "--full" in d["config"]["verification"]
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert {"root", "public", "status", "h_out_all", "records"} <= set(got) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert (got["status"] == 0).all() and got["h_out_all"].shape == (4096, 8)
+    m = T.pkg()
+    assert list(got["root"].astype(np.uint32)) == B.hash_words(m.workloads.lcg_preimage(1 << 18, seed=1).tobytes())
+
+
 def test_nova_line_is_labelled_config3():
     d = _bench("--circuit", "nova_vesta", "--batch", "512", "--steps", "2", "--warmup", "1", "--inner", "2", "--cpu-seconds", "0", "--placement", "plain", "--traffic", "quoted")
     assert d["roofline"]["traffic_measured"] is None and "--traffic quoted" in (d["roofline"]["traffic_source"] or "--traffic quoted")
@@ -87,7 +127,7 @@ def test_gpus_2_exchange_modes(mode, impl):
     every rank's own kernel time and the collective's own time are in the line.  --exchange-impl native: the gather goes through the
     C-ABI's b3w_comm (here its host shared-memory transport: two ranks on one GPU) instead of torch.distributed."""
     d = _bench("--gpus", "2", "--batch", "256", "--steps", "2", "--warmup", "1", "--inner", "3", "--exchange", mode, "--placement", "plain",
-               "--exchange-impl", impl, env={"B3W_DIST_BACKEND": "gloo"})
+               "--exchange-impl", impl, "--full", env={"B3W_DIST_BACKEND": "gloo"})
     c, r = d["config"], d["roofline"]
     assert d["n_gpus"] == 2 and c["exchange_mode"] == mode and c["exchange"].startswith(f"--exchange {mode}")
     assert c["exchange_impl"] == ("native b3w_comm (host)" if impl == "native" else "torch.distributed")
@@ -141,7 +181,7 @@ def test_chain_workload_with_each_consumer(consumer):
     the N = 1 line.  (commit and check alone: tools/jobs/r04 runs; here one of each roofline kind)"""
     # (placement: the default, placed ring only for the plain pass — the allocator's search and claim check are seconds per process)
     d = _bench("--workload", "chain", "--preimage-mib", "0.25", "--steps", "1", "--warmup", "1", "--consumer", consumer, "--cpu-seconds", "1",
-               *([] if consumer == "none" else ["--placement", "plain"]))
+               "--full", *([] if consumer == "none" else ["--placement", "plain"]))
     r = d["roofline"]
     assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9 and r["frac"] > 0.001, r
     if consumer == "none":

@@ -99,7 +99,7 @@ def test_generic_wasm_fallback_reproduces_the_reference_loader():
 
 
 @needs_node
-def test_addon_identifies_reference_binaries_and_module_swap():
+def test_addon_identifies_reference_binaries_and_module_swap(tmp_path):
     if not os.path.isdir(REF):
         pytest.skip("reference checkout not present (GPU box)")
     r = _node("""
@@ -115,8 +115,7 @@ def test_addon_identifies_reference_binaries_and_module_swap():
     import torch
     if torch.cuda.is_available():
         return
-    inp = os.path.join(T.ROOT, "gpurun_out", "_swap_in.json")
-    os.makedirs(os.path.dirname(inp), exist_ok=True)
+    inp = str(tmp_path / "swap_in.json")
     json.dump(T.golden("compression")["cases"][0]["input"], open(inp, "w"))
     gw = os.path.join(REF, "build/blake3_compression/blake3_compression_js/generate_witness.js")
     r = subprocess.run([NODE, "-r", os.path.join(JS, "register.js"), gw,

@@ -3,9 +3,9 @@
 fault soonest, every line held against what has never run anywhere yet (an RCCL communicator of more than one rank, xGMI).
 
 For N in --gpus-list (default 1 2 4 8):
-  batch     python bench.py --gpus N                                      (config 2: weak scaling, all-gather of the public outputs)
-  chain     python bench.py --gpus N --workload chain --preimage-mib 1    --exchange-impl native   (config 4)
-  stream    python bench.py --gpus N --workload chain --preimage-mib M    --exchange-impl native   (config 5: M = 1024, --quick: 64)
+  batch     python bench.py --full --gpus N                                      (config 2: weak scaling, all-gather of the public outputs)
+  chain     python bench.py --full --gpus N --workload chain --preimage-mib 1    --exchange-impl native   (config 4)
+  stream    python bench.py --full --gpus N --workload chain --preimage-mib M    --exchange-impl native   (config 5: M = 1024, --quick: 64)
 and per run, from the JSON line: n_gpus = N; one device per rank and all distinct under RCCL (bench.py refuses otherwise: checked again here);
 every rank's body-buffer placement; kernel_ms_per_rank and exchange_ms_per_rank complete (N values each) and the spread between ranks;
 the cross-rank checks bench.py makes at the end of every N > 1 run (batch: each rank recomputes rows of every other rank's gathered
@@ -22,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def run_bench(extra, timeout):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + extra          # (--full: the cross-rank checks and the collective alone)
     t0 = time.time()
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
