@@ -21,7 +21,7 @@ from . import workloads  # noqa: F401
 
 
 def __getattr__(name):
-    if name in ("sharding", "chain"):  # import torch.distributed: load on demand
+    if name in ("sharding", "chain", "bao"):  # import torch (.distributed): load on demand
         import importlib
         return importlib.import_module(__name__ + "." + name)
     raise AttributeError(name)
@@ -35,6 +35,7 @@ CIRCUIT_ID = {c: i for i, c in enumerate(CIRCUITS)}
 B3W_OK = 0
 PLACEMENT_NAMES = {0: "plain", 1: "mixed", 2: "interleaved"}          # B3W_PLACEMENT_* of include/b3wit.h
 B3W_E_ASSERT_FAILED = 4
+B3W_E_BAD_ARGUMENT = 100
 B3W_E_NO_DEVICE = 101
 B3W_E_DOMAIN = 103
 
@@ -164,6 +165,12 @@ def lib():
         "b3w_chain_status": (vp, [vp]),
         "b3w_chain_local_cvs": (vp, [vp]),
         "b3w_chain_root": (vp, [vp]),
+        "b3w_bao_outboard_size": (u64, [u64]),
+        "b3w_bao_outboard_device": (i32, [vp, vp, u64, vp, vp, vp, vp]),
+        "b3w_bao_path_nodes": (i32, [u64, u64, ctypes.POINTER(u64), ctypes.POINTER(u32)]),
+        "b3w_bao_slice": (i32, [vp, u64, u64, vp, vp, ctypes.POINTER(u64)]),
+        "b3w_sample_rows": (ctypes.c_int64, [u64, vp, u32, vp]),
+        "b3w_sample_plan_device": (i32, [vp, u64, vp, vp, vp, u32, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -183,7 +190,9 @@ EXPORTED_SYMBOLS = ("b3w_abi_version", "b3w_identify_wasm", "b3w_create", "b3w_d
                     "b3w_commit_key_create", "b3w_commit_key_create_ex", "b3w_commit_key_create_folded", "b3w_slot_widths", "b3w_commit_key_window", "b3w_commit_key_destroy", "b3w_commit_key_count", "b3w_commit_key_counts", "b3w_commit_records_device", "b3w_commit_records", "b3w_chain_commit_only", "b3w_chain_commit_from_records", "b3w_chain_commit_overlap", "b3w_chain_violations_device", "b3w_chain_commitments", "b3w_chain_check_constraints", "b3w_chain_violations", "b3w_batch_commit_device", "b3w_batch_commit", "b3w_commit_consumer",
                     "b3w_comm_unique_id", "b3w_comm_create", "b3w_comm_create_host", "b3w_comm_create_external", "b3w_comm_rank", "b3w_comm_size", "b3w_comm_destroy", "b3w_comm_allgather", "b3w_batch_allgather_public",
                     "b3w_chain_create", "b3w_chain_destroy", "b3w_chain_run_leaves", "b3w_chain_run_parents", "b3w_chain_shard", "b3w_chain_run_parents_sharded", "b3w_chain_allgather_hout", "b3w_chain_allgather_hout_host", "b3w_chain_exchange_ms", "b3w_chain_info",
-                    "b3w_chain_outputs", "b3w_chain_records", "b3w_chain_public", "b3w_chain_status", "b3w_chain_local_cvs", "b3w_chain_root")
+                    "b3w_chain_outputs", "b3w_chain_records", "b3w_chain_public", "b3w_chain_status", "b3w_chain_local_cvs", "b3w_chain_root",
+                    "b3w_bao_outboard_size", "b3w_bao_outboard_device", "b3w_bao_path_nodes", "b3w_bao_slice", "b3w_sample_rows",
+                    "b3w_sample_plan_device")
 
 
 class graph_capture:

@@ -1,0 +1,159 @@
+"""Bao outboards and challenged chunk paths (b3w_bao_* / b3w_sample_*).
+
+A data-availability challenge names a few chunk indices; the provider answers from the file and its bao outboard (the tree's
+parent nodes, kept beside the file).  outboard() makes the outboard of a preimage in device memory; plan_samples() plans the step
+records of the challenged chunk paths from the outboard and those chunks' bytes alone, verifying each path against the root;
+prove_samples() runs their witnesses, constraint checks and commitments through the batch calls, batch by batch.  The records are
+word for word those the chain planner writes for the same chunks (ChainPlanner.plan), so every step is the reference's
+prove_chunk_hash step (rust_fold/src/main.rs:41-203 over hash_with_path's slice, rust_fold/src/blake3_hash.rs:17-93)."""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import B3W_OK, B3WError, BodyBuffer, lib
+
+STATUS = {0: "verified", 1: "chunk bytes do not match", 2: "a path node or the root does not match", 3: "outboard header is not the length"}
+
+
+def _chk(ctx, rc, what):
+    if rc != B3W_OK:
+        raise B3WError(rc, f"{what}: status {rc}: {ctx.last_error() if ctx is not None else ''}")
+
+
+def _stream(stream):
+    return stream or torch.cuda.current_stream().cuda_stream
+
+
+def num_chunks(length):
+    return max(1, (length + 1023) // 1024)
+
+
+def outboard_size(length):
+    return lib().b3w_bao_outboard_size(length)
+
+
+def outboard(ctx, d_preimage, stream=0):
+    """-> (uint8 CUDA tensor: the bao outboard, root words as uint32 numpy [8] = BLAKE3(preimage)).
+    d_preimage: a uint8 CUDA tensor (the device-resident case this is built for), or host bytes — those are copied to the device
+    first, and for a large file that copy takes far longer than the outboard itself."""
+    if not isinstance(d_preimage, torch.Tensor):
+        d_preimage = torch.from_numpy(np.frombuffer(bytes(d_preimage), dtype=np.uint8).copy()).cuda()
+    assert d_preimage.is_cuda and d_preimage.dtype == torch.uint8 and d_preimage.is_contiguous()
+    length = d_preimage.numel()
+    n = num_chunks(length)
+    dev = d_preimage.device
+    ob = torch.empty(outboard_size(length), dtype=torch.uint8, device=dev)
+    levels = torch.empty((2 * n + 64) * 8, dtype=torch.int32, device=dev)
+    root = torch.empty(8, dtype=torch.int32, device=dev)
+    _chk(ctx, lib().b3w_bao_outboard_device(ctx.handle, d_preimage.data_ptr() if length else None, length, ob.data_ptr(), levels.data_ptr(),
+                                             root.data_ptr(), _stream(stream)), "b3w_bao_outboard_device")
+    return ob, root.cpu().numpy().view(np.uint32).copy()
+
+
+def path_nodes(chunk, n_chunks):
+    """pre-order indices of the chunk's path nodes, root first (node i: outboard bytes [8 + 64 i, 8 + 64 i + 64))"""
+    out = (ctypes.c_uint64 * 64)()
+    cnt = ctypes.c_uint32()
+    _chk(None, lib().b3w_bao_path_nodes(chunk, n_chunks, out, ctypes.byref(cnt)), "b3w_bao_path_nodes")
+    return list(out[:cnt.value])
+
+
+def slice_chunk(outboard_bytes, length, chunk, chunk_bytes):
+    """the bao slice of one chunk (header, path nodes root first, the chunk's bytes) from a host outboard"""
+    ob = outboard_bytes.cpu().numpy().tobytes() if isinstance(outboard_bytes, torch.Tensor) else bytes(outboard_bytes)
+    cb = bytes(chunk_bytes)
+    ln = ctypes.c_uint64()
+    _chk(None, lib().b3w_bao_slice(ob, length, chunk, cb, None, ctypes.byref(ln)), "b3w_bao_slice")
+    out = ctypes.create_string_buffer(ln.value)
+    _chk(None, lib().b3w_bao_slice(ob, length, chunk, cb, out, ctypes.byref(ln)), "b3w_bao_slice")
+    return out.raw
+
+
+def sample_rows(length, chunks):
+    """-> row_first (numpy uint64 [n_samples + 1]): sample s owns rows [row_first[s], row_first[s + 1])"""
+    ch = np.ascontiguousarray(chunks, dtype=np.uint64)
+    rf = np.zeros(ch.size + 1, dtype=np.uint64)
+    total = lib().b3w_sample_rows(length, ch.ctypes.data, ch.size, rf.ctypes.data)
+    if total < 0:
+        raise B3WError(-total, "b3w_sample_rows: a chunk index is not below the chunk count")
+    return rf
+
+
+def chunk_bytes(preimage, chunks, device="cuda"):
+    """the sampled chunks' bytes as plan_samples takes them (uint8 [n_samples, 1024], zero past the end): what a provider reads
+    from its file for a challenge.  preimage: host bytes / numpy, or a CUDA tensor."""
+    ch = [int(c) for c in chunks]
+    if isinstance(preimage, torch.Tensor):
+        pad = torch.zeros(num_chunks(preimage.numel()) * 1024, dtype=torch.uint8, device=preimage.device)
+        pad[:preimage.numel()] = preimage
+        return pad.view(-1, 1024)[torch.tensor(ch, dtype=torch.long, device=preimage.device)].contiguous()
+    data = np.frombuffer(bytes(preimage), dtype=np.uint8)
+    out = np.zeros((len(ch), 1024), dtype=np.uint8)
+    for s, c in enumerate(ch):
+        part = data[c * 1024:c * 1024 + 1024]
+        out[s, :part.size] = part
+    return torch.from_numpy(out).to(device)
+
+
+def plan_samples(ctx, d_outboard, length, root, chunks, d_chunk_bytes, stream=0):
+    """The step records of the challenged chunk paths, from the outboard and the sampled chunks' bytes alone.  Returns a dict:
+    records (int32 CUDA [rows, 32], sample-major: each sample's leaf blocks, then its parent steps bottom up), row_first (numpy
+    [n_samples + 1]), sample_status (numpy int32: 0 verified, 1 chunk bytes, 2 a path node or the root, 3 the header — STATUS),
+    provable (numpy bool: the reference's fold of that path ends in the root, b3w_chain_path_provable)."""
+    L = lib()
+    ch = np.ascontiguousarray(chunks, dtype=np.uint64)
+    rf = sample_rows(length, ch)
+    dev = d_outboard.device
+    assert d_chunk_bytes.is_cuda and d_chunk_bytes.dtype == torch.uint8 and d_chunk_bytes.numel() >= ch.size * 1024
+    recs = torch.empty((int(rf[-1]), 32), dtype=torch.int32, device=dev)
+    st = torch.full((ch.size,), -1, dtype=torch.int32, device=dev)
+    rw = np.ascontiguousarray(root, dtype=np.uint32)
+    _chk(ctx, L.b3w_sample_plan_device(ctx.handle, length, d_outboard.data_ptr(), rw.ctypes.data, ch.ctypes.data, ch.size,
+                                       d_chunk_bytes.data_ptr(), recs.data_ptr(), st.data_ptr(), _stream(stream)), "b3w_sample_plan_device")
+    n = num_chunks(length)
+    provable = np.array([bool(L.b3w_chain_path_provable(int(c), n)) for c in ch], dtype=bool)
+    return dict(records=recs, row_first=rf, sample_status=st.cpu().numpy(), provable=provable)
+
+
+def prove_samples(ctx, d_outboard, length, root, chunks, d_chunk_bytes, batch_steps=4096, consumer=None, commit_key=None, r1cs=None,
+                  stream=0):
+    """plan_samples, then every row's witness through ONE body buffer of batch_steps bodies: per batch the witness kernel
+    (b3w_batch_run_device), the constraint check (r1cs), the commitments from the records (commit_key) and
+    consumer(d_bodies [count, body_bytes] uint8 view, pitch, first_row, count).  With a commit_key and neither consumer nor r1cs
+    no bodies are written at all: the commitments come from the records alone (as b3w_chain_commit_only).
+    Returns plan_samples' dict plus public (int32 CUDA [rows, 15]), status (int32 CUDA [rows]), violations (int32 CUDA [rows] or
+    None) and points (uint8 CUDA [rows, 64] or None)."""
+    s = _stream(stream)
+    out = plan_samples(ctx, d_outboard, length, root, chunks, d_chunk_bytes, stream=s)
+    recs = out["records"]
+    rows = recs.shape[0]
+    dev = recs.device
+    pub = torch.zeros((rows, ctx.public_words), dtype=torch.int32, device=dev)
+    status = torch.full((rows,), -1, dtype=torch.int32, device=dev)
+    viol = torch.full((rows,), -1, dtype=torch.int32, device=dev) if r1cs is not None else None
+    points = torch.zeros((rows, 64), dtype=torch.uint8, device=dev) if commit_key is not None else None
+    bodies_needed = consumer is not None or r1cs is not None or commit_key is None
+    body = ctx.body_bytes
+    buf = BodyBuffer(ctx, min(batch_steps, max(rows, 1)) * body) if bodies_needed and rows else None
+    try:
+        view = buf.tensor() if buf is not None else None
+        for r0 in range(0, rows, batch_steps):
+            k = min(batch_steps, rows - r0)
+            d_rec = recs.data_ptr() + r0 * 128
+            if commit_key is not None:
+                commit_key.commit_records_device(d_rec, k, points.data_ptr() + r0 * 64, status.data_ptr() + r0 * 4,
+                                                 0 if bodies_needed else pub.data_ptr() + r0 * ctx.public_words * 4, s)
+            if not bodies_needed:
+                continue
+            ctx.run_device(d_rec, k, buf.ptr, 0, pub.data_ptr() + r0 * ctx.public_words * 4, status.data_ptr() + r0 * 4, s)
+            if r1cs is not None:
+                r1cs.check_device(buf.ptr, k, 0, viol.data_ptr() + r0 * 4, 0, s)
+            if consumer is not None:
+                consumer(view[:k * body].view(k, body), body, r0, k)
+        torch.cuda.synchronize(dev)
+    finally:
+        if buf is not None:
+            buf.free()
+    out.update(public=pub, status=status, violations=viol, points=points)
+    return out

@@ -1,0 +1,389 @@
+// b3w_bao.hip — bao outboards of device-resident preimages, and the step records of challenged chunk paths planned from an
+// outboard plus the challenged chunks' bytes alone.
+//
+// Format (bao 0.12 as the reference's hash_with_path consumes it, rust_fold/src/blake3_hash.rs:17-93; 1 KiB chunks, BLAKE3's tree:
+// the left subtree holds the largest power of two of chunks strictly below the count):
+//   outboard = 8-byte little-endian content length, then the n_chunks - 1 parent nodes in pre-order, 64 bytes each
+//              (left child CV || right child CV, 8 little-endian words each)
+//   pre-order: the root is node 0; a node at position p over m chunks (k = largest power of two below m) has its left subtree
+//              from p + 1 and its right subtree from p + k
+//   slice of chunk c = the header, the path's nodes root first, the chunk's bytes
+//
+//   b3w_bao_cv_kernel        one lane per chunk: 1 KiB in, its chaining value out (no step records) — the throughput shape
+//   b3w_bao_cv_quad_kernel   four lanes per chunk (the leaf planner's quad compression): small chunk counts, where latency counts
+//   (the tree)               b3w_chain_tree_device: the chain's own level arrays, spine and root
+//   b3w_bao_emit_kernel      one thread per parent node: its two child CVs from the level arrays to its pre-order position
+//   b3w_sample_plan_kernel   one thread per challenged chunk: its leaf records from its bytes, its path verified top down against the
+//                            root the way bao's decoder does, its parent records bottom up with the outboard's CVs
+#include "b3w_internal.h"
+#include "b3w_blake3_dev.h"
+
+namespace {
+
+// ---- the step records (b3wit.h batch input format) --------------------------------------------------------------------
+// The same words b3w_plan_leaf_kernel and plan_path (b3w_plan.hip) write for a chunk: the sampled path's records must equal the
+// chain planner's row for row (tests/test_gpu_bao.py), so these restate those loops for one chunk whose sibling CVs come from
+// the outboard instead of the level arrays.
+// the leaf steps of one chunk of `bytes` bytes (<= 1024) with P parents above it: one record per block into rec (32 words each) and the
+// chunk's chaining value into h (with P == 0 it is the ROOT-flagged output: the hash words of a one-chunk input)
+__device__ __forceinline__ void plan_leaf_chunk(const uint8_t *src, uint32_t bytes, uint64_t c, uint32_t P, uint32_t *rec, uint32_t h[8]) {
+  const uint32_t n_blocks = bytes ? (bytes + 63) / 64 : 1;
+  iv(h);
+  for (uint32_t j = 0; j < n_blocks; ++j) {
+    const uint32_t bb = bytes - j * 64 < 64 ? bytes - j * 64 : 64;
+    uint32_t m[16];
+    if (bb == 64 && ((uintptr_t)src & 3) == 0) {
+#pragma unroll
+      for (int k = 0; k < 16; ++k) m[k] = reinterpret_cast<const uint32_t *>(src + j * 64)[k];
+    } else {
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        uint32_t w = 0;
+        for (int q = 0; q < 4; ++q) { const uint32_t p = k * 4 + q; if (p < bb) w |= (uint32_t)src[j * 64 + p] << (8 * q); }
+        m[k] = w;
+      }
+    }
+    uint32_t *r = rec + j * 32;
+    r[0] = n_blocks; r[1] = j;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r[2 + k] = h[k];
+    r[10] = (uint32_t)c; r[11] = (uint32_t)(c >> 32);
+    r[12] = P + 1; r[13] = P + 1; r[14] = P;              // leaf_depth, total_depth, depth (blake3_circuit.rs:83-110)
+#pragma unroll
+    for (int k = 0; k < 16; ++k) r[15 + k] = m[k];
+    r[31] = bb;
+    // flags as Blake3GetFlag assigns them (circuits/blake3_nova.circom:122-167)
+    const uint32_t last = j == n_blocks - 1;
+    const uint32_t d = (j == 0 ? 1u : 0u) | (last ? 2u : 0u) | ((last && P == 0) ? 8u : 0u);
+    uint32_t o[8];
+    blake3_cv(h, m, (uint32_t)c, (uint32_t)(c >> 32), bb, d, o);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) h[k] = o[k];
+  }
+}
+
+// one parent step of chunk c's path (height g: bit_left = bit g of c is clear, depth = plen - 1 - g): its record into r, and h, the
+// running value, becomes the step's h_out.  m8 = the CV the reference's driver hands the circuit at that height (blake3_hash.rs:63-78).
+__device__ __forceinline__ void plan_parent_step(uint32_t *r, uint32_t h[8], const uint32_t *m8, bool bit_left, uint64_t c, uint32_t n_blocks,
+                                                 uint32_t plen, uint32_t depth) {
+  r[0] = n_blocks; r[1] = n_blocks;                       // block_count stays at n_blocks on parent steps (blake3_nova.circom:251)
+#pragma unroll
+  for (int k = 0; k < 8; ++k) r[2 + k] = h[k];
+  r[10] = (uint32_t)c; r[11] = (uint32_t)(c >> 32);
+  r[12] = plen + 1; r[13] = plen + 1; r[14] = depth;
+  uint32_t m[16];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { const uint32_t w = m8[k]; r[15 + k] = w; r[23 + k] = 0; m[bit_left ? 8 + k : k] = w; }   // sibling CV, then zeros (blake3_circuit.rs:230-245)
+  r[31] = 64;
+  // the next step's h = this step's h_out: compress(IV, h || sibling or sibling || h, PARENT [| ROOT at depth 0])
+#pragma unroll
+  for (int k = 0; k < 8; ++k) m[bit_left ? k : 8 + k] = h[k];
+  uint32_t ivv[8], o[8];
+  iv(ivv);
+  blake3_cv(ivv, m, 0, 0, 64, 4u | (depth == 0 ? 8u : 0u), o);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) h[k] = o[k];
+}
+
+// ---- chunk chaining values -----------------------------------------------------------------------------------------
+// lane = chunk.  Neighbouring lanes' blocks lie 1 KiB apart, so every load is a whole 16-byte quarter of a block and the next block's
+// four loads are in flight while the current block is compressed.  n == 1: the chunk's output carries ROOT (the hash itself).
+__global__ __launch_bounds__(256) void b3w_bao_cv_kernel(const uint8_t *__restrict__ pre, uint64_t len, uint64_t n, uint32_t *__restrict__ cv) {
+  const uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= n) return;
+  const uint64_t off = c * 1024;
+  const uint32_t bytes = (uint32_t)(len - off < 1024 ? len - off : 1024);
+  const uint32_t root = n == 1 ? 8u : 0u;
+  const uint8_t *src = pre + off;
+  uint32_t h[8], o[8], m[16];
+  iv(h);
+  if (bytes == 1024 && ((uintptr_t)src & 15) == 0) {
+    const uint4 *p = reinterpret_cast<const uint4 *>(src);
+    uint4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
+    for (uint32_t j = 0; j < 16; ++j) {
+      m[0] = q0.x; m[1] = q0.y; m[2] = q0.z; m[3] = q0.w; m[4] = q1.x; m[5] = q1.y; m[6] = q1.z; m[7] = q1.w;
+      m[8] = q2.x; m[9] = q2.y; m[10] = q2.z; m[11] = q2.w; m[12] = q3.x; m[13] = q3.y; m[14] = q3.z; m[15] = q3.w;
+      if (j < 15) { q0 = p[4 * j + 4]; q1 = p[4 * j + 5]; q2 = p[4 * j + 6]; q3 = p[4 * j + 7]; }
+      const uint32_t d = (j == 0 ? 1u : 0u) | (j == 15 ? 2u | root : 0u);
+      blake3_cv(h, m, (uint32_t)c, (uint32_t)(c >> 32), 64, d, o);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) h[k] = o[k];
+    }
+  } else {                                               // the last chunk of a length that is no multiple of 1 KiB, or an unaligned preimage
+    const uint32_t nb = bytes ? (bytes + 63) / 64 : 1;
+    for (uint32_t j = 0; j < nb; ++j) {
+      const uint32_t bb = bytes - j * 64 < 64 ? bytes - j * 64 : 64;
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        uint32_t w = 0;
+        for (int x = 0; x < 4; ++x) { const uint32_t q = k * 4 + x; if (q < bb) w |= (uint32_t)src[j * 64 + q] << (8 * x); }
+        m[k] = w;
+      }
+      const uint32_t d = (j == 0 ? 1u : 0u) | (j == nb - 1 ? 2u | root : 0u);
+      blake3_cv(h, m, (uint32_t)c, (uint32_t)(c >> 32), bb, d, o);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) h[k] = o[k];
+    }
+  }
+  uint4 *dst = reinterpret_cast<uint4 *>(cv + c * 8);
+  dst[0] = make_uint4(h[0], h[1], h[2], h[3]);
+  dst[1] = make_uint4(h[4], h[5], h[6], h[7]);
+}
+
+// four lanes per chunk (b3w_plan_leaf_quad_kernel without the records): lane col holds column col of the state
+__global__ __launch_bounds__(64) void b3w_bao_cv_quad_kernel(const uint8_t *__restrict__ pre, uint64_t len, uint64_t n, uint32_t *__restrict__ cv) {
+  __shared__ uint32_t Ms[16][16];
+  const uint32_t q = threadIdx.x >> 2, col = threadIdx.x & 3u;
+  const uint64_t i = (uint64_t)blockIdx.x * 16 + q;
+  const bool live = i < n;                               // (a dead quad walks the workgroup's first chunk with its store masked: DPP wants whole quads)
+  const uint64_t c = live ? i : (uint64_t)blockIdx.x * 16;
+  const uint64_t off = c * 1024;
+  const uint32_t bytes = (uint32_t)(len - off < 1024 ? len - off : 1024);
+  const uint32_t nb = bytes ? (bytes + 63) / 64 : 1;
+  const uint32_t root = n == 1 ? 8u : 0u;
+  const uint8_t *src = pre + off;
+  uint32_t *M = Ms[q];
+  uint32_t h_lo = col == 0 ? 0x6A09E667u : col == 1 ? 0xBB67AE85u : col == 2 ? 0x3C6EF372u : 0xA54FF53Au;
+  uint32_t h_hi = col == 0 ? 0x510E527Fu : col == 1 ? 0x9B05688Cu : col == 2 ? 0x1F83D9ABu : 0x5BE0CD19u;
+  for (uint32_t j = 0; j < nb; ++j) {                    // (uniform over the quad)
+    const uint32_t bb = bytes - j * 64 < 64 ? bytes - j * 64 : 64;
+    uint32_t m4[4];
+    if (bb == 64 && ((uintptr_t)src & 15) == 0) {
+      const uint4 v = *reinterpret_cast<const uint4 *>(src + j * 64 + col * 16);
+      m4[0] = v.x; m4[1] = v.y; m4[2] = v.z; m4[3] = v.w;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        uint32_t w = 0;
+        for (int x = 0; x < 4; ++x) { const uint32_t p = (col * 4 + k) * 4 + x; if (p < bb) w |= (uint32_t)src[j * 64 + p] << (8 * x); }
+        m4[k] = w;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) M[col * 4 + k] = m4[k];
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (one wave: the quad's words are in LDS)
+    const uint32_t d = (j == 0 ? 1u : 0u) | (j == nb - 1 ? 2u | root : 0u);
+    plan_quad_cv(h_lo, h_hi, M, (int)col, (uint32_t)c, (uint32_t)(c >> 32), bb, d);
+    __builtin_amdgcn_wave_barrier();                     // (every lane has read this block's words before the next block's overwrite them)
+  }
+  if (live) { cv[c * 8 + col] = h_lo; cv[c * 8 + 4 + col] = h_hi; }
+}
+
+// ---- pre-order emission ---------------------------------------------------------------------------------------------
+// A node with d ancestors, r of them passed on their right, covering chunks from a, sits at pre-order position d + a - r: the nodes
+// before it are its ancestors and the parents of the left subtrees hanging off its path (a chunks in r subtrees: a - r parents).
+// Complete subtree node (level t >= 1, index i, chunks from a = i 2^t) inside spine segment s (2^L chunks from lo, its root at depth
+// plen - L reached by s right turns): d = plen - t, r = s + popcount((a - lo) >> t).  Spine node suffix[k] (k < last): d = r = k, a = lo[k].
+// Threads [0, n - popcount(n)) take the complete nodes level by level, the last `last` threads the spine nodes.  Thread 0 also writes
+// the header.  (The nodes sit 8 bytes off a 16-byte boundary: 8-byte stores.)
+__global__ __launch_bounds__(256) void b3w_bao_emit_kernel(const uint32_t *__restrict__ levels, uint64_t n, uint64_t len, B3wSpine sp,
+                                                           uint8_t *__restrict__ out) {
+  const uint64_t tid = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (tid == 0) *reinterpret_cast<uint2 *>(out) = make_uint2((uint32_t)len, (uint32_t)(len >> 32));
+  const uint64_t ncomplete = n - __popcll(n);
+  if (tid >= n - 1) return;
+  const uint32_t *lc, *rc;
+  uint64_t pos;
+  if (tid < ncomplete) {
+    uint64_t rem = tid, off = 0;                         // off: word offset of level t - 1
+    uint32_t t = 1;
+    while (rem >= (n >> t)) { rem -= n >> t; off += (n >> (t - 1)) * 8; t++; }
+    const uint64_t a = rem << t;
+    const uint32_t s = seg_of(sp, a);
+    pos = (uint64_t)(sp.plen[s] - t) + a - s - (uint64_t)__popcll((a - sp.lo[s]) >> t);
+    lc = levels + off + rem * 16;
+    rc = lc + 8;
+  } else {
+    const uint32_t k = (uint32_t)(tid - ncomplete);
+    pos = sp.lo[k];
+    lc = levels + sp.seg_off[k];
+    rc = levels + sp.suf_off[k + 1];
+  }
+  uint2 *dst = reinterpret_cast<uint2 *>(out + 8 + pos * 64);
+  const uint4 l0 = reinterpret_cast<const uint4 *>(lc)[0], l1 = reinterpret_cast<const uint4 *>(lc)[1];
+  const uint4 r0 = reinterpret_cast<const uint4 *>(rc)[0], r1 = reinterpret_cast<const uint4 *>(rc)[1];
+  dst[0] = make_uint2(l0.x, l0.y); dst[1] = make_uint2(l0.z, l0.w); dst[2] = make_uint2(l1.x, l1.y); dst[3] = make_uint2(l1.z, l1.w);
+  dst[4] = make_uint2(r0.x, r0.y); dst[5] = make_uint2(r0.z, r0.w); dst[6] = make_uint2(r1.x, r1.y); dst[7] = make_uint2(r1.z, r1.w);
+}
+
+// ---- challenged paths ------------------------------------------------------------------------------------------------
+struct Root8 { uint32_t w[8]; };
+
+__device__ __forceinline__ bool eq8(const uint32_t *a, const uint32_t *b) {
+  uint32_t x = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) x |= a[k] ^ b[k];
+  return x == 0;
+}
+
+// desc[2 s] = chunk, desc[2 s + 1] = first row of sample s.  status: 0 verified, 1 chunk bytes, 2 a path node or the root, 3 header.
+__global__ __launch_bounds__(64) void b3w_sample_plan_kernel(uint64_t len, uint64_t n, const uint32_t *__restrict__ ob, Root8 root,
+                                                             const uint64_t *__restrict__ desc, uint32_t n_samples,
+                                                             const uint8_t *__restrict__ chunk_bytes, uint32_t *__restrict__ recs,
+                                                             int32_t *__restrict__ status) {
+  const uint32_t s = blockIdx.x * 64 + threadIdx.x;
+  if (s >= n_samples) return;
+  const uint64_t c = desc[2 * s], row = desc[2 * s + 1];
+  const uint32_t P = path_len(c, n);
+  const uint64_t off = c * 1024;
+  const uint32_t bytes = (uint32_t)(len - off < 1024 ? len - off : 1024);
+  const uint32_t n_blocks = bytes ? (bytes + 63) / 64 : 1;
+  uint32_t *r = recs + row * 32;
+  uint32_t h[8];
+  plan_leaf_chunk(chunk_bytes + (uint64_t)s * 1024, bytes, c, P, r, h);
+  int32_t st = ((uint64_t)ob[0] | ((uint64_t)ob[1] << 32)) != len ? 3 : 0;
+  // top down, as bao's decoder: the root node against the root, every lower node against its half of the node above, the chunk
+  // against its half of the lowest node
+  uint64_t pos[64];
+  uint32_t want[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) want[k] = root.w[k];
+  uint64_t p = 0, cc = c, m = n;
+  for (uint32_t i = 0; i < P; ++i) {
+    const uint32_t *node = ob + 2 + p * 16;
+    uint32_t mw[16], ivv[8], o[8];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) mw[k] = node[k];
+    iv(ivv);
+    blake3_cv(ivv, mw, 0, 0, 64, 4u | (i == 0 ? 8u : 0u), o);
+    if (!eq8(o, want) && st == 0) st = 2;
+    uint64_t k2 = 1;
+    while (k2 * 2 < m) k2 *= 2;
+    const bool left = cc < k2;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) want[k] = left ? mw[k] : mw[8 + k];
+    pos[i] = p;
+    if (left) { p += 1; m = k2; } else { p += k2; cc -= k2; m -= k2; }
+  }
+  if (!eq8(h, want) && st == 0) st = 1;                  // (one chunk: its ROOT-flagged output against the root)
+  status[s] = st;
+  // parent steps bottom up: the CV the reference's driver picks by bit g of the index (blake3_hash.rs:63-78)
+  r += (uint64_t)n_blocks * 32;
+  for (uint32_t g = 0; g < P; ++g, r += 32) {
+    const uint32_t *node = ob + 2 + pos[P - 1 - g] * 16;
+    const bool bit_left = ((c >> g) & 1) == 0;
+    plan_parent_step(r, h, bit_left ? node + 8 : node, bit_left, c, n_blocks, P, P - 1 - g);
+  }
+}
+
+uint64_t num_chunks(uint64_t len) { return len ? (len + 1023) / 1024 : 1; }
+uint32_t chunk_blocks(uint64_t len, uint64_t c) {
+  const uint64_t off = c * 1024, bytes = len - off < 1024 ? len - off : 1024;
+  return bytes ? (uint32_t)((bytes + 63) / 64) : 1;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t b3w_bao_outboard_size(uint64_t len) { return 8 + 64 * (num_chunks(len) - 1); }
+
+int32_t b3w_bao_outboard_device(b3w_ctx *ctx, const uint8_t *d_preimage, uint64_t len, uint8_t *d_outboard, uint32_t *d_levels, uint32_t *d_root,
+                                void *stream) {
+  if (!ctx || (!d_preimage && len) || !d_outboard || !d_levels || !d_root) return B3W_E_BAD_ARGUMENT;
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t n = num_chunks(len);
+  // four lanes per chunk up to 64 Ki chunks (latency), one lane per chunk above (throughput); B3W_BAO_QUAD=0 / 1: measurements
+  const char *env = getenv("B3W_BAO_QUAD");
+  const bool quad = env ? atoi(env) != 0 : n <= 65536u;
+  if (quad) hipLaunchKernelGGL(b3w_bao_cv_quad_kernel, dim3((uint32_t)((n + 15) / 16)), dim3(64), 0, st, d_preimage, len, n, d_levels);
+  else hipLaunchKernelGGL(b3w_bao_cv_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, d_preimage, len, n, d_levels);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(ctx, e, "bao chunk CV launch");
+  const int32_t rc = b3w_chain_tree_device(ctx, d_levels, n, d_root, stream);
+  if (rc) return rc;
+  const B3wSpine sp = n > 1 ? spine_of(n) : B3wSpine{};
+  hipLaunchKernelGGL(b3w_bao_emit_kernel, dim3((uint32_t)(n > 1 ? (n - 1 + 255) / 256 : 1)), dim3(256), 0, st, d_levels, n, len, sp, d_outboard);
+  e = hipGetLastError();
+  return e != hipSuccess ? hip_fail(ctx, e, "bao emit launch") : B3W_OK;
+}
+
+int32_t b3w_bao_path_nodes(uint64_t chunk, uint64_t n_chunks, uint64_t *out_index, uint32_t *out_count) {
+  if (!out_index || !out_count || !n_chunks || chunk >= n_chunks) return B3W_E_BAD_ARGUMENT;
+  uint64_t p = 0, c = chunk, m = n_chunks;
+  uint32_t i = 0;
+  while (m > 1) {
+    uint64_t k = 1;
+    while (k * 2 < m) k *= 2;
+    out_index[i++] = p;
+    if (c < k) { p += 1; m = k; } else { p += k; c -= k; m -= k; }
+  }
+  *out_count = i;
+  return B3W_OK;
+}
+
+int32_t b3w_bao_slice(const uint8_t *outboard, uint64_t len, uint64_t chunk, const uint8_t *chunk_bytes, uint8_t *out, uint64_t *out_len) {
+  const uint64_t n = num_chunks(len);
+  if (!outboard || !out_len || chunk >= n) return B3W_E_BAD_ARGUMENT;
+  uint64_t hdr = 0;
+  for (int k = 0; k < 8; ++k) hdr |= (uint64_t)outboard[k] << (8 * k);
+  if (hdr != len) return B3W_E_BAD_ARGUMENT;
+  uint64_t idx[64];
+  uint32_t P = 0;
+  (void)b3w_bao_path_nodes(chunk, n, idx, &P);
+  const uint64_t off = chunk * 1024, bytes = len - off < 1024 ? len - off : 1024;
+  *out_len = 8 + 64ull * P + bytes;
+  if (!out) return B3W_OK;
+  if (bytes && !chunk_bytes) return B3W_E_BAD_ARGUMENT;
+  memcpy(out, outboard, 8);
+  for (uint32_t i = 0; i < P; ++i) memcpy(out + 8 + 64ull * i, outboard + 8 + 64 * idx[i], 64);
+  if (bytes) memcpy(out + 8 + 64ull * P, chunk_bytes, bytes);
+  return B3W_OK;
+}
+
+int64_t b3w_sample_rows(uint64_t len, const uint64_t *host_chunks, uint32_t n_samples, uint64_t *row_first) {
+  if ((!host_chunks && n_samples) || !row_first) return -B3W_E_BAD_ARGUMENT;
+  const uint64_t n = num_chunks(len);
+  for (uint32_t s = 0; s < n_samples; ++s)
+    if (host_chunks[s] >= n) return -B3W_E_BAD_ARGUMENT;
+  uint64_t row = 0;
+  for (uint32_t s = 0; s < n_samples; ++s) {
+    row_first[s] = row;
+    row += chunk_blocks(len, host_chunks[s]) + b3w_plan_path_len(host_chunks[s], n);
+  }
+  row_first[n_samples] = row;
+  return (int64_t)row;
+}
+
+int32_t b3w_sample_plan_device(b3w_ctx *ctx, uint64_t len, const uint8_t *d_outboard, const uint32_t *root, const uint64_t *host_chunks,
+                               uint32_t n_samples, const uint8_t *d_chunk_bytes, uint32_t *d_records, int32_t *d_sample_status, void *stream) {
+  if (!ctx || !d_outboard || !root || (n_samples && (!host_chunks || !d_chunk_bytes || !d_records || !d_sample_status))) return B3W_E_BAD_ARGUMENT;
+  if (ctx->desc.kind == B3W_KIND_COMP) { ctx->last_error = "sampled paths plan the nova step circuits' records"; return B3W_E_BAD_ARGUMENT; }
+  const uint64_t n = num_chunks(len);
+  for (uint32_t s = 0; s < n_samples; ++s)
+    if (host_chunks[s] >= n) { ctx->last_error = "a sampled chunk index is not below the chunk count"; return B3W_E_BAD_ARGUMENT; }
+  if (!n_samples) return B3W_OK;
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  // the per-sample {chunk, first row} table goes through the context's pinned staging buffer; the event of the previous call says
+  // when that call's copy and kernel are done with both buffers
+  if (ctx->samples_done) HIP_TRY(ctx, hipEventSynchronize(ctx->samples_done));
+  else HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->samples_done, hipEventDisableTiming));
+  if (ctx->samples_cap < n_samples) {
+    if (ctx->h_samples) (void)hipHostFree(ctx->h_samples);
+    if (ctx->d_samples) (void)hipFree(ctx->d_samples);
+    ctx->h_samples = nullptr; ctx->d_samples = nullptr; ctx->samples_cap = 0;
+    HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_samples, (size_t)n_samples * 16, hipHostMallocDefault));
+    HIP_TRY(ctx, hipMalloc((void **)&ctx->d_samples, (size_t)n_samples * 16));
+    ctx->samples_cap = n_samples;
+  }
+  uint64_t row = 0;
+  for (uint32_t s = 0; s < n_samples; ++s) {
+    ctx->h_samples[2 * s] = host_chunks[s];
+    ctx->h_samples[2 * s + 1] = row;
+    row += chunk_blocks(len, host_chunks[s]) + b3w_plan_path_len(host_chunks[s], n);
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_samples, ctx->h_samples, (size_t)n_samples * 16, hipMemcpyHostToDevice, st));
+  Root8 r8;
+  for (int k = 0; k < 8; ++k) r8.w[k] = root[k];
+  hipLaunchKernelGGL(b3w_sample_plan_kernel, dim3((n_samples + 63) / 64), dim3(64), 0, st, len, n, reinterpret_cast<const uint32_t *>(d_outboard), r8,
+                     ctx->d_samples, n_samples, d_chunk_bytes, d_records, d_sample_status);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(ctx, e, "sample plan launch");
+  HIP_TRY(ctx, hipEventRecord(ctx->samples_done, st));
+  return B3W_OK;
+}
+
+}  // extern "C"

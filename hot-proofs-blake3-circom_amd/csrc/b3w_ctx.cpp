@@ -303,7 +303,7 @@ int b3w_int_default_variant(const b3w_ctx *ctx, uint32_t n, const uint8_t *d_bod
 
 extern "C" {
 
-uint32_t b3w_abi_version(void) { return (1u << 16) | 0u; }
+uint32_t b3w_abi_version(void) { return (1u << 16) | 1u; }
 
 int32_t b3w_identify_wasm(const uint8_t *code, size_t len) {
   if (!code) return B3W_CIRCUIT_UNKNOWN;
@@ -482,6 +482,9 @@ void b3w_destroy(b3w_ctx *ctx) {
   if (ctx->d_rec1) (void)hipFree(ctx->d_rec1);
   if (ctx->d_body1) (void)hipFree(ctx->d_body1);
   if (ctx->d_status1) (void)hipFree(ctx->d_status1);
+  if (ctx->samples_done) { (void)hipEventSynchronize(ctx->samples_done); (void)hipEventDestroy(ctx->samples_done); }
+  if (ctx->h_samples) (void)hipHostFree(ctx->h_samples);
+  if (ctx->d_samples) (void)hipFree(ctx->d_samples);
   delete ctx;
 }
 

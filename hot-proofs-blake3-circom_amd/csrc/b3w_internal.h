@@ -71,6 +71,11 @@ struct b3w_ctx {
   struct Spare { void *ptr; uint64_t bytes; int32_t placement; };
   std::vector<Spare> ring_spares;     // ring buffers of destroyed chains, reused by the next b3w_chain_create of the same size;
                                       // one size at a time, at most RING_SPARE_CAP bytes, released by b3w_ctx_trim (b3wit.h)
+  // b3w_sample_plan_device: the per-sample {chunk, first row} table, pinned on the host and on the device; samples_done = the last
+  // call's copy and kernel are through with both
+  uint64_t *h_samples = nullptr, *d_samples = nullptr;
+  uint32_t samples_cap = 0;
+  hipEvent_t samples_done = nullptr;
   std::string last_error;
 };
 

@@ -550,6 +550,44 @@ int32_t *b3w_chain_status(b3w_chain *chain);       /* device: (n_leaf + n_parent
 uint32_t *b3w_chain_local_cvs(b3w_chain *chain);   /* device: n_chunks_local * 8 u32 */
 uint32_t *b3w_chain_root(b3w_chain *chain);        /* device: 8 u32 = BLAKE3(preimage) words, after run_parents */
 
+/* ---- bao outboards and challenged chunk paths (ABI 1.1) -------------------------------------------------
+ * A data-availability challenge names a few chunk indices; the provider answers from the file and its bao OUTBOARD
+ * (bao 0.12, 1 KiB chunks, as rust_fold/src/blake3_hash.rs:17-93 consumes it):
+ *   outboard = 8-byte little-endian content length, then the n_chunks - 1 parent nodes of BLAKE3's tree in pre-order,
+ *              64 bytes each (left child CV, right child CV: 8 little-endian words each); at most one chunk: the header alone.
+ *   pre-order: the root is node 0; a node at position p over m chunks (k = the largest power of two below m) has its left
+ *              subtree from p + 1 and its right subtree from p + k.
+ *   slice of chunk c = the header, the nodes of c's path root first, the chunk's bytes [c*1024, min(len, c*1024 + 1024)).
+ * b3w_bao_outboard_device: the outboard and the 8 root words (= BLAKE3(preimage)) of a preimage in device memory.  d_outboard:
+ * b3w_bao_outboard_size(len) bytes, 8-byte aligned; d_levels: caller's scratch of (2 n_chunks + 64) * 8 u32 (b3w_chain_tree_device's
+ * format; it holds the tree's level arrays afterwards); d_root: 8 u32.  No allocation. */
+uint64_t b3w_bao_outboard_size(uint64_t preimage_len);                /* 8 + 64 * (n_chunks - 1) */
+int32_t b3w_bao_outboard_device(b3w_ctx *ctx, const uint8_t *d_preimage, uint64_t preimage_len, uint8_t *d_outboard,
+                                uint32_t *d_levels, uint32_t *d_root, void *stream);
+/* Host only.  The pre-order indices of chunk's path nodes, root first (b3w_chain_path_len of them, at most 64): the nodes a
+ * provider reads from an outboard on disk (node i lies at byte 8 + 64 i). */
+int32_t b3w_bao_path_nodes(uint64_t chunk, uint64_t n_chunks, uint64_t *out_index, uint32_t *out_count);
+/* Host only.  The bao slice of one chunk: *out_len = 8 + 64 * path_len + the chunk's byte count, and with out != NULL the bytes.
+ * outboard: the whole outboard of a preimage of preimage_len bytes (its header must say so); chunk_bytes: the chunk's bytes. */
+int32_t b3w_bao_slice(const uint8_t *outboard, uint64_t preimage_len, uint64_t chunk, const uint8_t *chunk_bytes, uint8_t *out,
+                      uint64_t *out_len);
+/* Rows of the step records of sampled chunk paths, sample-major: sample s owns rows [row_first[s], row_first[s + 1]) — its
+ * leaf blocks, then its parent steps bottom up (the order a fold of that one path consumes them).  row_first: n_samples + 1
+ * entries.  Returns the total row count, or -B3W_E_BAD_ARGUMENT (an index >= n_chunks; duplicates are fine). */
+int64_t b3w_sample_rows(uint64_t preimage_len, const uint64_t *host_chunks, uint32_t n_samples, uint64_t *row_first);
+/* The step records of the sampled chunk paths (rows as b3w_sample_rows says; 32 u32 each), from the outboard and the sampled
+ * chunks' bytes alone (d_chunk_bytes: 1024 bytes per sample, bytes past the preimage's end ignored): word for word the records
+ * b3w_chain_plan_leaves_device / b3w_chain_plan_parents_device write for those chunks, sibling-by-index-bit rule included.
+ * Every path is verified top down as bao's decoder does (root node against `root` with the ROOT flag, each lower node against its
+ * half of the node above, the chunk's CV against its half of the lowest node; one chunk: its ROOT-flagged output against `root`).
+ * d_sample_status[s]: 0 verified, 1 the chunk's bytes do not match, 2 a path node or the root does not match, 3 the outboard's
+ * header is not preimage_len.  Records are written for failing samples too; a sample never affects another.  Nova contexts
+ * only.  The witnesses, commitments and constraint checks of the records are the batch calls' (b3w_batch_run_device,
+ * b3w_commit_records_device, b3w_r1cs_check_device).  Asynchronous on `stream`; waits for this context's previous call. */
+int32_t b3w_sample_plan_device(b3w_ctx *ctx, uint64_t preimage_len, const uint8_t *d_outboard, const uint32_t *root /* host, 8 u32 */,
+                               const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_chunk_bytes, uint32_t *d_records,
+                               int32_t *d_sample_status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
