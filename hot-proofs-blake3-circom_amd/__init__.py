@@ -171,6 +171,11 @@ def lib():
         "b3w_bao_slice": (i32, [vp, u64, u64, vp, vp, ctypes.POINTER(u64)]),
         "b3w_sample_rows": (ctypes.c_int64, [u64, vp, u32, vp]),
         "b3w_sample_plan_device": (i32, [vp, u64, vp, vp, vp, u32, vp, vp, vp, vp]),
+        "b3w_bao_batch_layout": (u64, [vp, u32, vp]),
+        "b3w_bao_batch_scratch_bytes": (u64, [vp, u32]),
+        "b3w_bao_outboard_batch_device": (i32, [vp, vp, vp, vp, u32, vp, vp, vp, u64, vp]),
+        "b3w_sample_rows_batch": (ctypes.c_int64, [vp, u32, vp, vp, u32, vp]),
+        "b3w_sample_plan_batch_device": (i32, [vp, vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -192,7 +197,8 @@ EXPORTED_SYMBOLS = ("b3w_abi_version", "b3w_identify_wasm", "b3w_create", "b3w_d
                     "b3w_chain_create", "b3w_chain_destroy", "b3w_chain_run_leaves", "b3w_chain_run_parents", "b3w_chain_shard", "b3w_chain_run_parents_sharded", "b3w_chain_allgather_hout", "b3w_chain_allgather_hout_host", "b3w_chain_exchange_ms", "b3w_chain_info",
                     "b3w_chain_outputs", "b3w_chain_records", "b3w_chain_public", "b3w_chain_status", "b3w_chain_local_cvs", "b3w_chain_root",
                     "b3w_bao_outboard_size", "b3w_bao_outboard_device", "b3w_bao_path_nodes", "b3w_bao_slice", "b3w_sample_rows",
-                    "b3w_sample_plan_device")
+                    "b3w_sample_plan_device", "b3w_bao_batch_layout", "b3w_bao_batch_scratch_bytes", "b3w_bao_outboard_batch_device",
+                    "b3w_sample_rows_batch", "b3w_sample_plan_batch_device")
 
 
 class graph_capture:

@@ -3,7 +3,8 @@
 A data-availability challenge names a few chunk indices; the provider answers from the file and its bao outboard (the tree's
 parent nodes, kept beside the file).  outboard() makes the outboard of a preimage in device memory; plan_samples() plans the step
 records of the challenged chunk paths from the outboard and those chunks' bytes alone, verifying each path against the root;
-prove_samples() runs their witnesses, constraint checks and commitments through the batch calls, batch by batch.  The records are
+prove_samples() runs their witnesses, constraint checks and commitments through the batch calls, batch by batch.  outboard_batch(),
+plan_samples_batch() and prove_samples_batch() do the same for a whole batch of files of one device arena at once.  The records are
 word for word those the chain planner writes for the same chunks (ChainPlanner.plan), so every step is the reference's
 prove_chunk_hash step (rust_fold/src/main.rs:41-203 over hash_with_path's slice, rust_fold/src/blake3_hash.rs:17-93)."""
 import ctypes
@@ -126,6 +127,11 @@ def prove_samples(ctx, d_outboard, length, root, chunks, d_chunk_bytes, batch_st
     None) and points (uint8 CUDA [rows, 64] or None)."""
     s = _stream(stream)
     out = plan_samples(ctx, d_outboard, length, root, chunks, d_chunk_bytes, stream=s)
+    return _prove_planned(ctx, out, batch_steps, consumer, commit_key, r1cs, s)
+
+
+def _prove_planned(ctx, out, batch_steps, consumer, commit_key, r1cs, s):
+    """the batch loop of prove_samples / prove_samples_batch over a plan's records; adds public, status, violations, points to `out`"""
     recs = out["records"]
     rows = recs.shape[0]
     dev = recs.device
@@ -157,3 +163,101 @@ def prove_samples(ctx, d_outboard, length, root, chunks, d_chunk_bytes, batch_st
             buf.free()
     out.update(public=pub, status=status, violations=viol, points=points)
     return out
+
+
+# ---- a batch of files --------------------------------------------------------------------------------------------------
+def _u64(a):
+    return np.ascontiguousarray(a, dtype=np.uint64)
+
+
+def batch_layout(lens):
+    """-> ob_first (numpy uint64 [n_files + 1]): file f's outboard is bytes [ob_first[f], ob_first[f + 1]) of the packed outboards"""
+    ln = _u64(lens)
+    ob_first = np.zeros(ln.size + 1, dtype=np.uint64)
+    lib().b3w_bao_batch_layout(ln.ctypes.data, ln.size, ob_first.ctypes.data)
+    return ob_first
+
+
+def outboard_batch(ctx, d_arena, offsets, lens, stream=0):
+    """The outboards and roots of every file of a batch in a number of launches that does not depend on the file count: file f is
+    bytes [offsets[f], offsets[f] + lens[f]) of d_arena (a uint8 CUDA tensor; any offsets).  Returns a dict: outboards (uint8 CUDA
+    tensor, packed in file order), ob_first (numpy uint64 [n_files + 1]), roots (int32 CUDA tensor [n_files, 8], left on the device:
+    plan_samples_batch takes them there)."""
+    L = lib()
+    off, ln = _u64(offsets), _u64(lens)
+    assert off.size == ln.size
+    assert d_arena.is_cuda and d_arena.dtype == torch.uint8 and d_arena.is_contiguous()
+    if ln.size and int((off + ln).max()) > d_arena.numel():
+        raise B3WError(100, "outboard_batch: a file reaches past the end of the arena")
+    dev = d_arena.device
+    ob_first = batch_layout(ln)
+    obs = torch.empty(int(ob_first[-1]), dtype=torch.uint8, device=dev)
+    roots = torch.empty((ln.size, 8), dtype=torch.int32, device=dev)
+    need = L.b3w_bao_batch_scratch_bytes(ln.ctypes.data, ln.size)
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    _chk(ctx, L.b3w_bao_outboard_batch_device(ctx.handle, d_arena.data_ptr() if d_arena.numel() else None, off.ctypes.data, ln.ctypes.data, ln.size,
+                                              obs.data_ptr(), roots.data_ptr(), scratch.data_ptr() if need else None, need, _stream(stream)),
+         "b3w_bao_outboard_batch_device")
+    return dict(outboards=obs, ob_first=ob_first, roots=roots)
+
+
+def chunk_bytes_batch(arena, offsets, lens, files, chunks, device="cuda"):
+    """the sampled chunks' bytes as plan_samples_batch takes them (uint8 [n_samples, 1024], zero past a file's end); sample s is chunk
+    chunks[s] of file files[s].  arena: host bytes / numpy, or a CUDA tensor."""
+    off, ln = _u64(offsets).astype(np.int64), _u64(lens).astype(np.int64)
+    fi, ch = np.asarray(files, dtype=np.int64), np.asarray(chunks, dtype=np.int64)
+    start = off[fi] + ch * 1024
+    count = np.clip(ln[fi] - ch * 1024, 0, 1024)
+    if isinstance(arena, torch.Tensor):
+        dev = arena.device
+        col = torch.arange(1024, device=dev)
+        idx = torch.from_numpy(start).to(dev)[:, None] + col[None, :]
+        live = col[None, :] < torch.from_numpy(count).to(dev)[:, None]
+        if arena.numel() == 0:
+            return torch.zeros((fi.size, 1024), dtype=torch.uint8, device=dev)
+        got = arena[idx.clamp_(max=arena.numel() - 1)]
+        return torch.where(live, got, torch.zeros((), dtype=torch.uint8, device=dev)).contiguous()
+    data = np.frombuffer(bytes(arena), dtype=np.uint8) if not isinstance(arena, np.ndarray) else arena
+    out = np.zeros((fi.size, 1024), dtype=np.uint8)
+    for s in range(fi.size):
+        out[s, :count[s]] = data[start[s]:start[s] + count[s]]
+    return torch.from_numpy(out).to(device)
+
+
+def sample_rows_batch(lens, files, chunks):
+    """-> row_first (numpy uint64 [n_samples + 1]) of samples (files[s], chunks[s]), sample-major as sample_rows"""
+    ln, ch = _u64(lens), _u64(chunks)
+    fi = np.ascontiguousarray(files, dtype=np.uint32)
+    assert fi.size == ch.size
+    rf = np.zeros(ch.size + 1, dtype=np.uint64)
+    total = lib().b3w_sample_rows_batch(ln.ctypes.data, ln.size, fi.ctypes.data, ch.ctypes.data, ch.size, rf.ctypes.data)
+    if total < 0:
+        raise B3WError(-total, "b3w_sample_rows_batch: a file index is not below the file count, or a chunk index not below its file's chunk count")
+    return rf
+
+
+def plan_samples_batch(ctx, d_outboards, lens, d_roots, files, chunks, d_chunk_bytes, stream=0):
+    """plan_samples over a batch: sample s is chunk chunks[s] of file files[s]; d_outboards and d_roots as outboard_batch returns them
+    (the roots stay on the device).  Returns the dict plan_samples returns, `provable` from each sample's own file."""
+    L = lib()
+    ln, ch = _u64(lens), _u64(chunks)
+    fi = np.ascontiguousarray(files, dtype=np.uint32)
+    rf = sample_rows_batch(ln, fi, ch)
+    dev = d_outboards.device
+    assert d_roots.is_cuda and d_roots.is_contiguous() and d_roots.numel() >= ln.size * 8
+    assert d_chunk_bytes.is_cuda and d_chunk_bytes.dtype == torch.uint8 and d_chunk_bytes.numel() >= ch.size * 1024
+    recs = torch.empty((int(rf[-1]), 32), dtype=torch.int32, device=dev)
+    st = torch.full((ch.size,), -1, dtype=torch.int32, device=dev)
+    _chk(ctx, L.b3w_sample_plan_batch_device(ctx.handle, ln.ctypes.data, ln.size, d_outboards.data_ptr(), d_roots.data_ptr(), fi.ctypes.data,
+                                             ch.ctypes.data, ch.size, d_chunk_bytes.data_ptr(), recs.data_ptr(), st.data_ptr(), _stream(stream)),
+         "b3w_sample_plan_batch_device")
+    provable = np.array([bool(L.b3w_chain_path_provable(int(c), num_chunks(int(ln[f])))) for f, c in zip(fi, ch)], dtype=bool)
+    return dict(records=recs, row_first=rf, sample_status=st.cpu().numpy(), provable=provable)
+
+
+def prove_samples_batch(ctx, d_outboards, lens, d_roots, files, chunks, d_chunk_bytes, batch_steps=4096, consumer=None, commit_key=None,
+                        r1cs=None, stream=0):
+    """prove_samples over a batch of files: plan_samples_batch, then the same witness / constraint / commitment batches over its rows"""
+    s = _stream(stream)
+    out = plan_samples_batch(ctx, d_outboards, lens, d_roots, files, chunks, d_chunk_bytes, stream=s)
+    return _prove_planned(ctx, out, batch_steps, consumer, commit_key, r1cs, s)

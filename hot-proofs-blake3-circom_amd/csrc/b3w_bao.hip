@@ -13,6 +13,8 @@
 //   b3w_bao_cv_quad_kernel   four lanes per chunk (the leaf planner's quad compression): small chunk counts, where latency counts
 //   (the tree)               b3w_chain_tree_device: the chain's own level arrays, spine and root
 //   b3w_bao_emit_kernel      one thread per parent node: its two child CVs from the level arrays to its pre-order position
+//   b3w_bao_tile_kernel      a batch of files: one workgroup per tile of 1 024 chunks, chunk CVs and the tile's tree in LDS, nodes straight to
+//   b3w_bao_merge_kernel     their pre-order places; the tree over the tile CVs, one workgroup per 1 024 of them (see "batches of files")
 //   b3w_sample_plan_kernel   one thread per challenged chunk: its leaf records from its bytes, its path verified top down against the
 //                            root the way bao's decoder does, its parent records bottom up with the outboard's CVs
 #include "b3w_internal.h"
@@ -86,16 +88,11 @@ __device__ __forceinline__ void plan_parent_step(uint32_t *r, uint32_t h[8], con
 }
 
 // ---- chunk chaining values -----------------------------------------------------------------------------------------
-// lane = chunk.  Neighbouring lanes' blocks lie 1 KiB apart, so every load is a whole 16-byte quarter of a block and the next block's
-// four loads are in flight while the current block is compressed.  n == 1: the chunk's output carries ROOT (the hash itself).
-__global__ __launch_bounds__(256) void b3w_bao_cv_kernel(const uint8_t *__restrict__ pre, uint64_t len, uint64_t n, uint32_t *__restrict__ cv) {
-  const uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (c >= n) return;
-  const uint64_t off = c * 1024;
-  const uint32_t bytes = (uint32_t)(len - off < 1024 ? len - off : 1024);
-  const uint32_t root = n == 1 ? 8u : 0u;
-  const uint8_t *src = pre + off;
-  uint32_t h[8], o[8], m[16];
+// the CV of chunk c (`bytes` bytes from src; root: 8 where the chunk is the whole input, its output then carries ROOT: the hash itself).
+// Where the chunk is whole and starts 16-byte aligned every load is a whole 16-byte quarter of a block and the next block's four loads are
+// in flight while the current block is compressed.
+__device__ __forceinline__ void chunk_cv(const uint8_t *__restrict__ src, uint32_t bytes, uint64_t c, uint32_t root, uint32_t h[8]) {
+  uint32_t o[8], m[16];
   iv(h);
   if (bytes == 1024 && ((uintptr_t)src & 15) == 0) {
     const uint4 *p = reinterpret_cast<const uint4 *>(src);
@@ -109,7 +106,7 @@ __global__ __launch_bounds__(256) void b3w_bao_cv_kernel(const uint8_t *__restri
 #pragma unroll
       for (int k = 0; k < 8; ++k) h[k] = o[k];
     }
-  } else {                                               // the last chunk of a length that is no multiple of 1 KiB, or an unaligned preimage
+  } else {                                               // a ragged last chunk, or a file that starts off a 16-byte boundary
     const uint32_t nb = bytes ? (bytes + 63) / 64 : 1;
     for (uint32_t j = 0; j < nb; ++j) {
       const uint32_t bb = bytes - j * 64 < 64 ? bytes - j * 64 : 64;
@@ -125,6 +122,15 @@ __global__ __launch_bounds__(256) void b3w_bao_cv_kernel(const uint8_t *__restri
       for (int k = 0; k < 8; ++k) h[k] = o[k];
     }
   }
+}
+
+// lane = chunk (neighbouring lanes' blocks lie 1 KiB apart)
+__global__ __launch_bounds__(256) void b3w_bao_cv_kernel(const uint8_t *__restrict__ pre, uint64_t len, uint64_t n, uint32_t *__restrict__ cv) {
+  const uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= n) return;
+  const uint64_t off = c * 1024;
+  uint32_t h[8];
+  chunk_cv(pre + off, (uint32_t)(len - off < 1024 ? len - off : 1024), c, n == 1 ? 8u : 0u, h);
   uint4 *dst = reinterpret_cast<uint4 *>(cv + c * 8);
   dst[0] = make_uint4(h[0], h[1], h[2], h[3]);
   dst[1] = make_uint4(h[4], h[5], h[6], h[7]);
@@ -207,6 +213,154 @@ __global__ __launch_bounds__(256) void b3w_bao_emit_kernel(const uint32_t *__res
   dst[4] = make_uint2(r0.x, r0.y); dst[5] = make_uint2(r0.z, r0.w); dst[6] = make_uint2(r1.x, r1.y); dst[7] = make_uint2(r1.z, r1.w);
 }
 
+// ---- batches of files: tiles ------------------------------------------------------------------------------------------
+// A tile = up to B3W_TILE consecutive chunks of one file from a multiple of B3W_TILE.  Every tile is a subtree of the file's tree (the left
+// subtree of a node over m > B3W_TILE chunks holds a power of two >= B3W_TILE of them), and the tree above the tiles is BLAKE3's tree shape over
+// the tile CVs.  The same holds one storey up for groups of 1 024 tiles.  So:
+//   b3w_bao_tile_kernel       one workgroup per tile, lane = chunk: the chunk CVs into LDS, merged level by level in LDS, every parent
+//                             node straight to its pre-order place in the file's outboard; one CV per tile to `tile_cv`, or the root and
+//                             the header for a one-tile file.  Files of more than 64 chunks.
+//   b3w_bao_small_kernel      the files of at most 64 chunks, packed several to a wave
+//   b3w_bao_merge_kernel      one workgroup per group of up to 1 024 items (tile CVs; for files past 1 GiB a second launch over the groups'
+//                             CVs): the same merge over them, ROOT on a file's top merge.
+// Merging in place: the CV of the item that starts at slot i stays in slot i, so level l pairs slot (2 j) << l with slot ((2 j) << l) +
+// (1 << l) where that one exists, and an odd item out simply waits — which is BLAKE3's tree (tests/test_bao_batch_cpu.py restates it).
+constexpr uint32_t B3W_TILE = 1024;                      // chunks per tile = items per merge group
+struct BatchEnt { uint64_t off, len, ob; uint32_t first, file; };   // tile launches: arena offset; merge launches: first input CV slot
+
+// pre-order position, relative to the root of a tree over `total` chunks, of its node over chunks [a, a + size)
+__device__ __forceinline__ uint64_t preorder_pos(uint64_t total, uint64_t a, uint64_t size) {
+  uint64_t p = 0, lo = 0, cnt = total;
+  while (cnt > 1 && !(lo == a && cnt == size)) {
+    const uint64_t k = 1ull << (63 - __clzll((long long)(cnt - 1)));
+    if (a < lo + k) { p += 1; cnt = k; } else { p += k; lo += k; cnt -= k; }
+  }
+  return p;
+}
+
+// the entry whose workgroups include wg: the last one with first <= wg
+__device__ __forceinline__ BatchEnt batch_ent(const BatchEnt *__restrict__ ents, uint32_t n_ents, uint32_t wg) {
+  uint32_t lo = 0, hi = n_ents;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (ents[mid].first <= wg) lo = mid; else hi = mid;
+  }
+  return ents[lo];
+}
+
+// one parent: the CVs in slots i0 (left) and i1 (right) of cv to the node at dst, their parent's CV to slot i0 (d = PARENT [| ROOT])
+__device__ __forceinline__ void merge_pair(uint32_t *cv, uint32_t i0, uint32_t i1, uint8_t *__restrict__ node, uint32_t d) {
+  uint32_t m[16], ivv[8], o[8];
+  const uint4 l0 = reinterpret_cast<const uint4 *>(cv + i0 * 8)[0], l1 = reinterpret_cast<const uint4 *>(cv + i0 * 8)[1];
+  const uint4 r0 = reinterpret_cast<const uint4 *>(cv + i1 * 8)[0], r1 = reinterpret_cast<const uint4 *>(cv + i1 * 8)[1];
+  uint2 *dst = reinterpret_cast<uint2 *>(node);                      // (8 off a 16-byte boundary)
+  dst[0] = make_uint2(l0.x, l0.y); dst[1] = make_uint2(l0.z, l0.w); dst[2] = make_uint2(l1.x, l1.y); dst[3] = make_uint2(l1.z, l1.w);
+  dst[4] = make_uint2(r0.x, r0.y); dst[5] = make_uint2(r0.z, r0.w); dst[6] = make_uint2(r1.x, r1.y); dst[7] = make_uint2(r1.z, r1.w);
+  m[0] = l0.x; m[1] = l0.y; m[2] = l0.z; m[3] = l0.w; m[4] = l1.x; m[5] = l1.y; m[6] = l1.z; m[7] = l1.w;
+  m[8] = r0.x; m[9] = r0.y; m[10] = r0.z; m[11] = r0.w; m[12] = r1.x; m[13] = r1.y; m[14] = r1.z; m[15] = r1.w;
+  iv(ivv);
+  blake3_cv(ivv, m, 0, 0, 64, d, o);
+  reinterpret_cast<uint4 *>(cv + i0 * 8)[0] = make_uint4(o[0], o[1], o[2], o[3]);          // (slot i0 is read by this thread alone at this level)
+  reinterpret_cast<uint4 *>(cv + i0 * 8)[1] = make_uint4(o[4], o[5], o[6], o[7]);
+}
+
+// cv: cnt items of `unit` chunks each (the last one maybe fewer) of a tree over `total` chunks whose nodes go to `nodes` (its root's place).
+// Leaves the tree's CV in cv[0 .. 8) (ROOT-flagged where `root` says so); ends with a barrier.
+template <int BS>
+__device__ __forceinline__ void merge_in_lds(uint32_t *cv, uint32_t cnt, uint64_t unit, uint64_t total, uint8_t *__restrict__ nodes, bool root) {
+  for (uint32_t l = 0; (1u << l) < cnt; ++l) {
+    __syncthreads();
+    const bool top = (2u << l) >= cnt;
+    for (uint32_t j = threadIdx.x;; j += BS) {
+      const uint32_t i0 = (2 * j) << l, i1 = i0 + (1u << l);
+      if (i1 >= cnt) break;
+      const uint64_t a = i0 * unit, e = (uint64_t)(i0 + (2u << l)) * unit;
+      merge_pair(cv, i0, i1, nodes + preorder_pos(total, a, (e < total ? e : total) - a) * 64, 4u | (top && root ? 8u : 0u));
+    }
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_tile_kernel(const uint8_t *__restrict__ arena, const BatchEnt *__restrict__ ents, uint32_t n_ents,
+                                                                uint8_t *__restrict__ outboards, uint32_t *__restrict__ roots,
+                                                                uint32_t *__restrict__ tile_cv) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
+  const BatchEnt e = batch_ent(ents, n_ents, blockIdx.x);
+  const uint64_t n = (e.len + 1023) / 1024;                           // (more than 64 chunks)
+  const uint64_t a0 = (uint64_t)(blockIdx.x - e.first) * B3W_TILE;
+  const uint32_t m = (uint32_t)(n - a0 < B3W_TILE ? n - a0 : B3W_TILE);
+  const bool sole = n <= B3W_TILE;
+  if (threadIdx.x < m) {
+    const uint64_t c = a0 + threadIdx.x, off = c * 1024;
+    uint32_t h[8];
+    chunk_cv(arena + e.off + off, (uint32_t)(e.len - off < 1024 ? e.len - off : 1024), c, 0, h);
+    reinterpret_cast<uint4 *>(cv + threadIdx.x * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
+    reinterpret_cast<uint4 *>(cv + threadIdx.x * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
+  }
+  uint8_t *ob = outboards + e.ob;
+  if (a0 == 0 && threadIdx.x == 0) *reinterpret_cast<uint2 *>(ob) = make_uint2((uint32_t)e.len, (uint32_t)(e.len >> 32));
+  merge_in_lds<B3W_TILE>(cv, m, 1, m, ob + 8 + preorder_pos(n, a0, m) * 64, sole);
+  if (threadIdx.x < 8) (sole ? roots + (uint64_t)e.file * 8 : tile_cv + (uint64_t)blockIdx.x * 8)[threadIdx.x] = cv[threadIdx.x];
+}
+
+// Files of at most 64 chunks, several to a wave: wave w takes the files [wave_first[w], wave_first[w + 1]) of `ents`, which have at most 64
+// chunks together; ents[f].first = the lane of file f's chunk 0.  lane = chunk, every lane busy where the files fill the wave (a wave a
+// file would leave 60 of 64 lanes idle on 4 KiB files, and idle lanes cost the same issue cycles).  The same in-place merge, each file
+// in its own run of slots: at level l the lane of a chunk index that is a multiple of 2 << l merges with the slot 1 << l further on.
+__global__ __launch_bounds__(64) void b3w_bao_small_kernel(const uint8_t *__restrict__ arena, const BatchEnt *__restrict__ ents,
+                                                           const uint32_t *__restrict__ wave_first, uint8_t *__restrict__ outboards,
+                                                           uint32_t *__restrict__ roots) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[64 * 8];
+  const uint32_t lane = threadIdx.x;
+  uint32_t lo = wave_first[blockIdx.x], hi = wave_first[blockIdx.x + 1];
+  while (hi - lo > 1) {                                               // this lane's file: the last one that starts at or before the lane
+    const uint32_t mid = (lo + hi) / 2;
+    if (ents[mid].first <= lane) lo = mid; else hi = mid;
+  }
+  const BatchEnt e = ents[lo];
+  const uint32_t n = e.len ? (uint32_t)((e.len + 1023) / 1024) : 1, i = lane - e.first;
+  const bool live = i < n;                                            // (the lanes behind the last file's chunks are not)
+  if (live) {
+    const uint32_t off = i * 1024;
+    uint32_t h[8];
+    chunk_cv(arena + e.off + off, (uint32_t)(e.len - off < 1024 ? e.len - off : 1024), i, n == 1 ? 8u : 0u, h);
+    reinterpret_cast<uint4 *>(cv + lane * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
+    reinterpret_cast<uint4 *>(cv + lane * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
+  }
+  uint8_t *ob = outboards + e.ob;
+  if (live && i == 0) *reinterpret_cast<uint2 *>(ob) = make_uint2((uint32_t)e.len, (uint32_t)(e.len >> 32));
+  for (uint32_t l = 0; l < 6; ++l) {
+    __syncthreads();
+    if (!__any(live && (1u << l) < n)) break;                         // (uniform: the workgroup is this one wave)
+    if (live && (i & ((2u << l) - 1)) == 0 && i + (1u << l) < n) {
+      const uint32_t size = n - i < (2u << l) ? n - i : (2u << l);
+      merge_pair(cv, lane, lane + (1u << l), ob + 8 + preorder_pos(n, i, size) * 64, 4u | (i == 0 && (2u << l) >= n ? 8u : 0u));
+    }
+  }
+  __syncthreads();
+  if (live && i == 0) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) roots[(uint64_t)e.file * 8 + k] = cv[lane * 8 + k];
+  }
+}
+
+// unit = chunks per input item (B3W_TILE, or B3W_TILE^2 for the launch over the groups' CVs); input item i of the file: in_cv slot e.off + i
+__global__ __launch_bounds__(256) void b3w_bao_merge_kernel(const BatchEnt *__restrict__ ents, uint32_t n_ents, uint64_t unit,
+                                                            const uint32_t *__restrict__ in_cv, uint32_t *__restrict__ out_cv,
+                                                            uint8_t *__restrict__ outboards, uint32_t *__restrict__ roots) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
+  const BatchEnt e = batch_ent(ents, n_ents, blockIdx.x);
+  const uint64_t n = (e.len + 1023) / 1024;                           // (more than one tile)
+  const uint64_t g = blockIdx.x - e.first, span = unit * B3W_TILE, a0 = g * span;
+  const uint64_t tot = n - a0 < span ? n - a0 : span;
+  const uint32_t cnt = (uint32_t)((tot + unit - 1) / unit);
+  const bool sole = n <= span;
+  const uint4 *src = reinterpret_cast<const uint4 *>(in_cv + (e.off + g * B3W_TILE) * 8);
+  for (uint32_t i = threadIdx.x; i < cnt * 2; i += 256) reinterpret_cast<uint4 *>(cv)[i] = src[i];
+  merge_in_lds<256>(cv, cnt, unit, tot, outboards + e.ob + 8 + preorder_pos(n, a0, tot) * 64, sole);
+  if (threadIdx.x < 8) (sole ? roots + (uint64_t)e.file * 8 : out_cv + (uint64_t)blockIdx.x * 8)[threadIdx.x] = cv[threadIdx.x];
+}
+
 // ---- challenged paths ------------------------------------------------------------------------------------------------
 struct Root8 { uint32_t w[8]; };
 
@@ -217,28 +371,24 @@ __device__ __forceinline__ bool eq8(const uint32_t *a, const uint32_t *b) {
   return x == 0;
 }
 
-// desc[2 s] = chunk, desc[2 s + 1] = first row of sample s.  status: 0 verified, 1 chunk bytes, 2 a path node or the root, 3 header.
-__global__ __launch_bounds__(64) void b3w_sample_plan_kernel(uint64_t len, uint64_t n, const uint32_t *__restrict__ ob, Root8 root,
-                                                             const uint64_t *__restrict__ desc, uint32_t n_samples,
-                                                             const uint8_t *__restrict__ chunk_bytes, uint32_t *__restrict__ recs,
-                                                             int32_t *__restrict__ status) {
-  const uint32_t s = blockIdx.x * 64 + threadIdx.x;
-  if (s >= n_samples) return;
-  const uint64_t c = desc[2 * s], row = desc[2 * s + 1];
+// One challenged chunk: chunk c of a file of len bytes (n chunks) whose outboard starts at ob and whose root words are root8; its records
+// from row `row` on.  Returns the status: 0 verified, 1 chunk bytes, 2 a path node or the root, 3 header.
+__device__ __forceinline__ int32_t sample_plan_one(uint64_t len, uint64_t n, const uint32_t *__restrict__ ob, const uint32_t *root8, uint64_t c,
+                                                   uint64_t row, const uint8_t *__restrict__ cb, uint32_t *__restrict__ recs) {
   const uint32_t P = path_len(c, n);
   const uint64_t off = c * 1024;
   const uint32_t bytes = (uint32_t)(len - off < 1024 ? len - off : 1024);
   const uint32_t n_blocks = bytes ? (bytes + 63) / 64 : 1;
   uint32_t *r = recs + row * 32;
   uint32_t h[8];
-  plan_leaf_chunk(chunk_bytes + (uint64_t)s * 1024, bytes, c, P, r, h);
+  plan_leaf_chunk(cb, bytes, c, P, r, h);
   int32_t st = ((uint64_t)ob[0] | ((uint64_t)ob[1] << 32)) != len ? 3 : 0;
   // top down, as bao's decoder: the root node against the root, every lower node against its half of the node above, the chunk
   // against its half of the lowest node
   uint64_t pos[64];
   uint32_t want[8];
 #pragma unroll
-  for (int k = 0; k < 8; ++k) want[k] = root.w[k];
+  for (int k = 0; k < 8; ++k) want[k] = root8[k];
   uint64_t p = 0, cc = c, m = n;
   for (uint32_t i = 0; i < P; ++i) {
     const uint32_t *node = ob + 2 + p * 16;
@@ -257,7 +407,6 @@ __global__ __launch_bounds__(64) void b3w_sample_plan_kernel(uint64_t len, uint6
     if (left) { p += 1; m = k2; } else { p += k2; cc -= k2; m -= k2; }
   }
   if (!eq8(h, want) && st == 0) st = 1;                  // (one chunk: its ROOT-flagged output against the root)
-  status[s] = st;
   // parent steps bottom up: the CV the reference's driver picks by bit g of the index (blake3_hash.rs:63-78)
   r += (uint64_t)n_blocks * 32;
   for (uint32_t g = 0; g < P; ++g, r += 32) {
@@ -265,12 +414,79 @@ __global__ __launch_bounds__(64) void b3w_sample_plan_kernel(uint64_t len, uint6
     const bool bit_left = ((c >> g) & 1) == 0;
     plan_parent_step(r, h, bit_left ? node + 8 : node, bit_left, c, n_blocks, P, P - 1 - g);
   }
+  return st;
+}
+
+// desc[2 s] = chunk, desc[2 s + 1] = first row of sample s.  status: 0 verified, 1 chunk bytes, 2 a path node or the root, 3 header.
+__global__ __launch_bounds__(64) void b3w_sample_plan_kernel(uint64_t len, uint64_t n, const uint32_t *__restrict__ ob, Root8 root,
+                                                             const uint64_t *__restrict__ desc, uint32_t n_samples,
+                                                             const uint8_t *__restrict__ chunk_bytes, uint32_t *__restrict__ recs,
+                                                             int32_t *__restrict__ status) {
+  const uint32_t s = blockIdx.x * 64 + threadIdx.x;
+  if (s >= n_samples) return;
+  status[s] = sample_plan_one(len, n, ob, root.w, desc[2 * s], desc[2 * s + 1], chunk_bytes + (uint64_t)s * 1024, recs);
+}
+
+// the same over a batch of files: desc[5 s ..] = chunk, first row, the file's length, the byte offset of its outboard in `obs`, the file
+// (its root: 8 words of `roots`, on the device)
+__global__ __launch_bounds__(64) void b3w_sample_plan_batch_kernel(const uint8_t *__restrict__ obs, const uint32_t *__restrict__ roots,
+                                                                   const uint64_t *__restrict__ desc, uint32_t n_samples,
+                                                                   const uint8_t *__restrict__ chunk_bytes, uint32_t *__restrict__ recs,
+                                                                   int32_t *__restrict__ status) {
+  const uint32_t s = blockIdx.x * 64 + threadIdx.x;
+  if (s >= n_samples) return;
+  const uint64_t *d = desc + 5 * (uint64_t)s;
+  const uint64_t len = d[2];
+  uint32_t root[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) root[k] = roots[d[4] * 8 + k];
+  status[s] = sample_plan_one(len, len ? (len + 1023) / 1024 : 1, reinterpret_cast<const uint32_t *>(obs + d[3]), root, d[0], d[1],
+                              chunk_bytes + (uint64_t)s * 1024, recs);
 }
 
 uint64_t num_chunks(uint64_t len) { return len ? (len + 1023) / 1024 : 1; }
 uint32_t chunk_blocks(uint64_t len, uint64_t c) {
   const uint64_t off = c * 1024, bytes = len - off < 1024 ? len - off : 1024;
   return bytes ? (uint32_t)((bytes + 63) / 64) : 1;
+}
+
+// what a batch of these lengths launches: files of at most 64 chunks share waves, in file order, as many as fit (small), the others take a
+// workgroup per tile (big);
+// files of more than one tile a merge workgroup per 1 024 tiles (groups), files of more than 1 024 tiles one more over those (tops)
+struct BatchCounts { uint64_t small, waves, big, big_wgs, merged, groups, tops; bool too_long; };
+BatchCounts batch_counts(const uint64_t *lens, uint32_t n_files) {
+  BatchCounts k{};
+  uint64_t fill = 64;                                    // lanes taken in the current wave of small files (none open yet)
+  for (uint32_t f = 0; f < n_files; ++f) {
+    const uint64_t n = num_chunks(lens[f]);
+    if (n <= 64) {
+      if (fill + n > 64) { k.waves++; fill = 0; }
+      fill += n;
+      k.small++;
+      continue;
+    }
+    const uint64_t tiles = (n + B3W_TILE - 1) / B3W_TILE, groups = (tiles + B3W_TILE - 1) / B3W_TILE;
+    k.big++; k.big_wgs += tiles;
+    if (tiles > 1) { k.merged++; k.groups += groups; }
+    if (groups > 1) k.tops++;
+    if (groups > B3W_TILE) k.too_long = true;
+  }
+  return k;
+}
+
+// the context's staging for the batch calls' tables: waits for the previous batch call, grows both buffers to `bytes`
+int32_t batch_staging(b3w_ctx *ctx, uint64_t bytes) {
+  if (ctx->batch_done) HIP_TRY(ctx, hipEventSynchronize(ctx->batch_done));
+  else HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->batch_done, hipEventDisableTiming));
+  if (ctx->batch_cap < bytes) {
+    if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
+    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
+    ctx->h_batch = nullptr; ctx->d_batch = nullptr; ctx->batch_cap = 0;
+    HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_batch, (size_t)bytes, hipHostMallocDefault));
+    HIP_TRY(ctx, hipMalloc((void **)&ctx->d_batch, (size_t)bytes));
+    ctx->batch_cap = bytes;
+  }
+  return B3W_OK;
 }
 
 }  // namespace
@@ -383,6 +599,129 @@ int32_t b3w_sample_plan_device(b3w_ctx *ctx, uint64_t len, const uint8_t *d_outb
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(ctx, e, "sample plan launch");
   HIP_TRY(ctx, hipEventRecord(ctx->samples_done, st));
+  return B3W_OK;
+}
+
+uint64_t b3w_bao_batch_layout(const uint64_t *host_lens, uint32_t n_files, uint64_t *ob_first) {
+  if (!ob_first || (!host_lens && n_files)) return 0;
+  uint64_t at = 0;
+  for (uint32_t f = 0; f < n_files; ++f) { ob_first[f] = at; at += b3w_bao_outboard_size(host_lens[f]); }
+  ob_first[n_files] = at;
+  return at;
+}
+
+uint64_t b3w_bao_batch_scratch_bytes(const uint64_t *host_lens, uint32_t n_files) {
+  if (!host_lens) return 0;
+  const BatchCounts k = batch_counts(host_lens, n_files);
+  return (k.big_wgs + k.groups) * 32;
+}
+
+int32_t b3w_bao_outboard_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, const uint64_t *host_offsets, const uint64_t *host_lens,
+                                      uint32_t n_files, uint8_t *d_outboards, uint32_t *d_roots, void *d_scratch, uint64_t scratch_bytes,
+                                      void *stream) {
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  if (!n_files) return B3W_OK;
+  if (!host_offsets || !host_lens || !d_outboards || !d_roots) { ctx->last_error = "bao batch: a null pointer (offsets, lengths, outboards or roots)"; return B3W_E_BAD_ARGUMENT; }
+  if ((uintptr_t)d_outboards & 7) { ctx->last_error = "bao batch: d_outboards is not 8-byte aligned"; return B3W_E_BAD_ARGUMENT; }
+  const BatchCounts k = batch_counts(host_lens, n_files);
+  if (k.too_long || k.big_wgs > 0x7fffffffull) { ctx->last_error = "bao batch: a file of more than 2^30 chunks, or more than 2^31 tiles"; return B3W_E_BAD_ARGUMENT; }
+  const uint64_t need = (k.big_wgs + k.groups) * 32;
+  if (scratch_bytes < need) { ctx->last_error = "bao batch: the scratch is smaller than b3w_bao_batch_scratch_bytes says"; return B3W_E_BAD_ARGUMENT; }
+  if (need && (!d_scratch || ((uintptr_t)d_scratch & 15))) { ctx->last_error = "bao batch: the scratch is null or not 16-byte aligned"; return B3W_E_BAD_ARGUMENT; }
+  if (!d_arena)
+    for (uint32_t f = 0; f < n_files; ++f)
+      if (host_lens[f]) { ctx->last_error = "bao batch: a null arena with a file that is not empty"; return B3W_E_BAD_ARGUMENT; }
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  // the tables, one behind the other in the staging buffers, uploaded in one copy: small | big | merged | tops | the small waves' first files
+  const uint64_t n_ents = k.small + k.big + k.merged + k.tops, table_bytes = n_ents * sizeof(BatchEnt) + (k.small ? (k.waves + 1) * 4 : 0);
+  const int32_t rc = batch_staging(ctx, table_bytes);
+  if (rc) return rc;
+  BatchEnt *h_small = reinterpret_cast<BatchEnt *>(ctx->h_batch), *h_big = h_small + k.small, *h_merged = h_big + k.big, *h_tops = h_merged + k.merged;
+  uint32_t *h_waves = reinterpret_cast<uint32_t *>(h_tops + k.tops);
+  uint32_t i_small = 0, i_waves = 0, fill = 64, i_big = 0, i_merged = 0, i_tops = 0, big_wgs = 0, groups = 0;
+  uint64_t ob = 0;
+  for (uint32_t f = 0; f < n_files; ++f) {
+    const uint64_t len = host_lens[f], n = num_chunks(len);
+    if (n <= 64) {
+      if (fill + n > 64) { h_waves[i_waves++] = i_small; fill = 0; }
+      h_small[i_small] = BatchEnt{host_offsets[f], len, ob, fill, f};
+      fill += (uint32_t)n;
+      i_small++;
+    } else {
+      const uint32_t tiles = (uint32_t)((n + B3W_TILE - 1) / B3W_TILE), grp = (tiles + B3W_TILE - 1) / B3W_TILE;
+      h_big[i_big++] = BatchEnt{host_offsets[f], len, ob, big_wgs, f};
+      if (tiles > 1) h_merged[i_merged++] = BatchEnt{big_wgs, len, ob, groups, f};
+      if (grp > 1) { h_tops[i_tops] = BatchEnt{groups, len, ob, i_tops, f}; i_tops++; }
+      big_wgs += tiles;
+      if (tiles > 1) groups += grp;
+    }
+    ob += b3w_bao_outboard_size(len);
+  }
+  if (k.small) h_waves[i_waves] = i_small;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)table_bytes, hipMemcpyHostToDevice, st));
+  const BatchEnt *d_small = reinterpret_cast<const BatchEnt *>(ctx->d_batch), *d_big = d_small + k.small, *d_merged = d_big + k.big, *d_tops = d_merged + k.merged;
+  uint32_t *tile_cv = reinterpret_cast<uint32_t *>(d_scratch), *group_cv = tile_cv + k.big_wgs * 8;
+  if (k.small) hipLaunchKernelGGL(b3w_bao_small_kernel, dim3((uint32_t)k.waves), dim3(64), 0, st, d_arena, d_small, reinterpret_cast<const uint32_t *>(d_tops + k.tops), d_outboards, d_roots);
+  if (k.big) hipLaunchKernelGGL(b3w_bao_tile_kernel, dim3((uint32_t)k.big_wgs), dim3(B3W_TILE), 0, st, d_arena, d_big, (uint32_t)k.big, d_outboards, d_roots, tile_cv);
+  if (k.merged) hipLaunchKernelGGL(b3w_bao_merge_kernel, dim3((uint32_t)k.groups), dim3(256), 0, st, d_merged, (uint32_t)k.merged, (uint64_t)B3W_TILE, tile_cv, group_cv, d_outboards, d_roots);
+  if (k.tops) hipLaunchKernelGGL(b3w_bao_merge_kernel, dim3((uint32_t)k.tops), dim3(256), 0, st, d_tops, (uint32_t)k.tops, (uint64_t)B3W_TILE * B3W_TILE, group_cv, (uint32_t *)nullptr, d_outboards, d_roots);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(ctx, e, "bao batch launch");
+  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
+  return B3W_OK;
+}
+
+int64_t b3w_sample_rows_batch(const uint64_t *host_lens, uint32_t n_files, const uint32_t *host_files, const uint64_t *host_chunks,
+                              uint32_t n_samples, uint64_t *row_first) {
+  if (!row_first || (n_samples && (!host_lens || !host_files || !host_chunks))) return -B3W_E_BAD_ARGUMENT;
+  for (uint32_t s = 0; s < n_samples; ++s)
+    if (host_files[s] >= n_files || host_chunks[s] >= num_chunks(host_lens[host_files[s]])) return -B3W_E_BAD_ARGUMENT;
+  uint64_t row = 0;
+  for (uint32_t s = 0; s < n_samples; ++s) {
+    const uint64_t len = host_lens[host_files[s]];
+    row_first[s] = row;
+    row += chunk_blocks(len, host_chunks[s]) + b3w_plan_path_len(host_chunks[s], num_chunks(len));
+  }
+  row_first[n_samples] = row;
+  return (int64_t)row;
+}
+
+int32_t b3w_sample_plan_batch_device(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, const uint8_t *d_outboards, const uint32_t *d_roots,
+                                     const uint32_t *host_files, const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_chunk_bytes,
+                                     uint32_t *d_records, int32_t *d_sample_status, void *stream) {
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  if (ctx->desc.kind == B3W_KIND_COMP) { ctx->last_error = "sampled paths plan the nova step circuits' records"; return B3W_E_BAD_ARGUMENT; }
+  if (!n_samples) return B3W_OK;
+  if (!host_lens || !d_outboards || !d_roots || !host_files || !host_chunks || !d_chunk_bytes || !d_records || !d_sample_status) {
+    ctx->last_error = "sample plan batch: a null pointer"; return B3W_E_BAD_ARGUMENT;
+  }
+  for (uint32_t s = 0; s < n_samples; ++s) {
+    if (host_files[s] >= n_files) { ctx->last_error = "a sampled file index is not below the file count"; return B3W_E_BAD_ARGUMENT; }
+    if (host_chunks[s] >= num_chunks(host_lens[host_files[s]])) { ctx->last_error = "a sampled chunk index is not below its file's chunk count"; return B3W_E_BAD_ARGUMENT; }
+  }
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  // staging: the per-sample table {chunk, first row, length, outboard offset, file} (uploaded), then the files' outboard offsets (host only)
+  const uint64_t desc_bytes = (uint64_t)n_samples * 40;
+  const int32_t rc = batch_staging(ctx, desc_bytes + ((uint64_t)n_files + 1) * 8);
+  if (rc) return rc;
+  uint64_t *desc = reinterpret_cast<uint64_t *>(ctx->h_batch), *ob_first = desc + 5 * (uint64_t)n_samples;
+  (void)b3w_bao_batch_layout(host_lens, n_files, ob_first);
+  uint64_t row = 0;
+  for (uint32_t s = 0; s < n_samples; ++s) {
+    const uint32_t f = host_files[s];
+    const uint64_t len = host_lens[f];
+    uint64_t *d = desc + 5 * (uint64_t)s;
+    d[0] = host_chunks[s]; d[1] = row; d[2] = len; d[3] = ob_first[f]; d[4] = f;
+    row += chunk_blocks(len, host_chunks[s]) + b3w_plan_path_len(host_chunks[s], num_chunks(len));
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)desc_bytes, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(b3w_sample_plan_batch_kernel, dim3((n_samples + 63) / 64), dim3(64), 0, st, d_outboards, d_roots,
+                     reinterpret_cast<const uint64_t *>(ctx->d_batch), n_samples, d_chunk_bytes, d_records, d_sample_status);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(ctx, e, "sample plan batch launch");
+  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
   return B3W_OK;
 }
 

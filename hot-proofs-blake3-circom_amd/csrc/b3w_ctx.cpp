@@ -303,7 +303,7 @@ int b3w_int_default_variant(const b3w_ctx *ctx, uint32_t n, const uint8_t *d_bod
 
 extern "C" {
 
-uint32_t b3w_abi_version(void) { return (1u << 16) | 1u; }
+uint32_t b3w_abi_version(void) { return (1u << 16) | 2u; }   // 1.2: the bao batch calls
 
 int32_t b3w_identify_wasm(const uint8_t *code, size_t len) {
   if (!code) return B3W_CIRCUIT_UNKNOWN;
@@ -485,6 +485,9 @@ void b3w_destroy(b3w_ctx *ctx) {
   if (ctx->samples_done) { (void)hipEventSynchronize(ctx->samples_done); (void)hipEventDestroy(ctx->samples_done); }
   if (ctx->h_samples) (void)hipHostFree(ctx->h_samples);
   if (ctx->d_samples) (void)hipFree(ctx->d_samples);
+  if (ctx->batch_done) { (void)hipEventSynchronize(ctx->batch_done); (void)hipEventDestroy(ctx->batch_done); }
+  if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
+  if (ctx->d_batch) (void)hipFree(ctx->d_batch);
   delete ctx;
 }
 

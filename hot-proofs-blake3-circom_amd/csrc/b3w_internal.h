@@ -76,6 +76,11 @@ struct b3w_ctx {
   uint64_t *h_samples = nullptr, *d_samples = nullptr;
   uint32_t samples_cap = 0;
   hipEvent_t samples_done = nullptr;
+  // b3w_bao_outboard_batch_device / b3w_sample_plan_batch_device: the per-file (per-sample) tables, pinned on the host and on the device,
+  // grow-only; batch_done = the last batch call's copy and kernels are through with both
+  uint8_t *h_batch = nullptr, *d_batch = nullptr;
+  uint64_t batch_cap = 0;
+  hipEvent_t batch_done = nullptr;
   std::string last_error;
 };
 

@@ -588,6 +588,42 @@ int32_t b3w_sample_plan_device(b3w_ctx *ctx, uint64_t preimage_len, const uint8_
                                const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_chunk_bytes, uint32_t *d_records,
                                int32_t *d_sample_status, void *stream);
 
+/* ---- the same over a batch of files (ABI 1.2) -------------------------------------------------------------
+ * A provider holds very many files, most of them small.  The batch calls take all of them at once: the outboards and roots in a
+ * number of launches that does not depend on the file count (at most four: files of at most 64 chunks packed several to a wave; the others a
+ * workgroup per TILE of 1 024 chunks, chunk CVs and the tile's tree in LDS, every node written straight to its pre-order place; one
+ * workgroup per 1 024 tile CVs of the files of more than one tile; and, only with a file past 1 GiB, one more over those groups'
+ * CVs, so files up to 1 TiB take the same route as all the others: no fall-back to the single-file stages), and one planning
+ * call for challenges that name (file, chunk) pairs.  Nothing of a tile goes through level arrays: the scratch holds one CV per
+ * tile of the files of more than 64 chunks plus one per group of 1 024 tiles: 32 bytes per tile (1 MiB of file) + 32 per group. */
+/* Host only.  Outboards of a batch are packed in file order: file f's outboard (b3w_bao_outboard_size(lens[f]) bytes, byte for byte
+ * what b3w_bao_outboard_device writes for that file alone) lies at [ob_first[f], ob_first[f + 1]) of d_outboards; every entry is a
+ * multiple of 8.  ob_first: n_files + 1 entries.  Returns the total byte count. */
+uint64_t b3w_bao_batch_layout(const uint64_t *host_lens, uint32_t n_files, uint64_t *ob_first);
+/* Host only.  Bytes of caller's scratch the batch call needs for these lengths (may be 0: no file of more than 64 chunks). */
+uint64_t b3w_bao_batch_scratch_bytes(const uint64_t *host_lens, uint32_t n_files);
+/* File f is bytes [host_offsets[f], + host_lens[f]) of d_arena (any offsets: gaps, overlaps, repeats, unaligned starts, zero lengths;
+ * a file that starts 16-byte aligned is read in whole 16-byte quarters).  d_outboards: 8-byte aligned; d_roots: 8 u32 per file
+ * (= BLAKE3 of the file); d_scratch: 16-byte aligned.  The per-file table goes through staging the context owns (pinned host +
+ * device, grow-only, freed with the context); nothing else is allocated.  n_files == 0: a no-op.  B3W_E_BAD_ARGUMENT before anything
+ * is launched for a null pointer, a small scratch or a file of more than 2^30 chunks.  Asynchronous on `stream`; waits for this
+ * context's previous batch call. */
+int32_t b3w_bao_outboard_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, const uint64_t *host_offsets, const uint64_t *host_lens,
+                                      uint32_t n_files, uint8_t *d_outboards, uint32_t *d_roots, void *d_scratch,
+                                      uint64_t scratch_bytes, void *stream);
+/* Rows of the step records of samples (host_files[s], host_chunks[s]), sample-major as b3w_sample_rows.  -B3W_E_BAD_ARGUMENT for a
+ * file index >= n_files or a chunk index not below its file's chunk count. */
+int64_t b3w_sample_rows_batch(const uint64_t *host_lens, uint32_t n_files, const uint32_t *host_files, const uint64_t *host_chunks,
+                              uint32_t n_samples, uint64_t *row_first);
+/* b3w_sample_plan_device over a batch: d_outboards packed as b3w_bao_batch_layout says, d_roots ON THE DEVICE as the batch outboard
+ * call left them, d_chunk_bytes 1 024 bytes per sample.  Records and statuses sample by sample those of b3w_sample_plan_device
+ * on that sample's file alone; a bad sample touches no other, of its own file or another.  n_samples == 0: a no-op.  Nova contexts
+ * only. */
+int32_t b3w_sample_plan_batch_device(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, const uint8_t *d_outboards,
+                                     const uint32_t *d_roots, const uint32_t *host_files, const uint64_t *host_chunks,
+                                     uint32_t n_samples, const uint8_t *d_chunk_bytes, uint32_t *d_records,
+                                     int32_t *d_sample_status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
