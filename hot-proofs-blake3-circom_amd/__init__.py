@@ -176,6 +176,11 @@ def lib():
         "b3w_bao_outboard_batch_device": (i32, [vp, vp, vp, vp, u32, vp, vp, vp, u64, vp]),
         "b3w_sample_rows_batch": (ctypes.c_int64, [vp, u32, vp, vp, u32, vp]),
         "b3w_sample_plan_batch_device": (i32, [vp, vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp]),
+        "b3w_bao_group_outboard_size": (u64, [u64, u32]),
+        "b3w_bao_group_batch_layout": (u64, [vp, u32, u32, vp]),
+        "b3w_bao_group_path_nodes": (i32, [u64, u64, u32, ctypes.POINTER(u64), ctypes.POINTER(u32)]),
+        "b3w_bao_group_outboard_batch_device": (i32, [vp, vp, vp, vp, u32, u32, vp, vp, vp, u64, vp]),
+        "b3w_sample_plan_group_batch_device": (i32, [vp, vp, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -198,7 +203,8 @@ EXPORTED_SYMBOLS = ("b3w_abi_version", "b3w_identify_wasm", "b3w_create", "b3w_d
                     "b3w_chain_outputs", "b3w_chain_records", "b3w_chain_public", "b3w_chain_status", "b3w_chain_local_cvs", "b3w_chain_root",
                     "b3w_bao_outboard_size", "b3w_bao_outboard_device", "b3w_bao_path_nodes", "b3w_bao_slice", "b3w_sample_rows",
                     "b3w_sample_plan_device", "b3w_bao_batch_layout", "b3w_bao_batch_scratch_bytes", "b3w_bao_outboard_batch_device",
-                    "b3w_sample_rows_batch", "b3w_sample_plan_batch_device")
+                    "b3w_sample_rows_batch", "b3w_sample_plan_batch_device", "b3w_bao_group_outboard_size", "b3w_bao_group_batch_layout",
+                    "b3w_bao_group_path_nodes", "b3w_bao_group_outboard_batch_device", "b3w_sample_plan_group_batch_device")
 
 
 class graph_capture:

@@ -4,7 +4,9 @@ A data-availability challenge names a few chunk indices; the provider answers fr
 parent nodes, kept beside the file).  outboard() makes the outboard of a preimage in device memory; plan_samples() plans the step
 records of the challenged chunk paths from the outboard and those chunks' bytes alone, verifying each path against the root;
 prove_samples() runs their witnesses, constraint checks and commitments through the batch calls, batch by batch.  outboard_batch(),
-plan_samples_batch() and prove_samples_batch() do the same for a whole batch of files of one device arena at once.  The records are
+plan_samples_batch() and prove_samples_batch() do the same for a whole batch of files of one device arena at once;
+outboard_groups_batch(), plan_samples_groups_batch() and prove_samples_groups_batch() keep the outboards over chunk groups of
+2^group_log chunks, 2^group_log times smaller, and recompute the levels inside a group from the group's bytes.  The records are
 word for word those the chain planner writes for the same chunks (ChainPlanner.plan), so every step is the reference's
 prove_chunk_hash step (rust_fold/src/main.rs:41-203 over hash_with_path's slice, rust_fold/src/blake3_hash.rs:17-93)."""
 import ctypes
@@ -260,4 +262,114 @@ def prove_samples_batch(ctx, d_outboards, lens, d_roots, files, chunks, d_chunk_
     """prove_samples over a batch of files: plan_samples_batch, then the same witness / constraint / commitment batches over its rows"""
     s = _stream(stream)
     out = plan_samples_batch(ctx, d_outboards, lens, d_roots, files, chunks, d_chunk_bytes, stream=s)
+    return _prove_planned(ctx, out, batch_steps, consumer, commit_key, r1cs, s)
+
+
+# ---- outboards over chunk groups ---------------------------------------------------------------------------------------
+MAX_GROUP_LOG = 6
+GROUP_STATUS = {**STATUS, 1: "the group's bytes do not match", 2: "a stored node or the root does not match"}
+
+
+def group_outboard_size(length, group_log):
+    """8 + 64 (n_groups - 1): the outboard over groups of 2^group_log chunks"""
+    if not 0 <= group_log <= MAX_GROUP_LOG:
+        raise B3WError(100, f"group_log {group_log} is not in 0 .. {MAX_GROUP_LOG}")
+    return lib().b3w_bao_group_outboard_size(length, group_log)
+
+
+def group_batch_layout(lens, group_log):
+    """batch_layout for group outboards -> ob_first (numpy uint64 [n_files + 1])"""
+    if not 0 <= group_log <= MAX_GROUP_LOG:
+        raise B3WError(100, f"group_log {group_log} is not in 0 .. {MAX_GROUP_LOG}")
+    ln = _u64(lens)
+    ob_first = np.zeros(ln.size + 1, dtype=np.uint64)
+    lib().b3w_bao_group_batch_layout(ln.ctypes.data, ln.size, group_log, ob_first.ctypes.data)
+    return ob_first
+
+
+def group_path_nodes(chunk, n_chunks, group_log):
+    """indices in the group outboard of the stored part of the chunk's path, root first"""
+    out = (ctypes.c_uint64 * 64)()
+    cnt = ctypes.c_uint32()
+    _chk(None, lib().b3w_bao_group_path_nodes(chunk, n_chunks, group_log, out, ctypes.byref(cnt)), "b3w_bao_group_path_nodes")
+    return list(out[:cnt.value])
+
+
+def outboard_groups_batch(ctx, d_arena, offsets, lens, group_log, stream=0):
+    """outboard_batch writing group outboards (groups of 2^group_log chunks): the same dict, the outboards packed as
+    group_batch_layout says; the roots are the files' BLAKE3 hashes as before."""
+    L = lib()
+    off, ln = _u64(offsets), _u64(lens)
+    assert off.size == ln.size
+    assert d_arena.is_cuda and d_arena.dtype == torch.uint8 and d_arena.is_contiguous()
+    if ln.size and int((off + ln).max()) > d_arena.numel():
+        raise B3WError(100, "outboard_groups_batch: a file reaches past the end of the arena")
+    dev = d_arena.device
+    ob_first = group_batch_layout(ln, group_log)
+    obs = torch.empty(int(ob_first[-1]), dtype=torch.uint8, device=dev)
+    roots = torch.empty((ln.size, 8), dtype=torch.int32, device=dev)
+    need = L.b3w_bao_batch_scratch_bytes(ln.ctypes.data, ln.size)
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    _chk(ctx, L.b3w_bao_group_outboard_batch_device(ctx.handle, d_arena.data_ptr() if d_arena.numel() else None, off.ctypes.data, ln.ctypes.data,
+                                                    ln.size, group_log, obs.data_ptr(), roots.data_ptr(), scratch.data_ptr() if need else None,
+                                                    need, _stream(stream)), "b3w_bao_group_outboard_batch_device")
+    return dict(outboards=obs, ob_first=ob_first, roots=roots)
+
+
+def group_bytes_batch(arena, offsets, lens, files, chunks, group_log, device="cuda"):
+    """the bytes of the sampled chunks' groups as plan_samples_groups_batch takes them (uint8 [n_samples, 1024 << group_log], zero
+    past a file's end): what a provider reads from its file for a challenge.  arena: host bytes / numpy, or a CUDA tensor."""
+    off, ln = _u64(offsets).astype(np.int64), _u64(lens).astype(np.int64)
+    fi, ch = np.asarray(files, dtype=np.int64), np.asarray(chunks, dtype=np.int64)
+    width = 1024 << group_log
+    rel = (ch >> group_log << group_log) * 1024
+    start = off[fi] + rel
+    count = np.clip(ln[fi] - rel, 0, width)
+    if isinstance(arena, torch.Tensor):
+        dev = arena.device
+        if arena.numel() == 0:
+            return torch.zeros((fi.size, width), dtype=torch.uint8, device=dev)
+        col = torch.arange(width, device=dev)
+        out = torch.empty((fi.size, width), dtype=torch.uint8, device=dev)
+        step = max(1, (1 << 24) // width)                          # (the gather's index tensor: 128 MiB at a time)
+        for a in range(0, fi.size, step):
+            idx = torch.from_numpy(start[a:a + step]).to(dev)[:, None] + col[None, :]
+            live = col[None, :] < torch.from_numpy(count[a:a + step]).to(dev)[:, None]
+            out[a:a + step] = torch.where(live, arena[idx.clamp_(max=arena.numel() - 1)], torch.zeros((), dtype=torch.uint8, device=dev))
+        return out
+    data = np.frombuffer(bytes(arena), dtype=np.uint8) if not isinstance(arena, np.ndarray) else arena
+    out = np.zeros((fi.size, width), dtype=np.uint8)
+    for s in range(fi.size):
+        out[s, :count[s]] = data[start[s]:start[s] + count[s]]
+    return torch.from_numpy(out).to(device)
+
+
+def plan_samples_groups_batch(ctx, d_group_outboards, lens, d_roots, files, chunks, d_group_bytes, group_log, stream=0):
+    """plan_samples_batch from group outboards (outboard_groups_batch) and the sampled chunks' groups' bytes (group_bytes_batch): the
+    same dict, records and rows word for word plan_samples_batch's.  sample_status: GROUP_STATUS — 1 means a byte of the chunk's
+    GROUP does not match, the sampled chunk's or another's."""
+    L = lib()
+    ln, ch = _u64(lens), _u64(chunks)
+    fi = np.ascontiguousarray(files, dtype=np.uint32)
+    if not 0 <= group_log <= MAX_GROUP_LOG:
+        raise B3WError(100, f"group_log {group_log} is not in 0 .. {MAX_GROUP_LOG}")
+    rf = sample_rows_batch(ln, fi, ch)
+    dev = d_group_outboards.device
+    assert d_roots.is_cuda and d_roots.is_contiguous() and d_roots.numel() >= ln.size * 8
+    assert d_group_bytes.is_cuda and d_group_bytes.dtype == torch.uint8 and d_group_bytes.is_contiguous()
+    assert d_group_bytes.numel() >= ch.size * (1024 << group_log)
+    recs = torch.empty((int(rf[-1]), 32), dtype=torch.int32, device=dev)
+    st = torch.full((ch.size,), -1, dtype=torch.int32, device=dev)
+    _chk(ctx, L.b3w_sample_plan_group_batch_device(ctx.handle, ln.ctypes.data, ln.size, group_log, d_group_outboards.data_ptr(), d_roots.data_ptr(),
+                                                   fi.ctypes.data, ch.ctypes.data, ch.size, d_group_bytes.data_ptr(), recs.data_ptr(), st.data_ptr(),
+                                                   _stream(stream)), "b3w_sample_plan_group_batch_device")
+    provable = np.array([bool(L.b3w_chain_path_provable(int(c), num_chunks(int(ln[f])))) for f, c in zip(fi, ch)], dtype=bool)
+    return dict(records=recs, row_first=rf, sample_status=st.cpu().numpy(), provable=provable)
+
+
+def prove_samples_groups_batch(ctx, d_group_outboards, lens, d_roots, files, chunks, d_group_bytes, group_log, batch_steps=4096, consumer=None,
+                               commit_key=None, r1cs=None, stream=0):
+    """prove_samples_batch over plan_samples_groups_batch's plan"""
+    s = _stream(stream)
+    out = plan_samples_groups_batch(ctx, d_group_outboards, lens, d_roots, files, chunks, d_group_bytes, group_log, stream=s)
     return _prove_planned(ctx, out, batch_steps, consumer, commit_key, r1cs, s)

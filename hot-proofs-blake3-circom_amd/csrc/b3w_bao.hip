@@ -17,6 +17,10 @@
 //   b3w_bao_merge_kernel     their pre-order places; the tree over the tile CVs, one workgroup per 1 024 of them (see "batches of files")
 //   b3w_sample_plan_kernel   one thread per challenged chunk: its leaf records from its bytes, its path verified top down against the
 //                            root the way bao's decoder does, its parent records bottom up with the outboard's CVs
+//   b3w_bao_*_group_kernel   the three batch kernels writing GROUP outboards: the tree over chunk groups of 1 << gl chunks, every node over at
+//                            most a group's chunks computed and not stored ("outboards over chunk groups" in b3wit.h)
+//   b3w_sample_plan_group_kernel  a challenged chunk from a group outboard and its group's bytes: a lane per chunk of the group, the group's
+//                            tree merged in LDS, the stored part of the path verified across the sample's lanes, the same records
 #include "b3w_internal.h"
 #include "b3w_blake3_dev.h"
 
@@ -248,14 +252,26 @@ __device__ __forceinline__ BatchEnt batch_ent(const BatchEnt *__restrict__ ents,
   return ents[lo];
 }
 
-// one parent: the CVs in slots i0 (left) and i1 (right) of cv to the node at dst, their parent's CV to slot i0 (d = PARENT [| ROOT])
+// The barrier of the kernels that do not store every node.  In the group instantiation of the tile kernel the compiler (ROCm 7's clang) left
+// the level loop's s_barrier without a wait for the LDS stores of the level before (it keeps the wait in the instantiation that stores
+// every node), and a 64-chunk subtree's CV now and then came out wrong: the wait is spelled out.
+__device__ __forceinline__ void lds_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __syncthreads();
+}
+
+// one parent: the CVs in slots i0 (left) and i1 (right) of cv to the node at dst, their parent's CV to slot i0 (d = PARENT [| ROOT]).
+// GRP (group outboards): a null `node` is a node inside a chunk group, which is computed and not stored.
+template <bool GRP>
 __device__ __forceinline__ void merge_pair(uint32_t *cv, uint32_t i0, uint32_t i1, uint8_t *__restrict__ node, uint32_t d) {
   uint32_t m[16], ivv[8], o[8];
   const uint4 l0 = reinterpret_cast<const uint4 *>(cv + i0 * 8)[0], l1 = reinterpret_cast<const uint4 *>(cv + i0 * 8)[1];
   const uint4 r0 = reinterpret_cast<const uint4 *>(cv + i1 * 8)[0], r1 = reinterpret_cast<const uint4 *>(cv + i1 * 8)[1];
-  uint2 *dst = reinterpret_cast<uint2 *>(node);                      // (8 off a 16-byte boundary)
-  dst[0] = make_uint2(l0.x, l0.y); dst[1] = make_uint2(l0.z, l0.w); dst[2] = make_uint2(l1.x, l1.y); dst[3] = make_uint2(l1.z, l1.w);
-  dst[4] = make_uint2(r0.x, r0.y); dst[5] = make_uint2(r0.z, r0.w); dst[6] = make_uint2(r1.x, r1.y); dst[7] = make_uint2(r1.z, r1.w);
+  if (!GRP || node) {
+    uint2 *dst = reinterpret_cast<uint2 *>(node);                    // (8 off a 16-byte boundary)
+    dst[0] = make_uint2(l0.x, l0.y); dst[1] = make_uint2(l0.z, l0.w); dst[2] = make_uint2(l1.x, l1.y); dst[3] = make_uint2(l1.z, l1.w);
+    dst[4] = make_uint2(r0.x, r0.y); dst[5] = make_uint2(r0.z, r0.w); dst[6] = make_uint2(r1.x, r1.y); dst[7] = make_uint2(r1.z, r1.w);
+  }
   m[0] = l0.x; m[1] = l0.y; m[2] = l0.z; m[3] = l0.w; m[4] = l1.x; m[5] = l1.y; m[6] = l1.z; m[7] = l1.w;
   m[8] = r0.x; m[9] = r0.y; m[10] = r0.z; m[11] = r0.w; m[12] = r1.x; m[13] = r1.y; m[14] = r1.z; m[15] = r1.w;
   iv(ivv);
@@ -266,24 +282,34 @@ __device__ __forceinline__ void merge_pair(uint32_t *cv, uint32_t i0, uint32_t i
 
 // cv: cnt items of `unit` chunks each (the last one maybe fewer) of a tree over `total` chunks whose nodes go to `nodes` (its root's place).
 // Leaves the tree's CV in cv[0 .. 8) (ROOT-flagged where `root` says so); ends with a barrier.
-template <int BS>
-__device__ __forceinline__ void merge_in_lds(uint32_t *cv, uint32_t cnt, uint64_t unit, uint64_t total, uint8_t *__restrict__ nodes, bool root) {
+// GRP: `nodes` is the root's place in the file's GROUP outboard (groups of 1 << gl chunks; the tree starts at a multiple of that): a node
+// over at most a group's chunks is not stored, the others go to their pre-order places in the tree over the groups.
+template <int BS, bool GRP>
+__device__ __forceinline__ void merge_in_lds(uint32_t *cv, uint32_t cnt, uint64_t unit, uint64_t total, uint8_t *__restrict__ nodes, bool root,
+                                             uint32_t gl) {
   for (uint32_t l = 0; (1u << l) < cnt; ++l) {
-    __syncthreads();
+    if (GRP) lds_barrier(); else __syncthreads();
     const bool top = (2u << l) >= cnt;
     for (uint32_t j = threadIdx.x;; j += BS) {
       const uint32_t i0 = (2 * j) << l, i1 = i0 + (1u << l);
       if (i1 >= cnt) break;
-      const uint64_t a = i0 * unit, e = (uint64_t)(i0 + (2u << l)) * unit;
-      merge_pair(cv, i0, i1, nodes + preorder_pos(total, a, (e < total ? e : total) - a) * 64, 4u | (top && root ? 8u : 0u));
+      const uint64_t a = i0 * unit, e = (uint64_t)(i0 + (2u << l)) * unit, size = (e < total ? e : total) - a;
+      uint8_t *node;
+      if (GRP) {
+        const uint64_t G1 = (1ull << gl) - 1;
+        node = size > G1 + 1 ? nodes + preorder_pos((total + G1) >> gl, a >> gl, (size + G1) >> gl) * 64 : nullptr;
+      } else {
+        node = nodes + preorder_pos(total, a, size) * 64;
+      }
+      merge_pair<GRP>(cv, i0, i1, node, 4u | (top && root ? 8u : 0u));
     }
   }
-  __syncthreads();
+  if (GRP) lds_barrier(); else __syncthreads();
 }
 
-__global__ __launch_bounds__(B3W_TILE) void b3w_bao_tile_kernel(const uint8_t *__restrict__ arena, const BatchEnt *__restrict__ ents, uint32_t n_ents,
-                                                                uint8_t *__restrict__ outboards, uint32_t *__restrict__ roots,
-                                                                uint32_t *__restrict__ tile_cv) {
+template <bool GRP>
+__device__ __forceinline__ void tile_body(const uint8_t *__restrict__ arena, const BatchEnt *__restrict__ ents, uint32_t n_ents,
+                                          uint8_t *__restrict__ outboards, uint32_t *__restrict__ roots, uint32_t *__restrict__ tile_cv, uint32_t gl) {
   __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
   const BatchEnt e = batch_ent(ents, n_ents, blockIdx.x);
   const uint64_t n = (e.len + 1023) / 1024;                           // (more than 64 chunks)
@@ -299,17 +325,30 @@ __global__ __launch_bounds__(B3W_TILE) void b3w_bao_tile_kernel(const uint8_t *_
   }
   uint8_t *ob = outboards + e.ob;
   if (a0 == 0 && threadIdx.x == 0) *reinterpret_cast<uint2 *>(ob) = make_uint2((uint32_t)e.len, (uint32_t)(e.len >> 32));
-  merge_in_lds<B3W_TILE>(cv, m, 1, m, ob + 8 + preorder_pos(n, a0, m) * 64, sole);
+  const uint64_t G1 = GRP ? (1ull << gl) - 1 : 0;                     // (a tile starts at a multiple of every group size)
+  merge_in_lds<B3W_TILE, GRP>(cv, m, 1, m, ob + 8 + (GRP ? preorder_pos((n + G1) >> gl, a0 >> gl, (m + G1) >> gl) : preorder_pos(n, a0, m)) * 64, sole, gl);
   if (threadIdx.x < 8) (sole ? roots + (uint64_t)e.file * 8 : tile_cv + (uint64_t)blockIdx.x * 8)[threadIdx.x] = cv[threadIdx.x];
+}
+
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_tile_kernel(const uint8_t *__restrict__ arena, const BatchEnt *__restrict__ ents, uint32_t n_ents,
+                                                                uint8_t *__restrict__ outboards, uint32_t *__restrict__ roots,
+                                                                uint32_t *__restrict__ tile_cv) {
+  tile_body<false>(arena, ents, n_ents, outboards, roots, tile_cv, 0);
+}
+// the same into group outboards (groups of 1 << gl chunks, gl <= 6)
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_tile_group_kernel(const uint8_t *__restrict__ arena, const BatchEnt *__restrict__ ents, uint32_t n_ents,
+                                                                      uint8_t *__restrict__ outboards, uint32_t *__restrict__ roots,
+                                                                      uint32_t *__restrict__ tile_cv, uint32_t gl) {
+  tile_body<true>(arena, ents, n_ents, outboards, roots, tile_cv, gl);
 }
 
 // Files of at most 64 chunks, several to a wave: wave w takes the files [wave_first[w], wave_first[w + 1]) of `ents`, which have at most 64
 // chunks together; ents[f].first = the lane of file f's chunk 0.  lane = chunk, every lane busy where the files fill the wave (a wave a
 // file would leave 60 of 64 lanes idle on 4 KiB files, and idle lanes cost the same issue cycles).  The same in-place merge, each file
 // in its own run of slots: at level l the lane of a chunk index that is a multiple of 2 << l merges with the slot 1 << l further on.
-__global__ __launch_bounds__(64) void b3w_bao_small_kernel(const uint8_t *__restrict__ arena, const BatchEnt *__restrict__ ents,
-                                                           const uint32_t *__restrict__ wave_first, uint8_t *__restrict__ outboards,
-                                                           uint32_t *__restrict__ roots) {
+template <bool GRP>
+__device__ __forceinline__ void small_body(const uint8_t *__restrict__ arena, const BatchEnt *__restrict__ ents, const uint32_t *__restrict__ wave_first,
+                                           uint8_t *__restrict__ outboards, uint32_t *__restrict__ roots, uint32_t gl) {
   __shared__ __attribute__((aligned(16))) uint32_t cv[64 * 8];
   const uint32_t lane = threadIdx.x;
   uint32_t lo = wave_first[blockIdx.x], hi = wave_first[blockIdx.x + 1];
@@ -330,24 +369,43 @@ __global__ __launch_bounds__(64) void b3w_bao_small_kernel(const uint8_t *__rest
   uint8_t *ob = outboards + e.ob;
   if (live && i == 0) *reinterpret_cast<uint2 *>(ob) = make_uint2((uint32_t)e.len, (uint32_t)(e.len >> 32));
   for (uint32_t l = 0; l < 6; ++l) {
-    __syncthreads();
+    if (GRP) lds_barrier(); else __syncthreads();
     if (!__any(live && (1u << l) < n)) break;                         // (uniform: the workgroup is this one wave)
     if (live && (i & ((2u << l) - 1)) == 0 && i + (1u << l) < n) {
       const uint32_t size = n - i < (2u << l) ? n - i : (2u << l);
-      merge_pair(cv, lane, lane + (1u << l), ob + 8 + preorder_pos(n, i, size) * 64, 4u | (i == 0 && (2u << l) >= n ? 8u : 0u));
+      uint8_t *node;
+      if (GRP) {                                                      // (size > a group: i is a multiple of the group size)
+        const uint32_t G1 = (1u << gl) - 1;
+        node = size > G1 + 1 ? ob + 8 + preorder_pos((n + G1) >> gl, i >> gl, (size + G1) >> gl) * 64 : nullptr;
+      } else {
+        node = ob + 8 + preorder_pos(n, i, size) * 64;
+      }
+      merge_pair<GRP>(cv, lane, lane + (1u << l), node, 4u | (i == 0 && (2u << l) >= n ? 8u : 0u));
     }
   }
-  __syncthreads();
+  if (GRP) lds_barrier(); else __syncthreads();
   if (live && i == 0) {
 #pragma unroll
     for (int k = 0; k < 8; ++k) roots[(uint64_t)e.file * 8 + k] = cv[lane * 8 + k];
   }
 }
 
+__global__ __launch_bounds__(64) void b3w_bao_small_kernel(const uint8_t *__restrict__ arena, const BatchEnt *__restrict__ ents,
+                                                           const uint32_t *__restrict__ wave_first, uint8_t *__restrict__ outboards,
+                                                           uint32_t *__restrict__ roots) {
+  small_body<false>(arena, ents, wave_first, outboards, roots, 0);
+}
+// the same into group outboards: with gl >= 1 a file of at most a group's chunks gets its header alone
+__global__ __launch_bounds__(64) void b3w_bao_small_group_kernel(const uint8_t *__restrict__ arena, const BatchEnt *__restrict__ ents,
+                                                                 const uint32_t *__restrict__ wave_first, uint8_t *__restrict__ outboards,
+                                                                 uint32_t *__restrict__ roots, uint32_t gl) {
+  small_body<true>(arena, ents, wave_first, outboards, roots, gl);
+}
+
 // unit = chunks per input item (B3W_TILE, or B3W_TILE^2 for the launch over the groups' CVs); input item i of the file: in_cv slot e.off + i
-__global__ __launch_bounds__(256) void b3w_bao_merge_kernel(const BatchEnt *__restrict__ ents, uint32_t n_ents, uint64_t unit,
-                                                            const uint32_t *__restrict__ in_cv, uint32_t *__restrict__ out_cv,
-                                                            uint8_t *__restrict__ outboards, uint32_t *__restrict__ roots) {
+template <bool GRP>
+__device__ __forceinline__ void merge_body(const BatchEnt *__restrict__ ents, uint32_t n_ents, uint64_t unit, const uint32_t *__restrict__ in_cv,
+                                           uint32_t *__restrict__ out_cv, uint8_t *__restrict__ outboards, uint32_t *__restrict__ roots, uint32_t gl) {
   __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
   const BatchEnt e = batch_ent(ents, n_ents, blockIdx.x);
   const uint64_t n = (e.len + 1023) / 1024;                           // (more than one tile)
@@ -357,8 +415,21 @@ __global__ __launch_bounds__(256) void b3w_bao_merge_kernel(const BatchEnt *__re
   const bool sole = n <= span;
   const uint4 *src = reinterpret_cast<const uint4 *>(in_cv + (e.off + g * B3W_TILE) * 8);
   for (uint32_t i = threadIdx.x; i < cnt * 2; i += 256) reinterpret_cast<uint4 *>(cv)[i] = src[i];
-  merge_in_lds<256>(cv, cnt, unit, tot, outboards + e.ob + 8 + preorder_pos(n, a0, tot) * 64, sole);
+  const uint64_t G1 = GRP ? (1ull << gl) - 1 : 0;                     // (every node here is over more than a tile: all of them are stored)
+  merge_in_lds<256, GRP>(cv, cnt, unit, tot, outboards + e.ob + 8 + (GRP ? preorder_pos((n + G1) >> gl, a0 >> gl, (tot + G1) >> gl) : preorder_pos(n, a0, tot)) * 64,
+                         sole, gl);
   if (threadIdx.x < 8) (sole ? roots + (uint64_t)e.file * 8 : out_cv + (uint64_t)blockIdx.x * 8)[threadIdx.x] = cv[threadIdx.x];
+}
+
+__global__ __launch_bounds__(256) void b3w_bao_merge_kernel(const BatchEnt *__restrict__ ents, uint32_t n_ents, uint64_t unit,
+                                                            const uint32_t *__restrict__ in_cv, uint32_t *__restrict__ out_cv,
+                                                            uint8_t *__restrict__ outboards, uint32_t *__restrict__ roots) {
+  merge_body<false>(ents, n_ents, unit, in_cv, out_cv, outboards, roots, 0);
+}
+__global__ __launch_bounds__(256) void b3w_bao_merge_group_kernel(const BatchEnt *__restrict__ ents, uint32_t n_ents, uint64_t unit,
+                                                                  const uint32_t *__restrict__ in_cv, uint32_t *__restrict__ out_cv,
+                                                                  uint8_t *__restrict__ outboards, uint32_t *__restrict__ roots, uint32_t gl) {
+  merge_body<true>(ents, n_ents, unit, in_cv, out_cv, outboards, roots, gl);
 }
 
 // ---- challenged paths ------------------------------------------------------------------------------------------------
@@ -442,6 +513,148 @@ __global__ __launch_bounds__(64) void b3w_sample_plan_batch_kernel(const uint8_t
   for (int k = 0; k < 8; ++k) root[k] = roots[d[4] * 8 + k];
   status[s] = sample_plan_one(len, len ? (len + 1023) / 1024 : 1, reinterpret_cast<const uint32_t *>(obs + d[3]), root, d[0], d[1],
                               chunk_bytes + (uint64_t)s * 1024, recs);
+}
+
+// ---- challenged paths from group outboards ---------------------------------------------------------------------------
+// A group outboard (groups of G = 1 << gl chunks) holds the nodes over more than G chunks, which are the parent nodes of BLAKE3's tree
+// over the file's groups.  The lower part of a chunk's path, inside its group, is recomputed from the group's bytes.
+// One wave takes 64 >> gl samples, lane = one chunk of one sample's group (gl = 6: a sample a wave, gl = 4: four, gl = 0: 64, the
+// lane-per-sample planner above), so no lane hashes two chunks of a group:
+//   1. every lane its chunk's CV into LDS (2 KiB a wave); the lane of the sampled chunk (the sample's leader) writes the leaf records
+//      from the same compressions
+//   2. the in-place merge of b3w_bao_small_kernel over each group's run of slots, no node stored; before each level the leader takes the
+//      half of its path's node that the reference's driver picks by the index bit
+//   3. the stored part of the path top down, node j on lane j mod G of the sample: the root node with ROOT against the root, every other
+//      against its half of the node above; the leader holds the group's CV against its half of the lowest stored node (a file of one
+//      group: the group's ROOT-flagged output against the root)
+//   4. the leader writes the parent records bottom up: the recomputed halves, then the stored nodes'
+
+// the CV of one chunk as chunk_cv computes it, and with rec != NULL the chunk's leaf records (plan_leaf_chunk's words; P = the path length)
+__device__ __forceinline__ void group_chunk(const uint8_t *__restrict__ src, uint32_t bytes, uint64_t c, uint32_t P, uint32_t root,
+                                            uint32_t *__restrict__ rec, uint32_t h[8]) {
+  const uint32_t nb = bytes ? (bytes + 63) / 64 : 1;
+  const bool fast = ((uintptr_t)src & 15) == 0;
+  uint32_t o[8], m[16];
+  iv(h);
+  for (uint32_t j = 0; j < nb; ++j) {
+    const uint32_t bb = bytes - j * 64 < 64 ? bytes - j * 64 : 64;
+    if (bb == 64 && fast) {
+      const uint4 *p = reinterpret_cast<const uint4 *>(src + j * 64);
+      const uint4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
+      m[0] = q0.x; m[1] = q0.y; m[2] = q0.z; m[3] = q0.w; m[4] = q1.x; m[5] = q1.y; m[6] = q1.z; m[7] = q1.w;
+      m[8] = q2.x; m[9] = q2.y; m[10] = q2.z; m[11] = q2.w; m[12] = q3.x; m[13] = q3.y; m[14] = q3.z; m[15] = q3.w;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        uint32_t w = 0;
+        for (int x = 0; x < 4; ++x) { const uint32_t q = k * 4 + x; if (q < bb) w |= (uint32_t)src[j * 64 + q] << (8 * x); }
+        m[k] = w;
+      }
+    }
+    if (rec) {
+      uint32_t *r = rec + j * 32;
+      r[0] = nb; r[1] = j;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) r[2 + k] = h[k];
+      r[10] = (uint32_t)c; r[11] = (uint32_t)(c >> 32);
+      r[12] = P + 1; r[13] = P + 1; r[14] = P;
+#pragma unroll
+      for (int k = 0; k < 16; ++k) r[15 + k] = m[k];
+      r[31] = bb;
+    }
+    const uint32_t d = (j == 0 ? 1u : 0u) | (j == nb - 1 ? 2u | root : 0u);
+    blake3_cv(h, m, (uint32_t)c, (uint32_t)(c >> 32), bb, d, o);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) h[k] = o[k];
+  }
+}
+
+// desc as b3w_sample_plan_batch_kernel's, the outboard offsets those of the group layout; group_bytes: 1024 << gl bytes per sample.
+// status: 0 verified, 1 the group's bytes (any chunk of the group), 2 a stored node or the root, 3 header.
+__global__ __launch_bounds__(64) void b3w_sample_plan_group_kernel(const uint8_t *__restrict__ obs, const uint32_t *__restrict__ roots,
+                                                                   const uint64_t *__restrict__ desc, uint32_t n_samples, uint32_t gl,
+                                                                   const uint8_t *__restrict__ group_bytes, uint32_t *__restrict__ recs,
+                                                                   int32_t *__restrict__ status) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[64 * 8];
+  const uint32_t lane = threadIdx.x, G = 1u << gl, i = lane & (G - 1), base = lane - i;
+  const uint32_t s = blockIdx.x * (64u >> gl) + (lane >> gl);
+  const bool valid = s < n_samples;
+  const uint64_t *d = desc + 5 * (uint64_t)(valid ? s : 0);              // (a wave's lanes past the last sample read sample 0's row and write nothing)
+  const uint64_t c = d[0], len = d[2], n = len ? (len + 1023) / 1024 : 1;
+  const uint64_t first = (c >> gl) << gl, n_groups = (n + G - 1) >> gl;
+  const uint32_t gn = (uint32_t)(n - first < G ? n - first : G), ci = (uint32_t)(c - first);
+  const bool live = valid && i < gn, leader = live && i == ci;
+  const uint32_t P = path_len(c, n), U = path_len(c >> gl, n_groups);     // the whole path, its stored part
+  const uint64_t lc = first + i, off = lc * 1024;
+  const uint32_t bytes = live ? (uint32_t)(len - off < 1024 ? len - off : 1024) : 0;
+  const uint32_t n_blocks = bytes ? (bytes + 63) / 64 : 1;
+  uint32_t *r = recs + d[1] * 32;
+  uint32_t h[8];
+  if (live) {
+    group_chunk(group_bytes + ((uint64_t)s << (10 + gl)) + (uint64_t)i * 1024, bytes, lc, P, n == 1 ? 8u : 0u, leader ? r : nullptr, h);
+    reinterpret_cast<uint4 *>(cv + lane * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
+    reinterpret_cast<uint4 *>(cv + lane * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
+  }
+  // 2. the group's tree; sib: the leader's picks, bottom up
+  uint32_t sib[6 * 8], low = 0;
+  for (uint32_t l = 0; l < gl; ++l) {                                     // (uniform: the workgroup is this one wave)
+    lds_barrier();
+    if (leader) {
+      const uint32_t i0 = (ci >> (l + 1)) << (l + 1), i1 = i0 + (1u << l);
+      if (i1 < gn) {                                                      // (else the leader's subtree waits at this level)
+        const uint32_t *src = cv + (base + (((c >> low) & 1) == 0 ? i1 : i0)) * 8;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) sib[low * 8 + k] = src[k];
+        low++;
+      }
+    }
+    lds_barrier();
+    if (live && (i & ((2u << l) - 1)) == 0 && i + (1u << l) < gn)
+      merge_pair<true>(cv, lane, lane + (1u << l), nullptr, 4u | (n_groups == 1 && (2u << l) >= gn ? 8u : 0u));
+  }
+  lds_barrier();
+  // 3. the stored part, top down
+  const uint32_t *ob = reinterpret_cast<const uint32_t *>(obs + d[3]);
+  uint64_t pos[64], lefts = 0;
+  {
+    uint64_t p = 0, cc = c >> gl, m = n_groups;
+    for (uint32_t j = 0; j < U; ++j) {
+      uint64_t k2 = 1;
+      while (k2 * 2 < m) k2 *= 2;
+      pos[j] = p;
+      if (cc < k2) { lefts |= 1ull << j; p += 1; m = k2; } else { p += k2; cc -= k2; m -= k2; }
+    }
+  }
+  bool node_bad = false;
+  if (valid) {
+    for (uint32_t j = i; j < U; j += G) {
+      const uint32_t *node = ob + 2 + pos[j] * 16;
+      uint32_t mw[16], ivv[8], o[8];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) mw[k] = node[k];
+      iv(ivv);
+      blake3_cv(ivv, mw, 0, 0, 64, 4u | (j == 0 ? 8u : 0u), o);
+      const uint32_t *want = j == 0 ? roots + d[4] * 8 : ob + 2 + pos[j - 1] * 16 + (((lefts >> (j - 1)) & 1) ? 0 : 8);
+      if (!eq8(o, want)) node_bad = true;
+    }
+  }
+  const uint64_t bad_lanes = __ballot(node_bad);
+  if (!leader) return;
+  const uint32_t *want = U == 0 ? roots + d[4] * 8 : ob + 2 + pos[U - 1] * 16 + (((lefts >> (U - 1)) & 1) ? 0 : 8);
+  int32_t st = 0;
+  if (((uint64_t)ob[0] | ((uint64_t)ob[1] << 32)) != len) st = 3;
+  else if ((bad_lanes >> base) & (G == 64 ? ~0ull : (1ull << G) - 1)) st = 2;
+  else if (!eq8(cv + base * 8, want)) st = 1;
+  status[s] = st;
+  // 4. the parent records, bottom up: h is the leader's chunk CV
+  r += (uint64_t)n_blocks * 32;
+  for (uint32_t g = 0; g < P; ++g, r += 32) {
+    const bool bit_left = ((c >> g) & 1) == 0;
+    const uint32_t *m8;
+    if (g < low) m8 = sib + g * 8;
+    else { const uint32_t *node = ob + 2 + pos[U - 1 - (g - low)] * 16; m8 = bit_left ? node + 8 : node; }   // (P = low + U)
+    plan_parent_step(r, h, m8, bit_left, c, n_blocks, P, P - 1 - g);
+  }
 }
 
 uint64_t num_chunks(uint64_t len) { return len ? (len + 1023) / 1024 : 1; }
@@ -616,10 +829,11 @@ uint64_t b3w_bao_batch_scratch_bytes(const uint64_t *host_lens, uint32_t n_files
   return (k.big_wgs + k.groups) * 32;
 }
 
-int32_t b3w_bao_outboard_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, const uint64_t *host_offsets, const uint64_t *host_lens,
-                                      uint32_t n_files, uint8_t *d_outboards, uint32_t *d_roots, void *d_scratch, uint64_t scratch_bytes,
-                                      void *stream) {
+// gl < 0: full outboards, the kernels of ABI 1.2; 0 .. B3W_BAO_MAX_GROUP_LOG: group outboards, their group instantiations
+static int32_t outboard_batch(b3w_ctx *ctx, const uint8_t *d_arena, const uint64_t *host_offsets, const uint64_t *host_lens, uint32_t n_files, int gl,
+                              uint8_t *d_outboards, uint32_t *d_roots, void *d_scratch, uint64_t scratch_bytes, void *stream) {
   if (!ctx) return B3W_E_BAD_ARGUMENT;
+  if (gl > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "bao batch: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
   if (!n_files) return B3W_OK;
   if (!host_offsets || !host_lens || !d_outboards || !d_roots) { ctx->last_error = "bao batch: a null pointer (offsets, lengths, outboards or roots)"; return B3W_E_BAD_ARGUMENT; }
   if ((uintptr_t)d_outboards & 7) { ctx->last_error = "bao batch: d_outboards is not 8-byte aligned"; return B3W_E_BAD_ARGUMENT; }
@@ -641,6 +855,7 @@ int32_t b3w_bao_outboard_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, cons
   uint32_t *h_waves = reinterpret_cast<uint32_t *>(h_tops + k.tops);
   uint32_t i_small = 0, i_waves = 0, fill = 64, i_big = 0, i_merged = 0, i_tops = 0, big_wgs = 0, groups = 0;
   uint64_t ob = 0;
+  const uint32_t sh = gl < 0 ? 0 : (uint32_t)gl;
   for (uint32_t f = 0; f < n_files; ++f) {
     const uint64_t len = host_lens[f], n = num_chunks(len);
     if (n <= 64) {
@@ -656,12 +871,23 @@ int32_t b3w_bao_outboard_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, cons
       big_wgs += tiles;
       if (tiles > 1) groups += grp;
     }
-    ob += b3w_bao_outboard_size(len);
+    ob += 8 + 64 * (((n + ((1ull << sh) - 1)) >> sh) - 1);            // (b3w_bao_outboard_size / b3w_bao_group_outboard_size)
   }
   if (k.small) h_waves[i_waves] = i_small;
   HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)table_bytes, hipMemcpyHostToDevice, st));
   const BatchEnt *d_small = reinterpret_cast<const BatchEnt *>(ctx->d_batch), *d_big = d_small + k.small, *d_merged = d_big + k.big, *d_tops = d_merged + k.merged;
   uint32_t *tile_cv = reinterpret_cast<uint32_t *>(d_scratch), *group_cv = tile_cv + k.big_wgs * 8;
+  if (gl >= 0) {
+    const uint32_t g = (uint32_t)gl;
+    if (k.small) hipLaunchKernelGGL(b3w_bao_small_group_kernel, dim3((uint32_t)k.waves), dim3(64), 0, st, d_arena, d_small, reinterpret_cast<const uint32_t *>(d_tops + k.tops), d_outboards, d_roots, g);
+    if (k.big) hipLaunchKernelGGL(b3w_bao_tile_group_kernel, dim3((uint32_t)k.big_wgs), dim3(B3W_TILE), 0, st, d_arena, d_big, (uint32_t)k.big, d_outboards, d_roots, tile_cv, g);
+    if (k.merged) hipLaunchKernelGGL(b3w_bao_merge_group_kernel, dim3((uint32_t)k.groups), dim3(256), 0, st, d_merged, (uint32_t)k.merged, (uint64_t)B3W_TILE, tile_cv, group_cv, d_outboards, d_roots, g);
+    if (k.tops) hipLaunchKernelGGL(b3w_bao_merge_group_kernel, dim3((uint32_t)k.tops), dim3(256), 0, st, d_tops, (uint32_t)k.tops, (uint64_t)B3W_TILE * B3W_TILE, group_cv, (uint32_t *)nullptr, d_outboards, d_roots, g);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(ctx, e, "bao group batch launch");
+    HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
+    return B3W_OK;
+  }
   if (k.small) hipLaunchKernelGGL(b3w_bao_small_kernel, dim3((uint32_t)k.waves), dim3(64), 0, st, d_arena, d_small, reinterpret_cast<const uint32_t *>(d_tops + k.tops), d_outboards, d_roots);
   if (k.big) hipLaunchKernelGGL(b3w_bao_tile_kernel, dim3((uint32_t)k.big_wgs), dim3(B3W_TILE), 0, st, d_arena, d_big, (uint32_t)k.big, d_outboards, d_roots, tile_cv);
   if (k.merged) hipLaunchKernelGGL(b3w_bao_merge_kernel, dim3((uint32_t)k.groups), dim3(256), 0, st, d_merged, (uint32_t)k.merged, (uint64_t)B3W_TILE, tile_cv, group_cv, d_outboards, d_roots);
@@ -670,6 +896,12 @@ int32_t b3w_bao_outboard_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, cons
   if (e != hipSuccess) return hip_fail(ctx, e, "bao batch launch");
   HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
   return B3W_OK;
+}
+
+int32_t b3w_bao_outboard_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, const uint64_t *host_offsets, const uint64_t *host_lens,
+                                      uint32_t n_files, uint8_t *d_outboards, uint32_t *d_roots, void *d_scratch, uint64_t scratch_bytes,
+                                      void *stream) {
+  return outboard_batch(ctx, d_arena, host_offsets, host_lens, n_files, -1, d_outboards, d_roots, d_scratch, scratch_bytes, stream);
 }
 
 int64_t b3w_sample_rows_batch(const uint64_t *host_lens, uint32_t n_files, const uint32_t *host_files, const uint64_t *host_chunks,
@@ -721,6 +953,74 @@ int32_t b3w_sample_plan_batch_device(b3w_ctx *ctx, const uint64_t *host_lens, ui
                      reinterpret_cast<const uint64_t *>(ctx->d_batch), n_samples, d_chunk_bytes, d_records, d_sample_status);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(ctx, e, "sample plan batch launch");
+  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
+  return B3W_OK;
+}
+
+// ---- group outboards (ABI 1.3) ----------------------------------------------------------------------------------------
+uint64_t b3w_bao_group_outboard_size(uint64_t len, uint32_t group_log) {
+  if (group_log > B3W_BAO_MAX_GROUP_LOG) return 0;
+  const uint64_t G1 = (1ull << group_log) - 1;
+  return 8 + 64 * (((num_chunks(len) + G1) >> group_log) - 1);
+}
+
+uint64_t b3w_bao_group_batch_layout(const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, uint64_t *ob_first) {
+  if (!ob_first || (!host_lens && n_files) || group_log > B3W_BAO_MAX_GROUP_LOG) return 0;
+  uint64_t at = 0;
+  for (uint32_t f = 0; f < n_files; ++f) { ob_first[f] = at; at += b3w_bao_group_outboard_size(host_lens[f], group_log); }
+  ob_first[n_files] = at;
+  return at;
+}
+
+int32_t b3w_bao_group_path_nodes(uint64_t chunk, uint64_t n_chunks, uint32_t group_log, uint64_t *out_index, uint32_t *out_count) {
+  if (group_log > B3W_BAO_MAX_GROUP_LOG || !n_chunks || chunk >= n_chunks) return B3W_E_BAD_ARGUMENT;
+  return b3w_bao_path_nodes(chunk >> group_log, (n_chunks + (1ull << group_log) - 1) >> group_log, out_index, out_count);
+}
+
+int32_t b3w_bao_group_outboard_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, const uint64_t *host_offsets, const uint64_t *host_lens,
+                                            uint32_t n_files, uint32_t group_log, uint8_t *d_outboards, uint32_t *d_roots, void *d_scratch,
+                                            uint64_t scratch_bytes, void *stream) {
+  if (ctx && group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "bao group batch: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
+  return outboard_batch(ctx, d_arena, host_offsets, host_lens, n_files, (int)group_log, d_outboards, d_roots, d_scratch, scratch_bytes, stream);
+}
+
+int32_t b3w_sample_plan_group_batch_device(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, uint32_t group_log,
+                                           const uint8_t *d_group_outboards, const uint32_t *d_roots, const uint32_t *host_files,
+                                           const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_group_bytes, uint32_t *d_records,
+                                           int32_t *d_sample_status, void *stream) {
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  if (ctx->desc.kind == B3W_KIND_COMP) { ctx->last_error = "sampled paths plan the nova step circuits' records"; return B3W_E_BAD_ARGUMENT; }
+  if (group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "sample plan group batch: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
+  if (!n_samples) return B3W_OK;
+  if (!host_lens || !d_group_outboards || !d_roots || !host_files || !host_chunks || !d_group_bytes || !d_records || !d_sample_status) {
+    ctx->last_error = "sample plan group batch: a null pointer"; return B3W_E_BAD_ARGUMENT;
+  }
+  for (uint32_t s = 0; s < n_samples; ++s) {
+    if (host_files[s] >= n_files) { ctx->last_error = "a sampled file index is not below the file count"; return B3W_E_BAD_ARGUMENT; }
+    if (host_chunks[s] >= num_chunks(host_lens[host_files[s]])) { ctx->last_error = "a sampled chunk index is not below its file's chunk count"; return B3W_E_BAD_ARGUMENT; }
+  }
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  // staging as b3w_sample_plan_batch_device's: the per-sample table {chunk, first row, length, outboard offset, file}, then the group layout
+  const uint64_t desc_bytes = (uint64_t)n_samples * 40;
+  const int32_t rc = batch_staging(ctx, desc_bytes + ((uint64_t)n_files + 1) * 8);
+  if (rc) return rc;
+  uint64_t *desc = reinterpret_cast<uint64_t *>(ctx->h_batch), *ob_first = desc + 5 * (uint64_t)n_samples;
+  (void)b3w_bao_group_batch_layout(host_lens, n_files, group_log, ob_first);
+  uint64_t row = 0;
+  for (uint32_t s = 0; s < n_samples; ++s) {
+    const uint32_t f = host_files[s];
+    const uint64_t len = host_lens[f];
+    uint64_t *d = desc + 5 * (uint64_t)s;
+    d[0] = host_chunks[s]; d[1] = row; d[2] = len; d[3] = ob_first[f]; d[4] = f;
+    row += chunk_blocks(len, host_chunks[s]) + b3w_plan_path_len(host_chunks[s], num_chunks(len));
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)desc_bytes, hipMemcpyHostToDevice, st));
+  const uint32_t per_wave = 64u >> group_log;
+  hipLaunchKernelGGL(b3w_sample_plan_group_kernel, dim3((n_samples + per_wave - 1) / per_wave), dim3(64), 0, st, d_group_outboards, d_roots,
+                     reinterpret_cast<const uint64_t *>(ctx->d_batch), n_samples, group_log, d_group_bytes, d_records, d_sample_status);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(ctx, e, "sample plan group batch launch");
   HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
   return B3W_OK;
 }

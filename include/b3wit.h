@@ -624,6 +624,40 @@ int32_t b3w_sample_plan_batch_device(b3w_ctx *ctx, const uint64_t *host_lens, ui
                                      uint32_t n_samples, const uint8_t *d_chunk_bytes, uint32_t *d_records,
                                      int32_t *d_sample_status, void *stream);
 
+/* ---- outboards over chunk groups (ABI 1.3) ------------------------------------------------------------------
+ * The full outboard costs 64 bytes per KiB of file.  A GROUP outboard is built over chunk groups of G = 2^group_log chunks: every
+ * node of BLAKE3's tree over more than G chunks splits at a multiple of G, so those nodes are the parent nodes of BLAKE3's tree
+ * shape over the file's n_groups = ceil(n_chunks / G) groups.  The group outboard = the 8-byte LE length, then those n_groups - 1
+ * nodes in pre-order, 64 bytes each: the full outboard with every node over at most G chunks left out, in the same order (1 / G of
+ * its size; a file of at most G chunks: the header alone).  A chunk's path = its group's path in the tree over groups (stored),
+ * then the path of chunk c - first inside a BLAKE3 tree over the group's own min(G, n_chunks - first) chunks, first = c / G * G
+ * (recomputed from the group's bytes at challenge time).  group_log = 0 is the full outboard.  A group_log above
+ * B3W_BAO_MAX_GROUP_LOG is refused with B3W_E_BAD_ARGUMENT (the host-only size / layout calls return 0). */
+#define B3W_BAO_MAX_GROUP_LOG 6 /* a group fits the lanes of one wave */
+/* Host only.  8 + 64 * (n_groups - 1). */
+uint64_t b3w_bao_group_outboard_size(uint64_t preimage_len, uint32_t group_log);
+/* Host only.  b3w_bao_batch_layout for group outboards: packed in file order, every entry's start a multiple of 8. */
+uint64_t b3w_bao_group_batch_layout(const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, uint64_t *ob_first);
+/* Host only.  The indices in the group outboard of the stored part of the chunk's path, root first (out_index: room for 64). */
+int32_t b3w_bao_group_path_nodes(uint64_t chunk, uint64_t n_chunks, uint32_t group_log, uint64_t *out_index, uint32_t *out_count);
+/* b3w_bao_outboard_batch_device writing group outboards (packed as b3w_bao_group_batch_layout says): the same contract in every
+ * other respect — the same arena rules, scratch (b3w_bao_batch_scratch_bytes), launch count (at most four), roots left on the
+ * device, nothing written outside a file's own entry. */
+int32_t b3w_bao_group_outboard_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, const uint64_t *host_offsets,
+                                            const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, uint8_t *d_outboards,
+                                            uint32_t *d_roots, void *d_scratch, uint64_t scratch_bytes, void *stream);
+/* b3w_sample_plan_batch_device from group outboards.  d_group_bytes: 1024 << group_log bytes per sample, the bytes of the group
+ * that holds the sampled chunk (file bytes from (chunk >> group_log << group_log) * 1024 on; bytes past the file's end ignored).
+ * Rows are b3w_sample_rows_batch's (they do not depend on group_log), and the records are word for word those
+ * b3w_sample_plan_batch_device writes from the full outboard.  d_sample_status[s]: 0 verified; 1 the GROUP's bytes do not match —
+ * any byte of the sampled chunk's group, not only the sampled chunk's own, since the group's recomputed CV is what is held against
+ * the stored path; 2 a stored node or the root does not match; 3 the header is not the file's length.  Records are written either
+ * way; a bad sample touches no other.  n_samples == 0: a no-op.  Nova contexts only. */
+int32_t b3w_sample_plan_group_batch_device(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, uint32_t group_log,
+                                           const uint8_t *d_group_outboards, const uint32_t *d_roots, const uint32_t *host_files,
+                                           const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_group_bytes,
+                                           uint32_t *d_records, int32_t *d_sample_status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
