@@ -6,7 +6,9 @@ records of the challenged chunk paths from the outboard and those chunks' bytes 
 prove_samples() runs their witnesses, constraint checks and commitments through the batch calls, batch by batch.  outboard_batch(),
 plan_samples_batch() and prove_samples_batch() do the same for a whole batch of files of one device arena at once;
 outboard_groups_batch(), plan_samples_groups_batch() and prove_samples_groups_batch() keep the outboards over chunk groups of
-2^group_log chunks, 2^group_log times smaller, and recompute the levels inside a group from the group's bytes.  The records are
+2^group_log chunks, 2^group_log times smaller, and recompute the levels inside a group from the group's bytes.  slices_batch() extracts the standard bao slices of challenged chunks from either kind
+of outboard and plan_samples_slices() / prove_samples_slices() plan and prove from slices alone, so the prover need not hold the
+outboards (decode_slice(): the host decoder).  The records are
 word for word those the chain planner writes for the same chunks (ChainPlanner.plan), so every step is the reference's
 prove_chunk_hash step (rust_fold/src/main.rs:41-203 over hash_with_path's slice, rust_fold/src/blake3_hash.rs:17-93)."""
 import ctypes
@@ -373,3 +375,77 @@ def prove_samples_groups_batch(ctx, d_group_outboards, lens, d_roots, files, chu
     s = _stream(stream)
     out = plan_samples_groups_batch(ctx, d_group_outboards, lens, d_roots, files, chunks, d_group_bytes, group_log, stream=s)
     return _prove_planned(ctx, out, batch_steps, consumer, commit_key, r1cs, s)
+
+
+# ---- slices: the provider extracts, the prover plans from them alone ------------------------------------------------------
+def slice_size(length, chunk):
+    """8 + 64 path_len + the chunk's byte count: the bao slice of one chunk"""
+    size = lib().b3w_bao_slice_size(length, chunk)
+    if not size:
+        raise B3WError(100, "b3w_bao_slice_size: the chunk index is not below the chunk count")
+    return size
+
+
+def slice_layout(lens, files, chunks):
+    """-> slice_first (numpy uint64 [n_samples + 1]): sample s's slice is the slice_size(lens[files[s]], chunks[s]) bytes from
+    slice_first[s] of the packed slices (every start 8 modulo 16; what lies between slices is padding); the last entry is the total"""
+    ln, ch = _u64(lens), _u64(chunks)
+    fi = np.ascontiguousarray(files, dtype=np.uint32)
+    assert fi.size == ch.size
+    sf = np.zeros(ch.size + 1, dtype=np.uint64)
+    total = lib().b3w_bao_slice_batch_layout(ln.ctypes.data, ln.size, fi.ctypes.data, ch.ctypes.data, ch.size, sf.ctypes.data)
+    if total < 0:
+        raise B3WError(-total, "b3w_bao_slice_batch_layout: a file index is not below the file count, or a chunk index not below its file's chunk count")
+    return sf
+
+
+def slices_batch(ctx, d_outboards, lens, files, chunks, d_bytes, group_log=0, stream=0):
+    """The provider's side: the standard bao slices of samples (files[s], chunks[s]) in one launch.  group_log = 0: d_outboards as
+    outboard_batch returns them, d_bytes as chunk_bytes_batch; group_log 1 .. 6: outboard_groups_batch's outboards and
+    group_bytes_batch's bytes — the same slices.  Returns a dict: slices (uint8 CUDA tensor, packed), slice_first (slice_layout)."""
+    ln, ch = _u64(lens), _u64(chunks)
+    fi = np.ascontiguousarray(files, dtype=np.uint32)
+    if not 0 <= group_log <= MAX_GROUP_LOG:
+        raise B3WError(100, f"group_log {group_log} is not in 0 .. {MAX_GROUP_LOG}")
+    sf = slice_layout(ln, fi, ch)
+    assert d_bytes.is_cuda and d_bytes.dtype == torch.uint8 and d_bytes.is_contiguous() and d_bytes.numel() >= ch.size * (1024 << group_log)
+    d_slices = torch.zeros(int(sf[-1]), dtype=torch.uint8, device=d_outboards.device)
+    _chk(ctx, lib().b3w_bao_slice_batch_device(ctx.handle, ln.ctypes.data, ln.size, group_log, d_outboards.data_ptr(), fi.ctypes.data, ch.ctypes.data,
+                                               ch.size, d_bytes.data_ptr(), d_slices.data_ptr(), _stream(stream)), "b3w_bao_slice_batch_device")
+    return dict(slices=d_slices, slice_first=sf)
+
+
+def plan_samples_slices(ctx, lens, d_roots, files, chunks, d_slices, stream=0):
+    """The prover's side: plan_samples_batch from the slices alone (slices_batch's tensor, or slices received and packed as
+    slice_layout says) and the files' roots on the device — no outboard.  Returns the dict plan_samples_batch returns."""
+    L = lib()
+    ln, ch = _u64(lens), _u64(chunks)
+    fi = np.ascontiguousarray(files, dtype=np.uint32)
+    rf = sample_rows_batch(ln, fi, ch)
+    sf = slice_layout(ln, fi, ch)
+    dev = d_slices.device
+    assert d_roots.is_cuda and d_roots.is_contiguous() and d_roots.numel() >= ln.size * 8
+    assert d_slices.is_cuda and d_slices.dtype == torch.uint8 and d_slices.is_contiguous() and d_slices.numel() >= int(sf[-1])
+    recs = torch.empty((int(rf[-1]), 32), dtype=torch.int32, device=dev)
+    st = torch.full((ch.size,), -1, dtype=torch.int32, device=dev)
+    _chk(ctx, L.b3w_sample_plan_slices_device(ctx.handle, ln.ctypes.data, ln.size, d_roots.data_ptr(), fi.ctypes.data, ch.ctypes.data, ch.size,
+                                              d_slices.data_ptr(), recs.data_ptr(), st.data_ptr(), _stream(stream)), "b3w_sample_plan_slices_device")
+    provable = np.array([bool(L.b3w_chain_path_provable(int(c), num_chunks(int(ln[f])))) for f, c in zip(fi, ch)], dtype=bool)
+    return dict(records=recs, row_first=rf, sample_status=st.cpu().numpy(), provable=provable)
+
+
+def prove_samples_slices(ctx, lens, d_roots, files, chunks, d_slices, batch_steps=4096, consumer=None, commit_key=None, r1cs=None, stream=0):
+    """prove_samples_batch over plan_samples_slices' plan"""
+    s = _stream(stream)
+    out = plan_samples_slices(ctx, lens, d_roots, files, chunks, d_slices, stream=s)
+    return _prove_planned(ctx, out, batch_steps, consumer, commit_key, r1cs, s)
+
+
+def decode_slice(slice_bytes, length, chunk, root):
+    """bao's decoder for one slice on the host -> (status as STATUS, the chunk's bytes — empty unless status is 0)"""
+    sl = bytes(slice_bytes)
+    rw = np.ascontiguousarray(root, dtype=np.uint32)
+    out = ctypes.create_string_buffer(1024)
+    cnt, st = ctypes.c_uint32(), ctypes.c_int32()
+    _chk(None, lib().b3w_bao_slice_decode(sl, len(sl), length, chunk, rw.ctypes.data, out, ctypes.byref(cnt), ctypes.byref(st)), "b3w_bao_slice_decode")
+    return st.value, out.raw[:cnt.value]

@@ -21,6 +21,11 @@
 //                            most a group's chunks computed and not stored ("outboards over chunk groups" in b3wit.h)
 //   b3w_sample_plan_group_kernel  a challenged chunk from a group outboard and its group's bytes: a lane per chunk of the group, the group's
 //                            tree merged in LDS, the stored part of the path verified across the sample's lanes, the same records
+//   b3w_bao_slice_kernel     the bao slices of challenged chunks gathered from full outboards, 16 lanes a sample
+//   b3w_bao_slice_group_kernel  the same standard slices from GROUP outboards: the group planner's lanes and LDS merge, every node of the
+//                            path inside the group stored whole before its level's merge
+//   b3w_sample_plan_slices_kernel  the step records planned from slices alone (no outboard): a sample over several lanes, the path's nodes
+//                            checked side by side, the parent records without the running-h chain where that chain is redundant
 #include "b3w_internal.h"
 #include "b3w_blake3_dev.h"
 
@@ -657,6 +662,229 @@ __global__ __launch_bounds__(64) void b3w_sample_plan_group_kernel(const uint8_t
   }
 }
 
+// ---- bao slices (ABI 1.4) ------------------------------------------------------------------------------------------------
+// slice of chunk c = header (8) || the P nodes of c's path root first (64 each) || the chunk's bytes.  Packed slices start at 8 modulo 16
+// (b3w_bao_slice_batch_layout), so the nodes and the chunk's bytes, which follow the 8-byte header, lie on 16-byte boundaries.
+// desc of the two extraction kernels: desc[5 s ..] = chunk, the slice's byte offset in `slices`, the file's length, the byte offset of its
+// outboard in `obs`, the file.
+
+// 16 bytes from src (8-byte aligned: a node's quarter in an outboard, or chunk bytes) to dst (16-byte aligned)
+__device__ __forceinline__ void move16(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src) {
+  uint4 v;
+  if (((uintptr_t)src & 15) == 0) {
+    v = *reinterpret_cast<const uint4 *>(src);
+  } else {
+    const uint2 a = reinterpret_cast<const uint2 *>(src)[0], b = reinterpret_cast<const uint2 *>(src)[1];
+    v = make_uint4(a.x, a.y, b.x, b.y);
+  }
+  *reinterpret_cast<uint4 *>(dst) = v;
+}
+
+// the sampled chunk's `bytes` bytes to dst (16-byte aligned), lane t of T: whole 16-byte pieces where src is 8-byte aligned, the ragged
+// tail (or everything, from an odd src) byte-wise
+__device__ __forceinline__ void move_chunk(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint32_t bytes, uint32_t t, uint32_t T) {
+  uint32_t whole = 0;
+  if (((uintptr_t)src & 7) == 0) {
+    whole = bytes & ~15u;
+    for (uint32_t o = t * 16; o < whole; o += T * 16) move16(dst + o, src + o);
+  }
+  for (uint32_t o = whole + t; o < bytes; o += T) dst[o] = src[o];
+}
+
+// from full outboards: a gather, 16 lanes a sample.  Every lane walks the path (integer work); node j is moved by the four lanes t with
+// t / 4 == j mod 4, a quarter each, then all 16 move the chunk's bytes.
+constexpr uint32_t SLICE_LANES = 16;
+__global__ __launch_bounds__(256) void b3w_bao_slice_kernel(const uint8_t *__restrict__ obs, const uint64_t *__restrict__ desc, uint32_t n_samples,
+                                                            const uint8_t *__restrict__ chunk_bytes, uint8_t *__restrict__ slices) {
+  const uint32_t tid = blockIdx.x * 256 + threadIdx.x, s = tid / SLICE_LANES, t = tid % SLICE_LANES;
+  if (s >= n_samples) return;
+  const uint64_t *d = desc + 5 * (uint64_t)s;
+  const uint64_t c = d[0], len = d[2], n = len ? (len + 1023) / 1024 : 1;
+  const uint8_t *ob = obs + d[3];
+  uint8_t *sl = slices + d[1];
+  const uint32_t P = path_len(c, n);
+  if (t == 0) *reinterpret_cast<uint2 *>(sl) = *reinterpret_cast<const uint2 *>(ob);          // the header as the outboard has it
+  uint64_t p = 0, cc = c, m = n;
+  for (uint32_t j = 0; j < P; ++j) {
+    if ((j & 3) == (t >> 2)) move16(sl + 8 + 64 * (uint64_t)j + (t & 3) * 16, ob + 8 + p * 64 + (t & 3) * 16);
+    uint64_t k2 = 1;
+    while (k2 * 2 < m) k2 *= 2;
+    if (cc < k2) { p += 1; m = k2; } else { p += k2; cc -= k2; m -= k2; }
+  }
+  const uint64_t off = c * 1024;
+  move_chunk(sl + 8 + 64 * (uint64_t)P, chunk_bytes + (uint64_t)s * 1024, (uint32_t)(len - off < 1024 ? len - off : 1024), t, SLICE_LANES);
+}
+
+// from group outboards: phases 1 and 2 of b3w_sample_plan_group_kernel (lane = one chunk of one sample's group, the chunk CVs into LDS, the
+// in-place merge).  Before the merge of level l the node of the sampled chunk's path at that level, where it exists, is cv[i0] || cv[i1]:
+// the first lanes of the sample store it whole to its place in the slice (the k-th that exists bottom up at node P - 1 - k).  Then the U
+// stored nodes from the group outboard to the slice's first U places, the header and the sampled chunk's bytes, over the sample's G lanes.
+__global__ __launch_bounds__(64) void b3w_bao_slice_group_kernel(const uint8_t *__restrict__ obs, const uint64_t *__restrict__ desc, uint32_t n_samples,
+                                                                 uint32_t gl, const uint8_t *__restrict__ group_bytes, uint8_t *__restrict__ slices) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[64 * 8];
+  const uint32_t lane = threadIdx.x, G = 1u << gl, i = lane & (G - 1), base = lane - i;
+  const uint32_t s = blockIdx.x * (64u >> gl) + (lane >> gl);
+  const bool valid = s < n_samples;
+  const uint64_t *d = desc + 5 * (uint64_t)(valid ? s : 0);              // (a wave's lanes past the last sample read sample 0's row and write nothing)
+  const uint64_t c = d[0], len = d[2], n = len ? (len + 1023) / 1024 : 1;
+  const uint64_t first = (c >> gl) << gl, n_groups = (n + G - 1) >> gl;
+  const uint32_t gn = (uint32_t)(n - first < G ? n - first : G), ci = (uint32_t)(c - first);
+  const bool live = valid && i < gn;
+  const uint32_t P = path_len(c, n), U = path_len(c >> gl, n_groups);     // the whole path, its stored part
+  const uint64_t lc = first + i, off = lc * 1024;
+  const uint32_t bytes = live ? (uint32_t)(len - off < 1024 ? len - off : 1024) : 0;
+  const uint8_t *gb = group_bytes + ((uint64_t)s << (10 + gl));
+  uint8_t *sl = slices + d[1];
+  if (live) {
+    uint32_t h[8];
+    group_chunk(gb + (uint64_t)i * 1024, bytes, lc, P, n == 1 ? 8u : 0u, nullptr, h);
+    reinterpret_cast<uint4 *>(cv + lane * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
+    reinterpret_cast<uint4 *>(cv + lane * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
+  }
+  uint32_t low = 0;
+  for (uint32_t l = 0; l < gl; ++l) {                                     // (uniform: the workgroup is this one wave)
+    lds_barrier();
+    const uint32_t i0 = (ci >> (l + 1)) << (l + 1), i1 = i0 + (1u << l);
+    if (i1 < gn) {                                                        // (else the path's subtree waits at this level: no node)
+      if (valid && low < P)
+        for (uint32_t q = i; q < 4; q += G)                               // quarter q of the node: the halves of cv[i0], then of cv[i1]
+          *reinterpret_cast<uint4 *>(sl + 8 + 64 * (uint64_t)(P - 1 - low) + q * 16) = reinterpret_cast<const uint4 *>(cv + (base + (q < 2 ? i0 : i1)) * 8)[q & 1];
+      low++;
+    }
+    lds_barrier();
+    if (live && (i & ((2u << l) - 1)) == 0 && i + (1u << l) < gn)
+      merge_pair<true>(cv, lane, lane + (1u << l), nullptr, 4u | (n_groups == 1 && (2u << l) >= gn ? 8u : 0u));
+  }
+  lds_barrier();
+  if (!valid) return;
+  const uint8_t *ob = obs + d[3];
+  if (i == 0) *reinterpret_cast<uint2 *>(sl) = *reinterpret_cast<const uint2 *>(ob);
+  uint64_t p = 0, cc = c >> gl, m = n_groups;
+  for (uint32_t j = 0; j < U; ++j) {                                      // (P = low + U: the stored nodes fill the places in front)
+#pragma unroll
+    for (uint32_t q = 0; q < 4; ++q)
+      if (((j * 4 + q) & (G - 1)) == i) move16(sl + 8 + 64 * (uint64_t)j + q * 16, ob + 8 + p * 64 + q * 16);
+    uint64_t k2 = 1;
+    while (k2 * 2 < m) k2 *= 2;
+    if (cc < k2) { p += 1; m = k2; } else { p += k2; cc -= k2; m -= k2; }
+  }
+  const uint64_t offc = c * 1024;
+  move_chunk(sl + 8 + 64 * (uint64_t)P, gb + (uint64_t)ci * 1024, (uint32_t)(len - offc < 1024 ? len - offc : 1024), i, G);
+}
+
+// ---- challenged paths from slices ------------------------------------------------------------------------------------
+// The prover's side: the slice is all there is.  K lanes a sample (64 / K samples a wave):
+//   1. lane 0 of the sample (the leader) runs the chunk's blocks and writes the leaf records (plan_leaf_chunk on the slice's bytes)
+//   2. the P nodes lie side by side, so their checks do not wait for each other: node j on lane j mod K — node 0 with ROOT against the
+//      file's root, node j against its half of node j - 1 — and one ballot for the verdict; the leader holds the chunk's CV against its half
+//      of node P - 1 (P == 0: its ROOT-flagged output against the root)
+//   3. the parent records.  Record g carries the running value h of the reference's fold, which follows the index bits: P more compressions
+//      one after the other (plan_parent_step, the leader).  Where the sample verified and its path is provable (the index bits are the
+//      tree's own directions) that chain is redundant: every node hashed to its half of the node above, so h at height g IS the on-path
+//      half of node P - 1 - g, and the K lanes write record g = t, t + K, ... straight from the nodes.  Any other sample — a failed check,
+//      a path of an incomplete tree that is not provable — gets the chained words.
+// desc[5 s ..] = chunk, first row, the file's length, the slice's byte offset in `slices`, the file.
+
+// the words of plan_parent_step's record from a known h
+__device__ __forceinline__ void parent_record(uint32_t *__restrict__ r, const uint32_t *h, const uint32_t *m8, uint64_t c, uint32_t n_blocks, uint32_t plen,
+                                              uint32_t depth) {
+  r[0] = n_blocks; r[1] = n_blocks;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) r[2 + k] = h[k];
+  r[10] = (uint32_t)c; r[11] = (uint32_t)(c >> 32);
+  r[12] = plen + 1; r[13] = plen + 1; r[14] = depth;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { r[15 + k] = m8[k]; r[23 + k] = 0; }
+  r[31] = 64;
+}
+
+template <int K>
+__global__ __launch_bounds__(64) void b3w_sample_plan_slices_kernel(const uint8_t *__restrict__ slices, const uint32_t *__restrict__ roots,
+                                                                    const uint64_t *__restrict__ desc, uint32_t n_samples, uint32_t always_chain,
+                                                                    uint32_t *__restrict__ recs, int32_t *__restrict__ status) {
+  const uint32_t lane = threadIdx.x, t = lane & (K - 1), base = lane - t;
+  const uint32_t s = blockIdx.x * (64u / K) + lane / K;
+  const bool valid = s < n_samples, leader = valid && t == 0;
+  const uint64_t *d = desc + 5 * (uint64_t)(valid ? s : 0);              // (lanes past the last sample read sample 0's row and write nothing)
+  const uint64_t c = d[0], len = d[2], n = len ? (len + 1023) / 1024 : 1;
+  const uint8_t *sl = slices + d[3];
+  const uint32_t *nodes = reinterpret_cast<const uint32_t *>(sl + 8);     // (16-byte aligned)
+  const uint32_t P = path_len(c, n);
+  const uint64_t off = c * 1024;
+  const uint32_t bytes = (uint32_t)(len - off < 1024 ? len - off : 1024);
+  const uint32_t n_blocks = bytes ? (bytes + 63) / 64 : 1;
+  uint32_t *r = recs + d[1] * 32;
+  uint32_t h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (leader) plan_leaf_chunk(sl + 8 + 64 * (uint64_t)P, bytes, c, P, r, h);
+  // the tree's own directions, root first (bit j: left at node j), and whether the index bits spell them (b3w_plan_path_provable)
+  uint64_t lefts = 0;
+  bool provable = true;
+  {
+    uint64_t cc = c, m = n;
+    for (uint32_t j = 0; j < P; ++j) {
+      uint64_t k2 = 1;
+      while (k2 * 2 < m) k2 *= 2;
+      const bool left = cc < k2;
+      if (left) { lefts |= 1ull << j; m = k2; } else { cc -= k2; m -= k2; }
+      if (left != (((c >> (P - 1 - j)) & 1) == 0)) provable = false;
+    }
+  }
+  const uint32_t *root8 = roots + d[4] * 8;
+  bool node_bad = false;
+  if (valid) {
+    for (uint32_t j = t; j < P; j += K) {
+      const uint4 *q = reinterpret_cast<const uint4 *>(nodes + j * 16);
+      const uint4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
+      const uint32_t mw[16] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w};
+      uint32_t ivv[8], o[8];
+      iv(ivv);
+      blake3_cv(ivv, mw, 0, 0, 64, 4u | (j == 0 ? 8u : 0u), o);
+      const uint32_t *want = j == 0 ? root8 : nodes + (j - 1) * 16 + (((lefts >> (j - 1)) & 1) ? 0 : 8);
+      if (!eq8(o, want)) node_bad = true;
+    }
+  }
+  const uint64_t bad_lanes = __ballot(node_bad);
+  int32_t st = 0;
+  if (leader) {
+    const uint32_t *want = P == 0 ? root8 : nodes + (P - 1) * 16 + (((lefts >> (P - 1)) & 1) ? 0 : 8);
+    const uint32_t *hd = reinterpret_cast<const uint32_t *>(sl);
+    if (((uint64_t)hd[0] | ((uint64_t)hd[1] << 32)) != len) st = 3;
+    else if ((bad_lanes >> base) & ((1ull << K) - 1)) st = 2;
+    else if (!eq8(h, want)) st = 1;                                       // (one chunk: its ROOT-flagged output against the root)
+    status[s] = st;
+  }
+  if (K > 1) st = __shfl(st, (int)base);
+  r += (uint64_t)n_blocks * 32;
+  if (always_chain || st != 0 || !provable) {
+    if (!leader) return;
+    for (uint32_t g = 0; g < P; ++g, r += 32) {
+      const uint32_t *node = nodes + (P - 1 - g) * 16;
+      const bool bit_left = ((c >> g) & 1) == 0;
+      plan_parent_step(r, h, bit_left ? node + 8 : node, bit_left, c, n_blocks, P, P - 1 - g);
+    }
+    return;
+  }
+  if (!valid) return;
+  for (uint32_t g = t; g < P; g += K) {                                   // (g == 0 is the leader's: h is the chunk's CV)
+    const uint32_t *node = nodes + (P - 1 - g) * 16;
+    const bool bit_left = ((c >> g) & 1) == 0;
+    parent_record(r + (uint64_t)g * 32, g == 0 ? h : (bit_left ? node : node + 8), bit_left ? node + 8 : node, c, n_blocks, P, P - 1 - g);
+  }
+}
+
+// the CV of a chunk on the host (chunk_cv's loop over blake3_cv): b3w_bao_slice_decode
+void host_chunk_cv(const uint8_t *src, uint32_t bytes, uint64_t c, uint32_t root, uint32_t h[8]) {
+  const uint32_t nb = bytes ? (bytes + 63) / 64 : 1;
+  iv(h);
+  for (uint32_t j = 0; j < nb; ++j) {
+    const uint32_t bb = bytes - j * 64 < 64 ? bytes - j * 64 : 64;
+    uint32_t m[16] = {}, o[8];
+    for (uint32_t q = 0; q < bb; ++q) m[q / 4] |= (uint32_t)src[j * 64 + q] << (8 * (q & 3));
+    blake3_cv(h, m, (uint32_t)c, (uint32_t)(c >> 32), bb, (j == 0 ? 1u : 0u) | (j == nb - 1 ? 2u | root : 0u), o);
+    for (int k = 0; k < 8; ++k) h[k] = o[k];
+  }
+}
+
 uint64_t num_chunks(uint64_t len) { return len ? (len + 1023) / 1024 : 1; }
 uint32_t chunk_blocks(uint64_t len, uint64_t c) {
   const uint64_t off = c * 1024, bytes = len - off < 1024 ? len - off : 1024;
@@ -1021,6 +1249,162 @@ int32_t b3w_sample_plan_group_batch_device(b3w_ctx *ctx, const uint64_t *host_le
                      reinterpret_cast<const uint64_t *>(ctx->d_batch), n_samples, group_log, d_group_bytes, d_records, d_sample_status);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(ctx, e, "sample plan group batch launch");
+  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
+  return B3W_OK;
+}
+
+// ---- bao slices (ABI 1.4) ------------------------------------------------------------------------------------------------
+uint64_t b3w_bao_slice_size(uint64_t len, uint64_t chunk) {
+  const uint64_t n = num_chunks(len);
+  if (chunk >= n) return 0;
+  const uint64_t off = chunk * 1024;
+  return 8 + 64ull * path_len(chunk, n) + (len - off < 1024 ? len - off : 1024);
+}
+
+// the next slice start at or behind byte `end`: 8 modulo 16
+static uint64_t slice_start(uint64_t end) { return ((end + 7) & ~15ull) + 8; }
+
+int64_t b3w_bao_slice_batch_layout(const uint64_t *host_lens, uint32_t n_files, const uint32_t *host_files, const uint64_t *host_chunks,
+                                   uint32_t n_samples, uint64_t *slice_first) {
+  if (!slice_first || (n_samples && (!host_lens || !host_files || !host_chunks))) return -B3W_E_BAD_ARGUMENT;
+  for (uint32_t s = 0; s < n_samples; ++s)
+    if (host_files[s] >= n_files || host_chunks[s] >= num_chunks(host_lens[host_files[s]])) return -B3W_E_BAD_ARGUMENT;
+  uint64_t at = slice_start(0);
+  for (uint32_t s = 0; s < n_samples; ++s) {
+    slice_first[s] = at;
+    at = slice_start(at + b3w_bao_slice_size(host_lens[host_files[s]], host_chunks[s]));
+  }
+  slice_first[n_samples] = at;
+  return (int64_t)at;
+}
+
+int32_t b3w_bao_slice_decode(const uint8_t *slice, uint64_t slice_len, uint64_t len, uint64_t chunk, const uint32_t *root, uint8_t *out_chunk,
+                             uint32_t *out_bytes, int32_t *out_status) {
+  const uint64_t n = num_chunks(len);
+  if (!slice || !root || !out_status || chunk >= n || slice_len != b3w_bao_slice_size(len, chunk)) return B3W_E_BAD_ARGUMENT;
+  uint64_t hdr = 0;
+  for (int k = 0; k < 8; ++k) hdr |= (uint64_t)slice[k] << (8 * k);
+  int32_t st = hdr != len ? 3 : 0;
+  uint32_t want[8];
+  for (int k = 0; k < 8; ++k) want[k] = root[k];
+  const uint32_t P = path_len(chunk, n);
+  uint64_t cc = chunk, m = n;
+  for (uint32_t i = 0; i < P; ++i) {                     // top down, as sample_plan_one
+    uint32_t mw[16], ivv[8], o[8];
+    for (int k = 0; k < 16; ++k) {
+      const uint8_t *b = slice + 8 + 64ull * i + 4 * k;
+      mw[k] = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
+    }
+    iv(ivv);
+    blake3_cv(ivv, mw, 0, 0, 64, 4u | (i == 0 ? 8u : 0u), o);
+    if (memcmp(o, want, 32) != 0 && st == 0) st = 2;
+    uint64_t k2 = 1;
+    while (k2 * 2 < m) k2 *= 2;
+    const bool left = cc < k2;
+    for (int k = 0; k < 8; ++k) want[k] = left ? mw[k] : mw[8 + k];
+    if (left) m = k2; else { cc -= k2; m -= k2; }
+  }
+  const uint32_t bytes = (uint32_t)(slice_len - 8 - 64ull * P);
+  uint32_t h[8];
+  host_chunk_cv(slice + 8 + 64ull * P, bytes, chunk, n == 1 ? 8u : 0u, h);
+  if (memcmp(h, want, 32) != 0 && st == 0) st = 1;
+  *out_status = st;
+  if (out_bytes) *out_bytes = st == 0 ? bytes : 0;       // (the bytes are handed out only where they verified, as bao's decoder does)
+  if (out_chunk && st == 0 && bytes) memcpy(out_chunk, slice + 8 + 64ull * P, bytes);
+  return B3W_OK;
+}
+
+// the checks the two device calls share; the sample table's staging: desc (40 bytes a sample, uploaded), then n_files + 1 host-only words
+static int32_t slice_samples_ok(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, const uint32_t *host_files, const uint64_t *host_chunks,
+                                uint32_t n_samples) {
+  for (uint32_t s = 0; s < n_samples; ++s) {
+    if (host_files[s] >= n_files) { ctx->last_error = "a sampled file index is not below the file count"; return B3W_E_BAD_ARGUMENT; }
+    if (host_chunks[s] >= num_chunks(host_lens[host_files[s]])) { ctx->last_error = "a sampled chunk index is not below its file's chunk count"; return B3W_E_BAD_ARGUMENT; }
+  }
+  return B3W_OK;
+}
+
+int32_t b3w_bao_slice_batch_device(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint8_t *d_outboards,
+                                   const uint32_t *host_files, const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_bytes,
+                                   uint8_t *d_slices, void *stream) {
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  if (group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "bao slice batch: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
+  if (!n_samples) return B3W_OK;
+  if (!host_lens || !d_outboards || !host_files || !host_chunks || !d_bytes || !d_slices) { ctx->last_error = "bao slice batch: a null pointer"; return B3W_E_BAD_ARGUMENT; }
+  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) { ctx->last_error = "bao slice batch: d_outboards is not 8-byte or d_slices not 16-byte aligned"; return B3W_E_BAD_ARGUMENT; }
+  int32_t rc = slice_samples_ok(ctx, host_lens, n_files, host_files, host_chunks, n_samples);
+  if (rc) return rc;
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t desc_bytes = (uint64_t)n_samples * 40;
+  rc = batch_staging(ctx, desc_bytes + ((uint64_t)n_files + 1) * 8);
+  if (rc) return rc;
+  uint64_t *desc = reinterpret_cast<uint64_t *>(ctx->h_batch), *ob_first = desc + 5 * (uint64_t)n_samples;
+  (void)b3w_bao_group_batch_layout(host_lens, n_files, group_log, ob_first);        // (group_log 0: b3w_bao_batch_layout's)
+  uint64_t at = slice_start(0);
+  for (uint32_t s = 0; s < n_samples; ++s) {
+    const uint32_t f = host_files[s];
+    uint64_t *d = desc + 5 * (uint64_t)s;
+    d[0] = host_chunks[s]; d[1] = at; d[2] = host_lens[f]; d[3] = ob_first[f]; d[4] = f;
+    at = slice_start(at + b3w_bao_slice_size(host_lens[f], host_chunks[s]));
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)desc_bytes, hipMemcpyHostToDevice, st));
+  const uint64_t *d_desc = reinterpret_cast<const uint64_t *>(ctx->d_batch);
+  if (group_log == 0) {
+    const uint32_t per_wg = 256 / SLICE_LANES;
+    hipLaunchKernelGGL(b3w_bao_slice_kernel, dim3((n_samples + per_wg - 1) / per_wg), dim3(256), 0, st, d_outboards, d_desc, n_samples, d_bytes, d_slices);
+  } else {
+    const uint32_t per_wave = 64u >> group_log;
+    hipLaunchKernelGGL(b3w_bao_slice_group_kernel, dim3((n_samples + per_wave - 1) / per_wave), dim3(64), 0, st, d_outboards, d_desc, n_samples, group_log,
+                       d_bytes, d_slices);
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(ctx, e, "bao slice batch launch");
+  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
+  return B3W_OK;
+}
+
+int32_t b3w_sample_plan_slices_device(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, const uint32_t *d_roots, const uint32_t *host_files,
+                                      const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_slices, uint32_t *d_records,
+                                      int32_t *d_sample_status, void *stream) {
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  if (ctx->desc.kind == B3W_KIND_COMP) { ctx->last_error = "sampled paths plan the nova step circuits' records"; return B3W_E_BAD_ARGUMENT; }
+  if (!n_samples) return B3W_OK;
+  if (!host_lens || !d_roots || !host_files || !host_chunks || !d_slices || !d_records || !d_sample_status) {
+    ctx->last_error = "sample plan slices: a null pointer"; return B3W_E_BAD_ARGUMENT;
+  }
+  if ((uintptr_t)d_slices & 15) { ctx->last_error = "sample plan slices: d_slices is not 16-byte aligned"; return B3W_E_BAD_ARGUMENT; }
+  int32_t rc = slice_samples_ok(ctx, host_lens, n_files, host_files, host_chunks, n_samples);
+  if (rc) return rc;
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t desc_bytes = (uint64_t)n_samples * 40;
+  rc = batch_staging(ctx, desc_bytes);
+  if (rc) return rc;
+  uint64_t *desc = reinterpret_cast<uint64_t *>(ctx->h_batch);
+  uint64_t row = 0, at = slice_start(0);
+  for (uint32_t s = 0; s < n_samples; ++s) {
+    const uint32_t f = host_files[s];
+    const uint64_t len = host_lens[f];
+    uint64_t *d = desc + 5 * (uint64_t)s;
+    d[0] = host_chunks[s]; d[1] = row; d[2] = len; d[3] = at; d[4] = f;
+    row += chunk_blocks(len, host_chunks[s]) + b3w_plan_path_len(host_chunks[s], num_chunks(len));
+    at = slice_start(at + b3w_bao_slice_size(len, host_chunks[s]));
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)desc_bytes, hipMemcpyHostToDevice, st));
+  // lanes a sample: 16; B3W_SLICE_PLAN_LANES=1 / 4 and B3W_SLICE_PLAN_CHAIN=1 (the running-h chain for every sample): measurements
+  const char *env = getenv("B3W_SLICE_PLAN_LANES"), *env_chain = getenv("B3W_SLICE_PLAN_CHAIN");
+  const int lanes = env ? atoi(env) : 16;
+  const uint32_t chain = env_chain && atoi(env_chain) != 0;
+  const uint64_t *d_desc = reinterpret_cast<const uint64_t *>(ctx->d_batch);
+  if (lanes == 1)
+    hipLaunchKernelGGL(b3w_sample_plan_slices_kernel<1>, dim3((n_samples + 63) / 64), dim3(64), 0, st, d_slices, d_roots, d_desc, n_samples, chain, d_records, d_sample_status);
+  else if (lanes == 4)
+    hipLaunchKernelGGL(b3w_sample_plan_slices_kernel<4>, dim3((n_samples + 15) / 16), dim3(64), 0, st, d_slices, d_roots, d_desc, n_samples, chain, d_records, d_sample_status);
+  else
+    hipLaunchKernelGGL(b3w_sample_plan_slices_kernel<16>, dim3((n_samples + 3) / 4), dim3(64), 0, st, d_slices, d_roots, d_desc, n_samples, chain, d_records, d_sample_status);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(ctx, e, "sample plan slices launch");
   HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
   return B3W_OK;
 }

@@ -8,7 +8,7 @@
 
 namespace {
 
-__device__ __forceinline__ uint32_t rotr(uint32_t x, int r) { return (x >> r) | (x << (32 - r)); }
+__host__ __device__ __forceinline__ uint32_t rotr(uint32_t x, int r) { return (x >> r) | (x << (32 - r)); }
 
 #define B3_G(a, b, c, d, x, y)                                       \
   v[a] = v[a] + v[b] + (x); v[d] = rotr(v[d] ^ v[a], 16);            \
@@ -17,8 +17,9 @@ __device__ __forceinline__ uint32_t rotr(uint32_t x, int r) { return (x >> r) | 
   v[c] = v[c] + v[d];       v[b] = rotr(v[b] ^ v[c], 7);
 
 // plain BLAKE3 compression, first 8 output words (BLAKE3 spec 2.2; the circuit's Blake3Compression
-// computes the same function, circuits/blake3_compression.circom:171-228)
-__device__ void blake3_cv(const uint32_t h[8], const uint32_t m_in[16], uint32_t t0, uint32_t t1, uint32_t b, uint32_t d,
+// computes the same function, circuits/blake3_compression.circom:171-228).  Host-callable too: b3w_bao_slice_decode
+// (b3w_bao.hip) is the one host caller.
+__host__ __device__ void blake3_cv(const uint32_t h[8], const uint32_t m_in[16], uint32_t t0, uint32_t t1, uint32_t b, uint32_t d,
                           uint32_t out[8]) {
   uint32_t v[16], m[16];
 #pragma unroll
@@ -39,7 +40,7 @@ __device__ void blake3_cv(const uint32_t h[8], const uint32_t m_in[16], uint32_t
   for (int i = 0; i < 8; ++i) out[i] = v[i] ^ v[i + 8];
 }
 
-__device__ __forceinline__ void iv(uint32_t h[8]) {
+__host__ __device__ __forceinline__ void iv(uint32_t h[8]) {
   h[0] = 0x6A09E667u; h[1] = 0xBB67AE85u; h[2] = 0x3C6EF372u; h[3] = 0xA54FF53Au;
   h[4] = 0x510E527Fu; h[5] = 0x9B05688Cu; h[6] = 0x1F83D9ABu; h[7] = 0x5BE0CD19u;
 }

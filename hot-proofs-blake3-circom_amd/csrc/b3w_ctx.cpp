@@ -303,7 +303,7 @@ int b3w_int_default_variant(const b3w_ctx *ctx, uint32_t n, const uint8_t *d_bod
 
 extern "C" {
 
-uint32_t b3w_abi_version(void) { return (1u << 16) | 3u; }   // 1.3: bao group outboards
+uint32_t b3w_abi_version(void) { return (1u << 16) | 4u; }   // 1.4: bao slices
 
 int32_t b3w_identify_wasm(const uint8_t *code, size_t len) {
   if (!code) return B3W_CIRCUIT_UNKNOWN;

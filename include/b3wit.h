@@ -658,6 +658,51 @@ int32_t b3w_sample_plan_group_batch_device(b3w_ctx *ctx, const uint64_t *host_le
                                            const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_group_bytes,
                                            uint32_t *d_records, int32_t *d_sample_status, void *stream);
 
+/* ---- bao slices (ABI 1.4) ---------------------------------------------------------------------------------------
+ * The SLICE of one chunk is what travels between the party that stores a file and the party that proves or checks a challenge
+ * (the reference's hash_with_path extracts it and decodes it against the hash, rust_fold/src/blake3_hash.rs:17-93):
+ *   slice of chunk c = the 8-byte LE length || the P = b3w_chain_path_len(c, n_chunks) nodes of c's path, root first, 64 bytes each
+ *                      || the chunk's bytes [c*1024, min(len, c*1024 + 1024)); an empty file's slice is the header alone.
+ * The provider makes slices from its outboards — full or GROUP outboards, the slices are the same standard ones any bao decoder
+ * takes — and the prover plans the step records from the slices and the files' roots alone: it needs no outboard.  Every call here
+ * is a batch call over samples (host_files[s], host_chunks[s]) as b3w_sample_plan_batch_device takes them. */
+/* Host only.  8 + 64 P + the chunk's byte count; 0 for a chunk not below the chunk count. */
+uint64_t b3w_bao_slice_size(uint64_t preimage_len, uint64_t chunk);
+/* Host only.  Slices of a batch are packed in sample order: sample s's slice is the b3w_bao_slice_size bytes from slice_first[s]
+ * of d_slices.  Every start is 8 modulo 16 (so also a multiple of 8): with d_slices 16-byte aligned the nodes and the chunk's
+ * bytes, which follow the 8-byte header, lie on 16-byte boundaries, and the kernels move and read them 16 bytes at a time.  The
+ * bytes in front of the first slice and between slices are padding that no call reads or writes.  slice_first: n_samples + 1
+ * entries, the last one the total.  Returns the total byte count of d_slices, or -B3W_E_BAD_ARGUMENT for a file index >= n_files
+ * or a chunk index not below its file's chunk count. */
+int64_t b3w_bao_slice_batch_layout(const uint64_t *host_lens, uint32_t n_files, const uint32_t *host_files, const uint64_t *host_chunks,
+                                   uint32_t n_samples, uint64_t *slice_first);
+/* Host only.  Bao's top-down decoder for one slice (slice_len must be b3w_bao_slice_size(preimage_len, chunk), else
+ * B3W_E_BAD_ARGUMENT; so is a chunk out of range): for callers without a GPU.  *out_status: 0 verified, 1 the chunk's bytes do not
+ * match, 2 a path node or the root does not match (one chunk: its ROOT-flagged output is what meets the root, so a wrong root is
+ * 1 there), 3 the header is not preimage_len; 3 wins over 2 over 1, as in the planners.  out_chunk (room for 1024 bytes) and
+ * out_bytes may be NULL; the bytes are handed out only with status 0 (*out_bytes = 0 otherwise). */
+int32_t b3w_bao_slice_decode(const uint8_t *slice, uint64_t slice_len, uint64_t preimage_len, uint64_t chunk, const uint32_t *root /* 8 u32 */,
+                             uint8_t *out_chunk, uint32_t *out_bytes, int32_t *out_status);
+/* The provider's side: the slices of the samples into d_slices (16-byte aligned, packed as b3w_bao_slice_batch_layout says).
+ * group_log = 0: d_outboards are full outboards (b3w_bao_batch_layout), d_bytes 1 024 bytes per sample (the sampled chunk's).
+ * group_log = 1 .. B3W_BAO_MAX_GROUP_LOG: d_outboards are group outboards (b3w_bao_group_batch_layout), d_bytes 1024 << group_log
+ * bytes per sample (the sampled chunk's group's, as b3w_sample_plan_group_batch_device takes them); the nodes inside the group are
+ * recomputed.  Either way the same standard slices.  Nothing is verified (an extractor does not): the header is the outboard's.
+ * One launch; the sample table goes through the context's staging, nothing else is allocated.  B3W_E_BAD_ARGUMENT before anything
+ * is written for a group_log above the maximum, a null or misaligned pointer, a bad file or chunk index.  n_samples == 0: a no-op.
+ * Any context.  Asynchronous on `stream`; waits for this context's previous batch call. */
+int32_t b3w_bao_slice_batch_device(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint8_t *d_outboards,
+                                   const uint32_t *host_files, const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_bytes,
+                                   uint8_t *d_slices, void *stream);
+/* The prover's side: b3w_sample_plan_batch_device from the slices alone — no outboard.  d_slices: 16-byte aligned, packed as
+ * b3w_bao_slice_batch_layout says for these samples; d_roots: 8 u32 per file ON THE DEVICE.  Every slice is verified top down
+ * against its file's root.  Rows are b3w_sample_rows_batch's; records and statuses (the same four codes) are word for word those
+ * of b3w_sample_plan_batch_device for the same samples; records are written either way and a bad slice touches no other sample.
+ * One launch.  n_samples == 0: a no-op.  Nova contexts only. */
+int32_t b3w_sample_plan_slices_device(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, const uint32_t *d_roots,
+                                      const uint32_t *host_files, const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_slices,
+                                      uint32_t *d_records, int32_t *d_sample_status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
