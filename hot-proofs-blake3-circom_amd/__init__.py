@@ -186,6 +186,10 @@ def lib():
         "b3w_bao_slice_decode": (i32, [vp, u64, u64, u64, vp, vp, ctypes.POINTER(u32), ctypes.POINTER(i32)]),
         "b3w_bao_slice_batch_device": (i32, [vp, vp, u32, u32, vp, vp, vp, u32, vp, vp, vp]),
         "b3w_sample_plan_slices_device": (i32, [vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp]),
+        "b3w_bao_verify_layout": (u64, [vp, u32, u32, vp]),
+        "b3w_bao_verify_scratch_bytes": (u64, [vp, u32]),
+        "b3w_bao_verify_batch_device": (i32, [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, u64, vp]),
+        "b3w_bao_verify": (i32, [vp, u64, vp, u32, vp, vp, ctypes.POINTER(i32), ctypes.POINTER(u64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -211,7 +215,8 @@ EXPORTED_SYMBOLS = ("b3w_abi_version", "b3w_identify_wasm", "b3w_create", "b3w_d
                     "b3w_sample_rows_batch", "b3w_sample_plan_batch_device", "b3w_bao_group_outboard_size", "b3w_bao_group_batch_layout",
                     "b3w_bao_group_path_nodes", "b3w_bao_group_outboard_batch_device", "b3w_sample_plan_group_batch_device",
                     "b3w_bao_slice_size", "b3w_bao_slice_batch_layout", "b3w_bao_slice_decode", "b3w_bao_slice_batch_device",
-                    "b3w_sample_plan_slices_device")
+                    "b3w_sample_plan_slices_device",
+                    "b3w_bao_verify_layout", "b3w_bao_verify_scratch_bytes", "b3w_bao_verify_batch_device", "b3w_bao_verify")
 
 
 class graph_capture:

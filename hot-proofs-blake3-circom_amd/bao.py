@@ -8,7 +8,9 @@ plan_samples_batch() and prove_samples_batch() do the same for a whole batch of 
 outboard_groups_batch(), plan_samples_groups_batch() and prove_samples_groups_batch() keep the outboards over chunk groups of
 2^group_log chunks, 2^group_log times smaller, and recompute the levels inside a group from the group's bytes.  slices_batch() extracts the standard bao slices of challenged chunks from either kind
 of outboard and plan_samples_slices() / prove_samples_slices() plan and prove from slices alone, so the prover need not hold the
-outboards (decode_slice(): the host decoder).  The records are
+outboards (decode_slice(): the host decoder).  verify_batch() is bao's decoder over whole files: every chunk (or chunk group) of
+every file of a batch held against its outboard and root on the device, a status per unit (verify_host(): one file on the host).
+The records are
 word for word those the chain planner writes for the same chunks (ChainPlanner.plan), so every step is the reference's
 prove_chunk_hash step (rust_fold/src/main.rs:41-203 over hash_with_path's slice, rust_fold/src/blake3_hash.rs:17-93)."""
 import ctypes
@@ -449,3 +451,61 @@ def decode_slice(slice_bytes, length, chunk, root):
     cnt, st = ctypes.c_uint32(), ctypes.c_int32()
     _chk(None, lib().b3w_bao_slice_decode(sl, len(sl), length, chunk, rw.ctypes.data, out, ctypes.byref(cnt), ctypes.byref(st)), "b3w_bao_slice_decode")
     return st.value, out.raw[:cnt.value]
+
+
+# ---- verification: whole files against their outboards ------------------------------------------------------------------
+def verify_layout(lens, group_log=0):
+    """-> unit_first (numpy uint64 [n_files + 1]): file f's unit statuses are entries [unit_first[f], unit_first[f + 1]) of the packed
+    statuses; a unit is a chunk (group_log 0) or a group of 2^group_log chunks"""
+    if not 0 <= group_log <= MAX_GROUP_LOG:
+        raise B3WError(100, f"group_log {group_log} is not in 0 .. {MAX_GROUP_LOG}")
+    ln = _u64(lens)
+    unit_first = np.zeros(ln.size + 1, dtype=np.uint64)
+    lib().b3w_bao_verify_layout(ln.ctypes.data, ln.size, group_log, unit_first.ctypes.data)
+    return unit_first
+
+
+def verify_batch(ctx, d_arena, offsets, lens, d_outboards, d_roots, group_log=0, stream=0):
+    """Bao's decoder over every unit of every file of a batch at once, in a number of launches that does not depend on the file count:
+    the files as outboard_batch takes them, d_outboards / d_roots as outboard_batch (group_log 0) or outboard_groups_batch made them —
+    or as they arrived from elsewhere.  Returns a dict, everything left on the device: unit_status (uint8 CUDA, packed as unit_first
+    says; STATUS / GROUP_STATUS: 0 verified, 1 the unit's bytes, 2 a stored node on its path or the root, 3 the header), unit_first
+    (numpy uint64 [n_files + 1]), file_status (int32 CUDA [n_files]: the largest status among the file's units), first_bad (int64 CUDA
+    [n_files]: the lowest unit with a non-zero status, -1 = UINT64_MAX where there is none)."""
+    L = lib()
+    off, ln = _u64(offsets), _u64(lens)
+    assert off.size == ln.size
+    assert d_arena.is_cuda and d_arena.dtype == torch.uint8 and d_arena.is_contiguous()
+    if ln.size and int((off + ln).max()) > d_arena.numel():
+        raise B3WError(100, "verify_batch: a file reaches past the end of the arena")
+    dev = d_arena.device
+    unit_first = verify_layout(ln, group_log)
+    ob_first = group_batch_layout(ln, group_log)
+    assert d_outboards.is_cuda and d_outboards.dtype == torch.uint8 and d_outboards.is_contiguous() and d_outboards.numel() >= int(ob_first[-1])
+    assert d_roots.is_cuda and d_roots.is_contiguous() and d_roots.element_size() == 4 and d_roots.numel() >= ln.size * 8
+    unit_status = torch.empty(int(unit_first[-1]), dtype=torch.uint8, device=dev)
+    file_status = torch.empty(ln.size, dtype=torch.int32, device=dev)
+    first_bad = torch.empty(ln.size, dtype=torch.int64, device=dev)
+    need = L.b3w_bao_verify_scratch_bytes(ln.ctypes.data, ln.size)
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    _chk(ctx, L.b3w_bao_verify_batch_device(ctx.handle, d_arena.data_ptr() if d_arena.numel() else None, off.ctypes.data, ln.ctypes.data, ln.size,
+                                            group_log, d_outboards.data_ptr(), d_roots.data_ptr(), unit_status.data_ptr(), file_status.data_ptr(),
+                                            first_bad.data_ptr(), scratch.data_ptr() if need else None, need, _stream(stream)),
+         "b3w_bao_verify_batch_device")
+    return dict(unit_status=unit_status, unit_first=unit_first, file_status=file_status, first_bad=first_bad)
+
+
+def verify_host(data, outboard, root, group_log=0):
+    """verify_batch for one file on the host (no GPU) -> (unit_status numpy uint8, file_status, first_bad: an int, 2^64 - 1 = none)"""
+    if not 0 <= group_log <= MAX_GROUP_LOG:
+        raise B3WError(100, f"group_log {group_log} is not in 0 .. {MAX_GROUP_LOG}")
+    data = bytes(data)
+    ob = outboard.cpu().numpy().tobytes() if isinstance(outboard, torch.Tensor) else bytes(outboard)
+    if len(ob) != group_outboard_size(len(data), group_log):
+        raise B3WError(100, "verify_host: the outboard's size is not that of a file of this length")
+    rw = np.ascontiguousarray(root, dtype=np.uint32)
+    units = (num_chunks(len(data)) + (1 << group_log) - 1) >> group_log
+    st = np.zeros(units, dtype=np.uint8)
+    fs, fb = ctypes.c_int32(), ctypes.c_uint64()
+    _chk(None, lib().b3w_bao_verify(data, len(data), ob, group_log, rw.ctypes.data, st.ctypes.data, ctypes.byref(fs), ctypes.byref(fb)), "b3w_bao_verify")
+    return st, fs.value, fb.value

@@ -26,6 +26,8 @@
 //                            path inside the group stored whole before its level's merge
 //   b3w_sample_plan_slices_kernel  the step records planned from slices alone (no outboard): a sample over several lanes, the path's nodes
 //                            checked side by side, the parent records without the running-h chain where that chain is redundant
+//   b3w_bao_verify_*_kernel  whole files against their outboards: the three batch kernels with every store of a node turned into a check of
+//                            the stored node, the storey above the tiles first; a status per chunk or chunk group ("verification")
 #include "b3w_internal.h"
 #include "b3w_blake3_dev.h"
 
@@ -872,6 +874,239 @@ __global__ __launch_bounds__(64) void b3w_sample_plan_slices_kernel(const uint8_
   }
 }
 
+// ---- verification: whole files against their outboards ---------------------------------------------------------------------
+// Bao's decoder applied to every UNIT of every file at once (a unit: a chunk, or with group outboards a group of 1 << gl chunks).  The
+// mirror image of the three batch kernels: where those store a node, these load the stored node from the same pre-order place, hold the
+// two CVs in their LDS slots (what the children claim to be) against the node's halves, and leave hash(stored node) in slot i0 — so
+// above the lowest level a slot holds what the STORED child node hashes to, and every check is stored data against stored data: a bad
+// chunk marks its own unit, a bad node the units below it.  Inside a group there is no stored node: merge_pair<true> computes up to the
+// group's CV and the comparison starts there.
+//   b3w_bao_verify_upper_kernel  the storey above the tiles, which needs no file bytes and runs BEFORE the tile kernel: one workgroup
+//                                per 1 024 tiles (and, for files past 1 GiB, first one per 1 024 of those), the stored nodes over them
+//                                checked bottom up in LDS; leaves per tile the CV its tile must have (the stored half in the lowest node
+//                                above it) and a "path above is bad" flag in the scratch; a file's top workgroup initialises the file's
+//                                status and first bad unit
+//   b3w_bao_verify_tile_kernel   one workgroup per tile, lane = chunk: chunk CVs, the tile's stored nodes, the tile's CV against the
+//                                scratch (one-tile file: its ROOT-hashed root node against the root); every unit's final status, one
+//                                byte a lane; the per-file outputs by reduction (one-tile file) or atomicMax / atomicMin (others)
+//   b3w_bao_verify_small_kernel  the files of at most 64 chunks, several to a wave, everything in the wave
+// Mismatch flags, one word per slot: bit l = the subtree of 1 << l items that starts at this slot (a child at level l) is not the half
+// its stored parent holds for it; bit VER_TOP = the whole tile / file (slot 0) is not what is expected from above; VER_UNIT = the same
+// for a subtree that is a single unit, whose claim comes from the file's bytes (status 1, not 2).  An item's path is bad where bit l of
+// slot (item >> l) << l is set for some l: that slot starts the item's subtree at level l, whether it was paired there or waited.
+struct VerFile { uint64_t ufirst, slot, gslot; };         // a file's first unit in the packed statuses; its first tile's / group's scratch entry
+constexpr uint32_t VER_UNIT = 1u << 31, VER_TOP = 1u << 10;
+
+__device__ __forceinline__ void load_node(const uint8_t *__restrict__ node, uint32_t m[16]) {   // (8 off a 16-byte boundary)
+  const uint2 *s = reinterpret_cast<const uint2 *>(node);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { const uint2 v = s[k]; m[2 * k] = v.x; m[2 * k + 1] = v.y; }
+}
+
+// one stored parent at level l: slots i0 (left) and i1 (right) against the halves of the node at `node`, hash(node) to slot i0.  A child
+// over at most `leaf` chunks is a single unit (CLAIM: its slot holds its CV from the bytes) or a single item with no claim yet (!CLAIM:
+// its half goes to exp_out, the CV expected of it); sl, sr: the children's chunk counts.
+template <bool CLAIM>
+__device__ __forceinline__ void check_pair(uint32_t *cv, uint32_t *flags, uint32_t i0, uint32_t i1, uint32_t l, const uint8_t *__restrict__ node,
+                                           uint32_t d, uint64_t sl, uint64_t sr, uint64_t leaf, uint32_t *__restrict__ exp_out) {
+  uint32_t m[16], ivv[8], o[8];
+  load_node(node, m);
+  if (sl <= leaf) {
+    if (CLAIM) { if (!eq8(cv + i0 * 8, m)) flags[i0] |= VER_UNIT; }
+    else {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) exp_out[(uint64_t)i0 * 8 + k] = m[k];
+    }
+  } else if (!eq8(cv + i0 * 8, m)) flags[i0] |= 1u << l;
+  if (sr <= leaf) {
+    if (CLAIM) { if (!eq8(cv + i1 * 8, m + 8)) flags[i1] |= VER_UNIT; }
+    else {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) exp_out[(uint64_t)i1 * 8 + k] = m[8 + k];
+    }
+  } else if (!eq8(cv + i1 * 8, m + 8)) flags[i1] |= 1u << l;
+  iv(ivv);
+  blake3_cv(ivv, m, 0, 0, 64, d, o);
+  reinterpret_cast<uint4 *>(cv + i0 * 8)[0] = make_uint4(o[0], o[1], o[2], o[3]);          // (slot i0 is this thread's alone at this level)
+  reinterpret_cast<uint4 *>(cv + i0 * 8)[1] = make_uint4(o[4], o[5], o[6], o[7]);
+}
+
+// merge_in_lds with the stores turned into checks: cnt items of `unit` chunks of a tree over `total` chunks whose root's place in the
+// file's outboard (groups of 1 << gl chunks; gl = 0: the full outboard) is `nodes`.  Leaves hash(the tree's stored root node) in cv[0 .. 8)
+// (cnt == 1: the item's own slot untouched) and the children's flags in `flags` (zeroed by the caller); ends with a barrier.
+template <int BS, bool CLAIM>
+__device__ __forceinline__ void verify_in_lds(uint32_t *cv, uint32_t *flags, uint32_t cnt, uint64_t unit, uint64_t total,
+                                              const uint8_t *__restrict__ nodes, bool root, uint32_t gl, uint32_t *__restrict__ exp_out) {
+  const uint64_t G = 1ull << gl, G1 = G - 1, leaf = CLAIM ? G : unit;
+  for (uint32_t l = 0; (1u << l) < cnt; ++l) {
+    lds_barrier();
+    const bool top = (2u << l) >= cnt;
+    for (uint32_t j = threadIdx.x;; j += BS) {
+      const uint32_t i0 = (2 * j) << l, i1 = i0 + (1u << l);
+      if (i1 >= cnt) break;
+      const uint64_t a = i0 * unit, e = (uint64_t)(i0 + (2u << l)) * unit, size = (e < total ? e : total) - a;
+      const uint32_t d = 4u | (top && root ? 8u : 0u);
+      if (CLAIM && size <= G) { merge_pair<true>(cv, i0, i1, nullptr, d); continue; }          // inside a group: computed
+      const uint64_t sl = ((uint64_t)unit) << l;
+      check_pair<CLAIM>(cv, flags, i0, i1, l, nodes + preorder_pos((total + G1) >> gl, a >> gl, (size + G1) >> gl) * 64, d, sl, size - sl, leaf, exp_out);
+    }
+  }
+  lds_barrier();
+}
+
+// the OR of the node flags on item t's path
+__device__ __forceinline__ bool path_bad(const uint32_t *flags, uint32_t t) {
+  uint32_t x = 0;
+#pragma unroll
+  for (uint32_t l = 0; l <= 10; ++l) x |= flags[(t >> l) << l] & (1u << l);
+  return x != 0;
+}
+
+// unit = chunks per item (B3W_TILE: the items are tiles; B3W_TILE^2, the launch for files past 1 GiB, which runs first: groups of tiles).
+// Scratch entries: exp_cv 8 words and bad 1 word per entry; the tiles' entries first (n_tile_ents of them), then the groups'.
+__global__ __launch_bounds__(256) void b3w_bao_verify_upper_kernel(const BatchEnt *__restrict__ ents, uint32_t n_ents, uint64_t unit,
+                                                                   const VerFile *__restrict__ vf, uint64_t n_tile_ents,
+                                                                   const uint8_t *__restrict__ outboards, const uint32_t *__restrict__ roots,
+                                                                   uint32_t *__restrict__ exp_cv, uint32_t *__restrict__ bad, uint32_t gl,
+                                                                   int32_t *__restrict__ file_status, unsigned long long *__restrict__ first_bad) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
+  __shared__ uint32_t flags[B3W_TILE];
+  const BatchEnt e = batch_ent(ents, n_ents, blockIdx.x);
+  const VerFile v = vf[e.file];
+  const uint64_t n = (e.len + 1023) / 1024;                           // (more than one tile)
+  const uint64_t g = blockIdx.x - e.first, span = unit * B3W_TILE, a0 = g * span;
+  const uint64_t tot = n - a0 < span ? n - a0 : span;
+  const uint32_t cnt = (uint32_t)((tot + unit - 1) / unit);
+  const bool sole = n <= span;                                        // the file's top workgroup
+  const uint64_t out0 = unit == B3W_TILE ? v.slot + g * B3W_TILE : n_tile_ents + v.gslot, in = n_tile_ents + v.gslot + g;
+  const uint32_t *want = sole ? roots + (uint64_t)e.file * 8 : exp_cv + in * 8;
+  bool above = sole ? false : bad[in] != 0;
+  const uint32_t *ob = reinterpret_cast<const uint32_t *>(outboards + e.ob);
+  if (sole && threadIdx.x == 0) {                                     // (the tile kernel, which runs after this one, adds to these)
+    const bool hdr = ((uint64_t)ob[0] | ((uint64_t)ob[1] << 32)) != e.len;
+    file_status[e.file] = hdr ? 3 : 0;
+    first_bad[e.file] = hdr ? 0ull : ~0ull;
+  }
+  if (cnt == 1) {                                                     // a lone last tile (or group) hangs straight off the storey above
+    if (threadIdx.x < 8) exp_cv[out0 * 8 + threadIdx.x] = want[threadIdx.x];
+    if (threadIdx.x == 0) bad[out0] = above;
+    return;
+  }
+  for (uint32_t i = threadIdx.x; i < cnt; i += 256) flags[i] = 0;
+  const uint64_t G1 = (1ull << gl) - 1;
+  verify_in_lds<256, false>(cv, flags, cnt, unit, tot, outboards + e.ob + 8 + preorder_pos((n + G1) >> gl, a0 >> gl, (tot + G1) >> gl) * 64, sole, gl,
+                            exp_cv + out0 * 8);
+  above = above || !eq8(cv, want);
+  for (uint32_t t = threadIdx.x; t < cnt; t += 256) bad[out0 + t] = above || path_bad(flags, t);
+}
+
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_verify_tile_kernel(const uint8_t *__restrict__ arena, const BatchEnt *__restrict__ ents, uint32_t n_ents,
+                                                                       const VerFile *__restrict__ vf, const uint8_t *__restrict__ outboards,
+                                                                       const uint32_t *__restrict__ roots, const uint32_t *__restrict__ exp_cv,
+                                                                       const uint32_t *__restrict__ bad, uint32_t gl, uint8_t *__restrict__ unit_status,
+                                                                       int32_t *__restrict__ file_status, unsigned long long *__restrict__ first_bad) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
+  __shared__ uint32_t flags[B3W_TILE];
+  __shared__ uint32_t worst, first;
+  const BatchEnt e = batch_ent(ents, n_ents, blockIdx.x);
+  const VerFile v = vf[e.file];
+  const uint64_t n = (e.len + 1023) / 1024;                           // (more than 64 chunks)
+  const uint32_t tile = blockIdx.x - e.first, t = threadIdx.x, G = 1u << gl;
+  const uint64_t a0 = (uint64_t)tile * B3W_TILE;
+  const uint32_t m = (uint32_t)(n - a0 < B3W_TILE ? n - a0 : B3W_TILE);
+  const bool sole = n <= B3W_TILE;
+  if (t < m) {
+    const uint64_t c = a0 + t, off = c * 1024;
+    uint32_t h[8];
+    chunk_cv(arena + e.off + off, (uint32_t)(e.len - off < 1024 ? e.len - off : 1024), c, 0, h);
+    reinterpret_cast<uint4 *>(cv + t * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
+    reinterpret_cast<uint4 *>(cv + t * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
+  }
+  flags[t] = 0;
+  if (t == 0) { worst = 0; first = ~0u; }
+  const uint32_t *ob = reinterpret_cast<const uint32_t *>(outboards + e.ob);
+  const bool hdr = ((uint64_t)ob[0] | ((uint64_t)ob[1] << 32)) != e.len;
+  const uint64_t G1 = G - 1;
+  verify_in_lds<B3W_TILE, true>(cv, flags, m, 1, m, outboards + e.ob + 8 + preorder_pos((n + G1) >> gl, a0 >> gl, (m + G1) >> gl) * 64, sole, gl, nullptr);
+  const uint64_t ent = v.slot + tile;
+  if (t == 0 && !eq8(cv, sole ? roots + (uint64_t)e.file * 8 : exp_cv + ent * 8)) flags[0] |= m <= G ? VER_UNIT : VER_TOP;
+  const bool above = sole ? false : bad[ent] != 0;
+  lds_barrier();
+  if (t < m && (t & (G - 1)) == 0) {                                  // a unit's first chunk: its status
+    const uint32_t st = hdr ? 3u : above || path_bad(flags, t) ? 2u : (flags[t] & VER_UNIT) ? 1u : 0u;
+    unit_status[v.ufirst + ((a0 + t) >> gl)] = (uint8_t)st;
+    if (st) { atomicMax(&worst, st); atomicMin(&first, t >> gl); }    // (LDS; a clean tile issues none)
+  }
+  __syncthreads();
+  if (t != 0) return;
+  if (sole) {
+    file_status[e.file] = (int32_t)worst;
+    first_bad[e.file] = worst ? (unsigned long long)first : ~0ull;
+  } else if (worst) {                                                 // (initialised by the file's top workgroup of the storey above)
+    atomicMax(file_status + e.file, (int32_t)worst);
+    atomicMin(first_bad + e.file, (unsigned long long)((a0 >> gl) + first));
+  }
+}
+
+// small_body's wave packing: lane = chunk, each file in its own run of lanes, every stored node of a file checked by the lane that would
+// have stored it; the per-file outputs from ballots over the file's lanes
+__global__ __launch_bounds__(64) void b3w_bao_verify_small_kernel(const uint8_t *__restrict__ arena, const BatchEnt *__restrict__ ents,
+                                                                  const uint32_t *__restrict__ wave_first, const VerFile *__restrict__ vf,
+                                                                  const uint8_t *__restrict__ outboards, const uint32_t *__restrict__ roots, uint32_t gl,
+                                                                  uint8_t *__restrict__ unit_status, int32_t *__restrict__ file_status,
+                                                                  unsigned long long *__restrict__ first_bad) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[64 * 8];
+  __shared__ uint32_t flags[64];
+  const uint32_t lane = threadIdx.x, G = 1u << gl;
+  uint32_t lo = wave_first[blockIdx.x], hi = wave_first[blockIdx.x + 1];
+  while (hi - lo > 1) {                                               // this lane's file: the last one that starts at or before the lane
+    const uint32_t mid = (lo + hi) / 2;
+    if (ents[mid].first <= lane) lo = mid; else hi = mid;
+  }
+  const BatchEnt e = ents[lo];
+  const uint32_t n = e.len ? (uint32_t)((e.len + 1023) / 1024) : 1, i = lane - e.first;
+  const bool live = i < n;                                            // (the lanes behind the last file's chunks are not)
+  if (live) {
+    const uint32_t off = i * 1024;
+    uint32_t h[8];
+    chunk_cv(arena + e.off + off, (uint32_t)(e.len - off < 1024 ? e.len - off : 1024), i, n == 1 ? 8u : 0u, h);
+    reinterpret_cast<uint4 *>(cv + lane * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
+    reinterpret_cast<uint4 *>(cv + lane * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
+  }
+  flags[lane] = 0;
+  const uint8_t *ob = outboards + e.ob;
+  const bool hdr = ((uint64_t)reinterpret_cast<const uint32_t *>(ob)[0] | ((uint64_t)reinterpret_cast<const uint32_t *>(ob)[1] << 32)) != e.len;
+  for (uint32_t l = 0; l < 6; ++l) {
+    lds_barrier();
+    if (!__any(live && (1u << l) < n)) break;                         // (uniform: the workgroup is this one wave)
+    if (live && (i & ((2u << l) - 1)) == 0 && i + (1u << l) < n) {
+      const uint32_t size = n - i < (2u << l) ? n - i : (2u << l), d = 4u | (i == 0 && (2u << l) >= n ? 8u : 0u);
+      if (size <= G) merge_pair<true>(cv, lane, lane + (1u << l), nullptr, d);
+      else check_pair<true>(cv, flags, lane, lane + (1u << l), l, ob + 8 + preorder_pos((n + G - 1) >> gl, i >> gl, (size + G - 1) >> gl) * 64, d,
+                            1u << l, size - (1u << l), G, nullptr);
+    }
+  }
+  lds_barrier();
+  // the file's top (its ROOT-flagged CV, or what its stored root node hashes to with ROOT) against the root; bit 6: above every level here
+  if (live && i == 0 && !eq8(cv + lane * 8, roots + (uint64_t)e.file * 8)) flags[lane] |= n <= G ? VER_UNIT : 1u << 6;
+  lds_barrier();
+  const bool is_unit = live && (i & (G - 1)) == 0;
+  uint32_t st = 0;
+  if (is_unit) {
+    uint32_t x = 0;
+#pragma unroll
+    for (uint32_t l = 0; l <= 6; ++l) x |= flags[e.first + ((i >> l) << l)] & (1u << l);
+    st = hdr ? 3u : x ? 2u : (flags[lane] & VER_UNIT) ? 1u : 0u;
+    unit_status[vf[e.file].ufirst + (i >> gl)] = (uint8_t)st;
+  }
+  const uint64_t mine = (n == 64 ? ~0ull : (1ull << n) - 1) << e.first;
+  const uint64_t b1 = __ballot(st >= 1) & mine, b2 = __ballot(st >= 2) & mine, b3 = __ballot(st >= 3) & mine;
+  if (live && i == 0) {
+    file_status[e.file] = b3 ? 3 : b2 ? 2 : b1 ? 1 : 0;
+    first_bad[e.file] = b1 ? (unsigned long long)((__ffsll((unsigned long long)b1) - 1 - e.first) >> gl) : ~0ull;
+  }
+}
+
 // the CV of a chunk on the host (chunk_cv's loop over blake3_cv): b3w_bao_slice_decode
 void host_chunk_cv(const uint8_t *src, uint32_t bytes, uint64_t c, uint32_t root, uint32_t h[8]) {
   const uint32_t nb = bytes ? (bytes + 63) / 64 : 1;
@@ -1406,6 +1641,162 @@ int32_t b3w_sample_plan_slices_device(b3w_ctx *ctx, const uint64_t *host_lens, u
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(ctx, e, "sample plan slices launch");
   HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
+  return B3W_OK;
+}
+
+// ---- verification: whole files against their outboards ---------------------------------------------------------------------
+uint64_t b3w_bao_verify_layout(const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, uint64_t *unit_first) {
+  if (!unit_first || (!host_lens && n_files) || group_log > B3W_BAO_MAX_GROUP_LOG) return 0;
+  const uint64_t G1 = (1ull << group_log) - 1;
+  uint64_t at = 0;
+  for (uint32_t f = 0; f < n_files; ++f) { unit_first[f] = at; at += (num_chunks(host_lens[f]) + G1) >> group_log; }
+  unit_first[n_files] = at;
+  return at;
+}
+
+// scratch entries: one per tile of the files of more than one tile, one per group of 1 024 tiles of the files of more than one group
+static uint64_t verify_entries(const uint64_t *lens, uint32_t n_files, uint64_t *tile_ents) {
+  uint64_t tiles_sum = 0, groups_sum = 0;
+  for (uint32_t f = 0; f < n_files; ++f) {
+    const uint64_t tiles = (num_chunks(lens[f]) + B3W_TILE - 1) / B3W_TILE, groups = (tiles + B3W_TILE - 1) / B3W_TILE;
+    if (tiles > 1) tiles_sum += tiles;
+    if (groups > 1) groups_sum += groups;
+  }
+  if (tile_ents) *tile_ents = tiles_sum;
+  return tiles_sum + groups_sum;
+}
+
+uint64_t b3w_bao_verify_scratch_bytes(const uint64_t *host_lens, uint32_t n_files) {
+  if (!host_lens) return 0;
+  return (verify_entries(host_lens, n_files, nullptr) * 36 + 15) & ~15ull;           // the expected CV (32) and the flag (4) of every entry
+}
+
+int32_t b3w_bao_verify_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, const uint64_t *host_offsets, const uint64_t *host_lens, uint32_t n_files,
+                                    uint32_t group_log, const uint8_t *d_outboards, const uint32_t *d_roots, uint8_t *d_unit_status,
+                                    int32_t *d_file_status, uint64_t *d_first_bad, void *d_scratch, uint64_t scratch_bytes, void *stream) {
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  if (group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "bao verify: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
+  if (!n_files) return B3W_OK;
+  if (!host_offsets || !host_lens || !d_outboards || !d_roots || !d_unit_status || !d_file_status || !d_first_bad) {
+    ctx->last_error = "bao verify: a null pointer (offsets, lengths, outboards, roots or an output)"; return B3W_E_BAD_ARGUMENT;
+  }
+  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_first_bad & 7) || ((uintptr_t)d_file_status & 3) || ((uintptr_t)d_roots & 3)) {
+    ctx->last_error = "bao verify: d_outboards or d_first_bad is not 8-byte aligned, or d_file_status or d_roots not 4-byte aligned"; return B3W_E_BAD_ARGUMENT;
+  }
+  const BatchCounts k = batch_counts(host_lens, n_files);
+  if (k.too_long || k.big_wgs > 0x7fffffffull) { ctx->last_error = "bao verify: a file of more than 2^30 chunks, or more than 2^31 tiles"; return B3W_E_BAD_ARGUMENT; }
+  uint64_t tile_ents = 0;
+  const uint64_t n_scr = verify_entries(host_lens, n_files, &tile_ents), need = (n_scr * 36 + 15) & ~15ull;
+  if (scratch_bytes < need) { ctx->last_error = "bao verify: the scratch is smaller than b3w_bao_verify_scratch_bytes says"; return B3W_E_BAD_ARGUMENT; }
+  if (need && (!d_scratch || ((uintptr_t)d_scratch & 15))) { ctx->last_error = "bao verify: the scratch is null or not 16-byte aligned"; return B3W_E_BAD_ARGUMENT; }
+  if (!d_arena)
+    for (uint32_t f = 0; f < n_files; ++f)
+      if (host_lens[f]) { ctx->last_error = "bao verify: a null arena with a file that is not empty"; return B3W_E_BAD_ARGUMENT; }
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  // the tables of the outboard call, then one VerFile per file: small | big | merged | tops | files | the small waves' first files
+  const uint64_t n_ents = k.small + k.big + k.merged + k.tops;
+  const uint64_t table_bytes = n_ents * sizeof(BatchEnt) + (uint64_t)n_files * sizeof(VerFile) + (k.small ? (k.waves + 1) * 4 : 0);
+  const int32_t rc = batch_staging(ctx, table_bytes);
+  if (rc) return rc;
+  BatchEnt *h_small = reinterpret_cast<BatchEnt *>(ctx->h_batch), *h_big = h_small + k.small, *h_merged = h_big + k.big, *h_tops = h_merged + k.merged;
+  VerFile *h_files = reinterpret_cast<VerFile *>(h_tops + k.tops);
+  uint32_t *h_waves = reinterpret_cast<uint32_t *>(h_files + n_files);
+  uint32_t i_small = 0, i_waves = 0, fill = 64, i_big = 0, i_merged = 0, i_tops = 0, big_wgs = 0, groups = 0;
+  uint64_t ob = 0, units = 0, slot = 0, gslot = 0;
+  for (uint32_t f = 0; f < n_files; ++f) {
+    const uint64_t len = host_lens[f], n = num_chunks(len), n_units = (n + ((1ull << group_log) - 1)) >> group_log;
+    h_files[f] = VerFile{units, slot, gslot};
+    if (n <= 64) {
+      if (fill + n > 64) { h_waves[i_waves++] = i_small; fill = 0; }
+      h_small[i_small] = BatchEnt{host_offsets[f], len, ob, fill, f};
+      fill += (uint32_t)n;
+      i_small++;
+    } else {
+      const uint32_t tiles = (uint32_t)((n + B3W_TILE - 1) / B3W_TILE), grp = (tiles + B3W_TILE - 1) / B3W_TILE;
+      h_big[i_big++] = BatchEnt{host_offsets[f], len, ob, big_wgs, f};
+      if (tiles > 1) { h_merged[i_merged++] = BatchEnt{0, len, ob, groups, f}; slot += tiles; groups += grp; }
+      if (grp > 1) { h_tops[i_tops] = BatchEnt{0, len, ob, i_tops, f}; i_tops++; gslot += grp; }
+      big_wgs += tiles;
+    }
+    ob += 8 + 64 * (n_units - 1);                                      // (b3w_bao_group_outboard_size)
+    units += n_units;
+  }
+  if (k.small) h_waves[i_waves] = i_small;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)table_bytes, hipMemcpyHostToDevice, st));
+  const BatchEnt *d_small = reinterpret_cast<const BatchEnt *>(ctx->d_batch), *d_big = d_small + k.small, *d_merged = d_big + k.big, *d_tops = d_merged + k.merged;
+  const VerFile *d_files = reinterpret_cast<const VerFile *>(d_tops + k.tops);
+  const uint32_t *d_waves = reinterpret_cast<const uint32_t *>(d_files + n_files);
+  uint32_t *exp_cv = reinterpret_cast<uint32_t *>(d_scratch), *bad = exp_cv + n_scr * 8;
+  unsigned long long *fb = reinterpret_cast<unsigned long long *>(d_first_bad);
+  // top down: the storeys above the tiles first (stored nodes alone), then the kernels that read the files
+  if (k.tops) hipLaunchKernelGGL(b3w_bao_verify_upper_kernel, dim3((uint32_t)k.tops), dim3(256), 0, st, d_tops, (uint32_t)k.tops, (uint64_t)B3W_TILE * B3W_TILE, d_files, tile_ents, d_outboards, d_roots, exp_cv, bad, group_log, d_file_status, fb);
+  if (k.merged) hipLaunchKernelGGL(b3w_bao_verify_upper_kernel, dim3((uint32_t)k.groups), dim3(256), 0, st, d_merged, (uint32_t)k.merged, (uint64_t)B3W_TILE, d_files, tile_ents, d_outboards, d_roots, exp_cv, bad, group_log, d_file_status, fb);
+  if (k.small) hipLaunchKernelGGL(b3w_bao_verify_small_kernel, dim3((uint32_t)k.waves), dim3(64), 0, st, d_arena, d_small, d_waves, d_files, d_outboards, d_roots, group_log, d_unit_status, d_file_status, fb);
+  if (k.big) hipLaunchKernelGGL(b3w_bao_verify_tile_kernel, dim3((uint32_t)k.big_wgs), dim3(B3W_TILE), 0, st, d_arena, d_big, (uint32_t)k.big, d_files, d_outboards, d_roots, exp_cv, bad, group_log, d_unit_status, d_file_status, fb);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(ctx, e, "bao verify launch");
+  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
+  return B3W_OK;
+}
+
+// one unit's CV on the host: BLAKE3's tree over the chunks [first, first + cnt) of the file (root: the unit is the whole file)
+static void host_subtree_cv(const uint8_t *data, uint64_t len, uint64_t first, uint64_t cnt, bool root, uint32_t h[8]) {
+  if (cnt == 1) {
+    const uint64_t off = first * 1024;
+    host_chunk_cv(data + off, (uint32_t)(len - off < 1024 ? len - off : 1024), first, root ? 8u : 0u, h);
+    return;
+  }
+  uint64_t k2 = 1;
+  while (k2 * 2 < cnt) k2 *= 2;
+  uint32_t m[16], ivv[8];
+  host_subtree_cv(data, len, first, k2, false, m);
+  host_subtree_cv(data, len, first + k2, cnt - k2, false, m + 8);
+  iv(ivv);
+  blake3_cv(ivv, m, 0, 0, 64, 4u | (root ? 8u : 0u), h);
+}
+
+// bao's decoder top down over the units [first, first + cnt) whose stored node (cnt > 1) is node `pos`: `want` is what the stored data
+// above expects here, `bad` whether a node above failed
+static void host_verify_walk(const uint8_t *data, uint64_t len, uint64_t n, uint32_t gl, const uint8_t *nodes, uint64_t first, uint64_t cnt, uint64_t pos,
+                             const uint32_t want[8], bool bad, bool root, uint8_t *status) {
+  if (cnt == 1) {
+    const uint64_t c0 = first << gl, gn = n - c0 < (1ull << gl) ? n - c0 : (1ull << gl);
+    uint32_t h[8];
+    host_subtree_cv(data, len, c0, gn, root, h);
+    status[first] = bad ? 2 : memcmp(h, want, 32) != 0 ? 1 : 0;
+    return;
+  }
+  uint32_t mw[16], ivv[8], o[8];
+  for (int k = 0; k < 16; ++k) {
+    const uint8_t *b = nodes + 64 * pos + 4 * k;
+    mw[k] = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
+  }
+  iv(ivv);
+  blake3_cv(ivv, mw, 0, 0, 64, 4u | (root ? 8u : 0u), o);
+  if (memcmp(o, want, 32) != 0) bad = true;
+  uint64_t k2 = 1;
+  while (k2 * 2 < cnt) k2 *= 2;
+  host_verify_walk(data, len, n, gl, nodes, first, k2, pos + 1, mw, bad, false, status);
+  host_verify_walk(data, len, n, gl, nodes, first + k2, cnt - k2, pos + k2, mw + 8, bad, false, status);
+}
+
+int32_t b3w_bao_verify(const uint8_t *data, uint64_t len, const uint8_t *outboard, uint32_t group_log, const uint32_t *root, uint8_t *unit_status,
+                       int32_t *file_status, uint64_t *first_bad) {
+  if ((!data && len) || !outboard || !root || !unit_status || group_log > B3W_BAO_MAX_GROUP_LOG) return B3W_E_BAD_ARGUMENT;
+  const uint64_t n = num_chunks(len), n_units = (n + ((1ull << group_log) - 1)) >> group_log;
+  uint64_t hdr = 0;
+  for (int k = 0; k < 8; ++k) hdr |= (uint64_t)outboard[k] << (8 * k);
+  if (hdr != len) memset(unit_status, 3, (size_t)n_units);
+  else host_verify_walk(data, len, n, group_log, outboard + 8, 0, n_units, 0, root, false, true, unit_status);
+  int32_t worst = 0;
+  uint64_t first = ~0ull;
+  for (uint64_t u = 0; u < n_units; ++u) {
+    if (unit_status[u] > worst) worst = unit_status[u];
+    if (unit_status[u] && first == ~0ull) first = u;
+  }
+  if (file_status) *file_status = worst;
+  if (first_bad) *first_bad = first;
   return B3W_OK;
 }
 

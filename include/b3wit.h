@@ -703,6 +703,48 @@ int32_t b3w_sample_plan_slices_device(b3w_ctx *ctx, const uint64_t *host_lens, u
                                       const uint32_t *host_files, const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_slices,
                                       uint32_t *d_records, int32_t *d_sample_status, void *stream);
 
+/* ---- verification: whole files against their outboards (still ABI 1.4: new names only) ---------------------------
+ * Bao's decoder applied to every UNIT of a file at once, for the party that takes files and outboards in, scrubs what it stores or
+ * repairs after a fault.  A unit is a chunk (group_log = 0, full outboards) or a group of 2^group_log chunks (group outboards); a
+ * file has max(1, ceil(n_chunks / 2^group_log)) of them.  A unit's status is the status b3w_sample_plan_batch_device /
+ * b3w_sample_plan_group_batch_device give a sample in that unit, the first rule that applies:
+ *   3  the outboard's 8-byte header is not the file's length (every unit of the file)
+ *   2  a stored node on the unit's path fails: the root node hashed with PARENT | ROOT is not the file's root, or a lower stored
+ *      node hashed with PARENT is not its half of the stored node above it
+ *   1  the unit's CV, computed from the file's bytes (the levels inside a group recomputed), is not its half of the lowest stored
+ *      node on its path; a file of one unit has no stored node: its ROOT-flagged CV is held against the root (a wrong root: 1)
+ *   0  otherwise
+ * Every node check is stored data against stored data, so one bad byte of a chunk marks that unit alone (1), one bad byte of a
+ * node exactly the units below that node (2), a wrong root every unit of that file and no other file. */
+/* Host only.  Statuses of a batch are packed in file order, one byte a unit: file f's are entries [unit_first[f], unit_first[f + 1])
+ * of d_unit_status.  unit_first: n_files + 1 entries, the last one the total, which is also returned (0 for a group_log above
+ * B3W_BAO_MAX_GROUP_LOG or a null pointer). */
+uint64_t b3w_bao_verify_layout(const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, uint64_t *unit_first);
+/* Host only.  Bytes of caller's scratch b3w_bao_verify_batch_device needs for these lengths: the CV expected of a tile and a flag
+ * (36 bytes) per tile of 1 024 chunks of the files of more than one tile, the same per 1 024 tiles of the files of more than
+ * 1 024 tiles, rounded up to 16; 0 where no file has more than one tile. */
+uint64_t b3w_bao_verify_scratch_bytes(const uint64_t *host_lens, uint32_t n_files);
+/* Files as b3w_bao_outboard_batch_device takes them ([host_offsets[f], + host_lens[f]) of d_arena, any offsets); d_outboards packed
+ * as b3w_bao_batch_layout (group_log = 0) or b3w_bao_group_batch_layout says, 8-byte aligned; d_roots: 8 u32 per file ON THE
+ * DEVICE.  Outputs, all on the device, none needs clearing: d_unit_status, one byte a unit, packed as b3w_bao_verify_layout says;
+ * d_file_status[f], the largest status among file f's units; d_first_bad[f] (8-byte aligned), the lowest unit index of file f
+ * with a non-zero status, or UINT64_MAX.  Nothing is read back to the host.  At most four launches whatever the file count — no
+ * more than the outboard call's: the nodes above the tiles are checked first, from the stored nodes alone (one launch, one more
+ * for files past 1 GiB), then the files of at most 64 chunks and the tiles of the others write final statuses.  d_scratch: 16-byte
+ * aligned, b3w_bao_verify_scratch_bytes; the per-file tables go through the context's staging, nothing else is allocated.
+ * n_files == 0: a no-op.  B3W_E_BAD_ARGUMENT before anything is written for a group_log above the maximum, a null or misaligned
+ * pointer, a small scratch, a null arena with a file that is not empty, or a file of more than 2^30 chunks.  Any context.
+ * Asynchronous on `stream`; waits for this context's previous batch call. */
+int32_t b3w_bao_verify_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, const uint64_t *host_offsets, const uint64_t *host_lens,
+                                    uint32_t n_files, uint32_t group_log, const uint8_t *d_outboards, const uint32_t *d_roots,
+                                    uint8_t *d_unit_status, int32_t *d_file_status, uint64_t *d_first_bad, void *d_scratch,
+                                    uint64_t scratch_bytes, void *stream);
+/* Host only, one file, for callers without a GPU: the same statuses from `data` (len bytes), its outboard (full, or the group
+ * outboard of group_log) and the root (8 u32).  unit_status: room for max(1, ceil(n_chunks / 2^group_log)) bytes; file_status and
+ * first_bad may be NULL.  B3W_E_BAD_ARGUMENT for a null pointer or a group_log above the maximum. */
+int32_t b3w_bao_verify(const uint8_t *data, uint64_t len, const uint8_t *outboard, uint32_t group_log, const uint32_t *root /* 8 u32 */,
+                       uint8_t *unit_status, int32_t *file_status, uint64_t *first_bad);
+
 #ifdef __cplusplus
 }
 #endif
