@@ -190,6 +190,12 @@ def lib():
         "b3w_bao_verify_scratch_bytes": (u64, [vp, u32]),
         "b3w_bao_verify_batch_device": (i32, [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, u64, vp]),
         "b3w_bao_verify": (i32, [vp, u64, vp, u32, vp, vp, ctypes.POINTER(i32), ctypes.POINTER(u64)]),
+        "b3w_bao_stream_scratch_bytes": (u64, [u64, u32]),
+        "b3w_bao_stream_outboard_begin": (i32, [vp, u64, u32, vp, vp, vp, u64, ctypes.POINTER(vp)]),
+        "b3w_bao_stream_verify_begin": (i32, [vp, u64, u32, vp, vp, vp, vp, vp, vp, u64, vp, ctypes.POINTER(vp)]),
+        "b3w_bao_stream_push": (i32, [vp, u64, vp, u64, vp]),
+        "b3w_bao_stream_finish": (i32, [vp, vp]),
+        "b3w_bao_stream_free": (None, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -216,7 +222,9 @@ EXPORTED_SYMBOLS = ("b3w_abi_version", "b3w_identify_wasm", "b3w_create", "b3w_d
                     "b3w_bao_group_path_nodes", "b3w_bao_group_outboard_batch_device", "b3w_sample_plan_group_batch_device",
                     "b3w_bao_slice_size", "b3w_bao_slice_batch_layout", "b3w_bao_slice_decode", "b3w_bao_slice_batch_device",
                     "b3w_sample_plan_slices_device",
-                    "b3w_bao_verify_layout", "b3w_bao_verify_scratch_bytes", "b3w_bao_verify_batch_device", "b3w_bao_verify")
+                    "b3w_bao_verify_layout", "b3w_bao_verify_scratch_bytes", "b3w_bao_verify_batch_device", "b3w_bao_verify",
+                    "b3w_bao_stream_scratch_bytes", "b3w_bao_stream_outboard_begin", "b3w_bao_stream_verify_begin", "b3w_bao_stream_push",
+                    "b3w_bao_stream_finish", "b3w_bao_stream_free")
 
 
 class graph_capture:

@@ -9,7 +9,9 @@ outboard_groups_batch(), plan_samples_groups_batch() and prove_samples_groups_ba
 2^group_log chunks, 2^group_log times smaller, and recompute the levels inside a group from the group's bytes.  slices_batch() extracts the standard bao slices of challenged chunks from either kind
 of outboard and plan_samples_slices() / prove_samples_slices() plan and prove from slices alone, so the prover need not hold the
 outboards (decode_slice(): the host decoder).  verify_batch() is bao's decoder over whole files: every chunk (or chunk group) of
-every file of a batch held against its outboard and root on the device, a status per unit (verify_host(): one file on the host).
+every file of a batch held against its outboard and root on the device, a status per unit (verify_host(): one file on the host).  StreamOutboard / StreamVerify take ONE file window by window (whole MiB, any order, any
+stream) with the batch calls' results, and outboard_stream() / verify_stream() feed them from host memory or a reader through a ring
+of windows: the file need never be resident on the device.
 The records are
 word for word those the chain planner writes for the same chunks (ChainPlanner.plan), so every step is the reference's
 prove_chunk_hash step (rust_fold/src/main.rs:41-203 over hash_with_path's slice, rust_fold/src/blake3_hash.rs:17-93)."""
@@ -43,7 +45,8 @@ def outboard_size(length):
 def outboard(ctx, d_preimage, stream=0):
     """-> (uint8 CUDA tensor: the bao outboard, root words as uint32 numpy [8] = BLAKE3(preimage)).
     d_preimage: a uint8 CUDA tensor (the device-resident case this is built for), or host bytes — those are copied to the device
-    first, and for a large file that copy takes far longer than the outboard itself."""
+    first, and for a large file that copy takes far longer than the outboard itself (outboard_stream hashes behind the copy, a window
+    at a time, without the file ever being resident)."""
     if not isinstance(d_preimage, torch.Tensor):
         d_preimage = torch.from_numpy(np.frombuffer(bytes(d_preimage), dtype=np.uint8).copy()).cuda()
     assert d_preimage.is_cuda and d_preimage.dtype == torch.uint8 and d_preimage.is_contiguous()
@@ -509,3 +512,177 @@ def verify_host(data, outboard, root, group_log=0):
     fs, fb = ctypes.c_int32(), ctypes.c_uint64()
     _chk(None, lib().b3w_bao_verify(data, len(data), ob, group_log, rw.ctypes.data, st.ctypes.data, ctypes.byref(fs), ctypes.byref(fb)), "b3w_bao_verify")
     return st, fs.value, fb.value
+
+
+# ---- files streamed in windows ---------------------------------------------------------------------------------------------
+TILE_BYTES = 1 << 20                                   # a window is whole tiles of 1 024 chunks, except where it ends the file
+STREAM_OUTBOARD, STREAM_VERIFY = 0, 1
+DEFAULT_WINDOW_BYTES = 64 << 20                        # the fastest of 4, 16 and 64 MiB from host memory (a push's fixed 0.11 ms is 10 % of its copy)
+
+
+def stream_scratch_bytes(length, kind):
+    return lib().b3w_bao_stream_scratch_bytes(length, kind)
+
+
+def windows(length, window_bytes):
+    """-> [(offset, bytes)]: the windows outboard_stream / verify_stream push, in order: whole windows of window_bytes (a positive
+    multiple of 1 MiB), then what is left; they cover [0, length) exactly once.  An empty file has none."""
+    if window_bytes <= 0 or window_bytes % TILE_BYTES:
+        raise B3WError(100, f"window_bytes {window_bytes} is not a positive multiple of 1 MiB")
+    return [(off, min(window_bytes, length - off)) for off in range(0, length, window_bytes)]
+
+
+class _Stream:
+    """the session's handle and the calls both kinds share"""
+
+    def __init__(self, ctx, length, group_log):
+        self._h = ctypes.c_void_p()
+        if not 0 <= group_log <= MAX_GROUP_LOG:
+            raise B3WError(100, f"group_log {group_log} is not in 0 .. {MAX_GROUP_LOG}")
+        self.ctx, self.length, self.group_log = ctx, int(length), group_log
+
+    def push(self, offset, d_window, stream=0):
+        """the file's bytes [offset, offset + d_window.numel()) lie in d_window (a uint8 CUDA tensor, any alignment): one launch on
+        `stream`.  offset: a multiple of 1 MiB; the size: a multiple of 1 MiB unless the window ends the file.  Any order, any stream."""
+        assert d_window.is_cuda and d_window.dtype == torch.uint8 and d_window.is_contiguous()
+        _chk(self.ctx, lib().b3w_bao_stream_push(self._h, offset, d_window.data_ptr(), d_window.numel(), _stream(stream)), "b3w_bao_stream_push")
+
+    def _finish(self, stream):
+        _chk(self.ctx, lib().b3w_bao_stream_finish(self._h, _stream(stream)), "b3w_bao_stream_finish")
+
+    def close(self):
+        if self._h:
+            lib().b3w_bao_stream_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        self.close()
+
+
+class StreamOutboard(_Stream):
+    """The outboard (group_log = 0: full; 1 .. 6: over chunk groups) and root of ONE file of `length` bytes pushed window by window:
+    push(offset, d_window, stream) per window, then finish(stream), which the caller orders behind every push.  The session makes the
+    outboard, the root and the scratch on the device and nothing that grows with the file's bytes."""
+
+    def __init__(self, ctx, length, group_log=0, device="cuda"):
+        super().__init__(ctx, length, group_log)
+        self.ob_first = group_batch_layout([self.length], group_log)
+        self.outboards = torch.empty(int(self.ob_first[-1]), dtype=torch.uint8, device=device)
+        self.roots = torch.empty((1, 8), dtype=torch.int32, device=device)
+        need = stream_scratch_bytes(self.length, STREAM_OUTBOARD)
+        self.scratch = torch.empty(need, dtype=torch.uint8, device=device)
+        _chk(ctx, lib().b3w_bao_stream_outboard_begin(ctx.handle, self.length, group_log, self.outboards.data_ptr(), self.roots.data_ptr(),
+                                                      self.scratch.data_ptr() if need else None, need, ctypes.byref(self._h)), "b3w_bao_stream_outboard_begin")
+
+    def finish(self, stream=0):
+        """-> the dict outboard_batch / outboard_groups_batch return for this file as a batch of one"""
+        self._finish(stream)
+        return dict(outboards=self.outboards, ob_first=self.ob_first, roots=self.roots)
+
+
+class StreamVerify(_Stream):
+    """verify_batch for ONE file pushed window by window against its resident outboard and root.  The statuses of a window's units
+    (self.unit_status) are final once that push's work on its stream is done: a bad window shows before the next one arrives."""
+
+    def __init__(self, ctx, length, d_outboard, d_root, group_log=0, stream=0):
+        super().__init__(ctx, length, group_log)
+        dev = d_outboard.device
+        self.unit_first = verify_layout([self.length], group_log)
+        assert d_outboard.is_cuda and d_outboard.dtype == torch.uint8 and d_outboard.is_contiguous()
+        assert d_outboard.numel() >= group_outboard_size(self.length, group_log)
+        assert d_root.is_cuda and d_root.is_contiguous() and d_root.element_size() == 4 and d_root.numel() >= 8
+        self.d_outboard, self.d_root = d_outboard, d_root
+        self.unit_status = torch.empty(int(self.unit_first[-1]), dtype=torch.uint8, device=dev)
+        self.file_status = torch.empty(1, dtype=torch.int32, device=dev)
+        self.first_bad = torch.empty(1, dtype=torch.int64, device=dev)
+        need = stream_scratch_bytes(self.length, STREAM_VERIFY)
+        self.scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        _chk(ctx, lib().b3w_bao_stream_verify_begin(ctx.handle, self.length, group_log, d_outboard.data_ptr(), d_root.data_ptr(),
+                                                    self.unit_status.data_ptr(), self.file_status.data_ptr(), self.first_bad.data_ptr(),
+                                                    self.scratch.data_ptr() if need else None, need, _stream(stream), ctypes.byref(self._h)),
+             "b3w_bao_stream_verify_begin")
+
+    def finish(self, stream=0):
+        """-> the dict verify_batch returns for this file as a batch of one"""
+        self._finish(stream)
+        return dict(unit_status=self.unit_status, unit_first=self.unit_first, file_status=self.file_status, first_bad=self.first_bad)
+
+
+def _reader(source, length):
+    """-> fill(dst, offset): dst (a writable numpy uint8 view) takes the source's bytes from `offset` on"""
+    if hasattr(source, "readinto"):
+        def fill(dst, offset):                          # (read in order: the offset is where the reader stands)
+            view, got = memoryview(dst), 0
+            while got < len(view):
+                k = source.readinto(view[got:])
+                if not k:
+                    raise B3WError(100, f"the source ended at byte {offset + got}, before the length given ({length})")
+                got += k
+        return fill
+    data = np.frombuffer(source, dtype=np.uint8) if not isinstance(source, np.ndarray) else source.reshape(-1).view(np.uint8)
+    if data.size < length:
+        raise B3WError(100, f"the source holds {data.size} bytes, fewer than the length given ({length})")
+
+    def fill(dst, offset):
+        dst[:] = data[offset:offset + dst.size]
+    return fill
+
+
+def _pump(session, source, length, window_bytes, ring):
+    """the windows of `source` through `ring` pinned host buffers and `ring` device windows, each on a stream of its own: window i's
+    copy, push and buffer-reuse event stay on stream i mod ring; the current stream ends up behind all of them"""
+    if ring < 1:
+        raise B3WError(100, "ring must be at least 1")
+    wins = windows(length, window_bytes)
+    size = max((b for _, b in wins), default=0)
+    cur = torch.cuda.current_stream()
+    # a pinned uint8 tensor is copied from where it lies: no host buffers, the device windows alone
+    direct = source.reshape(-1) if isinstance(source, torch.Tensor) and source.dtype == torch.uint8 and source.is_pinned() else None
+    if direct is not None and direct.numel() < length:
+        raise B3WError(100, f"the source holds {direct.numel()} bytes, fewer than the length given ({length})")
+    fill = _reader(source.numpy() if isinstance(source, torch.Tensor) else source, length) if wins and direct is None else None
+    slots = [(torch.empty(size if direct is None else 0, dtype=torch.uint8, pin_memory=True), torch.empty(size, dtype=torch.uint8, device="cuda"),
+              torch.cuda.Stream(), torch.cuda.Event()) for _ in range(min(ring, len(wins)))]
+    for _, _, s, _ in slots:
+        s.wait_stream(cur)                              # (what the caller enqueued before, e.g. the outboard's arrival, comes first)
+    for i, (off, nb) in enumerate(wins):
+        h, d, s, ev = slots[i % len(slots)]
+        if direct is None:
+            if i >= len(slots):
+                ev.synchronize()                        # the slot's last copy and push are through with both buffers
+            fill(h.numpy()[:nb], off)
+        with torch.cuda.stream(s):                      # (the device window's reuse is ordered by its stream)
+            d[:nb].copy_(h[:nb] if direct is None else direct[off:off + nb], non_blocking=True)
+            session.push(off, d[:nb], stream=s.cuda_stream)
+            ev.record(s)
+    for _, _, s, _ in slots:
+        cur.wait_stream(s)
+
+
+def outboard_stream(ctx, source, length, window_bytes=DEFAULT_WINDOW_BYTES, group_log=0, ring=2):
+    """The outboard and root of a file that is NOT resident on the device: `source` (bytes-like, a numpy buffer, or an object with
+    readinto, read in order) goes through `ring` pinned host buffers and `ring` device windows of window_bytes (a multiple of 1 MiB),
+    each on a stream of its own, so window i + 1 is copied while window i is hashed.  A source that is a pinned uint8 torch tensor is
+    copied from where it lies, without the host buffers (filling them is the slow part: one host thread's memcpy).  Device memory made here is ring x window_bytes +
+    the outboard + the scratch (32 bytes per MiB of file), WHATEVER THE FILE'S LENGTH — outboard_batch needs the whole file resident.
+    Returns the dict outboard_batch / outboard_groups_batch return for this file as a batch of one; the work is enqueued, the
+    current stream ordered behind it."""
+    session = StreamOutboard(ctx, length, group_log)
+    try:
+        _pump(session, source, length, window_bytes, ring)
+        return session.finish()
+    finally:
+        session.close()
+
+
+def verify_stream(ctx, source, length, d_outboard, d_root, window_bytes=DEFAULT_WINDOW_BYTES, group_log=0, ring=2):
+    """verify_batch for a file that is not resident on the device, against its resident outboard (d_outboard, full or over groups of
+    2^group_log chunks) and root (d_root): the windows go as in outboard_stream.  Device memory made here is ring x window_bytes + the
+    statuses (a byte a unit) + the scratch (36 bytes per MiB of file), whatever the file's length.  Returns the dict verify_batch
+    returns for this file as a batch of one."""
+    session = StreamVerify(ctx, length, d_outboard, d_root, group_log)
+    try:
+        _pump(session, source, length, window_bytes, ring)
+        return session.finish()
+    finally:
+        session.close()

@@ -28,6 +28,8 @@
 //                            checked side by side, the parent records without the running-h chain where that chain is redundant
 //   b3w_bao_verify_*_kernel  whole files against their outboards: the three batch kernels with every store of a node turned into a check of
 //                            the stored node, the storey above the tiles first; a status per chunk or chunk group ("verification")
+//   b3w_bao_stream_*_kernel  one file whose bytes arrive in windows of whole tiles: the tile, merge and verify kernels with the file's entry
+//                            by value and the tiles' bytes taken from the window ("streamed files")
 #include "b3w_internal.h"
 #include "b3w_blake3_dev.h"
 
@@ -1107,6 +1109,154 @@ __global__ __launch_bounds__(64) void b3w_bao_verify_small_kernel(const uint8_t 
   }
 }
 
+// ---- streamed files: one file of known length whose bytes arrive in windows of whole tiles -------------------------------------
+// A tile is a subtree of the file's tree whatever else is known of the file, and the place of every node below its root follows from
+// the file's length and the tile's ABSOLUTE index alone.  So the kernels of a window are the tile kernels with the file's entry by value
+// (no table in device memory: a push uploads nothing) and the tile's bytes taken from the window, not from arena + offset:
+//   b3w_bao_stream_tile[_group]_kernel   a workgroup per tile of the window: tile_body's work, the tile's CV to scratch slot `tile`.
+//                                        A file of one tile, down to one chunk (ROOT on the chunk) or no byte at all, ends here too:
+//                                        its root and header, the bytes the small kernel writes for it
+//   b3w_bao_stream_merge[_group]_kernel  finish: merge_body over the tile CVs in scratch (files past 1 GiB: once more over the groups')
+//   b3w_bao_stream_upper_kernel          verification, at begin: the upper kernel's work for the one file, from the stored nodes alone
+//   b3w_bao_stream_verify_kernel         a workgroup per tile of the window: the verify tile kernel's work, exp_cv / bad read at `tile`
+// The merge and verify bodies (merge_in_lds, verify_in_lds) are the batch kernels' own, lds_barrier() around their level loops included.
+__device__ __forceinline__ void stream_chunk_cv(uint32_t *cv, const uint8_t *__restrict__ window, uint64_t len, uint64_t n, uint64_t a0, uint32_t m) {
+  if (threadIdx.x < m) {
+    const uint64_t c = a0 + threadIdx.x, off = c * 1024;
+    uint32_t h[8];
+    chunk_cv(window + ((uint64_t)blockIdx.x * B3W_TILE + threadIdx.x) * 1024, (uint32_t)(len - off < 1024 ? len - off : 1024), c, n == 1 ? 8u : 0u, h);
+    reinterpret_cast<uint4 *>(cv + threadIdx.x * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
+    reinterpret_cast<uint4 *>(cv + threadIdx.x * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
+  }
+}
+
+// window: the bytes of the file from tile `tile0` on; workgroup w takes tile tile0 + w
+template <bool GRP>
+__device__ __forceinline__ void stream_tile_body(const uint8_t *__restrict__ window, uint64_t len, uint32_t tile0, uint8_t *__restrict__ ob,
+                                                 uint32_t *__restrict__ root, uint32_t *__restrict__ tile_cv, uint32_t gl) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
+  const uint64_t n = len ? (len + 1023) / 1024 : 1;
+  const uint64_t tile = (uint64_t)tile0 + blockIdx.x, a0 = tile * B3W_TILE;
+  const uint32_t m = (uint32_t)(n - a0 < B3W_TILE ? n - a0 : B3W_TILE);
+  const bool sole = n <= B3W_TILE;
+  stream_chunk_cv(cv, window, len, n, a0, m);
+  if (a0 == 0 && threadIdx.x == 0) *reinterpret_cast<uint2 *>(ob) = make_uint2((uint32_t)len, (uint32_t)(len >> 32));
+  const uint64_t G1 = GRP ? (1ull << gl) - 1 : 0;                     // (a tile starts at a multiple of every group size)
+  merge_in_lds<B3W_TILE, GRP>(cv, m, 1, m, ob + 8 + (GRP ? preorder_pos((n + G1) >> gl, a0 >> gl, (m + G1) >> gl) : preorder_pos(n, a0, m)) * 64, sole, gl);
+  if (threadIdx.x < 8) (sole ? root : tile_cv + tile * 8)[threadIdx.x] = cv[threadIdx.x];
+}
+
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_tile_kernel(const uint8_t *__restrict__ window, uint64_t len, uint32_t tile0,
+                                                                       uint8_t *__restrict__ ob, uint32_t *__restrict__ root,
+                                                                       uint32_t *__restrict__ tile_cv) {
+  stream_tile_body<false>(window, len, tile0, ob, root, tile_cv, 0);
+}
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_tile_group_kernel(const uint8_t *__restrict__ window, uint64_t len, uint32_t tile0,
+                                                                             uint8_t *__restrict__ ob, uint32_t *__restrict__ root,
+                                                                             uint32_t *__restrict__ tile_cv, uint32_t gl) {
+  stream_tile_body<true>(window, len, tile0, ob, root, tile_cv, gl);
+}
+
+// merge_body for the one file (more than one tile): workgroup g merges items [1 024 g, ...) of in_cv, its CV to out_cv slot g or the root
+template <bool GRP>
+__device__ __forceinline__ void stream_merge_body(uint64_t len, uint64_t unit, const uint32_t *__restrict__ in_cv, uint32_t *__restrict__ out_cv,
+                                                  uint8_t *__restrict__ ob, uint32_t *__restrict__ root, uint32_t gl) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
+  const uint64_t n = (len + 1023) / 1024;
+  const uint64_t g = blockIdx.x, span = unit * B3W_TILE, a0 = g * span;
+  const uint64_t tot = n - a0 < span ? n - a0 : span;
+  const uint32_t cnt = (uint32_t)((tot + unit - 1) / unit);
+  const bool sole = n <= span;
+  const uint4 *src = reinterpret_cast<const uint4 *>(in_cv + g * B3W_TILE * 8);
+  for (uint32_t i = threadIdx.x; i < cnt * 2; i += 256) reinterpret_cast<uint4 *>(cv)[i] = src[i];
+  const uint64_t G1 = GRP ? (1ull << gl) - 1 : 0;                     // (every node here is over more than a tile: all of them are stored)
+  merge_in_lds<256, GRP>(cv, cnt, unit, tot, ob + 8 + (GRP ? preorder_pos((n + G1) >> gl, a0 >> gl, (tot + G1) >> gl) : preorder_pos(n, a0, tot)) * 64, sole, gl);
+  if (threadIdx.x < 8) (sole ? root : out_cv + g * 8)[threadIdx.x] = cv[threadIdx.x];
+}
+
+__global__ __launch_bounds__(256) void b3w_bao_stream_merge_kernel(uint64_t len, uint64_t unit, const uint32_t *__restrict__ in_cv,
+                                                                   uint32_t *__restrict__ out_cv, uint8_t *__restrict__ ob, uint32_t *__restrict__ root) {
+  stream_merge_body<false>(len, unit, in_cv, out_cv, ob, root, 0);
+}
+__global__ __launch_bounds__(256) void b3w_bao_stream_merge_group_kernel(uint64_t len, uint64_t unit, const uint32_t *__restrict__ in_cv,
+                                                                         uint32_t *__restrict__ out_cv, uint8_t *__restrict__ ob,
+                                                                         uint32_t *__restrict__ root, uint32_t gl) {
+  stream_merge_body<true>(len, unit, in_cv, out_cv, ob, root, gl);
+}
+
+// b3w_bao_verify_upper_kernel for the one file (more than one tile).  Scratch entries as there: the tiles' (n_tile_ents), then the groups'.
+__global__ __launch_bounds__(256) void b3w_bao_stream_upper_kernel(uint64_t len, uint64_t unit, uint64_t n_tile_ents, const uint8_t *__restrict__ ob8,
+                                                                   const uint32_t *__restrict__ root, uint32_t *__restrict__ exp_cv,
+                                                                   uint32_t *__restrict__ bad, uint32_t gl, int32_t *__restrict__ file_status,
+                                                                   unsigned long long *__restrict__ first_bad) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
+  __shared__ uint32_t flags[B3W_TILE];
+  const uint64_t n = (len + 1023) / 1024;
+  const uint64_t g = blockIdx.x, span = unit * B3W_TILE, a0 = g * span;
+  const uint64_t tot = n - a0 < span ? n - a0 : span;
+  const uint32_t cnt = (uint32_t)((tot + unit - 1) / unit);
+  const bool sole = n <= span;                                        // the file's top workgroup
+  const uint64_t out0 = unit == B3W_TILE ? g * B3W_TILE : n_tile_ents, in = n_tile_ents + g;
+  const uint32_t *want = sole ? root : exp_cv + in * 8;
+  bool above = sole ? false : bad[in] != 0;
+  const uint32_t *ob = reinterpret_cast<const uint32_t *>(ob8);
+  if (sole && threadIdx.x == 0) {                                     // (the windows' kernels, which run after this one, add to these)
+    const bool hdr = ((uint64_t)ob[0] | ((uint64_t)ob[1] << 32)) != len;
+    *file_status = hdr ? 3 : 0;
+    *first_bad = hdr ? 0ull : ~0ull;
+  }
+  if (cnt == 1) {                                                     // a lone last tile (or group) hangs straight off the storey above
+    if (threadIdx.x < 8) exp_cv[out0 * 8 + threadIdx.x] = want[threadIdx.x];
+    if (threadIdx.x == 0) bad[out0] = above;
+    return;
+  }
+  for (uint32_t i = threadIdx.x; i < cnt; i += 256) flags[i] = 0;
+  const uint64_t G1 = (1ull << gl) - 1;
+  verify_in_lds<256, false>(cv, flags, cnt, unit, tot, ob8 + 8 + preorder_pos((n + G1) >> gl, a0 >> gl, (tot + G1) >> gl) * 64, sole, gl, exp_cv + out0 * 8);
+  above = above || !eq8(cv, want);
+  for (uint32_t t = threadIdx.x; t < cnt; t += 256) bad[out0 + t] = above || path_bad(flags, t);
+}
+
+// b3w_bao_verify_tile_kernel for the tiles of a window; a file of one tile, down to one chunk or no byte at all, is settled here whole
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_verify_kernel(const uint8_t *__restrict__ window, uint64_t len, uint32_t tile0,
+                                                                         const uint8_t *__restrict__ ob8, const uint32_t *__restrict__ root,
+                                                                         const uint32_t *__restrict__ exp_cv, const uint32_t *__restrict__ bad,
+                                                                         uint32_t gl, uint8_t *__restrict__ unit_status,
+                                                                         int32_t *__restrict__ file_status, unsigned long long *__restrict__ first_bad) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
+  __shared__ uint32_t flags[B3W_TILE];
+  __shared__ uint32_t worst, first;
+  const uint64_t n = len ? (len + 1023) / 1024 : 1;
+  const uint32_t t = threadIdx.x, G = 1u << gl;
+  const uint64_t tile = (uint64_t)tile0 + blockIdx.x, a0 = tile * B3W_TILE;
+  const uint32_t m = (uint32_t)(n - a0 < B3W_TILE ? n - a0 : B3W_TILE);
+  const bool sole = n <= B3W_TILE;
+  stream_chunk_cv(cv, window, len, n, a0, m);
+  flags[t] = 0;
+  if (t == 0) { worst = 0; first = ~0u; }
+  const uint32_t *ob = reinterpret_cast<const uint32_t *>(ob8);
+  const bool hdr = ((uint64_t)ob[0] | ((uint64_t)ob[1] << 32)) != len;
+  const uint64_t G1 = G - 1;
+  verify_in_lds<B3W_TILE, true>(cv, flags, m, 1, m, ob8 + 8 + preorder_pos((n + G1) >> gl, a0 >> gl, (m + G1) >> gl) * 64, sole, gl, nullptr);
+  if (t == 0 && !eq8(cv, sole ? root : exp_cv + tile * 8)) flags[0] |= m <= G ? VER_UNIT : VER_TOP;
+  const bool above = sole ? false : bad[tile] != 0;
+  lds_barrier();
+  if (t < m && (t & (G - 1)) == 0) {                                  // a unit's first chunk: its status
+    const uint32_t st = hdr ? 3u : above || path_bad(flags, t) ? 2u : (flags[t] & VER_UNIT) ? 1u : 0u;
+    unit_status[(a0 + t) >> gl] = (uint8_t)st;
+    if (st) { atomicMax(&worst, st); atomicMin(&first, t >> gl); }    // (LDS; a clean tile issues none)
+  }
+  __syncthreads();
+  if (t != 0) return;
+  if (sole) {
+    *file_status = (int32_t)worst;
+    *first_bad = worst ? (unsigned long long)first : ~0ull;
+  } else if (worst) {                                                 // (initialised at begin by the file's top workgroup of the storey above)
+    atomicMax(file_status, (int32_t)worst);
+    atomicMin(first_bad, (unsigned long long)((a0 >> gl) + first));
+  }
+}
+
 // the CV of a chunk on the host (chunk_cv's loop over blake3_cv): b3w_bao_slice_decode
 void host_chunk_cv(const uint8_t *src, uint32_t bytes, uint64_t c, uint32_t root, uint32_t h[8]) {
   const uint32_t nb = bytes ? (bytes + 63) / 64 : 1;
@@ -1798,6 +1948,171 @@ int32_t b3w_bao_verify(const uint8_t *data, uint64_t len, const uint8_t *outboar
   if (file_status) *file_status = worst;
   if (first_bad) *first_bad = first;
   return B3W_OK;
+}
+
+}  // extern "C"
+
+// ---- stream sessions: outboards and verification of a file pushed in windows ---------------------------------------------------
+// A host object: the file's shape, the caller's device pointers, a bit per tile pushed and (verification) the event behind which the
+// storeys above the tiles have left what each tile must hash to.  No device memory of its own.
+struct b3w_bao_stream {
+  b3w_ctx *ctx = nullptr;
+  uint32_t kind = 0, gl = 0;
+  uint64_t len = 0, tiles = 0, groups = 0, pushed = 0;
+  uint8_t *ob = nullptr;
+  uint32_t *root = nullptr;
+  uint8_t *unit_status = nullptr;
+  int32_t *file_status = nullptr;
+  unsigned long long *first_bad = nullptr;
+  uint32_t *scratch = nullptr;
+  hipEvent_t begun = nullptr;
+  bool finished = false;
+  std::vector<uint64_t> seen;
+};
+
+namespace {
+
+// the session's kernel over `count` tiles from tile `tile0`, their bytes at `window`
+void stream_launch_tiles(const b3w_bao_stream *s, const uint8_t *window, uint32_t tile0, uint32_t count, hipStream_t st) {
+  if (s->kind == B3W_BAO_STREAM_VERIFY) {
+    const uint64_t n_scr = (s->tiles > 1 ? s->tiles : 0) + (s->groups > 1 ? s->groups : 0);
+    hipLaunchKernelGGL(b3w_bao_stream_verify_kernel, dim3(count), dim3(B3W_TILE), 0, st, window, s->len, tile0, (const uint8_t *)s->ob, (const uint32_t *)s->root,
+                       (const uint32_t *)s->scratch, (const uint32_t *)(s->scratch + n_scr * 8), s->gl, s->unit_status, s->file_status, s->first_bad);
+  } else if (s->gl) {
+    hipLaunchKernelGGL(b3w_bao_stream_tile_group_kernel, dim3(count), dim3(B3W_TILE), 0, st, window, s->len, tile0, s->ob, s->root, s->scratch, s->gl);
+  } else {
+    hipLaunchKernelGGL(b3w_bao_stream_tile_kernel, dim3(count), dim3(B3W_TILE), 0, st, window, s->len, tile0, s->ob, s->root, s->scratch);
+  }
+}
+
+int32_t stream_begin_checks(b3w_ctx *ctx, uint64_t len, uint32_t group_log, const void *d_outboard, const void *d_root, const void *d_scratch,
+                            uint64_t scratch_bytes, uint64_t need, b3w_bao_stream **out) {
+  if (!out) { ctx->last_error = "bao stream: a null session pointer"; return B3W_E_BAD_ARGUMENT; }
+  *out = nullptr;
+  if (group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "bao stream: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
+  if (num_chunks(len) > (1ull << 30)) { ctx->last_error = "bao stream: a file of more than 2^30 chunks"; return B3W_E_BAD_ARGUMENT; }
+  if (!d_outboard || !d_root) { ctx->last_error = "bao stream: a null pointer (outboard or root)"; return B3W_E_BAD_ARGUMENT; }
+  if (((uintptr_t)d_outboard & 7) || ((uintptr_t)d_root & 3)) { ctx->last_error = "bao stream: d_outboard is not 8-byte aligned, or d_root not 4-byte aligned"; return B3W_E_BAD_ARGUMENT; }
+  if (scratch_bytes < need) { ctx->last_error = "bao stream: the scratch is smaller than b3w_bao_stream_scratch_bytes says"; return B3W_E_BAD_ARGUMENT; }
+  if (need && (!d_scratch || ((uintptr_t)d_scratch & 15))) { ctx->last_error = "bao stream: the scratch is null or not 16-byte aligned"; return B3W_E_BAD_ARGUMENT; }
+  return B3W_OK;
+}
+
+b3w_bao_stream *stream_new(b3w_ctx *ctx, uint32_t kind, uint64_t len, uint32_t gl, void *d_scratch) {
+  b3w_bao_stream *s = new b3w_bao_stream;
+  s->ctx = ctx; s->kind = kind; s->gl = gl; s->len = len;
+  s->tiles = (num_chunks(len) + B3W_TILE - 1) / B3W_TILE;
+  s->groups = (s->tiles + B3W_TILE - 1) / B3W_TILE;
+  s->scratch = reinterpret_cast<uint32_t *>(d_scratch);
+  s->seen.assign((size_t)((s->tiles + 63) / 64), 0);
+  return s;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t b3w_bao_stream_scratch_bytes(uint64_t len, uint32_t kind) {
+  return kind == B3W_BAO_STREAM_OUTBOARD ? b3w_bao_batch_scratch_bytes(&len, 1) : kind == B3W_BAO_STREAM_VERIFY ? b3w_bao_verify_scratch_bytes(&len, 1) : 0;
+}
+
+int32_t b3w_bao_stream_outboard_begin(b3w_ctx *ctx, uint64_t len, uint32_t group_log, uint8_t *d_outboard, uint32_t *d_root, void *d_scratch,
+                                      uint64_t scratch_bytes, b3w_bao_stream **out_session) {
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  const int32_t rc = stream_begin_checks(ctx, len, group_log, d_outboard, d_root, d_scratch, scratch_bytes,
+                                         b3w_bao_stream_scratch_bytes(len, B3W_BAO_STREAM_OUTBOARD), out_session);
+  if (rc) return rc;
+  b3w_bao_stream *s = stream_new(ctx, B3W_BAO_STREAM_OUTBOARD, len, group_log, d_scratch);
+  s->ob = d_outboard; s->root = d_root;
+  *out_session = s;
+  return B3W_OK;
+}
+
+int32_t b3w_bao_stream_verify_begin(b3w_ctx *ctx, uint64_t len, uint32_t group_log, const uint8_t *d_outboard, const uint32_t *d_root,
+                                    uint8_t *d_unit_status, int32_t *d_file_status, uint64_t *d_first_bad, void *d_scratch, uint64_t scratch_bytes,
+                                    void *stream, b3w_bao_stream **out_session) {
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  const int32_t rc = stream_begin_checks(ctx, len, group_log, d_outboard, d_root, d_scratch, scratch_bytes,
+                                         b3w_bao_stream_scratch_bytes(len, B3W_BAO_STREAM_VERIFY), out_session);
+  if (rc) return rc;
+  if (!d_unit_status || !d_file_status || !d_first_bad) { ctx->last_error = "bao stream: a null output (unit status, file status or first bad)"; return B3W_E_BAD_ARGUMENT; }
+  if (((uintptr_t)d_first_bad & 7) || ((uintptr_t)d_file_status & 3)) { ctx->last_error = "bao stream: d_first_bad is not 8-byte aligned, or d_file_status not 4-byte aligned"; return B3W_E_BAD_ARGUMENT; }
+  ON_DEVICE(ctx);
+  b3w_bao_stream *s = stream_new(ctx, B3W_BAO_STREAM_VERIFY, len, group_log, d_scratch);
+  s->ob = const_cast<uint8_t *>(d_outboard); s->root = const_cast<uint32_t *>(d_root);
+  s->unit_status = d_unit_status; s->file_status = d_file_status; s->first_bad = reinterpret_cast<unsigned long long *>(d_first_bad);
+  if (s->tiles > 1) {                                                 // top down over the stored nodes alone, as the batch call begins
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t n_scr = s->tiles + (s->groups > 1 ? s->groups : 0);
+    uint32_t *exp_cv = s->scratch, *bad = exp_cv + n_scr * 8;
+    hipError_t e = hipEventCreateWithFlags(&s->begun, hipEventDisableTiming);
+    if (e != hipSuccess) { delete s; return hip_fail(ctx, e, "bao stream: hipEventCreateWithFlags"); }
+    if (s->groups > 1) hipLaunchKernelGGL(b3w_bao_stream_upper_kernel, dim3(1), dim3(256), 0, st, len, (uint64_t)B3W_TILE * B3W_TILE, s->tiles, d_outboard, d_root, exp_cv, bad, group_log, d_file_status, s->first_bad);
+    hipLaunchKernelGGL(b3w_bao_stream_upper_kernel, dim3((uint32_t)s->groups), dim3(256), 0, st, len, (uint64_t)B3W_TILE, s->tiles, d_outboard, d_root, exp_cv, bad, group_log, d_file_status, s->first_bad);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(s->begun, st);
+    if (e != hipSuccess) { (void)hipEventDestroy(s->begun); delete s; return hip_fail(ctx, e, "bao stream verify begin"); }
+  }
+  *out_session = s;
+  return B3W_OK;
+}
+
+int32_t b3w_bao_stream_push(b3w_bao_stream *s, uint64_t offset, const uint8_t *d_window, uint64_t bytes, void *stream) {
+  if (!s) return B3W_E_BAD_ARGUMENT;
+  b3w_ctx *ctx = s->ctx;
+  const uint64_t TB = (uint64_t)B3W_TILE * 1024;
+  if (s->finished) { ctx->last_error = "bao stream push: the session is finished"; return B3W_E_BAD_ARGUMENT; }
+  if (offset % TB) { ctx->last_error = "bao stream push: the offset is not a multiple of 1 MiB"; return B3W_E_BAD_ARGUMENT; }
+  if (!bytes || !d_window) { ctx->last_error = "bao stream push: an empty window or a null pointer"; return B3W_E_BAD_ARGUMENT; }
+  if (offset > s->len || bytes > s->len - offset) { ctx->last_error = "bao stream push: the window reaches past the file's end"; return B3W_E_BAD_ARGUMENT; }
+  if (bytes % TB && offset + bytes != s->len) { ctx->last_error = "bao stream push: the window is not whole tiles of 1 MiB and does not end at the file's end"; return B3W_E_BAD_ARGUMENT; }
+  const uint64_t t0 = offset / TB, cnt = (bytes + TB - 1) / TB;
+  for (uint64_t t = t0; t < t0 + cnt; ++t)
+    if (s->seen[t >> 6] >> (t & 63) & 1) { ctx->last_error = "bao stream push: tile " + std::to_string(t) + " was pushed before"; return B3W_E_BAD_ARGUMENT; }
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  if (s->begun) HIP_TRY(ctx, hipStreamWaitEvent(st, s->begun, 0));    // (on the device: the host waits for nothing)
+  stream_launch_tiles(s, d_window, (uint32_t)t0, (uint32_t)cnt, st);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(ctx, e, "bao stream push launch");
+  for (uint64_t t = t0; t < t0 + cnt; ++t) s->seen[t >> 6] |= 1ull << (t & 63);
+  s->pushed += cnt;
+  return B3W_OK;
+}
+
+int32_t b3w_bao_stream_finish(b3w_bao_stream *s, void *stream) {
+  if (!s) return B3W_E_BAD_ARGUMENT;
+  b3w_ctx *ctx = s->ctx;
+  if (s->finished) { ctx->last_error = "bao stream finish: the session is finished"; return B3W_E_BAD_ARGUMENT; }
+  if (s->len && s->pushed != s->tiles) {
+    ctx->last_error = "bao stream finish: " + std::to_string(s->tiles - s->pushed) + " of " + std::to_string(s->tiles) + " tiles have not been pushed";
+    return B3W_E_BAD_ARGUMENT;
+  }
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  if (!s->len) {                                                      // no byte, no push: the empty chunk's ROOT output, here
+    stream_launch_tiles(s, nullptr, 0, 1, st);
+  } else if (s->kind == B3W_BAO_STREAM_OUTBOARD && s->tiles > 1) {
+    uint32_t *tile_cv = s->scratch, *group_cv = tile_cv + s->tiles * 8;
+    const uint64_t T = B3W_TILE;
+    if (s->gl) {
+      hipLaunchKernelGGL(b3w_bao_stream_merge_group_kernel, dim3((uint32_t)s->groups), dim3(256), 0, st, s->len, T, (const uint32_t *)tile_cv, group_cv, s->ob, s->root, s->gl);
+      if (s->groups > 1) hipLaunchKernelGGL(b3w_bao_stream_merge_group_kernel, dim3(1), dim3(256), 0, st, s->len, T * T, (const uint32_t *)group_cv, (uint32_t *)nullptr, s->ob, s->root, s->gl);
+    } else {
+      hipLaunchKernelGGL(b3w_bao_stream_merge_kernel, dim3((uint32_t)s->groups), dim3(256), 0, st, s->len, T, (const uint32_t *)tile_cv, group_cv, s->ob, s->root);
+      if (s->groups > 1) hipLaunchKernelGGL(b3w_bao_stream_merge_kernel, dim3(1), dim3(256), 0, st, s->len, T * T, (const uint32_t *)group_cv, (uint32_t *)nullptr, s->ob, s->root);
+    }
+  }                                                                   // (verification: the windows' kernels have left the per-file outputs final)
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(ctx, e, "bao stream finish launch");
+  s->finished = true;
+  return B3W_OK;
+}
+
+void b3w_bao_stream_free(b3w_bao_stream *s) {
+  if (!s) return;
+  if (s->begun) (void)hipEventDestroy(s->begun);
+  delete s;
 }
 
 }  // extern "C"

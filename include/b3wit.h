@@ -745,6 +745,55 @@ int32_t b3w_bao_verify_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, const 
 int32_t b3w_bao_verify(const uint8_t *data, uint64_t len, const uint8_t *outboard, uint32_t group_log, const uint32_t *root /* 8 u32 */,
                        uint8_t *unit_status, int32_t *file_status, uint64_t *first_bad);
 
+/* ---- outboards and verification of a file streamed in windows (still ABI 1.4: new names only) ----------------------
+ * The calls above take the whole file resident in device memory.  A stream session takes ONE file of known length window by window,
+ * for the party that ingests from disk or the network and for files larger than device memory: the file's bytes need only be on the
+ * device a window at a time, and a window is 1 MiB (a tile of 1 024 chunks) or any multiple.  The session is a host object: it holds
+ * the caller's device pointers and a bit per tile pushed, and no device memory of its own.  Several sessions may be open on one
+ * context; one session is used by one host thread at a time.
+ * RESULTS are those of the batch calls for the same file as a batch of one, byte for byte: d_outboard and d_root after finish are
+ * what b3w_bao_outboard_batch_device (group_log = 0) or b3w_bao_group_outboard_batch_device write; d_unit_status, d_file_status and
+ * d_first_bad are what b3w_bao_verify_batch_device writes.
+ * REFUSALS are B3W_E_BAD_ARGUMENT with a b3w_last_error text; a refused call launches nothing and leaves the session as it was. */
+typedef struct b3w_bao_stream b3w_bao_stream;
+#define B3W_BAO_STREAM_OUTBOARD 0
+#define B3W_BAO_STREAM_VERIFY   1
+/* Host only.  Bytes of caller's scratch a session over a file of `len` bytes needs: b3w_bao_batch_scratch_bytes of the one length
+ * (kind B3W_BAO_STREAM_OUTBOARD: 32 bytes a tile and per 1 024 tiles) or b3w_bao_verify_scratch_bytes of it (B3W_BAO_STREAM_VERIFY);
+ * 0 for any other kind. */
+uint64_t b3w_bao_stream_scratch_bytes(uint64_t len, uint32_t kind);
+/* Opens an outboard session: group_log = 0 the full outboard (b3w_bao_outboard_size bytes at d_outboard), 1 .. B3W_BAO_MAX_GROUP_LOG
+ * the group outboard (b3w_bao_group_outboard_size).  d_outboard 8-byte aligned, d_root 8 u32 on the device, d_scratch 16-byte
+ * aligned; all three stay the caller's and must live until the work of finish is done.  Launches nothing.  Refused: a group_log
+ * above the maximum, a file of more than 2^30 chunks, a null or misaligned pointer, a small scratch. */
+int32_t b3w_bao_stream_outboard_begin(b3w_ctx *ctx, uint64_t len, uint32_t group_log, uint8_t *d_outboard, uint32_t *d_root, void *d_scratch,
+                                      uint64_t scratch_bytes, b3w_bao_stream **out_session);
+/* Opens a verification session against an outboard and a root that are resident (as they arrived from elsewhere); the outputs as
+ * b3w_bao_verify_batch_device's for one file (d_unit_status: max(1, ceil(n_chunks / 2^group_log)) bytes).  For a file of more than
+ * one tile it launches, on `stream`, the check of the stored nodes above the tiles (one launch, two past 1 GiB), which also
+ * initialises d_file_status and d_first_bad; every push waits for that work ON THE DEVICE (an event of the session), whatever
+ * stream it is given.  Refused as above, and for a null or misaligned output. */
+int32_t b3w_bao_stream_verify_begin(b3w_ctx *ctx, uint64_t len, uint32_t group_log, const uint8_t *d_outboard, const uint32_t *d_root,
+                                    uint8_t *d_unit_status, int32_t *d_file_status, uint64_t *d_first_bad, void *d_scratch,
+                                    uint64_t scratch_bytes, void *stream, b3w_bao_stream **out_session);
+/* The bytes [offset, offset + bytes) of the file lie at d_window (any byte alignment; 16-byte aligned windows take the fast loads).
+ * offset is a multiple of 1 MiB; bytes is a positive multiple of 1 MiB unless the window ends at the file's end.  Windows may come
+ * in any order and on any stream, each tile once.  One launch, a workgroup per tile of the window; nothing is allocated, no table is
+ * uploaded and the host waits for no earlier call.  d_window may be reused once this push's work on `stream` is done.
+ * Verification: the statuses of the window's units are FINAL once this push's work on `stream` is done, so a bad window can be
+ * dropped before the rest arrives.  Refused: an offset off a 1 MiB boundary, an empty window or a null pointer, a window that
+ * reaches past the file's end or that is not whole tiles and does not end at the file's end, a tile pushed before, a push after
+ * finish.  A file of no bytes takes no push. */
+int32_t b3w_bao_stream_push(b3w_bao_stream *session, uint64_t offset, const uint8_t *d_window, uint64_t bytes, void *stream);
+/* THE CALLER ORDERS `stream` BEHIND EVERY PUSH (the same stream, or events of the pushes' streams it has made `stream` wait for).
+ * Outboard sessions: the nodes above the tiles and the root from the tile CVs in the scratch (one launch for a file of more than
+ * one tile, two past 1 GiB; none for one tile, whose push wrote the root).  Verification: nothing is launched, the pushes have left
+ * d_file_status and d_first_bad final.  A file of no bytes gets its one launch here.  Refused: a tile that has not been pushed, a
+ * second finish. */
+int32_t b3w_bao_stream_finish(b3w_bao_stream *session, void *stream);
+/* Frees the host object (NULL: a no-op); work already enqueued is not waited for and needs nothing of the session. */
+void b3w_bao_stream_free(b3w_bao_stream *session);
+
 #ifdef __cplusplus
 }
 #endif
