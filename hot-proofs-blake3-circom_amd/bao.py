@@ -8,7 +8,8 @@ plan_samples_batch() and prove_samples_batch() do the same for a whole batch of 
 outboard_groups_batch(), plan_samples_groups_batch() and prove_samples_groups_batch() keep the outboards over chunk groups of
 2^group_log chunks, 2^group_log times smaller, and recompute the levels inside a group from the group's bytes.  slices_batch() extracts the standard bao slices of challenged chunks from either kind
 of outboard and plan_samples_slices() / prove_samples_slices() plan and prove from slices alone, so the prover need not hold the
-outboards (decode_slice(): the host decoder).  verify_batch() is bao's decoder over whole files: every chunk (or chunk group) of
+outboards (decode_slice(): the host decoder).  plan_samples_arena() / prove_samples_arena() / slices_arena() are the provider's calls
+without the gather: the sampled bytes are read where the files lie in the arena outboard_batch() took, at any byte offset.  verify_batch() is bao's decoder over whole files: every chunk (or chunk group) of
 every file of a batch held against its outboard and root on the device, a status per unit (verify_host(): one file on the host).  StreamOutboard / StreamVerify take ONE file window by window (whole MiB, any order, any
 stream) with the batch calls' results, and outboard_stream() / verify_stream() feed them from host memory or a reader through a ring
 of windows: the file need never be resident on the device.
@@ -454,6 +455,60 @@ def decode_slice(slice_bytes, length, chunk, root):
     cnt, st = ctypes.c_uint32(), ctypes.c_int32()
     _chk(None, lib().b3w_bao_slice_decode(sl, len(sl), length, chunk, rw.ctypes.data, out, ctypes.byref(cnt), ctypes.byref(st)), "b3w_bao_slice_decode")
     return st.value, out.raw[:cnt.value]
+
+
+# ---- challenged paths and slices read in place from the arena -------------------------------------------------------------
+def _arena_args(what, d_arena, offsets, lens, d_outboards, files, chunks, group_log):
+    """the checks plan_samples_arena and slices_arena share -> (off, ln, fi, ch)"""
+    off, ln, ch = _u64(offsets), _u64(lens), _u64(chunks)
+    fi = np.ascontiguousarray(files, dtype=np.uint32)
+    assert off.size == ln.size and fi.size == ch.size
+    if not 0 <= group_log <= MAX_GROUP_LOG:
+        raise B3WError(100, f"group_log {group_log} is not in 0 .. {MAX_GROUP_LOG}")
+    assert d_arena.is_cuda and d_arena.dtype == torch.uint8 and d_arena.is_contiguous()
+    ob_first = group_batch_layout(ln, group_log)
+    assert d_outboards.is_cuda and d_outboards.dtype == torch.uint8 and d_outboards.is_contiguous() and d_outboards.numel() >= int(ob_first[-1]), what
+    return off, ln, fi, ch
+
+
+def plan_samples_arena(ctx, d_arena, offsets, lens, d_outboards, d_roots, files, chunks, group_log=0, stream=0):
+    """plan_samples_batch (group_log = 0: full outboards) / plan_samples_groups_batch (1 .. 6: group outboards) with the samples' bytes
+    read where the files lie: file f is bytes [offsets[f], offsets[f] + lens[f]) of d_arena, the uint8 CUDA tensor outboard_batch and
+    verify_batch take, files at any byte offset.  No chunk_bytes_batch / group_bytes_batch gather, one launch, nothing outside a
+    sample's own file read.  Returns the dict plan_samples_batch returns, the records word for word the same."""
+    L = lib()
+    off, ln, fi, ch = _arena_args("plan_samples_arena", d_arena, offsets, lens, d_outboards, files, chunks, group_log)
+    rf = sample_rows_batch(ln, fi, ch)
+    dev = d_outboards.device
+    assert d_roots.is_cuda and d_roots.is_contiguous() and d_roots.numel() >= ln.size * 8
+    recs = torch.empty((int(rf[-1]), 32), dtype=torch.int32, device=dev)
+    st = torch.full((ch.size,), -1, dtype=torch.int32, device=dev)
+    _chk(ctx, L.b3w_sample_plan_arena_device(ctx.handle, d_arena.data_ptr() if d_arena.numel() else None, d_arena.numel(), off.ctypes.data,
+                                             ln.ctypes.data, ln.size, group_log, d_outboards.data_ptr(), d_roots.data_ptr(), fi.ctypes.data,
+                                             ch.ctypes.data, ch.size, recs.data_ptr(), st.data_ptr(), _stream(stream)), "b3w_sample_plan_arena_device")
+    provable = np.array([bool(L.b3w_chain_path_provable(int(c), num_chunks(int(ln[f])))) for f, c in zip(fi, ch)], dtype=bool)
+    return dict(records=recs, row_first=rf, sample_status=st.cpu().numpy(), provable=provable)
+
+
+def prove_samples_arena(ctx, d_arena, offsets, lens, d_outboards, d_roots, files, chunks, group_log=0, batch_steps=4096, consumer=None,
+                        commit_key=None, r1cs=None, stream=0):
+    """prove_samples_batch over plan_samples_arena's plan"""
+    s = _stream(stream)
+    out = plan_samples_arena(ctx, d_arena, offsets, lens, d_outboards, d_roots, files, chunks, group_log, stream=s)
+    return _prove_planned(ctx, out, batch_steps, consumer, commit_key, r1cs, s)
+
+
+def slices_arena(ctx, d_arena, offsets, lens, d_outboards, files, chunks, group_log=0, stream=0):
+    """slices_batch with the sampled chunks' (group_log 1 .. 6: their groups') bytes read where the files lie in d_arena (as
+    plan_samples_arena takes it): the same standard slices from either kind of outboard, one launch, no gather.  Returns the dict
+    slices_batch returns."""
+    off, ln, fi, ch = _arena_args("slices_arena", d_arena, offsets, lens, d_outboards, files, chunks, group_log)
+    sf = slice_layout(ln, fi, ch)
+    d_slices = torch.zeros(int(sf[-1]), dtype=torch.uint8, device=d_outboards.device)
+    _chk(ctx, lib().b3w_bao_slice_arena_device(ctx.handle, d_arena.data_ptr() if d_arena.numel() else None, d_arena.numel(), off.ctypes.data,
+                                               ln.ctypes.data, ln.size, group_log, d_outboards.data_ptr(), fi.ctypes.data, ch.ctypes.data, ch.size,
+                                               d_slices.data_ptr(), _stream(stream)), "b3w_bao_slice_arena_device")
+    return dict(slices=d_slices, slice_first=sf)
 
 
 # ---- verification: whole files against their outboards ------------------------------------------------------------------

@@ -26,6 +26,8 @@
 //                            path inside the group stored whole before its level's merge
 //   b3w_sample_plan_slices_kernel  the step records planned from slices alone (no outboard): a sample over several lanes, the path's nodes
 //                            checked side by side, the parent records without the running-h chain where that chain is redundant
+//   b3w_*_arena_kernel       the batch planner, the group planner and the two slice kernels with the samples' bytes read where the files lie
+//                            in the arena (any byte alignment) instead of from a gathered copy: the same bodies, the byte source a parameter
 //   b3w_bao_verify_*_kernel  whole files against their outboards: the three batch kernels with every store of a node turned into a check of
 //                            the stored node, the storey above the tiles first; a status per chunk or chunk group ("verification")
 //   b3w_bao_stream_*_kernel  one file whose bytes arrive in windows of whole tiles: the tile, merge and verify kernels with the file's entry
@@ -524,6 +526,27 @@ __global__ __launch_bounds__(64) void b3w_sample_plan_batch_kernel(const uint8_t
                               chunk_bytes + (uint64_t)s * 1024, recs);
 }
 
+// ARENA (this kernel and the <true> instantiations of the three below): the samples' bytes are read where the files lie.  The table has
+// a sixth word per sample, the byte offset of the sample's file in the arena, and a chunk's bytes start at arena + desc[6 s + 5] + 1024 chunk
+// instead of at the sample's row of a gathered copy.  A file starts at any byte, so a chunk lies at any of the 16 alignments; no byte outside
+// [offset, offset + len) of the sample's own file is read (the hashing reads a chunk's `bytes` bytes and the lanes of the chunks a short
+// last group lacks read nothing).
+// desc[6 s ..] = chunk, first row, the file's length, the byte offset of its outboard in `obs`, the file, the file's byte offset in `arena`
+__global__ __launch_bounds__(64) void b3w_sample_plan_arena_kernel(const uint8_t *__restrict__ obs, const uint32_t *__restrict__ roots,
+                                                                   const uint64_t *__restrict__ desc, uint32_t n_samples,
+                                                                   const uint8_t *__restrict__ arena, uint32_t *__restrict__ recs,
+                                                                   int32_t *__restrict__ status) {
+  const uint32_t s = blockIdx.x * 64 + threadIdx.x;
+  if (s >= n_samples) return;
+  const uint64_t *d = desc + 6 * (uint64_t)s;
+  const uint64_t len = d[2];
+  uint32_t root[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) root[k] = roots[d[4] * 8 + k];
+  status[s] = sample_plan_one(len, len ? (len + 1023) / 1024 : 1, reinterpret_cast<const uint32_t *>(obs + d[3]), root, d[0], d[1],
+                              arena + d[5] + d[0] * 1024, recs);
+}
+
 // ---- challenged paths from group outboards ---------------------------------------------------------------------------
 // A group outboard (groups of G = 1 << gl chunks) holds the nodes over more than G chunks, which are the parent nodes of BLAKE3's tree
 // over the file's groups.  The lower part of a chunk's path, inside its group, is recomputed from the group's bytes.
@@ -580,15 +603,18 @@ __device__ __forceinline__ void group_chunk(const uint8_t *__restrict__ src, uin
 
 // desc as b3w_sample_plan_batch_kernel's, the outboard offsets those of the group layout; group_bytes: 1024 << gl bytes per sample.
 // status: 0 verified, 1 the group's bytes (any chunk of the group), 2 a stored node or the root, 3 header.
+// ARENA (b3w_sample_plan_arena_kernel): src is the arena, the table has the file's offset in it and lane i reads chunk first + i of its file
+// where it lies.  <false>: the gathered bytes (b3w_sample_plan_group_batch_device), <true>: the arena (b3w_sample_plan_arena_device).
+template <bool ARENA>
 __global__ __launch_bounds__(64) void b3w_sample_plan_group_kernel(const uint8_t *__restrict__ obs, const uint32_t *__restrict__ roots,
                                                                    const uint64_t *__restrict__ desc, uint32_t n_samples, uint32_t gl,
-                                                                   const uint8_t *__restrict__ group_bytes, uint32_t *__restrict__ recs,
+                                                                   const uint8_t *__restrict__ src, uint32_t *__restrict__ recs,
                                                                    int32_t *__restrict__ status) {
   __shared__ __attribute__((aligned(16))) uint32_t cv[64 * 8];
   const uint32_t lane = threadIdx.x, G = 1u << gl, i = lane & (G - 1), base = lane - i;
   const uint32_t s = blockIdx.x * (64u >> gl) + (lane >> gl);
   const bool valid = s < n_samples;
-  const uint64_t *d = desc + 5 * (uint64_t)(valid ? s : 0);              // (a wave's lanes past the last sample read sample 0's row and write nothing)
+  const uint64_t *d = desc + (ARENA ? 6 : 5) * (uint64_t)(valid ? s : 0);   // (a wave's lanes past the last sample read sample 0's row and write nothing)
   const uint64_t c = d[0], len = d[2], n = len ? (len + 1023) / 1024 : 1;
   const uint64_t first = (c >> gl) << gl, n_groups = (n + G - 1) >> gl;
   const uint32_t gn = (uint32_t)(n - first < G ? n - first : G), ci = (uint32_t)(c - first);
@@ -600,7 +626,7 @@ __global__ __launch_bounds__(64) void b3w_sample_plan_group_kernel(const uint8_t
   uint32_t *r = recs + d[1] * 32;
   uint32_t h[8];
   if (live) {
-    group_chunk(group_bytes + ((uint64_t)s << (10 + gl)) + (uint64_t)i * 1024, bytes, lc, P, n == 1 ? 8u : 0u, leader ? r : nullptr, h);
+    group_chunk(ARENA ? src + d[5] + off : src + ((uint64_t)s << (10 + gl)) + (uint64_t)i * 1024, bytes, lc, P, n == 1 ? 8u : 0u, leader ? r : nullptr, h);
     reinterpret_cast<uint4 *>(cv + lane * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
     reinterpret_cast<uint4 *>(cv + lane * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
   }
@@ -672,25 +698,39 @@ __global__ __launch_bounds__(64) void b3w_sample_plan_group_kernel(const uint8_t
 // desc of the two extraction kernels: desc[5 s ..] = chunk, the slice's byte offset in `slices`, the file's length, the byte offset of its
 // outboard in `obs`, the file.
 
-// 16 bytes from src (8-byte aligned: a node's quarter in an outboard, or chunk bytes) to dst (16-byte aligned)
+// 16 bytes from src (8-byte aligned: a node's quarter in an outboard, or chunk bytes) to dst (16-byte aligned).
+// ANY: src at any alignment (chunk bytes where they lie in an arena).  The load width is the source's natural alignment, so that no load
+// straddles its own width and none reaches outside the 16 bytes moved: 16 bytes from a source at 0 modulo 16, 8 at 8, 4 at 4 and 12, single
+// bytes from every other one, put together in registers; the store is one 16-byte store either way.
+template <bool ANY>
 __device__ __forceinline__ void move16(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src) {
   uint4 v;
   if (((uintptr_t)src & 15) == 0) {
     v = *reinterpret_cast<const uint4 *>(src);
-  } else {
+  } else if (!ANY || ((uintptr_t)src & 7) == 0) {
     const uint2 a = reinterpret_cast<const uint2 *>(src)[0], b = reinterpret_cast<const uint2 *>(src)[1];
     v = make_uint4(a.x, a.y, b.x, b.y);
+  } else if (((uintptr_t)src & 3) == 0) {
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(src);
+    v = make_uint4(w[0], w[1], w[2], w[3]);
+  } else {
+    uint32_t w[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      w[k] = (uint32_t)src[4 * k] | ((uint32_t)src[4 * k + 1] << 8) | ((uint32_t)src[4 * k + 2] << 16) | ((uint32_t)src[4 * k + 3] << 24);
+    v = make_uint4(w[0], w[1], w[2], w[3]);
   }
   *reinterpret_cast<uint4 *>(dst) = v;
 }
 
 // the sampled chunk's `bytes` bytes to dst (16-byte aligned), lane t of T: whole 16-byte pieces where src is 8-byte aligned, the ragged
-// tail (or everything, from an odd src) byte-wise
+// tail (or everything, from an odd src) byte-wise.  ANY: whole pieces from a source at any alignment (move16<true>), the tail byte-wise.
+template <bool ANY>
 __device__ __forceinline__ void move_chunk(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint32_t bytes, uint32_t t, uint32_t T) {
   uint32_t whole = 0;
-  if (((uintptr_t)src & 7) == 0) {
+  if (ANY || ((uintptr_t)src & 7) == 0) {
     whole = bytes & ~15u;
-    for (uint32_t o = t * 16; o < whole; o += T * 16) move16(dst + o, src + o);
+    for (uint32_t o = t * 16; o < whole; o += T * 16) move16<ANY>(dst + o, src + o);
   }
   for (uint32_t o = whole + t; o < bytes; o += T) dst[o] = src[o];
 }
@@ -698,11 +738,14 @@ __device__ __forceinline__ void move_chunk(uint8_t *__restrict__ dst, const uint
 // from full outboards: a gather, 16 lanes a sample.  Every lane walks the path (integer work); node j is moved by the four lanes t with
 // t / 4 == j mod 4, a quarter each, then all 16 move the chunk's bytes.
 constexpr uint32_t SLICE_LANES = 16;
+// ARENA: src is the arena and the table has the file's offset in it (b3w_sample_plan_arena_kernel).  <false>: the gathered bytes
+// (b3w_bao_slice_batch_device), <true>: the arena (b3w_bao_slice_arena_device).
+template <bool ARENA>
 __global__ __launch_bounds__(256) void b3w_bao_slice_kernel(const uint8_t *__restrict__ obs, const uint64_t *__restrict__ desc, uint32_t n_samples,
-                                                            const uint8_t *__restrict__ chunk_bytes, uint8_t *__restrict__ slices) {
+                                                            const uint8_t *__restrict__ src, uint8_t *__restrict__ slices) {
   const uint32_t tid = blockIdx.x * 256 + threadIdx.x, s = tid / SLICE_LANES, t = tid % SLICE_LANES;
   if (s >= n_samples) return;
-  const uint64_t *d = desc + 5 * (uint64_t)s;
+  const uint64_t *d = desc + (ARENA ? 6 : 5) * (uint64_t)s;
   const uint64_t c = d[0], len = d[2], n = len ? (len + 1023) / 1024 : 1;
   const uint8_t *ob = obs + d[3];
   uint8_t *sl = slices + d[1];
@@ -710,26 +753,30 @@ __global__ __launch_bounds__(256) void b3w_bao_slice_kernel(const uint8_t *__res
   if (t == 0) *reinterpret_cast<uint2 *>(sl) = *reinterpret_cast<const uint2 *>(ob);          // the header as the outboard has it
   uint64_t p = 0, cc = c, m = n;
   for (uint32_t j = 0; j < P; ++j) {
-    if ((j & 3) == (t >> 2)) move16(sl + 8 + 64 * (uint64_t)j + (t & 3) * 16, ob + 8 + p * 64 + (t & 3) * 16);
+    if ((j & 3) == (t >> 2)) move16<false>(sl + 8 + 64 * (uint64_t)j + (t & 3) * 16, ob + 8 + p * 64 + (t & 3) * 16);
     uint64_t k2 = 1;
     while (k2 * 2 < m) k2 *= 2;
     if (cc < k2) { p += 1; m = k2; } else { p += k2; cc -= k2; m -= k2; }
   }
   const uint64_t off = c * 1024;
-  move_chunk(sl + 8 + 64 * (uint64_t)P, chunk_bytes + (uint64_t)s * 1024, (uint32_t)(len - off < 1024 ? len - off : 1024), t, SLICE_LANES);
+  move_chunk<ARENA>(sl + 8 + 64 * (uint64_t)P, ARENA ? src + d[5] + off : src + (uint64_t)s * 1024, (uint32_t)(len - off < 1024 ? len - off : 1024), t,
+                    SLICE_LANES);
 }
 
 // from group outboards: phases 1 and 2 of b3w_sample_plan_group_kernel (lane = one chunk of one sample's group, the chunk CVs into LDS, the
 // in-place merge).  Before the merge of level l the node of the sampled chunk's path at that level, where it exists, is cv[i0] || cv[i1]:
 // the first lanes of the sample store it whole to its place in the slice (the k-th that exists bottom up at node P - 1 - k).  Then the U
 // stored nodes from the group outboard to the slice's first U places, the header and the sampled chunk's bytes, over the sample's G lanes.
+// ARENA: src is the arena and the table has the file's offset in it (b3w_sample_plan_arena_kernel); gb is where the sample's group starts.
+// <false>: the gathered bytes (b3w_bao_slice_batch_device), <true>: the arena (b3w_bao_slice_arena_device).
+template <bool ARENA>
 __global__ __launch_bounds__(64) void b3w_bao_slice_group_kernel(const uint8_t *__restrict__ obs, const uint64_t *__restrict__ desc, uint32_t n_samples,
-                                                                 uint32_t gl, const uint8_t *__restrict__ group_bytes, uint8_t *__restrict__ slices) {
+                                                                 uint32_t gl, const uint8_t *__restrict__ src, uint8_t *__restrict__ slices) {
   __shared__ __attribute__((aligned(16))) uint32_t cv[64 * 8];
   const uint32_t lane = threadIdx.x, G = 1u << gl, i = lane & (G - 1), base = lane - i;
   const uint32_t s = blockIdx.x * (64u >> gl) + (lane >> gl);
   const bool valid = s < n_samples;
-  const uint64_t *d = desc + 5 * (uint64_t)(valid ? s : 0);              // (a wave's lanes past the last sample read sample 0's row and write nothing)
+  const uint64_t *d = desc + (ARENA ? 6 : 5) * (uint64_t)(valid ? s : 0);   // (a wave's lanes past the last sample read sample 0's row and write nothing)
   const uint64_t c = d[0], len = d[2], n = len ? (len + 1023) / 1024 : 1;
   const uint64_t first = (c >> gl) << gl, n_groups = (n + G - 1) >> gl;
   const uint32_t gn = (uint32_t)(n - first < G ? n - first : G), ci = (uint32_t)(c - first);
@@ -737,7 +784,7 @@ __global__ __launch_bounds__(64) void b3w_bao_slice_group_kernel(const uint8_t *
   const uint32_t P = path_len(c, n), U = path_len(c >> gl, n_groups);     // the whole path, its stored part
   const uint64_t lc = first + i, off = lc * 1024;
   const uint32_t bytes = live ? (uint32_t)(len - off < 1024 ? len - off : 1024) : 0;
-  const uint8_t *gb = group_bytes + ((uint64_t)s << (10 + gl));
+  const uint8_t *gb = ARENA ? src + d[5] + first * 1024 : src + ((uint64_t)s << (10 + gl));
   uint8_t *sl = slices + d[1];
   if (live) {
     uint32_t h[8];
@@ -767,13 +814,13 @@ __global__ __launch_bounds__(64) void b3w_bao_slice_group_kernel(const uint8_t *
   for (uint32_t j = 0; j < U; ++j) {                                      // (P = low + U: the stored nodes fill the places in front)
 #pragma unroll
     for (uint32_t q = 0; q < 4; ++q)
-      if (((j * 4 + q) & (G - 1)) == i) move16(sl + 8 + 64 * (uint64_t)j + q * 16, ob + 8 + p * 64 + q * 16);
+      if (((j * 4 + q) & (G - 1)) == i) move16<false>(sl + 8 + 64 * (uint64_t)j + q * 16, ob + 8 + p * 64 + q * 16);
     uint64_t k2 = 1;
     while (k2 * 2 < m) k2 *= 2;
     if (cc < k2) { p += 1; m = k2; } else { p += k2; cc -= k2; m -= k2; }
   }
   const uint64_t offc = c * 1024;
-  move_chunk(sl + 8 + 64 * (uint64_t)P, gb + (uint64_t)ci * 1024, (uint32_t)(len - offc < 1024 ? len - offc : 1024), i, G);
+  move_chunk<ARENA>(sl + 8 + 64 * (uint64_t)P, gb + (uint64_t)ci * 1024, (uint32_t)(len - offc < 1024 ? len - offc : 1024), i, G);
 }
 
 // ---- challenged paths from slices ------------------------------------------------------------------------------------
@@ -1630,7 +1677,7 @@ int32_t b3w_sample_plan_group_batch_device(b3w_ctx *ctx, const uint64_t *host_le
   }
   HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)desc_bytes, hipMemcpyHostToDevice, st));
   const uint32_t per_wave = 64u >> group_log;
-  hipLaunchKernelGGL(b3w_sample_plan_group_kernel, dim3((n_samples + per_wave - 1) / per_wave), dim3(64), 0, st, d_group_outboards, d_roots,
+  hipLaunchKernelGGL(b3w_sample_plan_group_kernel<false>, dim3((n_samples + per_wave - 1) / per_wave), dim3(64), 0, st, d_group_outboards, d_roots,
                      reinterpret_cast<const uint64_t *>(ctx->d_batch), n_samples, group_log, d_group_bytes, d_records, d_sample_status);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(ctx, e, "sample plan group batch launch");
@@ -1737,10 +1784,10 @@ int32_t b3w_bao_slice_batch_device(b3w_ctx *ctx, const uint64_t *host_lens, uint
   const uint64_t *d_desc = reinterpret_cast<const uint64_t *>(ctx->d_batch);
   if (group_log == 0) {
     const uint32_t per_wg = 256 / SLICE_LANES;
-    hipLaunchKernelGGL(b3w_bao_slice_kernel, dim3((n_samples + per_wg - 1) / per_wg), dim3(256), 0, st, d_outboards, d_desc, n_samples, d_bytes, d_slices);
+    hipLaunchKernelGGL(b3w_bao_slice_kernel<false>, dim3((n_samples + per_wg - 1) / per_wg), dim3(256), 0, st, d_outboards, d_desc, n_samples, d_bytes, d_slices);
   } else {
     const uint32_t per_wave = 64u >> group_log;
-    hipLaunchKernelGGL(b3w_bao_slice_group_kernel, dim3((n_samples + per_wave - 1) / per_wave), dim3(64), 0, st, d_outboards, d_desc, n_samples, group_log,
+    hipLaunchKernelGGL(b3w_bao_slice_group_kernel<false>, dim3((n_samples + per_wave - 1) / per_wave), dim3(64), 0, st, d_outboards, d_desc, n_samples, group_log,
                        d_bytes, d_slices);
   }
   hipError_t e = hipGetLastError();
@@ -1790,6 +1837,103 @@ int32_t b3w_sample_plan_slices_device(b3w_ctx *ctx, const uint64_t *host_lens, u
     hipLaunchKernelGGL(b3w_sample_plan_slices_kernel<16>, dim3((n_samples + 3) / 4), dim3(64), 0, st, d_slices, d_roots, d_desc, n_samples, chain, d_records, d_sample_status);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(ctx, e, "sample plan slices launch");
+  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
+  return B3W_OK;
+}
+
+// ---- challenged paths and slices read in place from the arena (still ABI 1.4: new names only) -------------------------------
+// the checks the two arena calls share: the samples' indices, and every sampled file inside [0, arena_bytes)
+static int32_t arena_samples_ok(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
+                                uint32_t n_files, const uint32_t *host_files, const uint64_t *host_chunks, uint32_t n_samples) {
+  const int32_t rc = slice_samples_ok(ctx, host_lens, n_files, host_files, host_chunks, n_samples);
+  if (rc) return rc;
+  for (uint32_t s = 0; s < n_samples; ++s) {
+    const uint64_t off = host_offsets[host_files[s]], len = host_lens[host_files[s]];
+    if (len && !d_arena) { ctx->last_error = "a null arena with a sampled file that is not empty"; return B3W_E_BAD_ARGUMENT; }
+    if (off > arena_bytes || len > arena_bytes - off) { ctx->last_error = "a sampled file reaches past arena_bytes"; return B3W_E_BAD_ARGUMENT; }
+  }
+  return B3W_OK;
+}
+
+// the arena calls' sample table into the staging: {chunk, first row or slice offset, length, outboard offset, file, the file's arena offset}
+static int32_t arena_table(b3w_ctx *ctx, const uint64_t *host_offsets, const uint64_t *host_lens, uint32_t n_files, uint32_t group_log,
+                           const uint32_t *host_files, const uint64_t *host_chunks, uint32_t n_samples, bool slices, hipStream_t st) {
+  const uint64_t desc_bytes = (uint64_t)n_samples * 48;
+  const int32_t rc = batch_staging(ctx, desc_bytes + ((uint64_t)n_files + 1) * 8);
+  if (rc) return rc;
+  uint64_t *desc = reinterpret_cast<uint64_t *>(ctx->h_batch), *ob_first = desc + 6 * (uint64_t)n_samples;
+  (void)b3w_bao_group_batch_layout(host_lens, n_files, group_log, ob_first);        // (group_log 0: b3w_bao_batch_layout's)
+  uint64_t row = 0, at = slice_start(0);
+  for (uint32_t s = 0; s < n_samples; ++s) {
+    const uint32_t f = host_files[s];
+    const uint64_t len = host_lens[f];
+    uint64_t *d = desc + 6 * (uint64_t)s;
+    d[0] = host_chunks[s]; d[1] = slices ? at : row; d[2] = len; d[3] = ob_first[f]; d[4] = f; d[5] = host_offsets[f];
+    row += chunk_blocks(len, host_chunks[s]) + b3w_plan_path_len(host_chunks[s], num_chunks(len));
+    at = slice_start(at + b3w_bao_slice_size(len, host_chunks[s]));
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)desc_bytes, hipMemcpyHostToDevice, st));
+  return B3W_OK;
+}
+
+int32_t b3w_sample_plan_arena_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
+                                     uint32_t n_files, uint32_t group_log, const uint8_t *d_outboards, const uint32_t *d_roots,
+                                     const uint32_t *host_files, const uint64_t *host_chunks, uint32_t n_samples, uint32_t *d_records,
+                                     int32_t *d_sample_status, void *stream) {
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  if (ctx->desc.kind == B3W_KIND_COMP) { ctx->last_error = "sampled paths plan the nova step circuits' records"; return B3W_E_BAD_ARGUMENT; }
+  if (group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "sample plan arena: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
+  if (!n_samples) return B3W_OK;
+  if (!host_offsets || !host_lens || !d_outboards || !d_roots || !host_files || !host_chunks || !d_records || !d_sample_status) {
+    ctx->last_error = "sample plan arena: a null pointer"; return B3W_E_BAD_ARGUMENT;
+  }
+  if ((uintptr_t)d_outboards & 7) { ctx->last_error = "sample plan arena: d_outboards is not 8-byte aligned"; return B3W_E_BAD_ARGUMENT; }
+  int32_t rc = arena_samples_ok(ctx, d_arena, arena_bytes, host_offsets, host_lens, n_files, host_files, host_chunks, n_samples);
+  if (rc) return rc;
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  rc = arena_table(ctx, host_offsets, host_lens, n_files, group_log, host_files, host_chunks, n_samples, false, st);
+  if (rc) return rc;
+  const uint64_t *d_desc = reinterpret_cast<const uint64_t *>(ctx->d_batch);
+  if (group_log == 0) {
+    hipLaunchKernelGGL(b3w_sample_plan_arena_kernel, dim3((n_samples + 63) / 64), dim3(64), 0, st, d_outboards, d_roots, d_desc, n_samples, d_arena, d_records,
+                       d_sample_status);
+  } else {
+    const uint32_t per_wave = 64u >> group_log;
+    hipLaunchKernelGGL(b3w_sample_plan_group_kernel<true>, dim3((n_samples + per_wave - 1) / per_wave), dim3(64), 0, st, d_outboards, d_roots, d_desc,
+                       n_samples, group_log, d_arena, d_records, d_sample_status);
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(ctx, e, "sample plan arena launch");
+  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
+  return B3W_OK;
+}
+
+int32_t b3w_bao_slice_arena_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
+                                   uint32_t n_files, uint32_t group_log, const uint8_t *d_outboards, const uint32_t *host_files,
+                                   const uint64_t *host_chunks, uint32_t n_samples, uint8_t *d_slices, void *stream) {
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  if (group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "bao slice arena: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
+  if (!n_samples) return B3W_OK;
+  if (!host_offsets || !host_lens || !d_outboards || !host_files || !host_chunks || !d_slices) { ctx->last_error = "bao slice arena: a null pointer"; return B3W_E_BAD_ARGUMENT; }
+  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) { ctx->last_error = "bao slice arena: d_outboards is not 8-byte or d_slices not 16-byte aligned"; return B3W_E_BAD_ARGUMENT; }
+  int32_t rc = arena_samples_ok(ctx, d_arena, arena_bytes, host_offsets, host_lens, n_files, host_files, host_chunks, n_samples);
+  if (rc) return rc;
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  rc = arena_table(ctx, host_offsets, host_lens, n_files, group_log, host_files, host_chunks, n_samples, true, st);
+  if (rc) return rc;
+  const uint64_t *d_desc = reinterpret_cast<const uint64_t *>(ctx->d_batch);
+  if (group_log == 0) {
+    const uint32_t per_wg = 256 / SLICE_LANES;
+    hipLaunchKernelGGL(b3w_bao_slice_kernel<true>, dim3((n_samples + per_wg - 1) / per_wg), dim3(256), 0, st, d_outboards, d_desc, n_samples, d_arena, d_slices);
+  } else {
+    const uint32_t per_wave = 64u >> group_log;
+    hipLaunchKernelGGL(b3w_bao_slice_group_kernel<true>, dim3((n_samples + per_wave - 1) / per_wave), dim3(64), 0, st, d_outboards, d_desc, n_samples, group_log,
+                       d_arena, d_slices);
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(ctx, e, "bao slice arena launch");
   HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
   return B3W_OK;
 }

@@ -794,6 +794,40 @@ int32_t b3w_bao_stream_finish(b3w_bao_stream *session, void *stream);
 /* Frees the host object (NULL: a no-op); work already enqueued is not waited for and needs nothing of the session. */
 void b3w_bao_stream_free(b3w_bao_stream *session);
 
+/* ---- challenged paths and slices read in place from the file arena (still ABI 1.4: new names only) -----------------
+ * b3w_sample_plan_batch_device, b3w_sample_plan_group_batch_device and b3w_bao_slice_batch_device take a dense copy of the sampled
+ * chunks' (or groups') bytes, which the caller has to gather first.  These two take the arena the outboard and verification calls
+ * read — file f is bytes [host_offsets[f], + host_lens[f]) of d_arena, any offsets: gaps, overlaps, repeats, zero lengths, a start at
+ * ANY byte — and read each sample's bytes where they lie: a provider that holds the arena, the offsets and the outboards answers a
+ * challenge with no kernel of its own and no copy.
+ * group_log = 0: d_outboards are full outboards packed as b3w_bao_batch_layout says; 1 .. B3W_BAO_MAX_GROUP_LOG: group outboards
+ * packed as b3w_bao_group_batch_layout says (8-byte aligned either way).  Samples are (host_files[s], host_chunks[s]).
+ * Both: ONE launch; the per-sample table (48 bytes a sample: the existing calls' five words and the file's arena offset) goes through
+ * the context's staging and nothing else is allocated; no byte outside [offset, offset + len) of a sample's OWN file is read — not the
+ * bytes behind a ragged last chunk, not the chunks a short last group lacks — so what lies between and behind the files never
+ * matters.  A chunk lies at offset mod 16: the hashing takes 16-byte loads from a 16-byte-aligned chunk and smaller ones otherwise
+ * (a file that starts 16-byte aligned is the fast case, as in b3w_bao_outboard_batch_device); the results do not depend on it.
+ * B3W_E_BAD_ARGUMENT before anything is written for a null pointer (d_arena may be NULL where every sampled file is empty), a
+ * misaligned d_outboards / d_slices, a group_log above the maximum, a file index >= n_files, a chunk index not below its file's
+ * chunk count, or a sampled file that reaches past arena_bytes (the arena's size: the bound that keeps every read inside it).
+ * n_samples == 0: a no-op.  Asynchronous on `stream`; waits for this context's previous batch call. */
+/* Rows are b3w_sample_rows_batch's; the records (word for word), the four status codes and their precedence are those of
+ * b3w_sample_plan_batch_device (group_log = 0) / b3w_sample_plan_group_batch_device on the gathered bytes of the same arena; d_roots
+ * 8 u32 per file ON THE DEVICE.  Records are written for failing samples too; a bad sample touches no other.  Nova contexts only. */
+int32_t b3w_sample_plan_arena_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets,
+                                     const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint8_t *d_outboards,
+                                     const uint32_t *d_roots, const uint32_t *host_files, const uint64_t *host_chunks,
+                                     uint32_t n_samples, uint32_t *d_records, int32_t *d_sample_status, void *stream);
+/* The slices b3w_bao_slice_batch_device makes, into d_slices (16-byte aligned, packed as b3w_bao_slice_batch_layout says).  Only each
+ * sample's b3w_bao_slice_size bytes are written: the padding between slices is neither read nor written.  The chunk's bytes are
+ * moved in 16-byte stores; the loads are 16 bytes wide from a source at 0 modulo 16, 8 at 8, 4 at 4 and 12, single bytes otherwise,
+ * as far as the source text goes (a compiler for a device that takes unaligned loads may merge them).  Nothing is verified.  Any
+ * context. */
+int32_t b3w_bao_slice_arena_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets,
+                                   const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint8_t *d_outboards,
+                                   const uint32_t *host_files, const uint64_t *host_chunks, uint32_t n_samples, uint8_t *d_slices,
+                                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif
