@@ -196,6 +196,8 @@ def lib():
         "b3w_bao_stream_push": (i32, [vp, u64, vp, u64, vp]),
         "b3w_bao_stream_finish": (i32, [vp, vp]),
         "b3w_bao_stream_free": (None, [vp]),
+        "b3w_bao_stream_push_many": (i32, [vp, vp, vp, vp, vp, u32, vp]),
+        "b3w_bao_stream_finish_many": (i32, [vp, vp, u32, vp]),
         "b3w_sample_plan_arena_device": (i32, [vp, vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp]),
         "b3w_bao_slice_arena_device": (i32, [vp, vp, u64, vp, vp, u32, u32, vp, vp, vp, u32, vp, vp]),
     }
@@ -226,7 +228,7 @@ EXPORTED_SYMBOLS = ("b3w_abi_version", "b3w_identify_wasm", "b3w_create", "b3w_d
                     "b3w_sample_plan_slices_device",
                     "b3w_bao_verify_layout", "b3w_bao_verify_scratch_bytes", "b3w_bao_verify_batch_device", "b3w_bao_verify",
                     "b3w_bao_stream_scratch_bytes", "b3w_bao_stream_outboard_begin", "b3w_bao_stream_verify_begin", "b3w_bao_stream_push",
-                    "b3w_bao_stream_finish", "b3w_bao_stream_free",
+                    "b3w_bao_stream_finish", "b3w_bao_stream_free", "b3w_bao_stream_push_many", "b3w_bao_stream_finish_many",
                     "b3w_sample_plan_arena_device", "b3w_bao_slice_arena_device")
 
 

@@ -741,3 +741,194 @@ def verify_stream(ctx, source, length, d_outboard, d_root, window_bytes=DEFAULT_
         return session.finish()
     finally:
         session.close()
+
+
+# ---- many stream sessions in one launch --------------------------------------------------------------------------------------------
+# Not measured yet ("many stream sessions in one launch"): 16 lanes of 4 MiB are 64 MiB a round, the bytes of one push
+# at DEFAULT_WINDOW_BYTES.  The host-source pass that is to replace them is listed there as outstanding.
+DEFAULT_MANY_WINDOW_BYTES = 4 << 20
+DEFAULT_MANY_LANES = 16
+
+
+def _handles(sessions):
+    hs = np.array([s._h.value or 0 for s in sessions], dtype=np.uint64)
+    if len(sessions) and not hs.all():
+        raise B3WError(100, "a closed session")
+    return hs
+
+
+def push_many(sessions, offsets, d_windows, stream=0):
+    """session.push(offsets[i], d_windows[i]) for every i, as ONE launch on `stream`: sessions are StreamOutboard / StreamVerify objects
+    of one context and one kind (their group_log may differ), d_windows uint8 CUDA tensors.  A session may appear more than once
+    with disjoint windows.  If any entry would be refused nothing is launched and no session changes (B3WError names the entry)."""
+    if not (len(sessions) == len(offsets) == len(d_windows)):
+        raise B3WError(100, "push_many: sessions, offsets and d_windows differ in length")
+    if not len(sessions):
+        return
+    for w in d_windows:
+        assert w.is_cuda and w.dtype == torch.uint8 and w.is_contiguous()
+    hs, off = _handles(sessions), _u64(offsets)
+    ptr = np.array([w.data_ptr() for w in d_windows], dtype=np.uint64)
+    nb = np.array([w.numel() for w in d_windows], dtype=np.uint64)
+    ctx = sessions[0].ctx
+    _chk(ctx, lib().b3w_bao_stream_push_many(ctx.handle, hs.ctypes.data, off.ctypes.data, ptr.ctypes.data, nb.ctypes.data, hs.size, _stream(stream)),
+         "b3w_bao_stream_push_many")
+
+
+def finish_many(sessions, stream=0):
+    """session.finish() for every session in at most three launches on `stream`, which the caller orders behind every push
+    -> the list of the dicts finish() returns"""
+    if not len(sessions):
+        return []
+    _finish_many(sessions, stream)
+    return [dict(outboards=s.outboards, ob_first=s.ob_first, roots=s.roots) if isinstance(s, StreamOutboard) else
+            dict(unit_status=s.unit_status, unit_first=s.unit_first, file_status=s.file_status, first_bad=s.first_bad) for s in sessions]
+
+
+def _finish_many(sessions, stream):
+    hs = _handles(sessions)
+    ctx = sessions[0].ctx
+    _chk(ctx, lib().b3w_bao_stream_finish_many(ctx.handle, hs.ctypes.data, hs.size, _stream(stream)), "b3w_bao_stream_finish_many")
+
+
+class _Lane(_Stream):
+    """a session of the *_stream_many helpers: its outputs are the file's places in the packed results of the whole batch"""
+
+    def __init__(self, ctx, kind, length, group_log, out, f):
+        super().__init__(ctx, length, group_log)
+        need = stream_scratch_bytes(self.length, kind)
+        self.scratch = torch.empty(need, dtype=torch.uint8, device=out["device"])
+        scr = self.scratch.data_ptr() if need else None
+        ob = out["outboards"][int(out["ob_first"][f]):int(out["ob_first"][f + 1])]
+        if kind == STREAM_OUTBOARD:
+            _chk(ctx, lib().b3w_bao_stream_outboard_begin(ctx.handle, self.length, group_log, ob.data_ptr(), out["roots"][f].data_ptr(), scr, need,
+                                                          ctypes.byref(self._h)), "b3w_bao_stream_outboard_begin")
+        else:
+            _chk(ctx, lib().b3w_bao_stream_verify_begin(ctx.handle, self.length, group_log, ob.data_ptr(), out["roots"].reshape(-1, 8)[f].data_ptr(),
+                                                        out["unit_status"][int(out["unit_first"][f]):].data_ptr(), out["file_status"][f:].data_ptr(),
+                                                        out["first_bad"][f:].data_ptr(), scr, need, _stream(0), ctypes.byref(self._h)),
+                 "b3w_bao_stream_verify_begin")
+
+
+def _many_args(sources, lengths, window_bytes, group_log, lanes, ring):
+    """what the *_stream_many helpers refuse before they make anything"""
+    if lanes < 1:
+        raise B3WError(100, "lanes must be at least 1")
+    if ring < 1:
+        raise B3WError(100, "ring must be at least 1")
+    if window_bytes <= 0 or window_bytes % TILE_BYTES:
+        raise B3WError(100, f"window_bytes {window_bytes} is not a positive multiple of 1 MiB")
+    if len(sources) != len(lengths):
+        raise B3WError(100, f"{len(sources)} sources and {len(lengths)} lengths")
+    if not 0 <= group_log <= MAX_GROUP_LOG:
+        raise B3WError(100, f"group_log {group_log} is not in 0 .. {MAX_GROUP_LOG}")
+
+
+def _pump_many(ctx, kind, sources, lengths, window_bytes, group_log, lanes, ring, out):
+    """Up to `lanes` files open at once; a round copies the next window of every open file into one of `ring` device slabs of
+    lanes x window_bytes (each slab with a stream and an event of its own) and makes ONE push_many of them; the files that end in a
+    round are finished by one finish_many and their lanes handed on.  The current stream ends up behind everything."""
+    n = len(sources)
+    if not n:
+        return
+    lengths = [int(x) for x in lengths]
+    lanes = min(lanes, n)
+    # a pinned uint8 tensor is copied from where it lies; every other source goes through the pinned host slabs
+    direct = [src.reshape(-1) if isinstance(src, torch.Tensor) and src.dtype == torch.uint8 and src.is_pinned() else None for src in sources]
+    for f in range(n):
+        if direct[f] is not None and direct[f].numel() < lengths[f]:
+            raise B3WError(100, f"source {f} holds {direct[f].numel()} bytes, fewer than the length given ({lengths[f]})")
+    staged = any(direct[f] is None and lengths[f] for f in range(n))
+    cur = torch.cuda.current_stream()
+    slabs = [dict(h=torch.empty(lanes * window_bytes if staged else 0, dtype=torch.uint8, pin_memory=True),
+                  d=torch.empty(lanes * window_bytes, dtype=torch.uint8, device=out["device"]), s=torch.cuda.Stream(), ev=torch.cuda.Event(), used=False)
+             for _ in range(ring)]
+    for sl in slabs:
+        sl["s"].wait_stream(cur)                        # (what the caller enqueued before, e.g. the outboards' arrival, comes first)
+    every, open_, nxt, rnd = [], [None] * lanes, 0, 0   # open_[lane] = [session, file, fill, next offset]
+    try:
+        while True:
+            ended = []
+            for lane in range(lanes):                   # free lanes take the next files; a file of no bytes only needs its finish
+                while open_[lane] is None and nxt < n:
+                    f, nxt = nxt, nxt + 1
+                    se = _Lane(ctx, kind, lengths[f], group_log, out, f)
+                    every.append(se)
+                    if not lengths[f]:
+                        ended.append(se)
+                        continue
+                    src = sources[f]
+                    fill = None if direct[f] is not None else _reader(src.numpy() if isinstance(src, torch.Tensor) else src, lengths[f])
+                    open_[lane] = [se, f, fill, 0]
+            live = [lane for lane in range(lanes) if open_[lane] is not None]
+            if not live and not ended:
+                break
+            sl = slabs[rnd % ring]
+            if live:
+                if sl["used"] and staged:
+                    sl["ev"].synchronize()              # the slab's last copies are through with the host buffer
+                ses, offs, wins = [], [], []
+                with torch.cuda.stream(sl["s"]):        # (the device slab's reuse is ordered by its stream)
+                    for lane in live:
+                        se, f, fill, off = open_[lane]
+                        nb = min(window_bytes, lengths[f] - off)
+                        d = sl["d"][lane * window_bytes:lane * window_bytes + nb]
+                        if fill is None:
+                            d.copy_(direct[f][off:off + nb], non_blocking=True)
+                        else:
+                            h = sl["h"][lane * window_bytes:lane * window_bytes + nb]
+                            fill(h.numpy(), off)
+                            d.copy_(h, non_blocking=True)
+                        ses.append(se); offs.append(off); wins.append(d)
+                        open_[lane][3] = off + nb
+                        if off + nb == lengths[f]:
+                            ended.append(se)
+                            open_[lane] = None
+                    push_many(ses, offs, wins, stream=sl["s"].cuda_stream)
+                    sl["ev"].record(sl["s"])
+                sl["used"] = True
+            if ended:                                   # behind every push of theirs: the other slabs' last rounds too
+                for other in slabs:
+                    if other is not sl and other["used"]:
+                        sl["s"].wait_event(other["ev"])
+                _finish_many(ended, sl["s"].cuda_stream)
+            rnd += 1
+        for sl in slabs:
+            cur.wait_stream(sl["s"])
+    finally:
+        for se in every:
+            se.close()
+
+
+def outboard_stream_many(ctx, sources, lengths, window_bytes=DEFAULT_MANY_WINDOW_BYTES, group_log=0, lanes=DEFAULT_MANY_LANES, ring=2, device="cuda"):
+    """The outboards and roots of MANY files that are not resident on the device, `lanes` of them in flight at once: sources[f] is a
+    source as outboard_stream takes one (bytes-like, numpy, an object with readinto, or a pinned uint8 tensor, which is copied from
+    where it lies) of lengths[f] bytes.  Every round is one launch whatever `lanes` is (push_many), and so are the finishes of the
+    files that end in it.  Device memory made here is ring x lanes x window_bytes + the outboards + the scratches (32 bytes per MiB of
+    a file), however many files there are and whatever their lengths.  Returns the dict outboard_batch (group_log 0) /
+    outboard_groups_batch return for the files as one batch; the work is enqueued, the current stream ordered behind it."""
+    _many_args(sources, lengths, window_bytes, group_log, lanes, ring)
+    ln = _u64([int(x) for x in lengths])
+    ob_first = group_batch_layout(ln, group_log)
+    out = dict(device=device, ob_first=ob_first, outboards=torch.empty(int(ob_first[-1]), dtype=torch.uint8, device=device),
+               roots=torch.empty((ln.size, 8), dtype=torch.int32, device=device))
+    _pump_many(ctx, STREAM_OUTBOARD, sources, lengths, window_bytes, group_log, lanes, ring, out)
+    return dict(outboards=out["outboards"], ob_first=ob_first, roots=out["roots"])
+
+
+def verify_stream_many(ctx, sources, lengths, d_outboards, d_roots, window_bytes=DEFAULT_MANY_WINDOW_BYTES, group_log=0, lanes=DEFAULT_MANY_LANES, ring=2):
+    """verify_batch for MANY files that are not resident on the device against their resident outboards (d_outboards, packed as
+    outboard_batch / outboard_groups_batch leave them) and roots (d_roots, 8 words a file): the windows go as in outboard_stream_many.
+    Device memory made here is ring x lanes x window_bytes + the statuses (a byte a unit, 12 bytes a file) + the scratches (36 bytes
+    per MiB of a file).  Returns the dict verify_batch returns for the files as one batch."""
+    _many_args(sources, lengths, window_bytes, group_log, lanes, ring)
+    ln = _u64([int(x) for x in lengths])
+    ob_first, unit_first = group_batch_layout(ln, group_log), verify_layout(ln, group_log)
+    assert d_outboards.is_cuda and d_outboards.dtype == torch.uint8 and d_outboards.is_contiguous() and d_outboards.numel() >= int(ob_first[-1])
+    assert d_roots.is_cuda and d_roots.is_contiguous() and d_roots.element_size() == 4 and d_roots.numel() >= ln.size * 8
+    dev = d_outboards.device
+    out = dict(device=dev, ob_first=ob_first, outboards=d_outboards, roots=d_roots, unit_first=unit_first,
+               unit_status=torch.empty(int(unit_first[-1]), dtype=torch.uint8, device=dev),
+               file_status=torch.empty(ln.size, dtype=torch.int32, device=dev), first_bad=torch.empty(ln.size, dtype=torch.int64, device=dev))
+    _pump_many(ctx, STREAM_VERIFY, sources, lengths, window_bytes, group_log, lanes, ring, out)
+    return dict(unit_status=out["unit_status"], unit_first=unit_first, file_status=out["file_status"], first_bad=out["first_bad"])

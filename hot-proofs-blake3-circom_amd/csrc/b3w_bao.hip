@@ -32,6 +32,8 @@
 //                            the stored node, the storey above the tiles first; a status per chunk or chunk group ("verification")
 //   b3w_bao_stream_*_kernel  one file whose bytes arrive in windows of whole tiles: the tile, merge and verify kernels with the file's entry
 //                            by value and the tiles' bytes taken from the window ("streamed files")
+//   b3w_bao_stream_*_many_*  the windows (and the finishes) of many stream sessions as one grid: the stream kernels with the entry's row
+//                            of a table in place of the arguments by value ("many stream sessions in one launch")
 #include "b3w_internal.h"
 #include "b3w_blake3_dev.h"
 
@@ -1304,6 +1306,142 @@ __global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_verify_kernel(const u
   }
 }
 
+// ---- many stream sessions in one launch ----------------------------------------------------------------------------------------------
+// The windows of many sessions, each a file of its own, as ONE grid: what the stream kernels take by value, or from blockIdx.x, comes from
+// a table with a row per (session, window) entry, found by bisection over the rows' first workgroups as batch_ent finds a file.  The
+// work on a tile is the stream kernels' own (chunk_cv, merge_in_lds, verify_in_lds, preorder_pos), so the bytes are theirs.
+//   b3w_bao_stream_tile_many[_group]_kernel   stream_tile_body per workgroup.  The group kernel takes gl from the row, and at gl = 0 it
+//                                             stores every node where the plain kernel does (a parent is over 2 chunks or more): a call
+//                                             that mixes full and group outboards is one launch of the group kernel
+//   b3w_bao_stream_verify_many_kernel         the body of b3w_bao_stream_verify_kernel
+//   b3w_bao_stream_merge_many[_group]_kernel  stream_merge_body; a row per session of more than one tile (unit = B3W_TILE) or of more
+//                                             than 1 024 tiles (unit = B3W_TILE^2)
+// cv / aux: tile kernels: the session's tile CVs / unused; verify: exp_cv / bad; merge: the input CVs / the output CVs
+struct ManyRow {
+  uint64_t len;
+  const uint8_t *window;                                 // the bytes of the file from tile `tile0` on
+  uint8_t *ob;
+  uint32_t *root, *cv, *aux;
+  uint8_t *unit_status;
+  int32_t *file_status;
+  unsigned long long *first_bad;
+  uint32_t first, tile0, gl, pad;                        // first: the entry's first workgroup
+};
+
+// p as a pointer the compiler knows to be device memory (by way of an integer: it folds a cast there and straight back away)
+template <class P>
+__device__ __forceinline__ P *as_global(P *p) { return (P *)(__attribute__((address_space(1))) P *)(uintptr_t)p; }
+
+__device__ __forceinline__ ManyRow many_row(const ManyRow *__restrict__ rows, uint32_t n_rows, uint32_t wg) {
+  uint32_t lo = 0, hi = n_rows;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (rows[mid].first <= wg) lo = mid; else hi = mid;
+  }
+  ManyRow r = rows[lo];
+  // (a pointer loaded from memory is a generic one to the compiler, and its loads and stores would be flat ones, which count against the
+  // LDS counter too; these are device memory, as the stream kernels' arguments are known to be)
+  r.window = as_global(r.window); r.ob = as_global(r.ob); r.root = as_global(r.root); r.cv = as_global(r.cv); r.aux = as_global(r.aux);
+  r.unit_status = as_global(r.unit_status); r.file_status = as_global(r.file_status); r.first_bad = as_global(r.first_bad);
+  return r;
+}
+
+// stream_chunk_cv with the workgroup's index within its entry (w) in blockIdx.x's place
+__device__ __forceinline__ void many_chunk_cv(uint32_t *cv, const uint8_t *__restrict__ window, uint32_t w, uint64_t len, uint64_t n, uint64_t a0, uint32_t m) {
+  if (threadIdx.x < m) {
+    const uint64_t c = a0 + threadIdx.x, off = c * 1024;
+    uint32_t h[8];
+    chunk_cv(window + ((uint64_t)w * B3W_TILE + threadIdx.x) * 1024, (uint32_t)(len - off < 1024 ? len - off : 1024), c, n == 1 ? 8u : 0u, h);
+    reinterpret_cast<uint4 *>(cv + threadIdx.x * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
+    reinterpret_cast<uint4 *>(cv + threadIdx.x * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
+  }
+}
+
+template <bool GRP>
+__device__ __forceinline__ void many_tile_body(const ManyRow *__restrict__ rows, uint32_t n_rows) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
+  const ManyRow r = many_row(rows, n_rows, blockIdx.x);
+  const uint32_t w = blockIdx.x - r.first, gl = GRP ? r.gl : 0;
+  const uint64_t len = r.len, n = len ? (len + 1023) / 1024 : 1;
+  const uint64_t tile = (uint64_t)r.tile0 + w, a0 = tile * B3W_TILE;
+  const uint32_t m = (uint32_t)(n - a0 < B3W_TILE ? n - a0 : B3W_TILE);
+  const bool sole = n <= B3W_TILE;
+  many_chunk_cv(cv, r.window, w, len, n, a0, m);
+  if (a0 == 0 && threadIdx.x == 0) *reinterpret_cast<uint2 *>(r.ob) = make_uint2((uint32_t)len, (uint32_t)(len >> 32));
+  const uint64_t G1 = GRP ? (1ull << gl) - 1 : 0;                     // (a tile starts at a multiple of every group size)
+  merge_in_lds<B3W_TILE, GRP>(cv, m, 1, m, r.ob + 8 + (GRP ? preorder_pos((n + G1) >> gl, a0 >> gl, (m + G1) >> gl) : preorder_pos(n, a0, m)) * 64, sole, gl);
+  if (threadIdx.x < 8) (sole ? r.root : r.cv + tile * 8)[threadIdx.x] = cv[threadIdx.x];
+}
+
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_tile_many_kernel(const ManyRow *__restrict__ rows, uint32_t n_rows) {
+  many_tile_body<false>(rows, n_rows);
+}
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_tile_many_group_kernel(const ManyRow *__restrict__ rows, uint32_t n_rows) {
+  many_tile_body<true>(rows, n_rows);
+}
+
+// workgroup g of a row merges items [1 024 g, ...) of the row's input CVs, its CV to output slot g or the root
+template <bool GRP>
+__device__ __forceinline__ void many_merge_body(const ManyRow *__restrict__ rows, uint32_t n_rows, uint64_t unit) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
+  const ManyRow r = many_row(rows, n_rows, blockIdx.x);
+  const uint32_t gl = GRP ? r.gl : 0;
+  const uint64_t n = (r.len + 1023) / 1024;                           // (more than one tile)
+  const uint64_t g = blockIdx.x - r.first, span = unit * B3W_TILE, a0 = g * span;
+  const uint64_t tot = n - a0 < span ? n - a0 : span;
+  const uint32_t cnt = (uint32_t)((tot + unit - 1) / unit);
+  const bool sole = n <= span;
+  const uint4 *src = reinterpret_cast<const uint4 *>(r.cv + g * B3W_TILE * 8);
+  for (uint32_t i = threadIdx.x; i < cnt * 2; i += 256) reinterpret_cast<uint4 *>(cv)[i] = src[i];
+  const uint64_t G1 = GRP ? (1ull << gl) - 1 : 0;                     // (every node here is over more than a tile: all of them are stored)
+  merge_in_lds<256, GRP>(cv, cnt, unit, tot, r.ob + 8 + (GRP ? preorder_pos((n + G1) >> gl, a0 >> gl, (tot + G1) >> gl) : preorder_pos(n, a0, tot)) * 64, sole, gl);
+  if (threadIdx.x < 8) (sole ? r.root : r.aux + g * 8)[threadIdx.x] = cv[threadIdx.x];
+}
+
+__global__ __launch_bounds__(256) void b3w_bao_stream_merge_many_kernel(const ManyRow *__restrict__ rows, uint32_t n_rows, uint64_t unit) {
+  many_merge_body<false>(rows, n_rows, unit);
+}
+__global__ __launch_bounds__(256) void b3w_bao_stream_merge_many_group_kernel(const ManyRow *__restrict__ rows, uint32_t n_rows, uint64_t unit) {
+  many_merge_body<true>(rows, n_rows, unit);
+}
+
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_verify_many_kernel(const ManyRow *__restrict__ rows, uint32_t n_rows) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
+  __shared__ uint32_t flags[B3W_TILE];
+  __shared__ uint32_t worst, first;
+  const ManyRow r = many_row(rows, n_rows, blockIdx.x);
+  const uint32_t w = blockIdx.x - r.first, gl = r.gl;
+  const uint64_t len = r.len, n = len ? (len + 1023) / 1024 : 1;
+  const uint32_t t = threadIdx.x, G = 1u << gl;
+  const uint64_t tile = (uint64_t)r.tile0 + w, a0 = tile * B3W_TILE;
+  const uint32_t m = (uint32_t)(n - a0 < B3W_TILE ? n - a0 : B3W_TILE);
+  const bool sole = n <= B3W_TILE;
+  many_chunk_cv(cv, r.window, w, len, n, a0, m);
+  flags[t] = 0;
+  if (t == 0) { worst = 0; first = ~0u; }
+  const uint32_t *ob = reinterpret_cast<const uint32_t *>(r.ob);
+  const bool hdr = ((uint64_t)ob[0] | ((uint64_t)ob[1] << 32)) != len;
+  const uint64_t G1 = G - 1;
+  verify_in_lds<B3W_TILE, true>(cv, flags, m, 1, m, r.ob + 8 + preorder_pos((n + G1) >> gl, a0 >> gl, (m + G1) >> gl) * 64, sole, gl, nullptr);
+  if (t == 0 && !eq8(cv, sole ? r.root : r.cv + tile * 8)) flags[0] |= m <= G ? VER_UNIT : VER_TOP;
+  const bool above = sole ? false : r.aux[tile] != 0;
+  lds_barrier();
+  if (t < m && (t & (G - 1)) == 0) {                                  // a unit's first chunk: its status
+    const uint32_t st = hdr ? 3u : above || path_bad(flags, t) ? 2u : (flags[t] & VER_UNIT) ? 1u : 0u;
+    r.unit_status[(a0 + t) >> gl] = (uint8_t)st;
+    if (st) { atomicMax(&worst, st); atomicMin(&first, t >> gl); }    // (LDS; a clean tile issues none)
+  }
+  __syncthreads();
+  if (t != 0) return;
+  if (sole) {
+    *r.file_status = (int32_t)worst;
+    *r.first_bad = worst ? (unsigned long long)first : ~0ull;
+  } else if (worst) {                                                 // (initialised at begin by the file's top workgroup of the storey above)
+    atomicMax(r.file_status, (int32_t)worst);
+    atomicMin(r.first_bad, (unsigned long long)((a0 >> gl) + first));
+  }
+}
+
 // the CV of a chunk on the host (chunk_cv's loop over blake3_cv): b3w_bao_slice_decode
 void host_chunk_cv(const uint8_t *src, uint32_t bytes, uint64_t c, uint32_t root, uint32_t h[8]) {
   const uint32_t nb = bytes ? (bytes + 63) / 64 : 1;
@@ -2257,6 +2395,222 @@ void b3w_bao_stream_free(b3w_bao_stream *s) {
   if (!s) return;
   if (s->begun) (void)hipEventDestroy(s->begun);
   delete s;
+}
+
+}  // extern "C"
+
+// ---- many stream sessions in one launch: the host side ---------------------------------------------------------------------------
+namespace {
+
+// A staging slot of the context's ring with room for `bytes` of rows: the first one, from many_next on, whose event has passed.  The
+// host waits (for the oldest slot) only where every slot is still in flight; hipHostMalloc / hipMalloc only where the slot has to grow.
+int32_t many_staging(b3w_ctx *ctx, uint64_t bytes, b3w_ctx::ManySlot **out) {
+  const uint32_t N = b3w_ctx::B3W_MANY_SLOTS;
+  b3w_ctx::ManySlot *m = nullptr;
+  for (uint32_t k = 0; k < N && !m; ++k) {
+    b3w_ctx::ManySlot &c = ctx->many_slots[(ctx->many_next + k) % N];
+    if (c.busy) {
+      const hipError_t e = hipEventQuery(c.done);
+      if (e == hipErrorNotReady) continue;
+      if (e != hipSuccess) return hip_fail(ctx, e, "bao stream many: hipEventQuery");
+      c.busy = false;
+    }
+    m = &c;
+    ctx->many_next = (ctx->many_next + k + 1) % N;
+  }
+  if (!m) {
+    m = &ctx->many_slots[ctx->many_next];
+    ctx->many_next = (ctx->many_next + 1) % N;
+    HIP_TRY(ctx, hipEventSynchronize(m->done));
+    m->busy = false;
+  }
+  if (!m->done) HIP_TRY(ctx, hipEventCreateWithFlags(&m->done, hipEventDisableTiming));
+  if (m->cap < bytes) {
+    uint64_t cap = 4096;
+    while (cap < bytes) cap *= 2;
+    if (m->h) (void)hipHostFree(m->h);
+    if (m->d) (void)hipFree(m->d);
+    m->h = nullptr; m->d = nullptr; m->cap = 0;
+    HIP_TRY(ctx, hipHostMalloc((void **)&m->h, (size_t)cap, hipHostMallocDefault));
+    HIP_TRY(ctx, hipMalloc((void **)&m->d, (size_t)cap));
+    m->cap = cap;
+  }
+  *out = m;
+  return B3W_OK;
+}
+
+// the rows to a slot and on to the device, on `st`; the caller launches behind the copy and then calls many_release
+int32_t many_upload(b3w_ctx *ctx, const std::vector<ManyRow> &rows, hipStream_t st, b3w_ctx::ManySlot **slot) {
+  const uint64_t bytes = rows.size() * sizeof(ManyRow);
+  const int32_t rc = many_staging(ctx, bytes, slot);
+  if (rc) return rc;
+  memcpy((*slot)->h, rows.data(), (size_t)bytes);
+  HIP_TRY(ctx, hipMemcpyAsync((*slot)->d, (*slot)->h, (size_t)bytes, hipMemcpyHostToDevice, st));
+  return B3W_OK;
+}
+// (called whether or not the launches went well: the copy is enqueued and reads the slot)
+void many_release(b3w_ctx::ManySlot *slot, hipStream_t st) {
+  if (hipEventRecord(slot->done, st) != hipSuccess) (void)hipStreamSynchronize(st);
+  slot->busy = true;
+}
+
+int32_t many_refuse(b3w_ctx *ctx, const char *call, uint32_t i, const std::string &why) {
+  ctx->last_error = std::string("bao stream ") + call + ": entry " + std::to_string(i) + ": " + why;
+  return B3W_E_BAD_ARGUMENT;
+}
+
+ManyRow many_tile_row(const b3w_bao_stream *s, const uint8_t *window, uint32_t tile0, uint32_t first) {
+  ManyRow r{};
+  r.len = s->len; r.window = window; r.ob = s->ob; r.root = s->root; r.cv = s->scratch;
+  r.first = first; r.tile0 = tile0; r.gl = s->gl;
+  if (s->kind == B3W_BAO_STREAM_VERIFY) {
+    const uint64_t n_scr = (s->tiles > 1 ? s->tiles : 0) + (s->groups > 1 ? s->groups : 0);
+    r.aux = s->scratch + n_scr * 8;
+    r.unit_status = s->unit_status; r.file_status = s->file_status; r.first_bad = s->first_bad;
+  }
+  return r;
+}
+
+// the tile kernel of the rows' kind over `rows` (on the device) with `wgs` workgroups in all
+void many_launch_tiles(uint32_t kind, bool grp, const ManyRow *d_rows, uint32_t n_rows, uint32_t wgs, hipStream_t st) {
+  if (kind == B3W_BAO_STREAM_VERIFY) hipLaunchKernelGGL(b3w_bao_stream_verify_many_kernel, dim3(wgs), dim3(B3W_TILE), 0, st, d_rows, n_rows);
+  else if (grp) hipLaunchKernelGGL(b3w_bao_stream_tile_many_group_kernel, dim3(wgs), dim3(B3W_TILE), 0, st, d_rows, n_rows);
+  else hipLaunchKernelGGL(b3w_bao_stream_tile_many_kernel, dim3(wgs), dim3(B3W_TILE), 0, st, d_rows, n_rows);
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t b3w_bao_stream_push_many(b3w_ctx *ctx, b3w_bao_stream *const *sessions, const uint64_t *offsets, const uint8_t *const *d_windows,
+                                 const uint64_t *bytes, uint32_t n, void *stream) {
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  if (!n) return B3W_OK;
+  if (!sessions || !offsets || !d_windows || !bytes) { ctx->last_error = "bao stream push_many: a null array"; return B3W_E_BAD_ARGUMENT; }
+  const char *call = "push_many";
+  const uint64_t TB = (uint64_t)B3W_TILE * 1024;
+  struct Span { b3w_bao_stream *s; uint64_t t0, cnt; uint32_t i; };
+  std::vector<Span> spans(n);
+  uint64_t total = 0;
+  bool grp = false;
+  for (uint32_t i = 0; i < n; ++i) {                                  // every entry is checked before anything is launched or marked
+    b3w_bao_stream *s = sessions[i];
+    if (!s) return many_refuse(ctx, call, i, "a null session");
+    if (s->ctx != ctx) return many_refuse(ctx, call, i, "the session belongs to another context");
+    if (s->kind != sessions[0]->kind) return many_refuse(ctx, call, i, "the session is not of the kind of entry 0 (outboard and verification sessions do not mix)");
+    if (s->finished) return many_refuse(ctx, call, i, "the session is finished");
+    if (offsets[i] % TB) return many_refuse(ctx, call, i, "the offset is not a multiple of 1 MiB");
+    if (!bytes[i] || !d_windows[i]) return many_refuse(ctx, call, i, "an empty window or a null pointer");
+    if (offsets[i] > s->len || bytes[i] > s->len - offsets[i]) return many_refuse(ctx, call, i, "the window reaches past the file's end");
+    if (bytes[i] % TB && offsets[i] + bytes[i] != s->len) return many_refuse(ctx, call, i, "the window is not whole tiles of 1 MiB and does not end at the file's end");
+    const uint64_t t0 = offsets[i] / TB, cnt = (bytes[i] + TB - 1) / TB;
+    for (uint64_t t = t0; t < t0 + cnt; ++t)
+      if (s->seen[t >> 6] >> (t & 63) & 1) return many_refuse(ctx, call, i, "tile " + std::to_string(t) + " was pushed before");
+    spans[i] = Span{s, t0, cnt, i};
+    total += cnt;
+    grp = grp || s->gl != 0;
+  }
+  if (total > 0x7fffffffull) { ctx->last_error = "bao stream push_many: " + std::to_string(total) + " tiles in one call do not fit a 32-bit grid"; return B3W_E_BAD_ARGUMENT; }
+  std::vector<Span> by_tile(spans);
+  std::sort(by_tile.begin(), by_tile.end(), [](const Span &a, const Span &b) { return a.s != b.s ? std::less<const void *>()(a.s, b.s) : a.t0 != b.t0 ? a.t0 < b.t0 : a.i < b.i; });
+  for (uint32_t k = 1; k < n; ++k) {
+    const Span &a = by_tile[k - 1], &b = by_tile[k];
+    if (a.s == b.s && a.t0 + a.cnt > b.t0)
+      return many_refuse(ctx, call, a.i > b.i ? a.i : b.i, "tile " + std::to_string(b.t0) + " is named twice in the call (entry " + std::to_string(a.i < b.i ? a.i : b.i) + " has it too)");
+  }
+  std::vector<ManyRow> rows(n);
+  uint32_t first = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    rows[i] = many_tile_row(spans[i].s, d_windows[i], (uint32_t)spans[i].t0, first);
+    first += (uint32_t)spans[i].cnt;
+  }
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  for (uint32_t k = 0; k < n; ++k)                                    // (on the device: the host waits for nothing)
+    if (by_tile[k].s->begun && (k == 0 || by_tile[k - 1].s != by_tile[k].s)) HIP_TRY(ctx, hipStreamWaitEvent(st, by_tile[k].s->begun, 0));
+  b3w_ctx::ManySlot *slot = nullptr;
+  const int32_t rc = many_upload(ctx, rows, st, &slot);
+  if (rc) return rc;
+  many_launch_tiles(sessions[0]->kind, grp, reinterpret_cast<const ManyRow *>(slot->d), n, first, st);
+  const hipError_t e = hipGetLastError();
+  many_release(slot, st);
+  if (e != hipSuccess) return hip_fail(ctx, e, "bao stream push_many launch");
+  for (const Span &sp : spans) {
+    for (uint64_t t = sp.t0; t < sp.t0 + sp.cnt; ++t) sp.s->seen[t >> 6] |= 1ull << (t & 63);
+    sp.s->pushed += sp.cnt;
+  }
+  return B3W_OK;
+}
+
+int32_t b3w_bao_stream_finish_many(b3w_ctx *ctx, b3w_bao_stream *const *sessions, uint32_t n, void *stream) {
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  if (!n) return B3W_OK;
+  if (!sessions) { ctx->last_error = "bao stream finish_many: a null array"; return B3W_E_BAD_ARGUMENT; }
+  const char *call = "finish_many";
+  uint64_t wgs = 0;
+  bool grp = false;
+  for (uint32_t i = 0; i < n; ++i) {
+    const b3w_bao_stream *s = sessions[i];
+    if (!s) return many_refuse(ctx, call, i, "a null session");
+    if (s->ctx != ctx) return many_refuse(ctx, call, i, "the session belongs to another context");
+    if (s->kind != sessions[0]->kind) return many_refuse(ctx, call, i, "the session is not of the kind of entry 0 (outboard and verification sessions do not mix)");
+    if (s->finished) return many_refuse(ctx, call, i, "the session is finished");
+    if (s->len && s->pushed != s->tiles)
+      return many_refuse(ctx, call, i, std::to_string(s->tiles - s->pushed) + " of " + std::to_string(s->tiles) + " tiles have not been pushed");
+    wgs += s->groups;
+    grp = grp || s->gl != 0;
+  }
+  if (wgs > 0x7fffffffull) { ctx->last_error = "bao stream finish_many: " + std::to_string(wgs) + " workgroups in one call do not fit a 32-bit grid"; return B3W_E_BAD_ARGUMENT; }
+  std::vector<std::pair<const b3w_bao_stream *, uint32_t>> by_ptr(n);
+  for (uint32_t i = 0; i < n; ++i) by_ptr[i] = {sessions[i], i};
+  std::sort(by_ptr.begin(), by_ptr.end(), [](const auto &a, const auto &b) { return a.first != b.first ? std::less<const void *>()(a.first, b.first) : a.second < b.second; });
+  for (uint32_t k = 1; k < n; ++k)
+    if (by_ptr[k - 1].first == by_ptr[k].first)
+      return many_refuse(ctx, call, by_ptr[k].second, "the session appears twice in the call (entry " + std::to_string(by_ptr[k - 1].second) + " is the same)");
+  // one table, three runs of rows: the first merge storey (a workgroup per 1 024 tiles), the second (files past 1 GiB), the files of no bytes
+  const bool outboard = sessions[0]->kind == B3W_BAO_STREAM_OUTBOARD;
+  std::vector<ManyRow> rows;
+  uint32_t n1 = 0, n2 = 0, n3 = 0, wg1 = 0;
+  if (outboard) {
+    for (uint32_t i = 0; i < n; ++i) {
+      const b3w_bao_stream *s = sessions[i];
+      if (!s->len || s->tiles <= 1) continue;
+      ManyRow r = many_tile_row(s, nullptr, 0, wg1);
+      r.aux = s->scratch + s->tiles * 8;
+      rows.push_back(r); n1++; wg1 += (uint32_t)s->groups;
+    }
+    for (uint32_t i = 0; i < n; ++i) {
+      const b3w_bao_stream *s = sessions[i];
+      if (!s->len || s->groups <= 1) continue;
+      ManyRow r = many_tile_row(s, nullptr, 0, n2);
+      r.cv = s->scratch + s->tiles * 8; r.aux = nullptr;
+      rows.push_back(r); n2++;
+    }
+  }
+  for (uint32_t i = 0; i < n; ++i)
+    if (!sessions[i]->len) { rows.push_back(many_tile_row(sessions[i], nullptr, 0, n3)); n3++; }
+  if (!rows.empty()) {
+    ON_DEVICE(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    b3w_ctx::ManySlot *slot = nullptr;
+    const int32_t rc = many_upload(ctx, rows, st, &slot);
+    if (rc) return rc;
+    const ManyRow *d_rows = reinterpret_cast<const ManyRow *>(slot->d);
+    const uint64_t T = B3W_TILE;
+    if (grp) {
+      if (n1) hipLaunchKernelGGL(b3w_bao_stream_merge_many_group_kernel, dim3(wg1), dim3(256), 0, st, d_rows, n1, T);
+      if (n2) hipLaunchKernelGGL(b3w_bao_stream_merge_many_group_kernel, dim3(n2), dim3(256), 0, st, d_rows + n1, n2, T * T);
+    } else {
+      if (n1) hipLaunchKernelGGL(b3w_bao_stream_merge_many_kernel, dim3(wg1), dim3(256), 0, st, d_rows, n1, T);
+      if (n2) hipLaunchKernelGGL(b3w_bao_stream_merge_many_kernel, dim3(n2), dim3(256), 0, st, d_rows + n1, n2, T * T);
+    }
+    if (n3) many_launch_tiles(sessions[0]->kind, grp, d_rows + n1 + n2, n3, n3, st);
+    const hipError_t e = hipGetLastError();
+    many_release(slot, st);
+    if (e != hipSuccess) return hip_fail(ctx, e, "bao stream finish_many launch");
+  }
+  for (uint32_t i = 0; i < n; ++i) sessions[i]->finished = true;
+  return B3W_OK;
 }
 
 }  // extern "C"

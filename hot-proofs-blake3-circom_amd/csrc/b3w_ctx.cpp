@@ -488,6 +488,11 @@ void b3w_destroy(b3w_ctx *ctx) {
   if (ctx->batch_done) { (void)hipEventSynchronize(ctx->batch_done); (void)hipEventDestroy(ctx->batch_done); }
   if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
   if (ctx->d_batch) (void)hipFree(ctx->d_batch);
+  for (b3w_ctx::ManySlot &m : ctx->many_slots) {
+    if (m.done) { if (m.busy) (void)hipEventSynchronize(m.done); (void)hipEventDestroy(m.done); }
+    if (m.h) (void)hipHostFree(m.h);
+    if (m.d) (void)hipFree(m.d);
+  }
   delete ctx;
 }
 

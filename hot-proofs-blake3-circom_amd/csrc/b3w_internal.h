@@ -81,6 +81,13 @@ struct b3w_ctx {
   uint8_t *h_batch = nullptr, *d_batch = nullptr;
   uint64_t batch_cap = 0;
   hipEvent_t batch_done = nullptr;
+  // b3w_bao_stream_push_many / _finish_many: the rows of a call's table go through one of B3W_MANY_SLOTS slots, each a pinned host and a
+  // device buffer (grow-only) and an event behind the copy and the kernels that read them; a call takes a slot whose event has passed
+  // and waits on the host only where all are in flight
+  static constexpr uint32_t B3W_MANY_SLOTS = 8;
+  struct ManySlot { uint8_t *h = nullptr, *d = nullptr; uint64_t cap = 0; hipEvent_t done = nullptr; bool busy = false; };
+  ManySlot many_slots[B3W_MANY_SLOTS];
+  uint32_t many_next = 0;
   std::string last_error;
 };
 

@@ -794,6 +794,32 @@ int32_t b3w_bao_stream_finish(b3w_bao_stream *session, void *stream);
 /* Frees the host object (NULL: a no-op); work already enqueued is not waited for and needs nothing of the session. */
 void b3w_bao_stream_free(b3w_bao_stream *session);
 
+/* ---- many stream sessions in one launch (still ABI 1.4: new names only) ---------------------------------------------
+ * A push costs the latency of one tile's workgroup whatever the window holds, and pushes on one stream run one behind the other: a
+ * party with several hundred uploads open, each receiving small windows, is bound by launches.  These two take the windows (the
+ * finishes) of MANY sessions and make one grid of them.  Entry i of push_many means exactly what b3w_bao_stream_push(sessions[i],
+ * offsets[i], d_windows[i], bytes[i], stream) means, under the same per-window rules, and the bytes left behind (outboards, roots,
+ * tile CVs in the scratches; unit statuses, file statuses, first bad units) are byte for byte those of the per-session calls.
+ * All sessions of one call belong to `ctx` and are of ONE kind, all outboard or all verification; group_log may differ from session
+ * to session; a session may appear more than once in a push_many whose entries name disjoint tiles of it.  n == 0: B3W_OK, nothing
+ * launched.
+ * LAUNCHES: push_many is ONE launch whatever n and the tile count are (a call that mixes group_log = 0 with group_log > 0 runs the
+ * group kernel for all: at group_log = 0 it stores the same nodes).  Verification: `stream` is made to wait ON THE DEVICE for the
+ * begin work of every distinct session in the call; the host waits for nothing.  finish_many: one launch over the first merge storey
+ * of all outboard sessions of more than one tile, one more if any session is past 1 GiB, one more for the sessions of no bytes: at
+ * most three whatever n is; verification sessions take the last one alone.  The caller orders `stream` behind every push.
+ * THE TABLE: which session, tile and window a workgroup takes is a row of 88 bytes per entry, copied to the device on `stream` in
+ * front of the launch through a ring of 8 staging slots in the context (pinned host + device, grow-only, an event each).  Once the
+ * slots have grown to the calls' size nothing is allocated, and the host waits for earlier device work only where all 8 slots are
+ * still in flight.  One context is used by one host thread at a time.
+ * REFUSALS ARE ATOMIC: if any entry would be refused the call returns B3W_E_BAD_ARGUMENT, nothing is launched and NO session's
+ * state changes; b3w_last_error names the entry's index and the reason.  Refused: what b3w_bao_stream_push / _finish refuse, a null
+ * array, a null session, a session of another context, sessions of mixed kinds, a tile named twice within the call, a session that
+ * appears twice in finish_many, more than 2^31 - 1 tiles (workgroups) in one call. */
+int32_t b3w_bao_stream_push_many(b3w_ctx *ctx, b3w_bao_stream *const *sessions, const uint64_t *offsets, const uint8_t *const *d_windows,
+                                 const uint64_t *bytes, uint32_t n, void *stream);
+int32_t b3w_bao_stream_finish_many(b3w_ctx *ctx, b3w_bao_stream *const *sessions, uint32_t n, void *stream);
+
 /* ---- challenged paths and slices read in place from the file arena (still ABI 1.4: new names only) -----------------
  * b3w_sample_plan_batch_device, b3w_sample_plan_group_batch_device and b3w_bao_slice_batch_device take a dense copy of the sampled
  * chunks' (or groups') bytes, which the caller has to gather first.  These two take the arena the outboard and verification calls
