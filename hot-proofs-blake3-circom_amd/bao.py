@@ -12,7 +12,9 @@ outboards (decode_slice(): the host decoder).  plan_samples_arena() / prove_samp
 without the gather: the sampled bytes are read where the files lie in the arena outboard_batch() took, at any byte offset.  verify_batch() is bao's decoder over whole files: every chunk (or chunk group) of
 every file of a batch held against its outboard and root on the device, a status per unit (verify_host(): one file on the host).  StreamOutboard / StreamVerify take ONE file window by window (whole MiB, any order, any
 stream) with the batch calls' results, and outboard_stream() / verify_stream() feed them from host memory or a reader through a ring
-of windows: the file need never be resident on the device.
+of windows: the file need never be resident on the device.  StreamOutboardOpen / outboard_stream_open() do the same for a file whose
+LENGTH IS NOT KNOWN until its last byte (an upper bound instead): full MiB are hashed as they come into a staging area, and finish(),
+which learns the length, moves them to their places in the outboard.
 The records are
 word for word those the chain planner writes for the same chunks (ChainPlanner.plan), so every step is the reference's
 prove_chunk_hash step (rust_fold/src/main.rs:41-203 over hash_with_path's slice, rust_fold/src/blake3_hash.rs:17-93)."""
@@ -601,9 +603,13 @@ class _Stream:
         `stream`.  offset: a multiple of 1 MiB; the size: a multiple of 1 MiB unless the window ends the file.  Any order, any stream."""
         assert d_window.is_cuda and d_window.dtype == torch.uint8 and d_window.is_contiguous()
         _chk(self.ctx, lib().b3w_bao_stream_push(self._h, offset, d_window.data_ptr(), d_window.numel(), _stream(stream)), "b3w_bao_stream_push")
+        self._pushed(d_window.numel())
 
     def _finish(self, stream):
         _chk(self.ctx, lib().b3w_bao_stream_finish(self._h, _stream(stream)), "b3w_bao_stream_finish")
+
+    def _pushed(self, nbytes):
+        """(a push of nbytes went through: only an open session keeps count)"""
 
     def close(self):
         if self._h:
@@ -743,6 +749,127 @@ def verify_stream(ctx, source, length, d_outboard, d_root, window_bytes=DEFAULT_
         session.close()
 
 
+# ---- files whose length is not known up front -----------------------------------------------------------------------------------------
+STREAM_OPEN = 2
+OPEN_STAGING_PAD = 16                                  # B3W_BAO_STREAM_OPEN_STAGING_PAD
+
+
+def _open_args(capacity, window_bytes, group_log, ring):
+    """what StreamOutboardOpen / outboard_stream_open refuse before they make anything"""
+    if ring < 1:
+        raise B3WError(100, "ring must be at least 1")
+    if window_bytes <= 0 or window_bytes % TILE_BYTES:
+        raise B3WError(100, f"window_bytes {window_bytes} is not a positive multiple of 1 MiB")
+    if not 0 <= group_log <= MAX_GROUP_LOG:
+        raise B3WError(100, f"group_log {group_log} is not in 0 .. {MAX_GROUP_LOG}")
+    if capacity < 0:
+        raise B3WError(100, f"capacity {capacity} is negative")
+
+
+class StreamOutboardOpen(_Stream):
+    """StreamOutboard for a file of at most `capacity` bytes whose length is known only at the end: push(offset, d_window, stream) takes
+    whole MiB (any order, any stream, each once), finish(d_tail, stream) the last bytes that fill no MiB, and with them the length.
+    The session makes a staging area (the outboard's size for `capacity`) and a scratch at once, the outboard and root in finish()."""
+
+    def __init__(self, ctx, capacity, group_log=0, device="cuda"):
+        super().__init__(ctx, 0, group_log)
+        _open_args(capacity, TILE_BYTES, group_log, 1)
+        self.capacity, self.length, self._bytes, self.device = int(capacity), None, 0, device
+        L = lib()
+        n_stage, n_scr = L.b3w_bao_stream_open_staging_bytes(self.capacity, group_log), L.b3w_bao_stream_open_scratch_bytes(self.capacity)
+        self.staging = torch.empty(n_stage, dtype=torch.uint8, device=device)
+        self.scratch = torch.empty(n_scr, dtype=torch.uint8, device=device)
+        _chk(ctx, L.b3w_bao_stream_open_begin(ctx.handle, self.capacity, group_log, self.staging.data_ptr(), n_stage, self.scratch.data_ptr(), n_scr,
+                                              ctypes.byref(self._h)), "b3w_bao_stream_open_begin")
+
+    def _pushed(self, nbytes):
+        self._bytes += nbytes
+
+    def finish(self, d_tail=None, stream=0):
+        """d_tail: the file's last bytes, fewer than 1 MiB (a uint8 CUDA tensor, any alignment; None or empty: the file ends with its
+        last MiB pushed).  The caller orders `stream` behind every push.  -> the dict outboard_batch / outboard_groups_batch return
+        for this file as a batch of one, and `length`."""
+        tail = 0 if d_tail is None else d_tail.numel()
+        if tail:
+            assert d_tail.is_cuda and d_tail.dtype == torch.uint8 and d_tail.is_contiguous()
+        ob_first = group_batch_layout([self._bytes + tail], self.group_log)
+        outboards = torch.empty(int(ob_first[-1]), dtype=torch.uint8, device=self.device)
+        roots = torch.empty((1, 8), dtype=torch.int32, device=self.device)
+        n = ctypes.c_uint64()
+        _chk(self.ctx, lib().b3w_bao_stream_open_finish(self._h, d_tail.data_ptr() if tail else None, tail, outboards.data_ptr(), outboards.numel(),
+                                                        roots.data_ptr(), _stream(stream), ctypes.byref(n)), "b3w_bao_stream_open_finish")
+        self.length, self.outboards, self.ob_first, self.roots = n.value, outboards, ob_first, roots
+        return dict(outboards=outboards, ob_first=ob_first, roots=roots, length=self.length)
+
+
+def outboard_stream_open(ctx, source, capacity, window_bytes=DEFAULT_WINDOW_BYTES, group_log=0, ring=2):
+    """outboard_stream for a source whose length is not known: `source` is an object with readinto, read until it returns 0 (a short
+    read is not the end), or a bytes-like / numpy buffer, taken whole; `capacity` bounds its length, and a source that yields more
+    raises B3WError.  The same ring of pinned host buffers and device windows, each on a stream of its own.  Of every window the whole
+    MiB are pushed; what the last read leaves below a MiB is the tail and stays in its device window until finish has read it.  Device
+    memory made here is ring x window_bytes + the staging (the outboard's size for `capacity`) + the scratch + the outboard.
+    Returns StreamOutboardOpen.finish()'s dict; the work is enqueued, the current stream ordered behind it."""
+    _open_args(capacity, window_bytes, group_log, ring)
+    if hasattr(source, "readinto"):
+        def fill(dst):
+            view, got = memoryview(dst), 0
+            while got < len(view):
+                k = source.readinto(view[got:])
+                if not k:
+                    break
+                got += k
+            return got
+    else:
+        data = np.frombuffer(source, dtype=np.uint8) if not isinstance(source, np.ndarray) else source.reshape(-1).view(np.uint8)
+        if data.size > capacity:
+            raise B3WError(100, f"the source holds {data.size} bytes, more than the capacity ({capacity})")
+        at = [0]
+
+        def fill(dst):
+            got = min(dst.size, data.size - at[0])
+            dst[:got] = data[at[0]:at[0] + got]
+            at[0] += got
+            return got
+    session = StreamOutboardOpen(ctx, capacity, group_log)
+    try:
+        size = min(window_bytes, max(TILE_BYTES, -(-int(capacity) // TILE_BYTES) * TILE_BYTES))
+        cur = torch.cuda.current_stream()
+        slots, total, tail, i = [], 0, None, 0
+        try:
+            while True:
+                if i < ring:                            # (a slot is made when its turn first comes and the source still has bytes)
+                    h = torch.empty(size, dtype=torch.uint8, pin_memory=True)
+                else:
+                    h, d, s, ev = slots[i % ring]
+                    ev.synchronize()                    # the slot's last copy and push are through with both buffers
+                got = fill(h.numpy())
+                if total + got > capacity:
+                    raise B3WError(100, f"the source yields more than the capacity ({capacity} bytes)")
+                if not got:                             # the source ended on a window's last byte: no tail, and no slot for nothing
+                    break
+                if i < ring:
+                    d, s, ev = torch.empty(size, dtype=torch.uint8, device="cuda"), torch.cuda.Stream(), torch.cuda.Event()
+                    slots.append((h, d, s, ev))
+                    s.wait_stream(cur)
+                whole = got // TILE_BYTES * TILE_BYTES
+                with torch.cuda.stream(s):
+                    d[:got].copy_(h[:got], non_blocking=True)
+                    if whole:
+                        session.push(total, d[:whole], stream=s.cuda_stream)
+                    ev.record(s)
+                total += got
+                i += 1
+                if got < size:                          # the source has ended
+                    tail = d[whole:got] if got > whole else None
+                    break
+        finally:                                        # (also on a raise: the staging and the windows are not freed under a push in flight)
+            for _, _, s, _ in slots:
+                cur.wait_stream(s)
+        return session.finish(tail)
+    finally:
+        session.close()
+
+
 # ---- many stream sessions in one launch --------------------------------------------------------------------------------------------
 # Not measured yet (DESIGN.md §8g, "many stream sessions in one launch"): 16 lanes of 4 MiB are 64 MiB a round, the bytes of one push
 # at DEFAULT_WINDOW_BYTES.  The host-source pass that is to replace them is listed there as outstanding.
@@ -758,8 +885,8 @@ def _handles(sessions):
 
 
 def push_many(sessions, offsets, d_windows, stream=0):
-    """session.push(offsets[i], d_windows[i]) for every i, as ONE launch on `stream`: sessions are StreamOutboard / StreamVerify objects
-    of one context and one kind (their group_log may differ), d_windows uint8 CUDA tensors.  A session may appear more than once
+    """session.push(offsets[i], d_windows[i]) for every i, as ONE launch on `stream`: sessions are StreamOutboard / StreamVerify /
+    StreamOutboardOpen objects of one context and one kind (their group_log may differ), d_windows uint8 CUDA tensors.  A session may appear more than once
     with disjoint windows.  If any entry would be refused nothing is launched and no session changes (B3WError names the entry)."""
     if not (len(sessions) == len(offsets) == len(d_windows)):
         raise B3WError(100, "push_many: sessions, offsets and d_windows differ in length")
@@ -773,6 +900,8 @@ def push_many(sessions, offsets, d_windows, stream=0):
     ctx = sessions[0].ctx
     _chk(ctx, lib().b3w_bao_stream_push_many(ctx.handle, hs.ctypes.data, off.ctypes.data, ptr.ctypes.data, nb.ctypes.data, hs.size, _stream(stream)),
          "b3w_bao_stream_push_many")
+    for s, w in zip(sessions, d_windows):
+        s._pushed(w.numel())
 
 
 def finish_many(sessions, stream=0):

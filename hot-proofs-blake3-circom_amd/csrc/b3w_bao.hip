@@ -34,6 +34,8 @@
 //                            by value and the tiles' bytes taken from the window ("streamed files")
 //   b3w_bao_stream_*_many_*  the windows (and the finishes) of many stream sessions as one grid: the stream kernels with the entry's row
 //                            of a table in place of the arguments by value ("many stream sessions in one launch")
+//   b3w_bao_stream_open_*    a file whose length is known only at finish: full tiles hashed into tile-local blocks of a staging area, and
+//                            the blocks moved to their pre-order places once the length is known ("open-length sessions")
 #include "b3w_internal.h"
 #include "b3w_blake3_dev.h"
 
@@ -1442,6 +1444,123 @@ __global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_verify_many_kernel(co
   }
 }
 
+// ---- open-length sessions: full tiles hashed before the file's length is known -----------------------------------------------------------
+// A FULL tile of 1 024 chunks is a complete subtree whatever the file's length turns out to be: its (1 024 >> gl) - 1 stored nodes are
+// contiguous in the file's pre-order outboard, in the order merge_in_lds gives them relative to the tile's root, and only the START of that
+// run depends on the total.  Its CV is never ROOT-flagged by the tile (a file of exactly one full tile: see the relocation kernel).  So:
+//   b3w_bao_stream_open_tile[_group]_kernel       a workgroup per full tile of the window: chunk CVs into LDS, merge_in_lds with `nodes` at
+//                                                 the tile's BLOCK of a staging area (block t = the nodes of tile t, tile-local order),
+//                                                 the tile's CV to scratch slot `tile`.  No header, no root, no length.
+//   b3w_bao_stream_open_tile_many[_group]_kernel  the same with the window, tile0, staging and scratch from a ManyRow (ob = the blocks)
+//   b3w_bao_stream_open_relocate_kernel           at finish, the length known: every block to ob + 8 + 64 preorder_pos(...), and the header
+// The tile of the file's tail goes through b3w_bao_stream_tile[_group]_kernel and the storeys above through b3w_bao_stream_merge[_group]_kernel
+// as they are.  Blocks start 8 bytes off a 16-byte boundary (the staging is 16-byte aligned and block 0 starts at byte 8), which is where
+// the nodes of a 16-byte-aligned outboard lie: merge_pair's 8-byte stores are aligned, and the relocation moves an 8-byte head, a body of
+// aligned 16-byte pieces and an 8-byte tail.
+constexpr uint32_t OPEN_PIECE = 16384;                   // the most bytes of blocks one relocation workgroup moves
+constexpr uint32_t OPEN_PAD = B3W_BAO_STREAM_OPEN_STAGING_PAD;                       // staging bytes that are no block's: 8 in front of block 0, 8 behind the last one
+struct OpenShape { uint32_t bb, ppb, tpw_log; };         // a block's bytes; workgroups per block; log2 of the blocks per workgroup
+__host__ __device__ __forceinline__ OpenShape open_shape(uint32_t gl) {
+  OpenShape s;
+  s.bb = ((B3W_TILE >> gl) - 1) * 64;                    // 65 472 (gl = 0) ... 960 (gl = 6)
+  s.ppb = (s.bb + OPEN_PIECE - 1) / OPEN_PIECE;          // 4, 2, 1, 1, ...
+  s.tpw_log = 0;                                         // 1, 1, 1, 2, 4, 8, 16 blocks
+  while (s.tpw_log < 4 && (s.bb << (s.tpw_log + 1)) <= OPEN_PIECE) s.tpw_log++;
+  return s;
+}
+
+// blocks: block 0's first byte; w: the tile's place in the window
+template <bool GRP>
+__device__ __forceinline__ void open_tile_body(const uint8_t *__restrict__ window, uint32_t w, uint64_t tile, uint8_t *__restrict__ blocks,
+                                               uint32_t *__restrict__ tile_cv, uint32_t gl) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
+  uint32_t h[8];
+  chunk_cv(window + ((uint64_t)w * B3W_TILE + threadIdx.x) * 1024, 1024, tile * B3W_TILE + threadIdx.x, 0, h);
+  reinterpret_cast<uint4 *>(cv + threadIdx.x * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
+  reinterpret_cast<uint4 *>(cv + threadIdx.x * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
+  merge_in_lds<B3W_TILE, GRP>(cv, B3W_TILE, 1, B3W_TILE, blocks + tile * (((B3W_TILE >> gl) - 1) * 64), false, gl);
+  if (threadIdx.x < 8) tile_cv[tile * 8 + threadIdx.x] = cv[threadIdx.x];
+}
+
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_open_tile_kernel(const uint8_t *__restrict__ window, uint32_t tile0,
+                                                                            uint8_t *__restrict__ blocks, uint32_t *__restrict__ tile_cv) {
+  open_tile_body<false>(window, blockIdx.x, (uint64_t)tile0 + blockIdx.x, blocks, tile_cv, 0);
+}
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_open_tile_group_kernel(const uint8_t *__restrict__ window, uint32_t tile0,
+                                                                                  uint8_t *__restrict__ blocks, uint32_t *__restrict__ tile_cv,
+                                                                                  uint32_t gl) {
+  open_tile_body<true>(window, blockIdx.x, (uint64_t)tile0 + blockIdx.x, blocks, tile_cv, gl);
+}
+// rows as the tile kernels of many sessions take them, with ob = the session's blocks (len, root and the rest unused)
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_open_tile_many_kernel(const ManyRow *__restrict__ rows, uint32_t n_rows) {
+  const ManyRow r = many_row(rows, n_rows, blockIdx.x);
+  const uint32_t w = blockIdx.x - r.first;
+  open_tile_body<false>(r.window, w, (uint64_t)r.tile0 + w, r.ob, r.cv, 0);
+}
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_open_tile_many_group_kernel(const ManyRow *__restrict__ rows, uint32_t n_rows) {
+  const ManyRow r = many_row(rows, n_rows, blockIdx.x);
+  const uint32_t w = blockIdx.x - r.first;
+  open_tile_body<true>(r.window, w, (uint64_t)r.tile0 + w, r.ob, r.cv, r.gl);
+}
+
+// The blocks of the `tiles` full tiles of a file of `len` bytes (tiles MiB <= len) to their places in its outboard, and the header.  A
+// workgroup takes a piece of at most OPEN_PIECE bytes of one block (gl <= 2) or 2 .. 16 whole blocks, 256 >> tpw_log lanes a block; which
+// tile it is comes from blockIdx.x by division, the place from preorder_pos: once per workgroup where the workgroup has one block.
+// Source and destination are different buffers and no two workgroups share a byte of either.
+// A file of EXACTLY one full tile has no storey above and no tail: its root is the ROOT-flagged parent compression of the block's first
+// node (left CV || right CV of the tile's top merge, stored for every gl <= 6), which workgroup 0 computes here.
+__global__ __launch_bounds__(256) void b3w_bao_stream_open_relocate_kernel(const uint8_t *__restrict__ blocks, uint64_t len, uint32_t tiles,
+                                                                           uint32_t gl, uint8_t *__restrict__ ob, uint32_t *__restrict__ root) {
+  const OpenShape s = open_shape(gl);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    *reinterpret_cast<uint2 *>(ob) = make_uint2((uint32_t)len, (uint32_t)(len >> 32));
+    if (len == (uint64_t)B3W_TILE * 1024) {
+      uint32_t m[16], ivv[8], o[8];
+      load_node(blocks, m);
+      iv(ivv);
+      blake3_cv(ivv, m, 0, 0, 64, 4u | 8u, o);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) root[k] = o[k];
+    }
+  }
+  const uint32_t L = 256u >> s.tpw_log, lane = threadIdx.x & (L - 1);
+  const uint32_t wg_tile = (blockIdx.x / s.ppb) << s.tpw_log, piece = blockIdx.x % s.ppb;
+  const uint32_t tile = wg_tile + (threadIdx.x >> (8 - s.tpw_log));
+  if (tile >= tiles) return;
+  const uint64_t G1 = (1ull << gl) - 1, ng = (((len + 1023) / 1024) + G1) >> gl;
+  const uint32_t sh = 10 - gl;                            // a tile is 1 << sh groups
+  const uint64_t pos = s.tpw_log == 0 ? preorder_pos(ng, (uint64_t)wg_tile << sh, 1ull << sh) : preorder_pos(ng, (uint64_t)tile << sh, 1ull << sh);
+  const uint32_t at = piece * OPEN_PIECE, nb = s.bb - at < OPEN_PIECE ? s.bb - at : OPEN_PIECE;     // (a multiple of 64)
+  const uint8_t *__restrict__ src = blocks + (uint64_t)tile * s.bb + at;                             // (8 off a 16-byte boundary)
+  uint8_t *__restrict__ dst = ob + 8 + pos * 64 + at;
+  if (((uintptr_t)dst & 15) == 8) {                       // a 16-byte-aligned outboard: the blocks' phase
+    if (lane == 0) {
+      *reinterpret_cast<uint2 *>(dst) = *reinterpret_cast<const uint2 *>(src);
+      *reinterpret_cast<uint2 *>(dst + nb - 8) = *reinterpret_cast<const uint2 *>(src + nb - 8);
+    }
+    // the body: (nb - 16) / 16 <= 4 L pieces whatever gl is (nb <= OPEN_PIECE >> tpw_log, L = 256 >> tpw_log), so a lane has at most
+    // four; all four loads are issued before the first store (the compiler cannot know that dst and src never meet), a lane with
+    // fewer pieces loading the piece's first bytes again in place of a branch around the load.  The empty asm keeps the compiler
+    // from sinking each load into the branch of its store, where every one would be waited for alone.
+    uint4 v[4];
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) { const uint32_t o = 8 + (lane + k * L) * 16; v[k] = *reinterpret_cast<const uint4 *>(src + (o < nb - 8 ? o : 8)); }
+    asm volatile("" : "+v"(v[0].x), "+v"(v[0].y), "+v"(v[0].z), "+v"(v[0].w), "+v"(v[1].x), "+v"(v[1].y), "+v"(v[1].z), "+v"(v[1].w),
+                      "+v"(v[2].x), "+v"(v[2].y), "+v"(v[2].z), "+v"(v[2].w), "+v"(v[3].x), "+v"(v[3].y), "+v"(v[3].z), "+v"(v[3].w));
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) { const uint32_t o = 8 + (lane + k * L) * 16; if (o < nb - 8) *reinterpret_cast<uint4 *>(dst + o) = v[k]; }
+  } else {                                                // an outboard at 8 modulo 16: 8 bytes at a time, nb / 8 <= 8 L pieces
+    for (uint32_t r = 0; r < 2; ++r) {
+      uint2 v[4];
+#pragma unroll
+      for (uint32_t k = 0; k < 4; ++k) { const uint32_t o = (lane + (4 * r + k) * L) * 8; v[k] = *reinterpret_cast<const uint2 *>(src + (o < nb ? o : 0)); }
+      asm volatile("" : "+v"(v[0].x), "+v"(v[0].y), "+v"(v[1].x), "+v"(v[1].y), "+v"(v[2].x), "+v"(v[2].y), "+v"(v[3].x), "+v"(v[3].y));
+#pragma unroll
+      for (uint32_t k = 0; k < 4; ++k) { const uint32_t o = (lane + (4 * r + k) * L) * 8; if (o < nb) *reinterpret_cast<uint2 *>(dst + o) = v[k]; }
+    }
+  }
+}
+
 // the CV of a chunk on the host (chunk_cv's loop over blake3_cv): b3w_bao_slice_decode
 void host_chunk_cv(const uint8_t *src, uint32_t bytes, uint64_t c, uint32_t root, uint32_t h[8]) {
   const uint32_t nb = bytes ? (bytes + 63) / 64 : 1;
@@ -2250,6 +2369,8 @@ struct b3w_bao_stream {
   hipEvent_t begun = nullptr;
   bool finished = false;
   std::vector<uint64_t> seen;
+  uint64_t capacity = 0;                                 // open sessions: the bound given at begin (len is set by open_finish) ...
+  uint8_t *blocks = nullptr;                             // ... and block 0 of the staging
 };
 
 namespace {
@@ -2288,6 +2409,50 @@ b3w_bao_stream *stream_new(b3w_ctx *ctx, uint32_t kind, uint64_t len, uint32_t g
   s->scratch = reinterpret_cast<uint32_t *>(d_scratch);
   s->seen.assign((size_t)((s->tiles + 63) / 64), 0);
   return s;
+}
+
+// ---- open-length sessions: the host side ---------------------------------------------------------------------------------------------
+// pre-order position of the node over chunks (or groups) [a, a + size) of a tree over `total`: preorder_pos on the host
+uint64_t host_preorder_pos(uint64_t total, uint64_t a, uint64_t size) {
+  uint64_t p = 0, lo = 0, cnt = total;
+  while (cnt > 1 && !(lo == a && cnt == size)) {
+    uint64_t k = 1;
+    while (k * 2 < cnt) k *= 2;
+    if (a < lo + k) { p += 1; cnt = k; } else { p += k; lo += k; cnt -= k; }
+  }
+  return p;
+}
+
+uint64_t open_cap_tiles(uint64_t capacity) { return (num_chunks(capacity) + B3W_TILE - 1) / B3W_TILE; }   // scratch slots: the tail's tile included
+
+// the per-window rules of an open session (whole tiles only, inside the capacity, each tile once): the reason, or nullptr
+const char *open_window_refusal(const b3w_bao_stream *s, uint64_t offset, const uint8_t *d_window, uint64_t bytes, std::string *twice) {
+  const uint64_t TB = (uint64_t)B3W_TILE * 1024;
+  if (s->finished) return "the session is finished";
+  if (offset % TB) return "the offset is not a multiple of 1 MiB";
+  if (!bytes || !d_window) return "an empty window or a null pointer";
+  if (bytes % TB) return "the window of an open session is not whole tiles of 1 MiB (what does not fill a tile goes to b3w_bao_stream_open_finish)";
+  if (offset > s->capacity || bytes > s->capacity - offset) return "the window reaches past the session's capacity";
+  for (uint64_t t = offset / TB; t < (offset + bytes) / TB; ++t)
+    if (s->seen[t >> 6] >> (t & 63) & 1) { *twice = "tile " + std::to_string(t) + " was pushed before"; return twice->c_str(); }
+  return nullptr;
+}
+
+int32_t open_push(b3w_bao_stream *s, uint64_t offset, const uint8_t *d_window, uint64_t bytes, void *stream) {
+  b3w_ctx *ctx = s->ctx;
+  const uint64_t TB = (uint64_t)B3W_TILE * 1024;
+  std::string twice;
+  if (const char *why = open_window_refusal(s, offset, d_window, bytes, &twice)) { ctx->last_error = std::string("bao stream push: ") + why; return B3W_E_BAD_ARGUMENT; }
+  const uint64_t t0 = offset / TB, cnt = bytes / TB;
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  if (s->gl) hipLaunchKernelGGL(b3w_bao_stream_open_tile_group_kernel, dim3((uint32_t)cnt), dim3(B3W_TILE), 0, st, d_window, (uint32_t)t0, s->blocks, s->scratch, s->gl);
+  else hipLaunchKernelGGL(b3w_bao_stream_open_tile_kernel, dim3((uint32_t)cnt), dim3(B3W_TILE), 0, st, d_window, (uint32_t)t0, s->blocks, s->scratch);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(ctx, e, "bao stream push launch (open session)");
+  for (uint64_t t = t0; t < t0 + cnt; ++t) s->seen[t >> 6] |= 1ull << (t & 63);
+  s->pushed += cnt;
+  return B3W_OK;
 }
 
 }  // namespace
@@ -2343,6 +2508,7 @@ int32_t b3w_bao_stream_push(b3w_bao_stream *s, uint64_t offset, const uint8_t *d
   if (!s) return B3W_E_BAD_ARGUMENT;
   b3w_ctx *ctx = s->ctx;
   const uint64_t TB = (uint64_t)B3W_TILE * 1024;
+  if (s->kind == B3W_BAO_STREAM_OPEN) return open_push(s, offset, d_window, bytes, stream);
   if (s->finished) { ctx->last_error = "bao stream push: the session is finished"; return B3W_E_BAD_ARGUMENT; }
   if (offset % TB) { ctx->last_error = "bao stream push: the offset is not a multiple of 1 MiB"; return B3W_E_BAD_ARGUMENT; }
   if (!bytes || !d_window) { ctx->last_error = "bao stream push: an empty window or a null pointer"; return B3W_E_BAD_ARGUMENT; }
@@ -2365,6 +2531,7 @@ int32_t b3w_bao_stream_push(b3w_bao_stream *s, uint64_t offset, const uint8_t *d
 int32_t b3w_bao_stream_finish(b3w_bao_stream *s, void *stream) {
   if (!s) return B3W_E_BAD_ARGUMENT;
   b3w_ctx *ctx = s->ctx;
+  if (s->kind == B3W_BAO_STREAM_OPEN) { ctx->last_error = "bao stream finish: an open session is finished by b3w_bao_stream_open_finish"; return B3W_E_BAD_ARGUMENT; }
   if (s->finished) { ctx->last_error = "bao stream finish: the session is finished"; return B3W_E_BAD_ARGUMENT; }
   if (s->len && s->pushed != s->tiles) {
     ctx->last_error = "bao stream finish: " + std::to_string(s->tiles - s->pushed) + " of " + std::to_string(s->tiles) + " tiles have not been pushed";
@@ -2478,6 +2645,61 @@ void many_launch_tiles(uint32_t kind, bool grp, const ManyRow *d_rows, uint32_t 
   else hipLaunchKernelGGL(b3w_bao_stream_tile_many_kernel, dim3(wgs), dim3(B3W_TILE), 0, st, d_rows, n_rows);
 }
 
+// b3w_bao_stream_push_many for a call whose entry 0 is an open session: every session open, the open per-window rules, one launch
+int32_t open_push_many(b3w_ctx *ctx, b3w_bao_stream *const *sessions, const uint64_t *offsets, const uint8_t *const *d_windows, const uint64_t *bytes,
+                       uint32_t n, void *stream) {
+  const char *call = "push_many";
+  const uint64_t TB = (uint64_t)B3W_TILE * 1024;
+  struct Span { b3w_bao_stream *s; uint64_t t0, cnt; uint32_t i; };
+  std::vector<Span> spans(n);
+  uint64_t total = 0;
+  bool grp = false;
+  for (uint32_t i = 0; i < n; ++i) {                                  // every entry is checked before anything is launched or marked
+    b3w_bao_stream *s = sessions[i];
+    if (!s) return many_refuse(ctx, call, i, "a null session");
+    if (s->ctx != ctx) return many_refuse(ctx, call, i, "the session belongs to another context");
+    if (s->kind != B3W_BAO_STREAM_OPEN) return many_refuse(ctx, call, i, "the session is not of the kind of entry 0 (open sessions do not mix with sessions of known length)");
+    std::string twice;
+    if (const char *why = open_window_refusal(s, offsets[i], d_windows[i], bytes[i], &twice)) return many_refuse(ctx, call, i, why);
+    spans[i] = Span{s, offsets[i] / TB, bytes[i] / TB, i};
+    total += bytes[i] / TB;
+    grp = grp || s->gl != 0;
+  }
+  if (total > 0x7fffffffull) { ctx->last_error = "bao stream push_many: " + std::to_string(total) + " tiles in one call do not fit a 32-bit grid"; return B3W_E_BAD_ARGUMENT; }
+  std::vector<Span> by_tile(spans);
+  std::sort(by_tile.begin(), by_tile.end(), [](const Span &a, const Span &b) { return a.s != b.s ? std::less<const void *>()(a.s, b.s) : a.t0 != b.t0 ? a.t0 < b.t0 : a.i < b.i; });
+  for (uint32_t k = 1; k < n; ++k) {
+    const Span &a = by_tile[k - 1], &b = by_tile[k];
+    if (a.s == b.s && a.t0 + a.cnt > b.t0)
+      return many_refuse(ctx, call, a.i > b.i ? a.i : b.i, "tile " + std::to_string(b.t0) + " is named twice in the call (entry " + std::to_string(a.i < b.i ? a.i : b.i) + " has it too)");
+  }
+  std::vector<ManyRow> rows(n);
+  uint32_t first = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    ManyRow r{};
+    r.window = d_windows[i]; r.ob = spans[i].s->blocks; r.cv = spans[i].s->scratch;
+    r.first = first; r.tile0 = (uint32_t)spans[i].t0; r.gl = spans[i].s->gl;
+    rows[i] = r;
+    first += (uint32_t)spans[i].cnt;
+  }
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  b3w_ctx::ManySlot *slot = nullptr;
+  const int32_t rc = many_upload(ctx, rows, st, &slot);
+  if (rc) return rc;
+  const ManyRow *d_rows = reinterpret_cast<const ManyRow *>(slot->d);
+  if (grp) hipLaunchKernelGGL(b3w_bao_stream_open_tile_many_group_kernel, dim3(first), dim3(B3W_TILE), 0, st, d_rows, n);
+  else hipLaunchKernelGGL(b3w_bao_stream_open_tile_many_kernel, dim3(first), dim3(B3W_TILE), 0, st, d_rows, n);
+  const hipError_t e = hipGetLastError();
+  many_release(slot, st);
+  if (e != hipSuccess) return hip_fail(ctx, e, "bao stream push_many launch (open sessions)");
+  for (const Span &sp : spans) {
+    for (uint64_t t = sp.t0; t < sp.t0 + sp.cnt; ++t) sp.s->seen[t >> 6] |= 1ull << (t & 63);
+    sp.s->pushed += sp.cnt;
+  }
+  return B3W_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2487,6 +2709,7 @@ int32_t b3w_bao_stream_push_many(b3w_ctx *ctx, b3w_bao_stream *const *sessions, 
   if (!ctx) return B3W_E_BAD_ARGUMENT;
   if (!n) return B3W_OK;
   if (!sessions || !offsets || !d_windows || !bytes) { ctx->last_error = "bao stream push_many: a null array"; return B3W_E_BAD_ARGUMENT; }
+  if (sessions[0] && sessions[0]->kind == B3W_BAO_STREAM_OPEN) return open_push_many(ctx, sessions, offsets, d_windows, bytes, n, stream);
   const char *call = "push_many";
   const uint64_t TB = (uint64_t)B3W_TILE * 1024;
   struct Span { b3w_bao_stream *s; uint64_t t0, cnt; uint32_t i; };
@@ -2553,6 +2776,7 @@ int32_t b3w_bao_stream_finish_many(b3w_ctx *ctx, b3w_bao_stream *const *sessions
     const b3w_bao_stream *s = sessions[i];
     if (!s) return many_refuse(ctx, call, i, "a null session");
     if (s->ctx != ctx) return many_refuse(ctx, call, i, "the session belongs to another context");
+    if (s->kind == B3W_BAO_STREAM_OPEN) return many_refuse(ctx, call, i, "an open session is finished by b3w_bao_stream_open_finish");
     if (s->kind != sessions[0]->kind) return many_refuse(ctx, call, i, "the session is not of the kind of entry 0 (outboard and verification sessions do not mix)");
     if (s->finished) return many_refuse(ctx, call, i, "the session is finished");
     if (s->len && s->pushed != s->tiles)
@@ -2610,6 +2834,96 @@ int32_t b3w_bao_stream_finish_many(b3w_ctx *ctx, b3w_bao_stream *const *sessions
     if (e != hipSuccess) return hip_fail(ctx, e, "bao stream finish_many launch");
   }
   for (uint32_t i = 0; i < n; ++i) sessions[i]->finished = true;
+  return B3W_OK;
+}
+
+// ---- open-length sessions (b3wit.h "outboards of streamed files whose length is not known up front") ---------------------------
+uint64_t b3w_bao_stream_open_staging_bytes(uint64_t capacity_bytes, uint32_t group_log) {
+  if (group_log > B3W_BAO_MAX_GROUP_LOG) return 0;
+  return (capacity_bytes / ((uint64_t)B3W_TILE * 1024)) * open_shape(group_log).bb + OPEN_PAD;
+}
+
+uint64_t b3w_bao_stream_open_scratch_bytes(uint64_t capacity_bytes) {
+  const uint64_t tiles = open_cap_tiles(capacity_bytes);
+  return (tiles + (tiles + B3W_TILE - 1) / B3W_TILE) * 32;
+}
+
+uint64_t b3w_bao_stream_open_block_pos(uint64_t len, uint32_t group_log, uint64_t tile) {
+  const uint64_t TB = (uint64_t)B3W_TILE * 1024;
+  if (group_log > B3W_BAO_MAX_GROUP_LOG || tile >= len / TB) return UINT64_MAX;
+  const uint64_t G1 = (1ull << group_log) - 1;
+  return host_preorder_pos((num_chunks(len) + G1) >> group_log, (tile * B3W_TILE) >> group_log, B3W_TILE >> group_log);
+}
+
+int32_t b3w_bao_stream_open_begin(b3w_ctx *ctx, uint64_t capacity_bytes, uint32_t group_log, void *d_staging, uint64_t staging_bytes, void *d_scratch,
+                                  uint64_t scratch_bytes, b3w_bao_stream **out_session) {
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  if (!out_session) { ctx->last_error = "bao stream open: a null session pointer"; return B3W_E_BAD_ARGUMENT; }
+  *out_session = nullptr;
+  if (group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "bao stream open: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
+  if (num_chunks(capacity_bytes) > (1ull << 30)) { ctx->last_error = "bao stream open: a capacity of more than 2^30 chunks"; return B3W_E_BAD_ARGUMENT; }
+  if (!d_staging || !d_scratch) { ctx->last_error = "bao stream open: a null pointer (staging or scratch)"; return B3W_E_BAD_ARGUMENT; }
+  if (((uintptr_t)d_staging & 15) || ((uintptr_t)d_scratch & 15)) { ctx->last_error = "bao stream open: the staging or the scratch is not 16-byte aligned"; return B3W_E_BAD_ARGUMENT; }
+  if (staging_bytes < b3w_bao_stream_open_staging_bytes(capacity_bytes, group_log)) { ctx->last_error = "bao stream open: the staging is smaller than b3w_bao_stream_open_staging_bytes says"; return B3W_E_BAD_ARGUMENT; }
+  if (scratch_bytes < b3w_bao_stream_open_scratch_bytes(capacity_bytes)) { ctx->last_error = "bao stream open: the scratch is smaller than b3w_bao_stream_open_scratch_bytes says"; return B3W_E_BAD_ARGUMENT; }
+  b3w_bao_stream *s = new b3w_bao_stream;
+  s->ctx = ctx; s->kind = B3W_BAO_STREAM_OPEN; s->gl = group_log; s->capacity = capacity_bytes;
+  s->tiles = capacity_bytes / ((uint64_t)B3W_TILE * 1024);             // (the tiles a push may name; open_finish sets len, tiles and groups)
+  s->scratch = reinterpret_cast<uint32_t *>(d_scratch);
+  s->blocks = reinterpret_cast<uint8_t *>(d_staging) + OPEN_PAD / 2;
+  s->seen.assign((size_t)((s->tiles + 63) / 64), 0);
+  *out_session = s;
+  return B3W_OK;
+}
+
+int32_t b3w_bao_stream_open_finish(b3w_bao_stream *s, const uint8_t *d_tail, uint64_t tail_bytes, uint8_t *d_outboard, uint64_t outboard_bytes,
+                                   uint32_t *d_root, void *stream, uint64_t *out_len) {
+  if (!s) return B3W_E_BAD_ARGUMENT;
+  b3w_ctx *ctx = s->ctx;
+  const uint64_t TB = (uint64_t)B3W_TILE * 1024, T = s->pushed;
+  if (s->kind != B3W_BAO_STREAM_OPEN) { ctx->last_error = "bao stream open_finish: not an open session"; return B3W_E_BAD_ARGUMENT; }
+  if (s->finished) { ctx->last_error = "bao stream open_finish: the session is finished"; return B3W_E_BAD_ARGUMENT; }
+  for (uint64_t t = 0; t < T; ++t)
+    if (!(s->seen[t >> 6] >> (t & 63) & 1)) {
+      ctx->last_error = "bao stream open_finish: tile " + std::to_string(t) + " has not been pushed and a later one has (" + std::to_string(T) + " tiles were pushed)";
+      return B3W_E_BAD_ARGUMENT;
+    }
+  if (tail_bytes >= TB) { ctx->last_error = "bao stream open_finish: a tail of 1 MiB or more (whole tiles are pushed)"; return B3W_E_BAD_ARGUMENT; }
+  if (tail_bytes && !d_tail) { ctx->last_error = "bao stream open_finish: a null tail with bytes"; return B3W_E_BAD_ARGUMENT; }
+  const uint64_t len = T * TB + tail_bytes;
+  if (len > s->capacity) { ctx->last_error = "bao stream open_finish: the file (" + std::to_string(len) + " bytes) is longer than the session's capacity"; return B3W_E_BAD_ARGUMENT; }
+  if (!d_outboard || !d_root) { ctx->last_error = "bao stream open_finish: a null pointer (outboard or root)"; return B3W_E_BAD_ARGUMENT; }
+  if (((uintptr_t)d_outboard & 7) || ((uintptr_t)d_root & 3)) { ctx->last_error = "bao stream open_finish: d_outboard is not 8-byte aligned, or d_root not 4-byte aligned"; return B3W_E_BAD_ARGUMENT; }
+  if (outboard_bytes < b3w_bao_group_outboard_size(len, s->gl)) { ctx->last_error = "bao stream open_finish: the outboard is smaller than b3w_bao_group_outboard_size of the file's length"; return B3W_E_BAD_ARGUMENT; }
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t tiles = T + (tail_bytes || !T ? 1 : 0), groups = (tiles + B3W_TILE - 1) / B3W_TILE;
+  uint32_t *tile_cv = s->scratch, *group_cv = tile_cv + open_cap_tiles(s->capacity) * 8;
+  // at most four launches: the tail's tile (for T = 0 the whole file, rooted; header and all), the blocks to their places, the storeys
+  if (tail_bytes || !T) {
+    if (s->gl) hipLaunchKernelGGL(b3w_bao_stream_tile_group_kernel, dim3(1), dim3(B3W_TILE), 0, st, d_tail, len, (uint32_t)T, d_outboard, d_root, tile_cv, s->gl);
+    else hipLaunchKernelGGL(b3w_bao_stream_tile_kernel, dim3(1), dim3(B3W_TILE), 0, st, d_tail, len, (uint32_t)T, d_outboard, d_root, tile_cv);
+  }
+  if (T) {
+    const OpenShape sh = open_shape(s->gl);
+    const uint64_t wgs = ((T + (1ull << sh.tpw_log) - 1) >> sh.tpw_log) * sh.ppb;                    // (at most 2^22)
+    hipLaunchKernelGGL(b3w_bao_stream_open_relocate_kernel, dim3((uint32_t)wgs), dim3(256), 0, st, (const uint8_t *)s->blocks, len, (uint32_t)T, s->gl, d_outboard, d_root);
+  }
+  if (tiles > 1) {
+    const uint64_t U = B3W_TILE;
+    if (s->gl) {
+      hipLaunchKernelGGL(b3w_bao_stream_merge_group_kernel, dim3((uint32_t)groups), dim3(256), 0, st, len, U, (const uint32_t *)tile_cv, group_cv, d_outboard, d_root, s->gl);
+      if (groups > 1) hipLaunchKernelGGL(b3w_bao_stream_merge_group_kernel, dim3(1), dim3(256), 0, st, len, U * U, (const uint32_t *)group_cv, (uint32_t *)nullptr, d_outboard, d_root, s->gl);
+    } else {
+      hipLaunchKernelGGL(b3w_bao_stream_merge_kernel, dim3((uint32_t)groups), dim3(256), 0, st, len, U, (const uint32_t *)tile_cv, group_cv, d_outboard, d_root);
+      if (groups > 1) hipLaunchKernelGGL(b3w_bao_stream_merge_kernel, dim3(1), dim3(256), 0, st, len, U * U, (const uint32_t *)group_cv, (uint32_t *)nullptr, d_outboard, d_root);
+    }
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(ctx, e, "bao stream open_finish launch");
+  s->len = len; s->ob = d_outboard; s->root = d_root;
+  s->finished = true;
+  if (out_len) *out_len = len;
   return B3W_OK;
 }
 

@@ -820,6 +820,58 @@ int32_t b3w_bao_stream_push_many(b3w_ctx *ctx, b3w_bao_stream *const *sessions, 
                                  const uint64_t *bytes, uint32_t n, void *stream);
 int32_t b3w_bao_stream_finish_many(b3w_ctx *ctx, b3w_bao_stream *const *sessions, uint32_t n, void *stream);
 
+/* ---- outboards of streamed files whose length is not known up front (still ABI 1.4: new names only) ------------------
+ * The sessions above take the file's length at begin: the pre-order place of every node depends on the total chunk count.  An upload
+ * over chunked transfer encoding, a pipe or an archive member being produced has no length until its last byte.  An OPEN session takes
+ * an upper bound (capacity_bytes) instead, FULL tiles of 1 MiB in any order and on any stream, and the length only at finish.
+ * WHY IT WORKS: a full tile of 1 024 chunks is a complete subtree whatever the length turns out to be; its (1024 >> group_log) - 1
+ * stored nodes are contiguous in the file's pre-order (group) outboard, in an order of their own that does not depend on the file, and
+ * only the START of that run depends on the total; its chaining value is not ROOT-flagged unless the file is exactly that tile.  A push
+ * hashes its tiles into tile-local BLOCKS of a staging area of the caller's; finish moves every block to its place (one launch, a copy
+ * of the outboard: 64 MiB per GiB of file at group_log = 0, 960 bytes a MiB at 6) and runs the merge storeys of the sessions above.
+ * RESULTS after b3w_bao_stream_open_finish are byte for byte those of the batch calls for the same bytes as a batch of one — header,
+ * every node, root — and nothing beyond b3w_bao_group_outboard_size(len, group_log) bytes of d_outboard is written.
+ * REFUSALS as above: B3W_E_BAD_ARGUMENT, a b3w_last_error text, nothing launched, the session as it was and still usable. */
+#define B3W_BAO_STREAM_OPEN 2
+/* The staging bytes that are no block's: block t lies at byte 8 + t * ((1024 >> group_log) - 1) * 64 of a 16-byte-aligned staging,
+ * 8 bytes off a 16-byte boundary as the nodes of a 16-byte-aligned outboard are, and 8 bytes follow the last block. */
+#define B3W_BAO_STREAM_OPEN_STAGING_PAD 16
+/* Host only.  floor(capacity_bytes / 1 MiB) * ((1024 >> group_log) - 1) * 64 + B3W_BAO_STREAM_OPEN_STAGING_PAD; 0 for a group_log
+ * above B3W_BAO_MAX_GROUP_LOG. */
+uint64_t b3w_bao_stream_open_staging_bytes(uint64_t capacity_bytes, uint32_t group_log);
+/* Host only.  32 bytes per MiB of capacity (rounded up, at least one) and per 1 024 of those: the tile and group CVs of any length up
+ * to the capacity.  Never 0. */
+uint64_t b3w_bao_stream_open_scratch_bytes(uint64_t capacity_bytes);
+/* Host only.  The node index, in the outboard (group_log = 0) or group outboard of a file of `len` bytes, of the first node of the
+ * block of full tile `tile`: what the relocation computes on the device.  The block's nodes follow it without a gap.  UINT64_MAX
+ * where (tile + 1) MiB > len (not a full tile of that file) or group_log is above the maximum. */
+uint64_t b3w_bao_stream_open_block_pos(uint64_t len, uint32_t group_log, uint64_t tile);
+/* Opens a session of kind B3W_BAO_STREAM_OPEN for a file of at most capacity_bytes.  d_staging and d_scratch: 16-byte aligned, at
+ * least what the two size calls say; both stay the caller's and must live until the work of open_finish is done.  Launches nothing
+ * and has no device memory of its own.  Refused: a null context or session pointer, a group_log above the maximum, a capacity of
+ * more than 2^30 chunks, a null or misaligned pointer, a small staging or scratch.
+ * b3w_bao_stream_push takes an open session under these rules: offset a multiple of 1 MiB; bytes a POSITIVE MULTIPLE of 1 MiB (there
+ * is no ragged window: what does not fill a tile goes to open_finish); offset + bytes <= capacity_bytes; each tile once; not after
+ * open_finish.  One launch, a workgroup per tile; no header and no root are written.
+ * b3w_bao_stream_push_many takes a call whose sessions are ALL open (open is a kind: mixed with sessions of known length the call is
+ * refused atomically), group_log free per session, through the same table and staging ring: one launch.
+ * b3w_bao_stream_finish and _finish_many refuse an open session (finish_many atomically); b3w_bao_stream_free frees it. */
+int32_t b3w_bao_stream_open_begin(b3w_ctx *ctx, uint64_t capacity_bytes, uint32_t group_log, void *d_staging, uint64_t staging_bytes,
+                                  void *d_scratch, uint64_t scratch_bytes, b3w_bao_stream **out_session);
+/* The end of the file: with T tiles pushed the file is len = T MiB + tail_bytes, and d_tail holds its last tail_bytes < 1 MiB bytes
+ * (any alignment; NULL where tail_bytes is 0; it must live until `stream` has passed this call's work).  THE CALLER ORDERS `stream`
+ * BEHIND EVERY PUSH.  d_outboard: 8-byte aligned (16-byte aligned outboards are moved 16 bytes at a time, the others 8), at least
+ * b3w_bao_group_outboard_size(len, group_log) of outboard_bytes; d_root: 8 u32 on the device.  *out_len (may be NULL) = len.
+ * AT MOST FOUR LAUNCHES whatever the length: the tail's tile through the kernel of the sessions above with the now known length (for
+ * T = 0 that is the whole file, rooted; a file of no bytes gets its one launch); the relocation of the blocks, which also writes the
+ * header; the merge storey over the tile CVs (files of more than one tile) and the one above it (past 1 GiB).  A file of exactly
+ * 1 MiB is one block and no storey: its root is computed in the relocation launch from the block's first node.
+ * Refused: pushed tiles that are not exactly 0 .. T - 1 (the text names the lowest missing one), tail_bytes >= 1 MiB, a null tail
+ * with bytes, len above the capacity, a small outboard, a null or misaligned d_outboard / d_root, a session that is finished or not
+ * open. */
+int32_t b3w_bao_stream_open_finish(b3w_bao_stream *session, const uint8_t *d_tail, uint64_t tail_bytes, uint8_t *d_outboard,
+                                   uint64_t outboard_bytes, uint32_t *d_root, void *stream, uint64_t *out_len);
+
 /* ---- challenged paths and slices read in place from the file arena (still ABI 1.4: new names only) -----------------
  * b3w_sample_plan_batch_device, b3w_sample_plan_group_batch_device and b3w_bao_slice_batch_device take a dense copy of the sampled
  * chunks' (or groups') bytes, which the caller has to gather first.  These two take the arena the outboard and verification calls
