@@ -203,6 +203,7 @@ def lib():
         "b3w_bao_stream_open_block_pos": (u64, [u64, u32, u64]),
         "b3w_bao_stream_open_begin": (i32, [vp, u64, u32, vp, u64, vp, u64, ctypes.POINTER(vp)]),
         "b3w_bao_stream_open_finish": (i32, [vp, vp, u64, vp, u64, vp, vp, ctypes.POINTER(u64)]),
+        "b3w_bao_stream_open_finish_many": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, vp, vp]),
         "b3w_sample_plan_arena_device": (i32, [vp, vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp]),
         "b3w_bao_slice_arena_device": (i32, [vp, vp, u64, vp, vp, u32, u32, vp, vp, vp, u32, vp, vp]),
     }
@@ -235,7 +236,7 @@ EXPORTED_SYMBOLS = ("b3w_abi_version", "b3w_identify_wasm", "b3w_create", "b3w_d
                     "b3w_bao_stream_scratch_bytes", "b3w_bao_stream_outboard_begin", "b3w_bao_stream_verify_begin", "b3w_bao_stream_push",
                     "b3w_bao_stream_finish", "b3w_bao_stream_free", "b3w_bao_stream_push_many", "b3w_bao_stream_finish_many",
                     "b3w_bao_stream_open_staging_bytes", "b3w_bao_stream_open_scratch_bytes", "b3w_bao_stream_open_block_pos",
-                    "b3w_bao_stream_open_begin", "b3w_bao_stream_open_finish",
+                    "b3w_bao_stream_open_begin", "b3w_bao_stream_open_finish", "b3w_bao_stream_open_finish_many",
                     "b3w_sample_plan_arena_device", "b3w_bao_slice_arena_device")
 
 

@@ -14,7 +14,8 @@ every file of a batch held against its outboard and root on the device, a status
 stream) with the batch calls' results, and outboard_stream() / verify_stream() feed them from host memory or a reader through a ring
 of windows: the file need never be resident on the device.  StreamOutboardOpen / outboard_stream_open() do the same for a file whose
 LENGTH IS NOT KNOWN until its last byte (an upper bound instead): full MiB are hashed as they come into a staging area, and finish(),
-which learns the length, moves them to their places in the outboard.
+which learns the length, moves them to their places in the outboard.  open_finish_many() ends many such sessions in one call of at
+most four launches, and outboard_stream_open_many() keeps `lanes` sources of unknown length in flight with it.
 The records are
 word for word those the chain planner writes for the same chunks (ChainPlanner.plan), so every step is the reference's
 prove_chunk_hash step (rust_fold/src/main.rs:41-203 over hash_with_path's slice, rust_fold/src/blake3_hash.rs:17-93)."""
@@ -1061,3 +1062,166 @@ def verify_stream_many(ctx, sources, lengths, d_outboards, d_roots, window_bytes
                file_status=torch.empty(ln.size, dtype=torch.int32, device=dev), first_bad=torch.empty(ln.size, dtype=torch.int64, device=dev))
     _pump_many(ctx, STREAM_VERIFY, sources, lengths, window_bytes, group_log, lanes, ring, out)
     return dict(unit_status=out["unit_status"], unit_first=unit_first, file_status=out["file_status"], first_bad=out["first_bad"])
+
+
+# ---- many open-length sessions finished at once ----------------------------------------------------------------------------------
+def open_finish_many(sessions, d_tails=None, stream=0):
+    """session.finish(d_tails[i]) for every StreamOutboardOpen session (of one context, group_log free per session) as ONE call of at
+    most four launches on `stream`, which the caller orders behind every push.  d_tails: a list of uint8 CUDA tensors or Nones (None:
+    no session has a tail).  Every outboard and root is made as finish() makes them, the length known from the bytes counted.  If any
+    entry would be refused nothing is launched and no session changes (B3WError names the entry).  -> the list of finish()'s dicts."""
+    n = len(sessions)
+    d_tails = [None] * n if d_tails is None else list(d_tails)
+    if len(d_tails) != n:
+        raise B3WError(100, f"open_finish_many: {n} sessions and {len(d_tails)} tails")
+    if not n:
+        return []
+    for se in sessions:
+        if not isinstance(se, StreamOutboardOpen):
+            raise B3WError(100, "open_finish_many: not a StreamOutboardOpen session")
+    hs = _handles(sessions)
+    tails = [0 if t is None else t.numel() for t in d_tails]
+    for t, nb in zip(d_tails, tails):
+        if nb:
+            assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+    ob_firsts = [group_batch_layout([se._bytes + nb], se.group_log) for se, nb in zip(sessions, tails)]
+    obs = [torch.empty(int(f[-1]), dtype=torch.uint8, device=se.device) for se, f in zip(sessions, ob_firsts)]
+    roots = [torch.empty((1, 8), dtype=torch.int32, device=se.device) for se in sessions]
+    tp = np.array([t.data_ptr() if nb else 0 for t, nb in zip(d_tails, tails)], dtype=np.uint64)
+    op, rp = np.array([o.data_ptr() for o in obs], dtype=np.uint64), np.array([r.data_ptr() for r in roots], dtype=np.uint64)
+    tb, ob = _u64(tails), _u64([o.numel() for o in obs])
+    lens = np.zeros(n, dtype=np.uint64)
+    ctx = sessions[0].ctx
+    _chk(ctx, lib().b3w_bao_stream_open_finish_many(ctx.handle, hs.ctypes.data, tp.ctypes.data, tb.ctypes.data, op.ctypes.data, ob.ctypes.data,
+                                                    rp.ctypes.data, n, _stream(stream), lens.ctypes.data), "b3w_bao_stream_open_finish_many")
+    out = []
+    for i, se in enumerate(sessions):
+        se.length, se.outboards, se.ob_first, se.roots = int(lens[i]), obs[i], ob_firsts[i], roots[i]
+        out.append(dict(outboards=obs[i], ob_first=ob_firsts[i], roots=roots[i], length=se.length))
+    return out
+
+
+def _open_many_args(sources, capacities, window_bytes, group_log, lanes, ring):
+    """what outboard_stream_open_many refuses before it makes anything"""
+    if lanes < 1:
+        raise B3WError(100, "lanes must be at least 1")
+    _open_args(0, window_bytes, group_log, ring)
+    if len(sources) != len(capacities):
+        raise B3WError(100, f"{len(sources)} sources and {len(capacities)} capacities")
+    for f, (src, cap) in enumerate(zip(sources, capacities)):
+        if cap < 0:
+            raise B3WError(100, f"capacity {cap} of source {f} is negative")
+        if not hasattr(src, "readinto"):                # a buffer is taken whole: its size is known at once
+            size = src.nbytes if isinstance(src, np.ndarray) else memoryview(src).nbytes
+            if size > cap:
+                raise B3WError(100, f"source {f} holds {size} bytes, more than its capacity ({cap})")
+
+
+def _open_reader(source):
+    """-> fill(dst) -> the bytes put into dst (a writable numpy uint8 view): fewer than dst holds only at the source's end"""
+    if hasattr(source, "readinto"):
+        def fill(dst):
+            view, got = memoryview(dst), 0
+            while got < len(view):
+                k = source.readinto(view[got:])
+                if not k:
+                    break
+                got += k
+            return got
+        return fill
+    data = np.frombuffer(source, dtype=np.uint8) if not isinstance(source, np.ndarray) else source.reshape(-1).view(np.uint8)
+    at = [0]
+
+    def fill(dst):
+        got = min(dst.size, data.size - at[0])
+        dst[:got] = data[at[0]:at[0] + got]
+        at[0] += got
+        return got
+    return fill
+
+
+def outboard_stream_open_many(ctx, sources, capacities, window_bytes=DEFAULT_MANY_WINDOW_BYTES, group_log=0, lanes=DEFAULT_MANY_LANES, ring=2):
+    """outboard_stream_many for sources of UNKNOWN length, `lanes` of them in flight at once: sources[f] is what outboard_stream_open
+    takes (an object with readinto, read until it returns 0, a short read not being the end; or a bytes-like / numpy buffer, taken
+    whole) and capacities[f] bounds it; a source that yields more raises B3WError.  A round copies the next window of every open file
+    into its place in one of `ring` slabs of lanes x window_bytes (pinned host + device, a stream and an event each), pushes the whole
+    MiB of all lanes with ONE push_many and finishes the files that ended in the round with ONE open_finish_many on the slab's stream,
+    their tails still lying in the slab; a file that ends exactly on a window's last byte is found by the empty read of the next round
+    and gets no push and no tail.  Device memory made here is ring x lanes x window_bytes + per open lane a staging and a scratch for
+    its file's capacity + the outboards and roots: a finished file's staging and scratch are dropped with its session.
+    -> the list of StreamOutboardOpen.finish()'s dicts, one per file (no packed tensor: no length is known before a file's end); the
+    work is enqueued, the current stream ordered behind it.
+    The defaults are outboard_stream_many's and as unmeasured as they are there."""
+    _open_many_args(sources, capacities, window_bytes, group_log, lanes, ring)
+    n = len(sources)
+    if not n:
+        return []
+    capacities = [int(c) for c in capacities]
+    lanes = min(lanes, n)
+    cur = torch.cuda.current_stream()
+    slabs = [dict(h=torch.empty(lanes * window_bytes, dtype=torch.uint8, pin_memory=True),
+                  d=torch.empty(lanes * window_bytes, dtype=torch.uint8, device="cuda"), s=torch.cuda.Stream(), ev=torch.cuda.Event(), used=False)
+             for _ in range(ring)]
+    for sl in slabs:
+        sl["s"].wait_stream(cur)
+    results, open_, nxt, rnd = [None] * n, [None] * lanes, 0, 0                # open_[lane] = [session, file, fill, bytes so far]
+    try:
+        try:
+            while True:
+                for lane in range(lanes):               # free lanes take the next files
+                    if open_[lane] is None and nxt < n:
+                        f, nxt = nxt, nxt + 1
+                        open_[lane] = [StreamOutboardOpen(ctx, capacities[f], group_log), f, _open_reader(sources[f]), 0]
+                live = [lane for lane in range(lanes) if open_[lane] is not None]
+                if not live:
+                    break
+                sl = slabs[rnd % ring]
+                if sl["used"]:
+                    sl["ev"].synchronize()              # the slab's last copies, pushes and finishes are through with both buffers
+                ses, offs, wins, ended, tails = [], [], [], [], []
+                with torch.cuda.stream(sl["s"]):        # (the device slab's reuse is ordered by its stream)
+                    for lane in live:
+                        se, f, fill, total = open_[lane]
+                        at = lane * window_bytes
+                        got = fill(sl["h"][at:at + window_bytes].numpy())
+                        if total + got > capacities[f]:
+                            raise B3WError(100, f"source {f} yields more than its capacity ({capacities[f]} bytes)")
+                        whole = got // TILE_BYTES * TILE_BYTES
+                        if got:
+                            sl["d"][at:at + got].copy_(sl["h"][at:at + got], non_blocking=True)
+                        if whole:
+                            ses.append(se); offs.append(total); wins.append(sl["d"][at:at + whole])
+                        open_[lane][3] = total + got
+                        if got < window_bytes:          # the source has ended: in this window, or on the last byte of the one before
+                            ended.append(lane)
+                            tails.append(sl["d"][at + whole:at + got] if got > whole else None)
+                    push_many(ses, offs, wins, stream=sl["s"].cuda_stream)
+                if ended:                               # behind every push of theirs: the other slabs' last rounds too
+                    for other in slabs:
+                        if other is not sl and other["used"]:
+                            sl["s"].wait_event(other["ev"])
+                    done = [open_[lane][0] for lane in ended]
+                    # (outside the slab's stream: the outboards and roots are the current stream's memory, as the sessions' is)
+                    for lane, got in zip(ended, open_finish_many(done, tails, stream=sl["s"].cuda_stream)):
+                        results[open_[lane][1]] = got
+                sl["ev"].record(sl["s"])
+                sl["used"] = True
+                if ended:
+                    # The finished sessions' stagings and scratches are dropped here, and the next sessions (or outboards) may be given
+                    # the same memory at once: every slab's stream is put behind these finishes first.
+                    for other in slabs:
+                        if other is not sl:
+                            other["s"].wait_event(sl["ev"])
+                    for lane in ended:
+                        open_[lane][0].close()
+                        open_[lane] = None
+                    se = done = None                    # (the loop's own references: a dropped session's memory goes with the last one)
+                rnd += 1
+        finally:                                        # (also on a raise: nothing is dropped under work in flight)
+            for sl in slabs:
+                cur.wait_stream(sl["s"])
+    finally:
+        for ent in open_:
+            if ent is not None:
+                ent[0].close()
+    return results

@@ -36,6 +36,7 @@
 //                            of a table in place of the arguments by value ("many stream sessions in one launch")
 //   b3w_bao_stream_open_*    a file whose length is known only at finish: full tiles hashed into tile-local blocks of a staging area, and
 //                            the blocks moved to their pre-order places once the length is known ("open-length sessions")
+//                            (b3w_bao_stream_open_relocate_many_kernel: the blocks of many sessions moved in one grid)
 #include "b3w_internal.h"
 #include "b3w_blake3_dev.h"
 
@@ -1453,6 +1454,7 @@ __global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_verify_many_kernel(co
 //                                                 the tile's CV to scratch slot `tile`.  No header, no root, no length.
 //   b3w_bao_stream_open_tile_many[_group]_kernel  the same with the window, tile0, staging and scratch from a ManyRow (ob = the blocks)
 //   b3w_bao_stream_open_relocate_kernel           at finish, the length known: every block to ob + 8 + 64 preorder_pos(...), and the header
+//   b3w_bao_stream_open_relocate_many_kernel      the same for the sessions of a ManyRow table (window = the blocks, tile0 = the full tiles)
 // The tile of the file's tail goes through b3w_bao_stream_tile[_group]_kernel and the storeys above through b3w_bao_stream_merge[_group]_kernel
 // as they are.  Blocks start 8 bytes off a 16-byte boundary (the staging is 16-byte aligned and block 0 starts at byte 8), which is where
 // the nodes of a 16-byte-aligned outboard lie: merge_pair's 8-byte stores are aligned, and the relocation moves an 8-byte head, a body of
@@ -1525,6 +1527,69 @@ __global__ __launch_bounds__(256) void b3w_bao_stream_open_relocate_kernel(const
   }
   const uint32_t L = 256u >> s.tpw_log, lane = threadIdx.x & (L - 1);
   const uint32_t wg_tile = (blockIdx.x / s.ppb) << s.tpw_log, piece = blockIdx.x % s.ppb;
+  const uint32_t tile = wg_tile + (threadIdx.x >> (8 - s.tpw_log));
+  if (tile >= tiles) return;
+  const uint64_t G1 = (1ull << gl) - 1, ng = (((len + 1023) / 1024) + G1) >> gl;
+  const uint32_t sh = 10 - gl;                            // a tile is 1 << sh groups
+  const uint64_t pos = s.tpw_log == 0 ? preorder_pos(ng, (uint64_t)wg_tile << sh, 1ull << sh) : preorder_pos(ng, (uint64_t)tile << sh, 1ull << sh);
+  const uint32_t at = piece * OPEN_PIECE, nb = s.bb - at < OPEN_PIECE ? s.bb - at : OPEN_PIECE;     // (a multiple of 64)
+  const uint8_t *__restrict__ src = blocks + (uint64_t)tile * s.bb + at;                             // (8 off a 16-byte boundary)
+  uint8_t *__restrict__ dst = ob + 8 + pos * 64 + at;
+  if (((uintptr_t)dst & 15) == 8) {                       // a 16-byte-aligned outboard: the blocks' phase
+    if (lane == 0) {
+      *reinterpret_cast<uint2 *>(dst) = *reinterpret_cast<const uint2 *>(src);
+      *reinterpret_cast<uint2 *>(dst + nb - 8) = *reinterpret_cast<const uint2 *>(src + nb - 8);
+    }
+    // the body: (nb - 16) / 16 <= 4 L pieces whatever gl is (nb <= OPEN_PIECE >> tpw_log, L = 256 >> tpw_log), so a lane has at most
+    // four; all four loads are issued before the first store (the compiler cannot know that dst and src never meet), a lane with
+    // fewer pieces loading the piece's first bytes again in place of a branch around the load.  The empty asm keeps the compiler
+    // from sinking each load into the branch of its store, where every one would be waited for alone.
+    uint4 v[4];
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) { const uint32_t o = 8 + (lane + k * L) * 16; v[k] = *reinterpret_cast<const uint4 *>(src + (o < nb - 8 ? o : 8)); }
+    asm volatile("" : "+v"(v[0].x), "+v"(v[0].y), "+v"(v[0].z), "+v"(v[0].w), "+v"(v[1].x), "+v"(v[1].y), "+v"(v[1].z), "+v"(v[1].w),
+                      "+v"(v[2].x), "+v"(v[2].y), "+v"(v[2].z), "+v"(v[2].w), "+v"(v[3].x), "+v"(v[3].y), "+v"(v[3].z), "+v"(v[3].w));
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) { const uint32_t o = 8 + (lane + k * L) * 16; if (o < nb - 8) *reinterpret_cast<uint4 *>(dst + o) = v[k]; }
+  } else {                                                // an outboard at 8 modulo 16: 8 bytes at a time, nb / 8 <= 8 L pieces
+    for (uint32_t r = 0; r < 2; ++r) {
+      uint2 v[4];
+#pragma unroll
+      for (uint32_t k = 0; k < 4; ++k) { const uint32_t o = (lane + (4 * r + k) * L) * 8; v[k] = *reinterpret_cast<const uint2 *>(src + (o < nb ? o : 0)); }
+      asm volatile("" : "+v"(v[0].x), "+v"(v[0].y), "+v"(v[1].x), "+v"(v[1].y), "+v"(v[2].x), "+v"(v[2].y), "+v"(v[3].x), "+v"(v[3].y));
+#pragma unroll
+      for (uint32_t k = 0; k < 4; ++k) { const uint32_t o = (lane + (4 * r + k) * L) * 8; if (o < nb) *reinterpret_cast<uint2 *>(dst + o) = v[k]; }
+    }
+  }
+}
+
+// The same for a table of sessions, one grid: a row per file of one full tile or more, with window = the session's blocks, ob and root
+// the file's, len its now-known length, tile0 = its count of full tiles and gl its group_log.  A row has
+// ((tile0 + 2^tpw_log - 1) >> tpw_log) * ppb workgroups of open_shape(gl), which differs from row to row; a workgroup lies in one row,
+// so its outboard's phase, and with it the choice between the 16-byte and the 8-byte moves, is one for all its lanes.  The body is the
+// kernel's above restated with the row's fields and the workgroup's index within the row (sharing one inlined body changed that
+// kernel's ISA: DESIGN.md 8g).
+__global__ __launch_bounds__(256) void b3w_bao_stream_open_relocate_many_kernel(const ManyRow *__restrict__ rows, uint32_t n_rows) {
+  const ManyRow row = many_row(rows, n_rows, blockIdx.x);
+  const uint8_t *__restrict__ blocks = row.window;
+  uint8_t *__restrict__ ob = row.ob;
+  uint32_t *__restrict__ root = row.root;
+  const uint64_t len = row.len;
+  const uint32_t tiles = row.tile0, gl = row.gl, wg = blockIdx.x - row.first;
+  const OpenShape s = open_shape(gl);
+  if (wg == 0 && threadIdx.x == 0) {
+    *reinterpret_cast<uint2 *>(ob) = make_uint2((uint32_t)len, (uint32_t)(len >> 32));
+    if (len == (uint64_t)B3W_TILE * 1024) {
+      uint32_t m[16], ivv[8], o[8];
+      load_node(blocks, m);
+      iv(ivv);
+      blake3_cv(ivv, m, 0, 0, 64, 4u | 8u, o);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) root[k] = o[k];
+    }
+  }
+  const uint32_t L = 256u >> s.tpw_log, lane = threadIdx.x & (L - 1);
+  const uint32_t wg_tile = (wg / s.ppb) << s.tpw_log, piece = wg % s.ppb;
   const uint32_t tile = wg_tile + (threadIdx.x >> (8 - s.tpw_log));
   if (tile >= tiles) return;
   const uint64_t G1 = (1ull << gl) - 1, ng = (((len + 1023) / 1024) + G1) >> gl;
@@ -2924,6 +2989,123 @@ int32_t b3w_bao_stream_open_finish(b3w_bao_stream *s, const uint8_t *d_tail, uin
   s->len = len; s->ob = d_outboard; s->root = d_root;
   s->finished = true;
   if (out_len) *out_len = len;
+  return B3W_OK;
+}
+
+// b3w_bao_stream_open_finish for n sessions in at most four launches: one table through the staging ring in four runs of rows (the
+// tails' tiles, the relocations, the first merge storey, the second), each run the rows of one grid.  The runs write disjoint bytes of
+// every file (the storeys only nodes above tiles, the tail's tile only nodes below its own root, the blocks neither), so their order on
+// the one stream is free.
+int32_t b3w_bao_stream_open_finish_many(b3w_ctx *ctx, b3w_bao_stream *const *sessions, const uint8_t *const *d_tails, const uint64_t *tail_bytes,
+                                        uint8_t *const *d_outboards, const uint64_t *outboard_bytes, uint32_t *const *d_roots, uint32_t n, void *stream,
+                                        uint64_t *out_lens) {
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  if (!n) return B3W_OK;
+  if (!sessions || !d_tails || !tail_bytes || !d_outboards || !outboard_bytes || !d_roots) { ctx->last_error = "bao stream open_finish_many: a null array"; return B3W_E_BAD_ARGUMENT; }
+  const char *call = "open_finish_many";
+  const uint64_t TB = (uint64_t)B3W_TILE * 1024, LIMIT = 0x7fffffffull;
+  std::vector<uint64_t> lens(n);
+  uint64_t wg_tail = 0, wg_move = 0, wg_one = 0, wg_two = 0;
+  bool grp = false;
+  for (uint32_t i = 0; i < n; ++i) {                                  // every entry is checked before anything is launched or marked
+    const b3w_bao_stream *s = sessions[i];
+    if (!s) return many_refuse(ctx, call, i, "a null session");
+    if (s->ctx != ctx) return many_refuse(ctx, call, i, "the session belongs to another context");
+    if (s->kind != B3W_BAO_STREAM_OPEN) return many_refuse(ctx, call, i, "not an open session");
+    if (s->finished) return many_refuse(ctx, call, i, "the session is finished");
+    const uint64_t T = s->pushed;
+    for (uint64_t t = 0; t < T; ++t)
+      if (!(s->seen[t >> 6] >> (t & 63) & 1))
+        return many_refuse(ctx, call, i, "tile " + std::to_string(t) + " has not been pushed and a later one has (" + std::to_string(T) + " tiles were pushed)");
+    if (tail_bytes[i] >= TB) return many_refuse(ctx, call, i, "a tail of 1 MiB or more (whole tiles are pushed)");
+    if (tail_bytes[i] && !d_tails[i]) return many_refuse(ctx, call, i, "a null tail with bytes");
+    const uint64_t len = T * TB + tail_bytes[i];
+    if (len > s->capacity) return many_refuse(ctx, call, i, "the file (" + std::to_string(len) + " bytes) is longer than the session's capacity");
+    if (!d_outboards[i] || !d_roots[i]) return many_refuse(ctx, call, i, "a null pointer (outboard or root)");
+    if (((uintptr_t)d_outboards[i] & 7) || ((uintptr_t)d_roots[i] & 3)) return many_refuse(ctx, call, i, "d_outboard is not 8-byte aligned, or d_root not 4-byte aligned");
+    if (outboard_bytes[i] < b3w_bao_group_outboard_size(len, s->gl)) return many_refuse(ctx, call, i, "the outboard is smaller than b3w_bao_group_outboard_size of the file's length");
+    lens[i] = len;
+    const bool tail = tail_bytes[i] || !T;
+    const uint64_t tiles = T + (tail ? 1 : 0);
+    const OpenShape sh = open_shape(s->gl);
+    wg_tail += tail ? 1 : 0;
+    wg_move += ((T + (1ull << sh.tpw_log) - 1) >> sh.tpw_log) * sh.ppb;
+    wg_one += tiles > 1 ? (tiles + B3W_TILE - 1) / B3W_TILE : 0;
+    wg_two += tiles > B3W_TILE ? 1 : 0;
+    if (wg_tail > LIMIT || wg_move > LIMIT || wg_one > LIMIT || wg_two > LIMIT)
+      return many_refuse(ctx, call, i, "with this entry one of the call's four grids has more than 2^31 - 1 workgroups");
+    grp = grp || s->gl != 0;
+  }
+  std::vector<std::pair<const b3w_bao_stream *, uint32_t>> by_ptr(n);
+  for (uint32_t i = 0; i < n; ++i) by_ptr[i] = {sessions[i], i};
+  std::sort(by_ptr.begin(), by_ptr.end(), [](const auto &a, const auto &b) { return a.first != b.first ? std::less<const void *>()(a.first, b.first) : a.second < b.second; });
+  for (uint32_t k = 1; k < n; ++k)
+    if (by_ptr[k - 1].first == by_ptr[k].first)
+      return many_refuse(ctx, call, by_ptr[k].second, "the session appears twice in the call (entry " + std::to_string(by_ptr[k - 1].second) + " is the same)");
+  // the row of entry i for one of the runs: the file's length, outboard, root and group_log; the run sets the rest
+  auto row = [&](uint32_t i, uint32_t first) {
+    ManyRow r{};
+    r.len = lens[i]; r.ob = d_outboards[i]; r.root = d_roots[i]; r.gl = sessions[i]->gl; r.tile0 = (uint32_t)sessions[i]->pushed; r.first = first;
+    return r;
+  };
+  std::vector<ManyRow> rows;
+  rows.reserve((size_t)n * 2);
+  uint32_t n_tail = 0, n_move = 0, n_one = 0, n_two = 0, first = 0;
+  for (uint32_t i = 0; i < n; ++i) {                                  // the tails' tiles (for T = 0 the whole file, rooted; header and all)
+    if (!tail_bytes[i] && sessions[i]->pushed) continue;
+    ManyRow r = row(i, n_tail);
+    r.window = d_tails[i]; r.cv = sessions[i]->scratch;
+    rows.push_back(r); n_tail++;
+  }
+  for (uint32_t i = 0; i < n; ++i) {                                  // the blocks to their places, and the headers
+    const uint64_t T = sessions[i]->pushed;
+    if (!T) continue;
+    const OpenShape sh = open_shape(sessions[i]->gl);
+    ManyRow r = row(i, first);
+    r.window = sessions[i]->blocks;
+    rows.push_back(r); n_move++;
+    first += (uint32_t)(((T + (1ull << sh.tpw_log) - 1) >> sh.tpw_log) * sh.ppb);
+  }
+  first = 0;
+  for (uint32_t i = 0; i < n; ++i) {                                  // the first merge storey: a workgroup per 1 024 tiles
+    const uint64_t tiles = (lens[i] + TB - 1) / TB;
+    if (tiles <= 1) continue;
+    ManyRow r = row(i, first);
+    r.cv = sessions[i]->scratch; r.aux = sessions[i]->scratch + open_cap_tiles(sessions[i]->capacity) * 8;
+    rows.push_back(r); n_one++;
+    first += (uint32_t)((tiles + B3W_TILE - 1) / B3W_TILE);
+  }
+  for (uint32_t i = 0; i < n; ++i) {                                  // the second: files past 1 GiB
+    if ((lens[i] + TB - 1) / TB <= B3W_TILE) continue;
+    ManyRow r = row(i, n_two);
+    r.cv = sessions[i]->scratch + open_cap_tiles(sessions[i]->capacity) * 8;
+    rows.push_back(r); n_two++;
+  }
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  b3w_ctx::ManySlot *slot = nullptr;
+  const int32_t rc = many_upload(ctx, rows, st, &slot);
+  if (rc) return rc;
+  const ManyRow *d_tail = reinterpret_cast<const ManyRow *>(slot->d), *d_move = d_tail + n_tail, *d_one = d_move + n_move, *d_two = d_one + n_one;
+  const uint64_t U = B3W_TILE;
+  if (n_tail) many_launch_tiles(B3W_BAO_STREAM_OUTBOARD, grp, d_tail, n_tail, n_tail, st);
+  if (n_move) hipLaunchKernelGGL(b3w_bao_stream_open_relocate_many_kernel, dim3((uint32_t)wg_move), dim3(256), 0, st, d_move, n_move);
+  if (grp) {
+    if (n_one) hipLaunchKernelGGL(b3w_bao_stream_merge_many_group_kernel, dim3((uint32_t)wg_one), dim3(256), 0, st, d_one, n_one, U);
+    if (n_two) hipLaunchKernelGGL(b3w_bao_stream_merge_many_group_kernel, dim3(n_two), dim3(256), 0, st, d_two, n_two, U * U);
+  } else {
+    if (n_one) hipLaunchKernelGGL(b3w_bao_stream_merge_many_kernel, dim3((uint32_t)wg_one), dim3(256), 0, st, d_one, n_one, U);
+    if (n_two) hipLaunchKernelGGL(b3w_bao_stream_merge_many_kernel, dim3(n_two), dim3(256), 0, st, d_two, n_two, U * U);
+  }
+  const hipError_t e = hipGetLastError();
+  many_release(slot, st);
+  if (e != hipSuccess) return hip_fail(ctx, e, "bao stream open_finish_many launch");
+  for (uint32_t i = 0; i < n; ++i) {
+    b3w_bao_stream *s = sessions[i];
+    s->len = lens[i]; s->ob = d_outboards[i]; s->root = d_roots[i];
+    s->finished = true;
+    if (out_lens) out_lens[i] = lens[i];
+  }
   return B3W_OK;
 }
 

@@ -855,7 +855,8 @@ uint64_t b3w_bao_stream_open_block_pos(uint64_t len, uint32_t group_log, uint64_
  * open_finish.  One launch, a workgroup per tile; no header and no root are written.
  * b3w_bao_stream_push_many takes a call whose sessions are ALL open (open is a kind: mixed with sessions of known length the call is
  * refused atomically), group_log free per session, through the same table and staging ring: one launch.
- * b3w_bao_stream_finish and _finish_many refuse an open session (finish_many atomically); b3w_bao_stream_free frees it. */
+ * b3w_bao_stream_finish and _finish_many refuse an open session (finish_many atomically): open sessions end through
+ * b3w_bao_stream_open_finish, or many of them at once through b3w_bao_stream_open_finish_many; b3w_bao_stream_free frees it. */
 int32_t b3w_bao_stream_open_begin(b3w_ctx *ctx, uint64_t capacity_bytes, uint32_t group_log, void *d_staging, uint64_t staging_bytes,
                                   void *d_scratch, uint64_t scratch_bytes, b3w_bao_stream **out_session);
 /* The end of the file: with T tiles pushed the file is len = T MiB + tail_bytes, and d_tail holds its last tail_bytes < 1 MiB bytes
@@ -871,6 +872,21 @@ int32_t b3w_bao_stream_open_begin(b3w_ctx *ctx, uint64_t capacity_bytes, uint32_
  * open. */
 int32_t b3w_bao_stream_open_finish(b3w_bao_stream *session, const uint8_t *d_tail, uint64_t tail_bytes, uint8_t *d_outboard,
                                    uint64_t outboard_bytes, uint32_t *d_root, void *stream, uint64_t *out_len);
+/* b3w_bao_stream_open_finish for MANY open sessions of `ctx` at once: entry i means exactly what b3w_bao_stream_open_finish(
+ * sessions[i], d_tails[i], tail_bytes[i], d_outboards[i], outboard_bytes[i], d_roots[i], stream, &out_lens[i]) means, and the bytes it
+ * leaves are that call's: header, every node, root, and nothing behind b3w_bao_group_outboard_size(len, group_log).  group_log is free
+ * per session.  out_lens may be NULL.  THE CALLER ORDERS `stream` BEHIND EVERY PUSH of every session.  n == 0: B3W_OK, nothing launched.
+ * AT MOST FOUR LAUNCHES whatever n and the lengths are: the tails' tiles of all sessions that have one (files of no bytes among them),
+ * the relocation of all blocks with the headers, the first merge storey of all files of more than one tile, the second of all files
+ * past 1 GiB.  One table of 88-byte rows, a row per session and launch it takes part in, goes through the staging ring of the many-calls
+ * above; a call that mixes group_log = 0 with larger ones runs the group kernels for all.  The host waits for nothing.
+ * REFUSALS ARE ATOMIC as in the many-calls above (B3W_E_BAD_ARGUMENT, nothing launched, no session changed, b3w_last_error names the
+ * entry and the reason): what open_finish refuses per entry, a null array (out_lens excepted), a null session, a session of another
+ * context, a session that is not open, a session twice in the call, more than 2^31 - 1 workgroups in one of the four grids.
+ * Two entries whose outboards or roots overlap are NOT looked for: that is the caller's business, as with two calls of open_finish. */
+int32_t b3w_bao_stream_open_finish_many(b3w_ctx *ctx, b3w_bao_stream *const *sessions, const uint8_t *const *d_tails,
+                                        const uint64_t *tail_bytes, uint8_t *const *d_outboards, const uint64_t *outboard_bytes,
+                                        uint32_t *const *d_roots, uint32_t n, void *stream, uint64_t *out_lens);
 
 /* ---- challenged paths and slices read in place from the file arena (still ABI 1.4: new names only) -----------------
  * b3w_sample_plan_batch_device, b3w_sample_plan_group_batch_device and b3w_bao_slice_batch_device take a dense copy of the sampled
