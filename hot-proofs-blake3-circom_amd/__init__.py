@@ -206,6 +206,9 @@ def lib():
         "b3w_bao_stream_open_finish_many": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, vp, vp]),
         "b3w_sample_plan_arena_device": (i32, [vp, vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp]),
         "b3w_bao_slice_arena_device": (i32, [vp, vp, u64, vp, vp, u32, u32, vp, vp, vp, u32, vp, vp]),
+        "b3w_bao_update_scratch_bytes": (u64, [vp, vp, vp, vp, u32]),
+        "b3w_bao_outboard_update_batch_device": (i32, [vp, vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, u32, vp, u64, vp]),
+        "b3w_bao_outboard_update": (i32, [vp, u64, vp, u32, vp, vp, u32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -237,7 +240,8 @@ EXPORTED_SYMBOLS = ("b3w_abi_version", "b3w_identify_wasm", "b3w_create", "b3w_d
                     "b3w_bao_stream_finish", "b3w_bao_stream_free", "b3w_bao_stream_push_many", "b3w_bao_stream_finish_many",
                     "b3w_bao_stream_open_staging_bytes", "b3w_bao_stream_open_scratch_bytes", "b3w_bao_stream_open_block_pos",
                     "b3w_bao_stream_open_begin", "b3w_bao_stream_open_finish", "b3w_bao_stream_open_finish_many",
-                    "b3w_sample_plan_arena_device", "b3w_bao_slice_arena_device")
+                    "b3w_sample_plan_arena_device", "b3w_bao_slice_arena_device",
+                    "b3w_bao_update_scratch_bytes", "b3w_bao_outboard_update_batch_device", "b3w_bao_outboard_update")
 
 
 class graph_capture:

@@ -1445,6 +1445,147 @@ __global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_verify_many_kernel(co
   }
 }
 
+// ---- updates in place: outboards of resident files after writes to some of their chunks ------------------------------------------------
+// A stored node is left CV || right CV, so the CV of every clean sibling on a dirty chunk's path is in the outboard already: only the dirty
+// chunks are hashed from bytes, and only the nodes with a dirty unit below them are written, each dirty half alone (b3wit.h "updates in
+// place").  The storeys are the batch kernels': a workgroup per DIRTY tile, then one per span of 1 024 tiles that holds a dirty tile (and
+// once more over the spans' CVs for files past 1 GiB).  Files of at most 64 chunks are rehashed whole by b3w_bao_small[_group]_kernel.
+//   b3w_bao_update_tile[_group]_kernel    lane = chunk; the lanes of dirty chunks hash; the sparse merge; the tile's CV to its compact
+//                                         scratch slot, or (a one-tile file) the ROOT-flagged top merge to the file's root
+//   b3w_bao_update_merge[_group]_kernel   the same merge over the tiles of a span (unit = B3W_TILE) or the spans of a file (B3W_TILE^2): the
+//                                         dirty items' CVs from consecutive scratch slots (the rows are sorted: slot = base + dirty items below)
+// A row per workgroup, indexed by blockIdx.x.  mask: bit i = item i of the workgroup (a chunk of the tile, a tile of the span, a span of the
+// file) is dirty; the host expands chunk masks to whole groups, so inside a dirty group every chunk is hashed and nothing is loaded.
+struct UpdRow {
+  uint64_t len;
+  const uint8_t *data;                                   // the file's first byte (tile rows)
+  uint8_t *ob;                                           // the file's outboard, header first
+  uint32_t *root;
+  uint32_t *in;                                          // merge rows: the scratch slot of the workgroup's first dirty item
+  uint32_t *out;                                         // the workgroup's own scratch slot (unused where its top merge is the file's)
+  uint32_t idx, gl;                                      // the tile within the file / the span within the file (0 one storey up)
+  uint32_t mask[B3W_TILE / 32];
+};
+
+// one parent of the sparse merge: a dirty half from its LDS slot, a clean half from the stored node; the dirty halves alone are stored,
+// the parent's CV goes to slot i0.  GRP: a null `node` is a node inside a (dirty) chunk group: both halves are in LDS, nothing is stored.
+template <bool GRP>
+__device__ __forceinline__ void update_pair(uint32_t *cv, uint32_t i0, uint32_t i1, bool d0, bool d1, uint8_t *__restrict__ node, uint32_t d) {
+  uint32_t m[16], ivv[8], o[8];
+  uint2 *nd = reinterpret_cast<uint2 *>(node);                       // (8 off a 16-byte boundary)
+  const bool inside = GRP && !node;
+  if (d0 || inside) {
+    const uint4 l0 = reinterpret_cast<const uint4 *>(cv + i0 * 8)[0], l1 = reinterpret_cast<const uint4 *>(cv + i0 * 8)[1];
+    m[0] = l0.x; m[1] = l0.y; m[2] = l0.z; m[3] = l0.w; m[4] = l1.x; m[5] = l1.y; m[6] = l1.z; m[7] = l1.w;
+    if (!inside) { nd[0] = make_uint2(m[0], m[1]); nd[1] = make_uint2(m[2], m[3]); nd[2] = make_uint2(m[4], m[5]); nd[3] = make_uint2(m[6], m[7]); }
+  } else {
+    const uint2 a = nd[0], b = nd[1], c = nd[2], e = nd[3];
+    m[0] = a.x; m[1] = a.y; m[2] = b.x; m[3] = b.y; m[4] = c.x; m[5] = c.y; m[6] = e.x; m[7] = e.y;
+  }
+  if (d1 || inside) {
+    const uint4 r0 = reinterpret_cast<const uint4 *>(cv + i1 * 8)[0], r1 = reinterpret_cast<const uint4 *>(cv + i1 * 8)[1];
+    m[8] = r0.x; m[9] = r0.y; m[10] = r0.z; m[11] = r0.w; m[12] = r1.x; m[13] = r1.y; m[14] = r1.z; m[15] = r1.w;
+    if (!inside) { nd[4] = make_uint2(m[8], m[9]); nd[5] = make_uint2(m[10], m[11]); nd[6] = make_uint2(m[12], m[13]); nd[7] = make_uint2(m[14], m[15]); }
+  } else {
+    const uint2 a = nd[4], b = nd[5], c = nd[6], e = nd[7];
+    m[8] = a.x; m[9] = a.y; m[10] = b.x; m[11] = b.y; m[12] = c.x; m[13] = c.y; m[14] = e.x; m[15] = e.y;
+  }
+  iv(ivv);
+  blake3_cv(ivv, m, 0, 0, 64, d, o);
+  reinterpret_cast<uint4 *>(cv + i0 * 8)[0] = make_uint4(o[0], o[1], o[2], o[3]);          // (slot i0 is this thread's alone at this level)
+  reinterpret_cast<uint4 *>(cv + i0 * 8)[1] = make_uint4(o[4], o[5], o[6], o[7]);
+}
+
+// merge_in_lds over the dirty items alone: dirty[i] says whether slot i holds a CV (an item with a dirty chunk below it).  A pair with no
+// dirty child is skipped; any other one leaves its CV in slot i0 and marks it; an odd item out waits and keeps its flag.  The arguments are
+// merge_in_lds's; ends with a barrier, the tree's CV in cv[0 .. 8) where the tree holds a dirty item.
+template <int BS, bool GRP>
+__device__ __forceinline__ void update_in_lds(uint32_t *cv, uint32_t *dirty, uint32_t cnt, uint64_t unit, uint64_t total, uint8_t *__restrict__ nodes,
+                                              bool root, uint32_t gl) {
+  for (uint32_t l = 0; (1u << l) < cnt; ++l) {
+    lds_barrier();
+    const bool top = (2u << l) >= cnt;
+    for (uint32_t j = threadIdx.x;; j += BS) {
+      const uint32_t i0 = (2 * j) << l, i1 = i0 + (1u << l);
+      if (i1 >= cnt) break;
+      const bool d0 = dirty[i0] != 0, d1 = dirty[i1] != 0;
+      if (!d0 && !d1) continue;
+      const uint64_t a = i0 * unit, e = (uint64_t)(i0 + (2u << l)) * unit, size = (e < total ? e : total) - a;
+      uint8_t *node;
+      if (GRP) {
+        const uint64_t G1 = (1ull << gl) - 1;
+        node = size > G1 + 1 ? nodes + preorder_pos((total + G1) >> gl, a >> gl, (size + G1) >> gl) * 64 : nullptr;
+      } else {
+        node = nodes + preorder_pos(total, a, size) * 64;
+      }
+      update_pair<GRP>(cv, i0, i1, d0, d1, node, 4u | (top && root ? 8u : 0u));
+      dirty[i0] = 1;
+    }
+  }
+  lds_barrier();
+}
+
+template <bool GRP>
+__device__ __forceinline__ void update_tile_body(const UpdRow *__restrict__ rows) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
+  __shared__ uint32_t dirty[B3W_TILE];
+  const UpdRow *__restrict__ r = rows + blockIdx.x;
+  const uint32_t t = threadIdx.x, gl = GRP ? r->gl : 0;
+  const uint64_t len = r->len, n = (len + 1023) / 1024;               // (more than 64 chunks)
+  const uint64_t a0 = (uint64_t)r->idx * B3W_TILE;
+  const uint32_t m = (uint32_t)(n - a0 < B3W_TILE ? n - a0 : B3W_TILE);
+  const bool sole = n <= B3W_TILE;
+  const bool mine = t < m && ((r->mask[t >> 5] >> (t & 31)) & 1u);
+  dirty[t] = mine ? 1u : 0u;
+  if (mine) {
+    const uint64_t c = a0 + t, off = c * 1024;
+    uint32_t h[8];
+    chunk_cv(as_global(r->data) + off, (uint32_t)(len - off < 1024 ? len - off : 1024), c, 0, h);
+    reinterpret_cast<uint4 *>(cv + t * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
+    reinterpret_cast<uint4 *>(cv + t * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
+  }
+  const uint64_t G1 = GRP ? (1ull << gl) - 1 : 0;                     // (a tile starts at a multiple of every group size)
+  update_in_lds<B3W_TILE, GRP>(cv, dirty, m, 1, m, as_global(r->ob) + 8 + (GRP ? preorder_pos((n + G1) >> gl, a0 >> gl, (m + G1) >> gl) : preorder_pos(n, a0, m)) * 64,
+                               sole, gl);
+  if (t < 8) as_global(sole ? r->root : r->out)[t] = cv[t];            // (the row's mask is not empty: slot 0 holds the tile's CV)
+}
+
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_update_tile_kernel(const UpdRow *__restrict__ rows) { update_tile_body<false>(rows); }
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_update_tile_group_kernel(const UpdRow *__restrict__ rows) { update_tile_body<true>(rows); }
+
+// unit = chunks per input item, as in merge_body; the workgroup's items are [1 024 idx, ...) of the file's
+template <bool GRP>
+__device__ __forceinline__ void update_merge_body(const UpdRow *__restrict__ rows, uint64_t unit) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
+  __shared__ uint32_t dirty[B3W_TILE];
+  const UpdRow *__restrict__ r = rows + blockIdx.x;
+  const uint32_t gl = GRP ? r->gl : 0;
+  const uint64_t n = (r->len + 1023) / 1024;                          // (more than one tile)
+  const uint64_t span = unit * B3W_TILE, a0 = (uint64_t)r->idx * span;
+  const uint64_t tot = n - a0 < span ? n - a0 : span;
+  const uint32_t cnt = (uint32_t)((tot + unit - 1) / unit);
+  const bool sole = n <= span;
+  const uint32_t *__restrict__ in = as_global(r->in);
+  for (uint32_t i = threadIdx.x; i < cnt; i += 256) {
+    const uint32_t w = r->mask[i >> 5], bit = 1u << (i & 31);
+    dirty[i] = (w & bit) ? 1u : 0u;
+    if (w & bit) {                                                    // its CV: the slot behind those of the dirty items below it
+      uint32_t below = __popc(w & (bit - 1));
+      for (uint32_t k = 0; k < (i >> 5); ++k) below += __popc(r->mask[k]);
+      const uint4 *src = reinterpret_cast<const uint4 *>(in + (uint64_t)below * 8);
+      reinterpret_cast<uint4 *>(cv + i * 8)[0] = src[0];
+      reinterpret_cast<uint4 *>(cv + i * 8)[1] = src[1];
+    }
+  }
+  const uint64_t G1 = GRP ? (1ull << gl) - 1 : 0;                     // (every node here is over more than a tile: all of them are stored)
+  update_in_lds<256, GRP>(cv, dirty, cnt, unit, tot, as_global(r->ob) + 8 + (GRP ? preorder_pos((n + G1) >> gl, a0 >> gl, (tot + G1) >> gl) : preorder_pos(n, a0, tot)) * 64,
+                          sole, gl);
+  if (threadIdx.x < 8) as_global(sole ? r->root : r->out)[threadIdx.x] = cv[threadIdx.x];
+}
+
+__global__ __launch_bounds__(256) void b3w_bao_update_merge_kernel(const UpdRow *__restrict__ rows, uint64_t unit) { update_merge_body<false>(rows, unit); }
+__global__ __launch_bounds__(256) void b3w_bao_update_merge_group_kernel(const UpdRow *__restrict__ rows, uint64_t unit) { update_merge_body<true>(rows, unit); }
+
 // ---- open-length sessions: full tiles hashed before the file's length is known -----------------------------------------------------------
 // A FULL tile of 1 024 chunks is a complete subtree whatever the file's length turns out to be: its (1 024 >> gl) - 1 stored nodes are
 // contiguous in the file's pre-order outboard, in the order merge_in_lds gives them relative to the tile's root, and only the START of that
@@ -3106,6 +3247,240 @@ int32_t b3w_bao_stream_open_finish_many(b3w_ctx *ctx, b3w_bao_stream *const *ses
     s->finished = true;
     if (out_lens) out_lens[i] = lens[i];
   }
+  return B3W_OK;
+}
+
+}  // extern "C"
+
+// ---- updates in place: the host side (b3wit.h "updates in place after writes to resident files") ----------------------------------------
+namespace {
+
+struct UpdRange { uint32_t file; uint64_t first, end; };              // chunks [first, end) of the file
+// a workgroup of the plan: the file, the tile / span within it, its own scratch slot and the slot of its first dirty input item
+struct UpdWg { uint32_t file, idx; uint64_t out, in; uint32_t mask[B3W_TILE / 32]; };
+struct UpdPlan {
+  std::vector<uint32_t> small;                                        // the dirty files of at most 64 chunks, ascending, each once
+  std::vector<UpdWg> tiles, spans, tops;                              // the three storeys, sorted by (file, idx)
+  uint64_t tile_slots = 0, span_slots = 0;                            // scratch: the dirty tiles of files of more than one tile, then the dirty spans past 1 GiB
+};
+
+void mask_set(uint32_t *mask, uint32_t lo, uint32_t hi) {
+  for (uint32_t w = lo >> 5; w <= (hi - 1) >> 5; ++w) {
+    const uint32_t a = w == lo >> 5 ? lo & 31 : 0, b = w == (hi - 1) >> 5 ? ((hi - 1) & 31) + 1 : 32;
+    mask[w] |= (b == 32 ? ~0u : (1u << b) - 1) & ~((1u << a) - 1);
+  }
+}
+
+// the ranges that are not empty, sorted by (file, first chunk), overlapping and adjoining ones of a file merged; ends clamped to the file
+std::vector<UpdRange> update_ranges(const uint64_t *lens, const uint32_t *files, const uint64_t *first, const uint64_t *count, uint32_t n_ranges) {
+  std::vector<UpdRange> v;
+  v.reserve(n_ranges);
+  for (uint32_t i = 0; i < n_ranges; ++i) {
+    const uint64_t n = num_chunks(lens[files[i]]);
+    if (!count[i] || first[i] >= n) continue;
+    v.push_back(UpdRange{files[i], first[i], count[i] < n - first[i] ? first[i] + count[i] : n});
+  }
+  std::sort(v.begin(), v.end(), [](const UpdRange &a, const UpdRange &b) { return a.file != b.file ? a.file < b.file : a.first < b.first; });
+  size_t k = 0;
+  for (size_t i = 0; i < v.size(); ++i) {
+    if (k && v[k - 1].file == v[i].file && v[i].first <= v[k - 1].end) { if (v[i].end > v[k - 1].end) v[k - 1].end = v[i].end; }
+    else v[k++] = v[i];
+  }
+  v.resize(k);
+  return v;
+}
+
+// what a call over these (sorted, merged) ranges launches; the chunk masks are expanded to whole groups of 1 << gl chunks
+UpdPlan update_plan(const uint64_t *lens, const std::vector<UpdRange> &ranges, uint32_t gl) {
+  UpdPlan p;
+  const uint64_t G1 = (1ull << gl) - 1;
+  for (const UpdRange &r : ranges) {
+    const uint64_t n = num_chunks(lens[r.file]);
+    if (n <= 64) {
+      if (p.small.empty() || p.small.back() != r.file) p.small.push_back(r.file);
+      continue;
+    }
+    const uint64_t tiles = (n + B3W_TILE - 1) / B3W_TILE;
+    uint64_t lo = r.first & ~G1, hi = (r.end + G1) & ~G1;
+    if (hi > n) hi = n;
+    for (uint64_t t = lo / B3W_TILE; t * B3W_TILE < hi; ++t) {
+      if (p.tiles.empty() || p.tiles.back().file != r.file || p.tiles.back().idx != t) {
+        UpdWg w{};
+        w.file = r.file; w.idx = (uint32_t)t;
+        w.out = tiles > 1 ? p.tile_slots++ : 0;
+        p.tiles.push_back(w);
+        if (tiles > 1) {                                              // the storey above: the tile is a dirty item of its span
+          const uint32_t s = (uint32_t)(t / B3W_TILE);
+          if (p.spans.empty() || p.spans.back().file != r.file || p.spans.back().idx != s) {
+            UpdWg u{};
+            u.file = r.file; u.idx = s; u.in = w.out;
+            u.out = tiles > B3W_TILE ? p.span_slots++ : 0;
+            p.spans.push_back(u);
+            if (tiles > B3W_TILE) {
+              if (p.tops.empty() || p.tops.back().file != r.file) {
+                UpdWg v{};
+                v.file = r.file; v.in = u.out;
+                p.tops.push_back(v);
+              }
+              mask_set(p.tops.back().mask, s, s + 1);
+            }
+          }
+          mask_set(p.spans.back().mask, (uint32_t)(t % B3W_TILE), (uint32_t)(t % B3W_TILE) + 1);
+        }
+      }
+      const uint64_t t0 = t * B3W_TILE, a = lo > t0 ? lo : t0, b = hi < t0 + B3W_TILE ? hi : t0 + B3W_TILE;
+      mask_set(p.tiles.back().mask, (uint32_t)(a - t0), (uint32_t)(b - t0));
+    }
+  }
+  return p;
+}
+
+int32_t update_refuse(b3w_ctx *ctx, const std::string &why) {
+  ctx->last_error = "bao update: " + why;
+  return B3W_E_BAD_ARGUMENT;
+}
+std::string update_range_text(uint32_t i, uint32_t file, uint64_t first, uint64_t count) {
+  return "range " + std::to_string(i) + " (file " + std::to_string(file) + ", chunks " + std::to_string(first) + " + " + std::to_string(count) + ")";
+}
+
+// the sparse walk on the host over the units [first, first + cnt) whose stored node (cnt > 1) is node `pos`: false where no range touches
+// them (nothing read, nothing written), else h = their CV, the dirty halves of the node stored
+bool host_update_walk(const uint8_t *data, uint64_t len, uint64_t n, uint32_t gl, uint8_t *nodes, const std::vector<UpdRange> &units, uint64_t first,
+                      uint64_t cnt, uint64_t pos, bool root, uint32_t h[8]) {
+  // the first range that ends behind `first`: dirty where it starts before first + cnt
+  auto it = std::upper_bound(units.begin(), units.end(), first, [](uint64_t x, const UpdRange &r) { return x < r.end; });
+  if (it == units.end() || it->first >= first + cnt) return false;
+  if (cnt == 1) {
+    const uint64_t c0 = first << gl, gn = n - c0 < (1ull << gl) ? n - c0 : (1ull << gl);
+    host_subtree_cv(data, len, c0, gn, root, h);
+    return true;
+  }
+  uint64_t k2 = 1;
+  while (k2 * 2 < cnt) k2 *= 2;
+  uint32_t m[16], ivv[8];
+  uint8_t *node = nodes + 64 * pos;
+  if (host_update_walk(data, len, n, gl, nodes, units, first, k2, pos + 1, false, m)) memcpy(node, m, 32); else memcpy(m, node, 32);
+  if (host_update_walk(data, len, n, gl, nodes, units, first + k2, cnt - k2, pos + k2, false, m + 8)) memcpy(node + 32, m + 8, 32); else memcpy(m + 8, node + 32, 32);
+  iv(ivv);
+  blake3_cv(ivv, m, 0, 0, 64, 4u | (root ? 8u : 0u), h);
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t b3w_bao_update_scratch_bytes(const uint64_t *host_lens, const uint32_t *host_files, const uint64_t *host_first_chunk,
+                                      const uint64_t *host_n_chunks, uint32_t n_ranges) {
+  if (!n_ranges || !host_lens || !host_files || !host_first_chunk || !host_n_chunks) return 0;
+  const UpdPlan p = update_plan(host_lens, update_ranges(host_lens, host_files, host_first_chunk, host_n_chunks, n_ranges), 0);
+  return (p.tile_slots + p.span_slots) * 32;
+}
+
+int32_t b3w_bao_outboard_update(const uint8_t *data, uint64_t len, uint8_t *outboard, uint32_t group_log, const uint64_t *host_first_chunk,
+                                const uint64_t *host_n_chunks, uint32_t n_ranges, uint32_t *root) {
+  if ((!data && len) || !outboard || !root || group_log > B3W_BAO_MAX_GROUP_LOG || (n_ranges && (!host_first_chunk || !host_n_chunks))) return B3W_E_BAD_ARGUMENT;
+  const uint64_t n = num_chunks(len), n_units = (n + ((1ull << group_log) - 1)) >> group_log;
+  for (uint32_t i = 0; i < n_ranges; ++i)
+    if (host_first_chunk[i] > n || host_n_chunks[i] > n - host_first_chunk[i]) return B3W_E_BAD_ARGUMENT;
+  std::vector<uint32_t> zero(n_ranges, 0);
+  std::vector<UpdRange> units = update_ranges(&len, zero.data(), host_first_chunk, host_n_chunks, n_ranges);
+  for (UpdRange &r : units) { r.first >>= group_log; r.end = (r.end + ((1ull << group_log) - 1)) >> group_log; }   // (still sorted; adjoining ones may now overlap: the walk does not mind)
+  for (size_t i = 1; i < units.size(); ++i)
+    if (units[i].end < units[i - 1].end) units[i].end = units[i - 1].end;          // (ends ascending, for the bisection)
+  uint32_t h[8];
+  if (host_update_walk(data, len, n, group_log, outboard + 8, units, 0, n_units, 0, true, h)) memcpy(root, h, 32);
+  return B3W_OK;
+}
+
+int32_t b3w_bao_outboard_update_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets,
+                                             const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint64_t *host_ob_first,
+                                             uint8_t *d_outboards, uint32_t *d_roots, const uint32_t *host_files, const uint64_t *host_first_chunk,
+                                             const uint64_t *host_n_chunks, uint32_t n_ranges, void *d_scratch, uint64_t scratch_bytes, void *stream) {
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  if (group_log > B3W_BAO_MAX_GROUP_LOG) return update_refuse(ctx, "group_log is above B3W_BAO_MAX_GROUP_LOG (6)");
+  if (!n_ranges) return B3W_OK;
+  if (!host_offsets || !host_lens || !host_ob_first || !d_outboards || !d_roots || !host_files || !host_first_chunk || !host_n_chunks)
+    return update_refuse(ctx, "a null pointer (offsets, lengths, outboard offsets, outboards, roots or a range array)");
+  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_roots & 3)) return update_refuse(ctx, "d_outboards is not 8-byte aligned, or d_roots not 4-byte aligned");
+  for (uint32_t i = 0; i < n_ranges; ++i) {                           // every range is checked before anything is launched or written
+    const uint32_t f = host_files[i];
+    const uint64_t a = host_first_chunk[i], c = host_n_chunks[i];
+    if (f >= n_files) return update_refuse(ctx, update_range_text(i, f, a, c) + ": the file index is not below the file count " + std::to_string(n_files));
+    const uint64_t len = host_lens[f], n = num_chunks(len);
+    if (n > (1ull << 30)) return update_refuse(ctx, update_range_text(i, f, a, c) + ": a file of more than 2^30 chunks");
+    if (a > n || c > n - a) return update_refuse(ctx, update_range_text(i, f, a, c) + " reaches past the file's " + std::to_string(n) + " chunks");
+    if (host_offsets[f] > arena_bytes || len > arena_bytes - host_offsets[f])
+      return update_refuse(ctx, update_range_text(i, f, a, c) + ": the file reaches past arena_bytes");
+    if (len && !d_arena) return update_refuse(ctx, update_range_text(i, f, a, c) + ": a null arena with a dirty file that is not empty");
+    if (host_ob_first[f] & 7) return update_refuse(ctx, update_range_text(i, f, a, c) + ": the file's outboard offset is not a multiple of 8");
+  }
+  const UpdPlan p = update_plan(host_lens, update_ranges(host_lens, host_files, host_first_chunk, host_n_chunks, n_ranges), group_log);
+  const uint64_t need = (p.tile_slots + p.span_slots) * 32;
+  if (scratch_bytes < need) return update_refuse(ctx, "the scratch is smaller than b3w_bao_update_scratch_bytes says (" + std::to_string(need) + " bytes)");
+  if (need && (!d_scratch || ((uintptr_t)d_scratch & 15))) return update_refuse(ctx, "the scratch is null or not 16-byte aligned");
+  if (p.tiles.size() > 0x7fffffffull) return update_refuse(ctx, "more than 2^31 - 1 dirty tiles in one call");
+  // the small files' waves, as the batch call packs them
+  uint64_t waves = 0, fill = 64;
+  for (uint32_t f : p.small) {
+    const uint64_t n = num_chunks(host_lens[f]);
+    if (fill + n > 64) { waves++; fill = 0; }
+    fill += n;
+  }
+  if (p.small.empty() && p.tiles.empty()) return B3W_OK;              // (every range was empty)
+  // one table: tile rows | span rows | top rows | the small files' entries | their waves' first files
+  const uint64_t n_rows = p.tiles.size() + p.spans.size() + p.tops.size();
+  const uint64_t bytes = n_rows * sizeof(UpdRow) + p.small.size() * sizeof(BatchEnt) + (p.small.empty() ? 0 : (waves + 1) * 4);
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  b3w_ctx::ManySlot *slot = nullptr;
+  const int32_t rc = many_staging(ctx, bytes, &slot);
+  if (rc) return rc;
+  uint32_t *scratch = reinterpret_cast<uint32_t *>(d_scratch), *span_cv = scratch + p.tile_slots * 8;
+  UpdRow *h_rows = reinterpret_cast<UpdRow *>(slot->h);
+  BatchEnt *h_small = reinterpret_cast<BatchEnt *>(h_rows + n_rows);
+  uint32_t *h_waves = reinterpret_cast<uint32_t *>(h_small + p.small.size());
+  auto row = [&](const UpdWg &w, uint32_t *in, uint32_t *out) {
+    UpdRow r{};
+    const uint32_t f = w.file;
+    r.len = host_lens[f]; r.data = d_arena + host_offsets[f]; r.ob = d_outboards + host_ob_first[f]; r.root = d_roots + (uint64_t)f * 8;
+    r.in = in; r.out = out; r.idx = w.idx; r.gl = group_log;
+    memcpy(r.mask, w.mask, sizeof r.mask);
+    return r;
+  };
+  UpdRow *at = h_rows;
+  for (const UpdWg &w : p.tiles) *at++ = row(w, nullptr, scratch + w.out * 8);
+  for (const UpdWg &w : p.spans) *at++ = row(w, scratch + w.in * 8, span_cv + w.out * 8);
+  for (const UpdWg &w : p.tops) *at++ = row(w, span_cv + w.in * 8, nullptr);
+  uint32_t i_small = 0, i_waves = 0;
+  fill = 64;
+  for (uint32_t f : p.small) {
+    const uint64_t n = num_chunks(host_lens[f]);
+    if (fill + n > 64) { h_waves[i_waves++] = i_small; fill = 0; }
+    h_small[i_small++] = BatchEnt{host_offsets[f], host_lens[f], host_ob_first[f], (uint32_t)fill, f};
+    fill += n;
+  }
+  if (i_small) h_waves[i_waves] = i_small;
+  const hipError_t ec = hipMemcpyAsync(slot->d, slot->h, (size_t)bytes, hipMemcpyHostToDevice, st);
+  if (ec != hipSuccess) return hip_fail(ctx, ec, "bao update: table upload");
+  const UpdRow *d_tiles = reinterpret_cast<const UpdRow *>(slot->d), *d_spans = d_tiles + p.tiles.size(), *d_tops = d_spans + p.spans.size();
+  const BatchEnt *d_small = reinterpret_cast<const BatchEnt *>(d_tops + p.tops.size());
+  const uint32_t *d_waves = reinterpret_cast<const uint32_t *>(d_small + p.small.size());
+  const uint64_t U = B3W_TILE;
+  if (group_log) {
+    if (i_small) hipLaunchKernelGGL(b3w_bao_small_group_kernel, dim3((uint32_t)waves), dim3(64), 0, st, d_arena, d_small, d_waves, d_outboards, d_roots, group_log);
+    if (!p.tiles.empty()) hipLaunchKernelGGL(b3w_bao_update_tile_group_kernel, dim3((uint32_t)p.tiles.size()), dim3(B3W_TILE), 0, st, d_tiles);
+    if (!p.spans.empty()) hipLaunchKernelGGL(b3w_bao_update_merge_group_kernel, dim3((uint32_t)p.spans.size()), dim3(256), 0, st, d_spans, U);
+    if (!p.tops.empty()) hipLaunchKernelGGL(b3w_bao_update_merge_group_kernel, dim3((uint32_t)p.tops.size()), dim3(256), 0, st, d_tops, U * U);
+  } else {
+    if (i_small) hipLaunchKernelGGL(b3w_bao_small_kernel, dim3((uint32_t)waves), dim3(64), 0, st, d_arena, d_small, d_waves, d_outboards, d_roots);
+    if (!p.tiles.empty()) hipLaunchKernelGGL(b3w_bao_update_tile_kernel, dim3((uint32_t)p.tiles.size()), dim3(B3W_TILE), 0, st, d_tiles);
+    if (!p.spans.empty()) hipLaunchKernelGGL(b3w_bao_update_merge_kernel, dim3((uint32_t)p.spans.size()), dim3(256), 0, st, d_spans, U);
+    if (!p.tops.empty()) hipLaunchKernelGGL(b3w_bao_update_merge_kernel, dim3((uint32_t)p.tops.size()), dim3(256), 0, st, d_tops, U * U);
+  }
+  const hipError_t e = hipGetLastError();
+  many_release(slot, st);
+  if (e != hipSuccess) return hip_fail(ctx, e, "bao update launch");
   return B3W_OK;
 }
 

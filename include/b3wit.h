@@ -922,6 +922,64 @@ int32_t b3w_bao_slice_arena_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_
                                    const uint32_t *host_files, const uint64_t *host_chunks, uint32_t n_samples, uint8_t *d_slices,
                                    void *stream);
 
+/* ---- updates in place after writes to resident files (still ABI 1.4: new names only) --------------------------------
+ * Every call above treats a file as immutable: after one rewritten block the only way to a correct outboard and root is the batch
+ * call over the whole file again.  These calls make the cost follow the bytes written.  GIVEN an arena with its offsets and
+ * lengths, the packed outboards and roots of those files as they were BEFORE some bytes changed, and a list of dirty ranges
+ * (host_files[i], host_first_chunk[i], host_n_chunks[i]) that covers every changed byte, d_outboards and d_roots are afterwards byte
+ * for byte what b3w_bao_outboard_batch_device (group_log = 0) / b3w_bao_group_outboard_batch_device (1 .. B3W_BAO_MAX_GROUP_LOG) write
+ * for the arena as it is now.  LENGTHS DO NOT CHANGE: an append or a truncation moves every node of a pre-order outboard and is the
+ * batch call's business.
+ * A stored node is left CV || right CV, so the CV of every clean sibling on a dirty chunk's path is in the outboard already: only
+ * dirty chunks are hashed from bytes.  A UNIT is a chunk (group_log = 0) or a group of 2^group_log chunks; a unit with a dirty chunk
+ * is hashed whole.
+ *   NOTHING EXTRA IS WRITTEN.  The only nodes written are those with a dirty unit below them, and of those only the halves over a
+ *     dirty unit.  Of a file of more than 64 chunks no header is written and no byte outside its dirty units is read.  A dirty file of
+ *     at most 64 chunks is rehashed whole (at most 64 KiB; header, nodes and root rewritten with the same values where nothing
+ *     changed).  No byte of a file without a dirty range is read or written.
+ *   AN INCOMPLETE LIST IS NOT DETECTED.  If the list misses a changed chunk the call cannot know: the result is an outboard that
+ *     b3w_bao_verify_batch_device reports with status 1 at exactly that unit (where the unit's file has more than 64 chunks and no
+ *     listed chunk shares the unit).
+ *   Ranges may be unsorted, overlapping or duplicated: the host sorts and merges them.  A range of 0 chunks is dropped.
+ *   n_ranges == 0: B3W_OK, nothing launched.
+ * WHEN TO CALL THE BATCH CALL INSTEAD (measured on an MI355X): the cost follows the DIRTY TILES of 1 024 chunks and the
+ * number of ranges, not the dirty chunks; a tile with one dirty chunk costs about what the batch call spends on a whole tile.  One
+ * 4 KiB write into a 1 GiB file: 0.09 ms against the batch call's 0.42; 1 024 scattered writes (0.4 % of the chunks): 0.22 ms; 4 096
+ * (1.6 %, a write in every tile): 0.42 ms, the batch call's time; more: slower than the batch call, up to 1.4 times with every chunk
+ * dirty in few ranges and several times with hundreds of thousands of ranges (about 17 ns of host work a range).  So: this call while
+ * fewer than about one tile in two holds a write, or while the dirty files are a small part of a batch of small files (4 096 of
+ * 262 144 files of 4 KiB: 0.11 ms against 1.10); the batch call otherwise. */
+/* Host only.  Bytes of caller's scratch b3w_bao_outboard_update_batch_device needs for these ranges: 32 per dirty tile of 1 024
+ * chunks of the files of more than one tile, plus 32 per dirty span of 1 024 tiles of the files past 1 GiB; files of one tile need
+ * none.  host_lens is indexed by host_files[i] (which is not checked here).  0 for a null pointer or no range. */
+uint64_t b3w_bao_update_scratch_bytes(const uint64_t *host_lens, const uint32_t *host_files, const uint64_t *host_first_chunk,
+                                      const uint64_t *host_n_chunks, uint32_t n_ranges);
+/* host_ob_first: the files' outboard byte offsets as b3w_bao_batch_layout / b3w_bao_group_batch_layout return them — taken, not
+ * recomputed, so that the call's host work and its table grow with the ranges and the dirty tiles and never with n_files.
+ * d_roots: 8 u32 per file ON THE DEVICE.  d_scratch: 16-byte aligned, b3w_bao_update_scratch_bytes.
+ * AT MOST FOUR LAUNCHES whatever the number of ranges, files or dirty tiles: the dirty files of at most 64 chunks through the batch
+ * call's kernel for them; a workgroup per dirty tile of the larger files; one per span of 1 024 tiles that holds a dirty tile; one
+ * more launch over the spans for files past 1 GiB.  One table (184 bytes per workgroup of the last three, 32 per small file) goes
+ * through the staging ring of the many-calls above; nothing else is allocated, the host waits for nothing.
+ * REFUSALS ARE ATOMIC: every range is checked first, and a refused call launches nothing and writes nothing (B3W_E_BAD_ARGUMENT,
+ * b3w_last_error names the range): a null pointer (d_arena may be NULL where every dirty file is empty), group_log above the
+ * maximum, a file index >= n_files, a range that reaches past its file's chunk count (an empty file has one chunk), a dirty file
+ * that reaches past arena_bytes or has more than 2^30 chunks, d_outboards off 8 bytes, a small, null or misaligned scratch.
+ * Any context.  Asynchronous on `stream`. */
+int32_t b3w_bao_outboard_update_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets,
+                                             const uint64_t *host_lens, uint32_t n_files, uint32_t group_log,
+                                             const uint64_t *host_ob_first, uint8_t *d_outboards, uint32_t *d_roots,
+                                             const uint32_t *host_files, const uint64_t *host_first_chunk,
+                                             const uint64_t *host_n_chunks, uint32_t n_ranges, void *d_scratch, uint64_t scratch_bytes,
+                                             void *stream);
+/* Host only, one file in host memory, for callers without a GPU: the same sparse walk.  `outboard` (full, or the group outboard of
+ * group_log) and `root` (8 u32) are updated in place for the dirty ranges of `data` (len bytes): only the nodes with a dirty unit
+ * below them are written, no byte outside the dirty units is read.  B3W_E_BAD_ARGUMENT, nothing written, for a null pointer, a
+ * group_log above the maximum or a range that reaches past the chunk count. */
+int32_t b3w_bao_outboard_update(const uint8_t *data, uint64_t len, uint8_t *outboard, uint32_t group_log,
+                                const uint64_t *host_first_chunk, const uint64_t *host_n_chunks, uint32_t n_ranges,
+                                uint32_t *root /* 8 u32 */);
+
 #ifdef __cplusplus
 }
 #endif
