@@ -1767,6 +1767,90 @@ __global__ __launch_bounds__(256) void b3w_bao_stream_open_relocate_many_kernel(
   }
 }
 
+// ---- resident files after appends and truncations: the kept blocks from the outboard of the old length to that of the new ----------------
+// A change of length moves the nodes of a pre-order outboard and changes none below a tile that is full before and after: the block of
+// such a tile is the same run of bytes at another place (see "open-length sessions"), and the tile's CV is the parent compression of the
+// block's first node.  So the kernel is b3w_bao_stream_open_relocate_many_kernel with an outboard of the OLD length as the source, and it
+// leaves the kept tiles' CVs where the merge storeys look for them (b3wit.h "resident files after appends and truncations").
+//   b3w_bao_resize_relocate_kernel   a row per file with at least one kept tile; workgroups of open_shape(gl) as above.  A workgroup moves
+//                                    a piece of a block (or 2 .. 16 whole blocks) from old_ob + 8 + 64 preorder_pos(old units, ...) to
+//                                    new_ob + 8 + 64 preorder_pos(new units, ...); the lane that moves a block's first node computes the
+//                                    tile's CV into slot `tile` of the row's CVs, or (a file that is now exactly one full tile) the
+//                                    ROOT-flagged one into the root; one lane per row writes the header.
+// The tiles behind the kept ones go through b3w_bao_stream_tile_many[_group]_kernel and the storeys above through
+// b3w_bao_stream_merge_many[_group]_kernel as they are.  The 16-byte moves need BOTH places at 8 modulo 16 (both outboards 16-byte
+// aligned); any other pair of phases takes the 8-byte moves.  The old outboard is only read.
+struct ResRow {
+  uint64_t old_len, new_len;
+  const uint8_t *old_ob;                                 // the file's outboard for old_len, header first
+  uint8_t *new_ob;                                       // where its outboard for new_len goes
+  uint32_t *cv;                                          // the file's tile CVs (unused where new_len is exactly one tile)
+  uint32_t *root;
+  uint32_t first, tiles, gl, pad;                        // first: the row's first workgroup; tiles: the kept ones
+};
+
+__global__ __launch_bounds__(256) void b3w_bao_resize_relocate_kernel(const ResRow *__restrict__ rows, uint32_t n_rows) {
+  uint32_t lo = 0, hi = n_rows;
+  while (hi - lo > 1) {                                   // the row whose workgroups include this one: the last with first <= blockIdx.x
+    const uint32_t mid = (lo + hi) / 2;
+    if (rows[mid].first <= blockIdx.x) lo = mid; else hi = mid;
+  }
+  const ResRow row = rows[lo];
+  const uint8_t *__restrict__ old_ob = as_global(row.old_ob);
+  uint8_t *__restrict__ new_ob = as_global(row.new_ob);
+  const uint64_t len = row.new_len;
+  const uint32_t tiles = row.tiles, gl = row.gl, wg = blockIdx.x - row.first;
+  const OpenShape s = open_shape(gl);
+  if (wg == 0 && threadIdx.x == 0) *reinterpret_cast<uint2 *>(new_ob) = make_uint2((uint32_t)len, (uint32_t)(len >> 32));
+  const uint32_t L = 256u >> s.tpw_log, lane = threadIdx.x & (L - 1);
+  const uint32_t wg_tile = (wg / s.ppb) << s.tpw_log, piece = wg % s.ppb;
+  const uint32_t tile = wg_tile + (threadIdx.x >> (8 - s.tpw_log));
+  if (tile >= tiles) return;
+  const uint64_t G1 = (1ull << gl) - 1;
+  const uint64_t ng_old = (((row.old_len + 1023) / 1024) + G1) >> gl, ng_new = (((len + 1023) / 1024) + G1) >> gl;
+  const uint32_t sh = 10 - gl;                            // a tile is 1 << sh groups
+  const uint64_t a = (uint64_t)(s.tpw_log == 0 ? wg_tile : tile) << sh;
+  const uint64_t pos_old = preorder_pos(ng_old, a, 1ull << sh), pos_new = preorder_pos(ng_new, a, 1ull << sh);
+  const uint32_t at = piece * OPEN_PIECE, nb = s.bb - at < OPEN_PIECE ? s.bb - at : OPEN_PIECE;     // (a multiple of 64)
+  const uint8_t *__restrict__ src = old_ob + 8 + pos_old * 64 + at;
+  uint8_t *__restrict__ dst = new_ob + 8 + pos_new * 64 + at;
+  if (((uintptr_t)dst & 15) == 8 && ((uintptr_t)src & 15) == 8) {     // both outboards 16-byte aligned: an 8-byte head, 16-byte pieces, an 8-byte tail
+    uint2 head = make_uint2(0, 0), tail = make_uint2(0, 0);
+    if (lane == 0) { head = *reinterpret_cast<const uint2 *>(src); tail = *reinterpret_cast<const uint2 *>(src + nb - 8); }
+    // (nb - 16) / 16 <= 4 L pieces whatever gl is, so a lane has at most four; every load of a lane is issued before its first store, a
+    // lane with fewer pieces loading the piece's first bytes again in place of a branch around the load (the relocation above)
+    uint4 v[4];
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) { const uint32_t o = 8 + (lane + k * L) * 16; v[k] = *reinterpret_cast<const uint4 *>(src + (o < nb - 8 ? o : 8)); }
+    asm volatile("" : "+v"(v[0].x), "+v"(v[0].y), "+v"(v[0].z), "+v"(v[0].w), "+v"(v[1].x), "+v"(v[1].y), "+v"(v[1].z), "+v"(v[1].w),
+                      "+v"(v[2].x), "+v"(v[2].y), "+v"(v[2].z), "+v"(v[2].w), "+v"(v[3].x), "+v"(v[3].y), "+v"(v[3].z), "+v"(v[3].w),
+                      "+v"(head.x), "+v"(head.y), "+v"(tail.x), "+v"(tail.y));
+    if (lane == 0) { *reinterpret_cast<uint2 *>(dst) = head; *reinterpret_cast<uint2 *>(dst + nb - 8) = tail; }
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) { const uint32_t o = 8 + (lane + k * L) * 16; if (o < nb - 8) *reinterpret_cast<uint4 *>(dst + o) = v[k]; }
+  } else {                                                // any other pair of phases: 8 bytes at a time, nb / 8 <= 8 L pieces
+    uint2 v[8];
+#pragma unroll
+    for (uint32_t k = 0; k < 8; ++k) { const uint32_t o = (lane + k * L) * 8; v[k] = *reinterpret_cast<const uint2 *>(src + (o < nb ? o : 0)); }
+    asm volatile("" : "+v"(v[0].x), "+v"(v[0].y), "+v"(v[1].x), "+v"(v[1].y), "+v"(v[2].x), "+v"(v[2].y), "+v"(v[3].x), "+v"(v[3].y),
+                      "+v"(v[4].x), "+v"(v[4].y), "+v"(v[5].x), "+v"(v[5].y), "+v"(v[6].x), "+v"(v[6].y), "+v"(v[7].x), "+v"(v[7].y));
+#pragma unroll
+    for (uint32_t k = 0; k < 8; ++k) { const uint32_t o = (lane + k * L) * 8; if (o < nb) *reinterpret_cast<uint2 *>(dst + o) = v[k]; }
+  }
+  // the kept tile's CV: left CV || right CV of its top merge is the block's first node, stored for every gl <= 6.  A file that is now
+  // EXACTLY this one tile has no storey above: the compression is ROOT-flagged and is the file's root.
+  if (piece == 0 && lane == 0) {
+    const bool sole = len == (uint64_t)B3W_TILE * 1024;
+    uint32_t m[16], ivv[8], o[8];
+    load_node(src, m);
+    iv(ivv);
+    blake3_cv(ivv, m, 0, 0, 64, 4u | (sole ? 8u : 0u), o);
+    uint32_t *__restrict__ out = sole ? as_global(row.root) : as_global(row.cv) + (uint64_t)tile * 8;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) out[k] = o[k];
+  }
+}
+
 // the CV of a chunk on the host (chunk_cv's loop over blake3_cv): b3w_bao_slice_decode
 void host_chunk_cv(const uint8_t *src, uint32_t bytes, uint64_t c, uint32_t root, uint32_t h[8]) {
   const uint32_t nb = bytes ? (bytes + 63) / 64 : 1;
@@ -3481,6 +3565,220 @@ int32_t b3w_bao_outboard_update_batch_device(b3w_ctx *ctx, const uint8_t *d_aren
   const hipError_t e = hipGetLastError();
   many_release(slot, st);
   if (e != hipSuccess) return hip_fail(ctx, e, "bao update launch");
+  return B3W_OK;
+}
+
+}  // extern "C"
+
+// ---- resident files after appends and truncations: the host side (b3wit.h "resident files after appends and truncations") ----------------
+namespace {
+
+constexpr uint64_t RES_TB = (uint64_t)B3W_TILE * 1024;                // a tile's bytes
+
+uint64_t resize_tiles(uint64_t len) { return (num_chunks(len) + B3W_TILE - 1) / B3W_TILE; }
+// scratch slots of a listed file at its new length: its tiles' CVs, then its spans' past 1 GiB; none for a file of one tile
+uint64_t resize_slots(uint64_t new_len) {
+  const uint64_t tiles = resize_tiles(new_len);
+  return tiles > 1 ? tiles + (tiles > B3W_TILE ? (tiles + B3W_TILE - 1) / B3W_TILE : 0) : 0;
+}
+
+int32_t resize_refuse(b3w_ctx *ctx, const std::string &why) {
+  ctx->last_error = "bao resize: " + why;
+  return B3W_E_BAD_ARGUMENT;
+}
+std::string resize_entry_text(uint32_t i, uint32_t file) { return "entry " + std::to_string(i) + " (file " + std::to_string(file) + ")"; }
+
+// the walk on the host over the units [first, first + cnt) of the file at its new length, whose stored node (cnt > 1) is node `pos`: a
+// kept tile's block is copied from the old outboard and its CV taken from the block's first node; everything else is hashed
+void host_resize_walk(const uint8_t *data, uint64_t len, uint64_t n, uint32_t gl, const uint8_t *old_nodes, uint64_t old_units, uint64_t kept,
+                      uint8_t *nodes, uint64_t first, uint64_t cnt, uint64_t pos, bool root, uint32_t h[8]) {
+  const uint32_t sh = 10 - gl;
+  uint32_t m[16], ivv[8];
+  if (cnt == (1ull << sh) && !(first & (cnt - 1)) && (first >> sh) < kept) {
+    const uint8_t *src = old_nodes + 64 * host_preorder_pos(old_units, first, cnt);
+    memcpy(nodes + 64 * pos, src, (size_t)(cnt - 1) * 64);
+    memcpy(m, src, 64);
+    iv(ivv);
+    blake3_cv(ivv, m, 0, 0, 64, 4u | (root ? 8u : 0u), h);
+    return;
+  }
+  if (cnt == 1) {
+    const uint64_t c0 = first << gl, gn = n - c0 < (1ull << gl) ? n - c0 : (1ull << gl);
+    host_subtree_cv(data, len, c0, gn, root, h);
+    return;
+  }
+  uint64_t k2 = 1;
+  while (k2 * 2 < cnt) k2 *= 2;
+  host_resize_walk(data, len, n, gl, old_nodes, old_units, kept, nodes, first, k2, pos + 1, false, m);
+  host_resize_walk(data, len, n, gl, old_nodes, old_units, kept, nodes, first + k2, cnt - k2, pos + k2, false, m + 8);
+  memcpy(nodes + 64 * pos, m, 64);
+  iv(ivv);
+  blake3_cv(ivv, m, 0, 0, 64, 4u | (root ? 8u : 0u), h);
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t b3w_bao_resize_kept_tiles(uint64_t old_len, uint64_t new_len) { return (old_len < new_len ? old_len : new_len) / RES_TB; }
+
+uint64_t b3w_bao_resize_scratch_bytes(const uint64_t *host_new_lens, const uint32_t *host_files, uint32_t n_resized) {
+  if (!n_resized || !host_new_lens || !host_files) return 0;
+  uint64_t slots = 0;
+  for (uint32_t i = 0; i < n_resized; ++i) slots += resize_slots(host_new_lens[host_files[i]]);
+  return slots * 32;
+}
+
+int32_t b3w_bao_outboard_resize(const uint8_t *data, uint64_t new_len, const uint8_t *old_outboard, uint64_t old_len, uint32_t group_log,
+                                uint8_t *new_outboard, uint32_t *root) {
+  if (!old_outboard || !new_outboard || !root || group_log > B3W_BAO_MAX_GROUP_LOG) return B3W_E_BAD_ARGUMENT;
+  const uint64_t kept = b3w_bao_resize_kept_tiles(old_len, new_len);
+  if (!data && new_len > kept * RES_TB) return B3W_E_BAD_ARGUMENT;
+  if (num_chunks(old_len) > (1ull << 30) || num_chunks(new_len) > (1ull << 30)) return B3W_E_BAD_ARGUMENT;
+  const uintptr_t a0 = (uintptr_t)old_outboard, a1 = a0 + b3w_bao_group_outboard_size(old_len, group_log);
+  const uintptr_t b0 = (uintptr_t)new_outboard, b1 = b0 + b3w_bao_group_outboard_size(new_len, group_log);
+  if (a0 < b1 && b0 < a1) return B3W_E_BAD_ARGUMENT;
+  const uint64_t G1 = (1ull << group_log) - 1, n = num_chunks(new_len);
+  uint32_t h[8];
+  host_resize_walk(data, new_len, n, group_log, old_outboard + 8, (num_chunks(old_len) + G1) >> group_log, kept, new_outboard + 8, 0, (n + G1) >> group_log,
+                   0, true, h);
+  for (int k = 0; k < 8; ++k) new_outboard[k] = (uint8_t)(new_len >> (8 * k));
+  memcpy(root, h, 32);
+  return B3W_OK;
+}
+
+// At most five launches: one table through the staging ring in runs of rows, each run the rows of one grid (the tiles behind the kept
+// ones, the relocations, the first merge storey, the second), then the small files' entries and their waves.  The runs write disjoint
+// bytes of every file, as those of b3w_bao_stream_open_finish_many do; the storeys read the CVs the two launches before them leave.
+int32_t b3w_bao_outboard_resize_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets,
+                                             const uint64_t *host_old_lens, const uint64_t *host_new_lens, uint32_t n_files, uint32_t group_log,
+                                             const uint64_t *host_old_ob_first, const uint8_t *d_old_outboards, const uint64_t *host_new_ob_first,
+                                             uint8_t *d_new_outboards, uint32_t *d_roots, const uint32_t *host_files, uint32_t n_resized, void *d_scratch,
+                                             uint64_t scratch_bytes, void *stream) {
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  if (group_log > B3W_BAO_MAX_GROUP_LOG) return resize_refuse(ctx, "group_log is above B3W_BAO_MAX_GROUP_LOG (6)");
+  if (!n_resized) return B3W_OK;
+  if (!host_offsets || !host_old_lens || !host_new_lens || !host_old_ob_first || !d_old_outboards || !host_new_ob_first || !d_new_outboards || !d_roots || !host_files)
+    return resize_refuse(ctx, "a null pointer (offsets, lengths, outboard offsets, outboards, roots or the file list)");
+  if (((uintptr_t)d_old_outboards & 7) || ((uintptr_t)d_new_outboards & 7) || ((uintptr_t)d_roots & 3))
+    return resize_refuse(ctx, "d_old_outboards or d_new_outboards is not 8-byte aligned, or d_roots not 4-byte aligned");
+  const uint64_t LIMIT = 0x7fffffffull;
+  const OpenShape sh = open_shape(group_log);
+  uint64_t n_small = 0, waves = 0, fill = 64, n_tile = 0, wg_tile = 0, n_move = 0, wg_move = 0, n_one = 0, wg_one = 0, n_two = 0, need = 0;
+  for (uint32_t i = 0; i < n_resized; ++i) {                          // every entry is checked before anything is launched or written
+    const uint32_t f = host_files[i];
+    if (f >= n_files) return resize_refuse(ctx, resize_entry_text(i, f) + ": the file index is not below the file count " + std::to_string(n_files));
+    const uint64_t old_len = host_old_lens[f], len = host_new_lens[f], n = num_chunks(len);
+    if (n > (1ull << 30) || num_chunks(old_len) > (1ull << 30)) return resize_refuse(ctx, resize_entry_text(i, f) + ": a file of more than 2^30 chunks at its old or new length");
+    if (host_offsets[f] > arena_bytes || len > arena_bytes - host_offsets[f]) return resize_refuse(ctx, resize_entry_text(i, f) + ": the file reaches past arena_bytes at its new length");
+    const uint64_t kept = b3w_bao_resize_kept_tiles(old_len, len), tiles = resize_tiles(len);
+    if (len > kept * RES_TB && !d_arena) return resize_refuse(ctx, resize_entry_text(i, f) + ": a null arena with a file whose bytes have to be read");
+    if ((host_old_ob_first[f] & 7) || (host_new_ob_first[f] & 7)) return resize_refuse(ctx, resize_entry_text(i, f) + ": an outboard offset of the file is not a multiple of 8");
+    const uintptr_t a0 = (uintptr_t)d_old_outboards + host_old_ob_first[f], a1 = a0 + b3w_bao_group_outboard_size(old_len, group_log);
+    const uintptr_t b0 = (uintptr_t)d_new_outboards + host_new_ob_first[f], b1 = b0 + b3w_bao_group_outboard_size(len, group_log);
+    if (a0 < b1 && b0 < a1) return resize_refuse(ctx, resize_entry_text(i, f) + ": the file's old and new outboards overlap");
+    need += resize_slots(len) * 32;
+    if (n <= 64) {
+      if (fill + n > 64) { waves++; fill = 0; }
+      fill += n;
+      n_small++;
+    } else {
+      if (tiles > kept) { n_tile++; wg_tile += tiles - kept; }
+      if (kept) { n_move++; wg_move += ((kept + (1ull << sh.tpw_log) - 1) >> sh.tpw_log) * sh.ppb; }
+      if (tiles > 1) { n_one++; wg_one += (tiles + B3W_TILE - 1) / B3W_TILE; }
+      if (tiles > B3W_TILE) n_two++;
+    }
+    if (waves > LIMIT || wg_tile > LIMIT || wg_move > LIMIT || wg_one > LIMIT || n_two > LIMIT)
+      return resize_refuse(ctx, resize_entry_text(i, f) + ": with this entry one of the call's five grids has more than 2^31 - 1 workgroups");
+  }
+  {
+    std::vector<std::pair<uint32_t, uint32_t>> by_file(n_resized);
+    for (uint32_t i = 0; i < n_resized; ++i) by_file[i] = {host_files[i], i};
+    std::sort(by_file.begin(), by_file.end());
+    for (uint32_t k = 1; k < n_resized; ++k)
+      if (by_file[k - 1].first == by_file[k].first)
+        return resize_refuse(ctx, resize_entry_text(by_file[k].second, by_file[k].first) + ": the file is listed twice (entry " + std::to_string(by_file[k - 1].second) + " is the same)");
+  }
+  if (scratch_bytes < need) return resize_refuse(ctx, "the scratch is smaller than b3w_bao_resize_scratch_bytes says (" + std::to_string(need) + " bytes)");
+  if (need && (!d_scratch || ((uintptr_t)d_scratch & 15))) return resize_refuse(ctx, "the scratch is null or not 16-byte aligned");
+  // one table: tile rows | relocation rows | first storey | second storey | the small files' entries | their waves' first files
+  const uint64_t bytes = (n_tile + n_one + n_two) * sizeof(ManyRow) + n_move * sizeof(ResRow) + n_small * sizeof(BatchEnt) + (n_small ? (waves + 1) * 4 : 0);
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  b3w_ctx::ManySlot *slot = nullptr;
+  const int32_t rc = many_staging(ctx, bytes, &slot);
+  if (rc) return rc;
+  ManyRow *h_tile = reinterpret_cast<ManyRow *>(slot->h), *h_one = h_tile + n_tile, *h_two = h_one + n_one;
+  ResRow *h_move = reinterpret_cast<ResRow *>(h_two + n_two);
+  BatchEnt *h_small = reinterpret_cast<BatchEnt *>(h_move + n_move);
+  uint32_t *h_waves = reinterpret_cast<uint32_t *>(h_small + n_small);
+  uint32_t *at = reinterpret_cast<uint32_t *>(d_scratch);
+  uint32_t i_tile = 0, i_move = 0, i_one = 0, i_two = 0, i_small = 0, i_waves = 0, f_tile = 0, f_move = 0, f_one = 0;
+  fill = 64;
+  for (uint32_t i = 0; i < n_resized; ++i) {
+    const uint32_t f = host_files[i];
+    const uint64_t old_len = host_old_lens[f], len = host_new_lens[f], n = num_chunks(len);
+    if (n <= 64) {
+      if (fill + n > 64) { h_waves[i_waves++] = i_small; fill = 0; }
+      h_small[i_small++] = BatchEnt{host_offsets[f], len, host_new_ob_first[f], (uint32_t)fill, f};
+      fill += n;
+      continue;
+    }
+    const uint64_t kept = b3w_bao_resize_kept_tiles(old_len, len), tiles = resize_tiles(len);
+    uint32_t *tile_cv = tiles > 1 ? at : nullptr, *span_cv = tiles > B3W_TILE ? at + tiles * 8 : nullptr;
+    at += resize_slots(len) * 8;
+    ManyRow r{};
+    r.len = len; r.ob = d_new_outboards + host_new_ob_first[f]; r.root = d_roots + (uint64_t)f * 8; r.gl = group_log;
+    if (tiles > kept) {                                               // the tiles behind the kept ones (kept = 0: every tile, the header with tile 0)
+      ManyRow t = r;
+      t.window = d_arena + host_offsets[f] + kept * RES_TB; t.cv = tile_cv; t.tile0 = (uint32_t)kept; t.first = f_tile;
+      h_tile[i_tile++] = t;
+      f_tile += (uint32_t)(tiles - kept);
+    }
+    if (kept) {                                                       // the kept blocks to their new places, the header, the kept tiles' CVs
+      ResRow m{};
+      m.old_len = old_len; m.new_len = len; m.old_ob = d_old_outboards + host_old_ob_first[f]; m.new_ob = r.ob; m.cv = tile_cv; m.root = r.root;
+      m.first = f_move; m.tiles = (uint32_t)kept; m.gl = group_log;
+      h_move[i_move++] = m;
+      f_move += (uint32_t)(((kept + (1ull << sh.tpw_log) - 1) >> sh.tpw_log) * sh.ppb);
+    }
+    if (tiles > 1) {                                                  // the first merge storey: a workgroup per 1 024 tiles
+      ManyRow t = r;
+      t.cv = tile_cv; t.aux = span_cv; t.first = f_one;
+      h_one[i_one++] = t;
+      f_one += (uint32_t)((tiles + B3W_TILE - 1) / B3W_TILE);
+    }
+    if (tiles > B3W_TILE) {                                           // the second: files past 1 GiB
+      ManyRow t = r;
+      t.cv = span_cv; t.first = i_two;
+      h_two[i_two++] = t;
+    }
+  }
+  if (i_small) h_waves[i_waves] = i_small;
+  const hipError_t ec = hipMemcpyAsync(slot->d, slot->h, (size_t)bytes, hipMemcpyHostToDevice, st);
+  if (ec != hipSuccess) return hip_fail(ctx, ec, "bao resize: table upload");
+  const ManyRow *d_tile = reinterpret_cast<const ManyRow *>(slot->d), *d_one = d_tile + n_tile, *d_two = d_one + n_one;
+  const ResRow *d_move = reinterpret_cast<const ResRow *>(d_two + n_two);
+  const BatchEnt *d_small = reinterpret_cast<const BatchEnt *>(d_move + n_move);
+  const uint32_t *d_waves = reinterpret_cast<const uint32_t *>(d_small + n_small);
+  const uint64_t U = B3W_TILE;
+  if (group_log) {
+    if (n_small) hipLaunchKernelGGL(b3w_bao_small_group_kernel, dim3((uint32_t)waves), dim3(64), 0, st, d_arena, d_small, d_waves, d_new_outboards, d_roots, group_log);
+  } else {
+    if (n_small) hipLaunchKernelGGL(b3w_bao_small_kernel, dim3((uint32_t)waves), dim3(64), 0, st, d_arena, d_small, d_waves, d_new_outboards, d_roots);
+  }
+  if (n_move) hipLaunchKernelGGL(b3w_bao_resize_relocate_kernel, dim3((uint32_t)wg_move), dim3(256), 0, st, d_move, (uint32_t)n_move);
+  if (n_tile) many_launch_tiles(B3W_BAO_STREAM_OUTBOARD, group_log != 0, d_tile, (uint32_t)n_tile, (uint32_t)wg_tile, st);
+  if (group_log) {
+    if (n_one) hipLaunchKernelGGL(b3w_bao_stream_merge_many_group_kernel, dim3((uint32_t)wg_one), dim3(256), 0, st, d_one, (uint32_t)n_one, U);
+    if (n_two) hipLaunchKernelGGL(b3w_bao_stream_merge_many_group_kernel, dim3((uint32_t)n_two), dim3(256), 0, st, d_two, (uint32_t)n_two, U * U);
+  } else {
+    if (n_one) hipLaunchKernelGGL(b3w_bao_stream_merge_many_kernel, dim3((uint32_t)wg_one), dim3(256), 0, st, d_one, (uint32_t)n_one, U);
+    if (n_two) hipLaunchKernelGGL(b3w_bao_stream_merge_many_kernel, dim3((uint32_t)n_two), dim3(256), 0, st, d_two, (uint32_t)n_two, U * U);
+  }
+  const hipError_t e = hipGetLastError();
+  many_release(slot, st);
+  if (e != hipSuccess) return hip_fail(ctx, e, "bao resize launch");
   return B3W_OK;
 }
 

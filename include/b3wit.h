@@ -928,8 +928,8 @@ int32_t b3w_bao_slice_arena_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_
  * lengths, the packed outboards and roots of those files as they were BEFORE some bytes changed, and a list of dirty ranges
  * (host_files[i], host_first_chunk[i], host_n_chunks[i]) that covers every changed byte, d_outboards and d_roots are afterwards byte
  * for byte what b3w_bao_outboard_batch_device (group_log = 0) / b3w_bao_group_outboard_batch_device (1 .. B3W_BAO_MAX_GROUP_LOG) write
- * for the arena as it is now.  LENGTHS DO NOT CHANGE: an append or a truncation moves every node of a pre-order outboard and is the
- * batch call's business.
+ * for the arena as it is now.  LENGTHS DO NOT CHANGE: an append or a truncation moves every node of a pre-order outboard and is
+ * b3w_bao_outboard_resize_batch_device's business ("resident files after appends and truncations" below).
  * A stored node is left CV || right CV, so the CV of every clean sibling on a dirty chunk's path is in the outboard already: only
  * dirty chunks are hashed from bytes.  A UNIT is a chunk (group_log = 0) or a group of 2^group_log chunks; a unit with a dirty chunk
  * is hashed whole.
@@ -979,6 +979,65 @@ int32_t b3w_bao_outboard_update_batch_device(b3w_ctx *ctx, const uint8_t *d_aren
 int32_t b3w_bao_outboard_update(const uint8_t *data, uint64_t len, uint8_t *outboard, uint32_t group_log,
                                 const uint64_t *host_first_chunk, const uint64_t *host_n_chunks, uint32_t n_ranges,
                                 uint32_t *root /* 8 u32 */);
+
+/* ---- resident files after appends and truncations (still ABI 1.4: new names only) -------------------------------------
+ * The update call above follows writes that keep a file's length.  These calls follow a CHANGE of length.  In a pre-order outboard
+ * the PLACE of every node can move when the length changes; the VALUES below a tile of 1 024 chunks that is full before and after
+ * do not ("open-length sessions" above): such a tile's (1 024 >> group_log) - 1 stored nodes are one contiguous block whose start
+ * alone depends on the length, and its chaining value is the parent compression of the block's first node.  GIVEN the arena with a
+ * file's bytes at its NEW length (the first min(old, new) bytes what they were) and its outboard for the OLD length as the batch
+ * calls made it, the file's outboard at its new place and its root are afterwards byte for byte what
+ * b3w_bao_outboard_batch_device (group_log = 0) / b3w_bao_group_outboard_batch_device write for the arena as it is now with the new
+ * lengths: header, every node.  With T = b3w_bao_resize_kept_tiles(old, new):
+ *   the blocks of tiles 0 .. T - 1 are MOVED from the old outboard to the new one and their CVs taken from their first nodes;
+ *   the tiles from T on are hashed from the arena; the one or two merge storeys above the tile CVs are run again.
+ *   NOTHING EXTRA IS READ OR WRITTEN.  No arena byte of a listed file below T MiB is read (a truncation to a whole number of MiB reads
+ *     no arena byte at all; a file that ends up exactly one full tile gets its root from the block's first node).  d_old_outboards is
+ *     never written.  Of d_new_outboards only the listed files' b3w_bao_group_outboard_size(new_len, group_log) bytes are written, of
+ *     d_roots only the listed files' rows.  Nothing of an unlisted file is read or written.
+ *   host_files[0 .. n_resized): the files whose length changed, each at most once.  An equal length is allowed and gives the same
+ *     bytes at the new place.  n_resized == 0: B3W_OK, nothing launched.
+ *   The old and the new outboard of a file are different extents (no resizing within one buffer).
+ * WHEN TO CALL THE BATCH CALL INSTEAD (measured on an MI355X): only the kept tiles are a gain.  4 KiB appended to (or
+ * cut from) a 1 GiB file: 0.17 ms against the batch call's 0.42 (0.16 at group_log = 4), the same for 1 MiB and for 64 MiB appended:
+ * a call that hashes a tile costs that one workgroup's latency, the move of 64 MiB of outboard about 0.02 ms.  512 MiB grown to
+ * 1 GiB: 0.27 against 0.42; 1 GiB cut to 512 MiB (nothing hashed): 0.05 against 0.25.  Files below 1 MiB at either length keep no
+ * tile and are hashed whole through a kernel that is slower than the batch call's: 16 384 files growing from 64 to 68 KiB take 1.63
+ * ms against 1.43.  So: this call where the listed files keep whole MiB tiles, the batch call for files below 1 MiB. */
+/* Host only.  floor(min(old_len, new_len) / 1 MiB): the tiles whose nodes are moved, not recomputed. */
+uint64_t b3w_bao_resize_kept_tiles(uint64_t old_len, uint64_t new_len);
+/* Host only.  Bytes of caller's scratch for the listed files at their NEW lengths: 32 per tile (a last partial tile counts) of every
+ * listed file of more than one tile, plus 32 per 1 024 tiles (rounded up) of those past 1 GiB; a file listed twice counts twice.
+ * host_new_lens is indexed by host_files[i] (which is not checked here).  0 for a null pointer or n_resized == 0. */
+uint64_t b3w_bao_resize_scratch_bytes(const uint64_t *host_new_lens, const uint32_t *host_files, uint32_t n_resized);
+/* File f is bytes [host_offsets[f], + host_new_lens[f]) of d_arena (any byte alignment); d_old_outboards + host_old_ob_first[f] holds
+ * its outboard for host_old_lens[f]; d_new_outboards + host_new_ob_first[f] receives the one for host_new_lens[f]; d_roots: 8 u32 per
+ * file ON THE DEVICE.  The ob_first arrays are taken, not recomputed, and only [f] of listed files is read: they need not be the packed
+ * layouts of b3w_bao_batch_layout, any 8-byte-aligned places will do, and the call's host work and its table grow with n_resized and
+ * never with n_files.  Blocks move in 16-byte pieces where the old and the new place are both 16-byte aligned and in 8-byte pieces
+ * otherwise; the bytes are the same.  d_scratch: 16-byte aligned, b3w_bao_resize_scratch_bytes.
+ * AT MOST FIVE LAUNCHES whatever n_resized and the lengths: the listed files of at most 64 chunks (new length) through the batch
+ * call's kernel for them; the relocation of all kept blocks with the headers, the kept tiles' CVs and the one-tile roots; the tiles
+ * from T on of the larger files; the first merge storey; the second, for files past 1 GiB.  One table (at most 328 bytes a listed
+ * file) goes through the staging ring of the many-calls above; nothing else is allocated, the host waits for nothing.
+ * REFUSALS ARE ATOMIC: every entry is checked first, and a refused call launches nothing and writes nothing (B3W_E_BAD_ARGUMENT,
+ * b3w_last_error names the entry): a null pointer (d_arena may be NULL where no listed file needs a byte read), group_log above the
+ * maximum, a file index >= n_files, a file listed twice, a listed file that reaches past arena_bytes at its new length or has more
+ * than 2^30 chunks at either length, an outboard place off 8 bytes, a listed file whose own old and new outboard extents overlap
+ * (addresses are compared; overlaps between different files' extents are the caller's business), a small, null or misaligned
+ * scratch, more than 2^31 - 1 workgroups in a grid.  Any context.  Asynchronous on `stream`. */
+int32_t b3w_bao_outboard_resize_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets,
+                                             const uint64_t *host_old_lens, const uint64_t *host_new_lens, uint32_t n_files,
+                                             uint32_t group_log, const uint64_t *host_old_ob_first, const uint8_t *d_old_outboards,
+                                             const uint64_t *host_new_ob_first, uint8_t *d_new_outboards, uint32_t *d_roots,
+                                             const uint32_t *host_files, uint32_t n_resized, void *d_scratch, uint64_t scratch_bytes,
+                                             void *stream);
+/* Host only, one file in host memory: the same walk (old blocks copied, the rest hashed with blake3_cv).  `data` is the file at its
+ * new length (no byte below T MiB is read; NULL where none is needed), old_outboard its outboard for old_len; new_outboard receives
+ * b3w_bao_group_outboard_size(new_len, group_log) bytes.  B3W_E_BAD_ARGUMENT, nothing written, for a null pointer, a group_log above
+ * the maximum, more than 2^30 chunks at either length or outboards that overlap. */
+int32_t b3w_bao_outboard_resize(const uint8_t *data, uint64_t new_len, const uint8_t *old_outboard, uint64_t old_len,
+                                uint32_t group_log, uint8_t *new_outboard, uint32_t *root /* 8 u32 */);
 
 #ifdef __cplusplus
 }
