@@ -213,6 +213,9 @@ def lib():
         "b3w_bao_resize_scratch_bytes": (u64, [vp, vp, u32]),
         "b3w_bao_outboard_resize_batch_device": (i32, [vp, vp, u64, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, u32, vp, u64, vp]),
         "b3w_bao_outboard_resize": (i32, [vp, u64, vp, u64, u32, vp, vp]),
+        "b3w_bao_verify_ranges_scratch_bytes": (u64, [vp, vp, vp, vp, u32]),
+        "b3w_bao_verify_ranges_batch_device": (i32, [vp, vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, u64, vp]),
+        "b3w_bao_verify_ranges": (i32, [vp, u64, vp, u32, vp, vp, vp, u32, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -246,7 +249,8 @@ EXPORTED_SYMBOLS = ("b3w_abi_version", "b3w_identify_wasm", "b3w_create", "b3w_d
                     "b3w_bao_stream_open_begin", "b3w_bao_stream_open_finish", "b3w_bao_stream_open_finish_many",
                     "b3w_sample_plan_arena_device", "b3w_bao_slice_arena_device",
                     "b3w_bao_update_scratch_bytes", "b3w_bao_outboard_update_batch_device", "b3w_bao_outboard_update",
-                    "b3w_bao_resize_kept_tiles", "b3w_bao_resize_scratch_bytes", "b3w_bao_outboard_resize_batch_device", "b3w_bao_outboard_resize")
+                    "b3w_bao_resize_kept_tiles", "b3w_bao_resize_scratch_bytes", "b3w_bao_outboard_resize_batch_device", "b3w_bao_outboard_resize",
+                    "b3w_bao_verify_ranges_scratch_bytes", "b3w_bao_verify_ranges_batch_device", "b3w_bao_verify_ranges")
 
 
 class graph_capture:

@@ -18,6 +18,8 @@ which learns the length, moves them to their places in the outboard.  open_finis
 most four launches, and outboard_stream_open_many() keeps `lanes` sources of unknown length in flight with it.
 outboard_update_batch() updates outboards and roots IN PLACE after writes into resident files, from the dirty chunk ranges alone
 (chunk_ranges() makes them from byte ranges; update_host(): one file on the host).
+verify_ranges_batch() is verify_batch() for the units that hold listed chunk ranges alone: only those are hashed, only the nodes above
+them read, only their status bytes written, plus a status and a first bad unit per range (verify_ranges_host(): one file on the host).
 The records are
 word for word those the chain planner writes for the same chunks (ChainPlanner.plan), so every step is the reference's
 prove_chunk_hash step (rust_fold/src/main.rs:41-203 over hash_with_path's slice, rust_fold/src/blake3_hash.rs:17-93)."""
@@ -653,6 +655,83 @@ def update_host(data, outboard, root, first_chunks, n_chunks, group_log=0):
          "b3w_bao_outboard_update")
     del buf
     return bytes(ob), rw
+
+
+# ---- verification of listed chunk ranges of resident files -------------------------------------------------------------------
+def verify_ranges_batch(ctx, d_arena, offsets, lens, d_outboards, d_roots, files, first_chunks, n_chunks, group_log=0, ob_first=None, unit_first=None,
+                        unit_status=None, stream=0):
+    """verify_batch for the units that hold the listed chunks alone: ranges are chunks [first_chunks[i], + n_chunks[i]) of file
+    files[i] (chunk_ranges() makes them from byte extents), unsorted, overlapping or repeated as they come.  Only listed units are
+    hashed and only the stored nodes above them read, in at most five launches.  Returns a dict, everything but unit_first left on the
+    device: unit_status (uint8 CUDA, packed as unit_first says): the byte of every unit with a listed chunk is what verify_batch
+    writes there, NO OTHER BYTE IS WRITTEN (a listed file of at most 64 chunks excepted: all its bytes are) — so pass the same
+    `unit_status` buffer to successive calls to build up the statuses of what a scrub has covered; without one a new buffer filled
+    with 0xFF is made.  range_status (int32 CUDA [n_ranges]: the largest status among the units range i touches) and range_first_bad
+    (int64 CUDA [n_ranges]: the lowest unit index within the file with a non-zero status among them, -1 = UINT64_MAX where there is
+    none), in the order the ranges were given; unit_first (numpy uint64 [n_files + 1]).  ob_first / unit_first: group_batch_layout /
+    verify_layout of lens, computed here when None (pass them for very many files: the call itself does no work per file).  When
+    to call verify_batch instead (MI355X): one 4 KiB range of a 1 GiB file takes 0.10 ms against verify_batch's 0.43,
+    1 024 scattered ones 0.23, 4 096 (a range in nearly every tile) 0.41, which is level; with every chunk listed it takes 0.59, 1.36
+    times verify_batch.  So: this call while the ranges leave tiles out or most chunks of the tiles they touch unlisted, verify_batch
+    when most of the file is listed."""
+    L = lib()
+    if not 0 <= group_log <= MAX_GROUP_LOG:
+        raise B3WError(100, f"group_log {group_log} is not in 0 .. {MAX_GROUP_LOG}")
+    off, ln = _u64(offsets), _u64(lens)
+    fi = np.ascontiguousarray(np.atleast_1d(files), dtype=np.uint32)
+    fc, nc = _ranges(first_chunks, n_chunks)
+    if off.size != ln.size or fi.size != fc.size:
+        raise B3WError(100, f"verify_ranges_batch: {off.size} offsets and {ln.size} lengths, {fi.size} files and {fc.size} ranges")
+    assert d_arena.is_cuda and d_arena.dtype == torch.uint8 and d_arena.is_contiguous()
+    assert d_outboards.is_cuda and d_outboards.dtype == torch.uint8 and d_outboards.is_contiguous()
+    assert d_roots.is_cuda and d_roots.is_contiguous() and d_roots.element_size() == 4 and d_roots.numel() >= ln.size * 8
+    obf = group_batch_layout(ln, group_log) if ob_first is None else _u64(ob_first)
+    if obf.size != ln.size + 1 or d_outboards.numel() < int(obf[-1]):
+        raise B3WError(100, "verify_ranges_batch: ob_first or d_outboards is not of these lengths' layout")
+    uf = verify_layout(ln, group_log) if unit_first is None else _u64(unit_first)
+    if uf.size != ln.size + 1:
+        raise B3WError(100, "verify_ranges_batch: unit_first is not of these lengths' layout")
+    dev = d_arena.device
+    if unit_status is None:
+        unit_status = torch.full((int(uf[-1]),), 0xFF, dtype=torch.uint8, device=dev)
+    assert unit_status.is_cuda and unit_status.dtype == torch.uint8 and unit_status.is_contiguous() and unit_status.numel() >= int(uf[-1])
+    range_status = torch.empty(fi.size, dtype=torch.int32, device=dev)
+    range_first_bad = torch.empty(fi.size, dtype=torch.int64, device=dev)
+    out = dict(unit_status=unit_status, range_status=range_status, range_first_bad=range_first_bad, unit_first=uf)
+    if fi.size == 0:
+        return out
+    if int(fi.max()) >= ln.size:
+        raise B3WError(100, f"verify_ranges_batch: file index {int(fi.max())} is not below the file count {ln.size}")
+    need = L.b3w_bao_verify_ranges_scratch_bytes(ln.ctypes.data, fi.ctypes.data, fc.ctypes.data, nc.ctypes.data, fi.size)
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    _chk(ctx, L.b3w_bao_verify_ranges_batch_device(ctx.handle, d_arena.data_ptr() if d_arena.numel() else None, d_arena.numel(), off.ctypes.data,
+                                                   ln.ctypes.data, ln.size, group_log, obf.ctypes.data, d_outboards.data_ptr(), d_roots.data_ptr(),
+                                                   fi.ctypes.data, fc.ctypes.data, nc.ctypes.data, fi.size, uf.ctypes.data, unit_status.data_ptr(),
+                                                   range_status.data_ptr(), range_first_bad.data_ptr(), scratch.data_ptr() if need else None, need,
+                                                   _stream(stream)), "b3w_bao_verify_ranges_batch_device")
+    return out
+
+
+def verify_ranges_host(data, outboard, root, first_chunks, n_chunks, group_log=0):
+    """verify_ranges_batch for one file on the host (no GPU) -> (unit_status numpy uint8, range_status numpy int32, range_first_bad numpy
+    uint64: 2^64 - 1 = none).  unit_status holds verify_host's byte at every unit with a listed chunk and 0xFF everywhere else (the
+    host walk writes listed units only, whatever the file's size); only the listed units' bytes and the nodes above them are read."""
+    if not 0 <= group_log <= MAX_GROUP_LOG:
+        raise B3WError(100, f"group_log {group_log} is not in 0 .. {MAX_GROUP_LOG}")
+    data = bytes(data)
+    ob = outboard.cpu().numpy().tobytes() if isinstance(outboard, torch.Tensor) else bytes(outboard)
+    if len(ob) != group_outboard_size(len(data), group_log):
+        raise B3WError(100, "verify_ranges_host: the outboard's size is not that of a file of this length")
+    fc, nc = _ranges(first_chunks, n_chunks)
+    rw = np.ascontiguousarray(root, dtype=np.uint32)
+    if rw.size != 8:
+        raise B3WError(100, "verify_ranges_host: the root is 8 words")
+    units = (num_chunks(len(data)) + (1 << group_log) - 1) >> group_log
+    st = np.full(units, 0xFF, dtype=np.uint8)
+    rs, rf = np.zeros(fc.size, dtype=np.int32), np.zeros(fc.size, dtype=np.uint64)
+    _chk(None, lib().b3w_bao_verify_ranges(data, len(data), ob, group_log, rw.ctypes.data, fc.ctypes.data, nc.ctypes.data, fc.size, st.ctypes.data,
+                                           rs.ctypes.data, rf.ctypes.data), "b3w_bao_verify_ranges")
+    return st, rs, rf
 
 
 # ---- resident files after appends and truncations ---------------------------------------------------------------------------

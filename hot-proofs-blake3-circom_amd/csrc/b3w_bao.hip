@@ -1586,6 +1586,268 @@ __device__ __forceinline__ void update_merge_body(const UpdRow *__restrict__ row
 __global__ __launch_bounds__(256) void b3w_bao_update_merge_kernel(const UpdRow *__restrict__ rows, uint64_t unit) { update_merge_body<false>(rows, unit); }
 __global__ __launch_bounds__(256) void b3w_bao_update_merge_group_kernel(const UpdRow *__restrict__ rows, uint64_t unit) { update_merge_body<true>(rows, unit); }
 
+// ---- ranged verification: listed chunk ranges of resident files against their outboards ------------------------------------------------
+// The update's sparse walk with check_pair where the update has its sparse merge (b3wit.h "verification of listed chunk ranges"): only
+// the LISTED units are hashed from bytes, only the stored nodes with a listed unit below them are loaded, and what is checked of such a
+// node is what verify_in_lds checks of it — its listed halves against the claims in LDS, its own hash against its half of the node
+// above.  A clean half is no claim and is not looked at.  The storeys run top down as in the whole-file call:
+//   b3w_bao_verify_ranges_upper_kernel   a workgroup per span of 1 024 tiles that holds a listed tile (unit = B3W_TILE; before it, for
+//                                        files past 1 GiB, one per file over its listed spans, unit = B3W_TILE^2): leaves, for each
+//                                        LISTED item, the CV it must have and the flags of the path above in the item's compact
+//                                        scratch entry (entry = the workgroup's base + the listed items below it: the rows are sorted)
+//   b3w_bao_verify_ranges_tile_kernel    a workgroup per listed tile, lane = chunk, the lanes of listed units alone hash: the status byte
+//                                        of every listed unit and of no other
+//   b3w_bao_verify_ranges_small_kernel   the listed files of at most 64 chunks, verified whole: b3w_bao_verify_small_kernel's wave with
+//                                        the entry by row (no per-file table, no per-file outputs)
+//   b3w_bao_verify_ranges_reduce_kernel  a workgroup per range AS THE CALLER GAVE IT: the largest status byte and the first non-zero
+//                                        one among the units the range touches, written plainly (nothing to clear, no global atomic)
+// A row per workgroup, indexed by blockIdx.x; mask as in UpdRow (expanded to whole groups by the host).  The word an upper workgroup
+// leaves beside an expected CV: VR_PATH = a stored node above fails, VR_HDR = the header is not the length (read once, by the file's top
+// workgroup; a one-tile file's tile reads it itself).
+struct VrRow {
+  uint64_t len;
+  const uint8_t *data;                                   // the file's first byte (tile rows)
+  const uint8_t *ob;                                     // the file's outboard, header first
+  const uint32_t *root;
+  const uint32_t *want;                                  // the workgroup's own scratch entry: 8 words of CV ... (unused by a file's top workgroup)
+  const uint32_t *above;                                 // ... and its word
+  uint32_t *out_cv, *out_word;                           // upper rows: the entry of the workgroup's first listed item
+  uint8_t *unit_status;                                  // tile rows: the status byte of the file's unit 0
+  uint32_t idx, gl;                                      // the tile within the file / the span within the file (0 one storey up)
+  uint32_t mask[B3W_TILE / 32];
+};
+struct VrSmall { uint64_t off, len; const uint8_t *ob; const uint32_t *root; uint8_t *unit_status; uint32_t first, pad; };
+struct VrRange { const uint8_t *units; uint64_t first, count; };      // status bytes [first, first + count) of the file whose unit 0 is at `units`
+constexpr uint32_t VR_PATH = 1u, VR_HDR = 2u;
+
+// check_pair over the listed halves alone (d0, d1: the half has a listed unit below it).  !CLAIM: rank[i] = the listed items below item i,
+// its entry behind exp_out.
+template <bool CLAIM>
+__device__ __forceinline__ void ranges_pair(uint32_t *cv, uint32_t *flags, const uint32_t *rank, uint32_t i0, uint32_t i1, bool d0, bool d1, uint32_t l,
+                                            const uint8_t *__restrict__ node, uint32_t d, uint64_t sl, uint64_t sr, uint64_t leaf,
+                                            uint32_t *__restrict__ exp_out) {
+  uint32_t m[16], ivv[8], o[8];
+  load_node(node, m);
+  if (d0) {
+    if (sl <= leaf) {
+      if (CLAIM) { if (!eq8(cv + i0 * 8, m)) flags[i0] |= VER_UNIT; }
+      else {
+        const uint64_t at = (uint64_t)rank[i0] * 8;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) exp_out[at + k] = m[k];
+      }
+    } else if (!eq8(cv + i0 * 8, m)) flags[i0] |= 1u << l;
+  }
+  if (d1) {
+    if (sr <= leaf) {
+      if (CLAIM) { if (!eq8(cv + i1 * 8, m + 8)) flags[i1] |= VER_UNIT; }
+      else {
+        const uint64_t at = (uint64_t)rank[i1] * 8;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) exp_out[at + k] = m[8 + k];
+      }
+    } else if (!eq8(cv + i1 * 8, m + 8)) flags[i1] |= 1u << l;
+  }
+  iv(ivv);
+  blake3_cv(ivv, m, 0, 0, 64, d, o);
+  reinterpret_cast<uint4 *>(cv + i0 * 8)[0] = make_uint4(o[0], o[1], o[2], o[3]);          // (slot i0 is this thread's alone at this level)
+  reinterpret_cast<uint4 *>(cv + i0 * 8)[1] = make_uint4(o[4], o[5], o[6], o[7]);
+}
+
+// verify_in_lds over the listed items alone: listed[i] says whether slot i holds a claim (CLAIM) or has a listed item below it.  A pair
+// with no listed child is skipped: nothing loaded, nothing checked.  Any other one leaves hash(stored node) in slot i0 and marks it; an
+// odd item out waits and keeps its mark.  Inside a (listed) group both halves are in LDS and nothing is loaded.  Ends with a barrier.
+template <int BS, bool CLAIM>
+__device__ __forceinline__ void ranges_in_lds(uint32_t *cv, uint32_t *flags, uint32_t *listed, const uint32_t *rank, uint32_t cnt, uint64_t unit,
+                                              uint64_t total, const uint8_t *__restrict__ nodes, bool root, uint32_t gl, uint32_t *__restrict__ exp_out) {
+  const uint64_t G = 1ull << gl, G1 = G - 1, leaf = CLAIM ? G : unit;
+  for (uint32_t l = 0; (1u << l) < cnt; ++l) {
+    lds_barrier();
+    const bool top = (2u << l) >= cnt;
+    for (uint32_t j = threadIdx.x;; j += BS) {
+      const uint32_t i0 = (2 * j) << l, i1 = i0 + (1u << l);
+      if (i1 >= cnt) break;
+      const bool d0 = listed[i0] != 0, d1 = listed[i1] != 0;
+      if (!d0 && !d1) continue;
+      const uint64_t a = i0 * unit, e = (uint64_t)(i0 + (2u << l)) * unit, size = (e < total ? e : total) - a;
+      const uint32_t d = 4u | (top && root ? 8u : 0u);
+      if (CLAIM && size <= G) { merge_pair<true>(cv, i0, i1, nullptr, d); continue; }          // inside a listed group: computed
+      const uint64_t sl = ((uint64_t)unit) << l;
+      ranges_pair<CLAIM>(cv, flags, rank, i0, i1, d0, d1, l, nodes + preorder_pos((total + G1) >> gl, a >> gl, (size + G1) >> gl) * 64, d, sl, size - sl,
+                         leaf, exp_out);
+      listed[i0] = 1;
+    }
+  }
+  lds_barrier();
+}
+
+// unit = chunks per item, as in b3w_bao_verify_upper_kernel; the workgroup's items are [1 024 idx, ...) of the file's
+__global__ __launch_bounds__(256) void b3w_bao_verify_ranges_upper_kernel(const VrRow *__restrict__ rows, uint64_t unit) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
+  __shared__ uint32_t flags[B3W_TILE], listed[B3W_TILE], rank[B3W_TILE];
+  const VrRow *__restrict__ r = rows + blockIdx.x;
+  const uint32_t gl = r->gl;
+  const uint64_t len = r->len, n = (len + 1023) / 1024;               // (more than one tile)
+  const uint64_t span = unit * B3W_TILE, a0 = (uint64_t)r->idx * span;
+  const uint64_t tot = n - a0 < span ? n - a0 : span;
+  const uint32_t cnt = (uint32_t)((tot + unit - 1) / unit);
+  const bool sole = n <= span;                                        // the file's top workgroup
+  const uint8_t *__restrict__ ob = as_global(r->ob);
+  const uint32_t *__restrict__ want = as_global(sole ? r->root : r->want);
+  uint32_t *__restrict__ out_cv = as_global(r->out_cv), *__restrict__ out_word = as_global(r->out_word);
+  uint32_t above;
+  if (sole) {
+    const uint32_t *h = reinterpret_cast<const uint32_t *>(ob);
+    above = ((uint64_t)h[0] | ((uint64_t)h[1] << 32)) != len ? VR_HDR : 0u;
+  } else {
+    above = *as_global(r->above);
+  }
+  if (cnt == 1) {                                                     // a lone last tile (or span) hangs straight off the storey above
+    if (threadIdx.x < 8) out_cv[threadIdx.x] = want[threadIdx.x];
+    if (threadIdx.x == 0) out_word[0] = above;
+    return;
+  }
+  for (uint32_t i = threadIdx.x; i < cnt; i += 256) {
+    const uint32_t w = r->mask[i >> 5], bit = 1u << (i & 31);
+    uint32_t below = __popc(w & (bit - 1));
+    for (uint32_t k = 0; k < (i >> 5); ++k) below += __popc(r->mask[k]);
+    flags[i] = 0; listed[i] = (w & bit) ? 1u : 0u; rank[i] = below;
+  }
+  const uint64_t G1 = (1ull << gl) - 1;
+  ranges_in_lds<256, false>(cv, flags, listed, rank, cnt, unit, tot, ob + 8 + preorder_pos((n + G1) >> gl, a0 >> gl, (tot + G1) >> gl) * 64, sole, gl, out_cv);
+  if (!eq8(cv, want)) above |= VR_PATH;
+  for (uint32_t t = threadIdx.x; t < cnt; t += 256)
+    if ((r->mask[t >> 5] >> (t & 31)) & 1u) out_word[rank[t]] = above | (path_bad(flags, t) ? VR_PATH : 0u);
+}
+
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_verify_ranges_tile_kernel(const VrRow *__restrict__ rows) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
+  __shared__ uint32_t flags[B3W_TILE], listed[B3W_TILE];
+  const VrRow *__restrict__ r = rows + blockIdx.x;
+  const uint32_t t = threadIdx.x, gl = r->gl, G = 1u << gl;
+  const uint64_t len = r->len, n = (len + 1023) / 1024;               // (more than 64 chunks)
+  const uint64_t a0 = (uint64_t)r->idx * B3W_TILE;
+  const uint32_t m = (uint32_t)(n - a0 < B3W_TILE ? n - a0 : B3W_TILE);
+  const bool sole = n <= B3W_TILE;
+  const bool mine = t < m && ((r->mask[t >> 5] >> (t & 31)) & 1u);
+  const uint8_t *__restrict__ ob = as_global(r->ob);
+  listed[t] = mine ? 1u : 0u;
+  flags[t] = 0;
+  if (mine) {
+    const uint64_t c = a0 + t, off = c * 1024;
+    uint32_t h[8];
+    chunk_cv(as_global(r->data) + off, (uint32_t)(len - off < 1024 ? len - off : 1024), c, 0, h);
+    reinterpret_cast<uint4 *>(cv + t * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
+    reinterpret_cast<uint4 *>(cv + t * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
+  }
+  uint32_t above;
+  if (sole) {
+    const uint32_t *h = reinterpret_cast<const uint32_t *>(ob);
+    above = ((uint64_t)h[0] | ((uint64_t)h[1] << 32)) != len ? VR_HDR : 0u;
+  } else {
+    above = *as_global(r->above);
+  }
+  const uint64_t G1 = G - 1;
+  ranges_in_lds<B3W_TILE, true>(cv, flags, listed, nullptr, m, 1, m, ob + 8 + preorder_pos((n + G1) >> gl, a0 >> gl, (m + G1) >> gl) * 64, sole, gl, nullptr);
+  // (the row's mask is not empty: slot 0 holds what the tile's stored root node hashes to, or the CV of a tile that is one unit)
+  if (t == 0 && !eq8(cv, as_global(sole ? r->root : r->want))) flags[0] |= m <= G ? VER_UNIT : VER_TOP;
+  lds_barrier();
+  if (mine && (t & (G - 1)) == 0) {                                   // a listed unit's first chunk: its status
+    const uint32_t st = (above & VR_HDR) ? 3u : (above & VR_PATH) || path_bad(flags, t) ? 2u : (flags[t] & VER_UNIT) ? 1u : 0u;
+    as_global(r->unit_status)[(a0 + t) >> gl] = (uint8_t)st;
+  }
+}
+
+// b3w_bao_verify_small_kernel with a row per file: wave w takes the rows [wave_first[w], wave_first[w + 1]), r.first = the lane of the
+// file's chunk 0; every unit byte of the file is written, with the whole-file call's value
+__global__ __launch_bounds__(64) void b3w_bao_verify_ranges_small_kernel(const uint8_t *__restrict__ arena, const VrSmall *__restrict__ rows,
+                                                                         const uint32_t *__restrict__ wave_first, uint32_t gl) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[64 * 8];
+  __shared__ uint32_t flags[64];
+  const uint32_t lane = threadIdx.x, G = 1u << gl;
+  uint32_t lo = wave_first[blockIdx.x], hi = wave_first[blockIdx.x + 1];
+  while (hi - lo > 1) {                                               // this lane's file: the last one that starts at or before the lane
+    const uint32_t mid = (lo + hi) / 2;
+    if (rows[mid].first <= lane) lo = mid; else hi = mid;
+  }
+  const VrSmall e = rows[lo];
+  const uint32_t n = e.len ? (uint32_t)((e.len + 1023) / 1024) : 1, i = lane - e.first;
+  const bool live = i < n;                                            // (the lanes behind the last file's chunks are not)
+  if (live) {
+    const uint32_t off = i * 1024;
+    uint32_t h[8];
+    chunk_cv(arena + e.off + off, (uint32_t)(e.len - off < 1024 ? e.len - off : 1024), i, n == 1 ? 8u : 0u, h);
+    reinterpret_cast<uint4 *>(cv + lane * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
+    reinterpret_cast<uint4 *>(cv + lane * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
+  }
+  flags[lane] = 0;
+  const uint8_t *__restrict__ ob = as_global(e.ob);
+  const bool hdr = ((uint64_t)reinterpret_cast<const uint32_t *>(ob)[0] | ((uint64_t)reinterpret_cast<const uint32_t *>(ob)[1] << 32)) != e.len;
+  for (uint32_t l = 0; l < 6; ++l) {
+    lds_barrier();
+    if (!__any(live && (1u << l) < n)) break;                         // (uniform: the workgroup is this one wave)
+    if (live && (i & ((2u << l) - 1)) == 0 && i + (1u << l) < n) {
+      const uint32_t size = n - i < (2u << l) ? n - i : (2u << l), d = 4u | (i == 0 && (2u << l) >= n ? 8u : 0u);
+      if (size <= G) merge_pair<true>(cv, lane, lane + (1u << l), nullptr, d);
+      else check_pair<true>(cv, flags, lane, lane + (1u << l), l, ob + 8 + preorder_pos((n + G - 1) >> gl, i >> gl, (size + G - 1) >> gl) * 64, d,
+                            1u << l, size - (1u << l), G, nullptr);
+    }
+  }
+  lds_barrier();
+  if (live && i == 0 && !eq8(cv + lane * 8, as_global(e.root))) flags[lane] |= n <= G ? VER_UNIT : 1u << 6;
+  lds_barrier();
+  if (live && (i & (G - 1)) == 0) {
+    uint32_t x = 0;
+#pragma unroll
+    for (uint32_t l = 0; l <= 6; ++l) x |= flags[e.first + ((i >> l) << l)] & (1u << l);
+    as_global(e.unit_status)[i >> gl] = (uint8_t)(hdr ? 3u : x ? 2u : (flags[lane] & VER_UNIT) ? 1u : 0u);
+  }
+}
+
+// range_status / range_first_bad of range blockIdx.x from the status bytes the launches before this one wrote (16 at a time between
+// the first and the last 16-byte boundary of the run)
+__global__ __launch_bounds__(256) void b3w_bao_verify_ranges_reduce_kernel(const VrRange *__restrict__ ranges, int32_t *__restrict__ range_status,
+                                                                           unsigned long long *__restrict__ range_first_bad) {
+  __shared__ uint32_t worst;
+  __shared__ unsigned long long first;
+  const VrRange r = ranges[blockIdx.x];
+  const uint8_t *__restrict__ u = as_global(r.units);
+  if (threadIdx.x == 0) { worst = 0; first = ~0ull; }
+  __syncthreads();
+  uint32_t w = 0;
+  unsigned long long f = ~0ull;
+  const uint64_t lo = r.first, hi = r.first + r.count;
+  const uint64_t mis = (16 - ((uintptr_t)(u + lo) & 15)) & 15;
+  const uint64_t b0 = lo + (mis < r.count ? mis : r.count), b1 = b0 + ((hi - b0) & ~15ull);
+  for (uint64_t i = lo + threadIdx.x; i < b0; i += 256) {
+    const uint32_t s = u[i];
+    if (s) { w = w > s ? w : s; f = f < i ? f : i; }
+  }
+  for (uint64_t i = b0 + (uint64_t)threadIdx.x * 16; i < b1; i += 256 * 16) {
+    const uint4 v = *reinterpret_cast<const uint4 *>(u + i);
+    const uint32_t q[4] = {v.x, v.y, v.z, v.w};
+    if (v.x | v.y | v.z | v.w) {
+#pragma unroll
+      for (int k = 3; k >= 0; --k)
+#pragma unroll
+        for (int b = 3; b >= 0; --b) {
+          const uint32_t s = (q[k] >> (8 * b)) & 255u;
+          if (s) { w = w > s ? w : s; const uint64_t at = i + 4 * k + b; f = f < at ? f : at; }
+        }
+    }
+  }
+  for (uint64_t i = b1 + threadIdx.x; i < hi; i += 256) {
+    const uint32_t s = u[i];
+    if (s) { w = w > s ? w : s; f = f < i ? f : i; }
+  }
+  if (w) { atomicMax(&worst, w); atomicMin(&first, f); }              // (LDS; a clean range issues none)
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    range_status[blockIdx.x] = (int32_t)worst;
+    range_first_bad[blockIdx.x] = first;
+  }
+}
+
 // ---- open-length sessions: full tiles hashed before the file's length is known -----------------------------------------------------------
 // A FULL tile of 1 024 chunks is a complete subtree whatever the file's length turns out to be: its (1 024 >> gl) - 1 stored nodes are
 // contiguous in the file's pre-order outboard, in the order merge_in_lds gives them relative to the tile's root, and only the START of that
@@ -3565,6 +3827,195 @@ int32_t b3w_bao_outboard_update_batch_device(b3w_ctx *ctx, const uint8_t *d_aren
   const hipError_t e = hipGetLastError();
   many_release(slot, st);
   if (e != hipSuccess) return hip_fail(ctx, e, "bao update launch");
+  return B3W_OK;
+}
+
+}  // extern "C"
+
+// ---- ranged verification: the host side (b3wit.h "verification of listed chunk ranges of resident files") --------------------------------
+namespace {
+
+int32_t ranges_refuse(b3w_ctx *ctx, const std::string &why) {
+  ctx->last_error = "bao verify ranges: " + why;
+  return B3W_E_BAD_ARGUMENT;
+}
+
+// host_verify_walk over the listed units alone (`units`: sorted unit ranges with ascending ends): a subtree that no range touches is
+// neither read nor written
+void host_ranges_walk(const uint8_t *data, uint64_t len, uint64_t n, uint32_t gl, const uint8_t *nodes, const std::vector<UpdRange> &units, uint64_t first,
+                      uint64_t cnt, uint64_t pos, const uint32_t want[8], bool bad, bool root, uint8_t *status) {
+  auto it = std::upper_bound(units.begin(), units.end(), first, [](uint64_t x, const UpdRange &r) { return x < r.end; });
+  if (it == units.end() || it->first >= first + cnt) return;
+  if (cnt == 1) {
+    const uint64_t c0 = first << gl, gn = n - c0 < (1ull << gl) ? n - c0 : (1ull << gl);
+    uint32_t h[8];
+    host_subtree_cv(data, len, c0, gn, root, h);
+    status[first] = bad ? 2 : memcmp(h, want, 32) != 0 ? 1 : 0;
+    return;
+  }
+  uint32_t mw[16], ivv[8], o[8];
+  for (int k = 0; k < 16; ++k) {
+    const uint8_t *b = nodes + 64 * pos + 4 * k;
+    mw[k] = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
+  }
+  iv(ivv);
+  blake3_cv(ivv, mw, 0, 0, 64, 4u | (root ? 8u : 0u), o);
+  if (memcmp(o, want, 32) != 0) bad = true;
+  uint64_t k2 = 1;
+  while (k2 * 2 < cnt) k2 *= 2;
+  host_ranges_walk(data, len, n, gl, nodes, units, first, k2, pos + 1, mw, bad, false, status);
+  host_ranges_walk(data, len, n, gl, nodes, units, first + k2, cnt - k2, pos + k2, mw + 8, bad, false, status);
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t b3w_bao_verify_ranges_scratch_bytes(const uint64_t *host_lens, const uint32_t *host_files, const uint64_t *host_first_chunk,
+                                             const uint64_t *host_n_chunks, uint32_t n_ranges) {
+  if (!n_ranges || !host_lens || !host_files || !host_first_chunk || !host_n_chunks) return 0;
+  const UpdPlan p = update_plan(host_lens, update_ranges(host_lens, host_files, host_first_chunk, host_n_chunks, n_ranges), 0);
+  return ((p.tile_slots + p.span_slots) * 36 + 15) & ~15ull;          // the expected CV (32) and the word (4) of every entry
+}
+
+int32_t b3w_bao_verify_ranges(const uint8_t *data, uint64_t len, const uint8_t *outboard, uint32_t group_log, const uint32_t *root,
+                              const uint64_t *host_first_chunk, const uint64_t *host_n_chunks, uint32_t n_ranges, uint8_t *unit_status,
+                              int32_t *range_status, uint64_t *range_first_bad) {
+  if ((!data && len) || !outboard || !root || !unit_status || group_log > B3W_BAO_MAX_GROUP_LOG || (n_ranges && (!host_first_chunk || !host_n_chunks)))
+    return B3W_E_BAD_ARGUMENT;
+  const uint64_t n = num_chunks(len), G1 = (1ull << group_log) - 1, n_units = (n + G1) >> group_log;
+  for (uint32_t i = 0; i < n_ranges; ++i)
+    if (host_first_chunk[i] > n || host_n_chunks[i] > n - host_first_chunk[i]) return B3W_E_BAD_ARGUMENT;
+  std::vector<uint32_t> zero(n_ranges, 0);
+  std::vector<UpdRange> units = update_ranges(&len, zero.data(), host_first_chunk, host_n_chunks, n_ranges);
+  for (UpdRange &r : units) { r.first >>= group_log; r.end = (r.end + G1) >> group_log; }   // (still sorted; adjoining ones may now overlap)
+  for (size_t i = 1; i < units.size(); ++i)
+    if (units[i].end < units[i - 1].end) units[i].end = units[i - 1].end;          // (ends ascending, for the bisection)
+  uint64_t hdr = 0;
+  if (!units.empty())                                                 // (read once, and only where something is listed)
+    for (int k = 0; k < 8; ++k) hdr |= (uint64_t)outboard[k] << (8 * k);
+  if (!units.empty() && hdr != len) {
+    for (const UpdRange &r : units) memset(unit_status + r.first, 3, (size_t)(r.end - r.first));
+  } else {
+    host_ranges_walk(data, len, n, group_log, outboard + 8, units, 0, n_units, 0, root, false, true, unit_status);
+  }
+  for (uint32_t i = 0; i < n_ranges; ++i) {
+    int32_t worst = 0;
+    uint64_t first = ~0ull;
+    if (host_n_chunks[i])
+      for (uint64_t u = host_first_chunk[i] >> group_log; u <= (host_first_chunk[i] + host_n_chunks[i] - 1) >> group_log; ++u) {
+        if (unit_status[u] > worst) worst = unit_status[u];
+        if (unit_status[u] && first == ~0ull) first = u;
+      }
+    if (range_status) range_status[i] = worst;
+    if (range_first_bad) range_first_bad[i] = first;
+  }
+  return B3W_OK;
+}
+
+int32_t b3w_bao_verify_ranges_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets,
+                                           const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint64_t *host_ob_first,
+                                           const uint8_t *d_outboards, const uint32_t *d_roots, const uint32_t *host_files,
+                                           const uint64_t *host_first_chunk, const uint64_t *host_n_chunks, uint32_t n_ranges,
+                                           const uint64_t *host_unit_first, uint8_t *d_unit_status, int32_t *d_range_status,
+                                           uint64_t *d_range_first_bad, void *d_scratch, uint64_t scratch_bytes, void *stream) {
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  if (group_log > B3W_BAO_MAX_GROUP_LOG) return ranges_refuse(ctx, "group_log is above B3W_BAO_MAX_GROUP_LOG (6)");
+  if (!n_ranges) return B3W_OK;
+  if (!host_offsets || !host_lens || !host_ob_first || !d_outboards || !d_roots || !host_files || !host_first_chunk || !host_n_chunks || !host_unit_first)
+    return ranges_refuse(ctx, "a null pointer (offsets, lengths, outboard offsets, unit offsets, outboards, roots or a range array)");
+  if (!d_unit_status || !d_range_status || !d_range_first_bad) return ranges_refuse(ctx, "a null output pointer (unit statuses, range statuses or first bad units)");
+  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_roots & 3)) return ranges_refuse(ctx, "d_outboards is not 8-byte aligned, or d_roots not 4-byte aligned");
+  if (((uintptr_t)d_range_first_bad & 7) || ((uintptr_t)d_range_status & 3))
+    return ranges_refuse(ctx, "d_range_first_bad is not 8-byte aligned, or d_range_status not 4-byte aligned");
+  if (n_ranges > 0x7fffffffu) return ranges_refuse(ctx, "more than 2^31 - 1 ranges in one call");
+  for (uint32_t i = 0; i < n_ranges; ++i) {                           // every range is checked before anything is launched or written
+    const uint32_t f = host_files[i];
+    const uint64_t a = host_first_chunk[i], c = host_n_chunks[i];
+    if (f >= n_files) return ranges_refuse(ctx, update_range_text(i, f, a, c) + ": the file index is not below the file count " + std::to_string(n_files));
+    const uint64_t len = host_lens[f], n = num_chunks(len);
+    if (n > (1ull << 30)) return ranges_refuse(ctx, update_range_text(i, f, a, c) + ": a file of more than 2^30 chunks");
+    if (a > n || c > n - a) return ranges_refuse(ctx, update_range_text(i, f, a, c) + " reaches past the file's " + std::to_string(n) + " chunks");
+    if (host_offsets[f] > arena_bytes || len > arena_bytes - host_offsets[f])
+      return ranges_refuse(ctx, update_range_text(i, f, a, c) + ": the file reaches past arena_bytes");
+    if (len && !d_arena) return ranges_refuse(ctx, update_range_text(i, f, a, c) + ": a null arena with a listed file that is not empty");
+    if (host_ob_first[f] & 7) return ranges_refuse(ctx, update_range_text(i, f, a, c) + ": the file's outboard offset is not a multiple of 8");
+  }
+  const UpdPlan p = update_plan(host_lens, update_ranges(host_lens, host_files, host_first_chunk, host_n_chunks, n_ranges), group_log);
+  const uint64_t n_scr = p.tile_slots + p.span_slots, need = (n_scr * 36 + 15) & ~15ull;
+  if (scratch_bytes < need) return ranges_refuse(ctx, "the scratch is smaller than b3w_bao_verify_ranges_scratch_bytes says (" + std::to_string(need) + " bytes)");
+  if (need && (!d_scratch || ((uintptr_t)d_scratch & 15))) return ranges_refuse(ctx, "the scratch is null or not 16-byte aligned");
+  if (p.tiles.size() > 0x7fffffffull) return ranges_refuse(ctx, "more than 2^31 - 1 listed tiles in one call");
+  // the small files' waves, as the batch call packs them
+  uint64_t waves = 0, fill = 64;
+  for (uint32_t f : p.small) {
+    const uint64_t n = num_chunks(host_lens[f]);
+    if (fill + n > 64) { waves++; fill = 0; }
+    fill += n;
+  }
+  // one table: tile rows | span rows | top rows | the ranges as given | the small files' rows | their waves' first files
+  const uint64_t n_rows = p.tiles.size() + p.spans.size() + p.tops.size();
+  const uint64_t bytes = n_rows * sizeof(VrRow) + (uint64_t)n_ranges * sizeof(VrRange) + p.small.size() * sizeof(VrSmall) + (p.small.empty() ? 0 : (waves + 1) * 4);
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  b3w_ctx::ManySlot *slot = nullptr;
+  const int32_t rc = many_staging(ctx, bytes, &slot);
+  if (rc) return rc;
+  // scratch: the expected CVs of the listed tiles, then of the listed spans, then their words in the same order
+  uint32_t *tile_cv = reinterpret_cast<uint32_t *>(d_scratch), *span_cv = tile_cv + p.tile_slots * 8, *tile_word = tile_cv + n_scr * 8,
+           *span_word = tile_word + p.tile_slots;
+  VrRow *h_rows = reinterpret_cast<VrRow *>(slot->h);
+  VrRange *h_ranges = reinterpret_cast<VrRange *>(h_rows + n_rows);
+  VrSmall *h_small = reinterpret_cast<VrSmall *>(h_ranges + n_ranges);
+  uint32_t *h_waves = reinterpret_cast<uint32_t *>(h_small + p.small.size());
+  auto row = [&](const UpdWg &w) {
+    VrRow r{};
+    const uint32_t f = w.file;
+    r.len = host_lens[f]; r.data = d_arena + host_offsets[f]; r.ob = d_outboards + host_ob_first[f]; r.root = d_roots + (uint64_t)f * 8;
+    r.unit_status = d_unit_status + host_unit_first[f];
+    r.idx = w.idx; r.gl = group_log;
+    memcpy(r.mask, w.mask, sizeof r.mask);
+    return r;
+  };
+  VrRow *at = h_rows;
+  for (const UpdWg &w : p.tiles) { VrRow r = row(w); r.want = tile_cv + w.out * 8; r.above = tile_word + w.out; *at++ = r; }
+  for (const UpdWg &w : p.spans) {
+    VrRow r = row(w);
+    r.want = span_cv + w.out * 8; r.above = span_word + w.out; r.out_cv = tile_cv + w.in * 8; r.out_word = tile_word + w.in;
+    *at++ = r;
+  }
+  for (const UpdWg &w : p.tops) { VrRow r = row(w); r.out_cv = span_cv + w.in * 8; r.out_word = span_word + w.in; *at++ = r; }
+  for (uint32_t i = 0; i < n_ranges; ++i) {
+    const uint64_t a = host_first_chunk[i], c = host_n_chunks[i];
+    h_ranges[i] = VrRange{d_unit_status + host_unit_first[host_files[i]], a >> group_log, c ? ((a + c - 1) >> group_log) - (a >> group_log) + 1 : 0};
+  }
+  uint32_t i_small = 0, i_waves = 0;
+  fill = 64;
+  for (uint32_t f : p.small) {
+    const uint64_t n = num_chunks(host_lens[f]);
+    if (fill + n > 64) { h_waves[i_waves++] = i_small; fill = 0; }
+    h_small[i_small++] = VrSmall{host_offsets[f], host_lens[f], d_outboards + host_ob_first[f], d_roots + (uint64_t)f * 8, d_unit_status + host_unit_first[f],
+                                 (uint32_t)fill, 0};
+    fill += n;
+  }
+  if (i_small) h_waves[i_waves] = i_small;
+  const hipError_t ec = hipMemcpyAsync(slot->d, slot->h, (size_t)bytes, hipMemcpyHostToDevice, st);
+  if (ec != hipSuccess) return hip_fail(ctx, ec, "bao verify ranges: table upload");
+  const VrRow *d_tiles = reinterpret_cast<const VrRow *>(slot->d), *d_spans = d_tiles + p.tiles.size(), *d_tops = d_spans + p.spans.size();
+  const VrRange *d_ranges = reinterpret_cast<const VrRange *>(d_tops + p.tops.size());
+  const VrSmall *d_small = reinterpret_cast<const VrSmall *>(d_ranges + n_ranges);
+  const uint32_t *d_waves = reinterpret_cast<const uint32_t *>(d_small + p.small.size());
+  const uint64_t U = B3W_TILE;
+  // top down: the storeys above the tiles first (stored nodes alone), then the kernels that read the files, then the ranges' reduction
+  if (i_small) hipLaunchKernelGGL(b3w_bao_verify_ranges_small_kernel, dim3((uint32_t)waves), dim3(64), 0, st, d_arena, d_small, d_waves, group_log);
+  if (!p.tops.empty()) hipLaunchKernelGGL(b3w_bao_verify_ranges_upper_kernel, dim3((uint32_t)p.tops.size()), dim3(256), 0, st, d_tops, U * U);
+  if (!p.spans.empty()) hipLaunchKernelGGL(b3w_bao_verify_ranges_upper_kernel, dim3((uint32_t)p.spans.size()), dim3(256), 0, st, d_spans, U);
+  if (!p.tiles.empty()) hipLaunchKernelGGL(b3w_bao_verify_ranges_tile_kernel, dim3((uint32_t)p.tiles.size()), dim3(B3W_TILE), 0, st, d_tiles);
+  hipLaunchKernelGGL(b3w_bao_verify_ranges_reduce_kernel, dim3(n_ranges), dim3(256), 0, st, d_ranges, d_range_status,
+                     reinterpret_cast<unsigned long long *>(d_range_first_bad));
+  const hipError_t e = hipGetLastError();
+  many_release(slot, st);
+  if (e != hipSuccess) return hip_fail(ctx, e, "bao verify ranges launch");
   return B3W_OK;
 }
 

@@ -980,6 +980,66 @@ int32_t b3w_bao_outboard_update(const uint8_t *data, uint64_t len, uint8_t *outb
                                 const uint64_t *host_first_chunk, const uint64_t *host_n_chunks, uint32_t n_ranges,
                                 uint32_t *root /* 8 u32 */);
 
+/* ---- verification of listed chunk ranges of resident files (still ABI 1.4: new names only) ----------------------------
+ * b3w_bao_verify_batch_device reads every byte of every file.  These calls make the cost of CHECKING follow the bytes of interest, as
+ * the update call does for writing: a provider that has served a 4 KiB read, a scrubber that takes a slice per pass, a repairer that
+ * re-checks what it has rewritten.  GIVEN the arena, outboards and roots as the update call takes them and a list of ranges
+ * (host_files[i], host_first_chunk[i], host_n_chunks[i]):
+ *   d_unit_status (packed as b3w_bao_verify_layout says, one byte a unit): the byte of every unit that holds a listed chunk is
+ *     afterwards the byte b3w_bao_verify_batch_device writes there for the same arena, outboards and roots — the same rules (3 header,
+ *     2 a stored node on the path or the root, 1 the unit's bytes, 0), the first that applies.  NO OTHER BYTE OF THE BUFFER IS WRITTEN,
+ *     so a scrubber can pass the same buffer to successive calls.  One exception: a listed file of at most 64 chunks is verified whole
+ *     and ALL its unit bytes are written, with the whole-file call's values.
+ *   d_range_status[i] (int32) and d_range_first_bad[i] (uint64, 8-byte aligned), in the order the ranges were given: the largest
+ *     status among the units range i touches, and the lowest unit index WITHIN THE FILE with a non-zero status among them, or
+ *     UINT64_MAX.  A range of 0 chunks gets 0 and UINT64_MAX.  None of the three outputs needs clearing.
+ *   WHAT IS READ.  A unit with a listed chunk is hashed whole.  Of a file of more than 64 chunks no arena byte outside its listed units
+ *     is read, the only stored nodes read are those with a listed unit below them (such a node is read whole), and the header is read
+ *     by one workgroup.  No byte of a file without a range is read.  Nothing of the arena, the outboards or the roots is written.
+ *   Ranges may be unsorted, overlapping or repeated: the host sorts and merges them for the walk.  n_ranges == 0: B3W_OK, nothing
+ *     launched.
+ * WHEN TO CALL b3w_bao_verify_batch_device INSTEAD (measured on an MI355X): a call that touches one tile is latency
+ * from end to end.  One 4 KiB range of a 1 GiB file: 0.10 ms against the whole-file call's 0.43; 64 scattered 4 KiB ranges: 0.13;
+ * 1 024: 0.23; 4 096 (a range in nearly every tile, 1.6 % of the chunks): 0.41, level with the whole-file call; EVERY chunk in one
+ * range: 0.59, 1.36 times the whole-file call.  4 096 listed files of 262 144 of 4 KiB: 0.13 ms against 1.57.  So: this call while
+ * the ranges leave tiles out or leave most chunks of the tiles they touch unlisted; the whole-file call when most of the file is
+ * listed (where exactly the two cross between 1.6 % and 100 % was not measured). */
+/* Host only.  Bytes of caller's scratch b3w_bao_verify_ranges_batch_device needs for these ranges: 36 (an expected CV and a word)
+ * per listed tile of 1 024 chunks of the files of more than one tile, plus 36 per listed span of 1 024 tiles of the files past 1 GiB,
+ * rounded up to 16; files of one tile (the files of at most 64 chunks among them) need none.  host_lens is indexed by host_files[i]
+ * (which is not checked here).  0 for a null pointer or no range. */
+uint64_t b3w_bao_verify_ranges_scratch_bytes(const uint64_t *host_lens, const uint32_t *host_files, const uint64_t *host_first_chunk,
+                                             const uint64_t *host_n_chunks, uint32_t n_ranges);
+/* host_ob_first (b3w_bao_batch_layout / b3w_bao_group_batch_layout) and host_unit_first (b3w_bao_verify_layout) are taken, not
+ * recomputed, and read at listed files only: the call's host work and its table grow with the ranges and the listed tiles and never
+ * with n_files.  d_roots: 8 u32 per file ON THE DEVICE.  d_scratch: 16-byte aligned, b3w_bao_verify_ranges_scratch_bytes.
+ * AT MOST FIVE LAUNCHES whatever the number of ranges, files or tiles: the listed files of at most 64 chunks; for files past 1 GiB a
+ * workgroup per file over its listed spans; a workgroup per span of 1 024 tiles that holds a listed tile (these two read stored nodes
+ * alone and leave, per listed tile, the CV it must have and whether the path above or the header is bad); a workgroup per listed
+ * tile; a workgroup per range that reduces the status bytes just written.  One table (208 bytes per workgroup of the middle three, 24
+ * per range, 48 per small file) goes through the staging ring of the many-calls above; nothing else is allocated, the host waits for
+ * nothing.
+ * REFUSALS ARE ATOMIC: every range is checked first, and a refused call launches nothing and writes nothing (B3W_E_BAD_ARGUMENT,
+ * b3w_last_error names the range): the update call's list (a null pointer — d_arena may be NULL where every listed file is empty —
+ * group_log above the maximum, a file index >= n_files, a range that reaches past its file's chunk count, a listed file that reaches
+ * past arena_bytes or has more than 2^30 chunks, d_outboards or an outboard offset off 8 bytes, a small, null or misaligned scratch),
+ * and a null output pointer, d_range_first_bad off 8 bytes or d_range_status off 4.  Any context.  Asynchronous on `stream`. */
+int32_t b3w_bao_verify_ranges_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets,
+                                           const uint64_t *host_lens, uint32_t n_files, uint32_t group_log,
+                                           const uint64_t *host_ob_first, const uint8_t *d_outboards, const uint32_t *d_roots,
+                                           const uint32_t *host_files, const uint64_t *host_first_chunk,
+                                           const uint64_t *host_n_chunks, uint32_t n_ranges, const uint64_t *host_unit_first,
+                                           uint8_t *d_unit_status, int32_t *d_range_status, uint64_t *d_range_first_bad, void *d_scratch,
+                                           uint64_t scratch_bytes, void *stream);
+/* Host only, one file in host memory, for callers without a GPU: the same sparse walk.  unit_status (room for the file's
+ * max(1, ceil(n_chunks / 2^group_log)) units) is written at the listed units only, whatever the file's size; range_status and
+ * range_first_bad (n_ranges entries each) may be NULL.  Only the listed units' bytes and the nodes with a listed unit below them are
+ * read; with no chunk listed nothing is read at all.  B3W_E_BAD_ARGUMENT, nothing written, for a null pointer, a group_log above
+ * the maximum or a range that reaches past the chunk count. */
+int32_t b3w_bao_verify_ranges(const uint8_t *data, uint64_t len, const uint8_t *outboard, uint32_t group_log, const uint32_t *root /* 8 u32 */,
+                              const uint64_t *host_first_chunk, const uint64_t *host_n_chunks, uint32_t n_ranges, uint8_t *unit_status,
+                              int32_t *range_status, uint64_t *range_first_bad);
+
 /* ---- resident files after appends and truncations (still ABI 1.4: new names only) -------------------------------------
  * The update call above follows writes that keep a file's length.  These calls follow a CHANGE of length.  In a pre-order outboard
  * the PLACE of every node can move when the length changes; the VALUES below a tile of 1 024 chunks that is full before and after
