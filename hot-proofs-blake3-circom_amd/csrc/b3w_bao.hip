@@ -928,6 +928,119 @@ __global__ __launch_bounds__(64) void b3w_sample_plan_slices_kernel(const uint8_
   }
 }
 
+// ---- slices taken in: the receiver's side ------------------------------------------------------------------------------
+// The mirror image of b3w_bao_slice_kernel<true>: the slice is verified as b3w_sample_plan_slices_kernel verifies it (no records), and
+// ONLY THEN its parts go to their places — the chunk's bytes into the file where it lies in the arena, the stored nodes of its path to
+// their pre-order places in the file's outboard (gl = 0: all P; gl > 0: the first U = path_len(c >> gl, n_groups), the walk of
+// b3w_bao_slice_group_kernel; the nodes inside the group are verified and dropped), the header in front.  K lanes a sample:
+//   1. the sample's lane 0 (the leader) hashes the chunk from the slice (chunk_cv: 16-byte loads, the slice's bytes lie on a 16-byte
+//      boundary); node j on lane j mod K against its half of node j - 1 (node 0 with ROOT against the root); one ballot; the leader's
+//      verdict to the sample's K lanes by shuffle.  The leader-only stretch keeps 64 / K lanes of the wave busy, so the host takes K = 4
+//      unless the batch's longest path is long enough to want sixteen lanes (b3w_bao_slice_ingest_device).
+//   2. a sample whose verdict is not 0 has written its status and ends here.  The others: quarter q of stored node j by lane
+//      (4 j + q) mod K, two 8-byte stores (an outboard's nodes lie 8 off a 16-byte boundary); then the chunk in 16-byte pieces, each
+//      loaded whole from the slice and stored at the width the DESTINATION is aligned to (put16), the ragged tail byte-wise.
+// Samples that name the same chunk, or share path nodes, store the same verified values to the same places.
+// desc: the arena calls' row, {chunk, the slice's byte offset in `slices`, length, outboard offset, file, the file's arena offset}.
+
+// 16 bytes from src (16-byte aligned) to dst at any alignment: the reverse of move16<true>.  The store width is the destination's natural
+// alignment, so that no store straddles its own width and none reaches outside the 16 bytes moved: one 16-byte store to a destination at
+// 0 modulo 16, two of 8 at 8, four of 4 at 4 and 12, single bytes to every other one.
+__device__ __forceinline__ void put16(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src) {
+  const uint4 v = *reinterpret_cast<const uint4 *>(src);
+  if (((uintptr_t)dst & 15) == 0) {
+    *reinterpret_cast<uint4 *>(dst) = v;
+  } else if (((uintptr_t)dst & 7) == 0) {
+    reinterpret_cast<uint2 *>(dst)[0] = make_uint2(v.x, v.y);
+    reinterpret_cast<uint2 *>(dst)[1] = make_uint2(v.z, v.w);
+  } else if (((uintptr_t)dst & 3) == 0) {
+    uint32_t *w = reinterpret_cast<uint32_t *>(dst);
+    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+  } else {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int k = 0; k < 16; ++k) dst[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+  }
+}
+
+template <int K>
+__global__ __launch_bounds__(64) void b3w_bao_slice_ingest_kernel(const uint8_t *__restrict__ slices, const uint32_t *__restrict__ roots,
+                                                                  const uint64_t *__restrict__ desc, uint32_t n_samples, uint32_t gl,
+                                                                  uint8_t *__restrict__ arena, uint8_t *__restrict__ obs, int32_t *__restrict__ status) {
+  const uint32_t lane = threadIdx.x, t = lane & (K - 1), base = lane - t;
+  const uint32_t s = blockIdx.x * (64u / K) + lane / K;
+  const bool valid = s < n_samples, leader = valid && t == 0;
+  const uint64_t *d = desc + 6 * (uint64_t)(valid ? s : 0);              // (lanes past the last sample read sample 0's row and write nothing)
+  const uint64_t c = d[0], len = d[2], n = len ? (len + 1023) / 1024 : 1;
+  const uint8_t *sl = slices + d[1];
+  const uint32_t *nodes = reinterpret_cast<const uint32_t *>(sl + 8);     // (16-byte aligned)
+  const uint32_t P = path_len(c, n);
+  const uint64_t off = c * 1024;
+  const uint32_t bytes = (uint32_t)(len - off < 1024 ? len - off : 1024);
+  const uint8_t *body = sl + 8 + 64 * (uint64_t)P;
+  // 1. the verdict
+  uint32_t h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (leader) chunk_cv(body, bytes, c, n == 1 ? 8u : 0u, h);
+  uint64_t lefts = 0;                                                     // the tree's own directions, root first (bit j: left at node j)
+  {
+    uint64_t cc = c, m = n;
+    for (uint32_t j = 0; j < P; ++j) {
+      uint64_t k2 = 1;
+      while (k2 * 2 < m) k2 *= 2;
+      if (cc < k2) { lefts |= 1ull << j; m = k2; } else { cc -= k2; m -= k2; }
+    }
+  }
+  const uint32_t *root8 = roots + d[4] * 8;
+  bool node_bad = false;
+  if (valid) {
+    for (uint32_t j = t; j < P; j += K) {
+      const uint4 *q = reinterpret_cast<const uint4 *>(nodes + j * 16);
+      const uint4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
+      const uint32_t mw[16] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w};
+      uint32_t ivv[8], o[8];
+      iv(ivv);
+      blake3_cv(ivv, mw, 0, 0, 64, 4u | (j == 0 ? 8u : 0u), o);
+      const uint32_t *want = j == 0 ? root8 : nodes + (j - 1) * 16 + (((lefts >> (j - 1)) & 1) ? 0 : 8);
+      if (!eq8(o, want)) node_bad = true;
+    }
+  }
+  const uint64_t bad_lanes = __ballot(node_bad);
+  int32_t st = 0;
+  if (leader) {
+    const uint32_t *want = P == 0 ? root8 : nodes + (P - 1) * 16 + (((lefts >> (P - 1)) & 1) ? 0 : 8);
+    const uint32_t *hd = reinterpret_cast<const uint32_t *>(sl);
+    if (((uint64_t)hd[0] | ((uint64_t)hd[1] << 32)) != len) st = 3;
+    else if ((bad_lanes >> base) & ((1ull << K) - 1)) st = 2;
+    else if (!eq8(h, want)) st = 1;                                       // (one chunk: its ROOT-flagged output against the root)
+    status[s] = st;
+  }
+  if (K > 1) st = __shfl(st, (int)base);
+  if (!valid || st != 0) return;                                          // nothing unverified is written
+  // 2. the places
+  uint8_t *ob = obs + d[3];
+  if (t == 0) *reinterpret_cast<uint2 *>(ob) = *reinterpret_cast<const uint2 *>(sl);          // the header (it is the length: just checked)
+  const uint64_t n_groups = (n + (1ull << gl) - 1) >> gl;
+  const uint32_t U = path_len(c >> gl, n_groups);                         // (gl = 0: P)
+  uint64_t p = 0, cc = c >> gl, m = n_groups;
+  for (uint32_t j = 0; j < U; ++j) {
+#pragma unroll
+    for (uint32_t q = 0; q < 4; ++q)
+      if (((j * 4 + q) & (K - 1)) == t) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(sl + 8 + 64 * (uint64_t)j + q * 16);
+        uint2 *node = reinterpret_cast<uint2 *>(ob + 8 + p * 64 + q * 16);
+        node[0] = make_uint2(v.x, v.y);
+        node[1] = make_uint2(v.z, v.w);
+      }
+    uint64_t k2 = 1;
+    while (k2 * 2 < m) k2 *= 2;
+    if (cc < k2) { p += 1; m = k2; } else { p += k2; cc -= k2; m -= k2; }
+  }
+  uint8_t *dst = arena + d[5] + off;
+  const uint32_t whole = bytes & ~15u;
+  for (uint32_t o = t * 16; o < whole; o += K * 16) put16(dst + o, body + o);
+  for (uint32_t o = whole + t; o < bytes; o += K) dst[o] = body[o];
+}
+
 // ---- verification: whole files against their outboards ---------------------------------------------------------------------
 // Bao's decoder applied to every UNIT of every file at once (a unit: a chunk, or with group outboards a group of 1 << gl chunks).  The
 // mirror image of the three batch kernels: where those store a node, these load the stored node from the same pre-order place, hold the
@@ -2743,6 +2856,85 @@ int32_t b3w_bao_slice_arena_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(ctx, e, "bao slice arena launch");
+  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
+  return B3W_OK;
+}
+
+// ---- slices taken in (still ABI 1.4: new names only) ------------------------------------------------------------------------
+int32_t b3w_bao_slice_ingest(const uint8_t *slice, uint64_t slice_len, uint64_t len, uint64_t chunk, const uint32_t *root, uint32_t group_log,
+                             uint8_t *data, uint8_t *outboard, int32_t *out_status) {
+  if (group_log > B3W_BAO_MAX_GROUP_LOG || !outboard || (!data && len)) return B3W_E_BAD_ARGUMENT;
+  int32_t st = 0;
+  const int32_t rc = b3w_bao_slice_decode(slice, slice_len, len, chunk, root, nullptr, nullptr, out_status ? &st : nullptr);   // (refuses the rest)
+  if (rc) return rc;
+  *out_status = st;
+  if (st) return B3W_OK;                                  // nothing unverified is written
+  const uint64_t n = num_chunks(len);
+  uint64_t idx[64];
+  uint32_t U = 0;
+  (void)b3w_bao_group_path_nodes(chunk, n, group_log, idx, &U);
+  memcpy(outboard, slice, 8);
+  for (uint32_t i = 0; i < U; ++i) memcpy(outboard + 8 + 64 * idx[i], slice + 8 + 64ull * i, 64);   // (the path's first U nodes are the stored ones)
+  const uint64_t bytes = slice_len - 8 - 64ull * path_len(chunk, n);
+  if (bytes) memcpy(data + chunk * 1024, slice + slice_len - bytes, bytes);
+  return B3W_OK;
+}
+
+int32_t b3w_bao_slice_ingest_device(b3w_ctx *ctx, uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
+                                    uint32_t n_files, uint32_t group_log, uint8_t *d_outboards, const uint32_t *d_roots, const uint32_t *host_files,
+                                    const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_slices, int32_t *d_sample_status, void *stream) {
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  if (group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "bao slice ingest: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
+  if (!n_samples) return B3W_OK;
+  if (!host_offsets || !host_lens || !d_outboards || !d_roots || !host_files || !host_chunks || !d_slices || !d_sample_status) {
+    ctx->last_error = "bao slice ingest: a null pointer"; return B3W_E_BAD_ARGUMENT;
+  }
+  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) { ctx->last_error = "bao slice ingest: d_outboards is not 8-byte or d_slices not 16-byte aligned"; return B3W_E_BAD_ARGUMENT; }
+  int32_t rc = arena_samples_ok(ctx, d_arena, arena_bytes, host_offsets, host_lens, n_files, host_files, host_chunks, n_samples);
+  if (rc) return rc;
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  // the arena calls' row (arena_table with slice offsets), filled here: the call is host work a sample before it is anything else, so the
+  // path's length is walked once a sample, with the split from a bit scan, and serves the slice's size and the batch's longest path
+  const uint64_t desc_bytes = (uint64_t)n_samples * 48;
+  rc = batch_staging(ctx, desc_bytes + ((uint64_t)n_files + 1) * 8);
+  if (rc) return rc;
+  uint64_t *desc = reinterpret_cast<uint64_t *>(ctx->h_batch), *ob_first = desc + 6 * (uint64_t)n_samples;
+  (void)b3w_bao_group_batch_layout(host_lens, n_files, group_log, ob_first);        // (group_log 0: b3w_bao_batch_layout's)
+  uint64_t at = slice_start(0);
+  uint32_t longest = 0;
+  for (uint32_t s = 0; s < n_samples; ++s) {
+    const uint32_t f = host_files[s];
+    const uint64_t len = host_lens[f], c = host_chunks[s], off = c * 1024;
+    uint32_t P = 0;
+    for (uint64_t cc = c, m = num_chunks(len); m > 1; ++P) {                        // path_len's walk
+      const uint64_t k2 = 1ull << (63 - __builtin_clzll(m - 1));                    // the largest power of two strictly below m
+      if (cc < k2) m = k2; else { cc -= k2; m -= k2; }
+    }
+    uint64_t *d = desc + 6 * (uint64_t)s;
+    d[0] = c; d[1] = at; d[2] = len; d[3] = ob_first[f]; d[4] = f; d[5] = host_offsets[f];
+    at = slice_start(at + 8 + 64ull * P + (len - off < 1024 ? len - off : 1024));   // (b3w_bao_slice_size)
+    if (P > longest) longest = P;
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)desc_bytes, hipMemcpyHostToDevice, st));
+  // lanes a sample, from the batch's longest path P: node j is checked by lane j mod K, ceil(P / K) rounds beside the chunk's sixteen blocks,
+  // and every lane fewer a sample is a leader more a wave in the stretch only leaders run.  Measured at P = 20: four lanes
+  // (five rounds) beat sixteen (two) at 4 096 and at 65 536 slices, so four up to six rounds; sixteen for the longer paths (files past
+  // 16 GiB; not measured).  B3W_SLICE_INGEST_LANES=1 / 4 / 16: measurements
+  const char *env = getenv("B3W_SLICE_INGEST_LANES");
+  const int lanes = env ? atoi(env) : (longest <= 24 ? 4 : 16);
+  const uint64_t *d_desc = reinterpret_cast<const uint64_t *>(ctx->d_batch);
+  if (lanes == 1)
+    hipLaunchKernelGGL(b3w_bao_slice_ingest_kernel<1>, dim3((n_samples + 63) / 64), dim3(64), 0, st, d_slices, d_roots, d_desc, n_samples, group_log, d_arena,
+                       d_outboards, d_sample_status);
+  else if (lanes == 4)
+    hipLaunchKernelGGL(b3w_bao_slice_ingest_kernel<4>, dim3((n_samples + 15) / 16), dim3(64), 0, st, d_slices, d_roots, d_desc, n_samples, group_log, d_arena,
+                       d_outboards, d_sample_status);
+  else
+    hipLaunchKernelGGL(b3w_bao_slice_ingest_kernel<16>, dim3((n_samples + 3) / 4), dim3(64), 0, st, d_slices, d_roots, d_desc, n_samples, group_log, d_arena,
+                       d_outboards, d_sample_status);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(ctx, e, "bao slice ingest launch");
   HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
   return B3W_OK;
 }

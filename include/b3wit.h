@@ -922,6 +922,44 @@ int32_t b3w_bao_slice_arena_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_
                                    const uint32_t *host_files, const uint64_t *host_chunks, uint32_t n_samples, uint8_t *d_slices,
                                    void *stream);
 
+/* ---- slices taken in: the receiver's side (still ABI 1.4: new names only) --------------------------------------------
+ * A party that holds only a file's ROOT and is sent chunks with their paths — fetching a sparse file, repairing the units a ranged
+ * verification marked bad, following a remote read.  b3w_bao_slice_ingest_device is the mirror image of b3w_bao_slice_arena_device and
+ * takes its arguments the same way: the files are [host_offsets[f], + host_lens[f]) of d_arena at any byte offset, d_outboards (8-byte
+ * aligned) is packed as b3w_bao_batch_layout (group_log 0) / b3w_bao_group_batch_layout (1 .. 6) says, d_slices (16-byte aligned) holds
+ * the samples' slices packed as b3w_bao_slice_batch_layout says, d_roots 8 u32 per file ON THE DEVICE.  d_arena, d_outboards and
+ * d_slices must not overlap (not checked).
+ *   d_sample_status[s]: the four codes and the precedence of b3w_bao_slice_decode / b3w_sample_plan_slices_device — 3 the header is not
+ *   the length, 2 a path node or the root fails, 1 the chunk's bytes fail (a one-chunk file's wrong root is 1), else 0.
+ *   NOTHING UNVERIFIED IS WRITTEN: a sample writes only after its whole slice has verified against the root; one with a non-zero status
+ *   writes its status and nothing else.  A verified sample writes exactly (a) the chunk's min(1024, len - 1024 c) bytes at d_arena +
+ *   offset[f] + 1024 c, no byte in front of or behind them (stores as wide as the destination is aligned: 16 / 8 / 4 / 1 bytes, the ragged
+ *   tail byte-wise), (b) the STORED nodes of its path at their pre-order places in file f's outboard — group_log 0: all of them;
+ *   group_log > 0: the first b3w_bao_group_path_nodes of them, the nodes inside the group are verified and dropped — and (c) the 8-byte
+ *   header.  An empty file's slice is its header: checked against the root of the empty input and written.
+ *   Samples may repeat, come in any order and share path nodes: every writer of a byte that writes at all writes the same verified
+ *   value, so a good and a bad slice of one chunk in one call leave the good one's bytes.  Once every chunk of a file has come in
+ *   its outboard is the provider's byte for byte (b3w_bao_outboard_batch_device / b3w_bao_group_outboard_batch_device), from the traffic
+ *   itself, and every other call here applies to it.  The caller keeps track of which chunks have arrived (d_sample_status).
+ * One launch; the per-sample table (48 bytes a sample) goes through the context's staging and nothing else is allocated; the host waits
+ * for nothing but this context's previous batch call.  B3W_E_BAD_ARGUMENT before anything is written for what
+ * b3w_bao_slice_arena_device refuses and for a null d_roots / d_sample_status.  n_samples == 0: a no-op.  Any context.  Asynchronous on
+ * `stream`.
+ * When not to (MI355X): the call costs about 23 ns a slice, host loop included — 4 096 slices of a 1 GiB file 0.18 ms,
+ * 65 536 1.52 ms, every chunk (1 048 576) 23.7 ms for 2.27 times the file's bytes in slices — where hashing the whole resident GiB
+ * takes 0.43 ms (b3w_bao_outboard_batch_device, then compare the root) or 0.45 (b3w_bao_verify_batch_device against an outboard sent
+ * once).  So: slices for the sparse fetch, the repair and the remote read, up to a few per cent of a file's chunks; a file that
+ * arrives whole goes through the b3w_bao_stream_verify_* session or the batch calls on its bytes alone. */
+int32_t b3w_bao_slice_ingest_device(b3w_ctx *ctx, uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets,
+                                    const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, uint8_t *d_outboards,
+                                    const uint32_t *d_roots, const uint32_t *host_files, const uint64_t *host_chunks,
+                                    uint32_t n_samples, const uint8_t *d_slices, int32_t *d_sample_status, void *stream);
+/* Host only: the same verdict and the same writes for ONE slice — `data` is the file (len bytes), `outboard` its (group) outboard.
+ * B3W_E_BAD_ARGUMENT for what b3w_bao_slice_decode refuses, a group_log above the maximum and a null pointer; data may be NULL only for
+ * an empty file. */
+int32_t b3w_bao_slice_ingest(const uint8_t *slice, uint64_t slice_len, uint64_t preimage_len, uint64_t chunk, const uint32_t *root /* 8 u32 */,
+                             uint32_t group_log, uint8_t *data, uint8_t *outboard, int32_t *out_status);
+
 /* ---- updates in place after writes to resident files (still ABI 1.4: new names only) --------------------------------
  * Every call above treats a file as immutable: after one rewritten block the only way to a correct outboard and root is the batch
  * call over the whole file again.  These calls make the cost follow the bytes written.  GIVEN an arena with its offsets and
