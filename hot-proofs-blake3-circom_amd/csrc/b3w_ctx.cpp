@@ -200,18 +200,35 @@ bool build_exact_table(const CircuitDesc &c, std::vector<uint32_t> &table) {
       const uint32_t slot = run.slot + j;
       if (slot >= c.nwit) return false;
       if (run.kind == 'W') table[slot] = (run.atom + j) | (0xFFFFu << 16);
-      else table[slot] = run.atom | ((run.bit0 + j) << 16);
+      // The only bit slots the layouts give chunk_idx_low are down_left_path's Num2Bits(65).out[0..31]: bits of chunk_idx = low +
+      // high * 2^32.  The batch kernels' canonical records cannot tell the two apart; a chunk_idx_high that wraps mod p can.
+      else table[slot] = (run.atom == B3W_A_NV + NV_CIL ? B3W_A_NV + NV_CHUNK_IDX : run.atom) | ((run.bit0 + j) << 16);
     }
   }
   return true;
 }
 
-// the reference WASM's own trace for this assert site, if it was tabulated (tools/probe_traces.py)
-const char *reference_trace(int circuit, uint32_t site) {
+// The reference WASM's own trace for this assert site: tabulated (tools/probe_traces.py), or, for add1 (Bits34) in rounds 1..6,
+// composed from the first-round trace of the same (G, half).  Template instances are shared by all seven rounds, so only the frame
+// of Blake3Compression differs: rounds[0] is started at its own line (194 standalone, 195 nova), rounds[i + 1] from the loop
+// (207 / 208).  No other site is reachable behind round 0: a round's outputs are 32-bit words.
+bool reference_trace(int circuit, uint32_t site, std::string &text) {
   static const b3w_trace_entry *const T[4] = {B3W_TRACES_0, B3W_TRACES_1, B3W_TRACES_2, B3W_TRACES_3};
   static const uint32_t N[4] = {B3W_TRACES_0_N, B3W_TRACES_1_N, B3W_TRACES_2_N, B3W_TRACES_3_N};
-  for (uint32_t i = 0; i < N[circuit]; i++) if (T[circuit][i].site == site) return T[circuit][i].text;
-  return nullptr;
+  const uint32_t code = site & 0xFF, r = (site >> 8) & 0xF;
+  const bool later = code == 1 && r >= 1 && r <= 6;
+  const uint32_t key = later ? site & ~0xF00u : site;
+  for (uint32_t i = 0; i < N[circuit]; i++) {
+    if (T[circuit][i].site != key) continue;
+    text = T[circuit][i].text;
+    if (!later) return true;
+    const std::string frame = "Error in template Blake3Compression_";
+    const size_t at = text.find(frame), num = at == std::string::npos ? at : text.find(" line: ", at), end = num == std::string::npos ? num : text.find('\n', num);
+    if (end == std::string::npos) return false;
+    text.replace(num + 7, end - (num + 7), circuit == 0 ? "207" : "208");
+    return true;
+  }
+  return false;
 }
 
 // VERIFY mode: record word j of a witness is read back from slot in_slots[j] of its body (the slot the
@@ -696,8 +713,8 @@ static int32_t calc_witness_run(b3w_ctx *ctx, const std::vector<uint32_t> &rec, 
   uint32_t st2[2] = {0, 0};
   HIP_TRY(ctx, hipMemcpy(st2, ctx->d_status2, 8, hipMemcpyDeviceToHost));
   if (st2[0] != 0) {
-    const char *ref = reference_trace(ctx->circuit, st2[1]);
-    ctx->last_error = ref ? std::string(ref) : std::string("Assert Failed.\n") + assert_site_text(st2[1], msg, sizeof msg);
+    if (!reference_trace(ctx->circuit, st2[1], ctx->last_error))
+      ctx->last_error = std::string("Assert Failed.\n") + assert_site_text(st2[1], msg, sizeof msg);
     return B3W_E_ASSERT_FAILED;
   }
   HIP_TRY(ctx, hipMemcpy(out_body, ctx->d_body1, (size_t)d.nwit * 32, hipMemcpyDeviceToHost));

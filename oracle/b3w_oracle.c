@@ -328,6 +328,10 @@ int b3wo_load_layout(int circuit, const char *path) {
     if (line[0] == 'W' && sscanf(line + 1, "%d %d %d", &s, &a, &len) == 3) {
       for (int j = 0; j < len; j++) { if (s + j >= c->nwit) goto bad; sa[s + j] = a + j; sb[s + j] = -1; }
     } else if (line[0] == 'B' && sscanf(line + 1, "%d %d %d %d", &s, &a, &b0, &len) == 4) {
+      /* The only bit slots the layouts give chunk_idx_low are down_left_path's Num2Bits(65).out[0..31] (blake3_nova.circom:57-59):
+       * bits of chunk_idx = low + high * 2^32.  The two agree whenever high * 2^32 does not wrap mod p, which is all the
+       * fingerprinting saw; with high = 5 / 2^32 and low = 7 the WASM holds the bits of 12 (tests/golden/assert_sites.json.gz). */
+      if (a == A_NV + NV_CIL) a = A_NV + NV_CHUNK_IDX;
       for (int j = 0; j < len; j++) { if (s + j >= c->nwit) goto bad; sa[s + j] = a; sb[s + j] = (int16_t)(b0 + j); }
     }
   }

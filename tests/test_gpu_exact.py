@@ -4,6 +4,7 @@ import random
 import numpy as np
 import pytest
 import b3w_testlib as T
+import assert_site_cases as A
 
 pytestmark = pytest.mark.gpu
 
@@ -56,13 +57,15 @@ def _wild_inputs(circuit, n, seed):
     return out
 
 
+@pytest.mark.parametrize("seed", [77, 1077, 2077])
 @pytest.mark.parametrize("circuit", T.CIRCUITS)
-def test_exact_kernel_matches_oracle_on_wild_inputs(circuit):
+def test_exact_kernel_matches_oracle_on_wild_inputs(circuit, seed):
     m = T.pkg()
     wc = m.builder(circuit)
+    texts = A.known_texts(T, circuit)
     nok = nrej = 0
-    for inp in _wild_inputs(circuit, 160, 77):
-        rc, want, _ = T.oracle_witness(circuit, T.normalize_input(circuit, inp))
+    for inp in _wild_inputs(circuit, 160, seed):
+        rc, want, err = T.oracle_witness(circuit, T.normalize_input(circuit, inp))
         if rc == 0:
             got = wc.calculateBinWitness(inp, 0)
             assert np.array_equal(got, want), inp
@@ -71,5 +74,7 @@ def test_exact_kernel_matches_oracle_on_wild_inputs(circuit):
             with pytest.raises(m.B3WError, match="Assert Failed") as e:
                 wc.calculateBinWitness(inp, 0)
             assert e.value.status == m.B3W_E_ASSERT_FAILED
+            site = A.oracle_site(rc, err)
+            assert str(e.value) == A.expected_text(circuit, texts, site), (site, inp)      # WHICH assert: the WASM's text for the oracle's site
             nrej += 1
     assert nok >= 50 and nrej >= 10, (nok, nrej)
