@@ -1,5 +1,6 @@
 // b3w_commit_api.cpp — C-ABI part 5: commitment keys and the commit entry points (on-device consumer #2) over b3w_commit.hip.
 #include "b3w_internal.h"
+#include "b3w_commit_arith.h"      // make_curve and the two moduli
 
 
 struct b3w_commit_key {
@@ -21,37 +22,6 @@ struct b3w_commit_key {
   bool counting = false;
 };
 
-namespace {
-// 256-bit helpers for the curve constants (host, little-endian u32 limbs)
-bool u256_geq(const uint32_t a[8], const uint32_t b[8]) { for (int i = 7; i >= 0; --i) if (a[i] != b[i]) return a[i] > b[i]; return true; }
-void u256_sub_host(uint32_t a[8], const uint32_t b[8]) {
-  uint64_t br = 0;
-  for (int i = 0; i < 8; i++) { const uint64_t t = (uint64_t)a[i] - b[i] - br; a[i] = (uint32_t)t; br = (t >> 63) & 1; }
-}
-void u256_double_mod(uint32_t a[8], const uint32_t p[8]) {            // a = 2a mod p (a < p < 2^255)
-  uint32_t c = 0;
-  for (int i = 0; i < 8; i++) { const uint32_t n = (a[i] << 1) | c; c = a[i] >> 31; a[i] = n; }
-  if (c || u256_geq(a, p)) u256_sub_host(a, p);
-}
-B3wCurve make_curve(const uint64_t p64[4]) {
-  B3wCurve C{};
-  memcpy(C.p, p64, 32);
-  uint32_t x[8] = {1, 0, 0, 0, 0, 0, 0, 0};
-  for (int i = 0; i < 256; i++) u256_double_mod(x, C.p);
-  memcpy(C.one, x, 32);
-  for (int i = 0; i < 256; i++) u256_double_mod(x, C.p);
-  memcpy(C.r2, x, 32);
-  memcpy(C.pm2, C.p, 32);
-  const uint32_t two[8] = {2, 0, 0, 0, 0, 0, 0, 0};
-  u256_sub_host(C.pm2, two);
-  uint32_t inv = C.p[0];                                             // Newton: inv = p^-1 mod 2^32
-  for (int i = 0; i < 5; i++) inv *= 2u - C.p[0] * inv;
-  C.inv = 0u - inv;
-  return C;
-}
-const uint64_t Q_BN254[4] = {0x3c208c16d87cfd47ull, 0x97816a916871ca8dull, 0xb85045b68181585dull, 0x30644e72e131a029ull};
-const uint64_t P_VESTA_BASE[4] = {0x992d30ed00000001ull, 0x224698fc094cf91bull, 0x0ull, 0x4000000000000000ull};
-}  // namespace
 
 extern "C" {
 

@@ -85,14 +85,7 @@ extern "C" int b3w_place_store_rate(uint8_t *buf, uint64_t pitch, uint32_t n, ui
 #define B3W_COMMIT_WINDOW_OK(w) ((w) == B3W_COMMIT_WINDOW_SMALL || (w) == B3W_COMMIT_WINDOW_LARGE || (w) == B3W_COMMIT_WINDOW_XL)
 #define B3W_COMMIT_ENTRIES(W) ((1u << (W)) - 1u)
 #define B3W_COMMIT_SUM_WORDS 36        // per witness between the commit and the normalise kernel: X, Y, ZZ, ZZZ in nine 29-bit limbs each
-// Field of the curve's coordinates:
-struct B3wCurve {
-  uint32_t p[8];      // modulus, little-endian limbs
-  uint32_t r2[8];     // 2^512 mod p   (into Montgomery form)
-  uint32_t one[8];    // 2^256 mod p   (1 in Montgomery form)
-  uint32_t pm2[8];    // p - 2         (Fermat inversion exponent)
-  uint32_t inv;       // -p^-1 mod 2^32
-};
+#include "b3w_commit_curve.h"          // B3wCurve: the field of the curve's coordinates (shared with the HIP-free arithmetic header)
 extern "C" int b3w_launch_commit_setup(const uint32_t *d_gens, const uint32_t *d_first_v, const uint32_t *d_nbits, uint32_t nslots,
                                        uint32_t *d_points, const B3wCurve *curve, hipStream_t stream);
 extern "C" int b3w_launch_commit_windows(const uint32_t *d_points, uint32_t nwin, uint32_t window, uint32_t *d_table, const B3wCurve *curve, hipStream_t stream);
