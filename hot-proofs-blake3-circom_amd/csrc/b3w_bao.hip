@@ -37,6 +37,17 @@
 //   b3w_bao_stream_open_*    a file whose length is known only at finish: full tiles hashed into tile-local blocks of a staging area, and
 //                            the blocks moved to their pre-order places once the length is known ("open-length sessions")
 //                            (b3w_bao_stream_open_relocate_many_kernel: the blocks of many sessions moved in one grid)
+//
+// The routes (batch table, one streamed file by value, a table of sessions, update / ranges / resize rows) differ only in where a file's
+// entry comes from.  Each kernel, or its *_body wrapper, finds its entry and calls one of the bodies every route shares:
+//   put_cv, header_is, find_first, preorder_pos (host and device), node_pos / node_at       the small pieces
+//   lane_chunk_cv / tile_chunk_cvs      a lane's chunk, a tile's chunks, hashed into LDS
+//   tree_levels                         the level loop over a tree in LDS; merge_in_lds and verify_in_lds hand it their work on a pair
+//                                       (update_in_lds and ranges_in_lds keep the loop written out: it measured slower for them)
+//   tile_outboard, merge_storey         a tile's outboard and the storey above the tiles (batch, stream, many)
+//   verify_tile, verify_upper           the same two storeys of verification (batch, stream, many)
+//   small_lane, small_levels, small_verify   the packed wave of files of at most 64 chunks (outboards, verify, ranged verify)
+//   block_piece, move_piece, block_cv   the relocation of a full tile's block (open sessions, many sessions, resize)
 #include "b3w_internal.h"
 #include "b3w_blake3_dev.h"
 
@@ -248,27 +259,49 @@ __global__ __launch_bounds__(256) void b3w_bao_emit_kernel(const uint32_t *__res
 constexpr uint32_t B3W_TILE = 1024;                      // chunks per tile = items per merge group
 struct BatchEnt { uint64_t off, len, ob; uint32_t first, file; };   // tile launches: arena offset; merge launches: first input CV slot
 
-// pre-order position, relative to the root of a tree over `total` chunks, of its node over chunks [a, a + size)
-__device__ __forceinline__ uint64_t preorder_pos(uint64_t total, uint64_t a, uint64_t size) {
+// pre-order position, relative to the root of a tree over `total` chunks, of its node over chunks [a, a + size); the host walks use it too
+__host__ __device__ __forceinline__ uint64_t preorder_pos(uint64_t total, uint64_t a, uint64_t size) {
   uint64_t p = 0, lo = 0, cnt = total;
   while (cnt > 1 && !(lo == a && cnt == size)) {
+#ifdef __HIP_DEVICE_COMPILE__
     const uint64_t k = 1ull << (63 - __clzll((long long)(cnt - 1)));
+#else
+    uint64_t k = 1;
+    while (k * 2 < cnt) k *= 2;
+#endif
     if (a < lo + k) { p += 1; cnt = k; } else { p += k; lo += k; cnt -= k; }
   }
   return p;
 }
 
-// the entry whose workgroups include wg: the last one with first <= wg
-__device__ __forceinline__ BatchEnt batch_ent(const BatchEnt *__restrict__ ents, uint32_t n_ents, uint32_t wg) {
-  uint32_t lo = 0, hi = n_ents;
+// the last row of rows[lo .. hi) whose `first` is at or before x (rows sorted by first, rows[lo].first <= x): the entry whose workgroups
+// include workgroup x, or the small file whose lanes include lane x
+template <class Row>
+__device__ __forceinline__ uint32_t find_first(const Row *__restrict__ rows, uint32_t lo, uint32_t hi, uint32_t x) {
   while (hi - lo > 1) {
     const uint32_t mid = (lo + hi) / 2;
-    if (ents[mid].first <= wg) lo = mid; else hi = mid;
+    if (rows[mid].first <= x) lo = mid; else hi = mid;
   }
-  return ents[lo];
+  return lo;
 }
 
-// The barrier of the kernels that do not store every node.  In the group instantiation of the tile kernel the compiler (ROCm 7's clang) left
+__device__ __forceinline__ BatchEnt batch_ent(const BatchEnt *__restrict__ ents, uint32_t n_ents, uint32_t wg) {
+  return ents[find_first(ents, 0, n_ents, wg)];
+}
+
+// the CV h to slot i of an LDS array of CVs
+__device__ __forceinline__ void put_cv(uint32_t *cv, uint32_t i, const uint32_t h[8]) {
+  reinterpret_cast<uint4 *>(cv + i * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
+  reinterpret_cast<uint4 *>(cv + i * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
+}
+
+// whether the header of the outboard at ob is `len`
+__device__ __forceinline__ bool header_is(const uint8_t *ob, uint64_t len) {
+  const uint32_t *h = reinterpret_cast<const uint32_t *>(ob);
+  return ((uint64_t)h[0] | ((uint64_t)h[1] << 32)) == len;
+}
+
+// The barrier of the walks that do not store every node (tree_levels and small_levels with WAIT, the planners' group merges).  In the group instantiation of the tile kernel the compiler (ROCm 7's clang) left
 // the level loop's s_barrier without a wait for the LDS stores of the level before (it keeps the wait in the instantiation that stores
 // every node), and a 64-chunk subtree's CV now and then came out wrong: the wait is spelled out.
 __device__ __forceinline__ void lds_barrier() {
@@ -292,58 +325,95 @@ __device__ __forceinline__ void merge_pair(uint32_t *cv, uint32_t i0, uint32_t i
   m[8] = r0.x; m[9] = r0.y; m[10] = r0.z; m[11] = r0.w; m[12] = r1.x; m[13] = r1.y; m[14] = r1.z; m[15] = r1.w;
   iv(ivv);
   blake3_cv(ivv, m, 0, 0, 64, d, o);
-  reinterpret_cast<uint4 *>(cv + i0 * 8)[0] = make_uint4(o[0], o[1], o[2], o[3]);          // (slot i0 is read by this thread alone at this level)
-  reinterpret_cast<uint4 *>(cv + i0 * 8)[1] = make_uint4(o[4], o[5], o[6], o[7]);
+  put_cv(cv, i0, o);                                                 // (slot i0 is read by this thread alone at this level)
 }
 
-// cv: cnt items of `unit` chunks each (the last one maybe fewer) of a tree over `total` chunks whose nodes go to `nodes` (its root's place).
-// Leaves the tree's CV in cv[0 .. 8) (ROOT-flagged where `root` says so); ends with a barrier.
-// GRP: `nodes` is the root's place in the file's GROUP outboard (groups of 1 << gl chunks; the tree starts at a multiple of that): a node
-// over at most a group's chunks is not stored, the others go to their pre-order places in the tree over the groups.
-template <int BS, bool GRP>
-__device__ __forceinline__ void merge_in_lds(uint32_t *cv, uint32_t cnt, uint64_t unit, uint64_t total, uint8_t *__restrict__ nodes, bool root,
-                                             uint32_t gl) {
+// pre-order position of the node over chunks [a, a + size) of a tree over `total` chunks.  GRP: in the GROUP outboard (groups of 1 << gl
+// chunks; a is a multiple of that), which is the tree over the file's groups; gl = 0 is the full outboard.
+template <bool GRP>
+__device__ __forceinline__ uint64_t node_pos(uint64_t total, uint64_t a, uint64_t size, uint32_t gl) {
+  if (!GRP) return preorder_pos(total, a, size);
+  const uint64_t G1 = (1ull << gl) - 1;
+  return preorder_pos((total + G1) >> gl, a >> gl, (size + G1) >> gl);
+}
+// that node's place where `nodes` is the root's.  GRP: null for a node over at most a group's chunks, which is computed and not stored.
+template <bool GRP>
+__device__ __forceinline__ uint8_t *node_at(uint8_t *__restrict__ nodes, uint64_t total, uint64_t a, uint64_t size, uint32_t gl) {
+  if (!GRP) return nodes + preorder_pos(total, a, size) * 64;
+  const uint64_t G1 = (1ull << gl) - 1;
+  return size > G1 + 1 ? nodes + preorder_pos((total + G1) >> gl, a >> gl, (size + G1) >> gl) * 64 : nullptr;
+}
+
+// The level loop of the dense walks over a tree in LDS (merge, verify): cnt items of `unit` chunks each (the last one
+// maybe fewer) of a tree over `total` chunks, item i in slot i.  At level l thread j takes the pairs of slots i0 = (2 j) << l and
+// i1 = i0 + (1 << l) and hands pair(l, i0, i1, a, size, d) the node over chunks [a, a + size) with d = PARENT [| ROOT on the top pair where
+// `root` says so]; the pair's work leaves the node's CV in slot i0.  A barrier before every level and one behind the last.
+// WAIT: the barriers are lds_barrier().  Every walk that does not store every node takes it (the group outboards and all of verify, as
+// do the sparse walks below); the merge into a full outboard keeps __syncthreads(), behind which the compiler does wait.
+// The sparse walks (update_in_lds, ranges_in_lds) keep this loop written out, with their skip test in front of the pair's span: through
+// tree_levels the update and the ranged verify of 4 096 scattered blocks of a 1 GiB file took 3.5 % longer (profiles/r21/bao_shared_bodies_ab.json).
+template <int BS, bool WAIT, class Pair>
+__device__ __forceinline__ void tree_levels(uint32_t cnt, uint64_t unit, uint64_t total, bool root, Pair pair) {
   for (uint32_t l = 0; (1u << l) < cnt; ++l) {
-    if (GRP) lds_barrier(); else __syncthreads();
+    if (WAIT) lds_barrier(); else __syncthreads();
     const bool top = (2u << l) >= cnt;
     for (uint32_t j = threadIdx.x;; j += BS) {
       const uint32_t i0 = (2 * j) << l, i1 = i0 + (1u << l);
       if (i1 >= cnt) break;
       const uint64_t a = i0 * unit, e = (uint64_t)(i0 + (2u << l)) * unit, size = (e < total ? e : total) - a;
-      uint8_t *node;
-      if (GRP) {
-        const uint64_t G1 = (1ull << gl) - 1;
-        node = size > G1 + 1 ? nodes + preorder_pos((total + G1) >> gl, a >> gl, (size + G1) >> gl) * 64 : nullptr;
-      } else {
-        node = nodes + preorder_pos(total, a, size) * 64;
-      }
-      merge_pair<GRP>(cv, i0, i1, node, 4u | (top && root ? 8u : 0u));
+      pair(l, i0, i1, a, size, 4u | (top && root ? 8u : 0u));
     }
   }
-  if (GRP) lds_barrier(); else __syncthreads();
+  if (WAIT) lds_barrier(); else __syncthreads();
+}
+
+// cv: the items of a tree whose nodes go to `nodes` (its root's place; GRP: in the file's group outboard, the tree starts at a multiple
+// of the group size).  Leaves the tree's CV in cv[0 .. 8); ends with a barrier.
+template <int BS, bool GRP>
+__device__ __forceinline__ void merge_in_lds(uint32_t *cv, uint32_t cnt, uint64_t unit, uint64_t total, uint8_t *__restrict__ nodes, bool root,
+                                             uint32_t gl) {
+  tree_levels<BS, GRP>(cnt, unit, total, root, [&](uint32_t, uint32_t i0, uint32_t i1, uint64_t a, uint64_t size, uint32_t d) {
+    merge_pair<GRP>(cv, i0, i1, node_at<GRP>(nodes, total, a, size, gl), d);
+  });
+}
+
+// this lane's chunk c of a file of len bytes and n chunks, its bytes at base + 1024 at: its CV to the lane's slot.  lone: the file may be
+// a single chunk, whose CV carries ROOT (it is the hash itself); no file of more than 64 chunks is, the small and the streamed ones may be.
+__device__ __forceinline__ void lane_chunk_cv(uint32_t *cv, const uint8_t *__restrict__ base, uint64_t at, uint64_t len, uint64_t n, uint64_t c, bool lone) {
+  const uint64_t off = c * 1024;
+  uint32_t h[8];
+  chunk_cv(base + at * 1024, (uint32_t)(len - off < 1024 ? len - off : 1024), c, lone && n == 1 ? 8u : 0u, h);
+  put_cv(cv, threadIdx.x, h);
+}
+// lane = chunk: the CVs of the m chunks from a0 on of a file of n chunks into slots [0, m); the tile's bytes start at base + 1024 at (the
+// file's first byte and a0, or a window and the tile's place in it)
+__device__ __forceinline__ void tile_chunk_cvs(uint32_t *cv, const uint8_t *__restrict__ base, uint64_t at, uint64_t len, uint64_t n, uint64_t a0, uint32_t m,
+                                               bool lone) {
+  if (threadIdx.x < m) lane_chunk_cv(cv, base, at + threadIdx.x, len, n, a0 + threadIdx.x, lone);
+}
+
+// A tile's outboard: the tile of chunks from a0 (its bytes at base + 1024 at) of a file of len bytes and n chunks whose outboard starts
+// at ob.  lone: lane_chunk_cv's.  The tile's CV goes to tile_cv, or (a file of this one tile) the root to `root`.  The batch, stream and
+// many-session kernels find their file's entry and call this.
+template <bool GRP>
+__device__ __forceinline__ void tile_outboard(const uint8_t *__restrict__ base, uint64_t at, uint64_t len, uint64_t n, uint64_t a0, bool lone,
+                                              uint8_t *__restrict__ ob, uint32_t *root, uint32_t *tile_cv, uint32_t gl) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
+  const uint32_t m = (uint32_t)(n - a0 < B3W_TILE ? n - a0 : B3W_TILE);
+  const bool sole = n <= B3W_TILE;
+  tile_chunk_cvs(cv, base, at, len, n, a0, m, lone);
+  if (a0 == 0 && threadIdx.x == 0) *reinterpret_cast<uint2 *>(ob) = make_uint2((uint32_t)len, (uint32_t)(len >> 32));
+  merge_in_lds<B3W_TILE, GRP>(cv, m, 1, m, ob + 8 + node_pos<GRP>(n, a0, m, gl) * 64, sole, gl);   // (a tile starts at a multiple of every group size)
+  if (threadIdx.x < 8) (sole ? root : tile_cv)[threadIdx.x] = cv[threadIdx.x];
 }
 
 template <bool GRP>
 __device__ __forceinline__ void tile_body(const uint8_t *__restrict__ arena, const BatchEnt *__restrict__ ents, uint32_t n_ents,
                                           uint8_t *__restrict__ outboards, uint32_t *__restrict__ roots, uint32_t *__restrict__ tile_cv, uint32_t gl) {
-  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
   const BatchEnt e = batch_ent(ents, n_ents, blockIdx.x);
-  const uint64_t n = (e.len + 1023) / 1024;                           // (more than 64 chunks)
   const uint64_t a0 = (uint64_t)(blockIdx.x - e.first) * B3W_TILE;
-  const uint32_t m = (uint32_t)(n - a0 < B3W_TILE ? n - a0 : B3W_TILE);
-  const bool sole = n <= B3W_TILE;
-  if (threadIdx.x < m) {
-    const uint64_t c = a0 + threadIdx.x, off = c * 1024;
-    uint32_t h[8];
-    chunk_cv(arena + e.off + off, (uint32_t)(e.len - off < 1024 ? e.len - off : 1024), c, 0, h);
-    reinterpret_cast<uint4 *>(cv + threadIdx.x * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
-    reinterpret_cast<uint4 *>(cv + threadIdx.x * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
-  }
-  uint8_t *ob = outboards + e.ob;
-  if (a0 == 0 && threadIdx.x == 0) *reinterpret_cast<uint2 *>(ob) = make_uint2((uint32_t)e.len, (uint32_t)(e.len >> 32));
-  const uint64_t G1 = GRP ? (1ull << gl) - 1 : 0;                     // (a tile starts at a multiple of every group size)
-  merge_in_lds<B3W_TILE, GRP>(cv, m, 1, m, ob + 8 + (GRP ? preorder_pos((n + G1) >> gl, a0 >> gl, (m + G1) >> gl) : preorder_pos(n, a0, m)) * 64, sole, gl);
-  if (threadIdx.x < 8) (sole ? roots + (uint64_t)e.file * 8 : tile_cv + (uint64_t)blockIdx.x * 8)[threadIdx.x] = cv[threadIdx.x];
+  tile_outboard<GRP>(arena + e.off, a0, e.len, (e.len + 1023) / 1024, a0, false, outboards + e.ob, roots + (uint64_t)e.file * 8,   // (more than 64 chunks)
+                     tile_cv + (uint64_t)blockIdx.x * 8, gl);
 }
 
 __global__ __launch_bounds__(B3W_TILE) void b3w_bao_tile_kernel(const uint8_t *__restrict__ arena, const BatchEnt *__restrict__ ents, uint32_t n_ents,
@@ -358,49 +428,51 @@ __global__ __launch_bounds__(B3W_TILE) void b3w_bao_tile_group_kernel(const uint
   tile_body<true>(arena, ents, n_ents, outboards, roots, tile_cv, gl);
 }
 
-// Files of at most 64 chunks, several to a wave: wave w takes the files [wave_first[w], wave_first[w + 1]) of `ents`, which have at most 64
-// chunks together; ents[f].first = the lane of file f's chunk 0.  lane = chunk, every lane busy where the files fill the wave (a wave a
-// file would leave 60 of 64 lanes idle on 4 KiB files, and idle lanes cost the same issue cycles).  The same in-place merge, each file
-// in its own run of slots: at level l the lane of a chunk index that is a multiple of 2 << l merges with the slot 1 << l further on.
+// Files of at most 64 chunks, several to a wave: wave w takes the files [wave_first[w], wave_first[w + 1]) of `rows`, which have at most 64
+// chunks together; rows[f].first = the lane of file f's chunk 0.  lane = chunk, every lane busy where the files fill the wave (a wave a
+// file would leave 60 of 64 lanes idle on 4 KiB files, and idle lanes cost the same issue cycles).
+// This lane's file (Row: BatchEnt or VrSmall), the file's chunk count n, the lane's chunk i of it, and whether the file has such a chunk
+// (the lanes behind the last file's chunks do not); a live lane's chunk CV goes to slot `lane` of cv.
+template <class Row>
+struct SmallLane { Row e; uint32_t n, i; bool live; };
+template <class Row>
+__device__ __forceinline__ SmallLane<Row> small_lane(uint32_t *cv, const uint8_t *__restrict__ arena, const Row *__restrict__ rows,
+                                                     const uint32_t *__restrict__ wave_first) {
+  const uint32_t lane = threadIdx.x;
+  SmallLane<Row> s;
+  s.e = rows[find_first(rows, wave_first[blockIdx.x], wave_first[blockIdx.x + 1], lane)];
+  s.n = s.e.len ? (uint32_t)((s.e.len + 1023) / 1024) : 1;
+  s.i = lane - s.e.first;
+  s.live = s.i < s.n;
+  if (s.live) lane_chunk_cv(cv, arena + s.e.off, s.i, s.e.len, s.n, s.i, true);
+  return s;
+}
+// The in-place merge with each file in its own run of slots: at level l the lane of a chunk index that is a multiple of 2 << l takes the
+// slot 1 << l further on, and pair(l, size, d) gets the node over the file's chunks [i, i + size).  Barriers as in tree_levels.
+template <bool WAIT, class Pair>
+__device__ __forceinline__ void small_levels(uint32_t n, uint32_t i, bool live, Pair pair) {
+  for (uint32_t l = 0; l < 6; ++l) {
+    if (WAIT) lds_barrier(); else __syncthreads();
+    if (!__any(live && (1u << l) < n)) break;                         // (uniform: the workgroup is this one wave)
+    if (live && (i & ((2u << l) - 1)) == 0 && i + (1u << l) < n)
+      pair(l, n - i < (2u << l) ? n - i : (2u << l), 4u | (i == 0 && (2u << l) >= n ? 8u : 0u));
+  }
+  if (WAIT) lds_barrier(); else __syncthreads();
+}
+
 template <bool GRP>
 __device__ __forceinline__ void small_body(const uint8_t *__restrict__ arena, const BatchEnt *__restrict__ ents, const uint32_t *__restrict__ wave_first,
                                            uint8_t *__restrict__ outboards, uint32_t *__restrict__ roots, uint32_t gl) {
   __shared__ __attribute__((aligned(16))) uint32_t cv[64 * 8];
   const uint32_t lane = threadIdx.x;
-  uint32_t lo = wave_first[blockIdx.x], hi = wave_first[blockIdx.x + 1];
-  while (hi - lo > 1) {                                               // this lane's file: the last one that starts at or before the lane
-    const uint32_t mid = (lo + hi) / 2;
-    if (ents[mid].first <= lane) lo = mid; else hi = mid;
-  }
-  const BatchEnt e = ents[lo];
-  const uint32_t n = e.len ? (uint32_t)((e.len + 1023) / 1024) : 1, i = lane - e.first;
-  const bool live = i < n;                                            // (the lanes behind the last file's chunks are not)
-  if (live) {
-    const uint32_t off = i * 1024;
-    uint32_t h[8];
-    chunk_cv(arena + e.off + off, (uint32_t)(e.len - off < 1024 ? e.len - off : 1024), i, n == 1 ? 8u : 0u, h);
-    reinterpret_cast<uint4 *>(cv + lane * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
-    reinterpret_cast<uint4 *>(cv + lane * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
-  }
+  const SmallLane<BatchEnt> s = small_lane(cv, arena, ents, wave_first);
+  const BatchEnt &e = s.e;
   uint8_t *ob = outboards + e.ob;
-  if (live && i == 0) *reinterpret_cast<uint2 *>(ob) = make_uint2((uint32_t)e.len, (uint32_t)(e.len >> 32));
-  for (uint32_t l = 0; l < 6; ++l) {
-    if (GRP) lds_barrier(); else __syncthreads();
-    if (!__any(live && (1u << l) < n)) break;                         // (uniform: the workgroup is this one wave)
-    if (live && (i & ((2u << l) - 1)) == 0 && i + (1u << l) < n) {
-      const uint32_t size = n - i < (2u << l) ? n - i : (2u << l);
-      uint8_t *node;
-      if (GRP) {                                                      // (size > a group: i is a multiple of the group size)
-        const uint32_t G1 = (1u << gl) - 1;
-        node = size > G1 + 1 ? ob + 8 + preorder_pos((n + G1) >> gl, i >> gl, (size + G1) >> gl) * 64 : nullptr;
-      } else {
-        node = ob + 8 + preorder_pos(n, i, size) * 64;
-      }
-      merge_pair<GRP>(cv, lane, lane + (1u << l), node, 4u | (i == 0 && (2u << l) >= n ? 8u : 0u));
-    }
-  }
-  if (GRP) lds_barrier(); else __syncthreads();
-  if (live && i == 0) {
+  if (s.live && s.i == 0) *reinterpret_cast<uint2 *>(ob) = make_uint2((uint32_t)e.len, (uint32_t)(e.len >> 32));
+  small_levels<GRP>(s.n, s.i, s.live, [&](uint32_t l, uint32_t size, uint32_t d) {   // (GRP, size > a group: i is a multiple of the group size)
+    merge_pair<GRP>(cv, lane, lane + (1u << l), node_at<GRP>(ob + 8, s.n, s.i, size, gl), d);
+  });
+  if (s.live && s.i == 0) {
 #pragma unroll
     for (int k = 0; k < 8; ++k) roots[(uint64_t)e.file * 8 + k] = cv[lane * 8 + k];
   }
@@ -418,23 +490,30 @@ __global__ __launch_bounds__(64) void b3w_bao_small_group_kernel(const uint8_t *
   small_body<true>(arena, ents, wave_first, outboards, roots, gl);
 }
 
-// unit = chunks per input item (B3W_TILE, or B3W_TILE^2 for the launch over the groups' CVs); input item i of the file: in_cv slot e.off + i
+// The merge storey: workgroup g of a file of n chunks (more than one tile) merges up to 1 024 items of `unit` chunks each (B3W_TILE, or
+// B3W_TILE^2 for the launch over the groups' CVs), whose CVs lie from `in` on; its CV goes to out_cv, or (the file's top) the root to `root`.
 template <bool GRP>
-__device__ __forceinline__ void merge_body(const BatchEnt *__restrict__ ents, uint32_t n_ents, uint64_t unit, const uint32_t *__restrict__ in_cv,
-                                           uint32_t *__restrict__ out_cv, uint8_t *__restrict__ outboards, uint32_t *__restrict__ roots, uint32_t gl) {
+__device__ __forceinline__ void merge_storey(uint64_t n, uint64_t g, uint64_t unit, const uint32_t *__restrict__ in, uint8_t *__restrict__ ob,
+                                             uint32_t *root, uint32_t *out_cv, uint32_t gl) {
   __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
-  const BatchEnt e = batch_ent(ents, n_ents, blockIdx.x);
-  const uint64_t n = (e.len + 1023) / 1024;                           // (more than one tile)
-  const uint64_t g = blockIdx.x - e.first, span = unit * B3W_TILE, a0 = g * span;
+  const uint64_t span = unit * B3W_TILE, a0 = g * span;
   const uint64_t tot = n - a0 < span ? n - a0 : span;
   const uint32_t cnt = (uint32_t)((tot + unit - 1) / unit);
   const bool sole = n <= span;
-  const uint4 *src = reinterpret_cast<const uint4 *>(in_cv + (e.off + g * B3W_TILE) * 8);
+  const uint4 *src = reinterpret_cast<const uint4 *>(in);
   for (uint32_t i = threadIdx.x; i < cnt * 2; i += 256) reinterpret_cast<uint4 *>(cv)[i] = src[i];
-  const uint64_t G1 = GRP ? (1ull << gl) - 1 : 0;                     // (every node here is over more than a tile: all of them are stored)
-  merge_in_lds<256, GRP>(cv, cnt, unit, tot, outboards + e.ob + 8 + (GRP ? preorder_pos((n + G1) >> gl, a0 >> gl, (tot + G1) >> gl) : preorder_pos(n, a0, tot)) * 64,
-                         sole, gl);
-  if (threadIdx.x < 8) (sole ? roots + (uint64_t)e.file * 8 : out_cv + (uint64_t)blockIdx.x * 8)[threadIdx.x] = cv[threadIdx.x];
+  merge_in_lds<256, GRP>(cv, cnt, unit, tot, ob + 8 + node_pos<GRP>(n, a0, tot, gl) * 64, sole, gl);   // (every node here is over more than a tile: all are stored)
+  if (threadIdx.x < 8) (sole ? root : out_cv)[threadIdx.x] = cv[threadIdx.x];
+}
+
+// input item i of the file: in_cv slot e.off + i
+template <bool GRP>
+__device__ __forceinline__ void merge_body(const BatchEnt *__restrict__ ents, uint32_t n_ents, uint64_t unit, const uint32_t *__restrict__ in_cv,
+                                           uint32_t *__restrict__ out_cv, uint8_t *__restrict__ outboards, uint32_t *__restrict__ roots, uint32_t gl) {
+  const BatchEnt e = batch_ent(ents, n_ents, blockIdx.x);
+  const uint64_t n = (e.len + 1023) / 1024, g = blockIdx.x - e.first;
+  merge_storey<GRP>(n, g, unit, in_cv + (e.off + g * B3W_TILE) * 8, outboards + e.ob, roots + (uint64_t)e.file * 8,
+                    out_cv + (uint64_t)blockIdx.x * 8, gl);
 }
 
 __global__ __launch_bounds__(256) void b3w_bao_merge_kernel(const BatchEnt *__restrict__ ents, uint32_t n_ents, uint64_t unit,
@@ -1094,8 +1173,7 @@ __device__ __forceinline__ void check_pair(uint32_t *cv, uint32_t *flags, uint32
   } else if (!eq8(cv + i1 * 8, m + 8)) flags[i1] |= 1u << l;
   iv(ivv);
   blake3_cv(ivv, m, 0, 0, 64, d, o);
-  reinterpret_cast<uint4 *>(cv + i0 * 8)[0] = make_uint4(o[0], o[1], o[2], o[3]);          // (slot i0 is this thread's alone at this level)
-  reinterpret_cast<uint4 *>(cv + i0 * 8)[1] = make_uint4(o[4], o[5], o[6], o[7]);
+  put_cv(cv, i0, o);                                                 // (slot i0 is this thread's alone at this level)
 }
 
 // merge_in_lds with the stores turned into checks: cnt items of `unit` chunks of a tree over `total` chunks whose root's place in the
@@ -1104,21 +1182,12 @@ __device__ __forceinline__ void check_pair(uint32_t *cv, uint32_t *flags, uint32
 template <int BS, bool CLAIM>
 __device__ __forceinline__ void verify_in_lds(uint32_t *cv, uint32_t *flags, uint32_t cnt, uint64_t unit, uint64_t total,
                                               const uint8_t *__restrict__ nodes, bool root, uint32_t gl, uint32_t *__restrict__ exp_out) {
-  const uint64_t G = 1ull << gl, G1 = G - 1, leaf = CLAIM ? G : unit;
-  for (uint32_t l = 0; (1u << l) < cnt; ++l) {
-    lds_barrier();
-    const bool top = (2u << l) >= cnt;
-    for (uint32_t j = threadIdx.x;; j += BS) {
-      const uint32_t i0 = (2 * j) << l, i1 = i0 + (1u << l);
-      if (i1 >= cnt) break;
-      const uint64_t a = i0 * unit, e = (uint64_t)(i0 + (2u << l)) * unit, size = (e < total ? e : total) - a;
-      const uint32_t d = 4u | (top && root ? 8u : 0u);
-      if (CLAIM && size <= G) { merge_pair<true>(cv, i0, i1, nullptr, d); continue; }          // inside a group: computed
-      const uint64_t sl = ((uint64_t)unit) << l;
-      check_pair<CLAIM>(cv, flags, i0, i1, l, nodes + preorder_pos((total + G1) >> gl, a >> gl, (size + G1) >> gl) * 64, d, sl, size - sl, leaf, exp_out);
-    }
-  }
-  lds_barrier();
+  const uint64_t G = 1ull << gl, leaf = CLAIM ? G : unit;
+  tree_levels<BS, true>(cnt, unit, total, root, [&](uint32_t l, uint32_t i0, uint32_t i1, uint64_t a, uint64_t size, uint32_t d) {
+    if (CLAIM && size <= G) { merge_pair<true>(cv, i0, i1, nullptr, d); return; }               // inside a group: computed
+    const uint64_t sl = ((uint64_t)unit) << l;
+    check_pair<CLAIM>(cv, flags, i0, i1, l, nodes + node_pos<true>(total, a, size, gl) * 64, d, sl, size - sl, leaf, exp_out);
+  });
 }
 
 // the OR of the node flags on item t's path
@@ -1129,282 +1198,71 @@ __device__ __forceinline__ bool path_bad(const uint32_t *flags, uint32_t t) {
   return x != 0;
 }
 
-// unit = chunks per item (B3W_TILE: the items are tiles; B3W_TILE^2, the launch for files past 1 GiB, which runs first: groups of tiles).
-// Scratch entries: exp_cv 8 words and bad 1 word per entry; the tiles' entries first (n_tile_ents of them), then the groups'.
+// The storey above the tiles of one file (len bytes, more than one tile, its outboard at ob): workgroup g takes up to 1 024 items of `unit`
+// chunks each (B3W_TILE: the items are tiles; B3W_TILE^2, the launch for files past 1 GiB, which runs first: groups of tiles).
+// Scratch entries: an expected CV of 8 words and a "path above is bad" word.  exp_in / bad_in: the workgroup's own entry, left by the
+// launch before (unused by the file's top workgroup, which takes `root`); exp_out / bad_out: the entry of its first item.
+__device__ __forceinline__ void verify_upper(uint64_t len, uint64_t g, uint64_t unit, const uint8_t *__restrict__ ob, const uint32_t *root,
+                                             const uint32_t *exp_in, const uint32_t *bad_in, uint32_t *exp_out, uint32_t *bad_out, uint32_t gl,
+                                             int32_t *file_status, unsigned long long *first_bad) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
+  __shared__ uint32_t flags[B3W_TILE];
+  const uint64_t n = (len + 1023) / 1024;
+  const uint64_t span = unit * B3W_TILE, a0 = g * span;
+  const uint64_t tot = n - a0 < span ? n - a0 : span;
+  const uint32_t cnt = (uint32_t)((tot + unit - 1) / unit);
+  const bool sole = n <= span;                                        // the file's top workgroup
+  const uint32_t *want = sole ? root : exp_in;
+  bool above = sole ? false : *bad_in != 0;
+  if (sole && threadIdx.x == 0) {                                     // (the tile kernel, which runs after this one, adds to these)
+    const bool hdr = !header_is(ob, len);
+    *file_status = hdr ? 3 : 0;
+    *first_bad = hdr ? 0ull : ~0ull;
+  }
+  if (cnt == 1) {                                                     // a lone last tile (or group) hangs straight off the storey above
+    if (threadIdx.x < 8) exp_out[threadIdx.x] = want[threadIdx.x];
+    if (threadIdx.x == 0) *bad_out = above;
+    return;
+  }
+  for (uint32_t i = threadIdx.x; i < cnt; i += 256) flags[i] = 0;
+  verify_in_lds<256, false>(cv, flags, cnt, unit, tot, ob + 8 + node_pos<true>(n, a0, tot, gl) * 64, sole, gl, exp_out);
+  above = above || !eq8(cv, want);
+  for (uint32_t t = threadIdx.x; t < cnt; t += 256) bad_out[t] = above || path_bad(flags, t);
+}
+
+// Scratch entries: the tiles' first (n_tile_ents of them), then the groups'.
 __global__ __launch_bounds__(256) void b3w_bao_verify_upper_kernel(const BatchEnt *__restrict__ ents, uint32_t n_ents, uint64_t unit,
                                                                    const VerFile *__restrict__ vf, uint64_t n_tile_ents,
                                                                    const uint8_t *__restrict__ outboards, const uint32_t *__restrict__ roots,
                                                                    uint32_t *__restrict__ exp_cv, uint32_t *__restrict__ bad, uint32_t gl,
                                                                    int32_t *__restrict__ file_status, unsigned long long *__restrict__ first_bad) {
-  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
-  __shared__ uint32_t flags[B3W_TILE];
   const BatchEnt e = batch_ent(ents, n_ents, blockIdx.x);
   const VerFile v = vf[e.file];
-  const uint64_t n = (e.len + 1023) / 1024;                           // (more than one tile)
-  const uint64_t g = blockIdx.x - e.first, span = unit * B3W_TILE, a0 = g * span;
-  const uint64_t tot = n - a0 < span ? n - a0 : span;
-  const uint32_t cnt = (uint32_t)((tot + unit - 1) / unit);
-  const bool sole = n <= span;                                        // the file's top workgroup
+  const uint64_t g = blockIdx.x - e.first;
   const uint64_t out0 = unit == B3W_TILE ? v.slot + g * B3W_TILE : n_tile_ents + v.gslot, in = n_tile_ents + v.gslot + g;
-  const uint32_t *want = sole ? roots + (uint64_t)e.file * 8 : exp_cv + in * 8;
-  bool above = sole ? false : bad[in] != 0;
-  const uint32_t *ob = reinterpret_cast<const uint32_t *>(outboards + e.ob);
-  if (sole && threadIdx.x == 0) {                                     // (the tile kernel, which runs after this one, adds to these)
-    const bool hdr = ((uint64_t)ob[0] | ((uint64_t)ob[1] << 32)) != e.len;
-    file_status[e.file] = hdr ? 3 : 0;
-    first_bad[e.file] = hdr ? 0ull : ~0ull;
-  }
-  if (cnt == 1) {                                                     // a lone last tile (or group) hangs straight off the storey above
-    if (threadIdx.x < 8) exp_cv[out0 * 8 + threadIdx.x] = want[threadIdx.x];
-    if (threadIdx.x == 0) bad[out0] = above;
-    return;
-  }
-  for (uint32_t i = threadIdx.x; i < cnt; i += 256) flags[i] = 0;
-  const uint64_t G1 = (1ull << gl) - 1;
-  verify_in_lds<256, false>(cv, flags, cnt, unit, tot, outboards + e.ob + 8 + preorder_pos((n + G1) >> gl, a0 >> gl, (tot + G1) >> gl) * 64, sole, gl,
-                            exp_cv + out0 * 8);
-  above = above || !eq8(cv, want);
-  for (uint32_t t = threadIdx.x; t < cnt; t += 256) bad[out0 + t] = above || path_bad(flags, t);
+  verify_upper(e.len, g, unit, outboards + e.ob, roots + (uint64_t)e.file * 8, exp_cv + in * 8, bad + in, exp_cv + out0 * 8, bad + out0, gl,
+               file_status + e.file, first_bad + e.file);
 }
 
-__global__ __launch_bounds__(B3W_TILE) void b3w_bao_verify_tile_kernel(const uint8_t *__restrict__ arena, const BatchEnt *__restrict__ ents, uint32_t n_ents,
-                                                                       const VerFile *__restrict__ vf, const uint8_t *__restrict__ outboards,
-                                                                       const uint32_t *__restrict__ roots, const uint32_t *__restrict__ exp_cv,
-                                                                       const uint32_t *__restrict__ bad, uint32_t gl, uint8_t *__restrict__ unit_status,
-                                                                       int32_t *__restrict__ file_status, unsigned long long *__restrict__ first_bad) {
+// One tile against the file's outboard: the tile of chunks from a0 (its bytes at base + 1024 at) of a file of len bytes and n chunks.  exp / bad:
+// the tile's scratch entry from the storey above (unused by a file of this one tile, which takes `root`); unit_status: the status byte of
+// the file's unit 0; lone: lane_chunk_cv's.  The per-file outputs by reduction (one-tile file) or atomicMax / atomicMin (others).
+__device__ __forceinline__ void verify_tile(const uint8_t *__restrict__ base, uint64_t at, uint64_t len, uint64_t n, uint64_t a0, bool lone,
+                                            const uint8_t *__restrict__ ob, const uint32_t *root, const uint32_t *exp, const uint32_t *bad,
+                                            uint32_t gl, uint8_t *unit_status, int32_t *file_status, unsigned long long *first_bad) {
   __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
   __shared__ uint32_t flags[B3W_TILE];
   __shared__ uint32_t worst, first;
-  const BatchEnt e = batch_ent(ents, n_ents, blockIdx.x);
-  const VerFile v = vf[e.file];
-  const uint64_t n = (e.len + 1023) / 1024;                           // (more than 64 chunks)
-  const uint32_t tile = blockIdx.x - e.first, t = threadIdx.x, G = 1u << gl;
-  const uint64_t a0 = (uint64_t)tile * B3W_TILE;
-  const uint32_t m = (uint32_t)(n - a0 < B3W_TILE ? n - a0 : B3W_TILE);
-  const bool sole = n <= B3W_TILE;
-  if (t < m) {
-    const uint64_t c = a0 + t, off = c * 1024;
-    uint32_t h[8];
-    chunk_cv(arena + e.off + off, (uint32_t)(e.len - off < 1024 ? e.len - off : 1024), c, 0, h);
-    reinterpret_cast<uint4 *>(cv + t * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
-    reinterpret_cast<uint4 *>(cv + t * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
-  }
-  flags[t] = 0;
-  if (t == 0) { worst = 0; first = ~0u; }
-  const uint32_t *ob = reinterpret_cast<const uint32_t *>(outboards + e.ob);
-  const bool hdr = ((uint64_t)ob[0] | ((uint64_t)ob[1] << 32)) != e.len;
-  const uint64_t G1 = G - 1;
-  verify_in_lds<B3W_TILE, true>(cv, flags, m, 1, m, outboards + e.ob + 8 + preorder_pos((n + G1) >> gl, a0 >> gl, (m + G1) >> gl) * 64, sole, gl, nullptr);
-  const uint64_t ent = v.slot + tile;
-  if (t == 0 && !eq8(cv, sole ? roots + (uint64_t)e.file * 8 : exp_cv + ent * 8)) flags[0] |= m <= G ? VER_UNIT : VER_TOP;
-  const bool above = sole ? false : bad[ent] != 0;
-  lds_barrier();
-  if (t < m && (t & (G - 1)) == 0) {                                  // a unit's first chunk: its status
-    const uint32_t st = hdr ? 3u : above || path_bad(flags, t) ? 2u : (flags[t] & VER_UNIT) ? 1u : 0u;
-    unit_status[v.ufirst + ((a0 + t) >> gl)] = (uint8_t)st;
-    if (st) { atomicMax(&worst, st); atomicMin(&first, t >> gl); }    // (LDS; a clean tile issues none)
-  }
-  __syncthreads();
-  if (t != 0) return;
-  if (sole) {
-    file_status[e.file] = (int32_t)worst;
-    first_bad[e.file] = worst ? (unsigned long long)first : ~0ull;
-  } else if (worst) {                                                 // (initialised by the file's top workgroup of the storey above)
-    atomicMax(file_status + e.file, (int32_t)worst);
-    atomicMin(first_bad + e.file, (unsigned long long)((a0 >> gl) + first));
-  }
-}
-
-// small_body's wave packing: lane = chunk, each file in its own run of lanes, every stored node of a file checked by the lane that would
-// have stored it; the per-file outputs from ballots over the file's lanes
-__global__ __launch_bounds__(64) void b3w_bao_verify_small_kernel(const uint8_t *__restrict__ arena, const BatchEnt *__restrict__ ents,
-                                                                  const uint32_t *__restrict__ wave_first, const VerFile *__restrict__ vf,
-                                                                  const uint8_t *__restrict__ outboards, const uint32_t *__restrict__ roots, uint32_t gl,
-                                                                  uint8_t *__restrict__ unit_status, int32_t *__restrict__ file_status,
-                                                                  unsigned long long *__restrict__ first_bad) {
-  __shared__ __attribute__((aligned(16))) uint32_t cv[64 * 8];
-  __shared__ uint32_t flags[64];
-  const uint32_t lane = threadIdx.x, G = 1u << gl;
-  uint32_t lo = wave_first[blockIdx.x], hi = wave_first[blockIdx.x + 1];
-  while (hi - lo > 1) {                                               // this lane's file: the last one that starts at or before the lane
-    const uint32_t mid = (lo + hi) / 2;
-    if (ents[mid].first <= lane) lo = mid; else hi = mid;
-  }
-  const BatchEnt e = ents[lo];
-  const uint32_t n = e.len ? (uint32_t)((e.len + 1023) / 1024) : 1, i = lane - e.first;
-  const bool live = i < n;                                            // (the lanes behind the last file's chunks are not)
-  if (live) {
-    const uint32_t off = i * 1024;
-    uint32_t h[8];
-    chunk_cv(arena + e.off + off, (uint32_t)(e.len - off < 1024 ? e.len - off : 1024), i, n == 1 ? 8u : 0u, h);
-    reinterpret_cast<uint4 *>(cv + lane * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
-    reinterpret_cast<uint4 *>(cv + lane * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
-  }
-  flags[lane] = 0;
-  const uint8_t *ob = outboards + e.ob;
-  const bool hdr = ((uint64_t)reinterpret_cast<const uint32_t *>(ob)[0] | ((uint64_t)reinterpret_cast<const uint32_t *>(ob)[1] << 32)) != e.len;
-  for (uint32_t l = 0; l < 6; ++l) {
-    lds_barrier();
-    if (!__any(live && (1u << l) < n)) break;                         // (uniform: the workgroup is this one wave)
-    if (live && (i & ((2u << l) - 1)) == 0 && i + (1u << l) < n) {
-      const uint32_t size = n - i < (2u << l) ? n - i : (2u << l), d = 4u | (i == 0 && (2u << l) >= n ? 8u : 0u);
-      if (size <= G) merge_pair<true>(cv, lane, lane + (1u << l), nullptr, d);
-      else check_pair<true>(cv, flags, lane, lane + (1u << l), l, ob + 8 + preorder_pos((n + G - 1) >> gl, i >> gl, (size + G - 1) >> gl) * 64, d,
-                            1u << l, size - (1u << l), G, nullptr);
-    }
-  }
-  lds_barrier();
-  // the file's top (its ROOT-flagged CV, or what its stored root node hashes to with ROOT) against the root; bit 6: above every level here
-  if (live && i == 0 && !eq8(cv + lane * 8, roots + (uint64_t)e.file * 8)) flags[lane] |= n <= G ? VER_UNIT : 1u << 6;
-  lds_barrier();
-  const bool is_unit = live && (i & (G - 1)) == 0;
-  uint32_t st = 0;
-  if (is_unit) {
-    uint32_t x = 0;
-#pragma unroll
-    for (uint32_t l = 0; l <= 6; ++l) x |= flags[e.first + ((i >> l) << l)] & (1u << l);
-    st = hdr ? 3u : x ? 2u : (flags[lane] & VER_UNIT) ? 1u : 0u;
-    unit_status[vf[e.file].ufirst + (i >> gl)] = (uint8_t)st;
-  }
-  const uint64_t mine = (n == 64 ? ~0ull : (1ull << n) - 1) << e.first;
-  const uint64_t b1 = __ballot(st >= 1) & mine, b2 = __ballot(st >= 2) & mine, b3 = __ballot(st >= 3) & mine;
-  if (live && i == 0) {
-    file_status[e.file] = b3 ? 3 : b2 ? 2 : b1 ? 1 : 0;
-    first_bad[e.file] = b1 ? (unsigned long long)((__ffsll((unsigned long long)b1) - 1 - e.first) >> gl) : ~0ull;
-  }
-}
-
-// ---- streamed files: one file of known length whose bytes arrive in windows of whole tiles -------------------------------------
-// A tile is a subtree of the file's tree whatever else is known of the file, and the place of every node below its root follows from
-// the file's length and the tile's ABSOLUTE index alone.  So the kernels of a window are the tile kernels with the file's entry by value
-// (no table in device memory: a push uploads nothing) and the tile's bytes taken from the window, not from arena + offset:
-//   b3w_bao_stream_tile[_group]_kernel   a workgroup per tile of the window: tile_body's work, the tile's CV to scratch slot `tile`.
-//                                        A file of one tile, down to one chunk (ROOT on the chunk) or no byte at all, ends here too:
-//                                        its root and header, the bytes the small kernel writes for it
-//   b3w_bao_stream_merge[_group]_kernel  finish: merge_body over the tile CVs in scratch (files past 1 GiB: once more over the groups')
-//   b3w_bao_stream_upper_kernel          verification, at begin: the upper kernel's work for the one file, from the stored nodes alone
-//   b3w_bao_stream_verify_kernel         a workgroup per tile of the window: the verify tile kernel's work, exp_cv / bad read at `tile`
-// The merge and verify bodies (merge_in_lds, verify_in_lds) are the batch kernels' own, lds_barrier() around their level loops included.
-__device__ __forceinline__ void stream_chunk_cv(uint32_t *cv, const uint8_t *__restrict__ window, uint64_t len, uint64_t n, uint64_t a0, uint32_t m) {
-  if (threadIdx.x < m) {
-    const uint64_t c = a0 + threadIdx.x, off = c * 1024;
-    uint32_t h[8];
-    chunk_cv(window + ((uint64_t)blockIdx.x * B3W_TILE + threadIdx.x) * 1024, (uint32_t)(len - off < 1024 ? len - off : 1024), c, n == 1 ? 8u : 0u, h);
-    reinterpret_cast<uint4 *>(cv + threadIdx.x * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
-    reinterpret_cast<uint4 *>(cv + threadIdx.x * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
-  }
-}
-
-// window: the bytes of the file from tile `tile0` on; workgroup w takes tile tile0 + w
-template <bool GRP>
-__device__ __forceinline__ void stream_tile_body(const uint8_t *__restrict__ window, uint64_t len, uint32_t tile0, uint8_t *__restrict__ ob,
-                                                 uint32_t *__restrict__ root, uint32_t *__restrict__ tile_cv, uint32_t gl) {
-  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
-  const uint64_t n = len ? (len + 1023) / 1024 : 1;
-  const uint64_t tile = (uint64_t)tile0 + blockIdx.x, a0 = tile * B3W_TILE;
-  const uint32_t m = (uint32_t)(n - a0 < B3W_TILE ? n - a0 : B3W_TILE);
-  const bool sole = n <= B3W_TILE;
-  stream_chunk_cv(cv, window, len, n, a0, m);
-  if (a0 == 0 && threadIdx.x == 0) *reinterpret_cast<uint2 *>(ob) = make_uint2((uint32_t)len, (uint32_t)(len >> 32));
-  const uint64_t G1 = GRP ? (1ull << gl) - 1 : 0;                     // (a tile starts at a multiple of every group size)
-  merge_in_lds<B3W_TILE, GRP>(cv, m, 1, m, ob + 8 + (GRP ? preorder_pos((n + G1) >> gl, a0 >> gl, (m + G1) >> gl) : preorder_pos(n, a0, m)) * 64, sole, gl);
-  if (threadIdx.x < 8) (sole ? root : tile_cv + tile * 8)[threadIdx.x] = cv[threadIdx.x];
-}
-
-__global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_tile_kernel(const uint8_t *__restrict__ window, uint64_t len, uint32_t tile0,
-                                                                       uint8_t *__restrict__ ob, uint32_t *__restrict__ root,
-                                                                       uint32_t *__restrict__ tile_cv) {
-  stream_tile_body<false>(window, len, tile0, ob, root, tile_cv, 0);
-}
-__global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_tile_group_kernel(const uint8_t *__restrict__ window, uint64_t len, uint32_t tile0,
-                                                                             uint8_t *__restrict__ ob, uint32_t *__restrict__ root,
-                                                                             uint32_t *__restrict__ tile_cv, uint32_t gl) {
-  stream_tile_body<true>(window, len, tile0, ob, root, tile_cv, gl);
-}
-
-// merge_body for the one file (more than one tile): workgroup g merges items [1 024 g, ...) of in_cv, its CV to out_cv slot g or the root
-template <bool GRP>
-__device__ __forceinline__ void stream_merge_body(uint64_t len, uint64_t unit, const uint32_t *__restrict__ in_cv, uint32_t *__restrict__ out_cv,
-                                                  uint8_t *__restrict__ ob, uint32_t *__restrict__ root, uint32_t gl) {
-  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
-  const uint64_t n = (len + 1023) / 1024;
-  const uint64_t g = blockIdx.x, span = unit * B3W_TILE, a0 = g * span;
-  const uint64_t tot = n - a0 < span ? n - a0 : span;
-  const uint32_t cnt = (uint32_t)((tot + unit - 1) / unit);
-  const bool sole = n <= span;
-  const uint4 *src = reinterpret_cast<const uint4 *>(in_cv + g * B3W_TILE * 8);
-  for (uint32_t i = threadIdx.x; i < cnt * 2; i += 256) reinterpret_cast<uint4 *>(cv)[i] = src[i];
-  const uint64_t G1 = GRP ? (1ull << gl) - 1 : 0;                     // (every node here is over more than a tile: all of them are stored)
-  merge_in_lds<256, GRP>(cv, cnt, unit, tot, ob + 8 + (GRP ? preorder_pos((n + G1) >> gl, a0 >> gl, (tot + G1) >> gl) : preorder_pos(n, a0, tot)) * 64, sole, gl);
-  if (threadIdx.x < 8) (sole ? root : out_cv + g * 8)[threadIdx.x] = cv[threadIdx.x];
-}
-
-__global__ __launch_bounds__(256) void b3w_bao_stream_merge_kernel(uint64_t len, uint64_t unit, const uint32_t *__restrict__ in_cv,
-                                                                   uint32_t *__restrict__ out_cv, uint8_t *__restrict__ ob, uint32_t *__restrict__ root) {
-  stream_merge_body<false>(len, unit, in_cv, out_cv, ob, root, 0);
-}
-__global__ __launch_bounds__(256) void b3w_bao_stream_merge_group_kernel(uint64_t len, uint64_t unit, const uint32_t *__restrict__ in_cv,
-                                                                         uint32_t *__restrict__ out_cv, uint8_t *__restrict__ ob,
-                                                                         uint32_t *__restrict__ root, uint32_t gl) {
-  stream_merge_body<true>(len, unit, in_cv, out_cv, ob, root, gl);
-}
-
-// b3w_bao_verify_upper_kernel for the one file (more than one tile).  Scratch entries as there: the tiles' (n_tile_ents), then the groups'.
-__global__ __launch_bounds__(256) void b3w_bao_stream_upper_kernel(uint64_t len, uint64_t unit, uint64_t n_tile_ents, const uint8_t *__restrict__ ob8,
-                                                                   const uint32_t *__restrict__ root, uint32_t *__restrict__ exp_cv,
-                                                                   uint32_t *__restrict__ bad, uint32_t gl, int32_t *__restrict__ file_status,
-                                                                   unsigned long long *__restrict__ first_bad) {
-  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
-  __shared__ uint32_t flags[B3W_TILE];
-  const uint64_t n = (len + 1023) / 1024;
-  const uint64_t g = blockIdx.x, span = unit * B3W_TILE, a0 = g * span;
-  const uint64_t tot = n - a0 < span ? n - a0 : span;
-  const uint32_t cnt = (uint32_t)((tot + unit - 1) / unit);
-  const bool sole = n <= span;                                        // the file's top workgroup
-  const uint64_t out0 = unit == B3W_TILE ? g * B3W_TILE : n_tile_ents, in = n_tile_ents + g;
-  const uint32_t *want = sole ? root : exp_cv + in * 8;
-  bool above = sole ? false : bad[in] != 0;
-  const uint32_t *ob = reinterpret_cast<const uint32_t *>(ob8);
-  if (sole && threadIdx.x == 0) {                                     // (the windows' kernels, which run after this one, add to these)
-    const bool hdr = ((uint64_t)ob[0] | ((uint64_t)ob[1] << 32)) != len;
-    *file_status = hdr ? 3 : 0;
-    *first_bad = hdr ? 0ull : ~0ull;
-  }
-  if (cnt == 1) {                                                     // a lone last tile (or group) hangs straight off the storey above
-    if (threadIdx.x < 8) exp_cv[out0 * 8 + threadIdx.x] = want[threadIdx.x];
-    if (threadIdx.x == 0) bad[out0] = above;
-    return;
-  }
-  for (uint32_t i = threadIdx.x; i < cnt; i += 256) flags[i] = 0;
-  const uint64_t G1 = (1ull << gl) - 1;
-  verify_in_lds<256, false>(cv, flags, cnt, unit, tot, ob8 + 8 + preorder_pos((n + G1) >> gl, a0 >> gl, (tot + G1) >> gl) * 64, sole, gl, exp_cv + out0 * 8);
-  above = above || !eq8(cv, want);
-  for (uint32_t t = threadIdx.x; t < cnt; t += 256) bad[out0 + t] = above || path_bad(flags, t);
-}
-
-// b3w_bao_verify_tile_kernel for the tiles of a window; a file of one tile, down to one chunk or no byte at all, is settled here whole
-__global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_verify_kernel(const uint8_t *__restrict__ window, uint64_t len, uint32_t tile0,
-                                                                         const uint8_t *__restrict__ ob8, const uint32_t *__restrict__ root,
-                                                                         const uint32_t *__restrict__ exp_cv, const uint32_t *__restrict__ bad,
-                                                                         uint32_t gl, uint8_t *__restrict__ unit_status,
-                                                                         int32_t *__restrict__ file_status, unsigned long long *__restrict__ first_bad) {
-  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
-  __shared__ uint32_t flags[B3W_TILE];
-  __shared__ uint32_t worst, first;
-  const uint64_t n = len ? (len + 1023) / 1024 : 1;
   const uint32_t t = threadIdx.x, G = 1u << gl;
-  const uint64_t tile = (uint64_t)tile0 + blockIdx.x, a0 = tile * B3W_TILE;
   const uint32_t m = (uint32_t)(n - a0 < B3W_TILE ? n - a0 : B3W_TILE);
   const bool sole = n <= B3W_TILE;
-  stream_chunk_cv(cv, window, len, n, a0, m);
+  tile_chunk_cvs(cv, base, at, len, n, a0, m, lone);
   flags[t] = 0;
   if (t == 0) { worst = 0; first = ~0u; }
-  const uint32_t *ob = reinterpret_cast<const uint32_t *>(ob8);
-  const bool hdr = ((uint64_t)ob[0] | ((uint64_t)ob[1] << 32)) != len;
-  const uint64_t G1 = G - 1;
-  verify_in_lds<B3W_TILE, true>(cv, flags, m, 1, m, ob8 + 8 + preorder_pos((n + G1) >> gl, a0 >> gl, (m + G1) >> gl) * 64, sole, gl, nullptr);
-  if (t == 0 && !eq8(cv, sole ? root : exp_cv + tile * 8)) flags[0] |= m <= G ? VER_UNIT : VER_TOP;
-  const bool above = sole ? false : bad[tile] != 0;
+  const bool hdr = !header_is(ob, len);
+  verify_in_lds<B3W_TILE, true>(cv, flags, m, 1, m, ob + 8 + node_pos<true>(n, a0, m, gl) * 64, sole, gl, nullptr);
+  if (t == 0 && !eq8(cv, sole ? root : exp)) flags[0] |= m <= G ? VER_UNIT : VER_TOP;
+  const bool above = sole ? false : *bad != 0;
   lds_barrier();
   if (t < m && (t & (G - 1)) == 0) {                                  // a unit's first chunk: its status
     const uint32_t st = hdr ? 3u : above || path_bad(flags, t) ? 2u : (flags[t] & VER_UNIT) ? 1u : 0u;
@@ -1416,21 +1274,147 @@ __global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_verify_kernel(const u
   if (sole) {
     *file_status = (int32_t)worst;
     *first_bad = worst ? (unsigned long long)first : ~0ull;
-  } else if (worst) {                                                 // (initialised at begin by the file's top workgroup of the storey above)
+  } else if (worst) {                                                 // (initialised by the file's top workgroup of the storey above)
     atomicMax(file_status, (int32_t)worst);
     atomicMin(first_bad, (unsigned long long)((a0 >> gl) + first));
   }
 }
 
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_verify_tile_kernel(const uint8_t *__restrict__ arena, const BatchEnt *__restrict__ ents, uint32_t n_ents,
+                                                                       const VerFile *__restrict__ vf, const uint8_t *__restrict__ outboards,
+                                                                       const uint32_t *__restrict__ roots, const uint32_t *__restrict__ exp_cv,
+                                                                       const uint32_t *__restrict__ bad, uint32_t gl, uint8_t *__restrict__ unit_status,
+                                                                       int32_t *__restrict__ file_status, unsigned long long *__restrict__ first_bad) {
+  const BatchEnt e = batch_ent(ents, n_ents, blockIdx.x);
+  const VerFile v = vf[e.file];
+  const uint32_t tile = blockIdx.x - e.first;
+  const uint64_t a0 = (uint64_t)tile * B3W_TILE, ent = v.slot + tile;
+  verify_tile(arena + e.off, a0, e.len, (e.len + 1023) / 1024, a0, false, outboards + e.ob, roots + (uint64_t)e.file * 8,   // (more than 64 chunks)
+              exp_cv + ent * 8, bad + ent, gl, unit_status + v.ufirst, file_status + e.file, first_bad + e.file);
+}
+
+// small_body's wave with every stored node of a file checked by the lane that would have stored it (cv: the chunk CVs from small_lane;
+// `first`: the lane of the file's chunk 0).  Returns the status of the unit whose first chunk the lane holds, in `is_unit` whether it
+// holds one.
+__device__ __forceinline__ uint32_t small_verify(uint32_t *cv, uint32_t *flags, uint64_t len, uint32_t first, uint32_t n, uint32_t i, bool live,
+                                                 const uint8_t *__restrict__ ob, const uint32_t *root, uint32_t gl, bool &is_unit) {
+  const uint32_t lane = threadIdx.x, G = 1u << gl;
+  flags[lane] = 0;
+  const bool hdr = !header_is(ob, len);
+  small_levels<true>(n, i, live, [&](uint32_t l, uint32_t size, uint32_t d) {
+    if (size <= G) merge_pair<true>(cv, lane, lane + (1u << l), nullptr, d);
+    else check_pair<true>(cv, flags, lane, lane + (1u << l), l, ob + 8 + node_pos<true>(n, i, size, gl) * 64, d, 1u << l, size - (1u << l), G, nullptr);
+  });
+  // the file's top (its ROOT-flagged CV, or what its stored root node hashes to with ROOT) against the root; bit 6: above every level here
+  if (live && i == 0 && !eq8(cv + lane * 8, root)) flags[lane] |= n <= G ? VER_UNIT : 1u << 6;
+  lds_barrier();
+  is_unit = live && (i & (G - 1)) == 0;
+  if (!is_unit) return 0;
+  uint32_t x = 0;
+#pragma unroll
+  for (uint32_t l = 0; l <= 6; ++l) x |= flags[first + ((i >> l) << l)] & (1u << l);
+  return hdr ? 3u : x ? 2u : (flags[lane] & VER_UNIT) ? 1u : 0u;
+}
+
+// the files of at most 64 chunks; the per-file outputs from ballots over the file's lanes
+__global__ __launch_bounds__(64) void b3w_bao_verify_small_kernel(const uint8_t *__restrict__ arena, const BatchEnt *__restrict__ ents,
+                                                                  const uint32_t *__restrict__ wave_first, const VerFile *__restrict__ vf,
+                                                                  const uint8_t *__restrict__ outboards, const uint32_t *__restrict__ roots, uint32_t gl,
+                                                                  uint8_t *__restrict__ unit_status, int32_t *__restrict__ file_status,
+                                                                  unsigned long long *__restrict__ first_bad) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[64 * 8];
+  __shared__ uint32_t flags[64];
+  const SmallLane<BatchEnt> s = small_lane(cv, arena, ents, wave_first);
+  const BatchEnt &e = s.e;
+  bool is_unit;
+  const uint32_t st = small_verify(cv, flags, e.len, e.first, s.n, s.i, s.live, outboards + e.ob, roots + (uint64_t)e.file * 8, gl, is_unit);
+  if (is_unit) unit_status[vf[e.file].ufirst + (s.i >> gl)] = (uint8_t)st;
+  const uint64_t mine = (s.n == 64 ? ~0ull : (1ull << s.n) - 1) << e.first;
+  const uint64_t b1 = __ballot(st >= 1) & mine, b2 = __ballot(st >= 2) & mine, b3 = __ballot(st >= 3) & mine;
+  if (s.live && s.i == 0) {
+    file_status[e.file] = b3 ? 3 : b2 ? 2 : b1 ? 1 : 0;
+    first_bad[e.file] = b1 ? (unsigned long long)((__ffsll((unsigned long long)b1) - 1 - e.first) >> gl) : ~0ull;
+  }
+}
+
+// ---- streamed files: one file of known length whose bytes arrive in windows of whole tiles -------------------------------------
+// A tile is a subtree of the file's tree whatever else is known of the file, and the place of every node below its root follows from
+// the file's length and the tile's ABSOLUTE index alone.  So the kernels of a window are the tile kernels with the file's entry by value
+// (no table in device memory: a push uploads nothing) and the tile's bytes taken from the window, not from arena + offset:
+//   b3w_bao_stream_tile[_group]_kernel   a workgroup per tile of the window: tile_outboard, the tile's CV to scratch slot `tile`.
+//                                        A file of one tile, down to one chunk (ROOT on the chunk) or no byte at all, ends here too:
+//                                        its root and header, the bytes the small kernel writes for it
+//   b3w_bao_stream_merge[_group]_kernel  finish: merge_storey over the tile CVs in scratch (files past 1 GiB: once more over the groups')
+//   b3w_bao_stream_upper_kernel          verification, at begin: verify_upper for the one file, from the stored nodes alone
+//   b3w_bao_stream_verify_kernel         a workgroup per tile of the window: verify_tile, exp_cv / bad read at `tile`
+// Every one of these bodies is the batch kernels' own (one definition, above); a stream kernel only says where the one file's fields are.
+// window: the bytes of the file from tile `tile0` on; workgroup w takes tile tile0 + w
+template <bool GRP>
+__device__ __forceinline__ void stream_tile_body(const uint8_t *__restrict__ window, uint32_t w, uint64_t len, uint32_t tile0, uint8_t *__restrict__ ob,
+                                                 uint32_t *__restrict__ root, uint32_t *__restrict__ tile_cv, uint32_t gl) {
+  const uint64_t n = len ? (len + 1023) / 1024 : 1, tile = (uint64_t)tile0 + w;
+  tile_outboard<GRP>(window, (uint64_t)w * B3W_TILE, len, n, tile * B3W_TILE, true, ob, root, tile_cv + tile * 8, gl);
+}
+
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_tile_kernel(const uint8_t *__restrict__ window, uint64_t len, uint32_t tile0,
+                                                                       uint8_t *__restrict__ ob, uint32_t *__restrict__ root,
+                                                                       uint32_t *__restrict__ tile_cv) {
+  stream_tile_body<false>(window, blockIdx.x, len, tile0, ob, root, tile_cv, 0);
+}
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_tile_group_kernel(const uint8_t *__restrict__ window, uint64_t len, uint32_t tile0,
+                                                                             uint8_t *__restrict__ ob, uint32_t *__restrict__ root,
+                                                                             uint32_t *__restrict__ tile_cv, uint32_t gl) {
+  stream_tile_body<true>(window, blockIdx.x, len, tile0, ob, root, tile_cv, gl);
+}
+
+// the merge storey of the one file (more than one tile): workgroup g merges items [1 024 g, ...) of in_cv, its CV to out_cv slot g or the root
+__global__ __launch_bounds__(256) void b3w_bao_stream_merge_kernel(uint64_t len, uint64_t unit, const uint32_t *__restrict__ in_cv,
+                                                                   uint32_t *__restrict__ out_cv, uint8_t *__restrict__ ob, uint32_t *__restrict__ root) {
+  const uint64_t g = blockIdx.x;
+  merge_storey<false>((len + 1023) / 1024, g, unit, in_cv + g * B3W_TILE * 8, ob, root, out_cv + g * 8, 0);
+}
+__global__ __launch_bounds__(256) void b3w_bao_stream_merge_group_kernel(uint64_t len, uint64_t unit, const uint32_t *__restrict__ in_cv,
+                                                                         uint32_t *__restrict__ out_cv, uint8_t *__restrict__ ob,
+                                                                         uint32_t *__restrict__ root, uint32_t gl) {
+  const uint64_t g = blockIdx.x;
+  merge_storey<true>((len + 1023) / 1024, g, unit, in_cv + g * B3W_TILE * 8, ob, root, out_cv + g * 8, gl);
+}
+
+// verify_upper for the one file (more than one tile).  Scratch entries as in the batch: the tiles' (n_tile_ents), then the groups'.
+__global__ __launch_bounds__(256) void b3w_bao_stream_upper_kernel(uint64_t len, uint64_t unit, uint64_t n_tile_ents, const uint8_t *__restrict__ ob8,
+                                                                   const uint32_t *__restrict__ root, uint32_t *__restrict__ exp_cv,
+                                                                   uint32_t *__restrict__ bad, uint32_t gl, int32_t *__restrict__ file_status,
+                                                                   unsigned long long *__restrict__ first_bad) {
+  const uint64_t g = blockIdx.x, out0 = unit == B3W_TILE ? g * B3W_TILE : n_tile_ents, in = n_tile_ents + g;
+  verify_upper(len, g, unit, ob8, root, exp_cv + in * 8, bad + in, exp_cv + out0 * 8, bad + out0, gl, file_status, first_bad);
+}
+
+// verify_tile for tile tile0 + w of a window, exp_cv / bad read at the tile's index; a file of one tile, down to one chunk or no byte at
+// all, is settled here whole
+__device__ __forceinline__ void stream_verify_body(const uint8_t *__restrict__ window, uint32_t w, uint64_t len, uint32_t tile0, const uint8_t *__restrict__ ob,
+                                                   const uint32_t *root, const uint32_t *exp_cv, const uint32_t *bad, uint32_t gl, uint8_t *unit_status,
+                                                   int32_t *file_status, unsigned long long *first_bad) {
+  const uint64_t n = len ? (len + 1023) / 1024 : 1, tile = (uint64_t)tile0 + w;
+  verify_tile(window, (uint64_t)w * B3W_TILE, len, n, tile * B3W_TILE, true, ob, root, exp_cv + tile * 8, bad + tile, gl,
+              unit_status, file_status, first_bad);
+}
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_verify_kernel(const uint8_t *__restrict__ window, uint64_t len, uint32_t tile0,
+                                                                         const uint8_t *__restrict__ ob8, const uint32_t *__restrict__ root,
+                                                                         const uint32_t *__restrict__ exp_cv, const uint32_t *__restrict__ bad,
+                                                                         uint32_t gl, uint8_t *__restrict__ unit_status,
+                                                                         int32_t *__restrict__ file_status, unsigned long long *__restrict__ first_bad) {
+  stream_verify_body(window, blockIdx.x, len, tile0, ob8, root, exp_cv, bad, gl, unit_status, file_status, first_bad);
+}
+
 // ---- many stream sessions in one launch ----------------------------------------------------------------------------------------------
 // The windows of many sessions, each a file of its own, as ONE grid: what the stream kernels take by value, or from blockIdx.x, comes from
 // a table with a row per (session, window) entry, found by bisection over the rows' first workgroups as batch_ent finds a file.  The
-// work on a tile is the stream kernels' own (chunk_cv, merge_in_lds, verify_in_lds, preorder_pos), so the bytes are theirs.
+// work on a tile is the stream kernels' own bodies, called with the row's fields, so the bytes are theirs.
 //   b3w_bao_stream_tile_many[_group]_kernel   stream_tile_body per workgroup.  The group kernel takes gl from the row, and at gl = 0 it
 //                                             stores every node where the plain kernel does (a parent is over 2 chunks or more): a call
 //                                             that mixes full and group outboards is one launch of the group kernel
-//   b3w_bao_stream_verify_many_kernel         the body of b3w_bao_stream_verify_kernel
-//   b3w_bao_stream_merge_many[_group]_kernel  stream_merge_body; a row per session of more than one tile (unit = B3W_TILE) or of more
+//   b3w_bao_stream_verify_many_kernel         verify_tile's work, restated (it measured slower through the shared body)
+//   b3w_bao_stream_merge_many[_group]_kernel  merge_storey; a row per session of more than one tile (unit = B3W_TILE) or of more
 //                                             than 1 024 tiles (unit = B3W_TILE^2)
 // cv / aux: tile kernels: the session's tile CVs / unused; verify: exp_cv / bad; merge: the input CVs / the output CVs
 struct ManyRow {
@@ -1449,12 +1433,7 @@ template <class P>
 __device__ __forceinline__ P *as_global(P *p) { return (P *)(__attribute__((address_space(1))) P *)(uintptr_t)p; }
 
 __device__ __forceinline__ ManyRow many_row(const ManyRow *__restrict__ rows, uint32_t n_rows, uint32_t wg) {
-  uint32_t lo = 0, hi = n_rows;
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) / 2;
-    if (rows[mid].first <= wg) lo = mid; else hi = mid;
-  }
-  ManyRow r = rows[lo];
+  ManyRow r = rows[find_first(rows, 0, n_rows, wg)];
   // (a pointer loaded from memory is a generic one to the compiler, and its loads and stores would be flat ones, which count against the
   // LDS counter too; these are device memory, as the stream kernels' arguments are known to be)
   r.window = as_global(r.window); r.ob = as_global(r.ob); r.root = as_global(r.root); r.cv = as_global(r.cv); r.aux = as_global(r.aux);
@@ -1462,31 +1441,10 @@ __device__ __forceinline__ ManyRow many_row(const ManyRow *__restrict__ rows, ui
   return r;
 }
 
-// stream_chunk_cv with the workgroup's index within its entry (w) in blockIdx.x's place
-__device__ __forceinline__ void many_chunk_cv(uint32_t *cv, const uint8_t *__restrict__ window, uint32_t w, uint64_t len, uint64_t n, uint64_t a0, uint32_t m) {
-  if (threadIdx.x < m) {
-    const uint64_t c = a0 + threadIdx.x, off = c * 1024;
-    uint32_t h[8];
-    chunk_cv(window + ((uint64_t)w * B3W_TILE + threadIdx.x) * 1024, (uint32_t)(len - off < 1024 ? len - off : 1024), c, n == 1 ? 8u : 0u, h);
-    reinterpret_cast<uint4 *>(cv + threadIdx.x * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
-    reinterpret_cast<uint4 *>(cv + threadIdx.x * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
-  }
-}
-
 template <bool GRP>
 __device__ __forceinline__ void many_tile_body(const ManyRow *__restrict__ rows, uint32_t n_rows) {
-  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
   const ManyRow r = many_row(rows, n_rows, blockIdx.x);
-  const uint32_t w = blockIdx.x - r.first, gl = GRP ? r.gl : 0;
-  const uint64_t len = r.len, n = len ? (len + 1023) / 1024 : 1;
-  const uint64_t tile = (uint64_t)r.tile0 + w, a0 = tile * B3W_TILE;
-  const uint32_t m = (uint32_t)(n - a0 < B3W_TILE ? n - a0 : B3W_TILE);
-  const bool sole = n <= B3W_TILE;
-  many_chunk_cv(cv, r.window, w, len, n, a0, m);
-  if (a0 == 0 && threadIdx.x == 0) *reinterpret_cast<uint2 *>(r.ob) = make_uint2((uint32_t)len, (uint32_t)(len >> 32));
-  const uint64_t G1 = GRP ? (1ull << gl) - 1 : 0;                     // (a tile starts at a multiple of every group size)
-  merge_in_lds<B3W_TILE, GRP>(cv, m, 1, m, r.ob + 8 + (GRP ? preorder_pos((n + G1) >> gl, a0 >> gl, (m + G1) >> gl) : preorder_pos(n, a0, m)) * 64, sole, gl);
-  if (threadIdx.x < 8) (sole ? r.root : r.cv + tile * 8)[threadIdx.x] = cv[threadIdx.x];
+  stream_tile_body<GRP>(r.window, blockIdx.x - r.first, r.len, r.tile0, r.ob, r.root, r.cv, GRP ? r.gl : 0);
 }
 
 __global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_tile_many_kernel(const ManyRow *__restrict__ rows, uint32_t n_rows) {
@@ -1499,19 +1457,9 @@ __global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_tile_many_group_kerne
 // workgroup g of a row merges items [1 024 g, ...) of the row's input CVs, its CV to output slot g or the root
 template <bool GRP>
 __device__ __forceinline__ void many_merge_body(const ManyRow *__restrict__ rows, uint32_t n_rows, uint64_t unit) {
-  __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
   const ManyRow r = many_row(rows, n_rows, blockIdx.x);
-  const uint32_t gl = GRP ? r.gl : 0;
-  const uint64_t n = (r.len + 1023) / 1024;                           // (more than one tile)
-  const uint64_t g = blockIdx.x - r.first, span = unit * B3W_TILE, a0 = g * span;
-  const uint64_t tot = n - a0 < span ? n - a0 : span;
-  const uint32_t cnt = (uint32_t)((tot + unit - 1) / unit);
-  const bool sole = n <= span;
-  const uint4 *src = reinterpret_cast<const uint4 *>(r.cv + g * B3W_TILE * 8);
-  for (uint32_t i = threadIdx.x; i < cnt * 2; i += 256) reinterpret_cast<uint4 *>(cv)[i] = src[i];
-  const uint64_t G1 = GRP ? (1ull << gl) - 1 : 0;                     // (every node here is over more than a tile: all of them are stored)
-  merge_in_lds<256, GRP>(cv, cnt, unit, tot, r.ob + 8 + (GRP ? preorder_pos((n + G1) >> gl, a0 >> gl, (tot + G1) >> gl) : preorder_pos(n, a0, tot)) * 64, sole, gl);
-  if (threadIdx.x < 8) (sole ? r.root : r.aux + g * 8)[threadIdx.x] = cv[threadIdx.x];
+  const uint64_t n = (r.len + 1023) / 1024, g = blockIdx.x - r.first;
+  merge_storey<GRP>(n, g, unit, r.cv + g * B3W_TILE * 8, r.ob, r.root, r.aux + g * 8, GRP ? r.gl : 0);
 }
 
 __global__ __launch_bounds__(256) void b3w_bao_stream_merge_many_kernel(const ManyRow *__restrict__ rows, uint32_t n_rows, uint64_t unit) {
@@ -1521,6 +1469,27 @@ __global__ __launch_bounds__(256) void b3w_bao_stream_merge_many_group_kernel(co
   many_merge_body<true>(rows, n_rows, unit);
 }
 
+// verify_in_lds<B3W_TILE, true> with tree_levels's loop written out, for the kernel below alone
+__device__ __forceinline__ void verify_many_walk(uint32_t *cv, uint32_t *flags, uint32_t cnt, uint64_t unit, uint64_t total,
+                                                 const uint8_t *__restrict__ nodes, bool root, uint32_t gl) {
+  const uint64_t G = 1ull << gl, G1 = G - 1, leaf = G;
+  for (uint32_t l = 0; (1u << l) < cnt; ++l) {
+    lds_barrier();
+    const bool top = (2u << l) >= cnt;
+    for (uint32_t j = threadIdx.x;; j += B3W_TILE) {
+      const uint32_t i0 = (2 * j) << l, i1 = i0 + (1u << l);
+      if (i1 >= cnt) break;
+      const uint64_t a = i0 * unit, e = (uint64_t)(i0 + (2u << l)) * unit, size = (e < total ? e : total) - a;
+      const uint32_t d = 4u | (top && root ? 8u : 0u);
+      if (size <= G) { merge_pair<true>(cv, i0, i1, nullptr, d); continue; }                   // inside a group: computed
+      const uint64_t sl = ((uint64_t)unit) << l;
+      check_pair<true>(cv, flags, i0, i1, l, nodes + preorder_pos((total + G1) >> gl, a >> gl, (size + G1) >> gl) * 64, d, sl, size - sl, leaf, nullptr);
+    }
+  }
+  lds_barrier();
+}
+
+// verify_tile and its walk restated with the row's fields: through verify_tile this kernel measured 0.02 to 0.2 % slower at gl = 0 (profiles/r21/bao_shared_bodies_ab.json)
 __global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_verify_many_kernel(const ManyRow *__restrict__ rows, uint32_t n_rows) {
   __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
   __shared__ uint32_t flags[B3W_TILE];
@@ -1532,13 +1501,13 @@ __global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_verify_many_kernel(co
   const uint64_t tile = (uint64_t)r.tile0 + w, a0 = tile * B3W_TILE;
   const uint32_t m = (uint32_t)(n - a0 < B3W_TILE ? n - a0 : B3W_TILE);
   const bool sole = n <= B3W_TILE;
-  many_chunk_cv(cv, r.window, w, len, n, a0, m);
+  tile_chunk_cvs(cv, r.window, (uint64_t)w * B3W_TILE, len, n, a0, m, true);
   flags[t] = 0;
   if (t == 0) { worst = 0; first = ~0u; }
   const uint32_t *ob = reinterpret_cast<const uint32_t *>(r.ob);
   const bool hdr = ((uint64_t)ob[0] | ((uint64_t)ob[1] << 32)) != len;
   const uint64_t G1 = G - 1;
-  verify_in_lds<B3W_TILE, true>(cv, flags, m, 1, m, r.ob + 8 + preorder_pos((n + G1) >> gl, a0 >> gl, (m + G1) >> gl) * 64, sole, gl, nullptr);
+  verify_many_walk(cv, flags, m, 1, m, r.ob + 8 + preorder_pos((n + G1) >> gl, a0 >> gl, (m + G1) >> gl) * 64, sole, gl);
   if (t == 0 && !eq8(cv, sole ? r.root : r.cv + tile * 8)) flags[0] |= m <= G ? VER_UNIT : VER_TOP;
   const bool above = sole ? false : r.aux[tile] != 0;
   lds_barrier();
@@ -1605,13 +1574,12 @@ __device__ __forceinline__ void update_pair(uint32_t *cv, uint32_t i0, uint32_t 
   }
   iv(ivv);
   blake3_cv(ivv, m, 0, 0, 64, d, o);
-  reinterpret_cast<uint4 *>(cv + i0 * 8)[0] = make_uint4(o[0], o[1], o[2], o[3]);          // (slot i0 is this thread's alone at this level)
-  reinterpret_cast<uint4 *>(cv + i0 * 8)[1] = make_uint4(o[4], o[5], o[6], o[7]);
+  put_cv(cv, i0, o);                                                 // (slot i0 is this thread's alone at this level)
 }
 
 // merge_in_lds over the dirty items alone: dirty[i] says whether slot i holds a CV (an item with a dirty chunk below it).  A pair with no
 // dirty child is skipped; any other one leaves its CV in slot i0 and marks it; an odd item out waits and keeps its flag.  The arguments are
-// merge_in_lds's; ends with a barrier, the tree's CV in cv[0 .. 8) where the tree holds a dirty item.
+// merge_in_lds's; ends with a barrier, the tree's CV in cv[0 .. 8) where the tree holds a dirty item.  (tree_levels's loop written out: see there.)
 template <int BS, bool GRP>
 __device__ __forceinline__ void update_in_lds(uint32_t *cv, uint32_t *dirty, uint32_t cnt, uint64_t unit, uint64_t total, uint8_t *__restrict__ nodes,
                                               bool root, uint32_t gl) {
@@ -1624,14 +1592,7 @@ __device__ __forceinline__ void update_in_lds(uint32_t *cv, uint32_t *dirty, uin
       const bool d0 = dirty[i0] != 0, d1 = dirty[i1] != 0;
       if (!d0 && !d1) continue;
       const uint64_t a = i0 * unit, e = (uint64_t)(i0 + (2u << l)) * unit, size = (e < total ? e : total) - a;
-      uint8_t *node;
-      if (GRP) {
-        const uint64_t G1 = (1ull << gl) - 1;
-        node = size > G1 + 1 ? nodes + preorder_pos((total + G1) >> gl, a >> gl, (size + G1) >> gl) * 64 : nullptr;
-      } else {
-        node = nodes + preorder_pos(total, a, size) * 64;
-      }
-      update_pair<GRP>(cv, i0, i1, d0, d1, node, 4u | (top && root ? 8u : 0u));
+      update_pair<GRP>(cv, i0, i1, d0, d1, node_at<GRP>(nodes, total, a, size, gl), 4u | (top && root ? 8u : 0u));
       dirty[i0] = 1;
     }
   }
@@ -1650,23 +1611,15 @@ __device__ __forceinline__ void update_tile_body(const UpdRow *__restrict__ rows
   const bool sole = n <= B3W_TILE;
   const bool mine = t < m && ((r->mask[t >> 5] >> (t & 31)) & 1u);
   dirty[t] = mine ? 1u : 0u;
-  if (mine) {
-    const uint64_t c = a0 + t, off = c * 1024;
-    uint32_t h[8];
-    chunk_cv(as_global(r->data) + off, (uint32_t)(len - off < 1024 ? len - off : 1024), c, 0, h);
-    reinterpret_cast<uint4 *>(cv + t * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
-    reinterpret_cast<uint4 *>(cv + t * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
-  }
-  const uint64_t G1 = GRP ? (1ull << gl) - 1 : 0;                     // (a tile starts at a multiple of every group size)
-  update_in_lds<B3W_TILE, GRP>(cv, dirty, m, 1, m, as_global(r->ob) + 8 + (GRP ? preorder_pos((n + G1) >> gl, a0 >> gl, (m + G1) >> gl) : preorder_pos(n, a0, m)) * 64,
-                               sole, gl);
+  if (mine) lane_chunk_cv(cv, as_global(r->data), a0 + t, len, n, a0 + t, false);
+  update_in_lds<B3W_TILE, GRP>(cv, dirty, m, 1, m, as_global(r->ob) + 8 + node_pos<GRP>(n, a0, m, gl) * 64, sole, gl);   // (a tile starts at a multiple of every group size)
   if (t < 8) as_global(sole ? r->root : r->out)[t] = cv[t];            // (the row's mask is not empty: slot 0 holds the tile's CV)
 }
 
 __global__ __launch_bounds__(B3W_TILE) void b3w_bao_update_tile_kernel(const UpdRow *__restrict__ rows) { update_tile_body<false>(rows); }
 __global__ __launch_bounds__(B3W_TILE) void b3w_bao_update_tile_group_kernel(const UpdRow *__restrict__ rows) { update_tile_body<true>(rows); }
 
-// unit = chunks per input item, as in merge_body; the workgroup's items are [1 024 idx, ...) of the file's
+// unit = chunks per input item, as in merge_storey; the workgroup's items are [1 024 idx, ...) of the file's
 template <bool GRP>
 __device__ __forceinline__ void update_merge_body(const UpdRow *__restrict__ rows, uint64_t unit) {
   __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
@@ -1690,9 +1643,7 @@ __device__ __forceinline__ void update_merge_body(const UpdRow *__restrict__ row
       reinterpret_cast<uint4 *>(cv + i * 8)[1] = src[1];
     }
   }
-  const uint64_t G1 = GRP ? (1ull << gl) - 1 : 0;                     // (every node here is over more than a tile: all of them are stored)
-  update_in_lds<256, GRP>(cv, dirty, cnt, unit, tot, as_global(r->ob) + 8 + (GRP ? preorder_pos((n + G1) >> gl, a0 >> gl, (tot + G1) >> gl) : preorder_pos(n, a0, tot)) * 64,
-                          sole, gl);
+  update_in_lds<256, GRP>(cv, dirty, cnt, unit, tot, as_global(r->ob) + 8 + node_pos<GRP>(n, a0, tot, gl) * 64, sole, gl);   // (every node here is over more than a tile: all are stored)
   if (threadIdx.x < 8) as_global(sole ? r->root : r->out)[threadIdx.x] = cv[threadIdx.x];
 }
 
@@ -1763,17 +1714,17 @@ __device__ __forceinline__ void ranges_pair(uint32_t *cv, uint32_t *flags, const
   }
   iv(ivv);
   blake3_cv(ivv, m, 0, 0, 64, d, o);
-  reinterpret_cast<uint4 *>(cv + i0 * 8)[0] = make_uint4(o[0], o[1], o[2], o[3]);          // (slot i0 is this thread's alone at this level)
-  reinterpret_cast<uint4 *>(cv + i0 * 8)[1] = make_uint4(o[4], o[5], o[6], o[7]);
+  put_cv(cv, i0, o);                                                 // (slot i0 is this thread's alone at this level)
 }
 
 // verify_in_lds over the listed items alone: listed[i] says whether slot i holds a claim (CLAIM) or has a listed item below it.  A pair
 // with no listed child is skipped: nothing loaded, nothing checked.  Any other one leaves hash(stored node) in slot i0 and marks it; an
 // odd item out waits and keeps its mark.  Inside a (listed) group both halves are in LDS and nothing is loaded.  Ends with a barrier.
+// (tree_levels's loop written out: see there.)
 template <int BS, bool CLAIM>
 __device__ __forceinline__ void ranges_in_lds(uint32_t *cv, uint32_t *flags, uint32_t *listed, const uint32_t *rank, uint32_t cnt, uint64_t unit,
                                               uint64_t total, const uint8_t *__restrict__ nodes, bool root, uint32_t gl, uint32_t *__restrict__ exp_out) {
-  const uint64_t G = 1ull << gl, G1 = G - 1, leaf = CLAIM ? G : unit;
+  const uint64_t G = 1ull << gl, leaf = CLAIM ? G : unit;
   for (uint32_t l = 0; (1u << l) < cnt; ++l) {
     lds_barrier();
     const bool top = (2u << l) >= cnt;
@@ -1786,8 +1737,7 @@ __device__ __forceinline__ void ranges_in_lds(uint32_t *cv, uint32_t *flags, uin
       const uint32_t d = 4u | (top && root ? 8u : 0u);
       if (CLAIM && size <= G) { merge_pair<true>(cv, i0, i1, nullptr, d); continue; }          // inside a listed group: computed
       const uint64_t sl = ((uint64_t)unit) << l;
-      ranges_pair<CLAIM>(cv, flags, rank, i0, i1, d0, d1, l, nodes + preorder_pos((total + G1) >> gl, a >> gl, (size + G1) >> gl) * 64, d, sl, size - sl,
-                         leaf, exp_out);
+      ranges_pair<CLAIM>(cv, flags, rank, i0, i1, d0, d1, l, nodes + node_pos<true>(total, a, size, gl) * 64, d, sl, size - sl, leaf, exp_out);
       listed[i0] = 1;
     }
   }
@@ -1808,14 +1758,8 @@ __global__ __launch_bounds__(256) void b3w_bao_verify_ranges_upper_kernel(const 
   const uint8_t *__restrict__ ob = as_global(r->ob);
   const uint32_t *__restrict__ want = as_global(sole ? r->root : r->want);
   uint32_t *__restrict__ out_cv = as_global(r->out_cv), *__restrict__ out_word = as_global(r->out_word);
-  uint32_t above;
-  if (sole) {
-    const uint32_t *h = reinterpret_cast<const uint32_t *>(ob);
-    above = ((uint64_t)h[0] | ((uint64_t)h[1] << 32)) != len ? VR_HDR : 0u;
-  } else {
-    above = *as_global(r->above);
-  }
-  if (cnt == 1) {                                                     // a lone last tile (or span) hangs straight off the storey above
+  uint32_t above = sole ? (header_is(ob, len) ? 0u : VR_HDR) : *as_global(r->above);
+  if (cnt == 1) {                                                    // a lone last tile (or span) hangs straight off the storey above
     if (threadIdx.x < 8) out_cv[threadIdx.x] = want[threadIdx.x];
     if (threadIdx.x == 0) out_word[0] = above;
     return;
@@ -1826,8 +1770,7 @@ __global__ __launch_bounds__(256) void b3w_bao_verify_ranges_upper_kernel(const 
     for (uint32_t k = 0; k < (i >> 5); ++k) below += __popc(r->mask[k]);
     flags[i] = 0; listed[i] = (w & bit) ? 1u : 0u; rank[i] = below;
   }
-  const uint64_t G1 = (1ull << gl) - 1;
-  ranges_in_lds<256, false>(cv, flags, listed, rank, cnt, unit, tot, ob + 8 + preorder_pos((n + G1) >> gl, a0 >> gl, (tot + G1) >> gl) * 64, sole, gl, out_cv);
+  ranges_in_lds<256, false>(cv, flags, listed, rank, cnt, unit, tot, ob + 8 + node_pos<true>(n, a0, tot, gl) * 64, sole, gl, out_cv);
   if (!eq8(cv, want)) above |= VR_PATH;
   for (uint32_t t = threadIdx.x; t < cnt; t += 256)
     if ((r->mask[t >> 5] >> (t & 31)) & 1u) out_word[rank[t]] = above | (path_bad(flags, t) ? VR_PATH : 0u);
@@ -1846,22 +1789,9 @@ __global__ __launch_bounds__(B3W_TILE) void b3w_bao_verify_ranges_tile_kernel(co
   const uint8_t *__restrict__ ob = as_global(r->ob);
   listed[t] = mine ? 1u : 0u;
   flags[t] = 0;
-  if (mine) {
-    const uint64_t c = a0 + t, off = c * 1024;
-    uint32_t h[8];
-    chunk_cv(as_global(r->data) + off, (uint32_t)(len - off < 1024 ? len - off : 1024), c, 0, h);
-    reinterpret_cast<uint4 *>(cv + t * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
-    reinterpret_cast<uint4 *>(cv + t * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
-  }
-  uint32_t above;
-  if (sole) {
-    const uint32_t *h = reinterpret_cast<const uint32_t *>(ob);
-    above = ((uint64_t)h[0] | ((uint64_t)h[1] << 32)) != len ? VR_HDR : 0u;
-  } else {
-    above = *as_global(r->above);
-  }
-  const uint64_t G1 = G - 1;
-  ranges_in_lds<B3W_TILE, true>(cv, flags, listed, nullptr, m, 1, m, ob + 8 + preorder_pos((n + G1) >> gl, a0 >> gl, (m + G1) >> gl) * 64, sole, gl, nullptr);
+  if (mine) lane_chunk_cv(cv, as_global(r->data), a0 + t, len, n, a0 + t, false);
+  const uint32_t above = sole ? (header_is(ob, len) ? 0u : VR_HDR) : *as_global(r->above);
+  ranges_in_lds<B3W_TILE, true>(cv, flags, listed, nullptr, m, 1, m, ob + 8 + node_pos<true>(n, a0, m, gl) * 64, sole, gl, nullptr);
   // (the row's mask is not empty: slot 0 holds what the tile's stored root node hashes to, or the CV of a tile that is one unit)
   if (t == 0 && !eq8(cv, as_global(sole ? r->root : r->want))) flags[0] |= m <= G ? VER_UNIT : VER_TOP;
   lds_barrier();
@@ -1872,49 +1802,16 @@ __global__ __launch_bounds__(B3W_TILE) void b3w_bao_verify_ranges_tile_kernel(co
 }
 
 // b3w_bao_verify_small_kernel with a row per file: wave w takes the rows [wave_first[w], wave_first[w + 1]), r.first = the lane of the
-// file's chunk 0; every unit byte of the file is written, with the whole-file call's value
+// file's chunk 0; every unit byte of the file is written, with the whole-file call's value; no per-file outputs
 __global__ __launch_bounds__(64) void b3w_bao_verify_ranges_small_kernel(const uint8_t *__restrict__ arena, const VrSmall *__restrict__ rows,
                                                                          const uint32_t *__restrict__ wave_first, uint32_t gl) {
   __shared__ __attribute__((aligned(16))) uint32_t cv[64 * 8];
   __shared__ uint32_t flags[64];
-  const uint32_t lane = threadIdx.x, G = 1u << gl;
-  uint32_t lo = wave_first[blockIdx.x], hi = wave_first[blockIdx.x + 1];
-  while (hi - lo > 1) {                                               // this lane's file: the last one that starts at or before the lane
-    const uint32_t mid = (lo + hi) / 2;
-    if (rows[mid].first <= lane) lo = mid; else hi = mid;
-  }
-  const VrSmall e = rows[lo];
-  const uint32_t n = e.len ? (uint32_t)((e.len + 1023) / 1024) : 1, i = lane - e.first;
-  const bool live = i < n;                                            // (the lanes behind the last file's chunks are not)
-  if (live) {
-    const uint32_t off = i * 1024;
-    uint32_t h[8];
-    chunk_cv(arena + e.off + off, (uint32_t)(e.len - off < 1024 ? e.len - off : 1024), i, n == 1 ? 8u : 0u, h);
-    reinterpret_cast<uint4 *>(cv + lane * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
-    reinterpret_cast<uint4 *>(cv + lane * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
-  }
-  flags[lane] = 0;
-  const uint8_t *__restrict__ ob = as_global(e.ob);
-  const bool hdr = ((uint64_t)reinterpret_cast<const uint32_t *>(ob)[0] | ((uint64_t)reinterpret_cast<const uint32_t *>(ob)[1] << 32)) != e.len;
-  for (uint32_t l = 0; l < 6; ++l) {
-    lds_barrier();
-    if (!__any(live && (1u << l) < n)) break;                         // (uniform: the workgroup is this one wave)
-    if (live && (i & ((2u << l) - 1)) == 0 && i + (1u << l) < n) {
-      const uint32_t size = n - i < (2u << l) ? n - i : (2u << l), d = 4u | (i == 0 && (2u << l) >= n ? 8u : 0u);
-      if (size <= G) merge_pair<true>(cv, lane, lane + (1u << l), nullptr, d);
-      else check_pair<true>(cv, flags, lane, lane + (1u << l), l, ob + 8 + preorder_pos((n + G - 1) >> gl, i >> gl, (size + G - 1) >> gl) * 64, d,
-                            1u << l, size - (1u << l), G, nullptr);
-    }
-  }
-  lds_barrier();
-  if (live && i == 0 && !eq8(cv + lane * 8, as_global(e.root))) flags[lane] |= n <= G ? VER_UNIT : 1u << 6;
-  lds_barrier();
-  if (live && (i & (G - 1)) == 0) {
-    uint32_t x = 0;
-#pragma unroll
-    for (uint32_t l = 0; l <= 6; ++l) x |= flags[e.first + ((i >> l) << l)] & (1u << l);
-    as_global(e.unit_status)[i >> gl] = (uint8_t)(hdr ? 3u : x ? 2u : (flags[lane] & VER_UNIT) ? 1u : 0u);
-  }
+  const SmallLane<VrSmall> s = small_lane(cv, arena, rows, wave_first);
+  const VrSmall &e = s.e;
+  bool is_unit;
+  const uint32_t st = small_verify(cv, flags, e.len, e.first, s.n, s.i, s.live, as_global(e.ob), as_global(e.root), gl, is_unit);
+  if (is_unit) as_global(e.unit_status)[s.i >> gl] = (uint8_t)st;
 }
 
 // range_status / range_first_bad of range blockIdx.x from the status bytes the launches before this one wrote (16 at a time between
@@ -1987,15 +1884,15 @@ __host__ __device__ __forceinline__ OpenShape open_shape(uint32_t gl) {
   return s;
 }
 
-// blocks: block 0's first byte; w: the tile's place in the window
+// blocks: block 0's first byte; w: the tile's place in the window.  (Every chunk is whole and the file's length is not known: the lanes
+// call chunk_cv with 1 024 bytes where the other tile bodies call tile_chunk_cvs with the length.)
 template <bool GRP>
 __device__ __forceinline__ void open_tile_body(const uint8_t *__restrict__ window, uint32_t w, uint64_t tile, uint8_t *__restrict__ blocks,
                                                uint32_t *__restrict__ tile_cv, uint32_t gl) {
   __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
   uint32_t h[8];
   chunk_cv(window + ((uint64_t)w * B3W_TILE + threadIdx.x) * 1024, 1024, tile * B3W_TILE + threadIdx.x, 0, h);
-  reinterpret_cast<uint4 *>(cv + threadIdx.x * 8)[0] = make_uint4(h[0], h[1], h[2], h[3]);
-  reinterpret_cast<uint4 *>(cv + threadIdx.x * 8)[1] = make_uint4(h[4], h[5], h[6], h[7]);
+  put_cv(cv, threadIdx.x, h);
   merge_in_lds<B3W_TILE, GRP>(cv, B3W_TILE, 1, B3W_TILE, blocks + tile * (((B3W_TILE >> gl) - 1) * 64), false, gl);
   if (threadIdx.x < 8) tile_cv[tile * 8 + threadIdx.x] = cv[threadIdx.x];
 }
@@ -2021,41 +1918,31 @@ __global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_open_tile_many_group_
   open_tile_body<true>(r.window, w, (uint64_t)r.tile0 + w, r.ob, r.cv, r.gl);
 }
 
-// The blocks of the `tiles` full tiles of a file of `len` bytes (tiles MiB <= len) to their places in its outboard, and the header.  A
-// workgroup takes a piece of at most OPEN_PIECE bytes of one block (gl <= 2) or 2 .. 16 whole blocks, 256 >> tpw_log lanes a block; which
-// tile it is comes from blockIdx.x by division, the place from preorder_pos: once per workgroup where the workgroup has one block.
-// Source and destination are different buffers and no two workgroups share a byte of either.
-// A file of EXACTLY one full tile has no storey above and no tail: its root is the ROOT-flagged parent compression of the block's first
-// node (left CV || right CV of the tile's top merge, stored for every gl <= 6), which workgroup 0 computes here.
-__global__ __launch_bounds__(256) void b3w_bao_stream_open_relocate_kernel(const uint8_t *__restrict__ blocks, uint64_t len, uint32_t tiles,
-                                                                           uint32_t gl, uint8_t *__restrict__ ob, uint32_t *__restrict__ root) {
+// What one lane of relocation workgroup wg (of those of one file, open_shape(gl)) moves.  A workgroup takes a piece of at most OPEN_PIECE
+// bytes of one block (gl <= 2) or 2 .. 16 whole blocks, L = 256 >> tpw_log lanes a block: bytes [at, at + nb) of the block of `tile`, as
+// lane `lane` of L.  pos_tile: the tile whose pre-order place the lane needs — the workgroup's first where the workgroup has one block,
+// so that the place is found once per workgroup.
+struct BlockPiece { uint32_t tile, pos_tile, piece, lane, L, at, nb, bb; };
+__device__ __forceinline__ BlockPiece block_piece(uint32_t gl, uint32_t wg) {
   const OpenShape s = open_shape(gl);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    *reinterpret_cast<uint2 *>(ob) = make_uint2((uint32_t)len, (uint32_t)(len >> 32));
-    if (len == (uint64_t)B3W_TILE * 1024) {
-      uint32_t m[16], ivv[8], o[8];
-      load_node(blocks, m);
-      iv(ivv);
-      blake3_cv(ivv, m, 0, 0, 64, 4u | 8u, o);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) root[k] = o[k];
-    }
-  }
-  const uint32_t L = 256u >> s.tpw_log, lane = threadIdx.x & (L - 1);
-  const uint32_t wg_tile = (blockIdx.x / s.ppb) << s.tpw_log, piece = blockIdx.x % s.ppb;
-  const uint32_t tile = wg_tile + (threadIdx.x >> (8 - s.tpw_log));
-  if (tile >= tiles) return;
-  const uint64_t G1 = (1ull << gl) - 1, ng = (((len + 1023) / 1024) + G1) >> gl;
-  const uint32_t sh = 10 - gl;                            // a tile is 1 << sh groups
-  const uint64_t pos = s.tpw_log == 0 ? preorder_pos(ng, (uint64_t)wg_tile << sh, 1ull << sh) : preorder_pos(ng, (uint64_t)tile << sh, 1ull << sh);
-  const uint32_t at = piece * OPEN_PIECE, nb = s.bb - at < OPEN_PIECE ? s.bb - at : OPEN_PIECE;     // (a multiple of 64)
-  const uint8_t *__restrict__ src = blocks + (uint64_t)tile * s.bb + at;                             // (8 off a 16-byte boundary)
-  uint8_t *__restrict__ dst = ob + 8 + pos * 64 + at;
-  if (((uintptr_t)dst & 15) == 8) {                       // a 16-byte-aligned outboard: the blocks' phase
-    if (lane == 0) {
-      *reinterpret_cast<uint2 *>(dst) = *reinterpret_cast<const uint2 *>(src);
-      *reinterpret_cast<uint2 *>(dst + nb - 8) = *reinterpret_cast<const uint2 *>(src + nb - 8);
-    }
+  BlockPiece p;
+  p.L = 256u >> s.tpw_log; p.lane = threadIdx.x & (p.L - 1);
+  const uint32_t wg_tile = (wg / s.ppb) << s.tpw_log;
+  p.piece = wg % s.ppb;
+  p.tile = wg_tile + (threadIdx.x >> (8 - s.tpw_log));
+  p.pos_tile = s.tpw_log == 0 ? wg_tile : p.tile;
+  p.bb = s.bb; p.at = p.piece * OPEN_PIECE;
+  p.nb = s.bb - p.at < OPEN_PIECE ? s.bb - p.at : OPEN_PIECE;         // (a multiple of 64)
+  return p;
+}
+
+// nb bytes of a block from src to dst by L lanes.  Source and destination are different buffers and no two workgroups share a byte of
+// either.  Both at 8 modulo 16 (the blocks' phase in a staging area and in a 16-byte-aligned outboard): an 8-byte head, 16-byte pieces,
+// an 8-byte tail; any other pair of phases: 8 bytes at a time.
+__device__ __forceinline__ void move_piece(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint32_t nb, uint32_t lane, uint32_t L) {
+  if (((uintptr_t)dst & 15) == 8 && ((uintptr_t)src & 15) == 8) {
+    uint2 head = make_uint2(0, 0), tail = make_uint2(0, 0);
+    if (lane == 0) { head = *reinterpret_cast<const uint2 *>(src); tail = *reinterpret_cast<const uint2 *>(src + nb - 8); }
     // the body: (nb - 16) / 16 <= 4 L pieces whatever gl is (nb <= OPEN_PIECE >> tpw_log, L = 256 >> tpw_log), so a lane has at most
     // four; all four loads are issued before the first store (the compiler cannot know that dst and src never meet), a lane with
     // fewer pieces loading the piece's first bytes again in place of a branch around the load.  The empty asm keeps the compiler
@@ -2064,82 +1951,62 @@ __global__ __launch_bounds__(256) void b3w_bao_stream_open_relocate_kernel(const
 #pragma unroll
     for (uint32_t k = 0; k < 4; ++k) { const uint32_t o = 8 + (lane + k * L) * 16; v[k] = *reinterpret_cast<const uint4 *>(src + (o < nb - 8 ? o : 8)); }
     asm volatile("" : "+v"(v[0].x), "+v"(v[0].y), "+v"(v[0].z), "+v"(v[0].w), "+v"(v[1].x), "+v"(v[1].y), "+v"(v[1].z), "+v"(v[1].w),
-                      "+v"(v[2].x), "+v"(v[2].y), "+v"(v[2].z), "+v"(v[2].w), "+v"(v[3].x), "+v"(v[3].y), "+v"(v[3].z), "+v"(v[3].w));
+                      "+v"(v[2].x), "+v"(v[2].y), "+v"(v[2].z), "+v"(v[2].w), "+v"(v[3].x), "+v"(v[3].y), "+v"(v[3].z), "+v"(v[3].w),
+                      "+v"(head.x), "+v"(head.y), "+v"(tail.x), "+v"(tail.y));
+    if (lane == 0) { *reinterpret_cast<uint2 *>(dst) = head; *reinterpret_cast<uint2 *>(dst + nb - 8) = tail; }
 #pragma unroll
     for (uint32_t k = 0; k < 4; ++k) { const uint32_t o = 8 + (lane + k * L) * 16; if (o < nb - 8) *reinterpret_cast<uint4 *>(dst + o) = v[k]; }
-  } else {                                                // an outboard at 8 modulo 16: 8 bytes at a time, nb / 8 <= 8 L pieces
-    for (uint32_t r = 0; r < 2; ++r) {
-      uint2 v[4];
+  } else {                                                // nb / 8 <= 8 L pieces
+    uint2 v[8];
 #pragma unroll
-      for (uint32_t k = 0; k < 4; ++k) { const uint32_t o = (lane + (4 * r + k) * L) * 8; v[k] = *reinterpret_cast<const uint2 *>(src + (o < nb ? o : 0)); }
-      asm volatile("" : "+v"(v[0].x), "+v"(v[0].y), "+v"(v[1].x), "+v"(v[1].y), "+v"(v[2].x), "+v"(v[2].y), "+v"(v[3].x), "+v"(v[3].y));
+    for (uint32_t k = 0; k < 8; ++k) { const uint32_t o = (lane + k * L) * 8; v[k] = *reinterpret_cast<const uint2 *>(src + (o < nb ? o : 0)); }
+    asm volatile("" : "+v"(v[0].x), "+v"(v[0].y), "+v"(v[1].x), "+v"(v[1].y), "+v"(v[2].x), "+v"(v[2].y), "+v"(v[3].x), "+v"(v[3].y),
+                      "+v"(v[4].x), "+v"(v[4].y), "+v"(v[5].x), "+v"(v[5].y), "+v"(v[6].x), "+v"(v[6].y), "+v"(v[7].x), "+v"(v[7].y));
 #pragma unroll
-      for (uint32_t k = 0; k < 4; ++k) { const uint32_t o = (lane + (4 * r + k) * L) * 8; if (o < nb) *reinterpret_cast<uint2 *>(dst + o) = v[k]; }
-    }
+    for (uint32_t k = 0; k < 8; ++k) { const uint32_t o = (lane + k * L) * 8; if (o < nb) *reinterpret_cast<uint2 *>(dst + o) = v[k]; }
   }
+}
+
+// the CV of a full tile from its block's first node (left CV || right CV of the tile's top merge, stored for every gl <= 6) to `out`;
+// root: 8 where the file is EXACTLY this one tile, which has no storey above: the compression is ROOT-flagged and is the file's root
+__device__ __forceinline__ void block_cv(const uint8_t *__restrict__ block, uint32_t root, uint32_t *__restrict__ out) {
+  uint32_t m[16], ivv[8], o[8];
+  load_node(block, m);
+  iv(ivv);
+  blake3_cv(ivv, m, 0, 0, 64, 4u | root, o);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) out[k] = o[k];
+}
+
+// The blocks of the `tiles` full tiles of a file of `len` bytes (tiles MiB <= len) to their places in its outboard, and the header; wg:
+// the workgroup's index among the file's.  Which tile a lane moves comes from wg by division (block_piece), the place from preorder_pos.
+// A file of exactly one full tile has no tail either: workgroup 0 computes its root here.
+__device__ __forceinline__ void open_relocate_body(const uint8_t *__restrict__ blocks, uint64_t len, uint32_t tiles, uint32_t gl, uint8_t *__restrict__ ob,
+                                                   uint32_t *__restrict__ root, uint32_t wg) {
+  if (wg == 0 && threadIdx.x == 0) {
+    *reinterpret_cast<uint2 *>(ob) = make_uint2((uint32_t)len, (uint32_t)(len >> 32));
+    if (len == (uint64_t)B3W_TILE * 1024) block_cv(blocks, 8u, root);
+  }
+  const BlockPiece p = block_piece(gl, wg);
+  if (p.tile >= tiles) return;
+  const uint64_t G1 = (1ull << gl) - 1, ng = (((len + 1023) / 1024) + G1) >> gl;
+  const uint32_t sh = 10 - gl;                            // a tile is 1 << sh groups
+  const uint64_t pos = preorder_pos(ng, (uint64_t)p.pos_tile << sh, 1ull << sh);
+  move_piece(ob + 8 + pos * 64 + p.at, blocks + (uint64_t)p.tile * p.bb + p.at, p.nb, p.lane, p.L);
+}
+
+__global__ __launch_bounds__(256) void b3w_bao_stream_open_relocate_kernel(const uint8_t *__restrict__ blocks, uint64_t len, uint32_t tiles,
+                                                                           uint32_t gl, uint8_t *__restrict__ ob, uint32_t *__restrict__ root) {
+  open_relocate_body(blocks, len, tiles, gl, ob, root, blockIdx.x);
 }
 
 // The same for a table of sessions, one grid: a row per file of one full tile or more, with window = the session's blocks, ob and root
 // the file's, len its now-known length, tile0 = its count of full tiles and gl its group_log.  A row has
 // ((tile0 + 2^tpw_log - 1) >> tpw_log) * ppb workgroups of open_shape(gl), which differs from row to row; a workgroup lies in one row,
-// so its outboard's phase, and with it the choice between the 16-byte and the 8-byte moves, is one for all its lanes.  The body is the
-// kernel's above restated with the row's fields and the workgroup's index within the row (sharing one inlined body changed that
-// kernel's ISA: DESIGN.md 8g).
+// so its outboard's phase, and with it the choice between the 16-byte and the 8-byte moves, is one for all its lanes.
 __global__ __launch_bounds__(256) void b3w_bao_stream_open_relocate_many_kernel(const ManyRow *__restrict__ rows, uint32_t n_rows) {
   const ManyRow row = many_row(rows, n_rows, blockIdx.x);
-  const uint8_t *__restrict__ blocks = row.window;
-  uint8_t *__restrict__ ob = row.ob;
-  uint32_t *__restrict__ root = row.root;
-  const uint64_t len = row.len;
-  const uint32_t tiles = row.tile0, gl = row.gl, wg = blockIdx.x - row.first;
-  const OpenShape s = open_shape(gl);
-  if (wg == 0 && threadIdx.x == 0) {
-    *reinterpret_cast<uint2 *>(ob) = make_uint2((uint32_t)len, (uint32_t)(len >> 32));
-    if (len == (uint64_t)B3W_TILE * 1024) {
-      uint32_t m[16], ivv[8], o[8];
-      load_node(blocks, m);
-      iv(ivv);
-      blake3_cv(ivv, m, 0, 0, 64, 4u | 8u, o);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) root[k] = o[k];
-    }
-  }
-  const uint32_t L = 256u >> s.tpw_log, lane = threadIdx.x & (L - 1);
-  const uint32_t wg_tile = (wg / s.ppb) << s.tpw_log, piece = wg % s.ppb;
-  const uint32_t tile = wg_tile + (threadIdx.x >> (8 - s.tpw_log));
-  if (tile >= tiles) return;
-  const uint64_t G1 = (1ull << gl) - 1, ng = (((len + 1023) / 1024) + G1) >> gl;
-  const uint32_t sh = 10 - gl;                            // a tile is 1 << sh groups
-  const uint64_t pos = s.tpw_log == 0 ? preorder_pos(ng, (uint64_t)wg_tile << sh, 1ull << sh) : preorder_pos(ng, (uint64_t)tile << sh, 1ull << sh);
-  const uint32_t at = piece * OPEN_PIECE, nb = s.bb - at < OPEN_PIECE ? s.bb - at : OPEN_PIECE;     // (a multiple of 64)
-  const uint8_t *__restrict__ src = blocks + (uint64_t)tile * s.bb + at;                             // (8 off a 16-byte boundary)
-  uint8_t *__restrict__ dst = ob + 8 + pos * 64 + at;
-  if (((uintptr_t)dst & 15) == 8) {                       // a 16-byte-aligned outboard: the blocks' phase
-    if (lane == 0) {
-      *reinterpret_cast<uint2 *>(dst) = *reinterpret_cast<const uint2 *>(src);
-      *reinterpret_cast<uint2 *>(dst + nb - 8) = *reinterpret_cast<const uint2 *>(src + nb - 8);
-    }
-    // the body: (nb - 16) / 16 <= 4 L pieces whatever gl is (nb <= OPEN_PIECE >> tpw_log, L = 256 >> tpw_log), so a lane has at most
-    // four; all four loads are issued before the first store (the compiler cannot know that dst and src never meet), a lane with
-    // fewer pieces loading the piece's first bytes again in place of a branch around the load.  The empty asm keeps the compiler
-    // from sinking each load into the branch of its store, where every one would be waited for alone.
-    uint4 v[4];
-#pragma unroll
-    for (uint32_t k = 0; k < 4; ++k) { const uint32_t o = 8 + (lane + k * L) * 16; v[k] = *reinterpret_cast<const uint4 *>(src + (o < nb - 8 ? o : 8)); }
-    asm volatile("" : "+v"(v[0].x), "+v"(v[0].y), "+v"(v[0].z), "+v"(v[0].w), "+v"(v[1].x), "+v"(v[1].y), "+v"(v[1].z), "+v"(v[1].w),
-                      "+v"(v[2].x), "+v"(v[2].y), "+v"(v[2].z), "+v"(v[2].w), "+v"(v[3].x), "+v"(v[3].y), "+v"(v[3].z), "+v"(v[3].w));
-#pragma unroll
-    for (uint32_t k = 0; k < 4; ++k) { const uint32_t o = 8 + (lane + k * L) * 16; if (o < nb - 8) *reinterpret_cast<uint4 *>(dst + o) = v[k]; }
-  } else {                                                // an outboard at 8 modulo 16: 8 bytes at a time, nb / 8 <= 8 L pieces
-    for (uint32_t r = 0; r < 2; ++r) {
-      uint2 v[4];
-#pragma unroll
-      for (uint32_t k = 0; k < 4; ++k) { const uint32_t o = (lane + (4 * r + k) * L) * 8; v[k] = *reinterpret_cast<const uint2 *>(src + (o < nb ? o : 0)); }
-      asm volatile("" : "+v"(v[0].x), "+v"(v[0].y), "+v"(v[1].x), "+v"(v[1].y), "+v"(v[2].x), "+v"(v[2].y), "+v"(v[3].x), "+v"(v[3].y));
-#pragma unroll
-      for (uint32_t k = 0; k < 4; ++k) { const uint32_t o = (lane + (4 * r + k) * L) * 8; if (o < nb) *reinterpret_cast<uint2 *>(dst + o) = v[k]; }
-    }
-  }
+  open_relocate_body(row.window, row.len, row.tile0, row.gl, row.ob, row.root, blockIdx.x - row.first);
 }
 
 // ---- resident files after appends and truncations: the kept blocks from the outboard of the old length to that of the new ----------------
@@ -2165,64 +2032,24 @@ struct ResRow {
 };
 
 __global__ __launch_bounds__(256) void b3w_bao_resize_relocate_kernel(const ResRow *__restrict__ rows, uint32_t n_rows) {
-  uint32_t lo = 0, hi = n_rows;
-  while (hi - lo > 1) {                                   // the row whose workgroups include this one: the last with first <= blockIdx.x
-    const uint32_t mid = (lo + hi) / 2;
-    if (rows[mid].first <= blockIdx.x) lo = mid; else hi = mid;
-  }
-  const ResRow row = rows[lo];
+  const ResRow row = rows[find_first(rows, 0, n_rows, blockIdx.x)];
   const uint8_t *__restrict__ old_ob = as_global(row.old_ob);
   uint8_t *__restrict__ new_ob = as_global(row.new_ob);
   const uint64_t len = row.new_len;
-  const uint32_t tiles = row.tiles, gl = row.gl, wg = blockIdx.x - row.first;
-  const OpenShape s = open_shape(gl);
+  const uint32_t gl = row.gl, wg = blockIdx.x - row.first;
   if (wg == 0 && threadIdx.x == 0) *reinterpret_cast<uint2 *>(new_ob) = make_uint2((uint32_t)len, (uint32_t)(len >> 32));
-  const uint32_t L = 256u >> s.tpw_log, lane = threadIdx.x & (L - 1);
-  const uint32_t wg_tile = (wg / s.ppb) << s.tpw_log, piece = wg % s.ppb;
-  const uint32_t tile = wg_tile + (threadIdx.x >> (8 - s.tpw_log));
-  if (tile >= tiles) return;
+  const BlockPiece p = block_piece(gl, wg);
+  if (p.tile >= row.tiles) return;
   const uint64_t G1 = (1ull << gl) - 1;
   const uint64_t ng_old = (((row.old_len + 1023) / 1024) + G1) >> gl, ng_new = (((len + 1023) / 1024) + G1) >> gl;
   const uint32_t sh = 10 - gl;                            // a tile is 1 << sh groups
-  const uint64_t a = (uint64_t)(s.tpw_log == 0 ? wg_tile : tile) << sh;
-  const uint64_t pos_old = preorder_pos(ng_old, a, 1ull << sh), pos_new = preorder_pos(ng_new, a, 1ull << sh);
-  const uint32_t at = piece * OPEN_PIECE, nb = s.bb - at < OPEN_PIECE ? s.bb - at : OPEN_PIECE;     // (a multiple of 64)
-  const uint8_t *__restrict__ src = old_ob + 8 + pos_old * 64 + at;
-  uint8_t *__restrict__ dst = new_ob + 8 + pos_new * 64 + at;
-  if (((uintptr_t)dst & 15) == 8 && ((uintptr_t)src & 15) == 8) {     // both outboards 16-byte aligned: an 8-byte head, 16-byte pieces, an 8-byte tail
-    uint2 head = make_uint2(0, 0), tail = make_uint2(0, 0);
-    if (lane == 0) { head = *reinterpret_cast<const uint2 *>(src); tail = *reinterpret_cast<const uint2 *>(src + nb - 8); }
-    // (nb - 16) / 16 <= 4 L pieces whatever gl is, so a lane has at most four; every load of a lane is issued before its first store, a
-    // lane with fewer pieces loading the piece's first bytes again in place of a branch around the load (the relocation above)
-    uint4 v[4];
-#pragma unroll
-    for (uint32_t k = 0; k < 4; ++k) { const uint32_t o = 8 + (lane + k * L) * 16; v[k] = *reinterpret_cast<const uint4 *>(src + (o < nb - 8 ? o : 8)); }
-    asm volatile("" : "+v"(v[0].x), "+v"(v[0].y), "+v"(v[0].z), "+v"(v[0].w), "+v"(v[1].x), "+v"(v[1].y), "+v"(v[1].z), "+v"(v[1].w),
-                      "+v"(v[2].x), "+v"(v[2].y), "+v"(v[2].z), "+v"(v[2].w), "+v"(v[3].x), "+v"(v[3].y), "+v"(v[3].z), "+v"(v[3].w),
-                      "+v"(head.x), "+v"(head.y), "+v"(tail.x), "+v"(tail.y));
-    if (lane == 0) { *reinterpret_cast<uint2 *>(dst) = head; *reinterpret_cast<uint2 *>(dst + nb - 8) = tail; }
-#pragma unroll
-    for (uint32_t k = 0; k < 4; ++k) { const uint32_t o = 8 + (lane + k * L) * 16; if (o < nb - 8) *reinterpret_cast<uint4 *>(dst + o) = v[k]; }
-  } else {                                                // any other pair of phases: 8 bytes at a time, nb / 8 <= 8 L pieces
-    uint2 v[8];
-#pragma unroll
-    for (uint32_t k = 0; k < 8; ++k) { const uint32_t o = (lane + k * L) * 8; v[k] = *reinterpret_cast<const uint2 *>(src + (o < nb ? o : 0)); }
-    asm volatile("" : "+v"(v[0].x), "+v"(v[0].y), "+v"(v[1].x), "+v"(v[1].y), "+v"(v[2].x), "+v"(v[2].y), "+v"(v[3].x), "+v"(v[3].y),
-                      "+v"(v[4].x), "+v"(v[4].y), "+v"(v[5].x), "+v"(v[5].y), "+v"(v[6].x), "+v"(v[6].y), "+v"(v[7].x), "+v"(v[7].y));
-#pragma unroll
-    for (uint32_t k = 0; k < 8; ++k) { const uint32_t o = (lane + k * L) * 8; if (o < nb) *reinterpret_cast<uint2 *>(dst + o) = v[k]; }
-  }
-  // the kept tile's CV: left CV || right CV of its top merge is the block's first node, stored for every gl <= 6.  A file that is now
-  // EXACTLY this one tile has no storey above: the compression is ROOT-flagged and is the file's root.
-  if (piece == 0 && lane == 0) {
+  const uint64_t a = (uint64_t)p.pos_tile << sh;
+  const uint8_t *__restrict__ src = old_ob + 8 + preorder_pos(ng_old, a, 1ull << sh) * 64 + p.at;
+  move_piece(new_ob + 8 + preorder_pos(ng_new, a, 1ull << sh) * 64 + p.at, src, p.nb, p.lane, p.L);
+  // the kept tile's CV, by the lane that moves the block's first node
+  if (p.piece == 0 && p.lane == 0) {
     const bool sole = len == (uint64_t)B3W_TILE * 1024;
-    uint32_t m[16], ivv[8], o[8];
-    load_node(src, m);
-    iv(ivv);
-    blake3_cv(ivv, m, 0, 0, 64, 4u | (sole ? 8u : 0u), o);
-    uint32_t *__restrict__ out = sole ? as_global(row.root) : as_global(row.cv) + (uint64_t)tile * 8;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) out[k] = o[k];
+    block_cv(src, sole ? 8u : 0u, sole ? as_global(row.root) : as_global(row.cv) + (uint64_t)p.tile * 8);
   }
 }
 
@@ -3156,17 +2983,6 @@ b3w_bao_stream *stream_new(b3w_ctx *ctx, uint32_t kind, uint64_t len, uint32_t g
 }
 
 // ---- open-length sessions: the host side ---------------------------------------------------------------------------------------------
-// pre-order position of the node over chunks (or groups) [a, a + size) of a tree over `total`: preorder_pos on the host
-uint64_t host_preorder_pos(uint64_t total, uint64_t a, uint64_t size) {
-  uint64_t p = 0, lo = 0, cnt = total;
-  while (cnt > 1 && !(lo == a && cnt == size)) {
-    uint64_t k = 1;
-    while (k * 2 < cnt) k *= 2;
-    if (a < lo + k) { p += 1; cnt = k; } else { p += k; lo += k; cnt -= k; }
-  }
-  return p;
-}
-
 uint64_t open_cap_tiles(uint64_t capacity) { return (num_chunks(capacity) + B3W_TILE - 1) / B3W_TILE; }   // scratch slots: the tail's tile included
 
 // the per-window rules of an open session (whole tiles only, inside the capacity, each tile once): the reason, or nullptr
@@ -3596,7 +3412,7 @@ uint64_t b3w_bao_stream_open_block_pos(uint64_t len, uint32_t group_log, uint64_
   const uint64_t TB = (uint64_t)B3W_TILE * 1024;
   if (group_log > B3W_BAO_MAX_GROUP_LOG || tile >= len / TB) return UINT64_MAX;
   const uint64_t G1 = (1ull << group_log) - 1;
-  return host_preorder_pos((num_chunks(len) + G1) >> group_log, (tile * B3W_TILE) >> group_log, B3W_TILE >> group_log);
+  return preorder_pos((num_chunks(len) + G1) >> group_log, (tile * B3W_TILE) >> group_log, B3W_TILE >> group_log);
 }
 
 int32_t b3w_bao_stream_open_begin(b3w_ctx *ctx, uint64_t capacity_bytes, uint32_t group_log, void *d_staging, uint64_t staging_bytes, void *d_scratch,
@@ -4238,7 +4054,7 @@ void host_resize_walk(const uint8_t *data, uint64_t len, uint64_t n, uint32_t gl
   const uint32_t sh = 10 - gl;
   uint32_t m[16], ivv[8];
   if (cnt == (1ull << sh) && !(first & (cnt - 1)) && (first >> sh) < kept) {
-    const uint8_t *src = old_nodes + 64 * host_preorder_pos(old_units, first, cnt);
+    const uint8_t *src = old_nodes + 64 * preorder_pos(old_units, first, cnt);
     memcpy(nodes + 64 * pos, src, (size_t)(cnt - 1) * 64);
     memcpy(m, src, 64);
     iv(ivv);
