@@ -208,6 +208,13 @@ def lib():
         "b3w_bao_slice_arena_device": (i32, [vp, vp, u64, vp, vp, u32, u32, vp, vp, vp, u32, vp, vp]),
         "b3w_bao_slice_ingest_device": (i32, [vp, vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp]),
         "b3w_bao_slice_ingest": (i32, [vp, u64, u64, u64, vp, u32, vp, vp, ctypes.POINTER(i32)]),
+        "b3w_bao_have_layout": (u64, [vp, u32, vp]),
+        "b3w_bao_slice_ingest_have_device": (i32, [vp, vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp]),
+        "b3w_bao_have_runs_scratch_bytes": (u64, [vp, u32]),
+        "b3w_bao_have_runs_device": (i32, [vp, vp, vp, u32, u32, u32, u64, vp, vp, vp, vp, vp, vp, u64, vp]),
+        "b3w_bao_have_from_status_device": (i32, [vp, vp, vp, u32, u32, vp, vp]),
+        "b3w_bao_have_runs": (i32, [vp, u64, u32, u32, u64, vp, vp, vp, vp]),
+        "b3w_bao_have_from_status": (i32, [vp, u64, u32, vp]),
         "b3w_bao_update_scratch_bytes": (u64, [vp, vp, vp, vp, u32]),
         "b3w_bao_outboard_update_batch_device": (i32, [vp, vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, u32, vp, u64, vp]),
         "b3w_bao_outboard_update": (i32, [vp, u64, vp, u32, vp, vp, u32, vp]),
@@ -253,7 +260,9 @@ EXPORTED_SYMBOLS = ("b3w_abi_version", "b3w_identify_wasm", "b3w_create", "b3w_d
                     "b3w_bao_update_scratch_bytes", "b3w_bao_outboard_update_batch_device", "b3w_bao_outboard_update",
                     "b3w_bao_resize_kept_tiles", "b3w_bao_resize_scratch_bytes", "b3w_bao_outboard_resize_batch_device", "b3w_bao_outboard_resize",
                     "b3w_bao_verify_ranges_scratch_bytes", "b3w_bao_verify_ranges_batch_device", "b3w_bao_verify_ranges",
-                    "b3w_bao_slice_ingest_device", "b3w_bao_slice_ingest")
+                    "b3w_bao_slice_ingest_device", "b3w_bao_slice_ingest",
+                    "b3w_bao_have_layout", "b3w_bao_slice_ingest_have_device", "b3w_bao_have_runs_scratch_bytes", "b3w_bao_have_runs_device",
+                    "b3w_bao_have_from_status_device", "b3w_bao_have_runs", "b3w_bao_have_from_status")
 
 
 class graph_capture:

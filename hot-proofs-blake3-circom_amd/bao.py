@@ -22,6 +22,9 @@ verify_ranges_batch() is verify_batch() for the units that hold listed chunk ran
 them read, only their status bytes written, plus a status and a first bad unit per range (verify_ranges_host(): one file on the host).
 ingest_slices() is the receiver's side of slices: slices verified against the roots on the device, the verified ones' chunks put at
 their places in the arena and their path nodes at their places in the outboards (ingest_slice_host(): one slice on the host).
+have_new() / ingest_slices(d_have=) keep a bitmap of the chunks that have arrived on the device, have_runs() turns it into the
+missing (or present) chunk runs of every file and have_from_status() rebuilds it from verify_batch's statuses after a restart
+(have_runs_host(), have_from_status_host(): one file on the host; runs_chunks(): the runs as sample lists).
 The records are
 word for word those the chain planner writes for the same chunks (ChainPlanner.plan), so every step is the reference's
 prove_chunk_hash step (rust_fold/src/main.rs:41-203 over hash_with_path's slice, rust_fold/src/blake3_hash.rs:17-93)."""
@@ -521,7 +524,7 @@ def slices_arena(ctx, d_arena, offsets, lens, d_outboards, files, chunks, group_
 
 
 # ---- slices taken in: the receiver's side --------------------------------------------------------------------------------
-def ingest_slices(ctx, d_arena, offsets, lens, d_outboards, d_roots, files, chunks, d_slices, group_log=0, stream=0):
+def ingest_slices(ctx, d_arena, offsets, lens, d_outboards, d_roots, files, chunks, d_slices, group_log=0, stream=0, d_have=None):
     """The receiver's side, slices_arena's mirror image: the slices of samples (files[s], chunks[s]) in d_slices (packed as slice_layout
     says, e.g. slices_arena's tensor) are verified against the files' roots on the device, and every slice that VERIFIES puts its chunk's
     bytes at their place in d_arena (file f is bytes [offsets[f], offsets[f] + lens[f]), any byte offset), the stored nodes of its path
@@ -533,12 +536,22 @@ def ingest_slices(ctx, d_arena, offsets, lens, d_outboards, d_roots, files, chun
     slices of a 1 GiB file 0.18 ms, 65 536 1.52, every chunk 23.7 for 2.27 times the file's bytes in slices — where outboard_batch over
     the whole resident GiB takes 0.43 ms.  So: slices for the sparse fetch, the repair and the remote read, up to a few per cent of a
     file's chunks; a file that arrives whole goes through verify_stream / outboard_batch on its bytes alone.
+    d_have (have_new()'s tensor, or None): the arrival bitmap — every sample that verifies also sets its chunk's bit there
+    (b3w_bao_slice_ingest_have_device: the same launch, the same bytes written, about 0.6 % slower — 65 536 slices 1.534 ms against
+    1.525; have_runs() then lists what is missing).
     Returns dict(sample_status=<int32 CUDA tensor: 0 verified and written, 1 / 2 / 3 as STATUS>)."""
     off, ln, fi, ch = _arena_args("ingest_slices", d_arena, offsets, lens, d_outboards, files, chunks, group_log)
     sf = slice_layout(ln, fi, ch)
     assert d_roots.is_cuda and d_roots.is_contiguous() and d_roots.numel() >= ln.size * 8
     assert d_slices.is_cuda and d_slices.dtype == torch.uint8 and d_slices.is_contiguous() and d_slices.numel() >= int(sf[-1])
     st = torch.full((ch.size,), -1, dtype=torch.int32, device=d_slices.device)
+    if d_have is not None:
+        _have_tensor("ingest_slices", d_have, ln)
+        _chk(ctx, lib().b3w_bao_slice_ingest_have_device(ctx.handle, d_arena.data_ptr() if d_arena.numel() else None, d_arena.numel(), off.ctypes.data,
+                                                         ln.ctypes.data, ln.size, group_log, d_outboards.data_ptr(), d_roots.data_ptr(), fi.ctypes.data,
+                                                         ch.ctypes.data, ch.size, d_slices.data_ptr(), st.data_ptr(), d_have.data_ptr(), _stream(stream)),
+             "b3w_bao_slice_ingest_have_device")
+        return dict(sample_status=st)
     _chk(ctx, lib().b3w_bao_slice_ingest_device(ctx.handle, d_arena.data_ptr() if d_arena.numel() else None, d_arena.numel(), off.ctypes.data,
                                                 ln.ctypes.data, ln.size, group_log, d_outboards.data_ptr(), d_roots.data_ptr(), fi.ctypes.data,
                                                 ch.ctypes.data, ch.size, d_slices.data_ptr(), st.data_ptr(), _stream(stream)), "b3w_bao_slice_ingest_device")
@@ -568,6 +581,141 @@ def ingest_slice_host(data, outboard, length, chunk, root, slice_bytes, group_lo
     _chk(None, lib().b3w_bao_slice_ingest(sl, len(sl), length, chunk, rw.ctypes.data, group_log, d.ctypes.data if d.size else None, ob.ctypes.data,
                                           ctypes.byref(st)), "b3w_bao_slice_ingest")
     return st.value
+
+
+# ---- the arrival bitmap: which chunks have come in, and what is still missing ----------------------------------------------
+HAVE_KINDS = {"missing": 0, "present": 1}
+
+
+def have_layout(lens):
+    """-> word_first (numpy uint64 [n_files + 1]): file f owns words [word_first[f], word_first[f + 1]) of the bitmap, 64 chunks a
+    word; chunk c is bit c & 63 of word word_first[f] + (c >> 6); the last entry is the total"""
+    ln = _u64(lens)
+    word_first = np.zeros(ln.size + 1, dtype=np.uint64)
+    lib().b3w_bao_have_layout(ln.ctypes.data, ln.size, word_first.ctypes.data)
+    return word_first
+
+
+def have_new(lens, device="cuda"):
+    """a cleared bitmap for these files: an int64 tensor of have_layout's size (ingest_slices(..., d_have=) sets its bits)"""
+    return torch.zeros(int(have_layout(lens)[-1]), dtype=torch.int64, device=device)
+
+
+def _have_tensor(what, d_have, ln):
+    if not (isinstance(d_have, torch.Tensor) and d_have.is_cuda and d_have.dtype == torch.int64 and d_have.is_contiguous()
+            and d_have.numel() >= int(have_layout(ln)[-1])):
+        raise B3WError(100, f"{what}: d_have is not a contiguous int64 CUDA tensor of have_layout's size")
+
+
+def _have_kind(kind):
+    if kind not in HAVE_KINDS:
+        raise B3WError(100, f"kind {kind!r} is neither 'missing' nor 'present'")
+    return HAVE_KINDS[kind]
+
+
+def have_runs_bound(lens, group_log=0):
+    """the number of rows that always suffices: a file of u units has at most ceil(u / 2) runs of one kind"""
+    n = np.maximum(1, (_u64(lens) + np.uint64(1023)) // np.uint64(1024))
+    units = (n + np.uint64((1 << group_log) - 1)) >> np.uint64(group_log)
+    return int(((units + np.uint64(1)) // np.uint64(2)).sum())
+
+
+def have_runs(ctx, d_have, lens, kind="missing", group_log=0, capacity=None, stream=0):
+    """The bitmap as ascending run lists, made on the device in at most four launches: kind "missing" lists the units (chunks, or
+    groups of 2^group_log chunks, the last one possibly ragged) with at least one chunk clear, "present" those with every chunk set;
+    a run is a maximal stretch of such units of one file, its row (file, first chunk, number of chunks) clipped to the file's chunk
+    count — what verify_ranges_batch and outboard_update_batch take, and through runs_chunks() what slices_arena and ingest_slices
+    take.  capacity (None: have_runs_bound, which always suffices; 0: count only) bounds the rows written; n_runs is the number found
+    even above it.  Returns dict(files uint32, first_chunks uint64, n_chunks uint64: host numpy, the rows written; n_runs: int64 CUDA
+    [1]; file_have: int64 CUDA [n_files], the chunks each file holds — it is complete when that is its chunk count).  When not to
+    (MI355X): the C call never takes less than about 0.05 ms.  The missing rows of a file of 2^20 chunks are on the
+    host in 0.11 ms (1 % missing) to 0.22 ms (50 %), against 0.67 to 3.64 ms for an ingest's statuses copied to the host, scattered
+    into a map and made into rows with numpy; 262 144 files of 4 chunks take 0.66 ms against 8.18.  Nothing smaller was measured: with
+    a few files of a few thousand chunks a caller that has the statuses on the host anyway may do as well there.  This wrapper also
+    makes its output tensors on every call; a loop that matters keeps them and calls b3w_bao_have_runs_device."""
+    L = lib()
+    if not 0 <= group_log <= MAX_GROUP_LOG:
+        raise B3WError(100, f"group_log {group_log} is not in 0 .. {MAX_GROUP_LOG}")
+    k = _have_kind(kind)
+    ln = _u64(lens)
+    _have_tensor("have_runs", d_have, ln)
+    dev = d_have.device
+    cap = have_runs_bound(ln, group_log) if capacity is None else int(capacity)
+    run_file = torch.empty(cap, dtype=torch.int32, device=dev)
+    run_first = torch.empty(cap, dtype=torch.int64, device=dev)
+    run_count = torch.empty(cap, dtype=torch.int64, device=dev)
+    n_runs = torch.empty(1, dtype=torch.int64, device=dev)
+    file_have = torch.empty(ln.size, dtype=torch.int64, device=dev)
+    need = L.b3w_bao_have_runs_scratch_bytes(ln.ctypes.data, ln.size)
+    scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    _chk(ctx, L.b3w_bao_have_runs_device(ctx.handle, d_have.data_ptr(), ln.ctypes.data, ln.size, group_log, k, cap, run_file.data_ptr() if cap else None,
+                                         run_first.data_ptr() if cap else None, run_count.data_ptr() if cap else None, n_runs.data_ptr(),
+                                         file_have.data_ptr() if ln.size else None, scratch.data_ptr(), scratch.numel(), _stream(stream)),
+         "b3w_bao_have_runs_device")
+    rows = min(int(n_runs.item()), cap)
+    return dict(files=run_file[:rows].cpu().numpy().view(np.uint32), first_chunks=run_first[:rows].cpu().numpy().view(np.uint64),
+                n_chunks=run_count[:rows].cpu().numpy().view(np.uint64), n_runs=n_runs, file_have=file_have)
+
+
+def have_from_status(ctx, unit_status, lens, group_log=0, d_have=None, stream=0):
+    """After a restart: the bitmap from verify_batch's / verify_ranges_batch's unit_status (uint8 CUDA, packed as verify_layout says
+    for this group_log) over the half-filled arena and outboards.  Chunk c of file f is set where the status of its unit is 0 (0xFF,
+    a unit the ranged call was not asked about, reads as absent); every word is written whole, pad bits zero — the one call that clears
+    bits.  One launch.  d_have: written in place when given, made here otherwise -> d_have."""
+    if not 0 <= group_log <= MAX_GROUP_LOG:
+        raise B3WError(100, f"group_log {group_log} is not in 0 .. {MAX_GROUP_LOG}")
+    ln = _u64(lens)
+    assert unit_status.is_cuda and unit_status.dtype == torch.uint8 and unit_status.is_contiguous() and unit_status.numel() >= int(verify_layout(ln, group_log)[-1])
+    if d_have is None:
+        d_have = torch.empty(int(have_layout(ln)[-1]), dtype=torch.int64, device=unit_status.device)
+    _have_tensor("have_from_status", d_have, ln)
+    _chk(ctx, lib().b3w_bao_have_from_status_device(ctx.handle, unit_status.data_ptr(), ln.ctypes.data, ln.size, group_log, d_have.data_ptr(), _stream(stream)),
+         "b3w_bao_have_from_status_device")
+    return d_have
+
+
+def have_runs_host(have, length, kind="missing", group_log=0, capacity=None):
+    """have_runs for one file on the host (no GPU): have = the file's words (numpy uint64) -> (first_chunks, n_chunks: the rows
+    written, numpy uint64; n_runs: the number found; n_have: the chunks held)"""
+    if not 0 <= group_log <= MAX_GROUP_LOG:
+        raise B3WError(100, f"group_log {group_log} is not in 0 .. {MAX_GROUP_LOG}")
+    k = _have_kind(kind)
+    hv = _u64(have)
+    if hv.size != (num_chunks(length) + 63) // 64:
+        raise B3WError(100, "have_runs_host: the bitmap is not that of a file of this length")
+    cap = have_runs_bound([length], group_log) if capacity is None else int(capacity)
+    first, count = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64)
+    n_runs, n_have = ctypes.c_uint64(), ctypes.c_uint64()
+    _chk(None, lib().b3w_bao_have_runs(hv.ctypes.data, length, group_log, k, cap, first.ctypes.data if cap else None, count.ctypes.data if cap else None,
+                                       ctypes.byref(n_runs), ctypes.byref(n_have)), "b3w_bao_have_runs")
+    rows = min(n_runs.value, cap)
+    return first[:rows], count[:rows], n_runs.value, n_have.value
+
+
+def have_from_status_host(unit_status, length, group_log=0):
+    """have_from_status for one file on the host (no GPU): unit_status as verify_host returns it -> the file's words (numpy uint64)"""
+    if not 0 <= group_log <= MAX_GROUP_LOG:
+        raise B3WError(100, f"group_log {group_log} is not in 0 .. {MAX_GROUP_LOG}")
+    st = np.ascontiguousarray(unit_status, dtype=np.uint8)
+    n = num_chunks(length)
+    if st.size != (n + (1 << group_log) - 1) >> group_log:
+        raise B3WError(100, "have_from_status_host: the statuses are not those of a file of this length")
+    have = np.zeros((n + 63) // 64, dtype=np.uint64)
+    _chk(None, lib().b3w_bao_have_from_status(st.ctypes.data, length, group_log, have.ctypes.data), "b3w_bao_have_from_status")
+    return have
+
+
+def runs_chunks(files, first_chunks, n_chunks):
+    """have_runs' rows as sample lists -> (files uint32, chunks uint64), a sample per chunk in the rows' order: what slices_arena and
+    ingest_slices take"""
+    fi = np.ascontiguousarray(files, dtype=np.uint32)
+    fc, nc = _ranges(first_chunks, n_chunks)
+    if fi.size != fc.size:
+        raise B3WError(100, f"runs_chunks: {fi.size} files and {fc.size} ranges")
+    cnt = nc.astype(np.int64)
+    starts = np.cumsum(cnt) - cnt
+    within = np.arange(int(cnt.sum()), dtype=np.int64) - np.repeat(starts, cnt)
+    return np.repeat(fi, cnt), (np.repeat(fc, cnt).astype(np.int64) + within).astype(np.uint64)
 
 
 # ---- verification: whole files against their outboards ------------------------------------------------------------------

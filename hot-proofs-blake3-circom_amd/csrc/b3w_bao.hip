@@ -1042,10 +1042,13 @@ __device__ __forceinline__ void put16(uint8_t *__restrict__ dst, const uint8_t *
   }
 }
 
-template <int K>
+// HAVE: a verified sample also ORs its chunk's bit into the arrival bitmap (b3w_bao_have_layout: chunk c of file f is bit c & 63 of word
+// word_first[f] + (c >> 6)), one atomicOr by the sample's leader behind its stores; the word offsets lie behind the rows of `desc`.
+template <int K, bool HAVE = false>
 __global__ __launch_bounds__(64) void b3w_bao_slice_ingest_kernel(const uint8_t *__restrict__ slices, const uint32_t *__restrict__ roots,
                                                                   const uint64_t *__restrict__ desc, uint32_t n_samples, uint32_t gl,
-                                                                  uint8_t *__restrict__ arena, uint8_t *__restrict__ obs, int32_t *__restrict__ status) {
+                                                                  uint8_t *__restrict__ arena, uint8_t *__restrict__ obs, int32_t *__restrict__ status,
+                                                                  unsigned long long *__restrict__ have) {
   const uint32_t lane = threadIdx.x, t = lane & (K - 1), base = lane - t;
   const uint32_t s = blockIdx.x * (64u / K) + lane / K;
   const bool valid = s < n_samples, leader = valid && t == 0;
@@ -1118,6 +1121,7 @@ __global__ __launch_bounds__(64) void b3w_bao_slice_ingest_kernel(const uint8_t 
   const uint32_t whole = bytes & ~15u;
   for (uint32_t o = t * 16; o < whole; o += K * 16) put16(dst + o, body + o);
   for (uint32_t o = whole + t; o < bytes; o += K) dst[o] = body[o];
+  if (HAVE && t == 0) atomicOr(have + desc[6 * (uint64_t)n_samples + d[4]] + (c >> 6), 1ull << (c & 63));
 }
 
 // ---- verification: whole files against their outboards ---------------------------------------------------------------------
@@ -2707,11 +2711,17 @@ int32_t b3w_bao_slice_ingest(const uint8_t *slice, uint64_t slice_len, uint64_t 
   return B3W_OK;
 }
 
-int32_t b3w_bao_slice_ingest_device(b3w_ctx *ctx, uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
-                                    uint32_t n_files, uint32_t group_log, uint8_t *d_outboards, const uint32_t *d_roots, const uint32_t *host_files,
-                                    const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_slices, int32_t *d_sample_status, void *stream) {
+}  // extern "C"
+
+namespace {
+// b3w_bao_slice_ingest_device (HAVE false: d_have is not looked at) and b3w_bao_slice_ingest_have_device
+template <bool HAVE>
+int32_t slice_ingest(b3w_ctx *ctx, uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
+                     uint32_t n_files, uint32_t group_log, uint8_t *d_outboards, const uint32_t *d_roots, const uint32_t *host_files,
+                     const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_slices, int32_t *d_sample_status, uint64_t *d_have, void *stream) {
   if (!ctx) return B3W_E_BAD_ARGUMENT;
   if (group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "bao slice ingest: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
+  if (HAVE && (!d_have || ((uintptr_t)d_have & 7))) { ctx->last_error = "bao slice ingest: d_have is null or not 8-byte aligned"; return B3W_E_BAD_ARGUMENT; }
   if (!n_samples) return B3W_OK;
   if (!host_offsets || !host_lens || !d_outboards || !d_roots || !host_files || !host_chunks || !d_slices || !d_sample_status) {
     ctx->last_error = "bao slice ingest: a null pointer"; return B3W_E_BAD_ARGUMENT;
@@ -2743,7 +2753,8 @@ int32_t b3w_bao_slice_ingest_device(b3w_ctx *ctx, uint8_t *d_arena, uint64_t are
     at = slice_start(at + 8 + 64ull * P + (len - off < 1024 ? len - off : 1024));   // (b3w_bao_slice_size)
     if (P > longest) longest = P;
   }
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)desc_bytes, hipMemcpyHostToDevice, st));
+  if (HAVE) (void)b3w_bao_have_layout(host_lens, n_files, ob_first);                // (the outboard offsets are in the rows by now)
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)(desc_bytes + (HAVE ? ((uint64_t)n_files + 1) * 8 : 0)), hipMemcpyHostToDevice, st));
   // lanes a sample, from the batch's longest path P: node j is checked by lane j mod K, ceil(P / K) rounds beside the chunk's sixteen blocks,
   // and every lane fewer a sample is a leader more a wave in the stretch only leaders run.  Measured at P = 20: four lanes
   // (five rounds) beat sixteen (two) at 4 096 and at 65 536 slices, so four up to six rounds; sixteen for the longer paths (files past
@@ -2751,19 +2762,41 @@ int32_t b3w_bao_slice_ingest_device(b3w_ctx *ctx, uint8_t *d_arena, uint64_t are
   const char *env = getenv("B3W_SLICE_INGEST_LANES");
   const int lanes = env ? atoi(env) : (longest <= 24 ? 4 : 16);
   const uint64_t *d_desc = reinterpret_cast<const uint64_t *>(ctx->d_batch);
+  unsigned long long *have = HAVE ? reinterpret_cast<unsigned long long *>(d_have) : nullptr;
   if (lanes == 1)
-    hipLaunchKernelGGL(b3w_bao_slice_ingest_kernel<1>, dim3((n_samples + 63) / 64), dim3(64), 0, st, d_slices, d_roots, d_desc, n_samples, group_log, d_arena,
-                       d_outboards, d_sample_status);
+    hipLaunchKernelGGL((b3w_bao_slice_ingest_kernel<1, HAVE>), dim3((n_samples + 63) / 64), dim3(64), 0, st, d_slices, d_roots, d_desc, n_samples, group_log, d_arena,
+                       d_outboards, d_sample_status, have);
   else if (lanes == 4)
-    hipLaunchKernelGGL(b3w_bao_slice_ingest_kernel<4>, dim3((n_samples + 15) / 16), dim3(64), 0, st, d_slices, d_roots, d_desc, n_samples, group_log, d_arena,
-                       d_outboards, d_sample_status);
+    hipLaunchKernelGGL((b3w_bao_slice_ingest_kernel<4, HAVE>), dim3((n_samples + 15) / 16), dim3(64), 0, st, d_slices, d_roots, d_desc, n_samples, group_log, d_arena,
+                       d_outboards, d_sample_status, have);
   else
-    hipLaunchKernelGGL(b3w_bao_slice_ingest_kernel<16>, dim3((n_samples + 3) / 4), dim3(64), 0, st, d_slices, d_roots, d_desc, n_samples, group_log, d_arena,
-                       d_outboards, d_sample_status);
+    hipLaunchKernelGGL((b3w_bao_slice_ingest_kernel<16, HAVE>), dim3((n_samples + 3) / 4), dim3(64), 0, st, d_slices, d_roots, d_desc, n_samples, group_log, d_arena,
+                       d_outboards, d_sample_status, have);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(ctx, e, "bao slice ingest launch");
   HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
   return B3W_OK;
+}
+}  // namespace
+
+// b3w_bao_have.hip's way to the staging of the batch calls
+int32_t b3w_int_batch_staging(b3w_ctx *ctx, uint64_t bytes) { return batch_staging(ctx, bytes); }
+
+extern "C" {
+
+int32_t b3w_bao_slice_ingest_device(b3w_ctx *ctx, uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
+                                    uint32_t n_files, uint32_t group_log, uint8_t *d_outboards, const uint32_t *d_roots, const uint32_t *host_files,
+                                    const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_slices, int32_t *d_sample_status, void *stream) {
+  return slice_ingest<false>(ctx, d_arena, arena_bytes, host_offsets, host_lens, n_files, group_log, d_outboards, d_roots, host_files, host_chunks, n_samples,
+                             d_slices, d_sample_status, nullptr, stream);
+}
+
+int32_t b3w_bao_slice_ingest_have_device(b3w_ctx *ctx, uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
+                                         uint32_t n_files, uint32_t group_log, uint8_t *d_outboards, const uint32_t *d_roots, const uint32_t *host_files,
+                                         const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_slices, int32_t *d_sample_status,
+                                         uint64_t *d_have, void *stream) {
+  return slice_ingest<true>(ctx, d_arena, arena_bytes, host_offsets, host_lens, n_files, group_log, d_outboards, d_roots, host_files, host_chunks, n_samples,
+                            d_slices, d_sample_status, d_have, stream);
 }
 
 // ---- verification: whole files against their outboards ---------------------------------------------------------------------

@@ -149,4 +149,6 @@ int32_t b3w_int_commit_records(b3w_ctx *ctx, const b3w_commit_key *key, const ui
                                int32_t *d_status, void *stream, uint32_t *d_sums_out, void *trace_stream = nullptr, hipEvent_t trace_done = nullptr);
 int32_t b3w_int_commit_normalize(b3w_ctx *ctx, const b3w_commit_key *key, const uint32_t *d_sums, uint64_t n, uint8_t *d_points, void *stream);
 b3w_ctx *b3w_int_r1cs_ctx(const b3w_r1cs *r1cs);
+// b3w_bao.hip: the context's staging for the batch calls' tables (h_batch / d_batch) — waits for the previous batch call, grows both to `bytes`
+int32_t b3w_int_batch_staging(b3w_ctx *ctx, uint64_t bytes);
 constexpr uint64_t B3W_RING_SPARE_CAP = 26ull << 30;    // ring buffers a context keeps between chains: two 16 384-step nova buffers

@@ -940,7 +940,8 @@ int32_t b3w_bao_slice_arena_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_
  *   Samples may repeat, come in any order and share path nodes: every writer of a byte that writes at all writes the same verified
  *   value, so a good and a bad slice of one chunk in one call leave the good one's bytes.  Once every chunk of a file has come in
  *   its outboard is the provider's byte for byte (b3w_bao_outboard_batch_device / b3w_bao_group_outboard_batch_device), from the traffic
- *   itself, and every other call here applies to it.  The caller keeps track of which chunks have arrived (d_sample_status).
+ *   itself, and every other call here applies to it.  b3w_bao_slice_ingest_have_device ("the arrival bitmap" below) also records on the
+ *   device which chunks have arrived.
  * One launch; the per-sample table (48 bytes a sample) goes through the context's staging and nothing else is allocated; the host waits
  * for nothing but this context's previous batch call.  B3W_E_BAD_ARGUMENT before anything is written for what
  * b3w_bao_slice_arena_device refuses and for a null d_roots / d_sample_status.  n_samples == 0: a no-op.  Any context.  Asynchronous on
@@ -959,6 +960,75 @@ int32_t b3w_bao_slice_ingest_device(b3w_ctx *ctx, uint8_t *d_arena, uint64_t are
  * an empty file. */
 int32_t b3w_bao_slice_ingest(const uint8_t *slice, uint64_t slice_len, uint64_t preimage_len, uint64_t chunk, const uint32_t *root /* 8 u32 */,
                              uint32_t group_log, uint8_t *data, uint8_t *outboard, int32_t *out_status);
+
+/* ---- the arrival bitmap: which chunks have come in, and what is still missing (still ABI 1.4: new names only) -------
+ * A receiver that takes slices in needs to know which chunks it holds, what to ask for next and when a file is complete.  These calls
+ * keep that record on the device and turn it into the run lists b3w_bao_verify_ranges_batch_device and
+ * b3w_bao_outboard_update_batch_device take, so that fetch -> ingest -> "what is missing?" -> fetch closes without the caller copying
+ * and scattering statuses.
+ * THE BITMAP.  File f owns ceil(b3w_chain_num_chunks(len_f) / 64) words of 64 bits, from word word_first[f] of d_have; chunk c is bit
+ * c & 63 of word word_first[f] + (c >> 6).  One bit per CHUNK at every group_log (slices are of one chunk at every group_log); an empty
+ * file has one chunk and one bit.  The bits at and above the chunk count in a file's last word are pad bits: the library never sets
+ * them and every reader masks them, so a stray pad bit never makes a run past the end of a file.  d_have is 8-byte aligned; the
+ * caller clears it once; only b3w_bao_have_from_status_device ever clears a bit. */
+#define B3W_BAO_HAVE_MISSING 0
+#define B3W_BAO_HAVE_PRESENT 1
+/* Host only: word_first [n_files + 1] -> the total number of words (0 for a null pointer). */
+uint64_t b3w_bao_have_layout(const uint64_t *host_lens, uint32_t n_files, uint64_t *word_first /* n_files + 1 */);
+/* b3w_bao_slice_ingest_device with the record: the same arguments in the same order, d_have in front of the stream.  It writes byte
+ * for byte what that call writes — arena, outboards, statuses — and for every sample whose status is 0 it also ORs that chunk's bit
+ * into d_have (one 8-byte atomic OR by the sample's first lane, behind that lane's stores).  A sample with another status sets
+ * nothing; duplicates and samples that share a word are fine; no other bit changes.  One launch, the same choice of lanes a sample;
+ * the per-file word offsets ride the staging behind the rows and nothing is allocated.  Refuses what that call refuses, and a null or
+ * misaligned d_have, before anything is written.
+ * When not to (MI355X): the record costs about 0.6 % — 65 536 slices of a 1 GiB file 1.534 ms with it against 1.525
+ * without (the spread of the yardstick 0.001), 4 096 slices 0.181 against 0.180 — so the only reason for the plain call is a caller
+ * that keeps no bitmap. */
+int32_t b3w_bao_slice_ingest_have_device(b3w_ctx *ctx, uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets,
+                                         const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, uint8_t *d_outboards,
+                                         const uint32_t *d_roots, const uint32_t *host_files, const uint64_t *host_chunks,
+                                         uint32_t n_samples, const uint8_t *d_slices, int32_t *d_sample_status, uint64_t *d_have,
+                                         void *stream);
+/* RUNS.  A UNIT is a chunk (group_log 0) or a group of 2^group_log chunks, the last one possibly ragged; group_log is only the
+ * granularity of the report (a caller who wants chunk-exact runs of a file kept with group outboards passes 0).  kind
+ * B3W_BAO_HAVE_PRESENT selects the units ALL of whose chunks are set, B3W_BAO_HAVE_MISSING those with at least one chunk clear: for
+ * one group_log the two partition every file's units.  A run is a maximal stretch of selected units of ONE file; its row is
+ * (d_run_file, d_run_first, d_run_count) = (file, first chunk, number of chunks): whole units, clipped to the file's chunk count, the
+ * shape the ranged calls take.  Rows come in ascending (file, first chunk) order; runs merge across words and never cross files.
+ *   *d_n_runs receives the number of runs FOUND, even above `capacity`; rows [0, min(found, capacity)) are written and no byte behind
+ *   them is touched.  capacity == 0 with null row pointers is a count-only call.  A file of u units has at most ceil(u / 2) runs of
+ *   one kind: the sum of that over the files is a capacity that always suffices.
+ *   d_file_have[f] (may be NULL): the number of set bits of file f that are not pad bits, whatever kind and group_log; the file is
+ *   complete when it equals the chunk count.
+ * At most four launches whatever the file and run counts (count; the scan over the workgroups' totals; rows; counts from ends) and no
+ * workgroup waits for another.  Asynchronous on `stream`; nothing is allocated beyond d_scratch (8-byte aligned, at least
+ * b3w_bao_have_runs_scratch_bytes, host only) and the context's staging for the per-file tables; the host waits for nothing but this
+ * context's previous batch call.  B3W_E_BAD_ARGUMENT before anything is written for a null or misaligned pointer (d_run_file 4-byte,
+ * the others 8-byte; the row pointers may be NULL only with capacity 0), a group_log above B3W_BAO_MAX_GROUP_LOG, an unknown kind, a
+ * scratch that is too small, or more than 2^26 bitmap words in total (2^32 chunks).  n_files == 0 writes *d_n_runs = 0.
+ * When not to (MI355X): no call takes less than about 0.05 ms (count only; 0.10 with a few thousand rows brought to
+ * the host).  One file of 2^20 chunks: the missing rows on the host in 0.11 ms (1 % missing, 10 426 rows), 0.22 (50 %, 262 147 rows)
+ * and 0.10 (one run), where copying an ingest's 65 536 statuses to the host, scattering them into a map and making the rows with
+ * numpy takes 0.67, 3.64 and 0.42; 262 144 files of 4 chunks: 0.66 ms against 8.18, 0.48 of it the host's per-file tables and their
+ * upload (about 1.8 ns a file: the one cost that follows the file count).  Nothing smaller was measured: for a few files of a few
+ * thousand chunks a caller that has the statuses on the host anyway may do as well there. */
+uint64_t b3w_bao_have_runs_scratch_bytes(const uint64_t *host_lens, uint32_t n_files);
+int32_t b3w_bao_have_runs_device(b3w_ctx *ctx, const uint64_t *d_have, const uint64_t *host_lens, uint32_t n_files, uint32_t group_log,
+                                 uint32_t kind, uint64_t capacity, uint32_t *d_run_file, uint64_t *d_run_first, uint64_t *d_run_count,
+                                 uint64_t *d_n_runs, uint64_t *d_file_have, void *d_scratch, uint64_t scratch_bytes, void *stream);
+/* AFTER A RESTART: a bitmap from the unit statuses b3w_bao_verify_batch_device / b3w_bao_verify_ranges_batch_device write (packed as
+ * b3w_bao_verify_layout says for this group_log) over the half-filled arena and outboards.  Bit c of file f becomes
+ * status[unit_first[f] + (c >> group_log)] == 0; 0xFF (a unit the ranged call was not asked about) reads as absent.  Every word of
+ * every file is written whole with its pad bits zero: the one call that clears bits.  One launch; the same staging, limits and
+ * refusals (a null pointer, a misaligned d_have, a group_log above the maximum, more than 2^26 words).  n_files == 0: a no-op. */
+int32_t b3w_bao_have_from_status_device(b3w_ctx *ctx, const uint8_t *d_unit_status, const uint64_t *host_lens, uint32_t n_files,
+                                        uint32_t group_log, uint64_t *d_have, void *stream);
+/* Host only, ONE file of preimage_len bytes whose bitmap starts at have[0]: the rows (without the file column), *n_runs and *n_have
+ * (may be NULL) as the device call gives them for that file; and the bitmap from that file's unit statuses.  B3W_E_BAD_ARGUMENT for a
+ * null pointer (the row pointers may be NULL with capacity 0), a group_log above the maximum or an unknown kind. */
+int32_t b3w_bao_have_runs(const uint64_t *have, uint64_t preimage_len, uint32_t group_log, uint32_t kind, uint64_t capacity,
+                          uint64_t *run_first, uint64_t *run_count, uint64_t *n_runs, uint64_t *n_have);
+int32_t b3w_bao_have_from_status(const uint8_t *unit_status, uint64_t preimage_len, uint32_t group_log, uint64_t *have);
 
 /* ---- updates in place after writes to resident files (still ABI 1.4: new names only) --------------------------------
  * Every call above treats a file as immutable: after one rewritten block the only way to a correct outboard and root is the batch
