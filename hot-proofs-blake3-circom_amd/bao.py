@@ -718,6 +718,137 @@ def runs_chunks(files, first_chunks, n_chunks):
     return np.repeat(fi, cnt), (np.repeat(fc, cnt).astype(np.int64) + within).astype(np.uint64)
 
 
+# ---- range slices: the slice of a run of chunks, extracted and taken in ---------------------------------------------------
+def range_slice_size(length, first_chunk, n_chunks):
+    """8 + 64 U + the range's bytes: the bao slice of chunks [first_chunk, first_chunk + n_chunks), every shared node once"""
+    size = lib().b3w_bao_range_slice_size(length, first_chunk, n_chunks)
+    if not size:
+        raise B3WError(100, "b3w_bao_range_slice_size: the range is empty or reaches past the chunk count")
+    return size
+
+
+def range_slice_layout(lens, files, first_chunks, n_chunks):
+    """-> slice_first (numpy uint64 [n_ranges + 1]): range r's slice is the range_slice_size bytes from slice_first[r] of the packed
+    slices (every start 8 modulo 16; what lies between slices is padding); the last entry is the total"""
+    ln = _u64(lens)
+    fi = np.ascontiguousarray(files, dtype=np.uint32)
+    fc, nc = _ranges(first_chunks, n_chunks)
+    assert fi.size == fc.size
+    sf = np.zeros(fc.size + 1, dtype=np.uint64)
+    total = lib().b3w_bao_range_slice_batch_layout(ln.ctypes.data, ln.size, fi.ctypes.data, fc.ctypes.data, nc.ctypes.data, fc.size, sf.ctypes.data)
+    if total < 0:
+        raise B3WError(-total, "b3w_bao_range_slice_batch_layout: a file index is not below the file count, or a range is empty or reaches past its file's chunk count")
+    return sf
+
+
+def _range_args(what, d_arena, offsets, lens, d_outboards, files, first_chunks, n_chunks, group_log):
+    off, ln, fi, fc = _arena_args(what, d_arena, offsets, lens, d_outboards, files, first_chunks, group_log)
+    fc, nc = _ranges(fc, n_chunks)
+    return off, ln, fi, fc, nc
+
+
+def range_slices_arena(ctx, d_arena, offsets, lens, d_outboards, files, first_chunks, n_chunks, group_log=0, stream=0):
+    """The provider's side for runs of chunks: slices_arena with ranges (files[r], first_chunks[r], n_chunks[r]) — have_runs' rows as
+    they come — where that takes one chunk a sample.  A range slice carries every node its chunks share once: 1 024 chunks of a 1 GiB
+    file are 1.06 times their payload where 1 024 one-chunk slices are 2.26 times.  At most two launches; nothing is verified.
+    Measured (MI355X, DESIGN.md §8g, against runs_chunks + slices_arena's C call of the commit before): 64 runs of 1 024 chunks
+    0.08 ms against 4.37, the runs of a half-missing bitmap 13.3 against 38.7, 65 536 runs of one chunk 5.35 against 5.16 (level).
+    Returns dict(slices: uint8 CUDA tensor, packed; slice_first: range_slice_layout)."""
+    off, ln, fi, fc, nc = _range_args("range_slices_arena", d_arena, offsets, lens, d_outboards, files, first_chunks, n_chunks, group_log)
+    sf = range_slice_layout(ln, fi, fc, nc)
+    d_slices = torch.zeros(int(sf[-1]), dtype=torch.uint8, device=d_outboards.device)
+    _chk(ctx, lib().b3w_bao_range_slice_arena_device(ctx.handle, d_arena.data_ptr() if d_arena.numel() else None, d_arena.numel(), off.ctypes.data,
+                                                     ln.ctypes.data, ln.size, group_log, d_outboards.data_ptr(), fi.ctypes.data, fc.ctypes.data,
+                                                     nc.ctypes.data, fc.size, d_slices.data_ptr(), _stream(stream)), "b3w_bao_range_slice_arena_device")
+    return dict(slices=d_slices, slice_first=sf)
+
+
+def ingest_range_slices(ctx, d_arena, offsets, lens, d_outboards, d_roots, files, first_chunks, n_chunks, d_slices, group_log=0, stream=0, d_have=None):
+    """The receiver's side for runs of chunks, range_slices_arena's mirror image and ingest_slices' twin: every chunk of every range
+    gets the status its own one-chunk slice would get, and the chunks of status 0 write what ingest_slices writes for them — bytes,
+    stored path nodes, header, and their bit in d_have where one is given.  A bad node keeps out the chunks below it and no other.
+    Ranges may overlap, repeat and come in any order.  At most three launches.  When not to (MI355X, DESIGN.md §8g, against a build
+    of the commit before doing the same with ingest_slices over runs_chunks): 64 runs of 1 024 chunks of a 1 GiB file 0.21 ms against
+    1.53, 4 096 runs of 16 0.47 against 1.52 — but a range takes at least a wave, so 65 536 runs of ONE chunk take 7.3 ms against 1.5
+    and the 262 507 runs of a half-missing bitmap 21.1 against 11.7 (for 26 % fewer bytes): runs of one or two chunks are faster to
+    take in through runs_chunks and ingest_slices; where between 2 and 16 chunks a run the two cross was not measured.  This wrapper
+    makes its outputs and its scratch on every call; a loop that matters keeps them and calls b3w_bao_range_slice_ingest_device.
+    Returns dict(range_status: int32 CUDA, the largest chunk status of each range; range_first_bad: int64 CUDA, the first chunk of
+    the file whose status is not 0, -1 for none)."""
+    L = lib()
+    off, ln, fi, fc, nc = _range_args("ingest_range_slices", d_arena, offsets, lens, d_outboards, files, first_chunks, n_chunks, group_log)
+    sf = range_slice_layout(ln, fi, fc, nc)
+    dev = d_slices.device
+    assert d_roots.is_cuda and d_roots.is_contiguous() and d_roots.numel() >= ln.size * 8
+    assert d_slices.is_cuda and d_slices.dtype == torch.uint8 and d_slices.is_contiguous() and d_slices.numel() >= int(sf[-1])
+    if d_have is not None:
+        _have_tensor("ingest_range_slices", d_have, ln)
+    st = torch.full((fc.size,), -1, dtype=torch.int32, device=dev)
+    fb = torch.full((fc.size,), -2, dtype=torch.int64, device=dev)
+    need = L.b3w_bao_range_slice_ingest_scratch_bytes(ln.ctypes.data, ln.size, fi.ctypes.data, fc.ctypes.data, nc.ctypes.data, fc.size)
+    scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    _chk(ctx, L.b3w_bao_range_slice_ingest_device(ctx.handle, d_arena.data_ptr() if d_arena.numel() else None, d_arena.numel(), off.ctypes.data,
+                                                  ln.ctypes.data, ln.size, group_log, d_outboards.data_ptr(), d_roots.data_ptr(), fi.ctypes.data,
+                                                  fc.ctypes.data, nc.ctypes.data, fc.size, d_slices.data_ptr(), st.data_ptr(), fb.data_ptr(),
+                                                  d_have.data_ptr() if d_have is not None else None, scratch.data_ptr(), scratch.numel(),
+                                                  _stream(stream)), "b3w_bao_range_slice_ingest_device")
+    return dict(range_status=st, range_first_bad=fb)
+
+
+def range_slice_host(outboard, length, first_chunk, n_chunks, range_bytes, group_log=0):
+    """The slice of one range on the host (no GPU) from the file's outboard of this group_log and range_bytes: the bytes of the
+    range's chunks (group_log 0) or of the whole groups it touches (above 0) -> bytes"""
+    if not 0 <= group_log <= MAX_GROUP_LOG:
+        raise B3WError(100, f"group_log {group_log} is not in 0 .. {MAX_GROUP_LOG}")
+    size = range_slice_size(length, first_chunk, n_chunks)
+    ob, rb = bytes(outboard), bytes(range_bytes)
+    n = num_chunks(length)
+    g0 = (first_chunk >> group_log) << group_log
+    g1 = min(n, (((first_chunk + n_chunks - 1) >> group_log) + 1) << group_log)
+    if len(ob) != group_outboard_size(length, group_log) or len(rb) != min(length, g1 * 1024) - g0 * 1024:
+        raise B3WError(100, "range_slice_host: the outboard is not that of a file of this length, or range_bytes not the bytes of the touched groups")
+    out = ctypes.create_string_buffer(size)
+    got = lib().b3w_bao_range_slice(ob, length, group_log, first_chunk, n_chunks, rb, out, size)
+    if got != size:
+        raise B3WError(100 if got >= 0 else -got, "b3w_bao_range_slice")
+    return out.raw
+
+
+def decode_range_slice(slice_bytes, length, first_chunk, n_chunks, root):
+    """The sequential decoder for one range slice on the host -> (range status as STATUS, first bad chunk or None, the range's bytes
+    with the chunks that did not verify left zero)"""
+    sl = bytes(slice_bytes)
+    rw = np.ascontiguousarray(root, dtype=np.uint32)
+    out = np.zeros(max(1, n_chunks) * 1024, dtype=np.uint8)
+    st, fb = ctypes.c_int32(), ctypes.c_uint64()
+    _chk(None, lib().b3w_bao_range_slice_decode(sl, len(sl), length, first_chunk, n_chunks, rw.ctypes.data, out.ctypes.data, ctypes.byref(st), ctypes.byref(fb)),
+         "b3w_bao_range_slice_decode")
+    end = min(length, (first_chunk + n_chunks) * 1024) - first_chunk * 1024
+    return st.value, (None if fb.value == 2 ** 64 - 1 else fb.value), out[:end].tobytes()
+
+
+def ingest_range_slice_host(data, outboard, length, first_chunk, n_chunks, root, slice_bytes, group_log=0, have=None):
+    """ingest_range_slices for one range on the host (no GPU): data, outboard (and have: the file's bitmap words, numpy uint64, or None)
+    are written in place where chunks verify -> (range status as STATUS, first bad chunk or None)"""
+    if not 0 <= group_log <= MAX_GROUP_LOG:
+        raise B3WError(100, f"group_log {group_log} is not in 0 .. {MAX_GROUP_LOG}")
+    d, ob = _writable(data, "data"), _writable(outboard, "outboard")
+    if d.size != length or ob.size != group_outboard_size(length, group_log):
+        raise B3WError(100, "ingest_range_slice_host: data is not of this length or the outboard not that of a file of this length")
+    if have is not None and not (isinstance(have, np.ndarray) and have.dtype == np.uint64 and have.flags.c_contiguous and have.flags.writeable
+                                 and have.size == (num_chunks(length) + 63) // 64):
+        raise B3WError(100, "ingest_range_slice_host: have is not the writable uint64 bitmap of a file of this length")
+    sl = bytes(slice_bytes)
+    rw = np.ascontiguousarray(root, dtype=np.uint32)
+    if rw.size != 8:
+        raise B3WError(100, "ingest_range_slice_host: the root is 8 words")
+    st, fb = ctypes.c_int32(), ctypes.c_uint64()
+    _chk(None, lib().b3w_bao_range_slice_ingest(sl, len(sl), length, first_chunk, n_chunks, rw.ctypes.data, group_log, d.ctypes.data if d.size else None,
+                                                ob.ctypes.data, have.ctypes.data if have is not None else None, ctypes.byref(st), ctypes.byref(fb)),
+         "b3w_bao_range_slice_ingest")
+    return st.value, (None if fb.value == 2 ** 64 - 1 else fb.value)
+
+
 # ---- verification: whole files against their outboards ------------------------------------------------------------------
 def verify_layout(lens, group_log=0):
     """-> unit_first (numpy uint64 [n_files + 1]): file f's unit statuses are entries [unit_first[f], unit_first[f + 1]) of the packed

@@ -37,6 +37,8 @@
 //   b3w_bao_stream_open_*    a file whose length is known only at finish: full tiles hashed into tile-local blocks of a staging area, and
 //                            the blocks moved to their pre-order places once the length is known ("open-length sessions")
 //                            (b3w_bao_stream_open_relocate_many_kernel: the blocks of many sessions moved in one grid)
+//   b3w_bao_range_*_kernel   the slice of a RUN of chunks (bao's general slice, every shared node once) extracted from the arena and the
+//                            outboards and taken in again, a row per (range, block of 64 or 1 024 chunks) ("range slices", at the end)
 //
 // The routes (batch table, one streamed file by value, a table of sessions, update / ranges / resize rows) differ only in where a file's
 // entry comes from.  Each kernel, or its *_body wrapper, finds its entry and calls one of the bodies every route shares:
@@ -4271,6 +4273,626 @@ int32_t b3w_bao_outboard_resize_batch_device(b3w_ctx *ctx, const uint8_t *d_aren
   const hipError_t e = hipGetLastError();
   many_release(slot, st);
   if (e != hipSuccess) return hip_fail(ctx, e, "bao resize launch");
+  return B3W_OK;
+}
+
+}  // extern "C"
+
+// ---- range slices: the slice of a run of chunks, extracted and taken in (still ABI 1.4: new names only) ----------------------------------
+// The slice of chunks [a, a + k) of a file of n chunks = the header, then the tree in pre-order restricted to the range: a parent node
+// whose span meets the range gives its 64 bytes, then its left subtree where that meets the range, then its right one; a chunk of the
+// range gives its bytes (b3wit.h "range slices").  Every shared node is carried once.  Places:
+//   U(a, c)      the parent nodes whose span meets [a, c] (range_nodes: the common path, the split node, then the two boundary paths, on
+//                which a sibling subtree of s chunks wholly inside the range adds s - 1 and one outside adds nothing: O(depth))
+//   chunk c      at 8 + 64 U(a, c) + 1024 (c - a)
+//   node X       over [lo, lo + size) that meets the range, c0 = max(lo, a): at place(c0) - 64 (the nodes of c0's path at or below X) —
+//                between X and the first chunk of the range below it the slice holds that chunk's path alone
+// Slices are packed at 8 modulo 16 (b3w_bao_range_slice_batch_layout), so nodes lie 8 off a 16-byte boundary and chunks on one.
+// A ROW is (range, block): a block is B aligned chunks of the file, which is a subtree of the file's tree (full, or the ragged last one).
+// Ranges of at most 64 chunks take rows of B = 64 (a wave each: one or two rows a range), longer ones rows of B = 1 024 (a workgroup per
+// touched tile); the two kinds are one template and one launch each.  No workgroup waits for another and nothing is handed between them:
+//   b3w_bao_range_slice_kernel<B>    the provider: the chunks' bytes from the arena and the nodes from the outboard to their places; with
+//                                    group outboards the chunks of every touched group are hashed and the nodes inside the groups stored
+//                                    from LDS before their level's merge (merge_pair<true> with a place), as b3w_bao_slice_group_kernel
+//                                    does for one chunk.  A node above the block is moved by the row that holds the first chunk of the
+//                                    range below it, the header by the row that holds chunk a: every byte has one writer.
+//   b3w_bao_range_ingest_kernel<B>   the receiver: lane = chunk, the lanes of the range hash their chunk from the slice; the block's tree
+//                                    is walked as ranges_in_lds walks it, the nodes loaded from the slice (ranges_pair<true>, a chunk the
+//                                    leaf at every group_log: the nodes inside a group are in the slice and are verified); the D nodes
+//                                    above the block are checked side by side by the first D lanes, each against its half of the node
+//                                    above it (the root: against the file's root), as b3w_bao_slice_ingest_kernel checks a path — D <= 22
+//                                    compressions a row for files up to 4 GiB, and every node of the block hashed once.  The verdicts go
+//                                    down through the LDS flags (path_bad).  ONLY THEN the writes: the verified chunks' bytes by all
+//                                    lanes in 16-byte pieces (put16), the stored nodes with a verified chunk below them (a second walk
+//                                    that ORs "verified" upwards, no hashing), the nodes above the block and the header where the block
+//                                    has a verified chunk, one atomicOr of a wave's 64 verdicts into the bitmap word.  The row's largest
+//                                    status and first bad chunk go to the scratch.
+//   b3w_bao_range_reduce_kernel      a wave per range: the largest status and the first bad chunk over the range's rows.
+namespace {
+
+// the chunks of the left subtree of a subtree over m >= 2 chunks: the largest power of two strictly below m
+__host__ __device__ __forceinline__ uint64_t left_of(uint64_t m) { return 1ull << (63 - __builtin_clzll(m - 1)); }
+
+// path_len with the split from a bit scan: the parent nodes above chunk c of a subtree over m chunks, its root included
+__host__ __device__ __forceinline__ uint32_t depth_in(uint64_t c, uint64_t m) {
+  uint32_t p = 0;
+  for (; m > 1; ++p) {
+    const uint64_t k = left_of(m);
+    if (c < k) m = k; else { c -= k; m -= k; }
+  }
+  return p;
+}
+
+// U(a, c), a <= c < n
+__host__ __device__ inline uint64_t range_nodes(uint64_t n, uint64_t a, uint64_t c) {
+  uint64_t u = 0, lo = 0, m = n;
+  while (m > 1) {                                          // the nodes above the split: both ends go the same way
+    const uint64_t k = left_of(m);
+    if (c < lo + k) m = k;
+    else if (a >= lo + k) { lo += k; m -= k; }
+    else break;
+    ++u;
+  }
+  if (m <= 1) return u;                                    // (a == c: the chunk's path)
+  const uint64_t k = left_of(m);
+  ++u;                                                     // the split node: a on its left, c on its right
+  for (uint64_t l = lo, s = k; s > 1;) {                   // a's path below it: what lies right of a is inside
+    const uint64_t kk = left_of(s);
+    ++u;
+    if (a < l + kk) { u += s - kk - 1; s = kk; } else { l += kk; s -= kk; }
+  }
+  for (uint64_t l = lo + k, s = m - k; s > 1;) {           // c's path below it: what lies left of c is inside
+    const uint64_t kk = left_of(s);
+    ++u;
+    if (c >= l + kk) { u += kk - 1; l += kk; s -= kk; } else s = kk;
+  }
+  return u;
+}
+
+// the place within the slice of chunks [a, ..) of a file of n chunks of chunk c >= a, and of the node over [lo, lo + size) that meets it
+__host__ __device__ __forceinline__ uint64_t range_chunk_at(uint64_t n, uint64_t a, uint64_t c) { return 8 + 64 * range_nodes(n, a, c) + 1024 * (c - a); }
+__host__ __device__ __forceinline__ uint64_t range_node_at(uint64_t n, uint64_t a, uint64_t lo, uint64_t size) {
+  const uint64_t c0 = lo > a ? lo : a;
+  return range_chunk_at(n, a, c0) - 64ull * depth_in(c0 - lo, size);
+}
+
+uint64_t range_slice_bytes(uint64_t len, uint64_t n, uint64_t a, uint64_t k) {     // (a + k <= n, k >= 1)
+  const uint64_t end = (a + k) * 1024 < len ? (a + k) * 1024 : len;
+  return 8 + 64 * range_nodes(n, a, a + k - 1) + (end - a * 1024);
+}
+
+// a range's entry and a workgroup's row of the two device calls' table
+struct RsRange { uint64_t len, off, ob, slice, first, count, have; uint32_t file, row0; };   // have: the file's first bitmap word; row0: its first row
+struct RsRow { uint32_t range, block; };
+constexpr uint64_t RS_SHORT = 64;                          // ranges of at most this many chunks take rows of 64 chunks
+
+__device__ __forceinline__ void copy_node(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src) {   // (both 8-byte aligned)
+  const uint2 *s = reinterpret_cast<const uint2 *>(src);
+  uint2 *d = reinterpret_cast<uint2 *>(dst);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) d[k] = s[k];
+}
+
+// The nodes above the block [a0, a0 + m) of a file of n chunks, root first: their number, lane t's own (the t-th) with the node above it
+// and the side it hangs on, and the lowest one with the side the block hangs on.
+struct RsAbove { uint64_t lo, cnt, plo, pcnt, last_lo, last_cnt; uint32_t depth; bool left, last_left; };
+__device__ __forceinline__ RsAbove range_above(uint64_t n, uint64_t a0, uint64_t m, uint32_t t) {
+  RsAbove r{};
+  uint64_t lo = 0, cnt = n;
+  uint32_t j = 0;
+  for (; cnt > 1 && !(lo == a0 && cnt == m); ++j) {
+    const uint64_t k = left_of(cnt);
+    const bool left = a0 < lo + k;
+    if (j == t) { r.lo = lo; r.cnt = cnt; }
+    if (j + 1 == t) { r.plo = lo; r.pcnt = cnt; r.left = left; }
+    r.last_lo = lo; r.last_cnt = cnt; r.last_left = left;
+    if (left) cnt = k; else { lo += k; cnt -= k; }
+  }
+  r.depth = j;
+  return r;
+}
+
+// what a row's lanes share: the block's place in the file and the part of the range inside it, [lo, hi) in the block's own lanes
+struct RsBlock { uint64_t len, n, a, a0; uint32_t m, lo, hi; bool sole; };
+template <int B>
+__device__ __forceinline__ RsBlock range_block(const RsRange &r, uint32_t block) {
+  RsBlock b;
+  b.len = r.len; b.n = r.len ? (r.len + 1023) / 1024 : 1; b.a = r.first; b.a0 = (uint64_t)block * B;
+  b.m = (uint32_t)(b.n - b.a0 < B ? b.n - b.a0 : B);
+  const uint64_t e = r.first + r.count, top = b.a0 + b.m;
+  b.lo = (uint32_t)((b.a > b.a0 ? b.a : b.a0) - b.a0);
+  b.hi = (uint32_t)((e < top ? e : top) - b.a0);
+  b.sole = b.n <= B;
+  return b;
+}
+__device__ __forceinline__ uint32_t range_chunk_bytes(uint64_t len, uint64_t c) { return (uint32_t)(len - c * 1024 < 1024 ? len - c * 1024 : 1024); }
+// the node over the block's lanes [i0, i0 + size): its place in the slice (before[]: U(a, c) of the range's lanes)
+__device__ __forceinline__ uint64_t range_block_node_at(const RsBlock &b, const uint32_t *before, uint32_t i0, uint32_t size) {
+  const uint32_t c0 = i0 > b.lo ? i0 : b.lo;
+  return 8 + 64ull * before[c0] + 1024 * (b.a0 + c0 - b.a) - 64ull * depth_in(c0 - i0, size);
+}
+
+template <int B>
+__global__ __launch_bounds__(B) void b3w_bao_range_slice_kernel(const RsRange *__restrict__ ranges, const RsRow *__restrict__ rows, uint32_t gl,
+                                                                const uint8_t *__restrict__ arena, const uint8_t *__restrict__ obs,
+                                                                uint8_t *__restrict__ slices) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B * 8];
+  __shared__ uint32_t before[B];
+  const RsRow row = rows[blockIdx.x];
+  const RsRange r = ranges[row.range];
+  const RsBlock b = range_block<B>(r, row.block);
+  const uint32_t t = threadIdx.x, G = 1u << gl;
+  const uint8_t *__restrict__ data = arena + r.off, *__restrict__ ob = obs + r.ob;
+  uint8_t *__restrict__ sl = slices + r.slice;
+  if (t >= b.lo && t < b.hi) before[t] = (uint32_t)range_nodes(b.n, b.a, b.a0 + t);
+  // group outboards: the chunks of the touched groups, hashed (no byte behind the file's last one is read)
+  const uint32_t gs = t & ~(G - 1);
+  const bool touched = gl != 0 && t < b.m && gs < b.hi && gs + G > b.lo;
+  if (touched) lane_chunk_cv(cv, data, b.a0 + t, b.len, b.n, b.a0 + t, true);
+  for (uint32_t l = 0; (1u << l) < b.m; ++l) {
+    if (l <= gl) lds_barrier();                            // (before[] and the level below inside a group; above the groups nothing is handed on)
+    const uint32_t i0 = (2 * t) << l, i1 = i0 + (1u << l);
+    if (i1 >= b.m) continue;
+    const uint32_t end = i0 + (2u << l), size = (end < b.m ? end : b.m) - i0;
+    const bool meets = i0 < b.hi && i0 + size > b.lo;
+    uint8_t *place = meets ? sl + range_block_node_at(b, before, i0, size) : nullptr;
+    if (l < gl) {                                          // inside a group: computed, and stored where the range wants it
+      const uint32_t g0 = i0 & ~(G - 1);
+      if (g0 < b.hi && g0 + G > b.lo) merge_pair<true>(cv, i0, i1, place, 4u | (b.sole && (2u << l) >= b.m ? 8u : 0u));
+    } else if (meets) {
+      copy_node(place, ob + 8 + node_pos<true>(b.n, b.a0 + i0, size, gl) * 64);
+    }
+  }
+  if (b.m == 1) lds_barrier();                             // (before[] for the bytes below; any other block has passed a barrier)
+  // the nodes above the block whose first chunk of the range lies in it, and the header in front of chunk a
+  const RsAbove up = range_above(b.n, b.a0, b.m, t);
+  if (t < up.depth) {
+    const uint64_t c0 = up.lo > b.a ? up.lo : b.a;
+    if (c0 >= b.a0 && c0 < b.a0 + b.m) copy_node(sl + range_node_at(b.n, b.a, up.lo, up.cnt), ob + 8 + node_pos<true>(b.n, up.lo, up.cnt, gl) * 64);
+  }
+  if (t == 0 && b.a >= b.a0) *reinterpret_cast<uint2 *>(sl) = *reinterpret_cast<const uint2 *>(ob);
+  for (uint32_t p = t; p < (b.hi - b.lo) * 64; p += B) {
+    const uint32_t ch = b.lo + (p >> 6), q = (p & 63) * 16;
+    const uint64_t c = b.a0 + ch;
+    const uint32_t bytes = range_chunk_bytes(b.len, c);
+    uint8_t *dst = sl + 8 + 64ull * before[ch] + 1024 * (c - b.a);
+    const uint8_t *src = data + c * 1024;
+    if (q + 16 <= bytes) move16<true>(dst + q, src + q);
+    else for (uint32_t o = q; o < bytes; ++o) dst[o] = src[o];
+  }
+}
+
+template <int B>
+__global__ __launch_bounds__(B) void b3w_bao_range_ingest_kernel(const RsRange *__restrict__ ranges, const RsRow *__restrict__ rows, uint32_t gl,
+                                                                 const uint8_t *__restrict__ slices, const uint32_t *__restrict__ roots,
+                                                                 uint8_t *__restrict__ arena, uint8_t *__restrict__ obs,
+                                                                 unsigned long long *__restrict__ have, uint4 *__restrict__ results) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B * 8];
+  __shared__ uint32_t flags[B], listed[B], before[B];
+  __shared__ uint32_t worst, first, above;
+  const RsRow row = rows[blockIdx.x];
+  const RsRange r = ranges[row.range];
+  const RsBlock b = range_block<B>(r, row.block);
+  const uint32_t t = threadIdx.x;
+  const bool mine = t >= b.lo && t < b.hi;
+  const uint8_t *__restrict__ sl = slices + r.slice;
+  const uint32_t *__restrict__ root = roots + (uint64_t)r.file * 8;
+  listed[t] = mine ? 1u : 0u;
+  flags[t] = 0;
+  if (t == 0) { worst = 0; first = ~0u; above = 0; }
+  __syncthreads();
+  // 1. the verdicts: the range's chunks, the block's nodes bottom up, the nodes above the block side by side
+  if (mine) {
+    const uint64_t c = b.a0 + t, u = range_nodes(b.n, b.a, c);
+    uint32_t h[8];
+    before[t] = (uint32_t)u;
+    chunk_cv(sl + 8 + 64 * u + 1024 * (c - b.a), range_chunk_bytes(b.len, c), c, b.n == 1 ? 8u : 0u, h);   // (16-byte aligned)
+    put_cv(cv, t, h);
+  }
+  const RsAbove up = range_above(b.n, b.a0, b.m, t);
+  if (t < up.depth) {
+    uint32_t mw[16], ivv[8], o[8];
+    load_node(sl + range_node_at(b.n, b.a, up.lo, up.cnt), mw);
+    iv(ivv);
+    blake3_cv(ivv, mw, 0, 0, 64, 4u | (t == 0 ? 8u : 0u), o);
+    const uint32_t *want = t == 0 ? root : reinterpret_cast<const uint32_t *>(sl + range_node_at(b.n, b.a, up.plo, up.pcnt) + (up.left ? 0 : 32));
+    if (!eq8(o, want)) atomicOr(&above, 1u);
+  }
+  for (uint32_t l = 0; (1u << l) < b.m; ++l) {             // (ranges_in_lds's loop: the node's place is the slice's)
+    lds_barrier();
+    const uint32_t i0 = (2 * t) << l, i1 = i0 + (1u << l);
+    if (i1 >= b.m) continue;
+    const bool d0 = listed[i0] != 0, d1 = listed[i1] != 0;
+    if (!d0 && !d1) continue;
+    const uint32_t end = i0 + (2u << l), size = (end < b.m ? end : b.m) - i0;
+    ranges_pair<true>(cv, flags, nullptr, i0, i1, d0, d1, l, sl + range_block_node_at(b, before, i0, size), 4u | (b.sole && (2u << l) >= b.m ? 8u : 0u),
+                      1ull << l, size - (1u << l), 1, nullptr);
+    listed[i0] = 1;
+  }
+  lds_barrier();
+  if (t == 0) {                                            // slot 0: what the block's stored root node hashes to, or the CV of a block of one chunk
+    const uint32_t *want = up.depth ? reinterpret_cast<const uint32_t *>(sl + range_node_at(b.n, b.a, up.last_lo, up.last_cnt) + (up.last_left ? 0 : 32)) : root;
+    if (!eq8(cv, want)) flags[0] |= b.m == 1 ? VER_UNIT : VER_TOP;
+  }
+  lds_barrier();
+  const uint2 hd = *reinterpret_cast<const uint2 *>(sl);
+  const bool hdr = ((uint64_t)hd.x | ((uint64_t)hd.y << 32)) != b.len;
+  uint32_t st = 0;
+  if (mine) {
+    st = hdr ? 3u : above || path_bad(flags, t) ? 2u : (flags[t] & VER_UNIT) ? 1u : 0u;
+    if (st) { atomicMax(&worst, st); atomicMin(&first, t); }          // (LDS; a clean row issues none)
+  }
+  const bool ok = mine && st == 0;
+  __syncthreads();
+  listed[t] = ok ? 1u : 0u;                                // from here on: a verified chunk (below this slot)
+  __syncthreads();
+  if (t == 0) results[blockIdx.x] = make_uint4(worst, 0, first == ~0u ? ~0u : (uint32_t)(b.a0 + first), first == ~0u ? ~0u : (uint32_t)((b.a0 + first) >> 32));
+  // 2. the places: nothing unverified is written
+  uint8_t *__restrict__ data = arena + r.off, *__restrict__ ob = obs + r.ob;
+  for (uint32_t p = t; p < (b.hi - b.lo) * 64; p += B) {
+    const uint32_t ch = b.lo + (p >> 6), q = (p & 63) * 16;
+    if (!listed[ch]) continue;
+    const uint64_t c = b.a0 + ch;
+    const uint32_t bytes = range_chunk_bytes(b.len, c);
+    const uint8_t *src = sl + 8 + 64ull * before[ch] + 1024 * (c - b.a);
+    uint8_t *dst = data + c * 1024;
+    if (q + 16 <= bytes) put16(dst + q, src + q);
+    else for (uint32_t o = q; o < bytes; ++o) dst[o] = src[o];
+  }
+  for (uint32_t l = 0; (1u << l) < b.m; ++l) {             // the stored nodes with a verified chunk below them
+    lds_barrier();
+    const uint32_t i0 = (2 * t) << l, i1 = i0 + (1u << l);
+    if (i1 >= b.m || !(listed[i0] | listed[i1])) continue;
+    const uint32_t end = i0 + (2u << l), size = (end < b.m ? end : b.m) - i0;
+    uint8_t *node = node_at<true>(ob + 8, b.n, b.a0 + i0, size, gl);
+    if (node) copy_node(node, sl + range_block_node_at(b, before, i0, size));
+    listed[i0] = 1;
+  }
+  lds_barrier();
+  if (listed[0]) {
+    if (t < up.depth) {
+      uint8_t *node = node_at<true>(ob + 8, b.n, up.lo, up.cnt, gl);
+      if (node) copy_node(node, sl + range_node_at(b.n, b.a, up.lo, up.cnt));
+    }
+    if (t == 0) *reinterpret_cast<uint2 *>(ob) = hd;       // the header (it is the length: just checked)
+  }
+  if (have) {                                              // a wave's lanes are the chunks of one word (a block starts at a multiple of 64)
+    const unsigned long long mask = __ballot(ok);
+    if ((t & 63) == 0 && mask) atomicOr(have + r.have + ((b.a0 + t) >> 6), mask);
+  }
+}
+
+// a wave per range: the largest status and the first bad chunk of its rows (results: a row's {status, -, first bad chunk low, high})
+__global__ __launch_bounds__(256) void b3w_bao_range_reduce_kernel(const RsRange *__restrict__ ranges, uint32_t n_ranges, const uint4 *__restrict__ results,
+                                                                   int32_t *__restrict__ range_status, unsigned long long *__restrict__ range_first_bad) {
+  const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (i >= n_ranges) return;
+  const uint64_t a = ranges[i].first, k = ranges[i].count, B = k <= RS_SHORT ? 64 : B3W_TILE;
+  const uint32_t n_rows = (uint32_t)((a + k - 1) / B - a / B + 1);
+  const uint4 *__restrict__ res = results + ranges[i].row0;
+  uint32_t w = 0;
+  unsigned long long f = ~0ull;
+  for (uint32_t j = lane; j < n_rows; j += 64) {
+    const uint4 v = res[j];
+    const unsigned long long at = (unsigned long long)v.z | ((unsigned long long)v.w << 32);
+    w = w > v.x ? w : v.x;
+    f = f < at ? f : at;
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d /= 2) {
+    const uint32_t ow = __shfl_xor(w, d);
+    const unsigned long long of = __shfl_xor(f, d);
+    w = w > ow ? w : ow;
+    f = f < of ? f : of;
+  }
+  if (lane == 0) { range_status[i] = (int32_t)w; range_first_bad[i] = f; }
+}
+
+// ---- the host side of the two device calls: the checks, the rows, the table --------------------------------------------------------------
+struct RangeRows { uint64_t big, small; };                // rows of 1 024 chunks, rows of 64
+
+// every refusal the two calls share that concerns the ranges; counts the rows
+int32_t range_list_ok(b3w_ctx *ctx, const char *what, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
+                      uint32_t n_files, const uint32_t *host_files, const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, RangeRows &rows) {
+  char msg[160];
+  rows = RangeRows{};
+  for (uint32_t i = 0; i < n_ranges; ++i) {
+    const char *why = nullptr;
+    const uint32_t f = host_files[i];
+    if (f >= n_files) why = "its file index is not below the file count";
+    else {
+      const uint64_t n = num_chunks(host_lens[f]), off = host_offsets[f], len = host_lens[f];
+      if (host_count[i] == 0) why = "it has no chunk";
+      else if (host_first[i] >= n || host_count[i] > n - host_first[i]) why = "it reaches past its file's chunk count";
+      else if (len && !d_arena) why = "a null arena with a file that is not empty";
+      else if (off > arena_bytes || len > arena_bytes - off) why = "its file reaches past arena_bytes";
+    }
+    if (why) {
+      snprintf(msg, sizeof msg, "%s: range %u: %s", what, i, why);
+      ctx->last_error = msg;
+      return B3W_E_BAD_ARGUMENT;
+    }
+    const uint64_t a = host_first[i], k = host_count[i], B = k <= RS_SHORT ? 64 : B3W_TILE;
+    (k <= RS_SHORT ? rows.small : rows.big) += (a + k - 1) / B - a / B + 1;
+  }
+  if (rows.big > 0x7fffffffull || rows.small > 0x7fffffffull) {
+    snprintf(msg, sizeof msg, "%s: more than 2^31 - 1 rows of one kind", what);
+    ctx->last_error = msg;
+    return B3W_E_BAD_ARGUMENT;
+  }
+  return B3W_OK;
+}
+
+// the table into the staging and on its way: the ranges' entries, the rows of 1 024 chunks, the rows of 64 (behind them, host only, the
+// files' outboard offsets and bitmap words)
+int32_t range_table(b3w_ctx *ctx, const uint64_t *host_offsets, const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint32_t *host_files,
+                    const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, RangeRows rows, hipStream_t st, const RsRange *&d_ranges,
+                    const RsRow *&d_big, const RsRow *&d_small) {
+  const uint64_t up_bytes = (uint64_t)n_ranges * sizeof(RsRange) + (rows.big + rows.small) * sizeof(RsRow);
+  const int32_t rc = batch_staging(ctx, up_bytes + 2 * ((uint64_t)n_files + 1) * 8);
+  if (rc) return rc;
+  RsRange *rg = reinterpret_cast<RsRange *>(ctx->h_batch);
+  RsRow *big = reinterpret_cast<RsRow *>(rg + n_ranges), *small = big + rows.big;
+  uint64_t *ob_first = reinterpret_cast<uint64_t *>(small + rows.small), *word_first = ob_first + n_files + 1;
+  (void)b3w_bao_group_batch_layout(host_lens, n_files, group_log, ob_first);        // (group_log 0: b3w_bao_batch_layout's)
+  (void)b3w_bao_have_layout(host_lens, n_files, word_first);
+  uint64_t at = slice_start(0), nb = 0, ns = 0;
+  for (uint32_t i = 0; i < n_ranges; ++i) {
+    const uint32_t f = host_files[i];
+    const uint64_t len = host_lens[f], a = host_first[i], k = host_count[i];
+    const bool shrt = k <= RS_SHORT;
+    const uint64_t B = shrt ? 64 : B3W_TILE, b0 = a / B, b1 = (a + k - 1) / B;
+    rg[i] = RsRange{len, host_offsets[f], ob_first[f], at, a, k, word_first[f], f, (uint32_t)(shrt ? rows.big + ns : nb)};
+    RsRow *out = shrt ? small + ns : big + nb;
+    for (uint64_t blk = b0; blk <= b1; ++blk) *out++ = RsRow{i, (uint32_t)blk};
+    (shrt ? ns : nb) += b1 - b0 + 1;
+    at = slice_start(at + range_slice_bytes(len, num_chunks(len), a, k));
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)up_bytes, hipMemcpyHostToDevice, st));
+  d_ranges = reinterpret_cast<const RsRange *>(ctx->d_batch);
+  d_big = reinterpret_cast<const RsRow *>(d_ranges + n_ranges);
+  d_small = d_big + rows.big;
+  return B3W_OK;
+}
+
+// ---- the host mirrors: one range, node by node ----------------------------------------------------------------------------------
+// the CV of the subtree over chunks [first, first + cnt) whose bytes start at `base` with chunk base_chunk (host_subtree_cv on a part of a file)
+void part_subtree_cv(const uint8_t *base, uint64_t base_chunk, uint64_t len, uint64_t first, uint64_t cnt, bool root, uint32_t h[8]) {
+  if (cnt == 1) {
+    const uint64_t off = first * 1024;
+    host_chunk_cv(base + (first - base_chunk) * 1024, (uint32_t)(len - off < 1024 ? len - off : 1024), first, root ? 8u : 0u, h);
+    return;
+  }
+  const uint64_t k = left_of(cnt);
+  uint32_t m[16], ivv[8];
+  part_subtree_cv(base, base_chunk, len, first, k, false, m);
+  part_subtree_cv(base, base_chunk, len, first + k, cnt - k, false, m + 8);
+  iv(ivv);
+  blake3_cv(ivv, m, 0, 0, 64, 4u | (root ? 8u : 0u), h);
+}
+
+void put_words(uint8_t *dst, const uint32_t *w, uint32_t n) {
+  for (uint32_t k = 0; k < n; ++k)
+    for (int q = 0; q < 4; ++q) dst[4 * k + q] = (uint8_t)(w[k] >> (8 * q));
+}
+
+// the extractor's walk: the subtree over [lo, lo + size) of a file of n chunks, which meets [a, e); appends to out at `at`
+struct RangeEnc { const uint8_t *ob, *bytes; uint64_t len, n, a, e, base_chunk; uint32_t gl; uint8_t *out; uint64_t at; };
+void range_encode(RangeEnc &w, uint64_t lo, uint64_t size) {
+  if (size == 1) {
+    const uint64_t off = lo * 1024, bytes = w.len - off < 1024 ? w.len - off : 1024;
+    if (bytes) memcpy(w.out + w.at, w.bytes + (lo - w.base_chunk) * 1024, bytes);
+    w.at += bytes;
+    return;
+  }
+  const uint64_t k = left_of(size), G = 1ull << w.gl;
+  if (size > G) memcpy(w.out + w.at, w.ob + 8 + 64 * preorder_pos((w.n + G - 1) >> w.gl, lo >> w.gl, (size + G - 1) >> w.gl), 64);
+  else {                                                  // inside a group: from the group's bytes
+    uint32_t m[16];
+    part_subtree_cv(w.bytes, w.base_chunk, w.len, lo, k, false, m);
+    part_subtree_cv(w.bytes, w.base_chunk, w.len, lo + k, size - k, false, m + 8);
+    put_words(w.out + w.at, m, 16);
+  }
+  w.at += 64;
+  if (w.a < lo + k) range_encode(w, lo, k);
+  if (w.e > lo + k) range_encode(w, lo + k, size - k);
+}
+
+// the decoder's walk, top down in slice order; the ingest's writes ride on it.  -> whether a chunk below verified
+struct RangeDec {
+  const uint8_t *sl; uint64_t len, n, a, e, at; bool hdr; uint32_t gl;
+  uint8_t *out_bytes, *data, *ob; uint64_t *have;          // decode: out_bytes; ingest: data, ob, have (may be null)
+  int32_t worst; uint64_t first_bad;
+};
+bool range_decode(RangeDec &w, uint64_t lo, uint64_t size, const uint32_t want[8], bool bad_above, bool root) {
+  if (size == 1) {
+    const uint64_t off = lo * 1024, bytes = w.len - off < 1024 ? w.len - off : 1024;
+    const uint8_t *src = w.sl + w.at;
+    w.at += bytes;
+    uint32_t h[8];
+    host_chunk_cv(src, (uint32_t)bytes, lo, root ? 8u : 0u, h);
+    const int32_t st = w.hdr ? 3 : bad_above ? 2 : memcmp(h, want, 32) != 0 ? 1 : 0;
+    if (st) {
+      if (st > w.worst) w.worst = st;
+      if (lo < w.first_bad) w.first_bad = lo;
+      return false;
+    }
+    if (bytes && w.out_bytes) memcpy(w.out_bytes + (lo - w.a) * 1024, src, bytes);
+    if (bytes && w.data) memcpy(w.data + off, src, bytes);
+    if (w.have) w.have[lo >> 6] |= 1ull << (lo & 63);
+    return true;
+  }
+  const uint8_t *node = w.sl + w.at;
+  w.at += 64;
+  uint32_t mw[16], ivv[8], o[8];
+  for (int k = 0; k < 16; ++k) mw[k] = (uint32_t)node[4 * k] | ((uint32_t)node[4 * k + 1] << 8) | ((uint32_t)node[4 * k + 2] << 16) | ((uint32_t)node[4 * k + 3] << 24);
+  iv(ivv);
+  blake3_cv(ivv, mw, 0, 0, 64, 4u | (root ? 8u : 0u), o);
+  const bool bad = bad_above || memcmp(o, want, 32) != 0;
+  const uint64_t k = left_of(size), G = 1ull << w.gl;
+  bool any = false;
+  if (w.a < lo + k) any |= range_decode(w, lo, k, mw, bad, false);
+  if (w.e > lo + k) any |= range_decode(w, lo + k, size - k, mw + 8, bad, false);
+  if (any && w.ob && size > G) memcpy(w.ob + 8 + 64 * preorder_pos((w.n + G - 1) >> w.gl, lo >> w.gl, (size + G - 1) >> w.gl), node, 64);
+  return any;
+}
+
+int32_t range_decode_run(const uint8_t *slice, uint64_t slice_len, uint64_t len, uint64_t first, uint64_t count, const uint32_t *root, RangeDec &w) {
+  const uint64_t n = num_chunks(len);
+  if (!slice || !root || count == 0 || first >= n || count > n - first || slice_len != range_slice_bytes(len, n, first, count)) return B3W_E_BAD_ARGUMENT;
+  uint64_t hdr = 0;
+  for (int k = 0; k < 8; ++k) hdr |= (uint64_t)slice[k] << (8 * k);
+  w.sl = slice; w.len = len; w.n = n; w.a = first; w.e = first + count; w.at = 8; w.hdr = hdr != len; w.worst = 0; w.first_bad = ~0ull;
+  const bool any = range_decode(w, 0, n, root, false, true);
+  if (any && w.ob) memcpy(w.ob, slice, 8);
+  return B3W_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t b3w_bao_range_slice_size(uint64_t len, uint64_t first_chunk, uint64_t n_chunks) {
+  const uint64_t n = num_chunks(len);
+  if (n_chunks == 0 || first_chunk >= n || n_chunks > n - first_chunk) return 0;
+  return range_slice_bytes(len, n, first_chunk, n_chunks);
+}
+
+int64_t b3w_bao_range_slice_batch_layout(const uint64_t *host_lens, uint32_t n_files, const uint32_t *host_files, const uint64_t *host_first,
+                                         const uint64_t *host_count, uint32_t n_ranges, uint64_t *slice_first) {
+  if (!slice_first || (n_ranges && (!host_lens || !host_files || !host_first || !host_count))) return -B3W_E_BAD_ARGUMENT;
+  for (uint32_t i = 0; i < n_ranges; ++i)
+    if (host_files[i] >= n_files || !b3w_bao_range_slice_size(host_lens[host_files[i]], host_first[i], host_count[i])) return -B3W_E_BAD_ARGUMENT;
+  uint64_t at = slice_start(0);
+  for (uint32_t i = 0; i < n_ranges; ++i) {
+    slice_first[i] = at;
+    at = slice_start(at + b3w_bao_range_slice_size(host_lens[host_files[i]], host_first[i], host_count[i]));
+  }
+  slice_first[n_ranges] = at;
+  return (int64_t)at;
+}
+
+int64_t b3w_bao_range_slice(const uint8_t *outboard, uint64_t len, uint32_t group_log, uint64_t first_chunk, uint64_t n_chunks, const uint8_t *range_bytes,
+                            uint8_t *out, uint64_t out_len) {
+  const uint64_t size = b3w_bao_range_slice_size(len, first_chunk, n_chunks);
+  if (!size || group_log > B3W_BAO_MAX_GROUP_LOG) return -B3W_E_BAD_ARGUMENT;
+  if (!out) return (int64_t)size;
+  if (!outboard || (!range_bytes && len) || out_len < size) return -B3W_E_BAD_ARGUMENT;
+  memcpy(out, outboard, 8);
+  RangeEnc w{outboard, range_bytes, len, num_chunks(len), first_chunk, first_chunk + n_chunks, (first_chunk >> group_log) << group_log, group_log, out, 8};
+  range_encode(w, 0, w.n);
+  return (int64_t)w.at;
+}
+
+int32_t b3w_bao_range_slice_decode(const uint8_t *slice, uint64_t slice_len, uint64_t len, uint64_t first_chunk, uint64_t n_chunks, const uint32_t *root,
+                                   uint8_t *out_bytes, int32_t *out_status, uint64_t *out_first_bad) {
+  if (!out_status) return B3W_E_BAD_ARGUMENT;
+  RangeDec w{};
+  w.out_bytes = out_bytes;
+  const int32_t rc = range_decode_run(slice, slice_len, len, first_chunk, n_chunks, root, w);
+  if (rc) return rc;
+  *out_status = w.worst;
+  if (out_first_bad) *out_first_bad = w.first_bad;
+  return B3W_OK;
+}
+
+int32_t b3w_bao_range_slice_ingest(const uint8_t *slice, uint64_t slice_len, uint64_t len, uint64_t first_chunk, uint64_t n_chunks, const uint32_t *root,
+                                   uint32_t group_log, uint8_t *data, uint8_t *outboard, uint64_t *have, int32_t *out_status, uint64_t *out_first_bad) {
+  if (group_log > B3W_BAO_MAX_GROUP_LOG || !outboard || (!data && len) || !out_status) return B3W_E_BAD_ARGUMENT;
+  RangeDec w{};
+  w.gl = group_log; w.data = data; w.ob = outboard; w.have = have;
+  const int32_t rc = range_decode_run(slice, slice_len, len, first_chunk, n_chunks, root, w);
+  if (rc) return rc;
+  *out_status = w.worst;
+  if (out_first_bad) *out_first_bad = w.first_bad;
+  return B3W_OK;
+}
+
+int32_t b3w_bao_range_slice_arena_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
+                                         uint32_t n_files, uint32_t group_log, const uint8_t *d_outboards, const uint32_t *host_files,
+                                         const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, uint8_t *d_slices, void *stream) {
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  if (group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "bao range slice arena: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
+  if (!n_ranges) return B3W_OK;
+  if (!host_offsets || !host_lens || !d_outboards || !host_files || !host_first || !host_count || !d_slices) {
+    ctx->last_error = "bao range slice arena: a null pointer"; return B3W_E_BAD_ARGUMENT;
+  }
+  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) {
+    ctx->last_error = "bao range slice arena: d_outboards is not 8-byte or d_slices not 16-byte aligned"; return B3W_E_BAD_ARGUMENT;
+  }
+  RangeRows rows;
+  int32_t rc = range_list_ok(ctx, "bao range slice arena", d_arena, arena_bytes, host_offsets, host_lens, n_files, host_files, host_first, host_count, n_ranges, rows);
+  if (rc) return rc;
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  const RsRange *d_ranges = nullptr;
+  const RsRow *d_big = nullptr, *d_small = nullptr;
+  rc = range_table(ctx, host_offsets, host_lens, n_files, group_log, host_files, host_first, host_count, n_ranges, rows, st, d_ranges, d_big, d_small);
+  if (rc) return rc;
+  if (rows.big) hipLaunchKernelGGL(b3w_bao_range_slice_kernel<(int)B3W_TILE>, dim3((uint32_t)rows.big), dim3(B3W_TILE), 0, st, d_ranges, d_big, group_log, d_arena, d_outboards, d_slices);
+  if (rows.small) hipLaunchKernelGGL(b3w_bao_range_slice_kernel<64>, dim3((uint32_t)rows.small), dim3(64), 0, st, d_ranges, d_small, group_log, d_arena, d_outboards, d_slices);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(ctx, e, "bao range slice arena launch");
+  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
+  return B3W_OK;
+}
+
+uint64_t b3w_bao_range_slice_ingest_scratch_bytes(const uint64_t *host_lens, uint32_t n_files, const uint32_t *host_files, const uint64_t *host_first,
+                                                  const uint64_t *host_count, uint32_t n_ranges) {
+  if (!host_lens || !host_files || !host_first || !host_count) return 0;
+  uint64_t rows = 0;
+  for (uint32_t i = 0; i < n_ranges; ++i) {
+    if (host_files[i] >= n_files || !b3w_bao_range_slice_size(host_lens[host_files[i]], host_first[i], host_count[i])) return 0;
+    const uint64_t a = host_first[i], k = host_count[i], B = k <= RS_SHORT ? 64 : B3W_TILE;
+    rows += (a + k - 1) / B - a / B + 1;
+  }
+  return rows * 16;                                       // a row's status and first bad chunk
+}
+
+int32_t b3w_bao_range_slice_ingest_device(b3w_ctx *ctx, uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
+                                          uint32_t n_files, uint32_t group_log, uint8_t *d_outboards, const uint32_t *d_roots, const uint32_t *host_files,
+                                          const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, const uint8_t *d_slices,
+                                          int32_t *d_range_status, uint64_t *d_range_first_bad, uint64_t *d_have, void *d_scratch, uint64_t scratch_bytes,
+                                          void *stream) {
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  if (group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "bao range slice ingest: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
+  if ((uintptr_t)d_have & 7) { ctx->last_error = "bao range slice ingest: d_have is not 8-byte aligned"; return B3W_E_BAD_ARGUMENT; }
+  if (!n_ranges) return B3W_OK;
+  if (!host_offsets || !host_lens || !d_outboards || !d_roots || !host_files || !host_first || !host_count || !d_slices || !d_range_status || !d_range_first_bad) {
+    ctx->last_error = "bao range slice ingest: a null pointer"; return B3W_E_BAD_ARGUMENT;
+  }
+  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) {
+    ctx->last_error = "bao range slice ingest: d_outboards is not 8-byte or d_slices not 16-byte aligned"; return B3W_E_BAD_ARGUMENT;
+  }
+  if (((uintptr_t)d_range_status & 3) || ((uintptr_t)d_range_first_bad & 7)) {
+    ctx->last_error = "bao range slice ingest: d_range_status is not 4-byte or d_range_first_bad not 8-byte aligned"; return B3W_E_BAD_ARGUMENT;
+  }
+  RangeRows rows;
+  int32_t rc = range_list_ok(ctx, "bao range slice ingest", d_arena, arena_bytes, host_offsets, host_lens, n_files, host_files, host_first, host_count, n_ranges, rows);
+  if (rc) return rc;
+  if (scratch_bytes < (rows.big + rows.small) * 16) {
+    ctx->last_error = "bao range slice ingest: the scratch is smaller than b3w_bao_range_slice_ingest_scratch_bytes says"; return B3W_E_BAD_ARGUMENT;
+  }
+  if (!d_scratch || ((uintptr_t)d_scratch & 15)) { ctx->last_error = "bao range slice ingest: the scratch is null or not 16-byte aligned"; return B3W_E_BAD_ARGUMENT; }
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  const RsRange *d_ranges = nullptr;
+  const RsRow *d_big = nullptr, *d_small = nullptr;
+  rc = range_table(ctx, host_offsets, host_lens, n_files, group_log, host_files, host_first, host_count, n_ranges, rows, st, d_ranges, d_big, d_small);
+  if (rc) return rc;
+  uint4 *res = reinterpret_cast<uint4 *>(d_scratch);
+  unsigned long long *have = reinterpret_cast<unsigned long long *>(d_have);
+  if (rows.big)
+    hipLaunchKernelGGL(b3w_bao_range_ingest_kernel<(int)B3W_TILE>, dim3((uint32_t)rows.big), dim3(B3W_TILE), 0, st, d_ranges, d_big, group_log, d_slices, d_roots, d_arena,
+                       d_outboards, have, res);
+  if (rows.small)
+    hipLaunchKernelGGL(b3w_bao_range_ingest_kernel<64>, dim3((uint32_t)rows.small), dim3(64), 0, st, d_ranges, d_small, group_log, d_slices, d_roots, d_arena, d_outboards,
+                       have, res + rows.big);
+  hipLaunchKernelGGL(b3w_bao_range_reduce_kernel, dim3((n_ranges + 3) / 4), dim3(256), 0, st, d_ranges, n_ranges, res, d_range_status,
+                     reinterpret_cast<unsigned long long *>(d_range_first_bad));
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(ctx, e, "bao range slice ingest launch");
+  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
   return B3W_OK;
 }
 

@@ -1030,6 +1030,99 @@ int32_t b3w_bao_have_runs(const uint64_t *have, uint64_t preimage_len, uint32_t 
                           uint64_t *run_first, uint64_t *run_count, uint64_t *n_runs, uint64_t *n_have);
 int32_t b3w_bao_have_from_status(const uint8_t *unit_status, uint64_t preimage_len, uint32_t group_log, uint64_t *have);
 
+/* ---- range slices: the slice of a run of chunks, extracted and taken in (still ABI 1.4: new names only) -------------
+ * The run lists above name what is missing as rows (file, first chunk, chunks); the slice calls above carry ONE chunk a slice, so a
+ * run of k chunks costs k slices and k whole paths (2 312 bytes for 1 024 of payload in a file of 2^20 chunks).  A RANGE SLICE carries
+ * every shared node once.  A range is (file f, first chunk a, chunks k), k >= 1, a + k <= b3w_chain_num_chunks(len_f).  Its slice is the
+ * 8-byte little-endian length, then the tree in pre-order restricted to the range: a parent node whose span meets [a, a + k) gives its
+ * 64 bytes, then its left subtree if that meets the range, then its right one likewise; a chunk c of the range gives its
+ * min(1024, len - 1024 c) bytes.  This is the slice `bao slice` makes for those bytes; an empty file's slice is its header.  With
+ * k = 1 it is b3w_bao_slice's slice byte for byte.
+ * PLACES.  U(a, c) = the parent nodes whose span meets [a, c] (the union of the paths of chunks a .. c).  Chunk c lies at
+ * 8 + 64 U(a, c) + 1024 (c - a); a node X over [lo, hi) that meets the range, c0 = max(lo, a), lies at place(c0) - 64 (the nodes of
+ * c0's path at or below X).  The size is 8 + 64 U(a, a + k - 1) + the range's bytes: 1 114 696 for 1 024 aligned chunks of 2^20
+ * (1.063 times the payload; 1 024 one-chunk slices are 2.258 times).
+ * PACKING.  Slice r starts at slice_first[r], 8 modulo 16 as b3w_bao_slice_batch_layout does it: with d_slices 16-byte aligned every
+ * node sits 8 off a 16-byte boundary and every chunk on one.  Padding is neither read nor written.
+ * THE RECEIVER IS DEFINED BY PROJECTION.  The projection of a range slice onto chunk c — the header, the nodes of c's path found in
+ * the slice root first, c's bytes — is the one-chunk slice of c.  Chunk status = b3w_bao_slice_decode's status of the projection (3 the
+ * header is not the length, 2 a path node or the root fails, 1 the chunk's bytes fail, the first that applies; a one-chunk file's
+ * wrong root is 1).  Writes = the union over the chunks of status 0 of what b3w_bao_slice_ingest writes for the projection: the
+ * chunk's bytes and no byte beside them, the STORED nodes of its path (group_log 0: all; above 0: those above the group, the others are
+ * verified and dropped), the header; and the chunk's bit in the bitmap where one is given.  Nothing unverified is written: a bad node
+ * keeps out the chunks below it and no other.  Range status = the largest chunk status of the range, range first bad = the first
+ * chunk (its index within the file) whose status is not 0, UINT64_MAX when there is none — what b3w_bao_verify_ranges_batch_device
+ * reports for a range.  Ranges may overlap, repeat and come in any order, in one call and across calls: every writer of a byte that
+ * writes at all writes the same verified value. */
+/* Host only.  The slice's byte count; 0 for n_chunks == 0 or a range that reaches past the file's chunk count. */
+uint64_t b3w_bao_range_slice_size(uint64_t preimage_len, uint64_t first_chunk, uint64_t n_chunks);
+/* Host only.  slice_first [n_ranges + 1] -> the total bytes, or -B3W_E_BAD_ARGUMENT (a null pointer, a file index >= n_files, a range
+ * b3w_bao_range_slice_size refuses), like b3w_bao_slice_batch_layout. */
+int64_t b3w_bao_range_slice_batch_layout(const uint64_t *host_lens, uint32_t n_files, const uint32_t *host_files, const uint64_t *host_first,
+                                         const uint64_t *host_count, uint32_t n_ranges, uint64_t *slice_first /* n_ranges + 1 */);
+/* Host only.  The slice of one range from the file's outboard (group_log 0: the full one; 1 .. 6: the group outboard) and range_bytes:
+ * the bytes of the range's chunks (group_log 0), or of the whole groups the range touches, from the first chunk of the first such
+ * group, clipped to the file (group_log > 0: the nodes inside those groups are recomputed from them).  out == NULL: -> the size.
+ * Otherwise -> the bytes written (the size), or -B3W_E_BAD_ARGUMENT for a refused range, a group_log above the maximum, a null pointer
+ * (range_bytes may be NULL for an empty file) or out_len below the size. */
+int64_t b3w_bao_range_slice(const uint8_t *outboard, uint64_t preimage_len, uint32_t group_log, uint64_t first_chunk, uint64_t n_chunks,
+                            const uint8_t *range_bytes, uint8_t *out, uint64_t out_len);
+/* Host only.  The sequential top-down decoder: the slice is read front to back, every node against its half of the node above it.
+ * *out_status / *out_first_bad (may be NULL) are the range status and first bad chunk defined above; out_bytes (may be NULL; room for
+ * 1024 n_chunks) receives the bytes of the chunks of status 0 at 1024 (c - first_chunk), the others' places are left alone.
+ * B3W_E_BAD_ARGUMENT for a null slice, root or out_status, a refused range, or a slice_len that is not b3w_bao_range_slice_size. */
+int32_t b3w_bao_range_slice_decode(const uint8_t *slice, uint64_t slice_len, uint64_t preimage_len, uint64_t first_chunk, uint64_t n_chunks,
+                                   const uint32_t *root /* 8 u32 */, uint8_t *out_bytes, int32_t *out_status, uint64_t *out_first_bad);
+/* Host only.  The receiver for ONE range: the same verdict and the writes defined above into `data` (the file), `outboard` (its
+ * outboard of this group_log) and `have` (may be NULL; the file's bitmap from its word 0).  Refuses what the decoder refuses, a
+ * group_log above the maximum and a null outboard (data may be NULL only for an empty file). */
+int32_t b3w_bao_range_slice_ingest(const uint8_t *slice, uint64_t slice_len, uint64_t preimage_len, uint64_t first_chunk, uint64_t n_chunks,
+                                   const uint32_t *root /* 8 u32 */, uint32_t group_log, uint8_t *data, uint8_t *outboard, uint64_t *have,
+                                   int32_t *out_status, uint64_t *out_first_bad);
+/* THE PROVIDER.  The range slices of ranges (host_files[r], host_first[r], host_count[r]) into d_slices (16-byte aligned, packed as
+ * b3w_bao_range_slice_batch_layout says); the other arguments are b3w_bao_slice_arena_device's.  Nothing is verified.  Only each
+ * slice's own bytes are written, each by one lane; no byte outside a range's own file is read.  group_log > 0: the chunks of every
+ * group the range touches are hashed and the nodes inside those groups come from that, as in b3w_bao_slice_arena_device.
+ * Both device calls: a ROW is (range, block of B aligned chunks).  A range of at most 64 chunks takes rows of B = 64, a wave each (one
+ * or two a range); a longer one takes a workgroup of 1 024 lanes per tile of 1 024 chunks it touches.  At most TWO launches here and
+ * THREE in the receiver (the rows of each kind, and a wave per range that reduces its rows' results), whatever the ranges; no
+ * workgroup waits for another.  One table (64 bytes a range, 8 a row) goes through the context's staging and nothing else is
+ * allocated; asynchronous on `stream`; any context; the host waits for nothing but this context's previous batch call.  REFUSALS ARE
+ * ATOMIC (B3W_E_BAD_ARGUMENT before anything is launched or written; b3w_last_error names the range): what the one-chunk twins refuse,
+ * a range with count 0 or that reaches past its file's chunk count, more than 2^31 - 1 rows of one kind.  n_ranges == 0: a no-op. */
+int32_t b3w_bao_range_slice_arena_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets,
+                                         const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint8_t *d_outboards,
+                                         const uint32_t *host_files, const uint64_t *host_first, const uint64_t *host_count,
+                                         uint32_t n_ranges, uint8_t *d_slices, void *stream);
+/* Host only.  Bytes of scratch the receiver needs: 16 per row (0 for a null pointer or a range the layout call refuses). */
+uint64_t b3w_bao_range_slice_ingest_scratch_bytes(const uint64_t *host_lens, uint32_t n_files, const uint32_t *host_files,
+                                                  const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges);
+/* THE RECEIVER, with the semantics above; the arguments of b3w_bao_slice_ingest_have_device with (first, count) for the chunk, the two
+ * range outputs (int32, and uint64 8-byte aligned, in the order the ranges were given; neither needs clearing) for the sample status,
+ * d_have (may be NULL: no record; else 8-byte aligned, bits set with one atomic OR of a whole word per wave) and the scratch (16-byte
+ * aligned, b3w_bao_range_slice_ingest_scratch_bytes).  Every node of the slice inside a block is hashed once by its row, in LDS, and
+ * the verdicts go down through flags as in the ranged verification; the nodes above a block (at most 22 for files up to 4 GiB) are
+ * checked once per row, side by side.  Also refused: a scratch that is too small, null or misaligned, a misaligned d_have, a null or
+ * misaligned output.
+ * WHEN NOT TO (MI355X, one 1 GiB file; the yardstick is a build of the commit before these calls doing the same job with
+ * one slice a chunk: bao.runs_chunks + b3w_bao_slice_arena_device, b3w_bao_slice_ingest_have_device).  64 runs of 1 024 chunks at starts
+ * that are not tile-aligned (68 MiB of slices against 145): the provider 0.081 ms against 4.37, the receiver 0.214 against 1.525 (the
+ * yardstick's spread 0.047 and 0.0003); at group_log 4 0.158 and 0.202, the file at 1 modulo 16 0.084 and 0.222.  4 096 runs of 16: 0.32
+ * against 4.25 and 0.47 against 1.52.  The whole file as one range: 1.11 ms to take in (bao.verify_batch plus a device copy of the
+ * bytes: 0.85) and 0.80 to extract.  SHORT RUNS LOSE IN THE RECEIVER: a range takes at least a wave, and a wave with one or two busy
+ * lanes hashes no faster than the one-chunk kernel's sixteen samples a wave.  65 536 runs of ONE chunk (the same bytes either way): the
+ * receiver 7.31 ms against 1.53, the provider 5.35 against 5.16 (spread 0.65); the 262 507 runs of a bitmap with half its chunks
+ * missing (2 chunks a run on average, 851 MiB of slices against 1 158): the provider 13.3 ms against 38.7, the receiver 21.1 against
+ * 11.7.  So: range slices for runs from about sixteen chunks on, where they save both bytes and time; runs of one or two chunks
+ * through bao.runs_chunks and the one-chunk calls, unless the bytes on the wire matter more than the receiver's milliseconds.  Where
+ * between 2 and 16 chunks a run the two cross was not measured, nor were files past 1 GiB or the kernels one by one. */
+int32_t b3w_bao_range_slice_ingest_device(b3w_ctx *ctx, uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets,
+                                          const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, uint8_t *d_outboards,
+                                          const uint32_t *d_roots, const uint32_t *host_files, const uint64_t *host_first,
+                                          const uint64_t *host_count, uint32_t n_ranges, const uint8_t *d_slices, int32_t *d_range_status,
+                                          uint64_t *d_range_first_bad, uint64_t *d_have /* may be NULL */, void *d_scratch,
+                                          uint64_t scratch_bytes, void *stream);
+
 /* ---- updates in place after writes to resident files (still ABI 1.4: new names only) --------------------------------
  * Every call above treats a file as immutable: after one rewritten block the only way to a correct outboard and root is the batch
  * call over the whole file again.  These calls make the cost follow the bytes written.  GIVEN an arena with its offsets and
