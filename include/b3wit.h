@@ -257,7 +257,8 @@ void b3w_r1cs_consumer(void *user, const uint8_t *d_bodies, uint64_t pitch, uint
  * signal), so a body satisfies all constraints iff it equals the witness recomputed from its own input
  * slots; the kernel reads each body once (HBM-read bound) and compares every 16-byte unit.
  * d_mismatch[i] = number of differing units of body i: 0 = valid witness; 0xFFFFFFFF = the body's inputs are
- * rejected by the circuit or are not plain 32-bit values (outside this path's domain).  Stands where the
+ * rejected by the circuit, are not plain 32-bit values, or make a record that b3w_batch_run_device answers with 103
+ * (outside this path's domain: DESIGN.md "Input domain" has the closed-form rule).  Stands where the
  * reference's consumers check a witness against the R1CS (circom_tester expectPass, test/blake3_hash.test.ts:36;
  * synthesize_with_vec's constraints, rust_fold/src/utils.rs:17-88). */
 int32_t b3w_batch_verify_device(b3w_ctx *ctx, const uint8_t *d_bodies, uint32_t n, uint64_t pitch, uint32_t *d_mismatch,

@@ -95,6 +95,19 @@ def oracle_batch_u32(circuit, recs):
     return bad, bodies
 
 
+def oracle_each_u32(circuit, recs):
+    """-> (rc int32 [n]: 0, or 4 = a failed assert; bodies uint8 [n, nwit*32], a fresh array; a rejected record's row is
+    whatever the oracle had written when it stopped)."""
+    lib = oracle()
+    recs = np.ascontiguousarray(recs, dtype=np.uint32)
+    n = recs.shape[0]
+    bodies = np.zeros((n, NWIT[circuit] * 32), dtype=np.uint8)
+    rc = np.zeros(n, dtype=np.int32)
+    for i in range(n):
+        rc[i] = lib.b3wo_witness_u32(CIRCUIT_ID[circuit], recs[i].ctypes.data, bodies[i].ctypes.data, None, 0)
+    return rc, bodies
+
+
 def oracle_header(circuit):
     hdr = np.zeros(76, dtype=np.uint8)
     oracle().b3wo_wtns_header(CIRCUIT_ID[circuit], hdr.ctypes.data)

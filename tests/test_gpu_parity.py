@@ -5,6 +5,7 @@ import ctypes, os
 import numpy as np
 import pytest
 import b3w_testlib as T
+from ref_models import _blake3_compress_np  # noqa: F401  (other test modules import it from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -22,28 +23,6 @@ def _run_batch(m, ctx, recs, pitch=0):
     b = m.Batch(ctx, max(1, recs.shape[0]), pitch)
     b.run(recs)
     return b
-
-
-def _blake3_compress_np(h, mm, t0, t1, b, d):
-    """Independent plain BLAKE3 compression, vectorised over the batch (BLAKE3 spec section 2.2)."""
-    IV = T.workloads().IV.astype(np.uint32)
-    perm = [2, 6, 3, 10, 7, 0, 4, 13, 1, 11, 12, 5, 9, 14, 15, 8]
-    n = h.shape[0]
-    v = [h[:, i].copy() for i in range(8)] + [np.full(n, IV[i], np.uint32) for i in range(4)] + [t0.copy(), t1.copy(), b.copy(), d.copy()]
-    msg = [mm[:, i].copy() for i in range(16)]
-    rot = lambda x, r: (x >> np.uint32(r)) | (x << np.uint32(32 - r))
-
-    def g(a, b_, c, d_, x, y):
-        v[a] = v[a] + v[b_] + x; v[d_] = rot(v[d_] ^ v[a], 16)
-        v[c] = v[c] + v[d_]; v[b_] = rot(v[b_] ^ v[c], 12)
-        v[a] = v[a] + v[b_] + y; v[d_] = rot(v[d_] ^ v[a], 8)
-        v[c] = v[c] + v[d_]; v[b_] = rot(v[b_] ^ v[c], 7)
-    for r in range(7):
-        g(0, 4, 8, 12, msg[0], msg[1]); g(1, 5, 9, 13, msg[2], msg[3]); g(2, 6, 10, 14, msg[4], msg[5]); g(3, 7, 11, 15, msg[6], msg[7])
-        g(0, 5, 10, 15, msg[8], msg[9]); g(1, 6, 11, 12, msg[10], msg[11]); g(2, 7, 8, 13, msg[12], msg[13]); g(3, 4, 9, 14, msg[14], msg[15])
-        msg = [msg[perm[j]] for j in range(16)]
-    out = [v[i] ^ v[i + 8] for i in range(8)] + [v[i + 8] ^ h[:, i] for i in range(8)]
-    return np.stack(out, axis=1)
 
 
 def test_compression_batch_matches_oracle_every_variant(m):

@@ -4,6 +4,7 @@ import os
 import numpy as np
 import pytest
 import b3w_testlib as T
+from ref_models import _nova_public_np
 
 pytestmark = pytest.mark.gpu
 NOVA = ["nova_bn254", "nova_vesta", "nova_bn254_o1"]
@@ -111,34 +112,6 @@ def test_nova_large_isZero_arguments_take_the_general_inverse_path(m):
         for i in range(24):
             assert np.array_equal(b.fetch(i), want[i]), (circuit, i)
         b.close(); ctx.close()
-
-
-def _nova_public_np(recs):
-    """Independent numpy model of the step's public outputs (h_out via plain BLAKE3)."""
-    from test_gpu_parity import _blake3_compress_np
-    IV = T.workloads().IV.astype(np.uint32)
-    nb, bc, h = recs[:, 0], recs[:, 1], recs[:, 2:10]
-    cil, cih, ld, td, depth, mm, b = recs[:, 10], recs[:, 11], recs[:, 12], recs[:, 13], recs[:, 14], recs[:, 15:31], recs[:, 31]
-    parent = depth.astype(np.int64) < ld.astype(np.int64) - 1
-    root = depth == 0
-    e0, e1 = bc == 0, nb.astype(np.int64) - 1 == bc.astype(np.int64)
-    first, last = e0 & ~parent, e1 & ~parent
-    d = first.astype(np.uint32) + 2 * last.astype(np.uint32) + 8 * ((parent | e1) & root).astype(np.uint32) + 4 * parent.astype(np.uint32)
-    istar = td.astype(np.int64) - 2 - depth.astype(np.int64)
-    ci = cil.astype(np.uint64) | (cih.astype(np.uint64) << np.uint64(32))
-    ok = (istar >= 0) & (istar < 64)
-    bit = (ci >> np.clip(istar, 0, 63).astype(np.uint64)) & np.uint64(1)
-    dl = np.where(parent, ok & (bit == 0), True)
-    msg = mm.copy()
-    left = np.where(dl[:, None], h, mm[:, :8])
-    right = np.where(dl[:, None], mm[:, :8], h)
-    msg[parent] = np.concatenate([left, right], axis=1)[parent]
-    hc = np.where(parent[:, None], IV[None, :], h)
-    t0, t1 = np.where(parent, 0, cil).astype(np.uint32), np.where(parent, 0, cih).astype(np.uint32)
-    out = _blake3_compress_np(hc.astype(np.uint32), msg.astype(np.uint32), t0, t1, b.copy(), d.astype(np.uint32))
-    bco = bc + (~parent).astype(np.uint32)
-    dout = depth - (((last | parent) & ~root)).astype(np.uint32)
-    return np.concatenate([nb[:, None], bco[:, None], out[:, :8], td[:, None], dout[:, None], cil[:, None], cih[:, None], ld[:, None]], axis=1).astype(np.uint32)
 
 
 def test_nova_full_config3_batch(m):
