@@ -50,8 +50,14 @@
 //   verify_tile, verify_upper           the same two storeys of verification (batch, stream, many)
 //   small_lane, small_levels, small_verify   the packed wave of files of at most 64 chunks (outboards, verify, ranged verify)
 //   block_piece, move_piece, block_cv   the relocation of a full tile's block (open sessions, many sessions, resize)
+//
+// Behind the device code comes the host side of the calls that launch it: first what the entry points share (one refusal path, one
+// launch epilogue for each staging kind, one builder for the sample table and one for the whole-batch tables, the small-file packer of
+// b3w_bao_tree.h), then the entry points, route by route, each route's own helpers in front of it.  The calls that touch no device (sizes, layouts, the host mirrors) are b3w_bao_host.cpp; the
+// arithmetic both need (B3W_TILE, preorder_pos, left_of, the places in a range slice) is b3w_bao_tree.h.
 #include "b3w_internal.h"
 #include "b3w_blake3_dev.h"
+#include "b3w_bao_plan.h"
 
 namespace {
 
@@ -258,23 +264,7 @@ __global__ __launch_bounds__(256) void b3w_bao_emit_kernel(const uint32_t *__res
 //                             CVs): the same merge over them, ROOT on a file's top merge.
 // Merging in place: the CV of the item that starts at slot i stays in slot i, so level l pairs slot (2 j) << l with slot ((2 j) << l) +
 // (1 << l) where that one exists, and an odd item out simply waits — which is BLAKE3's tree (tests/test_bao_batch_cpu.py restates it).
-constexpr uint32_t B3W_TILE = 1024;                      // chunks per tile = items per merge group
 struct BatchEnt { uint64_t off, len, ob; uint32_t first, file; };   // tile launches: arena offset; merge launches: first input CV slot
-
-// pre-order position, relative to the root of a tree over `total` chunks, of its node over chunks [a, a + size); the host walks use it too
-__host__ __device__ __forceinline__ uint64_t preorder_pos(uint64_t total, uint64_t a, uint64_t size) {
-  uint64_t p = 0, lo = 0, cnt = total;
-  while (cnt > 1 && !(lo == a && cnt == size)) {
-#ifdef __HIP_DEVICE_COMPILE__
-    const uint64_t k = 1ull << (63 - __clzll((long long)(cnt - 1)));
-#else
-    uint64_t k = 1;
-    while (k * 2 < cnt) k *= 2;
-#endif
-    if (a < lo + k) { p += 1; cnt = k; } else { p += k; lo += k; cnt -= k; }
-  }
-  return p;
-}
 
 // the last row of rows[lo .. hi) whose `first` is at or before x (rows sorted by first, rows[lo].first <= x): the entry whose workgroups
 // include workgroup x, or the small file whose lanes include lane x
@@ -2059,47 +2049,87 @@ __global__ __launch_bounds__(256) void b3w_bao_resize_relocate_kernel(const ResR
   }
 }
 
-// the CV of a chunk on the host (chunk_cv's loop over blake3_cv): b3w_bao_slice_decode
-void host_chunk_cv(const uint8_t *src, uint32_t bytes, uint64_t c, uint32_t root, uint32_t h[8]) {
-  const uint32_t nb = bytes ? (bytes + 63) / 64 : 1;
-  iv(h);
-  for (uint32_t j = 0; j < nb; ++j) {
-    const uint32_t bb = bytes - j * 64 < 64 ? bytes - j * 64 : 64;
-    uint32_t m[16] = {}, o[8];
-    for (uint32_t q = 0; q < bb; ++q) m[q / 4] |= (uint32_t)src[j * 64 + q] << (8 * (q & 3));
-    blake3_cv(h, m, (uint32_t)c, (uint32_t)(c >> 32), bb, (j == 0 ? 1u : 0u) | (j == nb - 1 ? 2u | root : 0u), o);
-    for (int k = 0; k < 8; ++k) h[k] = o[k];
+}  // namespace
+
+// ---- the host side: what the device entry points share ---------------------------------------------------------------------------------
+namespace {
+
+// ---- refusals: every bad argument of every call ends in refuse (b3w_internal.h, with group_log_ok) ---------------------------------------
+std::string entry_text(uint32_t i) { return "entry " + std::to_string(i) + ": "; }
+
+int32_t nova_ok(b3w_ctx *ctx) {
+  return ctx->desc.kind == B3W_KIND_COMP ? refuse(ctx, nullptr, "sampled paths plan the nova step circuits' records") : B3W_OK;
+}
+// every sample names a file of the batch and a chunk of that file
+int32_t samples_ok(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, const uint32_t *host_files, const uint64_t *host_chunks, uint32_t n_samples) {
+  for (uint32_t s = 0; s < n_samples; ++s) {
+    if (host_files[s] >= n_files) return refuse(ctx, nullptr, "a sampled file index is not below the file count");
+    if (host_chunks[s] >= num_chunks(host_lens[host_files[s]])) return refuse(ctx, nullptr, "a sampled chunk index is not below its file's chunk count");
   }
+  return B3W_OK;
+}
+// the arena calls: the samples' indices, and every sampled file inside [0, arena_bytes)
+int32_t arena_samples_ok(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
+                         uint32_t n_files, const uint32_t *host_files, const uint64_t *host_chunks, uint32_t n_samples) {
+  B3W_TRY(samples_ok(ctx, host_lens, n_files, host_files, host_chunks, n_samples));
+  for (uint32_t s = 0; s < n_samples; ++s) {
+    const uint64_t off = host_offsets[host_files[s]], len = host_lens[host_files[s]];
+    if (len && !d_arena) return refuse(ctx, nullptr, "a null arena with a sampled file that is not empty");
+    if (off > arena_bytes || len > arena_bytes - off) return refuse(ctx, nullptr, "a sampled file reaches past arena_bytes");
+  }
+  return B3W_OK;
+}
+// the whole-batch calls: no file too long for the grids, the scratch large enough and aligned, an arena where a file has bytes
+int32_t batch_ok(b3w_ctx *ctx, const char *call, const BatchCounts &k, const uint8_t *d_arena, const uint64_t *host_lens, uint32_t n_files, const void *d_scratch,
+                 uint64_t scratch_bytes, uint64_t need, const char *too_small) {
+  if (k.too_long || k.big_wgs > 0x7fffffffull) return refuse(ctx, call, "a file of more than 2^30 chunks, or more than 2^31 tiles");
+  if (scratch_bytes < need) return refuse(ctx, call, too_small);
+  if (need && (!d_scratch || ((uintptr_t)d_scratch & 15))) return refuse(ctx, call, "the scratch is null or not 16-byte aligned");
+  if (!d_arena)
+    for (uint32_t f = 0; f < n_files; ++f)
+      if (host_lens[f]) return refuse(ctx, call, "a null arena with a file that is not empty");
+  return B3W_OK;
 }
 
-uint64_t num_chunks(uint64_t len) { return len ? (len + 1023) / 1024 : 1; }
-uint32_t chunk_blocks(uint64_t len, uint64_t c) {
-  const uint64_t off = c * 1024, bytes = len - off < 1024 ? len - off : 1024;
-  return bytes ? (uint32_t)((bytes + 63) / 64) : 1;
+// ---- launches: which kernel, and what follows the last one -------------------------------------------------------------------------------
+// a kernel template over the lanes a sample (1, 4 or 16): f(K) launches the instantiation, lanes_grid its grid of waves
+template <class F>
+void with_lanes(int lanes, F f) {
+  if (lanes == 1) f(std::integral_constant<int, 1>{});
+  else if (lanes == 4) f(std::integral_constant<int, 4>{});
+  else f(std::integral_constant<int, 16>{});
+}
+template <int K>
+dim3 lanes_grid(uint32_t n_samples) { return dim3((n_samples + 64 / K - 1) / (64 / K)); }
+
+// a kernel, or with `grp` its group instantiation, which takes group_log behind the same arguments
+template <class P, class G, class... A>
+void launch_pair(bool grp, P plain, G group, uint32_t group_log, dim3 grid, dim3 block, hipStream_t st, A... args) {
+  if (grp) hipLaunchKernelGGL(group, grid, block, 0, st, args..., group_log);
+  else hipLaunchKernelGGL(plain, grid, block, 0, st, args...);
 }
 
-// what a batch of these lengths launches: files of at most 64 chunks share waves, in file order, as many as fit (small), the others take a
-// workgroup per tile (big);
-// files of more than one tile a merge workgroup per 1 024 tiles (groups), files of more than 1 024 tiles one more over those (tops)
-struct BatchCounts { uint64_t small, waves, big, big_wgs, merged, groups, tops; bool too_long; };
-BatchCounts batch_counts(const uint64_t *lens, uint32_t n_files) {
-  BatchCounts k{};
-  uint64_t fill = 64;                                    // lanes taken in the current wave of small files (none open yet)
-  for (uint32_t f = 0; f < n_files; ++f) {
-    const uint64_t n = num_chunks(lens[f]);
-    if (n <= 64) {
-      if (fill + n > 64) { k.waves++; fill = 0; }
-      fill += n;
-      k.small++;
-      continue;
-    }
-    const uint64_t tiles = (n + B3W_TILE - 1) / B3W_TILE, groups = (tiles + B3W_TILE - 1) / B3W_TILE;
-    k.big++; k.big_wgs += tiles;
-    if (tiles > 1) { k.merged++; k.groups += groups; }
-    if (groups > 1) k.tops++;
-    if (groups > B3W_TILE) k.too_long = true;
-  }
-  return k;
+// a file's merge storeys over the tile CVs of a streamed file: a workgroup per 1 024 tiles, one more over those past 1 GiB
+void stream_merge(uint64_t len, uint64_t groups, uint32_t gl, const uint32_t *tile_cv, uint32_t *group_cv, uint8_t *ob, uint32_t *root, hipStream_t st) {
+  const uint64_t T = B3W_TILE;
+  launch_pair(gl != 0, b3w_bao_stream_merge_kernel, b3w_bao_stream_merge_group_kernel, gl, dim3((uint32_t)groups), dim3(256), st, len, T, tile_cv, group_cv, ob, root);
+  if (groups > 1)
+    launch_pair(gl != 0, b3w_bao_stream_merge_kernel, b3w_bao_stream_merge_group_kernel, gl, dim3(1), dim3(256), st, len, T * T, (const uint32_t *)group_cv, (uint32_t *)nullptr, ob, root);
+}
+// the same two storeys over the rows of a table of files: n1 rows in wg1 workgroups, then n2 rows behind them
+void many_merge(bool grp, const ManyRow *d_one, uint32_t n1, uint32_t wg1, const ManyRow *d_two, uint32_t n2, hipStream_t st) {
+  const uint64_t T = B3W_TILE;
+  const auto kernel = grp ? b3w_bao_stream_merge_many_group_kernel : b3w_bao_stream_merge_many_kernel;
+  if (n1) hipLaunchKernelGGL(kernel, dim3(wg1), dim3(256), 0, st, d_one, n1, T);
+  if (n2) hipLaunchKernelGGL(kernel, dim3(n2), dim3(256), 0, st, d_two, n2, T * T);
+}
+
+// behind the launches of a call whose table went through the batch staging: the event is not recorded after a failed launch
+int32_t batch_launched(b3w_ctx *ctx, hipStream_t st, const char *what) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(ctx, e, what);
+  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
+  return B3W_OK;
 }
 
 // the context's staging for the batch calls' tables: waits for the previous batch call, grows both buffers to `bytes`
@@ -2117,11 +2147,188 @@ int32_t batch_staging(b3w_ctx *ctx, uint64_t bytes) {
   return B3W_OK;
 }
 
+// ---- the sample table of the sampled-path, slice and ingest calls -------------------------------------------------------------------------
+// A row is {chunk, word 1, length, word 3, file[, the file's arena offset]}.  The rows go into the batch staging and on to the device;
+// behind them, on the host, lies the files' outboard layout the rows are filled from (none where word 3 is the slice's offset).
+struct SampleRows {
+  uint32_t words;                                        // 5, or 6: with the file's arena offset
+  bool w1_slice, w3_slice;                               // word 1: the sample's slice offset, not its first record row; word 3: the same, not its file's outboard offset
+  bool have;                                             // the have layout takes the outboard layout's place once the rows are filled, and is uploaded with them
+};
+// -> the table on the device and the batch's longest path.  The call is host work a sample before it is anything else, so the path is
+// walked once a sample, with the split from a bit scan (depth_in), and serves the record rows, the slice's size and the longest path;
+// and the rows' kind is a template argument, so that a call's loop computes only what its rows hold (with the kind a run-time value the
+// ingest call at 65 536 slices took 3.6 % longer than the parent's own loop: profiles/r24/bao_host_ab.json, "first_build").
+template <uint32_t WORDS, bool W1_SLICE, bool W3_SLICE, bool HAVE>
+int32_t sample_table(b3w_ctx *ctx, const uint64_t *host_offsets, const uint64_t *host_lens, uint32_t n_files, uint32_t group_log,
+                     const uint32_t *host_files, const uint64_t *host_chunks, uint32_t n_samples, hipStream_t st, const uint64_t **d_desc,
+                     uint32_t *longest = nullptr) {
+  constexpr SampleRows k{WORDS, W1_SLICE, W3_SLICE, HAVE};
+  const uint64_t desc_bytes = (uint64_t)n_samples * k.words * 8, layout_bytes = k.w3_slice ? 0 : ((uint64_t)n_files + 1) * 8;
+  B3W_TRY(batch_staging(ctx, desc_bytes + layout_bytes));
+  uint64_t *desc = reinterpret_cast<uint64_t *>(ctx->h_batch), *ob_first = desc + (uint64_t)k.words * n_samples;
+  if (!k.w3_slice) (void)b3w_bao_group_batch_layout(host_lens, n_files, group_log, ob_first);        // (group_log 0: b3w_bao_batch_layout's)
+  uint64_t row = 0, at = slice_start(0);
+  uint32_t most = 0;
+  for (uint32_t s = 0; s < n_samples; ++s) {
+    const uint32_t f = host_files[s];
+    const uint64_t len = host_lens[f], c = host_chunks[s];
+    const uint32_t P = depth_in(c, num_chunks(len));
+    uint64_t *d = desc + (uint64_t)k.words * s;
+    d[0] = c; d[1] = k.w1_slice ? at : row; d[2] = len; d[3] = k.w3_slice ? at : ob_first[f]; d[4] = f;
+    if (k.words == 6) d[5] = host_offsets[f];
+    row += chunk_blocks(len, c) + P;
+    at = slice_start(at + slice_bytes(len, c, P));
+    if (P > most) most = P;
+  }
+  if (k.have) (void)b3w_bao_have_layout(host_lens, n_files, ob_first);
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)(desc_bytes + (k.have ? layout_bytes : 0)), hipMemcpyHostToDevice, st));
+  *d_desc = reinterpret_cast<const uint64_t *>(ctx->d_batch);
+  if (longest) *longest = most;
+  return B3W_OK;
+}
+
+// ---- the tables of the two whole-batch calls (outboards, verification) --------------------------------------------------------------------
+// one behind the other in the staging, uploaded in one copy: small | big | merged | tops | [verification: a VerFile a file |] the small
+// waves' first files
+struct BatchTables { BatchEnt *small, *big, *merged, *tops; VerFile *files; uint32_t *waves; };
+BatchTables batch_tables_at(uint8_t *base, const BatchCounts &k, uint32_t n_ver_files) {
+  BatchTables t;
+  t.small = reinterpret_cast<BatchEnt *>(base); t.big = t.small + k.small; t.merged = t.big + k.big; t.tops = t.merged + k.merged;
+  t.files = reinterpret_cast<VerFile *>(t.tops + k.tops);
+  t.waves = reinterpret_cast<uint32_t *>(t.files + n_ver_files);
+  return t;
+}
+// -> the tables on the device.  The outboard calls' merged and top entries start with their first input CV slot (big_wgs, groups);
+// verification's with 0, and it adds the files' rows {first unit, first tile's scratch entry, first group's}
+int32_t batch_tables(b3w_ctx *ctx, const BatchCounts &k, const uint64_t *host_offsets, const uint64_t *host_lens, uint32_t n_files, uint32_t gl, bool verify,
+                     hipStream_t st, BatchTables *d) {
+  const uint32_t n_ver = verify ? n_files : 0;
+  const uint64_t n_ents = k.small + k.big + k.merged + k.tops;
+  const uint64_t table_bytes = n_ents * sizeof(BatchEnt) + (uint64_t)n_ver * sizeof(VerFile) + (k.small ? (k.waves + 1) * 4 : 0);
+  B3W_TRY(batch_staging(ctx, table_bytes));
+  const BatchTables h = batch_tables_at(ctx->h_batch, k, n_ver);
+  SmallPack pack;
+  pack.first = h.waves;
+  uint32_t i_big = 0, i_merged = 0, i_tops = 0, big_wgs = 0, groups = 0;
+  uint64_t ob = 0, units = 0, slot = 0, gslot = 0;
+  for (uint32_t f = 0; f < n_files; ++f) {
+    const uint64_t len = host_lens[f], n = num_chunks(len);
+    if (verify) h.files[f] = VerFile{units, slot, gslot};
+    if (n <= 64) {
+      const uint32_t lane = pack.add(n);
+      h.small[pack.files - 1] = BatchEnt{host_offsets[f], len, ob, lane, f};
+    } else {
+      const uint32_t tiles = (uint32_t)((n + B3W_TILE - 1) / B3W_TILE), grp = (tiles + B3W_TILE - 1) / B3W_TILE;
+      h.big[i_big++] = BatchEnt{host_offsets[f], len, ob, big_wgs, f};
+      if (tiles > 1) h.merged[i_merged++] = BatchEnt{verify ? 0 : big_wgs, len, ob, groups, f};
+      if (grp > 1) { h.tops[i_tops] = BatchEnt{verify ? 0 : groups, len, ob, i_tops, f}; i_tops++; }
+      big_wgs += tiles;
+      if (tiles > 1) { groups += grp; slot += tiles; }
+      if (grp > 1) gslot += grp;
+    }
+    ob += group_outboard_bytes(len, gl);
+    units += n_units(len, gl);
+  }
+  pack.close();
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)table_bytes, hipMemcpyHostToDevice, st));
+  *d = batch_tables_at(ctx->d_batch, k, n_ver);
+  return B3W_OK;
+}
+
+// ---- the bodies of entry points that come in pairs ------------------------------------------------------------------------------------------
+// b3w_sample_plan_batch_device (the kernel of ABI 1.2 over full outboards) and b3w_sample_plan_group_batch_device
+int32_t sample_plan_batch(b3w_ctx *ctx, const char *call, const uint64_t *host_lens, uint32_t n_files, bool grp, uint32_t group_log, const uint8_t *d_outboards,
+                                 const uint32_t *d_roots, const uint32_t *host_files, const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_bytes,
+                                 uint32_t *d_records, int32_t *d_sample_status, void *stream, const char *launch) {
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  B3W_TRY(nova_ok(ctx));
+  B3W_TRY(group_log_ok(ctx, call, group_log));
+  if (!n_samples) return B3W_OK;
+  if (!host_lens || !d_outboards || !d_roots || !host_files || !host_chunks || !d_bytes || !d_records || !d_sample_status) return refuse(ctx, call, "a null pointer");
+  B3W_TRY(samples_ok(ctx, host_lens, n_files, host_files, host_chunks, n_samples));
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t *d_desc = nullptr;
+  B3W_TRY(sample_table<5, false, false, false>(ctx, nullptr, host_lens, n_files, group_log, host_files, host_chunks, n_samples, st, &d_desc));
+  const uint32_t per_wave = 64u >> group_log;
+  if (grp) hipLaunchKernelGGL(b3w_sample_plan_group_kernel<false>, dim3((n_samples + per_wave - 1) / per_wave), dim3(64), 0, st, d_outboards, d_roots, d_desc, n_samples, group_log, d_bytes, d_records, d_sample_status);
+  else hipLaunchKernelGGL(b3w_sample_plan_batch_kernel, dim3((n_samples + 63) / 64), dim3(64), 0, st, d_outboards, d_roots, d_desc, n_samples, d_bytes, d_records, d_sample_status);
+  return batch_launched(ctx, st, launch);
+}
+
+// grp false: full outboards, the kernels of ABI 1.2; true: group outboards (group_log 0 included), their group instantiations
+int32_t outboard_batch(b3w_ctx *ctx, const uint8_t *d_arena, const uint64_t *host_offsets, const uint64_t *host_lens, uint32_t n_files, bool grp, uint32_t gl,
+                              uint8_t *d_outboards, uint32_t *d_roots, void *d_scratch, uint64_t scratch_bytes, void *stream) {
+  const char *call = "bao batch";
+  if (!n_files) return B3W_OK;
+  if (!host_offsets || !host_lens || !d_outboards || !d_roots) return refuse(ctx, call, "a null pointer (offsets, lengths, outboards or roots)");
+  if ((uintptr_t)d_outboards & 7) return refuse(ctx, call, "d_outboards is not 8-byte aligned");
+  const BatchCounts k = batch_counts(host_lens, n_files);
+  B3W_TRY(batch_ok(ctx, call, k, d_arena, host_lens, n_files, d_scratch, scratch_bytes, (k.big_wgs + k.groups) * 32,
+                   "the scratch is smaller than b3w_bao_batch_scratch_bytes says"));
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  BatchTables d;
+  B3W_TRY(batch_tables(ctx, k, host_offsets, host_lens, n_files, gl, false, st, &d));
+  uint32_t *tile_cv = reinterpret_cast<uint32_t *>(d_scratch), *group_cv = tile_cv + k.big_wgs * 8;
+  const uint64_t T = B3W_TILE;
+  if (k.small) launch_pair(grp, b3w_bao_small_kernel, b3w_bao_small_group_kernel, gl, dim3((uint32_t)k.waves), dim3(64), st, d_arena, (const BatchEnt *)d.small, (const uint32_t *)d.waves, d_outboards, d_roots);
+  if (k.big) launch_pair(grp, b3w_bao_tile_kernel, b3w_bao_tile_group_kernel, gl, dim3((uint32_t)k.big_wgs), dim3(B3W_TILE), st, d_arena, (const BatchEnt *)d.big, (uint32_t)k.big, d_outboards, d_roots, tile_cv);
+  if (k.merged) launch_pair(grp, b3w_bao_merge_kernel, b3w_bao_merge_group_kernel, gl, dim3((uint32_t)k.groups), dim3(256), st, (const BatchEnt *)d.merged, (uint32_t)k.merged, T, (const uint32_t *)tile_cv, group_cv, d_outboards, d_roots);
+  if (k.tops) launch_pair(grp, b3w_bao_merge_kernel, b3w_bao_merge_group_kernel, gl, dim3((uint32_t)k.tops), dim3(256), st, (const BatchEnt *)d.tops, (uint32_t)k.tops, T * T, (const uint32_t *)group_cv, (uint32_t *)nullptr, d_outboards, d_roots);
+  return batch_launched(ctx, st, grp ? "bao group batch launch" : "bao batch launch");
+}
+
+// the slices of the samples gathered from the outboards: 16 lanes a sample from full outboards, a lane a chunk of the group from group
+// outboards; ARENA: the bytes read where the files lie
+template <bool ARENA>
+void launch_slices(uint32_t group_log, uint32_t n_samples, hipStream_t st, const uint8_t *d_outboards, const uint64_t *d_desc, const uint8_t *d_bytes, uint8_t *d_slices) {
+  const uint32_t per_wg = 256 / SLICE_LANES, per_wave = 64u >> group_log;
+  if (group_log == 0) hipLaunchKernelGGL(b3w_bao_slice_kernel<ARENA>, dim3((n_samples + per_wg - 1) / per_wg), dim3(256), 0, st, d_outboards, d_desc, n_samples, d_bytes, d_slices);
+  else hipLaunchKernelGGL(b3w_bao_slice_group_kernel<ARENA>, dim3((n_samples + per_wave - 1) / per_wave), dim3(64), 0, st, d_outboards, d_desc, n_samples, group_log, d_bytes, d_slices);
+}
+
+// b3w_bao_slice_ingest_device (HAVE false: d_have is not looked at) and b3w_bao_slice_ingest_have_device
+template <bool HAVE>
+int32_t slice_ingest(b3w_ctx *ctx, uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
+                            uint32_t n_files, uint32_t group_log, uint8_t *d_outboards, const uint32_t *d_roots, const uint32_t *host_files,
+                            const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_slices, int32_t *d_sample_status, uint64_t *d_have, void *stream) {
+  const char *call = "bao slice ingest";
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  B3W_TRY(group_log_ok(ctx, call, group_log));
+  if (HAVE && (!d_have || ((uintptr_t)d_have & 7))) return refuse(ctx, call, "d_have is null or not 8-byte aligned");
+  if (!n_samples) return B3W_OK;
+  if (!host_offsets || !host_lens || !d_outboards || !d_roots || !host_files || !host_chunks || !d_slices || !d_sample_status) return refuse(ctx, call, "a null pointer");
+  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) return refuse(ctx, call, "d_outboards is not 8-byte or d_slices not 16-byte aligned");
+  B3W_TRY(arena_samples_ok(ctx, d_arena, arena_bytes, host_offsets, host_lens, n_files, host_files, host_chunks, n_samples));
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t *d_desc = nullptr;
+  uint32_t longest = 0;
+  B3W_TRY(sample_table<6, true, false, HAVE>(ctx, host_offsets, host_lens, n_files, group_log, host_files, host_chunks, n_samples, st, &d_desc, &longest));
+  // lanes a sample, from the batch's longest path P: node j is checked by lane j mod K, ceil(P / K) rounds beside the chunk's sixteen blocks,
+  // and every lane fewer a sample is a leader more a wave in the stretch only leaders run.  Measured at P = 20 (DESIGN.md 8g): four lanes
+  // (five rounds) beat sixteen (two) at 4 096 and at 65 536 slices, so four up to six rounds; sixteen for the longer paths (files past
+  // 16 GiB; not measured).  B3W_SLICE_INGEST_LANES=1 / 4 / 16: measurements
+  const char *env = getenv("B3W_SLICE_INGEST_LANES");
+  unsigned long long *have = HAVE ? reinterpret_cast<unsigned long long *>(d_have) : nullptr;
+  with_lanes(env ? atoi(env) : (longest <= 24 ? 4 : 16), [&](auto K) {
+    constexpr int LANES = decltype(K)::value;
+    hipLaunchKernelGGL((b3w_bao_slice_ingest_kernel<LANES, HAVE>), lanes_grid<LANES>(n_samples), dim3(64), 0, st, d_slices, d_roots, d_desc, n_samples, group_log, d_arena,
+                       d_outboards, d_sample_status, have);
+  });
+  return batch_launched(ctx, st, "bao slice ingest launch");
+}
+
 }  // namespace
 
-extern "C" {
+// b3w_bao_have.hip's way to the staging of the batch calls and to their epilogue
+int32_t b3w_int_batch_staging(b3w_ctx *ctx, uint64_t bytes) { return batch_staging(ctx, bytes); }
+int32_t b3w_int_batch_launched(b3w_ctx *ctx, hipStream_t st, const char *what) { return batch_launched(ctx, st, what); }
 
-uint64_t b3w_bao_outboard_size(uint64_t len) { return 8 + 64 * (num_chunks(len) - 1); }
+// ---- the device entry points (the calls that touch no device: b3w_bao_host.cpp) ----------------------------------------------------------
+extern "C" {
 
 int32_t b3w_bao_outboard_device(b3w_ctx *ctx, const uint8_t *d_preimage, uint64_t len, uint8_t *d_outboard, uint32_t *d_levels, uint32_t *d_root,
                                 void *stream) {
@@ -2136,47 +2343,14 @@ int32_t b3w_bao_outboard_device(b3w_ctx *ctx, const uint8_t *d_preimage, uint64_
   else hipLaunchKernelGGL(b3w_bao_cv_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, d_preimage, len, n, d_levels);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(ctx, e, "bao chunk CV launch");
-  const int32_t rc = b3w_chain_tree_device(ctx, d_levels, n, d_root, stream);
-  if (rc) return rc;
+  B3W_TRY(b3w_chain_tree_device(ctx, d_levels, n, d_root, stream));
   const B3wSpine sp = n > 1 ? spine_of(n) : B3wSpine{};
   hipLaunchKernelGGL(b3w_bao_emit_kernel, dim3((uint32_t)(n > 1 ? (n - 1 + 255) / 256 : 1)), dim3(256), 0, st, d_levels, n, len, sp, d_outboard);
   e = hipGetLastError();
   return e != hipSuccess ? hip_fail(ctx, e, "bao emit launch") : B3W_OK;
 }
 
-int32_t b3w_bao_path_nodes(uint64_t chunk, uint64_t n_chunks, uint64_t *out_index, uint32_t *out_count) {
-  if (!out_index || !out_count || !n_chunks || chunk >= n_chunks) return B3W_E_BAD_ARGUMENT;
-  uint64_t p = 0, c = chunk, m = n_chunks;
-  uint32_t i = 0;
-  while (m > 1) {
-    uint64_t k = 1;
-    while (k * 2 < m) k *= 2;
-    out_index[i++] = p;
-    if (c < k) { p += 1; m = k; } else { p += k; c -= k; m -= k; }
-  }
-  *out_count = i;
-  return B3W_OK;
-}
-
-int32_t b3w_bao_slice(const uint8_t *outboard, uint64_t len, uint64_t chunk, const uint8_t *chunk_bytes, uint8_t *out, uint64_t *out_len) {
-  const uint64_t n = num_chunks(len);
-  if (!outboard || !out_len || chunk >= n) return B3W_E_BAD_ARGUMENT;
-  uint64_t hdr = 0;
-  for (int k = 0; k < 8; ++k) hdr |= (uint64_t)outboard[k] << (8 * k);
-  if (hdr != len) return B3W_E_BAD_ARGUMENT;
-  uint64_t idx[64];
-  uint32_t P = 0;
-  (void)b3w_bao_path_nodes(chunk, n, idx, &P);
-  const uint64_t off = chunk * 1024, bytes = len - off < 1024 ? len - off : 1024;
-  *out_len = 8 + 64ull * P + bytes;
-  if (!out) return B3W_OK;
-  if (bytes && !chunk_bytes) return B3W_E_BAD_ARGUMENT;
-  memcpy(out, outboard, 8);
-  for (uint32_t i = 0; i < P; ++i) memcpy(out + 8 + 64ull * i, outboard + 8 + 64 * idx[i], 64);
-  if (bytes) memcpy(out + 8 + 64ull * P, chunk_bytes, bytes);
-  return B3W_OK;
-}
-
+// ---- challenged paths: the record rows (here, where b3w_plan_path_len links) and the planners ------------------------------------------
 int64_t b3w_sample_rows(uint64_t len, const uint64_t *host_chunks, uint32_t n_samples, uint64_t *row_first) {
   if ((!host_chunks && n_samples) || !row_first) return -B3W_E_BAD_ARGUMENT;
   const uint64_t n = num_chunks(len);
@@ -2191,13 +2365,29 @@ int64_t b3w_sample_rows(uint64_t len, const uint64_t *host_chunks, uint32_t n_sa
   return (int64_t)row;
 }
 
+int64_t b3w_sample_rows_batch(const uint64_t *host_lens, uint32_t n_files, const uint32_t *host_files, const uint64_t *host_chunks,
+                              uint32_t n_samples, uint64_t *row_first) {
+  if (!row_first || (n_samples && (!host_lens || !host_files || !host_chunks))) return -B3W_E_BAD_ARGUMENT;
+  for (uint32_t s = 0; s < n_samples; ++s)
+    if (host_files[s] >= n_files || host_chunks[s] >= num_chunks(host_lens[host_files[s]])) return -B3W_E_BAD_ARGUMENT;
+  uint64_t row = 0;
+  for (uint32_t s = 0; s < n_samples; ++s) {
+    const uint64_t len = host_lens[host_files[s]];
+    row_first[s] = row;
+    row += chunk_blocks(len, host_chunks[s]) + b3w_plan_path_len(host_chunks[s], num_chunks(len));
+  }
+  row_first[n_samples] = row;
+  return (int64_t)row;
+}
+
+// (its own staging and event, h_samples / d_samples / samples_done: on the batch staging it would wait for the batch calls)
 int32_t b3w_sample_plan_device(b3w_ctx *ctx, uint64_t len, const uint8_t *d_outboard, const uint32_t *root, const uint64_t *host_chunks,
                                uint32_t n_samples, const uint8_t *d_chunk_bytes, uint32_t *d_records, int32_t *d_sample_status, void *stream) {
   if (!ctx || !d_outboard || !root || (n_samples && (!host_chunks || !d_chunk_bytes || !d_records || !d_sample_status))) return B3W_E_BAD_ARGUMENT;
-  if (ctx->desc.kind == B3W_KIND_COMP) { ctx->last_error = "sampled paths plan the nova step circuits' records"; return B3W_E_BAD_ARGUMENT; }
+  B3W_TRY(nova_ok(ctx));
   const uint64_t n = num_chunks(len);
   for (uint32_t s = 0; s < n_samples; ++s)
-    if (host_chunks[s] >= n) { ctx->last_error = "a sampled chunk index is not below the chunk count"; return B3W_E_BAD_ARGUMENT; }
+    if (host_chunks[s] >= n) return refuse(ctx, nullptr, "a sampled chunk index is not below the chunk count");
   if (!n_samples) return B3W_OK;
   ON_DEVICE(ctx);
   hipStream_t st = (hipStream_t)stream;
@@ -2230,562 +2420,154 @@ int32_t b3w_sample_plan_device(b3w_ctx *ctx, uint64_t len, const uint8_t *d_outb
   return B3W_OK;
 }
 
-uint64_t b3w_bao_batch_layout(const uint64_t *host_lens, uint32_t n_files, uint64_t *ob_first) {
-  if (!ob_first || (!host_lens && n_files)) return 0;
-  uint64_t at = 0;
-  for (uint32_t f = 0; f < n_files; ++f) { ob_first[f] = at; at += b3w_bao_outboard_size(host_lens[f]); }
-  ob_first[n_files] = at;
-  return at;
-}
-
-uint64_t b3w_bao_batch_scratch_bytes(const uint64_t *host_lens, uint32_t n_files) {
-  if (!host_lens) return 0;
-  const BatchCounts k = batch_counts(host_lens, n_files);
-  return (k.big_wgs + k.groups) * 32;
-}
-
-// gl < 0: full outboards, the kernels of ABI 1.2; 0 .. B3W_BAO_MAX_GROUP_LOG: group outboards, their group instantiations
-static int32_t outboard_batch(b3w_ctx *ctx, const uint8_t *d_arena, const uint64_t *host_offsets, const uint64_t *host_lens, uint32_t n_files, int gl,
-                              uint8_t *d_outboards, uint32_t *d_roots, void *d_scratch, uint64_t scratch_bytes, void *stream) {
-  if (!ctx) return B3W_E_BAD_ARGUMENT;
-  if (gl > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "bao batch: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
-  if (!n_files) return B3W_OK;
-  if (!host_offsets || !host_lens || !d_outboards || !d_roots) { ctx->last_error = "bao batch: a null pointer (offsets, lengths, outboards or roots)"; return B3W_E_BAD_ARGUMENT; }
-  if ((uintptr_t)d_outboards & 7) { ctx->last_error = "bao batch: d_outboards is not 8-byte aligned"; return B3W_E_BAD_ARGUMENT; }
-  const BatchCounts k = batch_counts(host_lens, n_files);
-  if (k.too_long || k.big_wgs > 0x7fffffffull) { ctx->last_error = "bao batch: a file of more than 2^30 chunks, or more than 2^31 tiles"; return B3W_E_BAD_ARGUMENT; }
-  const uint64_t need = (k.big_wgs + k.groups) * 32;
-  if (scratch_bytes < need) { ctx->last_error = "bao batch: the scratch is smaller than b3w_bao_batch_scratch_bytes says"; return B3W_E_BAD_ARGUMENT; }
-  if (need && (!d_scratch || ((uintptr_t)d_scratch & 15))) { ctx->last_error = "bao batch: the scratch is null or not 16-byte aligned"; return B3W_E_BAD_ARGUMENT; }
-  if (!d_arena)
-    for (uint32_t f = 0; f < n_files; ++f)
-      if (host_lens[f]) { ctx->last_error = "bao batch: a null arena with a file that is not empty"; return B3W_E_BAD_ARGUMENT; }
-  ON_DEVICE(ctx);
-  hipStream_t st = (hipStream_t)stream;
-  // the tables, one behind the other in the staging buffers, uploaded in one copy: small | big | merged | tops | the small waves' first files
-  const uint64_t n_ents = k.small + k.big + k.merged + k.tops, table_bytes = n_ents * sizeof(BatchEnt) + (k.small ? (k.waves + 1) * 4 : 0);
-  const int32_t rc = batch_staging(ctx, table_bytes);
-  if (rc) return rc;
-  BatchEnt *h_small = reinterpret_cast<BatchEnt *>(ctx->h_batch), *h_big = h_small + k.small, *h_merged = h_big + k.big, *h_tops = h_merged + k.merged;
-  uint32_t *h_waves = reinterpret_cast<uint32_t *>(h_tops + k.tops);
-  uint32_t i_small = 0, i_waves = 0, fill = 64, i_big = 0, i_merged = 0, i_tops = 0, big_wgs = 0, groups = 0;
-  uint64_t ob = 0;
-  const uint32_t sh = gl < 0 ? 0 : (uint32_t)gl;
-  for (uint32_t f = 0; f < n_files; ++f) {
-    const uint64_t len = host_lens[f], n = num_chunks(len);
-    if (n <= 64) {
-      if (fill + n > 64) { h_waves[i_waves++] = i_small; fill = 0; }
-      h_small[i_small] = BatchEnt{host_offsets[f], len, ob, fill, f};
-      fill += (uint32_t)n;
-      i_small++;
-    } else {
-      const uint32_t tiles = (uint32_t)((n + B3W_TILE - 1) / B3W_TILE), grp = (tiles + B3W_TILE - 1) / B3W_TILE;
-      h_big[i_big++] = BatchEnt{host_offsets[f], len, ob, big_wgs, f};
-      if (tiles > 1) h_merged[i_merged++] = BatchEnt{big_wgs, len, ob, groups, f};
-      if (grp > 1) { h_tops[i_tops] = BatchEnt{groups, len, ob, i_tops, f}; i_tops++; }
-      big_wgs += tiles;
-      if (tiles > 1) groups += grp;
-    }
-    ob += 8 + 64 * (((n + ((1ull << sh) - 1)) >> sh) - 1);            // (b3w_bao_outboard_size / b3w_bao_group_outboard_size)
-  }
-  if (k.small) h_waves[i_waves] = i_small;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)table_bytes, hipMemcpyHostToDevice, st));
-  const BatchEnt *d_small = reinterpret_cast<const BatchEnt *>(ctx->d_batch), *d_big = d_small + k.small, *d_merged = d_big + k.big, *d_tops = d_merged + k.merged;
-  uint32_t *tile_cv = reinterpret_cast<uint32_t *>(d_scratch), *group_cv = tile_cv + k.big_wgs * 8;
-  if (gl >= 0) {
-    const uint32_t g = (uint32_t)gl;
-    if (k.small) hipLaunchKernelGGL(b3w_bao_small_group_kernel, dim3((uint32_t)k.waves), dim3(64), 0, st, d_arena, d_small, reinterpret_cast<const uint32_t *>(d_tops + k.tops), d_outboards, d_roots, g);
-    if (k.big) hipLaunchKernelGGL(b3w_bao_tile_group_kernel, dim3((uint32_t)k.big_wgs), dim3(B3W_TILE), 0, st, d_arena, d_big, (uint32_t)k.big, d_outboards, d_roots, tile_cv, g);
-    if (k.merged) hipLaunchKernelGGL(b3w_bao_merge_group_kernel, dim3((uint32_t)k.groups), dim3(256), 0, st, d_merged, (uint32_t)k.merged, (uint64_t)B3W_TILE, tile_cv, group_cv, d_outboards, d_roots, g);
-    if (k.tops) hipLaunchKernelGGL(b3w_bao_merge_group_kernel, dim3((uint32_t)k.tops), dim3(256), 0, st, d_tops, (uint32_t)k.tops, (uint64_t)B3W_TILE * B3W_TILE, group_cv, (uint32_t *)nullptr, d_outboards, d_roots, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(ctx, e, "bao group batch launch");
-    HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
-    return B3W_OK;
-  }
-  if (k.small) hipLaunchKernelGGL(b3w_bao_small_kernel, dim3((uint32_t)k.waves), dim3(64), 0, st, d_arena, d_small, reinterpret_cast<const uint32_t *>(d_tops + k.tops), d_outboards, d_roots);
-  if (k.big) hipLaunchKernelGGL(b3w_bao_tile_kernel, dim3((uint32_t)k.big_wgs), dim3(B3W_TILE), 0, st, d_arena, d_big, (uint32_t)k.big, d_outboards, d_roots, tile_cv);
-  if (k.merged) hipLaunchKernelGGL(b3w_bao_merge_kernel, dim3((uint32_t)k.groups), dim3(256), 0, st, d_merged, (uint32_t)k.merged, (uint64_t)B3W_TILE, tile_cv, group_cv, d_outboards, d_roots);
-  if (k.tops) hipLaunchKernelGGL(b3w_bao_merge_kernel, dim3((uint32_t)k.tops), dim3(256), 0, st, d_tops, (uint32_t)k.tops, (uint64_t)B3W_TILE * B3W_TILE, group_cv, (uint32_t *)nullptr, d_outboards, d_roots);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(ctx, e, "bao batch launch");
-  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
-  return B3W_OK;
-}
-
-int32_t b3w_bao_outboard_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, const uint64_t *host_offsets, const uint64_t *host_lens,
-                                      uint32_t n_files, uint8_t *d_outboards, uint32_t *d_roots, void *d_scratch, uint64_t scratch_bytes,
-                                      void *stream) {
-  return outboard_batch(ctx, d_arena, host_offsets, host_lens, n_files, -1, d_outboards, d_roots, d_scratch, scratch_bytes, stream);
-}
-
-int64_t b3w_sample_rows_batch(const uint64_t *host_lens, uint32_t n_files, const uint32_t *host_files, const uint64_t *host_chunks,
-                              uint32_t n_samples, uint64_t *row_first) {
-  if (!row_first || (n_samples && (!host_lens || !host_files || !host_chunks))) return -B3W_E_BAD_ARGUMENT;
-  for (uint32_t s = 0; s < n_samples; ++s)
-    if (host_files[s] >= n_files || host_chunks[s] >= num_chunks(host_lens[host_files[s]])) return -B3W_E_BAD_ARGUMENT;
-  uint64_t row = 0;
-  for (uint32_t s = 0; s < n_samples; ++s) {
-    const uint64_t len = host_lens[host_files[s]];
-    row_first[s] = row;
-    row += chunk_blocks(len, host_chunks[s]) + b3w_plan_path_len(host_chunks[s], num_chunks(len));
-  }
-  row_first[n_samples] = row;
-  return (int64_t)row;
-}
-
 int32_t b3w_sample_plan_batch_device(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, const uint8_t *d_outboards, const uint32_t *d_roots,
                                      const uint32_t *host_files, const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_chunk_bytes,
                                      uint32_t *d_records, int32_t *d_sample_status, void *stream) {
-  if (!ctx) return B3W_E_BAD_ARGUMENT;
-  if (ctx->desc.kind == B3W_KIND_COMP) { ctx->last_error = "sampled paths plan the nova step circuits' records"; return B3W_E_BAD_ARGUMENT; }
-  if (!n_samples) return B3W_OK;
-  if (!host_lens || !d_outboards || !d_roots || !host_files || !host_chunks || !d_chunk_bytes || !d_records || !d_sample_status) {
-    ctx->last_error = "sample plan batch: a null pointer"; return B3W_E_BAD_ARGUMENT;
-  }
-  for (uint32_t s = 0; s < n_samples; ++s) {
-    if (host_files[s] >= n_files) { ctx->last_error = "a sampled file index is not below the file count"; return B3W_E_BAD_ARGUMENT; }
-    if (host_chunks[s] >= num_chunks(host_lens[host_files[s]])) { ctx->last_error = "a sampled chunk index is not below its file's chunk count"; return B3W_E_BAD_ARGUMENT; }
-  }
-  ON_DEVICE(ctx);
-  hipStream_t st = (hipStream_t)stream;
-  // staging: the per-sample table {chunk, first row, length, outboard offset, file} (uploaded), then the files' outboard offsets (host only)
-  const uint64_t desc_bytes = (uint64_t)n_samples * 40;
-  const int32_t rc = batch_staging(ctx, desc_bytes + ((uint64_t)n_files + 1) * 8);
-  if (rc) return rc;
-  uint64_t *desc = reinterpret_cast<uint64_t *>(ctx->h_batch), *ob_first = desc + 5 * (uint64_t)n_samples;
-  (void)b3w_bao_batch_layout(host_lens, n_files, ob_first);
-  uint64_t row = 0;
-  for (uint32_t s = 0; s < n_samples; ++s) {
-    const uint32_t f = host_files[s];
-    const uint64_t len = host_lens[f];
-    uint64_t *d = desc + 5 * (uint64_t)s;
-    d[0] = host_chunks[s]; d[1] = row; d[2] = len; d[3] = ob_first[f]; d[4] = f;
-    row += chunk_blocks(len, host_chunks[s]) + b3w_plan_path_len(host_chunks[s], num_chunks(len));
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)desc_bytes, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(b3w_sample_plan_batch_kernel, dim3((n_samples + 63) / 64), dim3(64), 0, st, d_outboards, d_roots,
-                     reinterpret_cast<const uint64_t *>(ctx->d_batch), n_samples, d_chunk_bytes, d_records, d_sample_status);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(ctx, e, "sample plan batch launch");
-  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
-  return B3W_OK;
-}
-
-// ---- group outboards (ABI 1.3) ----------------------------------------------------------------------------------------
-uint64_t b3w_bao_group_outboard_size(uint64_t len, uint32_t group_log) {
-  if (group_log > B3W_BAO_MAX_GROUP_LOG) return 0;
-  const uint64_t G1 = (1ull << group_log) - 1;
-  return 8 + 64 * (((num_chunks(len) + G1) >> group_log) - 1);
-}
-
-uint64_t b3w_bao_group_batch_layout(const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, uint64_t *ob_first) {
-  if (!ob_first || (!host_lens && n_files) || group_log > B3W_BAO_MAX_GROUP_LOG) return 0;
-  uint64_t at = 0;
-  for (uint32_t f = 0; f < n_files; ++f) { ob_first[f] = at; at += b3w_bao_group_outboard_size(host_lens[f], group_log); }
-  ob_first[n_files] = at;
-  return at;
-}
-
-int32_t b3w_bao_group_path_nodes(uint64_t chunk, uint64_t n_chunks, uint32_t group_log, uint64_t *out_index, uint32_t *out_count) {
-  if (group_log > B3W_BAO_MAX_GROUP_LOG || !n_chunks || chunk >= n_chunks) return B3W_E_BAD_ARGUMENT;
-  return b3w_bao_path_nodes(chunk >> group_log, (n_chunks + (1ull << group_log) - 1) >> group_log, out_index, out_count);
-}
-
-int32_t b3w_bao_group_outboard_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, const uint64_t *host_offsets, const uint64_t *host_lens,
-                                            uint32_t n_files, uint32_t group_log, uint8_t *d_outboards, uint32_t *d_roots, void *d_scratch,
-                                            uint64_t scratch_bytes, void *stream) {
-  if (ctx && group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "bao group batch: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
-  return outboard_batch(ctx, d_arena, host_offsets, host_lens, n_files, (int)group_log, d_outboards, d_roots, d_scratch, scratch_bytes, stream);
+  return sample_plan_batch(ctx, "sample plan batch", host_lens, n_files, false, 0, d_outboards, d_roots, host_files, host_chunks, n_samples, d_chunk_bytes, d_records,
+                           d_sample_status, stream, "sample plan batch launch");
 }
 
 int32_t b3w_sample_plan_group_batch_device(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, uint32_t group_log,
                                            const uint8_t *d_group_outboards, const uint32_t *d_roots, const uint32_t *host_files,
                                            const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_group_bytes, uint32_t *d_records,
                                            int32_t *d_sample_status, void *stream) {
+  return sample_plan_batch(ctx, "sample plan group batch", host_lens, n_files, true, group_log, d_group_outboards, d_roots, host_files, host_chunks, n_samples,
+                           d_group_bytes, d_records, d_sample_status, stream, "sample plan group batch launch");
+}
+
+// ---- outboards of a batch of files ---------------------------------------------------------------------------------------------------
+int32_t b3w_bao_outboard_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, const uint64_t *host_offsets, const uint64_t *host_lens,
+                                      uint32_t n_files, uint8_t *d_outboards, uint32_t *d_roots, void *d_scratch, uint64_t scratch_bytes,
+                                      void *stream) {
   if (!ctx) return B3W_E_BAD_ARGUMENT;
-  if (ctx->desc.kind == B3W_KIND_COMP) { ctx->last_error = "sampled paths plan the nova step circuits' records"; return B3W_E_BAD_ARGUMENT; }
-  if (group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "sample plan group batch: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
-  if (!n_samples) return B3W_OK;
-  if (!host_lens || !d_group_outboards || !d_roots || !host_files || !host_chunks || !d_group_bytes || !d_records || !d_sample_status) {
-    ctx->last_error = "sample plan group batch: a null pointer"; return B3W_E_BAD_ARGUMENT;
-  }
-  for (uint32_t s = 0; s < n_samples; ++s) {
-    if (host_files[s] >= n_files) { ctx->last_error = "a sampled file index is not below the file count"; return B3W_E_BAD_ARGUMENT; }
-    if (host_chunks[s] >= num_chunks(host_lens[host_files[s]])) { ctx->last_error = "a sampled chunk index is not below its file's chunk count"; return B3W_E_BAD_ARGUMENT; }
-  }
+  return outboard_batch(ctx, d_arena, host_offsets, host_lens, n_files, false, 0, d_outboards, d_roots, d_scratch, scratch_bytes, stream);
+}
+
+int32_t b3w_bao_group_outboard_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, const uint64_t *host_offsets, const uint64_t *host_lens,
+                                            uint32_t n_files, uint32_t group_log, uint8_t *d_outboards, uint32_t *d_roots, void *d_scratch,
+                                            uint64_t scratch_bytes, void *stream) {
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  B3W_TRY(group_log_ok(ctx, "bao group batch", group_log));
+  return outboard_batch(ctx, d_arena, host_offsets, host_lens, n_files, true, group_log, d_outboards, d_roots, d_scratch, scratch_bytes, stream);
+}
+
+// ---- verification: whole files against their outboards -----------------------------------------------------------------------------------
+int32_t b3w_bao_verify_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, const uint64_t *host_offsets, const uint64_t *host_lens, uint32_t n_files,
+                                    uint32_t group_log, const uint8_t *d_outboards, const uint32_t *d_roots, uint8_t *d_unit_status,
+                                    int32_t *d_file_status, uint64_t *d_first_bad, void *d_scratch, uint64_t scratch_bytes, void *stream) {
+  const char *call = "bao verify";
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  B3W_TRY(group_log_ok(ctx, call, group_log));
+  if (!n_files) return B3W_OK;
+  if (!host_offsets || !host_lens || !d_outboards || !d_roots || !d_unit_status || !d_file_status || !d_first_bad)
+    return refuse(ctx, call, "a null pointer (offsets, lengths, outboards, roots or an output)");
+  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_first_bad & 7) || ((uintptr_t)d_file_status & 3) || ((uintptr_t)d_roots & 3))
+    return refuse(ctx, call, "d_outboards or d_first_bad is not 8-byte aligned, or d_file_status or d_roots not 4-byte aligned");
+  const BatchCounts k = batch_counts(host_lens, n_files);
+  uint64_t tile_ents = 0;
+  const uint64_t n_scr = verify_entries(host_lens, n_files, &tile_ents);
+  B3W_TRY(batch_ok(ctx, call, k, d_arena, host_lens, n_files, d_scratch, scratch_bytes, (n_scr * 36 + 15) & ~15ull,
+                   "the scratch is smaller than b3w_bao_verify_scratch_bytes says"));
   ON_DEVICE(ctx);
   hipStream_t st = (hipStream_t)stream;
-  // staging as b3w_sample_plan_batch_device's: the per-sample table {chunk, first row, length, outboard offset, file}, then the group layout
-  const uint64_t desc_bytes = (uint64_t)n_samples * 40;
-  const int32_t rc = batch_staging(ctx, desc_bytes + ((uint64_t)n_files + 1) * 8);
-  if (rc) return rc;
-  uint64_t *desc = reinterpret_cast<uint64_t *>(ctx->h_batch), *ob_first = desc + 5 * (uint64_t)n_samples;
-  (void)b3w_bao_group_batch_layout(host_lens, n_files, group_log, ob_first);
-  uint64_t row = 0;
-  for (uint32_t s = 0; s < n_samples; ++s) {
-    const uint32_t f = host_files[s];
-    const uint64_t len = host_lens[f];
-    uint64_t *d = desc + 5 * (uint64_t)s;
-    d[0] = host_chunks[s]; d[1] = row; d[2] = len; d[3] = ob_first[f]; d[4] = f;
-    row += chunk_blocks(len, host_chunks[s]) + b3w_plan_path_len(host_chunks[s], num_chunks(len));
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)desc_bytes, hipMemcpyHostToDevice, st));
-  const uint32_t per_wave = 64u >> group_log;
-  hipLaunchKernelGGL(b3w_sample_plan_group_kernel<false>, dim3((n_samples + per_wave - 1) / per_wave), dim3(64), 0, st, d_group_outboards, d_roots,
-                     reinterpret_cast<const uint64_t *>(ctx->d_batch), n_samples, group_log, d_group_bytes, d_records, d_sample_status);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(ctx, e, "sample plan group batch launch");
-  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
-  return B3W_OK;
+  BatchTables d;
+  B3W_TRY(batch_tables(ctx, k, host_offsets, host_lens, n_files, group_log, true, st, &d));
+  uint32_t *exp_cv = reinterpret_cast<uint32_t *>(d_scratch), *bad = exp_cv + n_scr * 8;
+  unsigned long long *fb = reinterpret_cast<unsigned long long *>(d_first_bad);
+  const uint64_t T = B3W_TILE;
+  // top down: the storeys above the tiles first (stored nodes alone), then the kernels that read the files
+  if (k.tops) hipLaunchKernelGGL(b3w_bao_verify_upper_kernel, dim3((uint32_t)k.tops), dim3(256), 0, st, d.tops, (uint32_t)k.tops, T * T, d.files, tile_ents, d_outboards, d_roots, exp_cv, bad, group_log, d_file_status, fb);
+  if (k.merged) hipLaunchKernelGGL(b3w_bao_verify_upper_kernel, dim3((uint32_t)k.groups), dim3(256), 0, st, d.merged, (uint32_t)k.merged, T, d.files, tile_ents, d_outboards, d_roots, exp_cv, bad, group_log, d_file_status, fb);
+  if (k.small) hipLaunchKernelGGL(b3w_bao_verify_small_kernel, dim3((uint32_t)k.waves), dim3(64), 0, st, d_arena, d.small, d.waves, d.files, d_outboards, d_roots, group_log, d_unit_status, d_file_status, fb);
+  if (k.big) hipLaunchKernelGGL(b3w_bao_verify_tile_kernel, dim3((uint32_t)k.big_wgs), dim3(B3W_TILE), 0, st, d_arena, d.big, (uint32_t)k.big, d.files, d_outboards, d_roots, exp_cv, bad, group_log, d_unit_status, d_file_status, fb);
+  return batch_launched(ctx, st, "bao verify launch");
 }
 
-// ---- bao slices (ABI 1.4) ------------------------------------------------------------------------------------------------
-uint64_t b3w_bao_slice_size(uint64_t len, uint64_t chunk) {
-  const uint64_t n = num_chunks(len);
-  if (chunk >= n) return 0;
-  const uint64_t off = chunk * 1024;
-  return 8 + 64ull * path_len(chunk, n) + (len - off < 1024 ? len - off : 1024);
-}
-
-// the next slice start at or behind byte `end`: 8 modulo 16
-static uint64_t slice_start(uint64_t end) { return ((end + 7) & ~15ull) + 8; }
-
-int64_t b3w_bao_slice_batch_layout(const uint64_t *host_lens, uint32_t n_files, const uint32_t *host_files, const uint64_t *host_chunks,
-                                   uint32_t n_samples, uint64_t *slice_first) {
-  if (!slice_first || (n_samples && (!host_lens || !host_files || !host_chunks))) return -B3W_E_BAD_ARGUMENT;
-  for (uint32_t s = 0; s < n_samples; ++s)
-    if (host_files[s] >= n_files || host_chunks[s] >= num_chunks(host_lens[host_files[s]])) return -B3W_E_BAD_ARGUMENT;
-  uint64_t at = slice_start(0);
-  for (uint32_t s = 0; s < n_samples; ++s) {
-    slice_first[s] = at;
-    at = slice_start(at + b3w_bao_slice_size(host_lens[host_files[s]], host_chunks[s]));
-  }
-  slice_first[n_samples] = at;
-  return (int64_t)at;
-}
-
-int32_t b3w_bao_slice_decode(const uint8_t *slice, uint64_t slice_len, uint64_t len, uint64_t chunk, const uint32_t *root, uint8_t *out_chunk,
-                             uint32_t *out_bytes, int32_t *out_status) {
-  const uint64_t n = num_chunks(len);
-  if (!slice || !root || !out_status || chunk >= n || slice_len != b3w_bao_slice_size(len, chunk)) return B3W_E_BAD_ARGUMENT;
-  uint64_t hdr = 0;
-  for (int k = 0; k < 8; ++k) hdr |= (uint64_t)slice[k] << (8 * k);
-  int32_t st = hdr != len ? 3 : 0;
-  uint32_t want[8];
-  for (int k = 0; k < 8; ++k) want[k] = root[k];
-  const uint32_t P = path_len(chunk, n);
-  uint64_t cc = chunk, m = n;
-  for (uint32_t i = 0; i < P; ++i) {                     // top down, as sample_plan_one
-    uint32_t mw[16], ivv[8], o[8];
-    for (int k = 0; k < 16; ++k) {
-      const uint8_t *b = slice + 8 + 64ull * i + 4 * k;
-      mw[k] = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
-    }
-    iv(ivv);
-    blake3_cv(ivv, mw, 0, 0, 64, 4u | (i == 0 ? 8u : 0u), o);
-    if (memcmp(o, want, 32) != 0 && st == 0) st = 2;
-    uint64_t k2 = 1;
-    while (k2 * 2 < m) k2 *= 2;
-    const bool left = cc < k2;
-    for (int k = 0; k < 8; ++k) want[k] = left ? mw[k] : mw[8 + k];
-    if (left) m = k2; else { cc -= k2; m -= k2; }
-  }
-  const uint32_t bytes = (uint32_t)(slice_len - 8 - 64ull * P);
-  uint32_t h[8];
-  host_chunk_cv(slice + 8 + 64ull * P, bytes, chunk, n == 1 ? 8u : 0u, h);
-  if (memcmp(h, want, 32) != 0 && st == 0) st = 1;
-  *out_status = st;
-  if (out_bytes) *out_bytes = st == 0 ? bytes : 0;       // (the bytes are handed out only where they verified, as bao's decoder does)
-  if (out_chunk && st == 0 && bytes) memcpy(out_chunk, slice + 8 + 64ull * P, bytes);
-  return B3W_OK;
-}
-
-// the checks the two device calls share; the sample table's staging: desc (40 bytes a sample, uploaded), then n_files + 1 host-only words
-static int32_t slice_samples_ok(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, const uint32_t *host_files, const uint64_t *host_chunks,
-                                uint32_t n_samples) {
-  for (uint32_t s = 0; s < n_samples; ++s) {
-    if (host_files[s] >= n_files) { ctx->last_error = "a sampled file index is not below the file count"; return B3W_E_BAD_ARGUMENT; }
-    if (host_chunks[s] >= num_chunks(host_lens[host_files[s]])) { ctx->last_error = "a sampled chunk index is not below its file's chunk count"; return B3W_E_BAD_ARGUMENT; }
-  }
-  return B3W_OK;
-}
-
+// ---- bao slices, and challenged paths planned from them alone ------------------------------------------------------------------------------
 int32_t b3w_bao_slice_batch_device(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint8_t *d_outboards,
                                    const uint32_t *host_files, const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_bytes,
                                    uint8_t *d_slices, void *stream) {
+  const char *call = "bao slice batch";
   if (!ctx) return B3W_E_BAD_ARGUMENT;
-  if (group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "bao slice batch: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
+  B3W_TRY(group_log_ok(ctx, call, group_log));
   if (!n_samples) return B3W_OK;
-  if (!host_lens || !d_outboards || !host_files || !host_chunks || !d_bytes || !d_slices) { ctx->last_error = "bao slice batch: a null pointer"; return B3W_E_BAD_ARGUMENT; }
-  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) { ctx->last_error = "bao slice batch: d_outboards is not 8-byte or d_slices not 16-byte aligned"; return B3W_E_BAD_ARGUMENT; }
-  int32_t rc = slice_samples_ok(ctx, host_lens, n_files, host_files, host_chunks, n_samples);
-  if (rc) return rc;
+  if (!host_lens || !d_outboards || !host_files || !host_chunks || !d_bytes || !d_slices) return refuse(ctx, call, "a null pointer");
+  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) return refuse(ctx, call, "d_outboards is not 8-byte or d_slices not 16-byte aligned");
+  B3W_TRY(samples_ok(ctx, host_lens, n_files, host_files, host_chunks, n_samples));
   ON_DEVICE(ctx);
   hipStream_t st = (hipStream_t)stream;
-  const uint64_t desc_bytes = (uint64_t)n_samples * 40;
-  rc = batch_staging(ctx, desc_bytes + ((uint64_t)n_files + 1) * 8);
-  if (rc) return rc;
-  uint64_t *desc = reinterpret_cast<uint64_t *>(ctx->h_batch), *ob_first = desc + 5 * (uint64_t)n_samples;
-  (void)b3w_bao_group_batch_layout(host_lens, n_files, group_log, ob_first);        // (group_log 0: b3w_bao_batch_layout's)
-  uint64_t at = slice_start(0);
-  for (uint32_t s = 0; s < n_samples; ++s) {
-    const uint32_t f = host_files[s];
-    uint64_t *d = desc + 5 * (uint64_t)s;
-    d[0] = host_chunks[s]; d[1] = at; d[2] = host_lens[f]; d[3] = ob_first[f]; d[4] = f;
-    at = slice_start(at + b3w_bao_slice_size(host_lens[f], host_chunks[s]));
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)desc_bytes, hipMemcpyHostToDevice, st));
-  const uint64_t *d_desc = reinterpret_cast<const uint64_t *>(ctx->d_batch);
-  if (group_log == 0) {
-    const uint32_t per_wg = 256 / SLICE_LANES;
-    hipLaunchKernelGGL(b3w_bao_slice_kernel<false>, dim3((n_samples + per_wg - 1) / per_wg), dim3(256), 0, st, d_outboards, d_desc, n_samples, d_bytes, d_slices);
-  } else {
-    const uint32_t per_wave = 64u >> group_log;
-    hipLaunchKernelGGL(b3w_bao_slice_group_kernel<false>, dim3((n_samples + per_wave - 1) / per_wave), dim3(64), 0, st, d_outboards, d_desc, n_samples, group_log,
-                       d_bytes, d_slices);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(ctx, e, "bao slice batch launch");
-  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
-  return B3W_OK;
+  const uint64_t *d_desc = nullptr;
+  B3W_TRY(sample_table<5, true, false, false>(ctx, nullptr, host_lens, n_files, group_log, host_files, host_chunks, n_samples, st, &d_desc));
+  launch_slices<false>(group_log, n_samples, st, d_outboards, d_desc, d_bytes, d_slices);
+  return batch_launched(ctx, st, "bao slice batch launch");
 }
 
 int32_t b3w_sample_plan_slices_device(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, const uint32_t *d_roots, const uint32_t *host_files,
                                       const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_slices, uint32_t *d_records,
                                       int32_t *d_sample_status, void *stream) {
+  const char *call = "sample plan slices";
   if (!ctx) return B3W_E_BAD_ARGUMENT;
-  if (ctx->desc.kind == B3W_KIND_COMP) { ctx->last_error = "sampled paths plan the nova step circuits' records"; return B3W_E_BAD_ARGUMENT; }
+  B3W_TRY(nova_ok(ctx));
   if (!n_samples) return B3W_OK;
-  if (!host_lens || !d_roots || !host_files || !host_chunks || !d_slices || !d_records || !d_sample_status) {
-    ctx->last_error = "sample plan slices: a null pointer"; return B3W_E_BAD_ARGUMENT;
-  }
-  if ((uintptr_t)d_slices & 15) { ctx->last_error = "sample plan slices: d_slices is not 16-byte aligned"; return B3W_E_BAD_ARGUMENT; }
-  int32_t rc = slice_samples_ok(ctx, host_lens, n_files, host_files, host_chunks, n_samples);
-  if (rc) return rc;
+  if (!host_lens || !d_roots || !host_files || !host_chunks || !d_slices || !d_records || !d_sample_status) return refuse(ctx, call, "a null pointer");
+  if ((uintptr_t)d_slices & 15) return refuse(ctx, call, "d_slices is not 16-byte aligned");
+  B3W_TRY(samples_ok(ctx, host_lens, n_files, host_files, host_chunks, n_samples));
   ON_DEVICE(ctx);
   hipStream_t st = (hipStream_t)stream;
-  const uint64_t desc_bytes = (uint64_t)n_samples * 40;
-  rc = batch_staging(ctx, desc_bytes);
-  if (rc) return rc;
-  uint64_t *desc = reinterpret_cast<uint64_t *>(ctx->h_batch);
-  uint64_t row = 0, at = slice_start(0);
-  for (uint32_t s = 0; s < n_samples; ++s) {
-    const uint32_t f = host_files[s];
-    const uint64_t len = host_lens[f];
-    uint64_t *d = desc + 5 * (uint64_t)s;
-    d[0] = host_chunks[s]; d[1] = row; d[2] = len; d[3] = at; d[4] = f;
-    row += chunk_blocks(len, host_chunks[s]) + b3w_plan_path_len(host_chunks[s], num_chunks(len));
-    at = slice_start(at + b3w_bao_slice_size(len, host_chunks[s]));
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)desc_bytes, hipMemcpyHostToDevice, st));
+  const uint64_t *d_desc = nullptr;
+  B3W_TRY(sample_table<5, false, true, false>(ctx, nullptr, host_lens, n_files, 0, host_files, host_chunks, n_samples, st, &d_desc));
   // lanes a sample: 16; B3W_SLICE_PLAN_LANES=1 / 4 and B3W_SLICE_PLAN_CHAIN=1 (the running-h chain for every sample): measurements
   const char *env = getenv("B3W_SLICE_PLAN_LANES"), *env_chain = getenv("B3W_SLICE_PLAN_CHAIN");
-  const int lanes = env ? atoi(env) : 16;
   const uint32_t chain = env_chain && atoi(env_chain) != 0;
-  const uint64_t *d_desc = reinterpret_cast<const uint64_t *>(ctx->d_batch);
-  if (lanes == 1)
-    hipLaunchKernelGGL(b3w_sample_plan_slices_kernel<1>, dim3((n_samples + 63) / 64), dim3(64), 0, st, d_slices, d_roots, d_desc, n_samples, chain, d_records, d_sample_status);
-  else if (lanes == 4)
-    hipLaunchKernelGGL(b3w_sample_plan_slices_kernel<4>, dim3((n_samples + 15) / 16), dim3(64), 0, st, d_slices, d_roots, d_desc, n_samples, chain, d_records, d_sample_status);
-  else
-    hipLaunchKernelGGL(b3w_sample_plan_slices_kernel<16>, dim3((n_samples + 3) / 4), dim3(64), 0, st, d_slices, d_roots, d_desc, n_samples, chain, d_records, d_sample_status);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(ctx, e, "sample plan slices launch");
-  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
-  return B3W_OK;
+  with_lanes(env ? atoi(env) : 16, [&](auto K) {
+    constexpr int LANES = decltype(K)::value;
+    hipLaunchKernelGGL(b3w_sample_plan_slices_kernel<LANES>, lanes_grid<LANES>(n_samples), dim3(64), 0, st, d_slices, d_roots, d_desc, n_samples, chain, d_records, d_sample_status);
+  });
+  return batch_launched(ctx, st, "sample plan slices launch");
 }
 
-// ---- challenged paths and slices read in place from the arena (still ABI 1.4: new names only) -------------------------------
-// the checks the two arena calls share: the samples' indices, and every sampled file inside [0, arena_bytes)
-static int32_t arena_samples_ok(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
-                                uint32_t n_files, const uint32_t *host_files, const uint64_t *host_chunks, uint32_t n_samples) {
-  const int32_t rc = slice_samples_ok(ctx, host_lens, n_files, host_files, host_chunks, n_samples);
-  if (rc) return rc;
-  for (uint32_t s = 0; s < n_samples; ++s) {
-    const uint64_t off = host_offsets[host_files[s]], len = host_lens[host_files[s]];
-    if (len && !d_arena) { ctx->last_error = "a null arena with a sampled file that is not empty"; return B3W_E_BAD_ARGUMENT; }
-    if (off > arena_bytes || len > arena_bytes - off) { ctx->last_error = "a sampled file reaches past arena_bytes"; return B3W_E_BAD_ARGUMENT; }
-  }
-  return B3W_OK;
-}
-
-// the arena calls' sample table into the staging: {chunk, first row or slice offset, length, outboard offset, file, the file's arena offset}
-static int32_t arena_table(b3w_ctx *ctx, const uint64_t *host_offsets, const uint64_t *host_lens, uint32_t n_files, uint32_t group_log,
-                           const uint32_t *host_files, const uint64_t *host_chunks, uint32_t n_samples, bool slices, hipStream_t st) {
-  const uint64_t desc_bytes = (uint64_t)n_samples * 48;
-  const int32_t rc = batch_staging(ctx, desc_bytes + ((uint64_t)n_files + 1) * 8);
-  if (rc) return rc;
-  uint64_t *desc = reinterpret_cast<uint64_t *>(ctx->h_batch), *ob_first = desc + 6 * (uint64_t)n_samples;
-  (void)b3w_bao_group_batch_layout(host_lens, n_files, group_log, ob_first);        // (group_log 0: b3w_bao_batch_layout's)
-  uint64_t row = 0, at = slice_start(0);
-  for (uint32_t s = 0; s < n_samples; ++s) {
-    const uint32_t f = host_files[s];
-    const uint64_t len = host_lens[f];
-    uint64_t *d = desc + 6 * (uint64_t)s;
-    d[0] = host_chunks[s]; d[1] = slices ? at : row; d[2] = len; d[3] = ob_first[f]; d[4] = f; d[5] = host_offsets[f];
-    row += chunk_blocks(len, host_chunks[s]) + b3w_plan_path_len(host_chunks[s], num_chunks(len));
-    at = slice_start(at + b3w_bao_slice_size(len, host_chunks[s]));
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)desc_bytes, hipMemcpyHostToDevice, st));
-  return B3W_OK;
-}
-
+// ---- challenged paths and slices read in place from the arena --------------------------------------------------------------------------------
 int32_t b3w_sample_plan_arena_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
                                      uint32_t n_files, uint32_t group_log, const uint8_t *d_outboards, const uint32_t *d_roots,
                                      const uint32_t *host_files, const uint64_t *host_chunks, uint32_t n_samples, uint32_t *d_records,
                                      int32_t *d_sample_status, void *stream) {
+  const char *call = "sample plan arena";
   if (!ctx) return B3W_E_BAD_ARGUMENT;
-  if (ctx->desc.kind == B3W_KIND_COMP) { ctx->last_error = "sampled paths plan the nova step circuits' records"; return B3W_E_BAD_ARGUMENT; }
-  if (group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "sample plan arena: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
+  B3W_TRY(nova_ok(ctx));
+  B3W_TRY(group_log_ok(ctx, call, group_log));
   if (!n_samples) return B3W_OK;
-  if (!host_offsets || !host_lens || !d_outboards || !d_roots || !host_files || !host_chunks || !d_records || !d_sample_status) {
-    ctx->last_error = "sample plan arena: a null pointer"; return B3W_E_BAD_ARGUMENT;
-  }
-  if ((uintptr_t)d_outboards & 7) { ctx->last_error = "sample plan arena: d_outboards is not 8-byte aligned"; return B3W_E_BAD_ARGUMENT; }
-  int32_t rc = arena_samples_ok(ctx, d_arena, arena_bytes, host_offsets, host_lens, n_files, host_files, host_chunks, n_samples);
-  if (rc) return rc;
+  if (!host_offsets || !host_lens || !d_outboards || !d_roots || !host_files || !host_chunks || !d_records || !d_sample_status) return refuse(ctx, call, "a null pointer");
+  if ((uintptr_t)d_outboards & 7) return refuse(ctx, call, "d_outboards is not 8-byte aligned");
+  B3W_TRY(arena_samples_ok(ctx, d_arena, arena_bytes, host_offsets, host_lens, n_files, host_files, host_chunks, n_samples));
   ON_DEVICE(ctx);
   hipStream_t st = (hipStream_t)stream;
-  rc = arena_table(ctx, host_offsets, host_lens, n_files, group_log, host_files, host_chunks, n_samples, false, st);
-  if (rc) return rc;
-  const uint64_t *d_desc = reinterpret_cast<const uint64_t *>(ctx->d_batch);
-  if (group_log == 0) {
-    hipLaunchKernelGGL(b3w_sample_plan_arena_kernel, dim3((n_samples + 63) / 64), dim3(64), 0, st, d_outboards, d_roots, d_desc, n_samples, d_arena, d_records,
-                       d_sample_status);
-  } else {
-    const uint32_t per_wave = 64u >> group_log;
-    hipLaunchKernelGGL(b3w_sample_plan_group_kernel<true>, dim3((n_samples + per_wave - 1) / per_wave), dim3(64), 0, st, d_outboards, d_roots, d_desc,
-                       n_samples, group_log, d_arena, d_records, d_sample_status);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(ctx, e, "sample plan arena launch");
-  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
-  return B3W_OK;
+  const uint64_t *d_desc = nullptr;
+  B3W_TRY(sample_table<6, false, false, false>(ctx, host_offsets, host_lens, n_files, group_log, host_files, host_chunks, n_samples, st, &d_desc));
+  const uint32_t per_wave = 64u >> group_log;
+  if (group_log == 0) hipLaunchKernelGGL(b3w_sample_plan_arena_kernel, dim3((n_samples + 63) / 64), dim3(64), 0, st, d_outboards, d_roots, d_desc, n_samples, d_arena, d_records, d_sample_status);
+  else hipLaunchKernelGGL(b3w_sample_plan_group_kernel<true>, dim3((n_samples + per_wave - 1) / per_wave), dim3(64), 0, st, d_outboards, d_roots, d_desc, n_samples, group_log, d_arena, d_records, d_sample_status);
+  return batch_launched(ctx, st, "sample plan arena launch");
 }
 
 int32_t b3w_bao_slice_arena_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
                                    uint32_t n_files, uint32_t group_log, const uint8_t *d_outboards, const uint32_t *host_files,
                                    const uint64_t *host_chunks, uint32_t n_samples, uint8_t *d_slices, void *stream) {
+  const char *call = "bao slice arena";
   if (!ctx) return B3W_E_BAD_ARGUMENT;
-  if (group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "bao slice arena: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
+  B3W_TRY(group_log_ok(ctx, call, group_log));
   if (!n_samples) return B3W_OK;
-  if (!host_offsets || !host_lens || !d_outboards || !host_files || !host_chunks || !d_slices) { ctx->last_error = "bao slice arena: a null pointer"; return B3W_E_BAD_ARGUMENT; }
-  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) { ctx->last_error = "bao slice arena: d_outboards is not 8-byte or d_slices not 16-byte aligned"; return B3W_E_BAD_ARGUMENT; }
-  int32_t rc = arena_samples_ok(ctx, d_arena, arena_bytes, host_offsets, host_lens, n_files, host_files, host_chunks, n_samples);
-  if (rc) return rc;
+  if (!host_offsets || !host_lens || !d_outboards || !host_files || !host_chunks || !d_slices) return refuse(ctx, call, "a null pointer");
+  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) return refuse(ctx, call, "d_outboards is not 8-byte or d_slices not 16-byte aligned");
+  B3W_TRY(arena_samples_ok(ctx, d_arena, arena_bytes, host_offsets, host_lens, n_files, host_files, host_chunks, n_samples));
   ON_DEVICE(ctx);
   hipStream_t st = (hipStream_t)stream;
-  rc = arena_table(ctx, host_offsets, host_lens, n_files, group_log, host_files, host_chunks, n_samples, true, st);
-  if (rc) return rc;
-  const uint64_t *d_desc = reinterpret_cast<const uint64_t *>(ctx->d_batch);
-  if (group_log == 0) {
-    const uint32_t per_wg = 256 / SLICE_LANES;
-    hipLaunchKernelGGL(b3w_bao_slice_kernel<true>, dim3((n_samples + per_wg - 1) / per_wg), dim3(256), 0, st, d_outboards, d_desc, n_samples, d_arena, d_slices);
-  } else {
-    const uint32_t per_wave = 64u >> group_log;
-    hipLaunchKernelGGL(b3w_bao_slice_group_kernel<true>, dim3((n_samples + per_wave - 1) / per_wave), dim3(64), 0, st, d_outboards, d_desc, n_samples, group_log,
-                       d_arena, d_slices);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(ctx, e, "bao slice arena launch");
-  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
-  return B3W_OK;
+  const uint64_t *d_desc = nullptr;
+  B3W_TRY(sample_table<6, true, false, false>(ctx, host_offsets, host_lens, n_files, group_log, host_files, host_chunks, n_samples, st, &d_desc));
+  launch_slices<true>(group_log, n_samples, st, d_outboards, d_desc, d_arena, d_slices);
+  return batch_launched(ctx, st, "bao slice arena launch");
 }
 
-// ---- slices taken in (still ABI 1.4: new names only) ------------------------------------------------------------------------
-int32_t b3w_bao_slice_ingest(const uint8_t *slice, uint64_t slice_len, uint64_t len, uint64_t chunk, const uint32_t *root, uint32_t group_log,
-                             uint8_t *data, uint8_t *outboard, int32_t *out_status) {
-  if (group_log > B3W_BAO_MAX_GROUP_LOG || !outboard || (!data && len)) return B3W_E_BAD_ARGUMENT;
-  int32_t st = 0;
-  const int32_t rc = b3w_bao_slice_decode(slice, slice_len, len, chunk, root, nullptr, nullptr, out_status ? &st : nullptr);   // (refuses the rest)
-  if (rc) return rc;
-  *out_status = st;
-  if (st) return B3W_OK;                                  // nothing unverified is written
-  const uint64_t n = num_chunks(len);
-  uint64_t idx[64];
-  uint32_t U = 0;
-  (void)b3w_bao_group_path_nodes(chunk, n, group_log, idx, &U);
-  memcpy(outboard, slice, 8);
-  for (uint32_t i = 0; i < U; ++i) memcpy(outboard + 8 + 64 * idx[i], slice + 8 + 64ull * i, 64);   // (the path's first U nodes are the stored ones)
-  const uint64_t bytes = slice_len - 8 - 64ull * path_len(chunk, n);
-  if (bytes) memcpy(data + chunk * 1024, slice + slice_len - bytes, bytes);
-  return B3W_OK;
-}
-
-}  // extern "C"
-
-namespace {
-// b3w_bao_slice_ingest_device (HAVE false: d_have is not looked at) and b3w_bao_slice_ingest_have_device
-template <bool HAVE>
-int32_t slice_ingest(b3w_ctx *ctx, uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
-                     uint32_t n_files, uint32_t group_log, uint8_t *d_outboards, const uint32_t *d_roots, const uint32_t *host_files,
-                     const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_slices, int32_t *d_sample_status, uint64_t *d_have, void *stream) {
-  if (!ctx) return B3W_E_BAD_ARGUMENT;
-  if (group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "bao slice ingest: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
-  if (HAVE && (!d_have || ((uintptr_t)d_have & 7))) { ctx->last_error = "bao slice ingest: d_have is null or not 8-byte aligned"; return B3W_E_BAD_ARGUMENT; }
-  if (!n_samples) return B3W_OK;
-  if (!host_offsets || !host_lens || !d_outboards || !d_roots || !host_files || !host_chunks || !d_slices || !d_sample_status) {
-    ctx->last_error = "bao slice ingest: a null pointer"; return B3W_E_BAD_ARGUMENT;
-  }
-  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) { ctx->last_error = "bao slice ingest: d_outboards is not 8-byte or d_slices not 16-byte aligned"; return B3W_E_BAD_ARGUMENT; }
-  int32_t rc = arena_samples_ok(ctx, d_arena, arena_bytes, host_offsets, host_lens, n_files, host_files, host_chunks, n_samples);
-  if (rc) return rc;
-  ON_DEVICE(ctx);
-  hipStream_t st = (hipStream_t)stream;
-  // the arena calls' row (arena_table with slice offsets), filled here: the call is host work a sample before it is anything else, so the
-  // path's length is walked once a sample, with the split from a bit scan, and serves the slice's size and the batch's longest path
-  const uint64_t desc_bytes = (uint64_t)n_samples * 48;
-  rc = batch_staging(ctx, desc_bytes + ((uint64_t)n_files + 1) * 8);
-  if (rc) return rc;
-  uint64_t *desc = reinterpret_cast<uint64_t *>(ctx->h_batch), *ob_first = desc + 6 * (uint64_t)n_samples;
-  (void)b3w_bao_group_batch_layout(host_lens, n_files, group_log, ob_first);        // (group_log 0: b3w_bao_batch_layout's)
-  uint64_t at = slice_start(0);
-  uint32_t longest = 0;
-  for (uint32_t s = 0; s < n_samples; ++s) {
-    const uint32_t f = host_files[s];
-    const uint64_t len = host_lens[f], c = host_chunks[s], off = c * 1024;
-    uint32_t P = 0;
-    for (uint64_t cc = c, m = num_chunks(len); m > 1; ++P) {                        // path_len's walk
-      const uint64_t k2 = 1ull << (63 - __builtin_clzll(m - 1));                    // the largest power of two strictly below m
-      if (cc < k2) m = k2; else { cc -= k2; m -= k2; }
-    }
-    uint64_t *d = desc + 6 * (uint64_t)s;
-    d[0] = c; d[1] = at; d[2] = len; d[3] = ob_first[f]; d[4] = f; d[5] = host_offsets[f];
-    at = slice_start(at + 8 + 64ull * P + (len - off < 1024 ? len - off : 1024));   // (b3w_bao_slice_size)
-    if (P > longest) longest = P;
-  }
-  if (HAVE) (void)b3w_bao_have_layout(host_lens, n_files, ob_first);                // (the outboard offsets are in the rows by now)
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)(desc_bytes + (HAVE ? ((uint64_t)n_files + 1) * 8 : 0)), hipMemcpyHostToDevice, st));
-  // lanes a sample, from the batch's longest path P: node j is checked by lane j mod K, ceil(P / K) rounds beside the chunk's sixteen blocks,
-  // and every lane fewer a sample is a leader more a wave in the stretch only leaders run.  Measured at P = 20 (DESIGN.md 8g): four lanes
-  // (five rounds) beat sixteen (two) at 4 096 and at 65 536 slices, so four up to six rounds; sixteen for the longer paths (files past
-  // 16 GiB; not measured).  B3W_SLICE_INGEST_LANES=1 / 4 / 16: measurements
-  const char *env = getenv("B3W_SLICE_INGEST_LANES");
-  const int lanes = env ? atoi(env) : (longest <= 24 ? 4 : 16);
-  const uint64_t *d_desc = reinterpret_cast<const uint64_t *>(ctx->d_batch);
-  unsigned long long *have = HAVE ? reinterpret_cast<unsigned long long *>(d_have) : nullptr;
-  if (lanes == 1)
-    hipLaunchKernelGGL((b3w_bao_slice_ingest_kernel<1, HAVE>), dim3((n_samples + 63) / 64), dim3(64), 0, st, d_slices, d_roots, d_desc, n_samples, group_log, d_arena,
-                       d_outboards, d_sample_status, have);
-  else if (lanes == 4)
-    hipLaunchKernelGGL((b3w_bao_slice_ingest_kernel<4, HAVE>), dim3((n_samples + 15) / 16), dim3(64), 0, st, d_slices, d_roots, d_desc, n_samples, group_log, d_arena,
-                       d_outboards, d_sample_status, have);
-  else
-    hipLaunchKernelGGL((b3w_bao_slice_ingest_kernel<16, HAVE>), dim3((n_samples + 3) / 4), dim3(64), 0, st, d_slices, d_roots, d_desc, n_samples, group_log, d_arena,
-                       d_outboards, d_sample_status, have);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(ctx, e, "bao slice ingest launch");
-  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
-  return B3W_OK;
-}
-}  // namespace
-
-// b3w_bao_have.hip's way to the staging of the batch calls
-int32_t b3w_int_batch_staging(b3w_ctx *ctx, uint64_t bytes) { return batch_staging(ctx, bytes); }
-
-extern "C" {
-
+// ---- slices taken in --------------------------------------------------------------------------------------------------------------------
 int32_t b3w_bao_slice_ingest_device(b3w_ctx *ctx, uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
                                     uint32_t n_files, uint32_t group_log, uint8_t *d_outboards, const uint32_t *d_roots, const uint32_t *host_files,
                                     const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_slices, int32_t *d_sample_status, void *stream) {
@@ -2799,162 +2581,6 @@ int32_t b3w_bao_slice_ingest_have_device(b3w_ctx *ctx, uint8_t *d_arena, uint64_
                                          uint64_t *d_have, void *stream) {
   return slice_ingest<true>(ctx, d_arena, arena_bytes, host_offsets, host_lens, n_files, group_log, d_outboards, d_roots, host_files, host_chunks, n_samples,
                             d_slices, d_sample_status, d_have, stream);
-}
-
-// ---- verification: whole files against their outboards ---------------------------------------------------------------------
-uint64_t b3w_bao_verify_layout(const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, uint64_t *unit_first) {
-  if (!unit_first || (!host_lens && n_files) || group_log > B3W_BAO_MAX_GROUP_LOG) return 0;
-  const uint64_t G1 = (1ull << group_log) - 1;
-  uint64_t at = 0;
-  for (uint32_t f = 0; f < n_files; ++f) { unit_first[f] = at; at += (num_chunks(host_lens[f]) + G1) >> group_log; }
-  unit_first[n_files] = at;
-  return at;
-}
-
-// scratch entries: one per tile of the files of more than one tile, one per group of 1 024 tiles of the files of more than one group
-static uint64_t verify_entries(const uint64_t *lens, uint32_t n_files, uint64_t *tile_ents) {
-  uint64_t tiles_sum = 0, groups_sum = 0;
-  for (uint32_t f = 0; f < n_files; ++f) {
-    const uint64_t tiles = (num_chunks(lens[f]) + B3W_TILE - 1) / B3W_TILE, groups = (tiles + B3W_TILE - 1) / B3W_TILE;
-    if (tiles > 1) tiles_sum += tiles;
-    if (groups > 1) groups_sum += groups;
-  }
-  if (tile_ents) *tile_ents = tiles_sum;
-  return tiles_sum + groups_sum;
-}
-
-uint64_t b3w_bao_verify_scratch_bytes(const uint64_t *host_lens, uint32_t n_files) {
-  if (!host_lens) return 0;
-  return (verify_entries(host_lens, n_files, nullptr) * 36 + 15) & ~15ull;           // the expected CV (32) and the flag (4) of every entry
-}
-
-int32_t b3w_bao_verify_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, const uint64_t *host_offsets, const uint64_t *host_lens, uint32_t n_files,
-                                    uint32_t group_log, const uint8_t *d_outboards, const uint32_t *d_roots, uint8_t *d_unit_status,
-                                    int32_t *d_file_status, uint64_t *d_first_bad, void *d_scratch, uint64_t scratch_bytes, void *stream) {
-  if (!ctx) return B3W_E_BAD_ARGUMENT;
-  if (group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "bao verify: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
-  if (!n_files) return B3W_OK;
-  if (!host_offsets || !host_lens || !d_outboards || !d_roots || !d_unit_status || !d_file_status || !d_first_bad) {
-    ctx->last_error = "bao verify: a null pointer (offsets, lengths, outboards, roots or an output)"; return B3W_E_BAD_ARGUMENT;
-  }
-  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_first_bad & 7) || ((uintptr_t)d_file_status & 3) || ((uintptr_t)d_roots & 3)) {
-    ctx->last_error = "bao verify: d_outboards or d_first_bad is not 8-byte aligned, or d_file_status or d_roots not 4-byte aligned"; return B3W_E_BAD_ARGUMENT;
-  }
-  const BatchCounts k = batch_counts(host_lens, n_files);
-  if (k.too_long || k.big_wgs > 0x7fffffffull) { ctx->last_error = "bao verify: a file of more than 2^30 chunks, or more than 2^31 tiles"; return B3W_E_BAD_ARGUMENT; }
-  uint64_t tile_ents = 0;
-  const uint64_t n_scr = verify_entries(host_lens, n_files, &tile_ents), need = (n_scr * 36 + 15) & ~15ull;
-  if (scratch_bytes < need) { ctx->last_error = "bao verify: the scratch is smaller than b3w_bao_verify_scratch_bytes says"; return B3W_E_BAD_ARGUMENT; }
-  if (need && (!d_scratch || ((uintptr_t)d_scratch & 15))) { ctx->last_error = "bao verify: the scratch is null or not 16-byte aligned"; return B3W_E_BAD_ARGUMENT; }
-  if (!d_arena)
-    for (uint32_t f = 0; f < n_files; ++f)
-      if (host_lens[f]) { ctx->last_error = "bao verify: a null arena with a file that is not empty"; return B3W_E_BAD_ARGUMENT; }
-  ON_DEVICE(ctx);
-  hipStream_t st = (hipStream_t)stream;
-  // the tables of the outboard call, then one VerFile per file: small | big | merged | tops | files | the small waves' first files
-  const uint64_t n_ents = k.small + k.big + k.merged + k.tops;
-  const uint64_t table_bytes = n_ents * sizeof(BatchEnt) + (uint64_t)n_files * sizeof(VerFile) + (k.small ? (k.waves + 1) * 4 : 0);
-  const int32_t rc = batch_staging(ctx, table_bytes);
-  if (rc) return rc;
-  BatchEnt *h_small = reinterpret_cast<BatchEnt *>(ctx->h_batch), *h_big = h_small + k.small, *h_merged = h_big + k.big, *h_tops = h_merged + k.merged;
-  VerFile *h_files = reinterpret_cast<VerFile *>(h_tops + k.tops);
-  uint32_t *h_waves = reinterpret_cast<uint32_t *>(h_files + n_files);
-  uint32_t i_small = 0, i_waves = 0, fill = 64, i_big = 0, i_merged = 0, i_tops = 0, big_wgs = 0, groups = 0;
-  uint64_t ob = 0, units = 0, slot = 0, gslot = 0;
-  for (uint32_t f = 0; f < n_files; ++f) {
-    const uint64_t len = host_lens[f], n = num_chunks(len), n_units = (n + ((1ull << group_log) - 1)) >> group_log;
-    h_files[f] = VerFile{units, slot, gslot};
-    if (n <= 64) {
-      if (fill + n > 64) { h_waves[i_waves++] = i_small; fill = 0; }
-      h_small[i_small] = BatchEnt{host_offsets[f], len, ob, fill, f};
-      fill += (uint32_t)n;
-      i_small++;
-    } else {
-      const uint32_t tiles = (uint32_t)((n + B3W_TILE - 1) / B3W_TILE), grp = (tiles + B3W_TILE - 1) / B3W_TILE;
-      h_big[i_big++] = BatchEnt{host_offsets[f], len, ob, big_wgs, f};
-      if (tiles > 1) { h_merged[i_merged++] = BatchEnt{0, len, ob, groups, f}; slot += tiles; groups += grp; }
-      if (grp > 1) { h_tops[i_tops] = BatchEnt{0, len, ob, i_tops, f}; i_tops++; gslot += grp; }
-      big_wgs += tiles;
-    }
-    ob += 8 + 64 * (n_units - 1);                                      // (b3w_bao_group_outboard_size)
-    units += n_units;
-  }
-  if (k.small) h_waves[i_waves] = i_small;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)table_bytes, hipMemcpyHostToDevice, st));
-  const BatchEnt *d_small = reinterpret_cast<const BatchEnt *>(ctx->d_batch), *d_big = d_small + k.small, *d_merged = d_big + k.big, *d_tops = d_merged + k.merged;
-  const VerFile *d_files = reinterpret_cast<const VerFile *>(d_tops + k.tops);
-  const uint32_t *d_waves = reinterpret_cast<const uint32_t *>(d_files + n_files);
-  uint32_t *exp_cv = reinterpret_cast<uint32_t *>(d_scratch), *bad = exp_cv + n_scr * 8;
-  unsigned long long *fb = reinterpret_cast<unsigned long long *>(d_first_bad);
-  // top down: the storeys above the tiles first (stored nodes alone), then the kernels that read the files
-  if (k.tops) hipLaunchKernelGGL(b3w_bao_verify_upper_kernel, dim3((uint32_t)k.tops), dim3(256), 0, st, d_tops, (uint32_t)k.tops, (uint64_t)B3W_TILE * B3W_TILE, d_files, tile_ents, d_outboards, d_roots, exp_cv, bad, group_log, d_file_status, fb);
-  if (k.merged) hipLaunchKernelGGL(b3w_bao_verify_upper_kernel, dim3((uint32_t)k.groups), dim3(256), 0, st, d_merged, (uint32_t)k.merged, (uint64_t)B3W_TILE, d_files, tile_ents, d_outboards, d_roots, exp_cv, bad, group_log, d_file_status, fb);
-  if (k.small) hipLaunchKernelGGL(b3w_bao_verify_small_kernel, dim3((uint32_t)k.waves), dim3(64), 0, st, d_arena, d_small, d_waves, d_files, d_outboards, d_roots, group_log, d_unit_status, d_file_status, fb);
-  if (k.big) hipLaunchKernelGGL(b3w_bao_verify_tile_kernel, dim3((uint32_t)k.big_wgs), dim3(B3W_TILE), 0, st, d_arena, d_big, (uint32_t)k.big, d_files, d_outboards, d_roots, exp_cv, bad, group_log, d_unit_status, d_file_status, fb);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(ctx, e, "bao verify launch");
-  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
-  return B3W_OK;
-}
-
-// one unit's CV on the host: BLAKE3's tree over the chunks [first, first + cnt) of the file (root: the unit is the whole file)
-static void host_subtree_cv(const uint8_t *data, uint64_t len, uint64_t first, uint64_t cnt, bool root, uint32_t h[8]) {
-  if (cnt == 1) {
-    const uint64_t off = first * 1024;
-    host_chunk_cv(data + off, (uint32_t)(len - off < 1024 ? len - off : 1024), first, root ? 8u : 0u, h);
-    return;
-  }
-  uint64_t k2 = 1;
-  while (k2 * 2 < cnt) k2 *= 2;
-  uint32_t m[16], ivv[8];
-  host_subtree_cv(data, len, first, k2, false, m);
-  host_subtree_cv(data, len, first + k2, cnt - k2, false, m + 8);
-  iv(ivv);
-  blake3_cv(ivv, m, 0, 0, 64, 4u | (root ? 8u : 0u), h);
-}
-
-// bao's decoder top down over the units [first, first + cnt) whose stored node (cnt > 1) is node `pos`: `want` is what the stored data
-// above expects here, `bad` whether a node above failed
-static void host_verify_walk(const uint8_t *data, uint64_t len, uint64_t n, uint32_t gl, const uint8_t *nodes, uint64_t first, uint64_t cnt, uint64_t pos,
-                             const uint32_t want[8], bool bad, bool root, uint8_t *status) {
-  if (cnt == 1) {
-    const uint64_t c0 = first << gl, gn = n - c0 < (1ull << gl) ? n - c0 : (1ull << gl);
-    uint32_t h[8];
-    host_subtree_cv(data, len, c0, gn, root, h);
-    status[first] = bad ? 2 : memcmp(h, want, 32) != 0 ? 1 : 0;
-    return;
-  }
-  uint32_t mw[16], ivv[8], o[8];
-  for (int k = 0; k < 16; ++k) {
-    const uint8_t *b = nodes + 64 * pos + 4 * k;
-    mw[k] = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
-  }
-  iv(ivv);
-  blake3_cv(ivv, mw, 0, 0, 64, 4u | (root ? 8u : 0u), o);
-  if (memcmp(o, want, 32) != 0) bad = true;
-  uint64_t k2 = 1;
-  while (k2 * 2 < cnt) k2 *= 2;
-  host_verify_walk(data, len, n, gl, nodes, first, k2, pos + 1, mw, bad, false, status);
-  host_verify_walk(data, len, n, gl, nodes, first + k2, cnt - k2, pos + k2, mw + 8, bad, false, status);
-}
-
-int32_t b3w_bao_verify(const uint8_t *data, uint64_t len, const uint8_t *outboard, uint32_t group_log, const uint32_t *root, uint8_t *unit_status,
-                       int32_t *file_status, uint64_t *first_bad) {
-  if ((!data && len) || !outboard || !root || !unit_status || group_log > B3W_BAO_MAX_GROUP_LOG) return B3W_E_BAD_ARGUMENT;
-  const uint64_t n = num_chunks(len), n_units = (n + ((1ull << group_log) - 1)) >> group_log;
-  uint64_t hdr = 0;
-  for (int k = 0; k < 8; ++k) hdr |= (uint64_t)outboard[k] << (8 * k);
-  if (hdr != len) memset(unit_status, 3, (size_t)n_units);
-  else host_verify_walk(data, len, n, group_log, outboard + 8, 0, n_units, 0, root, false, true, unit_status);
-  int32_t worst = 0;
-  uint64_t first = ~0ull;
-  for (uint64_t u = 0; u < n_units; ++u) {
-    if (unit_status[u] > worst) worst = unit_status[u];
-    if (unit_status[u] && first == ~0ull) first = u;
-  }
-  if (file_status) *file_status = worst;
-  if (first_bad) *first_bad = first;
-  return B3W_OK;
 }
 
 }  // extern "C"
@@ -2987,38 +2613,78 @@ void stream_launch_tiles(const b3w_bao_stream *s, const uint8_t *window, uint32_
     const uint64_t n_scr = (s->tiles > 1 ? s->tiles : 0) + (s->groups > 1 ? s->groups : 0);
     hipLaunchKernelGGL(b3w_bao_stream_verify_kernel, dim3(count), dim3(B3W_TILE), 0, st, window, s->len, tile0, (const uint8_t *)s->ob, (const uint32_t *)s->root,
                        (const uint32_t *)s->scratch, (const uint32_t *)(s->scratch + n_scr * 8), s->gl, s->unit_status, s->file_status, s->first_bad);
-  } else if (s->gl) {
-    hipLaunchKernelGGL(b3w_bao_stream_tile_group_kernel, dim3(count), dim3(B3W_TILE), 0, st, window, s->len, tile0, s->ob, s->root, s->scratch, s->gl);
   } else {
-    hipLaunchKernelGGL(b3w_bao_stream_tile_kernel, dim3(count), dim3(B3W_TILE), 0, st, window, s->len, tile0, s->ob, s->root, s->scratch);
+    launch_pair(s->gl != 0, b3w_bao_stream_tile_kernel, b3w_bao_stream_tile_group_kernel, s->gl, dim3(count), dim3(B3W_TILE), st, window, s->len, tile0, s->ob, s->root, s->scratch);
   }
 }
 
 int32_t stream_begin_checks(b3w_ctx *ctx, uint64_t len, uint32_t group_log, const void *d_outboard, const void *d_root, const void *d_scratch,
                             uint64_t scratch_bytes, uint64_t need, b3w_bao_stream **out) {
-  if (!out) { ctx->last_error = "bao stream: a null session pointer"; return B3W_E_BAD_ARGUMENT; }
+  if (!out) return refuse(ctx, "bao stream", "a null session pointer");
   *out = nullptr;
-  if (group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "bao stream: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
-  if (num_chunks(len) > (1ull << 30)) { ctx->last_error = "bao stream: a file of more than 2^30 chunks"; return B3W_E_BAD_ARGUMENT; }
-  if (!d_outboard || !d_root) { ctx->last_error = "bao stream: a null pointer (outboard or root)"; return B3W_E_BAD_ARGUMENT; }
-  if (((uintptr_t)d_outboard & 7) || ((uintptr_t)d_root & 3)) { ctx->last_error = "bao stream: d_outboard is not 8-byte aligned, or d_root not 4-byte aligned"; return B3W_E_BAD_ARGUMENT; }
-  if (scratch_bytes < need) { ctx->last_error = "bao stream: the scratch is smaller than b3w_bao_stream_scratch_bytes says"; return B3W_E_BAD_ARGUMENT; }
-  if (need && (!d_scratch || ((uintptr_t)d_scratch & 15))) { ctx->last_error = "bao stream: the scratch is null or not 16-byte aligned"; return B3W_E_BAD_ARGUMENT; }
+  B3W_TRY(group_log_ok(ctx, "bao stream", group_log));
+  if (num_chunks(len) > (1ull << 30)) return refuse(ctx, "bao stream", "a file of more than 2^30 chunks");
+  if (!d_outboard || !d_root) return refuse(ctx, "bao stream", "a null pointer (outboard or root)");
+  if (((uintptr_t)d_outboard & 7) || ((uintptr_t)d_root & 3)) return refuse(ctx, "bao stream", "d_outboard is not 8-byte aligned, or d_root not 4-byte aligned");
+  if (scratch_bytes < need) return refuse(ctx, "bao stream", "the scratch is smaller than b3w_bao_stream_scratch_bytes says");
+  if (need && (!d_scratch || ((uintptr_t)d_scratch & 15))) return refuse(ctx, "bao stream", "the scratch is null or not 16-byte aligned");
   return B3W_OK;
 }
 
 b3w_bao_stream *stream_new(b3w_ctx *ctx, uint32_t kind, uint64_t len, uint32_t gl, void *d_scratch) {
   b3w_bao_stream *s = new b3w_bao_stream;
   s->ctx = ctx; s->kind = kind; s->gl = gl; s->len = len;
-  s->tiles = (num_chunks(len) + B3W_TILE - 1) / B3W_TILE;
+  s->tiles = tiles_of(len);
   s->groups = (s->tiles + B3W_TILE - 1) / B3W_TILE;
   s->scratch = reinterpret_cast<uint32_t *>(d_scratch);
   s->seen.assign((size_t)((s->tiles + 63) / 64), 0);
   return s;
 }
+// the session's tiles [t0, t0 + cnt) have been launched
+void stream_mark(b3w_bao_stream *s, uint64_t t0, uint64_t cnt) {
+  for (uint64_t t = t0; t < t0 + cnt; ++t) s->seen[t >> 6] |= 1ull << (t & 63);
+  s->pushed += cnt;
+}
+
+// the per-window rules of a session of known length (whole tiles or up to the file's end, each tile once): the reason, or nullptr
+const char *window_refusal(const b3w_bao_stream *s, uint64_t offset, const uint8_t *d_window, uint64_t bytes, std::string *twice) {
+  const uint64_t TB = (uint64_t)B3W_TILE * 1024;
+  if (s->finished) return "the session is finished";
+  if (offset % TB) return "the offset is not a multiple of 1 MiB";
+  if (!bytes || !d_window) return "an empty window or a null pointer";
+  if (offset > s->len || bytes > s->len - offset) return "the window reaches past the file's end";
+  if (bytes % TB && offset + bytes != s->len) return "the window is not whole tiles of 1 MiB and does not end at the file's end";
+  for (uint64_t t = offset / TB; t < (offset + bytes + TB - 1) / TB; ++t)
+    if (s->seen[t >> 6] >> (t & 63) & 1) { *twice = "tile " + std::to_string(t) + " was pushed before"; return twice->c_str(); }
+  return nullptr;
+}
 
 // ---- open-length sessions: the host side ---------------------------------------------------------------------------------------------
-uint64_t open_cap_tiles(uint64_t capacity) { return (num_chunks(capacity) + B3W_TILE - 1) / B3W_TILE; }   // scratch slots: the tail's tile included
+// an open session's group CVs: behind the tile CVs of its capacity in the scratch, the tail's tile included
+uint32_t *open_group_cv(const b3w_bao_stream *s) { return s->scratch + tiles_of(s->capacity) * 8; }
+// the relocation workgroups of T full tiles
+uint64_t open_move_wgs(uint64_t T, uint32_t gl) {
+  const OpenShape sh = open_shape(gl);
+  return ((T + (1ull << sh.tpw_log) - 1) >> sh.tpw_log) * sh.ppb;
+}
+// the rules of finishing an open session with this tail into this outboard: the reason, or "" and the file's length
+std::string open_finish_refusal(const b3w_bao_stream *s, const uint8_t *d_tail, uint64_t tail_bytes, const uint8_t *d_outboard, uint64_t outboard_bytes,
+                                const uint32_t *d_root, uint64_t *out_len) {
+  const uint64_t TB = (uint64_t)B3W_TILE * 1024, T = s->pushed;
+  if (s->kind != B3W_BAO_STREAM_OPEN) return "not an open session";
+  if (s->finished) return "the session is finished";
+  for (uint64_t t = 0; t < T; ++t)
+    if (!(s->seen[t >> 6] >> (t & 63) & 1)) return "tile " + std::to_string(t) + " has not been pushed and a later one has (" + std::to_string(T) + " tiles were pushed)";
+  if (tail_bytes >= TB) return "a tail of 1 MiB or more (whole tiles are pushed)";
+  if (tail_bytes && !d_tail) return "a null tail with bytes";
+  const uint64_t len = T * TB + tail_bytes;
+  if (len > s->capacity) return "the file (" + std::to_string(len) + " bytes) is longer than the session's capacity";
+  if (!d_outboard || !d_root) return "a null pointer (outboard or root)";
+  if (((uintptr_t)d_outboard & 7) || ((uintptr_t)d_root & 3)) return "d_outboard is not 8-byte aligned, or d_root not 4-byte aligned";
+  if (outboard_bytes < group_outboard_bytes(len, s->gl)) return "the outboard is smaller than b3w_bao_group_outboard_size of the file's length";
+  *out_len = len;
+  return std::string();
+}
 
 // the per-window rules of an open session (whole tiles only, inside the capacity, each tile once): the reason, or nullptr
 const char *open_window_refusal(const b3w_bao_stream *s, uint64_t offset, const uint8_t *d_window, uint64_t bytes, std::string *twice) {
@@ -3037,16 +2703,14 @@ int32_t open_push(b3w_bao_stream *s, uint64_t offset, const uint8_t *d_window, u
   b3w_ctx *ctx = s->ctx;
   const uint64_t TB = (uint64_t)B3W_TILE * 1024;
   std::string twice;
-  if (const char *why = open_window_refusal(s, offset, d_window, bytes, &twice)) { ctx->last_error = std::string("bao stream push: ") + why; return B3W_E_BAD_ARGUMENT; }
+  if (const char *why = open_window_refusal(s, offset, d_window, bytes, &twice)) return refuse(ctx, "bao stream push", why);
   const uint64_t t0 = offset / TB, cnt = bytes / TB;
   ON_DEVICE(ctx);
   hipStream_t st = (hipStream_t)stream;
-  if (s->gl) hipLaunchKernelGGL(b3w_bao_stream_open_tile_group_kernel, dim3((uint32_t)cnt), dim3(B3W_TILE), 0, st, d_window, (uint32_t)t0, s->blocks, s->scratch, s->gl);
-  else hipLaunchKernelGGL(b3w_bao_stream_open_tile_kernel, dim3((uint32_t)cnt), dim3(B3W_TILE), 0, st, d_window, (uint32_t)t0, s->blocks, s->scratch);
+  launch_pair(s->gl != 0, b3w_bao_stream_open_tile_kernel, b3w_bao_stream_open_tile_group_kernel, s->gl, dim3((uint32_t)cnt), dim3(B3W_TILE), st, d_window, (uint32_t)t0, s->blocks, s->scratch);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(ctx, e, "bao stream push launch (open session)");
-  for (uint64_t t = t0; t < t0 + cnt; ++t) s->seen[t >> 6] |= 1ull << (t & 63);
-  s->pushed += cnt;
+  stream_mark(s, t0, cnt);
   return B3W_OK;
 }
 
@@ -3054,16 +2718,12 @@ int32_t open_push(b3w_bao_stream *s, uint64_t offset, const uint8_t *d_window, u
 
 extern "C" {
 
-uint64_t b3w_bao_stream_scratch_bytes(uint64_t len, uint32_t kind) {
-  return kind == B3W_BAO_STREAM_OUTBOARD ? b3w_bao_batch_scratch_bytes(&len, 1) : kind == B3W_BAO_STREAM_VERIFY ? b3w_bao_verify_scratch_bytes(&len, 1) : 0;
-}
-
+// ---- stream sessions: outboards and verification of a file pushed in windows ---------------------------------------------------
 int32_t b3w_bao_stream_outboard_begin(b3w_ctx *ctx, uint64_t len, uint32_t group_log, uint8_t *d_outboard, uint32_t *d_root, void *d_scratch,
                                       uint64_t scratch_bytes, b3w_bao_stream **out_session) {
   if (!ctx) return B3W_E_BAD_ARGUMENT;
-  const int32_t rc = stream_begin_checks(ctx, len, group_log, d_outboard, d_root, d_scratch, scratch_bytes,
-                                         b3w_bao_stream_scratch_bytes(len, B3W_BAO_STREAM_OUTBOARD), out_session);
-  if (rc) return rc;
+  B3W_TRY(stream_begin_checks(ctx, len, group_log, d_outboard, d_root, d_scratch, scratch_bytes,
+                                         b3w_bao_stream_scratch_bytes(len, B3W_BAO_STREAM_OUTBOARD), out_session));
   b3w_bao_stream *s = stream_new(ctx, B3W_BAO_STREAM_OUTBOARD, len, group_log, d_scratch);
   s->ob = d_outboard; s->root = d_root;
   *out_session = s;
@@ -3074,11 +2734,10 @@ int32_t b3w_bao_stream_verify_begin(b3w_ctx *ctx, uint64_t len, uint32_t group_l
                                     uint8_t *d_unit_status, int32_t *d_file_status, uint64_t *d_first_bad, void *d_scratch, uint64_t scratch_bytes,
                                     void *stream, b3w_bao_stream **out_session) {
   if (!ctx) return B3W_E_BAD_ARGUMENT;
-  const int32_t rc = stream_begin_checks(ctx, len, group_log, d_outboard, d_root, d_scratch, scratch_bytes,
-                                         b3w_bao_stream_scratch_bytes(len, B3W_BAO_STREAM_VERIFY), out_session);
-  if (rc) return rc;
-  if (!d_unit_status || !d_file_status || !d_first_bad) { ctx->last_error = "bao stream: a null output (unit status, file status or first bad)"; return B3W_E_BAD_ARGUMENT; }
-  if (((uintptr_t)d_first_bad & 7) || ((uintptr_t)d_file_status & 3)) { ctx->last_error = "bao stream: d_first_bad is not 8-byte aligned, or d_file_status not 4-byte aligned"; return B3W_E_BAD_ARGUMENT; }
+  B3W_TRY(stream_begin_checks(ctx, len, group_log, d_outboard, d_root, d_scratch, scratch_bytes,
+                                         b3w_bao_stream_scratch_bytes(len, B3W_BAO_STREAM_VERIFY), out_session));
+  if (!d_unit_status || !d_file_status || !d_first_bad) return refuse(ctx, "bao stream", "a null output (unit status, file status or first bad)");
+  if (((uintptr_t)d_first_bad & 7) || ((uintptr_t)d_file_status & 3)) return refuse(ctx, "bao stream", "d_first_bad is not 8-byte aligned, or d_file_status not 4-byte aligned");
   ON_DEVICE(ctx);
   b3w_bao_stream *s = stream_new(ctx, B3W_BAO_STREAM_VERIFY, len, group_log, d_scratch);
   s->ob = const_cast<uint8_t *>(d_outboard); s->root = const_cast<uint32_t *>(d_root);
@@ -3104,49 +2763,30 @@ int32_t b3w_bao_stream_push(b3w_bao_stream *s, uint64_t offset, const uint8_t *d
   b3w_ctx *ctx = s->ctx;
   const uint64_t TB = (uint64_t)B3W_TILE * 1024;
   if (s->kind == B3W_BAO_STREAM_OPEN) return open_push(s, offset, d_window, bytes, stream);
-  if (s->finished) { ctx->last_error = "bao stream push: the session is finished"; return B3W_E_BAD_ARGUMENT; }
-  if (offset % TB) { ctx->last_error = "bao stream push: the offset is not a multiple of 1 MiB"; return B3W_E_BAD_ARGUMENT; }
-  if (!bytes || !d_window) { ctx->last_error = "bao stream push: an empty window or a null pointer"; return B3W_E_BAD_ARGUMENT; }
-  if (offset > s->len || bytes > s->len - offset) { ctx->last_error = "bao stream push: the window reaches past the file's end"; return B3W_E_BAD_ARGUMENT; }
-  if (bytes % TB && offset + bytes != s->len) { ctx->last_error = "bao stream push: the window is not whole tiles of 1 MiB and does not end at the file's end"; return B3W_E_BAD_ARGUMENT; }
+  std::string twice;
+  if (const char *why = window_refusal(s, offset, d_window, bytes, &twice)) return refuse(ctx, "bao stream push", why);
   const uint64_t t0 = offset / TB, cnt = (bytes + TB - 1) / TB;
-  for (uint64_t t = t0; t < t0 + cnt; ++t)
-    if (s->seen[t >> 6] >> (t & 63) & 1) { ctx->last_error = "bao stream push: tile " + std::to_string(t) + " was pushed before"; return B3W_E_BAD_ARGUMENT; }
   ON_DEVICE(ctx);
   hipStream_t st = (hipStream_t)stream;
   if (s->begun) HIP_TRY(ctx, hipStreamWaitEvent(st, s->begun, 0));    // (on the device: the host waits for nothing)
   stream_launch_tiles(s, d_window, (uint32_t)t0, (uint32_t)cnt, st);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(ctx, e, "bao stream push launch");
-  for (uint64_t t = t0; t < t0 + cnt; ++t) s->seen[t >> 6] |= 1ull << (t & 63);
-  s->pushed += cnt;
+  stream_mark(s, t0, cnt);
   return B3W_OK;
 }
 
 int32_t b3w_bao_stream_finish(b3w_bao_stream *s, void *stream) {
   if (!s) return B3W_E_BAD_ARGUMENT;
   b3w_ctx *ctx = s->ctx;
-  if (s->kind == B3W_BAO_STREAM_OPEN) { ctx->last_error = "bao stream finish: an open session is finished by b3w_bao_stream_open_finish"; return B3W_E_BAD_ARGUMENT; }
-  if (s->finished) { ctx->last_error = "bao stream finish: the session is finished"; return B3W_E_BAD_ARGUMENT; }
-  if (s->len && s->pushed != s->tiles) {
-    ctx->last_error = "bao stream finish: " + std::to_string(s->tiles - s->pushed) + " of " + std::to_string(s->tiles) + " tiles have not been pushed";
-    return B3W_E_BAD_ARGUMENT;
-  }
+  if (s->kind == B3W_BAO_STREAM_OPEN) return refuse(ctx, "bao stream finish", "an open session is finished by b3w_bao_stream_open_finish");
+  if (s->finished) return refuse(ctx, "bao stream finish", "the session is finished");
+  if (s->len && s->pushed != s->tiles) return refuse(ctx, "bao stream finish", std::to_string(s->tiles - s->pushed) + " of " + std::to_string(s->tiles) + " tiles have not been pushed");
   ON_DEVICE(ctx);
   hipStream_t st = (hipStream_t)stream;
-  if (!s->len) {                                                      // no byte, no push: the empty chunk's ROOT output, here
-    stream_launch_tiles(s, nullptr, 0, 1, st);
-  } else if (s->kind == B3W_BAO_STREAM_OUTBOARD && s->tiles > 1) {
-    uint32_t *tile_cv = s->scratch, *group_cv = tile_cv + s->tiles * 8;
-    const uint64_t T = B3W_TILE;
-    if (s->gl) {
-      hipLaunchKernelGGL(b3w_bao_stream_merge_group_kernel, dim3((uint32_t)s->groups), dim3(256), 0, st, s->len, T, (const uint32_t *)tile_cv, group_cv, s->ob, s->root, s->gl);
-      if (s->groups > 1) hipLaunchKernelGGL(b3w_bao_stream_merge_group_kernel, dim3(1), dim3(256), 0, st, s->len, T * T, (const uint32_t *)group_cv, (uint32_t *)nullptr, s->ob, s->root, s->gl);
-    } else {
-      hipLaunchKernelGGL(b3w_bao_stream_merge_kernel, dim3((uint32_t)s->groups), dim3(256), 0, st, s->len, T, (const uint32_t *)tile_cv, group_cv, s->ob, s->root);
-      if (s->groups > 1) hipLaunchKernelGGL(b3w_bao_stream_merge_kernel, dim3(1), dim3(256), 0, st, s->len, T * T, (const uint32_t *)group_cv, (uint32_t *)nullptr, s->ob, s->root);
-    }
-  }                                                                   // (verification: the windows' kernels have left the per-file outputs final)
+  if (!s->len) stream_launch_tiles(s, nullptr, 0, 1, st);             // no byte, no push: the empty chunk's ROOT output, here
+  else if (s->kind == B3W_BAO_STREAM_OUTBOARD && s->tiles > 1) stream_merge(s->len, s->groups, s->gl, s->scratch, s->scratch + s->tiles * 8, s->ob, s->root, st);
+  // (verification: the windows' kernels have left the per-file outputs final)
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(ctx, e, "bao stream finish launch");
   s->finished = true;
@@ -3161,9 +2801,9 @@ void b3w_bao_stream_free(b3w_bao_stream *s) {
 
 }  // extern "C"
 
-// ---- many stream sessions in one launch: the host side ---------------------------------------------------------------------------
 namespace {
 
+// ---- many stream sessions in one launch ----------------------------------------------------------------------------------------------
 // A staging slot of the context's ring with room for `bytes` of rows: the first one, from many_next on, whose event has passed.  The
 // host waits (for the oldest slot) only where every slot is still in flight; hipHostMalloc / hipMalloc only where the slot has to grow.
 int32_t many_staging(b3w_ctx *ctx, uint64_t bytes, b3w_ctx::ManySlot **out) {
@@ -3204,8 +2844,7 @@ int32_t many_staging(b3w_ctx *ctx, uint64_t bytes, b3w_ctx::ManySlot **out) {
 // the rows to a slot and on to the device, on `st`; the caller launches behind the copy and then calls many_release
 int32_t many_upload(b3w_ctx *ctx, const std::vector<ManyRow> &rows, hipStream_t st, b3w_ctx::ManySlot **slot) {
   const uint64_t bytes = rows.size() * sizeof(ManyRow);
-  const int32_t rc = many_staging(ctx, bytes, slot);
-  if (rc) return rc;
+  B3W_TRY(many_staging(ctx, bytes, slot));
   memcpy((*slot)->h, rows.data(), (size_t)bytes);
   HIP_TRY(ctx, hipMemcpyAsync((*slot)->d, (*slot)->h, (size_t)bytes, hipMemcpyHostToDevice, st));
   return B3W_OK;
@@ -3215,10 +2854,11 @@ void many_release(b3w_ctx::ManySlot *slot, hipStream_t st) {
   if (hipEventRecord(slot->done, st) != hipSuccess) (void)hipStreamSynchronize(st);
   slot->busy = true;
 }
-
-int32_t many_refuse(b3w_ctx *ctx, const char *call, uint32_t i, const std::string &why) {
-  ctx->last_error = std::string("bao stream ") + call + ": entry " + std::to_string(i) + ": " + why;
-  return B3W_E_BAD_ARGUMENT;
+// behind the launches of a call whose table went through a slot: the slot is released even when a launch failed
+int32_t many_launched(b3w_ctx *ctx, b3w_ctx::ManySlot *slot, hipStream_t st, const char *what) {
+  const hipError_t e = hipGetLastError();
+  many_release(slot, st);
+  return e != hipSuccess ? hip_fail(ctx, e, what) : B3W_OK;
 }
 
 ManyRow many_tile_row(const b3w_bao_stream *s, const uint8_t *window, uint32_t tile0, uint32_t first) {
@@ -3240,34 +2880,51 @@ void many_launch_tiles(uint32_t kind, bool grp, const ManyRow *d_rows, uint32_t 
   else hipLaunchKernelGGL(b3w_bao_stream_tile_many_kernel, dim3(wgs), dim3(B3W_TILE), 0, st, d_rows, n_rows);
 }
 
+// entry i of a push pushes the session's tiles [t0, t0 + cnt)
+struct Span { b3w_bao_stream *s; uint64_t t0, cnt; uint32_t i; };
+// `total` tiles fit a grid and no tile is named twice -> the spans by (session, first tile)
+int32_t spans_ok(b3w_ctx *ctx, const char *call, const std::vector<Span> &spans, uint64_t total, std::vector<Span> *by_tile) {
+  if (total > 0x7fffffffull) return refuse(ctx, call, std::to_string(total) + " tiles in one call do not fit a 32-bit grid");
+  *by_tile = spans;
+  std::sort(by_tile->begin(), by_tile->end(), [](const Span &a, const Span &b) { return a.s != b.s ? std::less<const void *>()(a.s, b.s) : a.t0 != b.t0 ? a.t0 < b.t0 : a.i < b.i; });
+  for (size_t k = 1; k < by_tile->size(); ++k) {
+    const Span &a = (*by_tile)[k - 1], &b = (*by_tile)[k];
+    if (a.s == b.s && a.t0 + a.cnt > b.t0)
+      return refuse(ctx, call, entry_text(a.i > b.i ? a.i : b.i) + "tile " + std::to_string(b.t0) + " is named twice in the call (entry " + std::to_string(a.i < b.i ? a.i : b.i) + " has it too)");
+  }
+  return B3W_OK;
+}
+// no session is named twice in a finish
+int32_t sessions_once(b3w_ctx *ctx, const char *call, b3w_bao_stream *const *sessions, uint32_t n) {
+  std::vector<std::pair<const b3w_bao_stream *, uint32_t>> by_ptr(n);
+  for (uint32_t i = 0; i < n; ++i) by_ptr[i] = {sessions[i], i};
+  std::sort(by_ptr.begin(), by_ptr.end(), [](const auto &a, const auto &b) { return a.first != b.first ? std::less<const void *>()(a.first, b.first) : a.second < b.second; });
+  for (uint32_t k = 1; k < n; ++k)
+    if (by_ptr[k - 1].first == by_ptr[k].first)
+      return refuse(ctx, call, entry_text(by_ptr[k].second) + "the session appears twice in the call (entry " + std::to_string(by_ptr[k - 1].second) + " is the same)");
+  return B3W_OK;
+}
+
 // b3w_bao_stream_push_many for a call whose entry 0 is an open session: every session open, the open per-window rules, one launch
 int32_t open_push_many(b3w_ctx *ctx, b3w_bao_stream *const *sessions, const uint64_t *offsets, const uint8_t *const *d_windows, const uint64_t *bytes,
                        uint32_t n, void *stream) {
-  const char *call = "push_many";
+  const char *call = "bao stream push_many";
   const uint64_t TB = (uint64_t)B3W_TILE * 1024;
-  struct Span { b3w_bao_stream *s; uint64_t t0, cnt; uint32_t i; };
-  std::vector<Span> spans(n);
+  std::vector<Span> spans(n), by_tile;
   uint64_t total = 0;
   bool grp = false;
   for (uint32_t i = 0; i < n; ++i) {                                  // every entry is checked before anything is launched or marked
     b3w_bao_stream *s = sessions[i];
-    if (!s) return many_refuse(ctx, call, i, "a null session");
-    if (s->ctx != ctx) return many_refuse(ctx, call, i, "the session belongs to another context");
-    if (s->kind != B3W_BAO_STREAM_OPEN) return many_refuse(ctx, call, i, "the session is not of the kind of entry 0 (open sessions do not mix with sessions of known length)");
+    if (!s) return refuse(ctx, call, entry_text(i) + "a null session");
+    if (s->ctx != ctx) return refuse(ctx, call, entry_text(i) + "the session belongs to another context");
+    if (s->kind != B3W_BAO_STREAM_OPEN) return refuse(ctx, call, entry_text(i) + "the session is not of the kind of entry 0 (open sessions do not mix with sessions of known length)");
     std::string twice;
-    if (const char *why = open_window_refusal(s, offsets[i], d_windows[i], bytes[i], &twice)) return many_refuse(ctx, call, i, why);
+    if (const char *why = open_window_refusal(s, offsets[i], d_windows[i], bytes[i], &twice)) return refuse(ctx, call, entry_text(i) + why);
     spans[i] = Span{s, offsets[i] / TB, bytes[i] / TB, i};
     total += bytes[i] / TB;
     grp = grp || s->gl != 0;
   }
-  if (total > 0x7fffffffull) { ctx->last_error = "bao stream push_many: " + std::to_string(total) + " tiles in one call do not fit a 32-bit grid"; return B3W_E_BAD_ARGUMENT; }
-  std::vector<Span> by_tile(spans);
-  std::sort(by_tile.begin(), by_tile.end(), [](const Span &a, const Span &b) { return a.s != b.s ? std::less<const void *>()(a.s, b.s) : a.t0 != b.t0 ? a.t0 < b.t0 : a.i < b.i; });
-  for (uint32_t k = 1; k < n; ++k) {
-    const Span &a = by_tile[k - 1], &b = by_tile[k];
-    if (a.s == b.s && a.t0 + a.cnt > b.t0)
-      return many_refuse(ctx, call, a.i > b.i ? a.i : b.i, "tile " + std::to_string(b.t0) + " is named twice in the call (entry " + std::to_string(a.i < b.i ? a.i : b.i) + " has it too)");
-  }
+  B3W_TRY(spans_ok(ctx, call, spans, total, &by_tile));
   std::vector<ManyRow> rows(n);
   uint32_t first = 0;
   for (uint32_t i = 0; i < n; ++i) {
@@ -3280,18 +2937,11 @@ int32_t open_push_many(b3w_ctx *ctx, b3w_bao_stream *const *sessions, const uint
   ON_DEVICE(ctx);
   hipStream_t st = (hipStream_t)stream;
   b3w_ctx::ManySlot *slot = nullptr;
-  const int32_t rc = many_upload(ctx, rows, st, &slot);
-  if (rc) return rc;
-  const ManyRow *d_rows = reinterpret_cast<const ManyRow *>(slot->d);
-  if (grp) hipLaunchKernelGGL(b3w_bao_stream_open_tile_many_group_kernel, dim3(first), dim3(B3W_TILE), 0, st, d_rows, n);
-  else hipLaunchKernelGGL(b3w_bao_stream_open_tile_many_kernel, dim3(first), dim3(B3W_TILE), 0, st, d_rows, n);
-  const hipError_t e = hipGetLastError();
-  many_release(slot, st);
-  if (e != hipSuccess) return hip_fail(ctx, e, "bao stream push_many launch (open sessions)");
-  for (const Span &sp : spans) {
-    for (uint64_t t = sp.t0; t < sp.t0 + sp.cnt; ++t) sp.s->seen[t >> 6] |= 1ull << (t & 63);
-    sp.s->pushed += sp.cnt;
-  }
+  B3W_TRY(many_upload(ctx, rows, st, &slot));
+  hipLaunchKernelGGL(grp ? b3w_bao_stream_open_tile_many_group_kernel : b3w_bao_stream_open_tile_many_kernel, dim3(first), dim3(B3W_TILE), 0, st,
+                     reinterpret_cast<const ManyRow *>(slot->d), n);
+  B3W_TRY(many_launched(ctx, slot, st, "bao stream push_many launch (open sessions)"));
+  for (const Span &sp : spans) stream_mark(sp.s, sp.t0, sp.cnt);
   return B3W_OK;
 }
 
@@ -3299,43 +2949,31 @@ int32_t open_push_many(b3w_ctx *ctx, b3w_bao_stream *const *sessions, const uint
 
 extern "C" {
 
+// ---- many stream sessions in one launch ----------------------------------------------------------------------------------------------
 int32_t b3w_bao_stream_push_many(b3w_ctx *ctx, b3w_bao_stream *const *sessions, const uint64_t *offsets, const uint8_t *const *d_windows,
                                  const uint64_t *bytes, uint32_t n, void *stream) {
   if (!ctx) return B3W_E_BAD_ARGUMENT;
   if (!n) return B3W_OK;
-  if (!sessions || !offsets || !d_windows || !bytes) { ctx->last_error = "bao stream push_many: a null array"; return B3W_E_BAD_ARGUMENT; }
+  const char *call = "bao stream push_many";
+  if (!sessions || !offsets || !d_windows || !bytes) return refuse(ctx, call, "a null array");
   if (sessions[0] && sessions[0]->kind == B3W_BAO_STREAM_OPEN) return open_push_many(ctx, sessions, offsets, d_windows, bytes, n, stream);
-  const char *call = "push_many";
   const uint64_t TB = (uint64_t)B3W_TILE * 1024;
-  struct Span { b3w_bao_stream *s; uint64_t t0, cnt; uint32_t i; };
-  std::vector<Span> spans(n);
+  std::vector<Span> spans(n), by_tile;
   uint64_t total = 0;
   bool grp = false;
   for (uint32_t i = 0; i < n; ++i) {                                  // every entry is checked before anything is launched or marked
     b3w_bao_stream *s = sessions[i];
-    if (!s) return many_refuse(ctx, call, i, "a null session");
-    if (s->ctx != ctx) return many_refuse(ctx, call, i, "the session belongs to another context");
-    if (s->kind != sessions[0]->kind) return many_refuse(ctx, call, i, "the session is not of the kind of entry 0 (outboard and verification sessions do not mix)");
-    if (s->finished) return many_refuse(ctx, call, i, "the session is finished");
-    if (offsets[i] % TB) return many_refuse(ctx, call, i, "the offset is not a multiple of 1 MiB");
-    if (!bytes[i] || !d_windows[i]) return many_refuse(ctx, call, i, "an empty window or a null pointer");
-    if (offsets[i] > s->len || bytes[i] > s->len - offsets[i]) return many_refuse(ctx, call, i, "the window reaches past the file's end");
-    if (bytes[i] % TB && offsets[i] + bytes[i] != s->len) return many_refuse(ctx, call, i, "the window is not whole tiles of 1 MiB and does not end at the file's end");
+    if (!s) return refuse(ctx, call, entry_text(i) + "a null session");
+    if (s->ctx != ctx) return refuse(ctx, call, entry_text(i) + "the session belongs to another context");
+    if (s->kind != sessions[0]->kind) return refuse(ctx, call, entry_text(i) + "the session is not of the kind of entry 0 (outboard and verification sessions do not mix)");
+    std::string twice;
+    if (const char *why = window_refusal(s, offsets[i], d_windows[i], bytes[i], &twice)) return refuse(ctx, call, entry_text(i) + why);
     const uint64_t t0 = offsets[i] / TB, cnt = (bytes[i] + TB - 1) / TB;
-    for (uint64_t t = t0; t < t0 + cnt; ++t)
-      if (s->seen[t >> 6] >> (t & 63) & 1) return many_refuse(ctx, call, i, "tile " + std::to_string(t) + " was pushed before");
     spans[i] = Span{s, t0, cnt, i};
     total += cnt;
     grp = grp || s->gl != 0;
   }
-  if (total > 0x7fffffffull) { ctx->last_error = "bao stream push_many: " + std::to_string(total) + " tiles in one call do not fit a 32-bit grid"; return B3W_E_BAD_ARGUMENT; }
-  std::vector<Span> by_tile(spans);
-  std::sort(by_tile.begin(), by_tile.end(), [](const Span &a, const Span &b) { return a.s != b.s ? std::less<const void *>()(a.s, b.s) : a.t0 != b.t0 ? a.t0 < b.t0 : a.i < b.i; });
-  for (uint32_t k = 1; k < n; ++k) {
-    const Span &a = by_tile[k - 1], &b = by_tile[k];
-    if (a.s == b.s && a.t0 + a.cnt > b.t0)
-      return many_refuse(ctx, call, a.i > b.i ? a.i : b.i, "tile " + std::to_string(b.t0) + " is named twice in the call (entry " + std::to_string(a.i < b.i ? a.i : b.i) + " has it too)");
-  }
+  B3W_TRY(spans_ok(ctx, call, spans, total, &by_tile));
   std::vector<ManyRow> rows(n);
   uint32_t first = 0;
   for (uint32_t i = 0; i < n; ++i) {
@@ -3347,45 +2985,34 @@ int32_t b3w_bao_stream_push_many(b3w_ctx *ctx, b3w_bao_stream *const *sessions, 
   for (uint32_t k = 0; k < n; ++k)                                    // (on the device: the host waits for nothing)
     if (by_tile[k].s->begun && (k == 0 || by_tile[k - 1].s != by_tile[k].s)) HIP_TRY(ctx, hipStreamWaitEvent(st, by_tile[k].s->begun, 0));
   b3w_ctx::ManySlot *slot = nullptr;
-  const int32_t rc = many_upload(ctx, rows, st, &slot);
-  if (rc) return rc;
+  B3W_TRY(many_upload(ctx, rows, st, &slot));
   many_launch_tiles(sessions[0]->kind, grp, reinterpret_cast<const ManyRow *>(slot->d), n, first, st);
-  const hipError_t e = hipGetLastError();
-  many_release(slot, st);
-  if (e != hipSuccess) return hip_fail(ctx, e, "bao stream push_many launch");
-  for (const Span &sp : spans) {
-    for (uint64_t t = sp.t0; t < sp.t0 + sp.cnt; ++t) sp.s->seen[t >> 6] |= 1ull << (t & 63);
-    sp.s->pushed += sp.cnt;
-  }
+  B3W_TRY(many_launched(ctx, slot, st, "bao stream push_many launch"));
+  for (const Span &sp : spans) stream_mark(sp.s, sp.t0, sp.cnt);
   return B3W_OK;
 }
 
 int32_t b3w_bao_stream_finish_many(b3w_ctx *ctx, b3w_bao_stream *const *sessions, uint32_t n, void *stream) {
   if (!ctx) return B3W_E_BAD_ARGUMENT;
   if (!n) return B3W_OK;
-  if (!sessions) { ctx->last_error = "bao stream finish_many: a null array"; return B3W_E_BAD_ARGUMENT; }
-  const char *call = "finish_many";
+  const char *call = "bao stream finish_many";
+  if (!sessions) return refuse(ctx, call, "a null array");
   uint64_t wgs = 0;
   bool grp = false;
   for (uint32_t i = 0; i < n; ++i) {
     const b3w_bao_stream *s = sessions[i];
-    if (!s) return many_refuse(ctx, call, i, "a null session");
-    if (s->ctx != ctx) return many_refuse(ctx, call, i, "the session belongs to another context");
-    if (s->kind == B3W_BAO_STREAM_OPEN) return many_refuse(ctx, call, i, "an open session is finished by b3w_bao_stream_open_finish");
-    if (s->kind != sessions[0]->kind) return many_refuse(ctx, call, i, "the session is not of the kind of entry 0 (outboard and verification sessions do not mix)");
-    if (s->finished) return many_refuse(ctx, call, i, "the session is finished");
+    if (!s) return refuse(ctx, call, entry_text(i) + "a null session");
+    if (s->ctx != ctx) return refuse(ctx, call, entry_text(i) + "the session belongs to another context");
+    if (s->kind == B3W_BAO_STREAM_OPEN) return refuse(ctx, call, entry_text(i) + "an open session is finished by b3w_bao_stream_open_finish");
+    if (s->kind != sessions[0]->kind) return refuse(ctx, call, entry_text(i) + "the session is not of the kind of entry 0 (outboard and verification sessions do not mix)");
+    if (s->finished) return refuse(ctx, call, entry_text(i) + "the session is finished");
     if (s->len && s->pushed != s->tiles)
-      return many_refuse(ctx, call, i, std::to_string(s->tiles - s->pushed) + " of " + std::to_string(s->tiles) + " tiles have not been pushed");
+      return refuse(ctx, call, entry_text(i) + std::to_string(s->tiles - s->pushed) + " of " + std::to_string(s->tiles) + " tiles have not been pushed");
     wgs += s->groups;
     grp = grp || s->gl != 0;
   }
-  if (wgs > 0x7fffffffull) { ctx->last_error = "bao stream finish_many: " + std::to_string(wgs) + " workgroups in one call do not fit a 32-bit grid"; return B3W_E_BAD_ARGUMENT; }
-  std::vector<std::pair<const b3w_bao_stream *, uint32_t>> by_ptr(n);
-  for (uint32_t i = 0; i < n; ++i) by_ptr[i] = {sessions[i], i};
-  std::sort(by_ptr.begin(), by_ptr.end(), [](const auto &a, const auto &b) { return a.first != b.first ? std::less<const void *>()(a.first, b.first) : a.second < b.second; });
-  for (uint32_t k = 1; k < n; ++k)
-    if (by_ptr[k - 1].first == by_ptr[k].first)
-      return many_refuse(ctx, call, by_ptr[k].second, "the session appears twice in the call (entry " + std::to_string(by_ptr[k - 1].second) + " is the same)");
+  if (wgs > 0x7fffffffull) return refuse(ctx, call, std::to_string(wgs) + " workgroups in one call do not fit a 32-bit grid");
+  B3W_TRY(sessions_once(ctx, call, sessions, n));
   // one table, three runs of rows: the first merge storey (a workgroup per 1 024 tiles), the second (files past 1 GiB), the files of no bytes
   const bool outboard = sessions[0]->kind == B3W_BAO_STREAM_OUTBOARD;
   std::vector<ManyRow> rows;
@@ -3412,21 +3039,11 @@ int32_t b3w_bao_stream_finish_many(b3w_ctx *ctx, b3w_bao_stream *const *sessions
     ON_DEVICE(ctx);
     hipStream_t st = (hipStream_t)stream;
     b3w_ctx::ManySlot *slot = nullptr;
-    const int32_t rc = many_upload(ctx, rows, st, &slot);
-    if (rc) return rc;
+    B3W_TRY(many_upload(ctx, rows, st, &slot));
     const ManyRow *d_rows = reinterpret_cast<const ManyRow *>(slot->d);
-    const uint64_t T = B3W_TILE;
-    if (grp) {
-      if (n1) hipLaunchKernelGGL(b3w_bao_stream_merge_many_group_kernel, dim3(wg1), dim3(256), 0, st, d_rows, n1, T);
-      if (n2) hipLaunchKernelGGL(b3w_bao_stream_merge_many_group_kernel, dim3(n2), dim3(256), 0, st, d_rows + n1, n2, T * T);
-    } else {
-      if (n1) hipLaunchKernelGGL(b3w_bao_stream_merge_many_kernel, dim3(wg1), dim3(256), 0, st, d_rows, n1, T);
-      if (n2) hipLaunchKernelGGL(b3w_bao_stream_merge_many_kernel, dim3(n2), dim3(256), 0, st, d_rows + n1, n2, T * T);
-    }
+    many_merge(grp, d_rows, n1, wg1, d_rows + n1, n2, st);
     if (n3) many_launch_tiles(sessions[0]->kind, grp, d_rows + n1 + n2, n3, n3, st);
-    const hipError_t e = hipGetLastError();
-    many_release(slot, st);
-    if (e != hipSuccess) return hip_fail(ctx, e, "bao stream finish_many launch");
+    B3W_TRY(many_launched(ctx, slot, st, "bao stream finish_many launch"));
   }
   for (uint32_t i = 0; i < n; ++i) sessions[i]->finished = true;
   return B3W_OK;
@@ -3438,29 +3055,17 @@ uint64_t b3w_bao_stream_open_staging_bytes(uint64_t capacity_bytes, uint32_t gro
   return (capacity_bytes / ((uint64_t)B3W_TILE * 1024)) * open_shape(group_log).bb + OPEN_PAD;
 }
 
-uint64_t b3w_bao_stream_open_scratch_bytes(uint64_t capacity_bytes) {
-  const uint64_t tiles = open_cap_tiles(capacity_bytes);
-  return (tiles + (tiles + B3W_TILE - 1) / B3W_TILE) * 32;
-}
-
-uint64_t b3w_bao_stream_open_block_pos(uint64_t len, uint32_t group_log, uint64_t tile) {
-  const uint64_t TB = (uint64_t)B3W_TILE * 1024;
-  if (group_log > B3W_BAO_MAX_GROUP_LOG || tile >= len / TB) return UINT64_MAX;
-  const uint64_t G1 = (1ull << group_log) - 1;
-  return preorder_pos((num_chunks(len) + G1) >> group_log, (tile * B3W_TILE) >> group_log, B3W_TILE >> group_log);
-}
-
 int32_t b3w_bao_stream_open_begin(b3w_ctx *ctx, uint64_t capacity_bytes, uint32_t group_log, void *d_staging, uint64_t staging_bytes, void *d_scratch,
                                   uint64_t scratch_bytes, b3w_bao_stream **out_session) {
   if (!ctx) return B3W_E_BAD_ARGUMENT;
-  if (!out_session) { ctx->last_error = "bao stream open: a null session pointer"; return B3W_E_BAD_ARGUMENT; }
+  if (!out_session) return refuse(ctx, "bao stream open", "a null session pointer");
   *out_session = nullptr;
-  if (group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "bao stream open: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
-  if (num_chunks(capacity_bytes) > (1ull << 30)) { ctx->last_error = "bao stream open: a capacity of more than 2^30 chunks"; return B3W_E_BAD_ARGUMENT; }
-  if (!d_staging || !d_scratch) { ctx->last_error = "bao stream open: a null pointer (staging or scratch)"; return B3W_E_BAD_ARGUMENT; }
-  if (((uintptr_t)d_staging & 15) || ((uintptr_t)d_scratch & 15)) { ctx->last_error = "bao stream open: the staging or the scratch is not 16-byte aligned"; return B3W_E_BAD_ARGUMENT; }
-  if (staging_bytes < b3w_bao_stream_open_staging_bytes(capacity_bytes, group_log)) { ctx->last_error = "bao stream open: the staging is smaller than b3w_bao_stream_open_staging_bytes says"; return B3W_E_BAD_ARGUMENT; }
-  if (scratch_bytes < b3w_bao_stream_open_scratch_bytes(capacity_bytes)) { ctx->last_error = "bao stream open: the scratch is smaller than b3w_bao_stream_open_scratch_bytes says"; return B3W_E_BAD_ARGUMENT; }
+  B3W_TRY(group_log_ok(ctx, "bao stream open", group_log));
+  if (num_chunks(capacity_bytes) > (1ull << 30)) return refuse(ctx, "bao stream open", "a capacity of more than 2^30 chunks");
+  if (!d_staging || !d_scratch) return refuse(ctx, "bao stream open", "a null pointer (staging or scratch)");
+  if (((uintptr_t)d_staging & 15) || ((uintptr_t)d_scratch & 15)) return refuse(ctx, "bao stream open", "the staging or the scratch is not 16-byte aligned");
+  if (staging_bytes < b3w_bao_stream_open_staging_bytes(capacity_bytes, group_log)) return refuse(ctx, "bao stream open", "the staging is smaller than b3w_bao_stream_open_staging_bytes says");
+  if (scratch_bytes < b3w_bao_stream_open_scratch_bytes(capacity_bytes)) return refuse(ctx, "bao stream open", "the scratch is smaller than b3w_bao_stream_open_scratch_bytes says");
   b3w_bao_stream *s = new b3w_bao_stream;
   s->ctx = ctx; s->kind = B3W_BAO_STREAM_OPEN; s->gl = group_log; s->capacity = capacity_bytes;
   s->tiles = capacity_bytes / ((uint64_t)B3W_TILE * 1024);             // (the tiles a push may name; open_finish sets len, tiles and groups)
@@ -3475,45 +3080,19 @@ int32_t b3w_bao_stream_open_finish(b3w_bao_stream *s, const uint8_t *d_tail, uin
                                    uint32_t *d_root, void *stream, uint64_t *out_len) {
   if (!s) return B3W_E_BAD_ARGUMENT;
   b3w_ctx *ctx = s->ctx;
-  const uint64_t TB = (uint64_t)B3W_TILE * 1024, T = s->pushed;
-  if (s->kind != B3W_BAO_STREAM_OPEN) { ctx->last_error = "bao stream open_finish: not an open session"; return B3W_E_BAD_ARGUMENT; }
-  if (s->finished) { ctx->last_error = "bao stream open_finish: the session is finished"; return B3W_E_BAD_ARGUMENT; }
-  for (uint64_t t = 0; t < T; ++t)
-    if (!(s->seen[t >> 6] >> (t & 63) & 1)) {
-      ctx->last_error = "bao stream open_finish: tile " + std::to_string(t) + " has not been pushed and a later one has (" + std::to_string(T) + " tiles were pushed)";
-      return B3W_E_BAD_ARGUMENT;
-    }
-  if (tail_bytes >= TB) { ctx->last_error = "bao stream open_finish: a tail of 1 MiB or more (whole tiles are pushed)"; return B3W_E_BAD_ARGUMENT; }
-  if (tail_bytes && !d_tail) { ctx->last_error = "bao stream open_finish: a null tail with bytes"; return B3W_E_BAD_ARGUMENT; }
-  const uint64_t len = T * TB + tail_bytes;
-  if (len > s->capacity) { ctx->last_error = "bao stream open_finish: the file (" + std::to_string(len) + " bytes) is longer than the session's capacity"; return B3W_E_BAD_ARGUMENT; }
-  if (!d_outboard || !d_root) { ctx->last_error = "bao stream open_finish: a null pointer (outboard or root)"; return B3W_E_BAD_ARGUMENT; }
-  if (((uintptr_t)d_outboard & 7) || ((uintptr_t)d_root & 3)) { ctx->last_error = "bao stream open_finish: d_outboard is not 8-byte aligned, or d_root not 4-byte aligned"; return B3W_E_BAD_ARGUMENT; }
-  if (outboard_bytes < b3w_bao_group_outboard_size(len, s->gl)) { ctx->last_error = "bao stream open_finish: the outboard is smaller than b3w_bao_group_outboard_size of the file's length"; return B3W_E_BAD_ARGUMENT; }
+  const uint64_t T = s->pushed;
+  uint64_t len = 0;
+  const std::string why = open_finish_refusal(s, d_tail, tail_bytes, d_outboard, outboard_bytes, d_root, &len);
+  if (!why.empty()) return refuse(ctx, "bao stream open_finish", why);
   ON_DEVICE(ctx);
   hipStream_t st = (hipStream_t)stream;
   const uint64_t tiles = T + (tail_bytes || !T ? 1 : 0), groups = (tiles + B3W_TILE - 1) / B3W_TILE;
-  uint32_t *tile_cv = s->scratch, *group_cv = tile_cv + open_cap_tiles(s->capacity) * 8;
+  uint32_t *tile_cv = s->scratch;
   // at most four launches: the tail's tile (for T = 0 the whole file, rooted; header and all), the blocks to their places, the storeys
-  if (tail_bytes || !T) {
-    if (s->gl) hipLaunchKernelGGL(b3w_bao_stream_tile_group_kernel, dim3(1), dim3(B3W_TILE), 0, st, d_tail, len, (uint32_t)T, d_outboard, d_root, tile_cv, s->gl);
-    else hipLaunchKernelGGL(b3w_bao_stream_tile_kernel, dim3(1), dim3(B3W_TILE), 0, st, d_tail, len, (uint32_t)T, d_outboard, d_root, tile_cv);
-  }
-  if (T) {
-    const OpenShape sh = open_shape(s->gl);
-    const uint64_t wgs = ((T + (1ull << sh.tpw_log) - 1) >> sh.tpw_log) * sh.ppb;                    // (at most 2^22)
-    hipLaunchKernelGGL(b3w_bao_stream_open_relocate_kernel, dim3((uint32_t)wgs), dim3(256), 0, st, (const uint8_t *)s->blocks, len, (uint32_t)T, s->gl, d_outboard, d_root);
-  }
-  if (tiles > 1) {
-    const uint64_t U = B3W_TILE;
-    if (s->gl) {
-      hipLaunchKernelGGL(b3w_bao_stream_merge_group_kernel, dim3((uint32_t)groups), dim3(256), 0, st, len, U, (const uint32_t *)tile_cv, group_cv, d_outboard, d_root, s->gl);
-      if (groups > 1) hipLaunchKernelGGL(b3w_bao_stream_merge_group_kernel, dim3(1), dim3(256), 0, st, len, U * U, (const uint32_t *)group_cv, (uint32_t *)nullptr, d_outboard, d_root, s->gl);
-    } else {
-      hipLaunchKernelGGL(b3w_bao_stream_merge_kernel, dim3((uint32_t)groups), dim3(256), 0, st, len, U, (const uint32_t *)tile_cv, group_cv, d_outboard, d_root);
-      if (groups > 1) hipLaunchKernelGGL(b3w_bao_stream_merge_kernel, dim3(1), dim3(256), 0, st, len, U * U, (const uint32_t *)group_cv, (uint32_t *)nullptr, d_outboard, d_root);
-    }
-  }
+  if (tail_bytes || !T)
+    launch_pair(s->gl != 0, b3w_bao_stream_tile_kernel, b3w_bao_stream_tile_group_kernel, s->gl, dim3(1), dim3(B3W_TILE), st, d_tail, len, (uint32_t)T, d_outboard, d_root, tile_cv);
+  if (T) hipLaunchKernelGGL(b3w_bao_stream_open_relocate_kernel, dim3((uint32_t)open_move_wgs(T, s->gl)), dim3(256), 0, st, (const uint8_t *)s->blocks, len, (uint32_t)T, s->gl, d_outboard, d_root);   // (at most 2^22)
+  if (tiles > 1) stream_merge(len, groups, s->gl, tile_cv, open_group_cv(s), d_outboard, d_root, st);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(ctx, e, "bao stream open_finish launch");
   s->len = len; s->ob = d_outboard; s->root = d_root;
@@ -3531,47 +3110,30 @@ int32_t b3w_bao_stream_open_finish_many(b3w_ctx *ctx, b3w_bao_stream *const *ses
                                         uint64_t *out_lens) {
   if (!ctx) return B3W_E_BAD_ARGUMENT;
   if (!n) return B3W_OK;
-  if (!sessions || !d_tails || !tail_bytes || !d_outboards || !outboard_bytes || !d_roots) { ctx->last_error = "bao stream open_finish_many: a null array"; return B3W_E_BAD_ARGUMENT; }
-  const char *call = "open_finish_many";
+  const char *call = "bao stream open_finish_many";
+  if (!sessions || !d_tails || !tail_bytes || !d_outboards || !outboard_bytes || !d_roots) return refuse(ctx, call, "a null array");
   const uint64_t TB = (uint64_t)B3W_TILE * 1024, LIMIT = 0x7fffffffull;
   std::vector<uint64_t> lens(n);
   uint64_t wg_tail = 0, wg_move = 0, wg_one = 0, wg_two = 0;
   bool grp = false;
   for (uint32_t i = 0; i < n; ++i) {                                  // every entry is checked before anything is launched or marked
     const b3w_bao_stream *s = sessions[i];
-    if (!s) return many_refuse(ctx, call, i, "a null session");
-    if (s->ctx != ctx) return many_refuse(ctx, call, i, "the session belongs to another context");
-    if (s->kind != B3W_BAO_STREAM_OPEN) return many_refuse(ctx, call, i, "not an open session");
-    if (s->finished) return many_refuse(ctx, call, i, "the session is finished");
+    if (!s) return refuse(ctx, call, entry_text(i) + "a null session");
+    if (s->ctx != ctx) return refuse(ctx, call, entry_text(i) + "the session belongs to another context");
+    const std::string why = open_finish_refusal(s, d_tails[i], tail_bytes[i], d_outboards[i], outboard_bytes[i], d_roots[i], &lens[i]);
+    if (!why.empty()) return refuse(ctx, call, entry_text(i) + why);
     const uint64_t T = s->pushed;
-    for (uint64_t t = 0; t < T; ++t)
-      if (!(s->seen[t >> 6] >> (t & 63) & 1))
-        return many_refuse(ctx, call, i, "tile " + std::to_string(t) + " has not been pushed and a later one has (" + std::to_string(T) + " tiles were pushed)");
-    if (tail_bytes[i] >= TB) return many_refuse(ctx, call, i, "a tail of 1 MiB or more (whole tiles are pushed)");
-    if (tail_bytes[i] && !d_tails[i]) return many_refuse(ctx, call, i, "a null tail with bytes");
-    const uint64_t len = T * TB + tail_bytes[i];
-    if (len > s->capacity) return many_refuse(ctx, call, i, "the file (" + std::to_string(len) + " bytes) is longer than the session's capacity");
-    if (!d_outboards[i] || !d_roots[i]) return many_refuse(ctx, call, i, "a null pointer (outboard or root)");
-    if (((uintptr_t)d_outboards[i] & 7) || ((uintptr_t)d_roots[i] & 3)) return many_refuse(ctx, call, i, "d_outboard is not 8-byte aligned, or d_root not 4-byte aligned");
-    if (outboard_bytes[i] < b3w_bao_group_outboard_size(len, s->gl)) return many_refuse(ctx, call, i, "the outboard is smaller than b3w_bao_group_outboard_size of the file's length");
-    lens[i] = len;
     const bool tail = tail_bytes[i] || !T;
     const uint64_t tiles = T + (tail ? 1 : 0);
-    const OpenShape sh = open_shape(s->gl);
     wg_tail += tail ? 1 : 0;
-    wg_move += ((T + (1ull << sh.tpw_log) - 1) >> sh.tpw_log) * sh.ppb;
+    wg_move += open_move_wgs(T, s->gl);
     wg_one += tiles > 1 ? (tiles + B3W_TILE - 1) / B3W_TILE : 0;
     wg_two += tiles > B3W_TILE ? 1 : 0;
     if (wg_tail > LIMIT || wg_move > LIMIT || wg_one > LIMIT || wg_two > LIMIT)
-      return many_refuse(ctx, call, i, "with this entry one of the call's four grids has more than 2^31 - 1 workgroups");
+      return refuse(ctx, call, entry_text(i) + "with this entry one of the call's four grids has more than 2^31 - 1 workgroups");
     grp = grp || s->gl != 0;
   }
-  std::vector<std::pair<const b3w_bao_stream *, uint32_t>> by_ptr(n);
-  for (uint32_t i = 0; i < n; ++i) by_ptr[i] = {sessions[i], i};
-  std::sort(by_ptr.begin(), by_ptr.end(), [](const auto &a, const auto &b) { return a.first != b.first ? std::less<const void *>()(a.first, b.first) : a.second < b.second; });
-  for (uint32_t k = 1; k < n; ++k)
-    if (by_ptr[k - 1].first == by_ptr[k].first)
-      return many_refuse(ctx, call, by_ptr[k].second, "the session appears twice in the call (entry " + std::to_string(by_ptr[k - 1].second) + " is the same)");
+  B3W_TRY(sessions_once(ctx, call, sessions, n));
   // the row of entry i for one of the runs: the file's length, outboard, root and group_log; the run sets the rest
   auto row = [&](uint32_t i, uint32_t first) {
     ManyRow r{};
@@ -3590,46 +3152,35 @@ int32_t b3w_bao_stream_open_finish_many(b3w_ctx *ctx, b3w_bao_stream *const *ses
   for (uint32_t i = 0; i < n; ++i) {                                  // the blocks to their places, and the headers
     const uint64_t T = sessions[i]->pushed;
     if (!T) continue;
-    const OpenShape sh = open_shape(sessions[i]->gl);
     ManyRow r = row(i, first);
     r.window = sessions[i]->blocks;
     rows.push_back(r); n_move++;
-    first += (uint32_t)(((T + (1ull << sh.tpw_log) - 1) >> sh.tpw_log) * sh.ppb);
+    first += (uint32_t)open_move_wgs(T, sessions[i]->gl);
   }
   first = 0;
   for (uint32_t i = 0; i < n; ++i) {                                  // the first merge storey: a workgroup per 1 024 tiles
     const uint64_t tiles = (lens[i] + TB - 1) / TB;
     if (tiles <= 1) continue;
     ManyRow r = row(i, first);
-    r.cv = sessions[i]->scratch; r.aux = sessions[i]->scratch + open_cap_tiles(sessions[i]->capacity) * 8;
+    r.cv = sessions[i]->scratch; r.aux = open_group_cv(sessions[i]);
     rows.push_back(r); n_one++;
     first += (uint32_t)((tiles + B3W_TILE - 1) / B3W_TILE);
   }
   for (uint32_t i = 0; i < n; ++i) {                                  // the second: files past 1 GiB
     if ((lens[i] + TB - 1) / TB <= B3W_TILE) continue;
     ManyRow r = row(i, n_two);
-    r.cv = sessions[i]->scratch + open_cap_tiles(sessions[i]->capacity) * 8;
+    r.cv = open_group_cv(sessions[i]);
     rows.push_back(r); n_two++;
   }
   ON_DEVICE(ctx);
   hipStream_t st = (hipStream_t)stream;
   b3w_ctx::ManySlot *slot = nullptr;
-  const int32_t rc = many_upload(ctx, rows, st, &slot);
-  if (rc) return rc;
+  B3W_TRY(many_upload(ctx, rows, st, &slot));
   const ManyRow *d_tail = reinterpret_cast<const ManyRow *>(slot->d), *d_move = d_tail + n_tail, *d_one = d_move + n_move, *d_two = d_one + n_one;
-  const uint64_t U = B3W_TILE;
   if (n_tail) many_launch_tiles(B3W_BAO_STREAM_OUTBOARD, grp, d_tail, n_tail, n_tail, st);
   if (n_move) hipLaunchKernelGGL(b3w_bao_stream_open_relocate_many_kernel, dim3((uint32_t)wg_move), dim3(256), 0, st, d_move, n_move);
-  if (grp) {
-    if (n_one) hipLaunchKernelGGL(b3w_bao_stream_merge_many_group_kernel, dim3((uint32_t)wg_one), dim3(256), 0, st, d_one, n_one, U);
-    if (n_two) hipLaunchKernelGGL(b3w_bao_stream_merge_many_group_kernel, dim3(n_two), dim3(256), 0, st, d_two, n_two, U * U);
-  } else {
-    if (n_one) hipLaunchKernelGGL(b3w_bao_stream_merge_many_kernel, dim3((uint32_t)wg_one), dim3(256), 0, st, d_one, n_one, U);
-    if (n_two) hipLaunchKernelGGL(b3w_bao_stream_merge_many_kernel, dim3(n_two), dim3(256), 0, st, d_two, n_two, U * U);
-  }
-  const hipError_t e = hipGetLastError();
-  many_release(slot, st);
-  if (e != hipSuccess) return hip_fail(ctx, e, "bao stream open_finish_many launch");
+  many_merge(grp, d_one, n_one, (uint32_t)wg_one, d_two, n_two, st);
+  B3W_TRY(many_launched(ctx, slot, st, "bao stream open_finish_many launch"));
   for (uint32_t i = 0; i < n; ++i) {
     b3w_bao_stream *s = sessions[i];
     s->len = lens[i]; s->ob = d_outboards[i]; s->root = d_roots[i];
@@ -3641,181 +3192,61 @@ int32_t b3w_bao_stream_open_finish_many(b3w_ctx *ctx, b3w_bao_stream *const *ses
 
 }  // extern "C"
 
-// ---- updates in place: the host side (b3wit.h "updates in place after writes to resident files") ----------------------------------------
 namespace {
 
-struct UpdRange { uint32_t file; uint64_t first, end; };              // chunks [first, end) of the file
-// a workgroup of the plan: the file, the tile / span within it, its own scratch slot and the slot of its first dirty input item
-struct UpdWg { uint32_t file, idx; uint64_t out, in; uint32_t mask[B3W_TILE / 32]; };
-struct UpdPlan {
-  std::vector<uint32_t> small;                                        // the dirty files of at most 64 chunks, ascending, each once
-  std::vector<UpdWg> tiles, spans, tops;                              // the three storeys, sorted by (file, idx)
-  uint64_t tile_slots = 0, span_slots = 0;                            // scratch: the dirty tiles of files of more than one tile, then the dirty spans past 1 GiB
-};
-
-void mask_set(uint32_t *mask, uint32_t lo, uint32_t hi) {
-  for (uint32_t w = lo >> 5; w <= (hi - 1) >> 5; ++w) {
-    const uint32_t a = w == lo >> 5 ? lo & 31 : 0, b = w == (hi - 1) >> 5 ? ((hi - 1) & 31) + 1 : 32;
-    mask[w] |= (b == 32 ? ~0u : (1u << b) - 1) & ~((1u << a) - 1);
-  }
-}
-
-// the ranges that are not empty, sorted by (file, first chunk), overlapping and adjoining ones of a file merged; ends clamped to the file
-std::vector<UpdRange> update_ranges(const uint64_t *lens, const uint32_t *files, const uint64_t *first, const uint64_t *count, uint32_t n_ranges) {
-  std::vector<UpdRange> v;
-  v.reserve(n_ranges);
-  for (uint32_t i = 0; i < n_ranges; ++i) {
-    const uint64_t n = num_chunks(lens[files[i]]);
-    if (!count[i] || first[i] >= n) continue;
-    v.push_back(UpdRange{files[i], first[i], count[i] < n - first[i] ? first[i] + count[i] : n});
-  }
-  std::sort(v.begin(), v.end(), [](const UpdRange &a, const UpdRange &b) { return a.file != b.file ? a.file < b.file : a.first < b.first; });
-  size_t k = 0;
-  for (size_t i = 0; i < v.size(); ++i) {
-    if (k && v[k - 1].file == v[i].file && v[i].first <= v[k - 1].end) { if (v[i].end > v[k - 1].end) v[k - 1].end = v[i].end; }
-    else v[k++] = v[i];
-  }
-  v.resize(k);
-  return v;
-}
-
-// what a call over these (sorted, merged) ranges launches; the chunk masks are expanded to whole groups of 1 << gl chunks
-UpdPlan update_plan(const uint64_t *lens, const std::vector<UpdRange> &ranges, uint32_t gl) {
-  UpdPlan p;
-  const uint64_t G1 = (1ull << gl) - 1;
-  for (const UpdRange &r : ranges) {
-    const uint64_t n = num_chunks(lens[r.file]);
-    if (n <= 64) {
-      if (p.small.empty() || p.small.back() != r.file) p.small.push_back(r.file);
-      continue;
-    }
-    const uint64_t tiles = (n + B3W_TILE - 1) / B3W_TILE;
-    uint64_t lo = r.first & ~G1, hi = (r.end + G1) & ~G1;
-    if (hi > n) hi = n;
-    for (uint64_t t = lo / B3W_TILE; t * B3W_TILE < hi; ++t) {
-      if (p.tiles.empty() || p.tiles.back().file != r.file || p.tiles.back().idx != t) {
-        UpdWg w{};
-        w.file = r.file; w.idx = (uint32_t)t;
-        w.out = tiles > 1 ? p.tile_slots++ : 0;
-        p.tiles.push_back(w);
-        if (tiles > 1) {                                              // the storey above: the tile is a dirty item of its span
-          const uint32_t s = (uint32_t)(t / B3W_TILE);
-          if (p.spans.empty() || p.spans.back().file != r.file || p.spans.back().idx != s) {
-            UpdWg u{};
-            u.file = r.file; u.idx = s; u.in = w.out;
-            u.out = tiles > B3W_TILE ? p.span_slots++ : 0;
-            p.spans.push_back(u);
-            if (tiles > B3W_TILE) {
-              if (p.tops.empty() || p.tops.back().file != r.file) {
-                UpdWg v{};
-                v.file = r.file; v.in = u.out;
-                p.tops.push_back(v);
-              }
-              mask_set(p.tops.back().mask, s, s + 1);
-            }
-          }
-          mask_set(p.spans.back().mask, (uint32_t)(t % B3W_TILE), (uint32_t)(t % B3W_TILE) + 1);
-        }
-      }
-      const uint64_t t0 = t * B3W_TILE, a = lo > t0 ? lo : t0, b = hi < t0 + B3W_TILE ? hi : t0 + B3W_TILE;
-      mask_set(p.tiles.back().mask, (uint32_t)(a - t0), (uint32_t)(b - t0));
-    }
-  }
-  return p;
-}
-
-int32_t update_refuse(b3w_ctx *ctx, const std::string &why) {
-  ctx->last_error = "bao update: " + why;
-  return B3W_E_BAD_ARGUMENT;
-}
+// ---- the sparse calls (update, ranged verification, resize) and the range slices ------------------------------------------------------
 std::string update_range_text(uint32_t i, uint32_t file, uint64_t first, uint64_t count) {
   return "range " + std::to_string(i) + " (file " + std::to_string(file) + ", chunks " + std::to_string(first) + " + " + std::to_string(count) + ")";
 }
-
-// the sparse walk on the host over the units [first, first + cnt) whose stored node (cnt > 1) is node `pos`: false where no range touches
-// them (nothing read, nothing written), else h = their CV, the dirty halves of the node stored
-bool host_update_walk(const uint8_t *data, uint64_t len, uint64_t n, uint32_t gl, uint8_t *nodes, const std::vector<UpdRange> &units, uint64_t first,
-                      uint64_t cnt, uint64_t pos, bool root, uint32_t h[8]) {
-  // the first range that ends behind `first`: dirty where it starts before first + cnt
-  auto it = std::upper_bound(units.begin(), units.end(), first, [](uint64_t x, const UpdRange &r) { return x < r.end; });
-  if (it == units.end() || it->first >= first + cnt) return false;
-  if (cnt == 1) {
-    const uint64_t c0 = first << gl, gn = n - c0 < (1ull << gl) ? n - c0 : (1ull << gl);
-    host_subtree_cv(data, len, c0, gn, root, h);
-    return true;
+// the update and ranged-verification calls: every range is checked before anything is launched or written
+int32_t sparse_ranges_ok(b3w_ctx *ctx, const char *call, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
+                         uint32_t n_files, const uint64_t *host_ob_first, const uint32_t *host_files, const uint64_t *host_first_chunk, const uint64_t *host_n_chunks,
+                         uint32_t n_ranges, const char *null_arena) {
+  for (uint32_t i = 0; i < n_ranges; ++i) {
+    const uint32_t f = host_files[i];
+    const uint64_t a = host_first_chunk[i], c = host_n_chunks[i];
+    if (f >= n_files) return refuse(ctx, call, update_range_text(i, f, a, c) + ": the file index is not below the file count " + std::to_string(n_files));
+    const uint64_t len = host_lens[f], n = num_chunks(len);
+    if (n > (1ull << 30)) return refuse(ctx, call, update_range_text(i, f, a, c) + ": a file of more than 2^30 chunks");
+    if (a > n || c > n - a) return refuse(ctx, call, update_range_text(i, f, a, c) + " reaches past the file's " + std::to_string(n) + " chunks");
+    if (host_offsets[f] > arena_bytes || len > arena_bytes - host_offsets[f]) return refuse(ctx, call, update_range_text(i, f, a, c) + ": the file reaches past arena_bytes");
+    if (len && !d_arena) return refuse(ctx, call, update_range_text(i, f, a, c) + null_arena);
+    if (host_ob_first[f] & 7) return refuse(ctx, call, update_range_text(i, f, a, c) + ": the file's outboard offset is not a multiple of 8");
   }
-  uint64_t k2 = 1;
-  while (k2 * 2 < cnt) k2 *= 2;
-  uint32_t m[16], ivv[8];
-  uint8_t *node = nodes + 64 * pos;
-  if (host_update_walk(data, len, n, gl, nodes, units, first, k2, pos + 1, false, m)) memcpy(node, m, 32); else memcpy(m, node, 32);
-  if (host_update_walk(data, len, n, gl, nodes, units, first + k2, cnt - k2, pos + k2, false, m + 8)) memcpy(node + 32, m + 8, 32); else memcpy(m + 8, node + 32, 32);
-  iv(ivv);
-  blake3_cv(ivv, m, 0, 0, 64, 4u | (root ? 8u : 0u), h);
-  return true;
+  return B3W_OK;
 }
+// the waves these small files pack into
+SmallPack small_waves(const uint64_t *lens, const std::vector<uint32_t> &files) {
+  SmallPack pack;
+  for (uint32_t f : files) (void)pack.add(num_chunks(lens[f]));
+  return pack;
+}
+std::string resize_entry_text(uint32_t i, uint32_t file) { return "entry " + std::to_string(i) + " (file " + std::to_string(file) + ")"; }
 
 }  // namespace
 
 extern "C" {
 
-uint64_t b3w_bao_update_scratch_bytes(const uint64_t *host_lens, const uint32_t *host_files, const uint64_t *host_first_chunk,
-                                      const uint64_t *host_n_chunks, uint32_t n_ranges) {
-  if (!n_ranges || !host_lens || !host_files || !host_first_chunk || !host_n_chunks) return 0;
-  const UpdPlan p = update_plan(host_lens, update_ranges(host_lens, host_files, host_first_chunk, host_n_chunks, n_ranges), 0);
-  return (p.tile_slots + p.span_slots) * 32;
-}
-
-int32_t b3w_bao_outboard_update(const uint8_t *data, uint64_t len, uint8_t *outboard, uint32_t group_log, const uint64_t *host_first_chunk,
-                                const uint64_t *host_n_chunks, uint32_t n_ranges, uint32_t *root) {
-  if ((!data && len) || !outboard || !root || group_log > B3W_BAO_MAX_GROUP_LOG || (n_ranges && (!host_first_chunk || !host_n_chunks))) return B3W_E_BAD_ARGUMENT;
-  const uint64_t n = num_chunks(len), n_units = (n + ((1ull << group_log) - 1)) >> group_log;
-  for (uint32_t i = 0; i < n_ranges; ++i)
-    if (host_first_chunk[i] > n || host_n_chunks[i] > n - host_first_chunk[i]) return B3W_E_BAD_ARGUMENT;
-  std::vector<uint32_t> zero(n_ranges, 0);
-  std::vector<UpdRange> units = update_ranges(&len, zero.data(), host_first_chunk, host_n_chunks, n_ranges);
-  for (UpdRange &r : units) { r.first >>= group_log; r.end = (r.end + ((1ull << group_log) - 1)) >> group_log; }   // (still sorted; adjoining ones may now overlap: the walk does not mind)
-  for (size_t i = 1; i < units.size(); ++i)
-    if (units[i].end < units[i - 1].end) units[i].end = units[i - 1].end;          // (ends ascending, for the bisection)
-  uint32_t h[8];
-  if (host_update_walk(data, len, n, group_log, outboard + 8, units, 0, n_units, 0, true, h)) memcpy(root, h, 32);
-  return B3W_OK;
-}
-
+// ---- updates in place, ranged verification, appends and truncations (b3wit.h) -----------------------------------------------------------
 int32_t b3w_bao_outboard_update_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets,
                                              const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint64_t *host_ob_first,
                                              uint8_t *d_outboards, uint32_t *d_roots, const uint32_t *host_files, const uint64_t *host_first_chunk,
                                              const uint64_t *host_n_chunks, uint32_t n_ranges, void *d_scratch, uint64_t scratch_bytes, void *stream) {
+  const char *call = "bao update";
   if (!ctx) return B3W_E_BAD_ARGUMENT;
-  if (group_log > B3W_BAO_MAX_GROUP_LOG) return update_refuse(ctx, "group_log is above B3W_BAO_MAX_GROUP_LOG (6)");
+  B3W_TRY(group_log_ok(ctx, call, group_log));
   if (!n_ranges) return B3W_OK;
   if (!host_offsets || !host_lens || !host_ob_first || !d_outboards || !d_roots || !host_files || !host_first_chunk || !host_n_chunks)
-    return update_refuse(ctx, "a null pointer (offsets, lengths, outboard offsets, outboards, roots or a range array)");
-  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_roots & 3)) return update_refuse(ctx, "d_outboards is not 8-byte aligned, or d_roots not 4-byte aligned");
-  for (uint32_t i = 0; i < n_ranges; ++i) {                           // every range is checked before anything is launched or written
-    const uint32_t f = host_files[i];
-    const uint64_t a = host_first_chunk[i], c = host_n_chunks[i];
-    if (f >= n_files) return update_refuse(ctx, update_range_text(i, f, a, c) + ": the file index is not below the file count " + std::to_string(n_files));
-    const uint64_t len = host_lens[f], n = num_chunks(len);
-    if (n > (1ull << 30)) return update_refuse(ctx, update_range_text(i, f, a, c) + ": a file of more than 2^30 chunks");
-    if (a > n || c > n - a) return update_refuse(ctx, update_range_text(i, f, a, c) + " reaches past the file's " + std::to_string(n) + " chunks");
-    if (host_offsets[f] > arena_bytes || len > arena_bytes - host_offsets[f])
-      return update_refuse(ctx, update_range_text(i, f, a, c) + ": the file reaches past arena_bytes");
-    if (len && !d_arena) return update_refuse(ctx, update_range_text(i, f, a, c) + ": a null arena with a dirty file that is not empty");
-    if (host_ob_first[f] & 7) return update_refuse(ctx, update_range_text(i, f, a, c) + ": the file's outboard offset is not a multiple of 8");
-  }
-  const UpdPlan p = update_plan(host_lens, update_ranges(host_lens, host_files, host_first_chunk, host_n_chunks, n_ranges), group_log);
+    return refuse(ctx, call, "a null pointer (offsets, lengths, outboard offsets, outboards, roots or a range array)");
+  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_roots & 3)) return refuse(ctx, call, "d_outboards is not 8-byte aligned, or d_roots not 4-byte aligned");
+  B3W_TRY(sparse_ranges_ok(ctx, call, d_arena, arena_bytes, host_offsets, host_lens, n_files, host_ob_first, host_files, host_first_chunk, host_n_chunks, n_ranges,
+                           ": a null arena with a dirty file that is not empty"));
+  const UpdPlan p = b3w_int_update_plan(host_lens, b3w_int_update_ranges(host_lens, host_files, host_first_chunk, host_n_chunks, n_ranges), group_log);
   const uint64_t need = (p.tile_slots + p.span_slots) * 32;
-  if (scratch_bytes < need) return update_refuse(ctx, "the scratch is smaller than b3w_bao_update_scratch_bytes says (" + std::to_string(need) + " bytes)");
-  if (need && (!d_scratch || ((uintptr_t)d_scratch & 15))) return update_refuse(ctx, "the scratch is null or not 16-byte aligned");
-  if (p.tiles.size() > 0x7fffffffull) return update_refuse(ctx, "more than 2^31 - 1 dirty tiles in one call");
-  // the small files' waves, as the batch call packs them
-  uint64_t waves = 0, fill = 64;
-  for (uint32_t f : p.small) {
-    const uint64_t n = num_chunks(host_lens[f]);
-    if (fill + n > 64) { waves++; fill = 0; }
-    fill += n;
-  }
+  if (scratch_bytes < need) return refuse(ctx, call, "the scratch is smaller than b3w_bao_update_scratch_bytes says (" + std::to_string(need) + " bytes)");
+  if (need && (!d_scratch || ((uintptr_t)d_scratch & 15))) return refuse(ctx, call, "the scratch is null or not 16-byte aligned");
+  if (p.tiles.size() > 0x7fffffffull) return refuse(ctx, call, "more than 2^31 - 1 dirty tiles in one call");
+  const uint64_t waves = small_waves(host_lens, p.small).waves;        // the small files' waves, as the batch call packs them
   if (p.small.empty() && p.tiles.empty()) return B3W_OK;              // (every range was empty)
   // one table: tile rows | span rows | top rows | the small files' entries | their waves' first files
   const uint64_t n_rows = p.tiles.size() + p.spans.size() + p.tops.size();
@@ -3823,8 +3254,7 @@ int32_t b3w_bao_outboard_update_batch_device(b3w_ctx *ctx, const uint8_t *d_aren
   ON_DEVICE(ctx);
   hipStream_t st = (hipStream_t)stream;
   b3w_ctx::ManySlot *slot = nullptr;
-  const int32_t rc = many_staging(ctx, bytes, &slot);
-  if (rc) return rc;
+  B3W_TRY(many_staging(ctx, bytes, &slot));
   uint32_t *scratch = reinterpret_cast<uint32_t *>(d_scratch), *span_cv = scratch + p.tile_slots * 8;
   UpdRow *h_rows = reinterpret_cast<UpdRow *>(slot->h);
   BatchEnt *h_small = reinterpret_cast<BatchEnt *>(h_rows + n_rows);
@@ -3841,119 +3271,27 @@ int32_t b3w_bao_outboard_update_batch_device(b3w_ctx *ctx, const uint8_t *d_aren
   for (const UpdWg &w : p.tiles) *at++ = row(w, nullptr, scratch + w.out * 8);
   for (const UpdWg &w : p.spans) *at++ = row(w, scratch + w.in * 8, span_cv + w.out * 8);
   for (const UpdWg &w : p.tops) *at++ = row(w, span_cv + w.in * 8, nullptr);
-  uint32_t i_small = 0, i_waves = 0;
-  fill = 64;
+  SmallPack pack;
+  pack.first = h_waves;
   for (uint32_t f : p.small) {
-    const uint64_t n = num_chunks(host_lens[f]);
-    if (fill + n > 64) { h_waves[i_waves++] = i_small; fill = 0; }
-    h_small[i_small++] = BatchEnt{host_offsets[f], host_lens[f], host_ob_first[f], (uint32_t)fill, f};
-    fill += n;
+    const uint32_t lane = pack.add(num_chunks(host_lens[f]));
+    h_small[pack.files - 1] = BatchEnt{host_offsets[f], host_lens[f], host_ob_first[f], lane, f};
   }
-  if (i_small) h_waves[i_waves] = i_small;
+  pack.close();
   const hipError_t ec = hipMemcpyAsync(slot->d, slot->h, (size_t)bytes, hipMemcpyHostToDevice, st);
   if (ec != hipSuccess) return hip_fail(ctx, ec, "bao update: table upload");
   const UpdRow *d_tiles = reinterpret_cast<const UpdRow *>(slot->d), *d_spans = d_tiles + p.tiles.size(), *d_tops = d_spans + p.spans.size();
   const BatchEnt *d_small = reinterpret_cast<const BatchEnt *>(d_tops + p.tops.size());
   const uint32_t *d_waves = reinterpret_cast<const uint32_t *>(d_small + p.small.size());
   const uint64_t U = B3W_TILE;
-  if (group_log) {
-    if (i_small) hipLaunchKernelGGL(b3w_bao_small_group_kernel, dim3((uint32_t)waves), dim3(64), 0, st, d_arena, d_small, d_waves, d_outboards, d_roots, group_log);
-    if (!p.tiles.empty()) hipLaunchKernelGGL(b3w_bao_update_tile_group_kernel, dim3((uint32_t)p.tiles.size()), dim3(B3W_TILE), 0, st, d_tiles);
-    if (!p.spans.empty()) hipLaunchKernelGGL(b3w_bao_update_merge_group_kernel, dim3((uint32_t)p.spans.size()), dim3(256), 0, st, d_spans, U);
-    if (!p.tops.empty()) hipLaunchKernelGGL(b3w_bao_update_merge_group_kernel, dim3((uint32_t)p.tops.size()), dim3(256), 0, st, d_tops, U * U);
-  } else {
-    if (i_small) hipLaunchKernelGGL(b3w_bao_small_kernel, dim3((uint32_t)waves), dim3(64), 0, st, d_arena, d_small, d_waves, d_outboards, d_roots);
-    if (!p.tiles.empty()) hipLaunchKernelGGL(b3w_bao_update_tile_kernel, dim3((uint32_t)p.tiles.size()), dim3(B3W_TILE), 0, st, d_tiles);
-    if (!p.spans.empty()) hipLaunchKernelGGL(b3w_bao_update_merge_kernel, dim3((uint32_t)p.spans.size()), dim3(256), 0, st, d_spans, U);
-    if (!p.tops.empty()) hipLaunchKernelGGL(b3w_bao_update_merge_kernel, dim3((uint32_t)p.tops.size()), dim3(256), 0, st, d_tops, U * U);
-  }
-  const hipError_t e = hipGetLastError();
-  many_release(slot, st);
-  if (e != hipSuccess) return hip_fail(ctx, e, "bao update launch");
-  return B3W_OK;
-}
-
-}  // extern "C"
-
-// ---- ranged verification: the host side (b3wit.h "verification of listed chunk ranges of resident files") --------------------------------
-namespace {
-
-int32_t ranges_refuse(b3w_ctx *ctx, const std::string &why) {
-  ctx->last_error = "bao verify ranges: " + why;
-  return B3W_E_BAD_ARGUMENT;
-}
-
-// host_verify_walk over the listed units alone (`units`: sorted unit ranges with ascending ends): a subtree that no range touches is
-// neither read nor written
-void host_ranges_walk(const uint8_t *data, uint64_t len, uint64_t n, uint32_t gl, const uint8_t *nodes, const std::vector<UpdRange> &units, uint64_t first,
-                      uint64_t cnt, uint64_t pos, const uint32_t want[8], bool bad, bool root, uint8_t *status) {
-  auto it = std::upper_bound(units.begin(), units.end(), first, [](uint64_t x, const UpdRange &r) { return x < r.end; });
-  if (it == units.end() || it->first >= first + cnt) return;
-  if (cnt == 1) {
-    const uint64_t c0 = first << gl, gn = n - c0 < (1ull << gl) ? n - c0 : (1ull << gl);
-    uint32_t h[8];
-    host_subtree_cv(data, len, c0, gn, root, h);
-    status[first] = bad ? 2 : memcmp(h, want, 32) != 0 ? 1 : 0;
-    return;
-  }
-  uint32_t mw[16], ivv[8], o[8];
-  for (int k = 0; k < 16; ++k) {
-    const uint8_t *b = nodes + 64 * pos + 4 * k;
-    mw[k] = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
-  }
-  iv(ivv);
-  blake3_cv(ivv, mw, 0, 0, 64, 4u | (root ? 8u : 0u), o);
-  if (memcmp(o, want, 32) != 0) bad = true;
-  uint64_t k2 = 1;
-  while (k2 * 2 < cnt) k2 *= 2;
-  host_ranges_walk(data, len, n, gl, nodes, units, first, k2, pos + 1, mw, bad, false, status);
-  host_ranges_walk(data, len, n, gl, nodes, units, first + k2, cnt - k2, pos + k2, mw + 8, bad, false, status);
-}
-
-}  // namespace
-
-extern "C" {
-
-uint64_t b3w_bao_verify_ranges_scratch_bytes(const uint64_t *host_lens, const uint32_t *host_files, const uint64_t *host_first_chunk,
-                                             const uint64_t *host_n_chunks, uint32_t n_ranges) {
-  if (!n_ranges || !host_lens || !host_files || !host_first_chunk || !host_n_chunks) return 0;
-  const UpdPlan p = update_plan(host_lens, update_ranges(host_lens, host_files, host_first_chunk, host_n_chunks, n_ranges), 0);
-  return ((p.tile_slots + p.span_slots) * 36 + 15) & ~15ull;          // the expected CV (32) and the word (4) of every entry
-}
-
-int32_t b3w_bao_verify_ranges(const uint8_t *data, uint64_t len, const uint8_t *outboard, uint32_t group_log, const uint32_t *root,
-                              const uint64_t *host_first_chunk, const uint64_t *host_n_chunks, uint32_t n_ranges, uint8_t *unit_status,
-                              int32_t *range_status, uint64_t *range_first_bad) {
-  if ((!data && len) || !outboard || !root || !unit_status || group_log > B3W_BAO_MAX_GROUP_LOG || (n_ranges && (!host_first_chunk || !host_n_chunks)))
-    return B3W_E_BAD_ARGUMENT;
-  const uint64_t n = num_chunks(len), G1 = (1ull << group_log) - 1, n_units = (n + G1) >> group_log;
-  for (uint32_t i = 0; i < n_ranges; ++i)
-    if (host_first_chunk[i] > n || host_n_chunks[i] > n - host_first_chunk[i]) return B3W_E_BAD_ARGUMENT;
-  std::vector<uint32_t> zero(n_ranges, 0);
-  std::vector<UpdRange> units = update_ranges(&len, zero.data(), host_first_chunk, host_n_chunks, n_ranges);
-  for (UpdRange &r : units) { r.first >>= group_log; r.end = (r.end + G1) >> group_log; }   // (still sorted; adjoining ones may now overlap)
-  for (size_t i = 1; i < units.size(); ++i)
-    if (units[i].end < units[i - 1].end) units[i].end = units[i - 1].end;          // (ends ascending, for the bisection)
-  uint64_t hdr = 0;
-  if (!units.empty())                                                 // (read once, and only where something is listed)
-    for (int k = 0; k < 8; ++k) hdr |= (uint64_t)outboard[k] << (8 * k);
-  if (!units.empty() && hdr != len) {
-    for (const UpdRange &r : units) memset(unit_status + r.first, 3, (size_t)(r.end - r.first));
-  } else {
-    host_ranges_walk(data, len, n, group_log, outboard + 8, units, 0, n_units, 0, root, false, true, unit_status);
-  }
-  for (uint32_t i = 0; i < n_ranges; ++i) {
-    int32_t worst = 0;
-    uint64_t first = ~0ull;
-    if (host_n_chunks[i])
-      for (uint64_t u = host_first_chunk[i] >> group_log; u <= (host_first_chunk[i] + host_n_chunks[i] - 1) >> group_log; ++u) {
-        if (unit_status[u] > worst) worst = unit_status[u];
-        if (unit_status[u] && first == ~0ull) first = u;
-      }
-    if (range_status) range_status[i] = worst;
-    if (range_first_bad) range_first_bad[i] = first;
-  }
-  return B3W_OK;
+  const bool grp = group_log != 0;
+  const auto tile_kernel = grp ? b3w_bao_update_tile_group_kernel : b3w_bao_update_tile_kernel;
+  const auto merge_kernel = grp ? b3w_bao_update_merge_group_kernel : b3w_bao_update_merge_kernel;
+  if (pack.files) launch_pair(grp, b3w_bao_small_kernel, b3w_bao_small_group_kernel, group_log, dim3((uint32_t)waves), dim3(64), st, d_arena, d_small, d_waves, d_outboards, d_roots);
+  if (!p.tiles.empty()) hipLaunchKernelGGL(tile_kernel, dim3((uint32_t)p.tiles.size()), dim3(B3W_TILE), 0, st, d_tiles);
+  if (!p.spans.empty()) hipLaunchKernelGGL(merge_kernel, dim3((uint32_t)p.spans.size()), dim3(256), 0, st, d_spans, U);
+  if (!p.tops.empty()) hipLaunchKernelGGL(merge_kernel, dim3((uint32_t)p.tops.size()), dim3(256), 0, st, d_tops, U * U);
+  return many_launched(ctx, slot, st, "bao update launch");
 }
 
 int32_t b3w_bao_verify_ranges_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets,
@@ -3962,48 +3300,32 @@ int32_t b3w_bao_verify_ranges_batch_device(b3w_ctx *ctx, const uint8_t *d_arena,
                                            const uint64_t *host_first_chunk, const uint64_t *host_n_chunks, uint32_t n_ranges,
                                            const uint64_t *host_unit_first, uint8_t *d_unit_status, int32_t *d_range_status,
                                            uint64_t *d_range_first_bad, void *d_scratch, uint64_t scratch_bytes, void *stream) {
+  const char *call = "bao verify ranges";
   if (!ctx) return B3W_E_BAD_ARGUMENT;
-  if (group_log > B3W_BAO_MAX_GROUP_LOG) return ranges_refuse(ctx, "group_log is above B3W_BAO_MAX_GROUP_LOG (6)");
+  B3W_TRY(group_log_ok(ctx, call, group_log));
   if (!n_ranges) return B3W_OK;
   if (!host_offsets || !host_lens || !host_ob_first || !d_outboards || !d_roots || !host_files || !host_first_chunk || !host_n_chunks || !host_unit_first)
-    return ranges_refuse(ctx, "a null pointer (offsets, lengths, outboard offsets, unit offsets, outboards, roots or a range array)");
-  if (!d_unit_status || !d_range_status || !d_range_first_bad) return ranges_refuse(ctx, "a null output pointer (unit statuses, range statuses or first bad units)");
-  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_roots & 3)) return ranges_refuse(ctx, "d_outboards is not 8-byte aligned, or d_roots not 4-byte aligned");
+    return refuse(ctx, call, "a null pointer (offsets, lengths, outboard offsets, unit offsets, outboards, roots or a range array)");
+  if (!d_unit_status || !d_range_status || !d_range_first_bad) return refuse(ctx, call, "a null output pointer (unit statuses, range statuses or first bad units)");
+  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_roots & 3)) return refuse(ctx, call, "d_outboards is not 8-byte aligned, or d_roots not 4-byte aligned");
   if (((uintptr_t)d_range_first_bad & 7) || ((uintptr_t)d_range_status & 3))
-    return ranges_refuse(ctx, "d_range_first_bad is not 8-byte aligned, or d_range_status not 4-byte aligned");
-  if (n_ranges > 0x7fffffffu) return ranges_refuse(ctx, "more than 2^31 - 1 ranges in one call");
-  for (uint32_t i = 0; i < n_ranges; ++i) {                           // every range is checked before anything is launched or written
-    const uint32_t f = host_files[i];
-    const uint64_t a = host_first_chunk[i], c = host_n_chunks[i];
-    if (f >= n_files) return ranges_refuse(ctx, update_range_text(i, f, a, c) + ": the file index is not below the file count " + std::to_string(n_files));
-    const uint64_t len = host_lens[f], n = num_chunks(len);
-    if (n > (1ull << 30)) return ranges_refuse(ctx, update_range_text(i, f, a, c) + ": a file of more than 2^30 chunks");
-    if (a > n || c > n - a) return ranges_refuse(ctx, update_range_text(i, f, a, c) + " reaches past the file's " + std::to_string(n) + " chunks");
-    if (host_offsets[f] > arena_bytes || len > arena_bytes - host_offsets[f])
-      return ranges_refuse(ctx, update_range_text(i, f, a, c) + ": the file reaches past arena_bytes");
-    if (len && !d_arena) return ranges_refuse(ctx, update_range_text(i, f, a, c) + ": a null arena with a listed file that is not empty");
-    if (host_ob_first[f] & 7) return ranges_refuse(ctx, update_range_text(i, f, a, c) + ": the file's outboard offset is not a multiple of 8");
-  }
-  const UpdPlan p = update_plan(host_lens, update_ranges(host_lens, host_files, host_first_chunk, host_n_chunks, n_ranges), group_log);
+    return refuse(ctx, call, "d_range_first_bad is not 8-byte aligned, or d_range_status not 4-byte aligned");
+  if (n_ranges > 0x7fffffffu) return refuse(ctx, call, "more than 2^31 - 1 ranges in one call");
+  B3W_TRY(sparse_ranges_ok(ctx, call, d_arena, arena_bytes, host_offsets, host_lens, n_files, host_ob_first, host_files, host_first_chunk, host_n_chunks, n_ranges,
+                           ": a null arena with a listed file that is not empty"));
+  const UpdPlan p = b3w_int_update_plan(host_lens, b3w_int_update_ranges(host_lens, host_files, host_first_chunk, host_n_chunks, n_ranges), group_log);
   const uint64_t n_scr = p.tile_slots + p.span_slots, need = (n_scr * 36 + 15) & ~15ull;
-  if (scratch_bytes < need) return ranges_refuse(ctx, "the scratch is smaller than b3w_bao_verify_ranges_scratch_bytes says (" + std::to_string(need) + " bytes)");
-  if (need && (!d_scratch || ((uintptr_t)d_scratch & 15))) return ranges_refuse(ctx, "the scratch is null or not 16-byte aligned");
-  if (p.tiles.size() > 0x7fffffffull) return ranges_refuse(ctx, "more than 2^31 - 1 listed tiles in one call");
-  // the small files' waves, as the batch call packs them
-  uint64_t waves = 0, fill = 64;
-  for (uint32_t f : p.small) {
-    const uint64_t n = num_chunks(host_lens[f]);
-    if (fill + n > 64) { waves++; fill = 0; }
-    fill += n;
-  }
+  if (scratch_bytes < need) return refuse(ctx, call, "the scratch is smaller than b3w_bao_verify_ranges_scratch_bytes says (" + std::to_string(need) + " bytes)");
+  if (need && (!d_scratch || ((uintptr_t)d_scratch & 15))) return refuse(ctx, call, "the scratch is null or not 16-byte aligned");
+  if (p.tiles.size() > 0x7fffffffull) return refuse(ctx, call, "more than 2^31 - 1 listed tiles in one call");
+  const uint64_t waves = small_waves(host_lens, p.small).waves;        // the small files' waves, as the batch call packs them
   // one table: tile rows | span rows | top rows | the ranges as given | the small files' rows | their waves' first files
   const uint64_t n_rows = p.tiles.size() + p.spans.size() + p.tops.size();
   const uint64_t bytes = n_rows * sizeof(VrRow) + (uint64_t)n_ranges * sizeof(VrRange) + p.small.size() * sizeof(VrSmall) + (p.small.empty() ? 0 : (waves + 1) * 4);
   ON_DEVICE(ctx);
   hipStream_t st = (hipStream_t)stream;
   b3w_ctx::ManySlot *slot = nullptr;
-  const int32_t rc = many_staging(ctx, bytes, &slot);
-  if (rc) return rc;
+  B3W_TRY(many_staging(ctx, bytes, &slot));
   // scratch: the expected CVs of the listed tiles, then of the listed spans, then their words in the same order
   uint32_t *tile_cv = reinterpret_cast<uint32_t *>(d_scratch), *span_cv = tile_cv + p.tile_slots * 8, *tile_word = tile_cv + n_scr * 8,
            *span_word = tile_word + p.tile_slots;
@@ -4032,16 +3354,13 @@ int32_t b3w_bao_verify_ranges_batch_device(b3w_ctx *ctx, const uint8_t *d_arena,
     const uint64_t a = host_first_chunk[i], c = host_n_chunks[i];
     h_ranges[i] = VrRange{d_unit_status + host_unit_first[host_files[i]], a >> group_log, c ? ((a + c - 1) >> group_log) - (a >> group_log) + 1 : 0};
   }
-  uint32_t i_small = 0, i_waves = 0;
-  fill = 64;
+  SmallPack pack;
+  pack.first = h_waves;
   for (uint32_t f : p.small) {
-    const uint64_t n = num_chunks(host_lens[f]);
-    if (fill + n > 64) { h_waves[i_waves++] = i_small; fill = 0; }
-    h_small[i_small++] = VrSmall{host_offsets[f], host_lens[f], d_outboards + host_ob_first[f], d_roots + (uint64_t)f * 8, d_unit_status + host_unit_first[f],
-                                 (uint32_t)fill, 0};
-    fill += n;
+    const uint32_t lane = pack.add(num_chunks(host_lens[f]));
+    h_small[pack.files - 1] = VrSmall{host_offsets[f], host_lens[f], d_outboards + host_ob_first[f], d_roots + (uint64_t)f * 8, d_unit_status + host_unit_first[f], lane, 0};
   }
-  if (i_small) h_waves[i_waves] = i_small;
+  pack.close();
   const hipError_t ec = hipMemcpyAsync(slot->d, slot->h, (size_t)bytes, hipMemcpyHostToDevice, st);
   if (ec != hipSuccess) return hip_fail(ctx, ec, "bao verify ranges: table upload");
   const VrRow *d_tiles = reinterpret_cast<const VrRow *>(slot->d), *d_spans = d_tiles + p.tiles.size(), *d_tops = d_spans + p.spans.size();
@@ -4050,95 +3369,13 @@ int32_t b3w_bao_verify_ranges_batch_device(b3w_ctx *ctx, const uint8_t *d_arena,
   const uint32_t *d_waves = reinterpret_cast<const uint32_t *>(d_small + p.small.size());
   const uint64_t U = B3W_TILE;
   // top down: the storeys above the tiles first (stored nodes alone), then the kernels that read the files, then the ranges' reduction
-  if (i_small) hipLaunchKernelGGL(b3w_bao_verify_ranges_small_kernel, dim3((uint32_t)waves), dim3(64), 0, st, d_arena, d_small, d_waves, group_log);
+  if (pack.files) hipLaunchKernelGGL(b3w_bao_verify_ranges_small_kernel, dim3((uint32_t)waves), dim3(64), 0, st, d_arena, d_small, d_waves, group_log);
   if (!p.tops.empty()) hipLaunchKernelGGL(b3w_bao_verify_ranges_upper_kernel, dim3((uint32_t)p.tops.size()), dim3(256), 0, st, d_tops, U * U);
   if (!p.spans.empty()) hipLaunchKernelGGL(b3w_bao_verify_ranges_upper_kernel, dim3((uint32_t)p.spans.size()), dim3(256), 0, st, d_spans, U);
   if (!p.tiles.empty()) hipLaunchKernelGGL(b3w_bao_verify_ranges_tile_kernel, dim3((uint32_t)p.tiles.size()), dim3(B3W_TILE), 0, st, d_tiles);
   hipLaunchKernelGGL(b3w_bao_verify_ranges_reduce_kernel, dim3(n_ranges), dim3(256), 0, st, d_ranges, d_range_status,
                      reinterpret_cast<unsigned long long *>(d_range_first_bad));
-  const hipError_t e = hipGetLastError();
-  many_release(slot, st);
-  if (e != hipSuccess) return hip_fail(ctx, e, "bao verify ranges launch");
-  return B3W_OK;
-}
-
-}  // extern "C"
-
-// ---- resident files after appends and truncations: the host side (b3wit.h "resident files after appends and truncations") ----------------
-namespace {
-
-constexpr uint64_t RES_TB = (uint64_t)B3W_TILE * 1024;                // a tile's bytes
-
-uint64_t resize_tiles(uint64_t len) { return (num_chunks(len) + B3W_TILE - 1) / B3W_TILE; }
-// scratch slots of a listed file at its new length: its tiles' CVs, then its spans' past 1 GiB; none for a file of one tile
-uint64_t resize_slots(uint64_t new_len) {
-  const uint64_t tiles = resize_tiles(new_len);
-  return tiles > 1 ? tiles + (tiles > B3W_TILE ? (tiles + B3W_TILE - 1) / B3W_TILE : 0) : 0;
-}
-
-int32_t resize_refuse(b3w_ctx *ctx, const std::string &why) {
-  ctx->last_error = "bao resize: " + why;
-  return B3W_E_BAD_ARGUMENT;
-}
-std::string resize_entry_text(uint32_t i, uint32_t file) { return "entry " + std::to_string(i) + " (file " + std::to_string(file) + ")"; }
-
-// the walk on the host over the units [first, first + cnt) of the file at its new length, whose stored node (cnt > 1) is node `pos`: a
-// kept tile's block is copied from the old outboard and its CV taken from the block's first node; everything else is hashed
-void host_resize_walk(const uint8_t *data, uint64_t len, uint64_t n, uint32_t gl, const uint8_t *old_nodes, uint64_t old_units, uint64_t kept,
-                      uint8_t *nodes, uint64_t first, uint64_t cnt, uint64_t pos, bool root, uint32_t h[8]) {
-  const uint32_t sh = 10 - gl;
-  uint32_t m[16], ivv[8];
-  if (cnt == (1ull << sh) && !(first & (cnt - 1)) && (first >> sh) < kept) {
-    const uint8_t *src = old_nodes + 64 * preorder_pos(old_units, first, cnt);
-    memcpy(nodes + 64 * pos, src, (size_t)(cnt - 1) * 64);
-    memcpy(m, src, 64);
-    iv(ivv);
-    blake3_cv(ivv, m, 0, 0, 64, 4u | (root ? 8u : 0u), h);
-    return;
-  }
-  if (cnt == 1) {
-    const uint64_t c0 = first << gl, gn = n - c0 < (1ull << gl) ? n - c0 : (1ull << gl);
-    host_subtree_cv(data, len, c0, gn, root, h);
-    return;
-  }
-  uint64_t k2 = 1;
-  while (k2 * 2 < cnt) k2 *= 2;
-  host_resize_walk(data, len, n, gl, old_nodes, old_units, kept, nodes, first, k2, pos + 1, false, m);
-  host_resize_walk(data, len, n, gl, old_nodes, old_units, kept, nodes, first + k2, cnt - k2, pos + k2, false, m + 8);
-  memcpy(nodes + 64 * pos, m, 64);
-  iv(ivv);
-  blake3_cv(ivv, m, 0, 0, 64, 4u | (root ? 8u : 0u), h);
-}
-
-}  // namespace
-
-extern "C" {
-
-uint64_t b3w_bao_resize_kept_tiles(uint64_t old_len, uint64_t new_len) { return (old_len < new_len ? old_len : new_len) / RES_TB; }
-
-uint64_t b3w_bao_resize_scratch_bytes(const uint64_t *host_new_lens, const uint32_t *host_files, uint32_t n_resized) {
-  if (!n_resized || !host_new_lens || !host_files) return 0;
-  uint64_t slots = 0;
-  for (uint32_t i = 0; i < n_resized; ++i) slots += resize_slots(host_new_lens[host_files[i]]);
-  return slots * 32;
-}
-
-int32_t b3w_bao_outboard_resize(const uint8_t *data, uint64_t new_len, const uint8_t *old_outboard, uint64_t old_len, uint32_t group_log,
-                                uint8_t *new_outboard, uint32_t *root) {
-  if (!old_outboard || !new_outboard || !root || group_log > B3W_BAO_MAX_GROUP_LOG) return B3W_E_BAD_ARGUMENT;
-  const uint64_t kept = b3w_bao_resize_kept_tiles(old_len, new_len);
-  if (!data && new_len > kept * RES_TB) return B3W_E_BAD_ARGUMENT;
-  if (num_chunks(old_len) > (1ull << 30) || num_chunks(new_len) > (1ull << 30)) return B3W_E_BAD_ARGUMENT;
-  const uintptr_t a0 = (uintptr_t)old_outboard, a1 = a0 + b3w_bao_group_outboard_size(old_len, group_log);
-  const uintptr_t b0 = (uintptr_t)new_outboard, b1 = b0 + b3w_bao_group_outboard_size(new_len, group_log);
-  if (a0 < b1 && b0 < a1) return B3W_E_BAD_ARGUMENT;
-  const uint64_t G1 = (1ull << group_log) - 1, n = num_chunks(new_len);
-  uint32_t h[8];
-  host_resize_walk(data, new_len, n, group_log, old_outboard + 8, (num_chunks(old_len) + G1) >> group_log, kept, new_outboard + 8, 0, (n + G1) >> group_log,
-                   0, true, h);
-  for (int k = 0; k < 8; ++k) new_outboard[k] = (uint8_t)(new_len >> (8 * k));
-  memcpy(root, h, 32);
-  return B3W_OK;
+  return many_launched(ctx, slot, st, "bao verify ranges launch");
 }
 
 // At most five launches: one table through the staging ring in runs of rows, each run the rows of one grid (the tiles behind the kept
@@ -4149,41 +3386,39 @@ int32_t b3w_bao_outboard_resize_batch_device(b3w_ctx *ctx, const uint8_t *d_aren
                                              const uint64_t *host_old_ob_first, const uint8_t *d_old_outboards, const uint64_t *host_new_ob_first,
                                              uint8_t *d_new_outboards, uint32_t *d_roots, const uint32_t *host_files, uint32_t n_resized, void *d_scratch,
                                              uint64_t scratch_bytes, void *stream) {
+  const char *call = "bao resize";
   if (!ctx) return B3W_E_BAD_ARGUMENT;
-  if (group_log > B3W_BAO_MAX_GROUP_LOG) return resize_refuse(ctx, "group_log is above B3W_BAO_MAX_GROUP_LOG (6)");
+  B3W_TRY(group_log_ok(ctx, call, group_log));
   if (!n_resized) return B3W_OK;
   if (!host_offsets || !host_old_lens || !host_new_lens || !host_old_ob_first || !d_old_outboards || !host_new_ob_first || !d_new_outboards || !d_roots || !host_files)
-    return resize_refuse(ctx, "a null pointer (offsets, lengths, outboard offsets, outboards, roots or the file list)");
+    return refuse(ctx, call, "a null pointer (offsets, lengths, outboard offsets, outboards, roots or the file list)");
   if (((uintptr_t)d_old_outboards & 7) || ((uintptr_t)d_new_outboards & 7) || ((uintptr_t)d_roots & 3))
-    return resize_refuse(ctx, "d_old_outboards or d_new_outboards is not 8-byte aligned, or d_roots not 4-byte aligned");
+    return refuse(ctx, call, "d_old_outboards or d_new_outboards is not 8-byte aligned, or d_roots not 4-byte aligned");
   const uint64_t LIMIT = 0x7fffffffull;
-  const OpenShape sh = open_shape(group_log);
-  uint64_t n_small = 0, waves = 0, fill = 64, n_tile = 0, wg_tile = 0, n_move = 0, wg_move = 0, n_one = 0, wg_one = 0, n_two = 0, need = 0;
+  SmallPack count;
+  uint64_t n_tile = 0, wg_tile = 0, n_move = 0, wg_move = 0, n_one = 0, wg_one = 0, n_two = 0, need = 0;
   for (uint32_t i = 0; i < n_resized; ++i) {                          // every entry is checked before anything is launched or written
     const uint32_t f = host_files[i];
-    if (f >= n_files) return resize_refuse(ctx, resize_entry_text(i, f) + ": the file index is not below the file count " + std::to_string(n_files));
+    if (f >= n_files) return refuse(ctx, call, resize_entry_text(i, f) + ": the file index is not below the file count " + std::to_string(n_files));
     const uint64_t old_len = host_old_lens[f], len = host_new_lens[f], n = num_chunks(len);
-    if (n > (1ull << 30) || num_chunks(old_len) > (1ull << 30)) return resize_refuse(ctx, resize_entry_text(i, f) + ": a file of more than 2^30 chunks at its old or new length");
-    if (host_offsets[f] > arena_bytes || len > arena_bytes - host_offsets[f]) return resize_refuse(ctx, resize_entry_text(i, f) + ": the file reaches past arena_bytes at its new length");
-    const uint64_t kept = b3w_bao_resize_kept_tiles(old_len, len), tiles = resize_tiles(len);
-    if (len > kept * RES_TB && !d_arena) return resize_refuse(ctx, resize_entry_text(i, f) + ": a null arena with a file whose bytes have to be read");
-    if ((host_old_ob_first[f] & 7) || (host_new_ob_first[f] & 7)) return resize_refuse(ctx, resize_entry_text(i, f) + ": an outboard offset of the file is not a multiple of 8");
-    const uintptr_t a0 = (uintptr_t)d_old_outboards + host_old_ob_first[f], a1 = a0 + b3w_bao_group_outboard_size(old_len, group_log);
-    const uintptr_t b0 = (uintptr_t)d_new_outboards + host_new_ob_first[f], b1 = b0 + b3w_bao_group_outboard_size(len, group_log);
-    if (a0 < b1 && b0 < a1) return resize_refuse(ctx, resize_entry_text(i, f) + ": the file's old and new outboards overlap");
+    if (n > (1ull << 30) || num_chunks(old_len) > (1ull << 30)) return refuse(ctx, call, resize_entry_text(i, f) + ": a file of more than 2^30 chunks at its old or new length");
+    if (host_offsets[f] > arena_bytes || len > arena_bytes - host_offsets[f]) return refuse(ctx, call, resize_entry_text(i, f) + ": the file reaches past arena_bytes at its new length");
+    const uint64_t kept = b3w_bao_resize_kept_tiles(old_len, len), tiles = tiles_of(len);
+    if (len > kept * RES_TB && !d_arena) return refuse(ctx, call, resize_entry_text(i, f) + ": a null arena with a file whose bytes have to be read");
+    if ((host_old_ob_first[f] & 7) || (host_new_ob_first[f] & 7)) return refuse(ctx, call, resize_entry_text(i, f) + ": an outboard offset of the file is not a multiple of 8");
+    const uintptr_t a0 = (uintptr_t)d_old_outboards + host_old_ob_first[f], a1 = a0 + group_outboard_bytes(old_len, group_log);
+    const uintptr_t b0 = (uintptr_t)d_new_outboards + host_new_ob_first[f], b1 = b0 + group_outboard_bytes(len, group_log);
+    if (a0 < b1 && b0 < a1) return refuse(ctx, call, resize_entry_text(i, f) + ": the file's old and new outboards overlap");
     need += resize_slots(len) * 32;
-    if (n <= 64) {
-      if (fill + n > 64) { waves++; fill = 0; }
-      fill += n;
-      n_small++;
-    } else {
+    if (n <= 64) (void)count.add(n);
+    else {
       if (tiles > kept) { n_tile++; wg_tile += tiles - kept; }
-      if (kept) { n_move++; wg_move += ((kept + (1ull << sh.tpw_log) - 1) >> sh.tpw_log) * sh.ppb; }
+      if (kept) { n_move++; wg_move += open_move_wgs(kept, group_log); }
       if (tiles > 1) { n_one++; wg_one += (tiles + B3W_TILE - 1) / B3W_TILE; }
       if (tiles > B3W_TILE) n_two++;
     }
-    if (waves > LIMIT || wg_tile > LIMIT || wg_move > LIMIT || wg_one > LIMIT || n_two > LIMIT)
-      return resize_refuse(ctx, resize_entry_text(i, f) + ": with this entry one of the call's five grids has more than 2^31 - 1 workgroups");
+    if (count.waves > LIMIT || wg_tile > LIMIT || wg_move > LIMIT || wg_one > LIMIT || n_two > LIMIT)
+      return refuse(ctx, call, resize_entry_text(i, f) + ": with this entry one of the call's five grids has more than 2^31 - 1 workgroups");
   }
   {
     std::vector<std::pair<uint32_t, uint32_t>> by_file(n_resized);
@@ -4191,34 +3426,34 @@ int32_t b3w_bao_outboard_resize_batch_device(b3w_ctx *ctx, const uint8_t *d_aren
     std::sort(by_file.begin(), by_file.end());
     for (uint32_t k = 1; k < n_resized; ++k)
       if (by_file[k - 1].first == by_file[k].first)
-        return resize_refuse(ctx, resize_entry_text(by_file[k].second, by_file[k].first) + ": the file is listed twice (entry " + std::to_string(by_file[k - 1].second) + " is the same)");
+        return refuse(ctx, call, resize_entry_text(by_file[k].second, by_file[k].first) + ": the file is listed twice (entry " + std::to_string(by_file[k - 1].second) + " is the same)");
   }
-  if (scratch_bytes < need) return resize_refuse(ctx, "the scratch is smaller than b3w_bao_resize_scratch_bytes says (" + std::to_string(need) + " bytes)");
-  if (need && (!d_scratch || ((uintptr_t)d_scratch & 15))) return resize_refuse(ctx, "the scratch is null or not 16-byte aligned");
+  if (scratch_bytes < need) return refuse(ctx, call, "the scratch is smaller than b3w_bao_resize_scratch_bytes says (" + std::to_string(need) + " bytes)");
+  if (need && (!d_scratch || ((uintptr_t)d_scratch & 15))) return refuse(ctx, call, "the scratch is null or not 16-byte aligned");
   // one table: tile rows | relocation rows | first storey | second storey | the small files' entries | their waves' first files
-  const uint64_t bytes = (n_tile + n_one + n_two) * sizeof(ManyRow) + n_move * sizeof(ResRow) + n_small * sizeof(BatchEnt) + (n_small ? (waves + 1) * 4 : 0);
+  const uint64_t n_small = count.files;
+  const uint64_t bytes = (n_tile + n_one + n_two) * sizeof(ManyRow) + n_move * sizeof(ResRow) + n_small * sizeof(BatchEnt) + count.first_bytes();
   ON_DEVICE(ctx);
   hipStream_t st = (hipStream_t)stream;
   b3w_ctx::ManySlot *slot = nullptr;
-  const int32_t rc = many_staging(ctx, bytes, &slot);
-  if (rc) return rc;
+  B3W_TRY(many_staging(ctx, bytes, &slot));
   ManyRow *h_tile = reinterpret_cast<ManyRow *>(slot->h), *h_one = h_tile + n_tile, *h_two = h_one + n_one;
   ResRow *h_move = reinterpret_cast<ResRow *>(h_two + n_two);
   BatchEnt *h_small = reinterpret_cast<BatchEnt *>(h_move + n_move);
   uint32_t *h_waves = reinterpret_cast<uint32_t *>(h_small + n_small);
   uint32_t *at = reinterpret_cast<uint32_t *>(d_scratch);
-  uint32_t i_tile = 0, i_move = 0, i_one = 0, i_two = 0, i_small = 0, i_waves = 0, f_tile = 0, f_move = 0, f_one = 0;
-  fill = 64;
+  uint32_t i_tile = 0, i_move = 0, i_one = 0, i_two = 0, f_tile = 0, f_move = 0, f_one = 0;
+  SmallPack pack;
+  pack.first = h_waves;
   for (uint32_t i = 0; i < n_resized; ++i) {
     const uint32_t f = host_files[i];
     const uint64_t old_len = host_old_lens[f], len = host_new_lens[f], n = num_chunks(len);
     if (n <= 64) {
-      if (fill + n > 64) { h_waves[i_waves++] = i_small; fill = 0; }
-      h_small[i_small++] = BatchEnt{host_offsets[f], len, host_new_ob_first[f], (uint32_t)fill, f};
-      fill += n;
+      const uint32_t lane = pack.add(n);
+      h_small[pack.files - 1] = BatchEnt{host_offsets[f], len, host_new_ob_first[f], lane, f};
       continue;
     }
-    const uint64_t kept = b3w_bao_resize_kept_tiles(old_len, len), tiles = resize_tiles(len);
+    const uint64_t kept = b3w_bao_resize_kept_tiles(old_len, len), tiles = tiles_of(len);
     uint32_t *tile_cv = tiles > 1 ? at : nullptr, *span_cv = tiles > B3W_TILE ? at + tiles * 8 : nullptr;
     at += resize_slots(len) * 8;
     ManyRow r{};
@@ -4234,7 +3469,7 @@ int32_t b3w_bao_outboard_resize_batch_device(b3w_ctx *ctx, const uint8_t *d_aren
       m.old_len = old_len; m.new_len = len; m.old_ob = d_old_outboards + host_old_ob_first[f]; m.new_ob = r.ob; m.cv = tile_cv; m.root = r.root;
       m.first = f_move; m.tiles = (uint32_t)kept; m.gl = group_log;
       h_move[i_move++] = m;
-      f_move += (uint32_t)(((kept + (1ull << sh.tpw_log) - 1) >> sh.tpw_log) * sh.ppb);
+      f_move += (uint32_t)open_move_wgs(kept, group_log);
     }
     if (tiles > 1) {                                                  // the first merge storey: a workgroup per 1 024 tiles
       ManyRow t = r;
@@ -4248,32 +3483,19 @@ int32_t b3w_bao_outboard_resize_batch_device(b3w_ctx *ctx, const uint8_t *d_aren
       h_two[i_two++] = t;
     }
   }
-  if (i_small) h_waves[i_waves] = i_small;
+  pack.close();
   const hipError_t ec = hipMemcpyAsync(slot->d, slot->h, (size_t)bytes, hipMemcpyHostToDevice, st);
   if (ec != hipSuccess) return hip_fail(ctx, ec, "bao resize: table upload");
   const ManyRow *d_tile = reinterpret_cast<const ManyRow *>(slot->d), *d_one = d_tile + n_tile, *d_two = d_one + n_one;
   const ResRow *d_move = reinterpret_cast<const ResRow *>(d_two + n_two);
   const BatchEnt *d_small = reinterpret_cast<const BatchEnt *>(d_move + n_move);
   const uint32_t *d_waves = reinterpret_cast<const uint32_t *>(d_small + n_small);
-  const uint64_t U = B3W_TILE;
-  if (group_log) {
-    if (n_small) hipLaunchKernelGGL(b3w_bao_small_group_kernel, dim3((uint32_t)waves), dim3(64), 0, st, d_arena, d_small, d_waves, d_new_outboards, d_roots, group_log);
-  } else {
-    if (n_small) hipLaunchKernelGGL(b3w_bao_small_kernel, dim3((uint32_t)waves), dim3(64), 0, st, d_arena, d_small, d_waves, d_new_outboards, d_roots);
-  }
+  const bool grp = group_log != 0;
+  if (n_small) launch_pair(grp, b3w_bao_small_kernel, b3w_bao_small_group_kernel, group_log, dim3((uint32_t)count.waves), dim3(64), st, d_arena, d_small, d_waves, d_new_outboards, d_roots);
   if (n_move) hipLaunchKernelGGL(b3w_bao_resize_relocate_kernel, dim3((uint32_t)wg_move), dim3(256), 0, st, d_move, (uint32_t)n_move);
-  if (n_tile) many_launch_tiles(B3W_BAO_STREAM_OUTBOARD, group_log != 0, d_tile, (uint32_t)n_tile, (uint32_t)wg_tile, st);
-  if (group_log) {
-    if (n_one) hipLaunchKernelGGL(b3w_bao_stream_merge_many_group_kernel, dim3((uint32_t)wg_one), dim3(256), 0, st, d_one, (uint32_t)n_one, U);
-    if (n_two) hipLaunchKernelGGL(b3w_bao_stream_merge_many_group_kernel, dim3((uint32_t)n_two), dim3(256), 0, st, d_two, (uint32_t)n_two, U * U);
-  } else {
-    if (n_one) hipLaunchKernelGGL(b3w_bao_stream_merge_many_kernel, dim3((uint32_t)wg_one), dim3(256), 0, st, d_one, (uint32_t)n_one, U);
-    if (n_two) hipLaunchKernelGGL(b3w_bao_stream_merge_many_kernel, dim3((uint32_t)n_two), dim3(256), 0, st, d_two, (uint32_t)n_two, U * U);
-  }
-  const hipError_t e = hipGetLastError();
-  many_release(slot, st);
-  if (e != hipSuccess) return hip_fail(ctx, e, "bao resize launch");
-  return B3W_OK;
+  if (n_tile) many_launch_tiles(B3W_BAO_STREAM_OUTBOARD, grp, d_tile, (uint32_t)n_tile, (uint32_t)wg_tile, st);
+  many_merge(grp, d_one, (uint32_t)n_one, (uint32_t)wg_one, d_two, (uint32_t)n_two, st);
+  return many_launched(ctx, slot, st, "bao resize launch");
 }
 
 }  // extern "C"
@@ -4310,61 +3532,9 @@ int32_t b3w_bao_outboard_resize_batch_device(b3w_ctx *ctx, const uint8_t *d_aren
 //   b3w_bao_range_reduce_kernel      a wave per range: the largest status and the first bad chunk over the range's rows.
 namespace {
 
-// the chunks of the left subtree of a subtree over m >= 2 chunks: the largest power of two strictly below m
-__host__ __device__ __forceinline__ uint64_t left_of(uint64_t m) { return 1ull << (63 - __builtin_clzll(m - 1)); }
-
-// path_len with the split from a bit scan: the parent nodes above chunk c of a subtree over m chunks, its root included
-__host__ __device__ __forceinline__ uint32_t depth_in(uint64_t c, uint64_t m) {
-  uint32_t p = 0;
-  for (; m > 1; ++p) {
-    const uint64_t k = left_of(m);
-    if (c < k) m = k; else { c -= k; m -= k; }
-  }
-  return p;
-}
-
-// U(a, c), a <= c < n
-__host__ __device__ inline uint64_t range_nodes(uint64_t n, uint64_t a, uint64_t c) {
-  uint64_t u = 0, lo = 0, m = n;
-  while (m > 1) {                                          // the nodes above the split: both ends go the same way
-    const uint64_t k = left_of(m);
-    if (c < lo + k) m = k;
-    else if (a >= lo + k) { lo += k; m -= k; }
-    else break;
-    ++u;
-  }
-  if (m <= 1) return u;                                    // (a == c: the chunk's path)
-  const uint64_t k = left_of(m);
-  ++u;                                                     // the split node: a on its left, c on its right
-  for (uint64_t l = lo, s = k; s > 1;) {                   // a's path below it: what lies right of a is inside
-    const uint64_t kk = left_of(s);
-    ++u;
-    if (a < l + kk) { u += s - kk - 1; s = kk; } else { l += kk; s -= kk; }
-  }
-  for (uint64_t l = lo + k, s = m - k; s > 1;) {           // c's path below it: what lies left of c is inside
-    const uint64_t kk = left_of(s);
-    ++u;
-    if (c >= l + kk) { u += kk - 1; l += kk; s -= kk; } else s = kk;
-  }
-  return u;
-}
-
-// the place within the slice of chunks [a, ..) of a file of n chunks of chunk c >= a, and of the node over [lo, lo + size) that meets it
-__host__ __device__ __forceinline__ uint64_t range_chunk_at(uint64_t n, uint64_t a, uint64_t c) { return 8 + 64 * range_nodes(n, a, c) + 1024 * (c - a); }
-__host__ __device__ __forceinline__ uint64_t range_node_at(uint64_t n, uint64_t a, uint64_t lo, uint64_t size) {
-  const uint64_t c0 = lo > a ? lo : a;
-  return range_chunk_at(n, a, c0) - 64ull * depth_in(c0 - lo, size);
-}
-
-uint64_t range_slice_bytes(uint64_t len, uint64_t n, uint64_t a, uint64_t k) {     // (a + k <= n, k >= 1)
-  const uint64_t end = (a + k) * 1024 < len ? (a + k) * 1024 : len;
-  return 8 + 64 * range_nodes(n, a, a + k - 1) + (end - a * 1024);
-}
-
 // a range's entry and a workgroup's row of the two device calls' table
 struct RsRange { uint64_t len, off, ob, slice, first, count, have; uint32_t file, row0; };   // have: the file's first bitmap word; row0: its first row
 struct RsRow { uint32_t range, block; };
-constexpr uint64_t RS_SHORT = 64;                          // ranges of at most this many chunks take rows of 64 chunks
 
 __device__ __forceinline__ void copy_node(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src) {   // (both 8-byte aligned)
   const uint2 *s = reinterpret_cast<const uint2 *>(src);
@@ -4588,13 +3758,11 @@ __global__ __launch_bounds__(256) void b3w_bao_range_reduce_kernel(const RsRange
   if (lane == 0) { range_status[i] = (int32_t)w; range_first_bad[i] = f; }
 }
 
-// ---- the host side of the two device calls: the checks, the rows, the table --------------------------------------------------------------
 struct RangeRows { uint64_t big, small; };                // rows of 1 024 chunks, rows of 64
 
 // every refusal the two calls share that concerns the ranges; counts the rows
 int32_t range_list_ok(b3w_ctx *ctx, const char *what, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
                       uint32_t n_files, const uint32_t *host_files, const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, RangeRows &rows) {
-  char msg[160];
   rows = RangeRows{};
   for (uint32_t i = 0; i < n_ranges; ++i) {
     const char *why = nullptr;
@@ -4607,19 +3775,10 @@ int32_t range_list_ok(b3w_ctx *ctx, const char *what, const uint8_t *d_arena, ui
       else if (len && !d_arena) why = "a null arena with a file that is not empty";
       else if (off > arena_bytes || len > arena_bytes - off) why = "its file reaches past arena_bytes";
     }
-    if (why) {
-      snprintf(msg, sizeof msg, "%s: range %u: %s", what, i, why);
-      ctx->last_error = msg;
-      return B3W_E_BAD_ARGUMENT;
-    }
-    const uint64_t a = host_first[i], k = host_count[i], B = k <= RS_SHORT ? 64 : B3W_TILE;
-    (k <= RS_SHORT ? rows.small : rows.big) += (a + k - 1) / B - a / B + 1;
+    if (why) return refuse(ctx, what, "range " + std::to_string(i) + ": " + why);
+    (host_count[i] <= RS_SHORT ? rows.small : rows.big) += range_rows(host_first[i], host_count[i]);
   }
-  if (rows.big > 0x7fffffffull || rows.small > 0x7fffffffull) {
-    snprintf(msg, sizeof msg, "%s: more than 2^31 - 1 rows of one kind", what);
-    ctx->last_error = msg;
-    return B3W_E_BAD_ARGUMENT;
-  }
+  if (rows.big > 0x7fffffffull || rows.small > 0x7fffffffull) return refuse(ctx, what, "more than 2^31 - 1 rows of one kind");
   return B3W_OK;
 }
 
@@ -4629,8 +3788,7 @@ int32_t range_table(b3w_ctx *ctx, const uint64_t *host_offsets, const uint64_t *
                     const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, RangeRows rows, hipStream_t st, const RsRange *&d_ranges,
                     const RsRow *&d_big, const RsRow *&d_small) {
   const uint64_t up_bytes = (uint64_t)n_ranges * sizeof(RsRange) + (rows.big + rows.small) * sizeof(RsRow);
-  const int32_t rc = batch_staging(ctx, up_bytes + 2 * ((uint64_t)n_files + 1) * 8);
-  if (rc) return rc;
+  B3W_TRY(batch_staging(ctx, up_bytes + 2 * ((uint64_t)n_files + 1) * 8));
   RsRange *rg = reinterpret_cast<RsRange *>(ctx->h_batch);
   RsRow *big = reinterpret_cast<RsRow *>(rg + n_ranges), *small = big + rows.big;
   uint64_t *ob_first = reinterpret_cast<uint64_t *>(small + rows.small), *word_first = ob_first + n_files + 1;
@@ -4655,198 +3813,30 @@ int32_t range_table(b3w_ctx *ctx, const uint64_t *host_offsets, const uint64_t *
   return B3W_OK;
 }
 
-// ---- the host mirrors: one range, node by node ----------------------------------------------------------------------------------
-// the CV of the subtree over chunks [first, first + cnt) whose bytes start at `base` with chunk base_chunk (host_subtree_cv on a part of a file)
-void part_subtree_cv(const uint8_t *base, uint64_t base_chunk, uint64_t len, uint64_t first, uint64_t cnt, bool root, uint32_t h[8]) {
-  if (cnt == 1) {
-    const uint64_t off = first * 1024;
-    host_chunk_cv(base + (first - base_chunk) * 1024, (uint32_t)(len - off < 1024 ? len - off : 1024), first, root ? 8u : 0u, h);
-    return;
-  }
-  const uint64_t k = left_of(cnt);
-  uint32_t m[16], ivv[8];
-  part_subtree_cv(base, base_chunk, len, first, k, false, m);
-  part_subtree_cv(base, base_chunk, len, first + k, cnt - k, false, m + 8);
-  iv(ivv);
-  blake3_cv(ivv, m, 0, 0, 64, 4u | (root ? 8u : 0u), h);
-}
-
-void put_words(uint8_t *dst, const uint32_t *w, uint32_t n) {
-  for (uint32_t k = 0; k < n; ++k)
-    for (int q = 0; q < 4; ++q) dst[4 * k + q] = (uint8_t)(w[k] >> (8 * q));
-}
-
-// the extractor's walk: the subtree over [lo, lo + size) of a file of n chunks, which meets [a, e); appends to out at `at`
-struct RangeEnc { const uint8_t *ob, *bytes; uint64_t len, n, a, e, base_chunk; uint32_t gl; uint8_t *out; uint64_t at; };
-void range_encode(RangeEnc &w, uint64_t lo, uint64_t size) {
-  if (size == 1) {
-    const uint64_t off = lo * 1024, bytes = w.len - off < 1024 ? w.len - off : 1024;
-    if (bytes) memcpy(w.out + w.at, w.bytes + (lo - w.base_chunk) * 1024, bytes);
-    w.at += bytes;
-    return;
-  }
-  const uint64_t k = left_of(size), G = 1ull << w.gl;
-  if (size > G) memcpy(w.out + w.at, w.ob + 8 + 64 * preorder_pos((w.n + G - 1) >> w.gl, lo >> w.gl, (size + G - 1) >> w.gl), 64);
-  else {                                                  // inside a group: from the group's bytes
-    uint32_t m[16];
-    part_subtree_cv(w.bytes, w.base_chunk, w.len, lo, k, false, m);
-    part_subtree_cv(w.bytes, w.base_chunk, w.len, lo + k, size - k, false, m + 8);
-    put_words(w.out + w.at, m, 16);
-  }
-  w.at += 64;
-  if (w.a < lo + k) range_encode(w, lo, k);
-  if (w.e > lo + k) range_encode(w, lo + k, size - k);
-}
-
-// the decoder's walk, top down in slice order; the ingest's writes ride on it.  -> whether a chunk below verified
-struct RangeDec {
-  const uint8_t *sl; uint64_t len, n, a, e, at; bool hdr; uint32_t gl;
-  uint8_t *out_bytes, *data, *ob; uint64_t *have;          // decode: out_bytes; ingest: data, ob, have (may be null)
-  int32_t worst; uint64_t first_bad;
-};
-bool range_decode(RangeDec &w, uint64_t lo, uint64_t size, const uint32_t want[8], bool bad_above, bool root) {
-  if (size == 1) {
-    const uint64_t off = lo * 1024, bytes = w.len - off < 1024 ? w.len - off : 1024;
-    const uint8_t *src = w.sl + w.at;
-    w.at += bytes;
-    uint32_t h[8];
-    host_chunk_cv(src, (uint32_t)bytes, lo, root ? 8u : 0u, h);
-    const int32_t st = w.hdr ? 3 : bad_above ? 2 : memcmp(h, want, 32) != 0 ? 1 : 0;
-    if (st) {
-      if (st > w.worst) w.worst = st;
-      if (lo < w.first_bad) w.first_bad = lo;
-      return false;
-    }
-    if (bytes && w.out_bytes) memcpy(w.out_bytes + (lo - w.a) * 1024, src, bytes);
-    if (bytes && w.data) memcpy(w.data + off, src, bytes);
-    if (w.have) w.have[lo >> 6] |= 1ull << (lo & 63);
-    return true;
-  }
-  const uint8_t *node = w.sl + w.at;
-  w.at += 64;
-  uint32_t mw[16], ivv[8], o[8];
-  for (int k = 0; k < 16; ++k) mw[k] = (uint32_t)node[4 * k] | ((uint32_t)node[4 * k + 1] << 8) | ((uint32_t)node[4 * k + 2] << 16) | ((uint32_t)node[4 * k + 3] << 24);
-  iv(ivv);
-  blake3_cv(ivv, mw, 0, 0, 64, 4u | (root ? 8u : 0u), o);
-  const bool bad = bad_above || memcmp(o, want, 32) != 0;
-  const uint64_t k = left_of(size), G = 1ull << w.gl;
-  bool any = false;
-  if (w.a < lo + k) any |= range_decode(w, lo, k, mw, bad, false);
-  if (w.e > lo + k) any |= range_decode(w, lo + k, size - k, mw + 8, bad, false);
-  if (any && w.ob && size > G) memcpy(w.ob + 8 + 64 * preorder_pos((w.n + G - 1) >> w.gl, lo >> w.gl, (size + G - 1) >> w.gl), node, 64);
-  return any;
-}
-
-int32_t range_decode_run(const uint8_t *slice, uint64_t slice_len, uint64_t len, uint64_t first, uint64_t count, const uint32_t *root, RangeDec &w) {
-  const uint64_t n = num_chunks(len);
-  if (!slice || !root || count == 0 || first >= n || count > n - first || slice_len != range_slice_bytes(len, n, first, count)) return B3W_E_BAD_ARGUMENT;
-  uint64_t hdr = 0;
-  for (int k = 0; k < 8; ++k) hdr |= (uint64_t)slice[k] << (8 * k);
-  w.sl = slice; w.len = len; w.n = n; w.a = first; w.e = first + count; w.at = 8; w.hdr = hdr != len; w.worst = 0; w.first_bad = ~0ull;
-  const bool any = range_decode(w, 0, n, root, false, true);
-  if (any && w.ob) memcpy(w.ob, slice, 8);
-  return B3W_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
-uint64_t b3w_bao_range_slice_size(uint64_t len, uint64_t first_chunk, uint64_t n_chunks) {
-  const uint64_t n = num_chunks(len);
-  if (n_chunks == 0 || first_chunk >= n || n_chunks > n - first_chunk) return 0;
-  return range_slice_bytes(len, n, first_chunk, n_chunks);
-}
-
-int64_t b3w_bao_range_slice_batch_layout(const uint64_t *host_lens, uint32_t n_files, const uint32_t *host_files, const uint64_t *host_first,
-                                         const uint64_t *host_count, uint32_t n_ranges, uint64_t *slice_first) {
-  if (!slice_first || (n_ranges && (!host_lens || !host_files || !host_first || !host_count))) return -B3W_E_BAD_ARGUMENT;
-  for (uint32_t i = 0; i < n_ranges; ++i)
-    if (host_files[i] >= n_files || !b3w_bao_range_slice_size(host_lens[host_files[i]], host_first[i], host_count[i])) return -B3W_E_BAD_ARGUMENT;
-  uint64_t at = slice_start(0);
-  for (uint32_t i = 0; i < n_ranges; ++i) {
-    slice_first[i] = at;
-    at = slice_start(at + b3w_bao_range_slice_size(host_lens[host_files[i]], host_first[i], host_count[i]));
-  }
-  slice_first[n_ranges] = at;
-  return (int64_t)at;
-}
-
-int64_t b3w_bao_range_slice(const uint8_t *outboard, uint64_t len, uint32_t group_log, uint64_t first_chunk, uint64_t n_chunks, const uint8_t *range_bytes,
-                            uint8_t *out, uint64_t out_len) {
-  const uint64_t size = b3w_bao_range_slice_size(len, first_chunk, n_chunks);
-  if (!size || group_log > B3W_BAO_MAX_GROUP_LOG) return -B3W_E_BAD_ARGUMENT;
-  if (!out) return (int64_t)size;
-  if (!outboard || (!range_bytes && len) || out_len < size) return -B3W_E_BAD_ARGUMENT;
-  memcpy(out, outboard, 8);
-  RangeEnc w{outboard, range_bytes, len, num_chunks(len), first_chunk, first_chunk + n_chunks, (first_chunk >> group_log) << group_log, group_log, out, 8};
-  range_encode(w, 0, w.n);
-  return (int64_t)w.at;
-}
-
-int32_t b3w_bao_range_slice_decode(const uint8_t *slice, uint64_t slice_len, uint64_t len, uint64_t first_chunk, uint64_t n_chunks, const uint32_t *root,
-                                   uint8_t *out_bytes, int32_t *out_status, uint64_t *out_first_bad) {
-  if (!out_status) return B3W_E_BAD_ARGUMENT;
-  RangeDec w{};
-  w.out_bytes = out_bytes;
-  const int32_t rc = range_decode_run(slice, slice_len, len, first_chunk, n_chunks, root, w);
-  if (rc) return rc;
-  *out_status = w.worst;
-  if (out_first_bad) *out_first_bad = w.first_bad;
-  return B3W_OK;
-}
-
-int32_t b3w_bao_range_slice_ingest(const uint8_t *slice, uint64_t slice_len, uint64_t len, uint64_t first_chunk, uint64_t n_chunks, const uint32_t *root,
-                                   uint32_t group_log, uint8_t *data, uint8_t *outboard, uint64_t *have, int32_t *out_status, uint64_t *out_first_bad) {
-  if (group_log > B3W_BAO_MAX_GROUP_LOG || !outboard || (!data && len) || !out_status) return B3W_E_BAD_ARGUMENT;
-  RangeDec w{};
-  w.gl = group_log; w.data = data; w.ob = outboard; w.have = have;
-  const int32_t rc = range_decode_run(slice, slice_len, len, first_chunk, n_chunks, root, w);
-  if (rc) return rc;
-  *out_status = w.worst;
-  if (out_first_bad) *out_first_bad = w.first_bad;
-  return B3W_OK;
-}
-
+// ---- range slices --------------------------------------------------------------------------------------------------------------------
 int32_t b3w_bao_range_slice_arena_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
                                          uint32_t n_files, uint32_t group_log, const uint8_t *d_outboards, const uint32_t *host_files,
                                          const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, uint8_t *d_slices, void *stream) {
+  const char *call = "bao range slice arena";
   if (!ctx) return B3W_E_BAD_ARGUMENT;
-  if (group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "bao range slice arena: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
+  B3W_TRY(group_log_ok(ctx, call, group_log));
   if (!n_ranges) return B3W_OK;
-  if (!host_offsets || !host_lens || !d_outboards || !host_files || !host_first || !host_count || !d_slices) {
-    ctx->last_error = "bao range slice arena: a null pointer"; return B3W_E_BAD_ARGUMENT;
-  }
-  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) {
-    ctx->last_error = "bao range slice arena: d_outboards is not 8-byte or d_slices not 16-byte aligned"; return B3W_E_BAD_ARGUMENT;
-  }
+  if (!host_offsets || !host_lens || !d_outboards || !host_files || !host_first || !host_count || !d_slices) return refuse(ctx, call, "a null pointer");
+  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) return refuse(ctx, call, "d_outboards is not 8-byte or d_slices not 16-byte aligned");
   RangeRows rows;
-  int32_t rc = range_list_ok(ctx, "bao range slice arena", d_arena, arena_bytes, host_offsets, host_lens, n_files, host_files, host_first, host_count, n_ranges, rows);
-  if (rc) return rc;
+  B3W_TRY(range_list_ok(ctx, call, d_arena, arena_bytes, host_offsets, host_lens, n_files, host_files, host_first, host_count, n_ranges, rows));
   ON_DEVICE(ctx);
   hipStream_t st = (hipStream_t)stream;
   const RsRange *d_ranges = nullptr;
   const RsRow *d_big = nullptr, *d_small = nullptr;
-  rc = range_table(ctx, host_offsets, host_lens, n_files, group_log, host_files, host_first, host_count, n_ranges, rows, st, d_ranges, d_big, d_small);
-  if (rc) return rc;
+  B3W_TRY(range_table(ctx, host_offsets, host_lens, n_files, group_log, host_files, host_first, host_count, n_ranges, rows, st, d_ranges, d_big, d_small));
   if (rows.big) hipLaunchKernelGGL(b3w_bao_range_slice_kernel<(int)B3W_TILE>, dim3((uint32_t)rows.big), dim3(B3W_TILE), 0, st, d_ranges, d_big, group_log, d_arena, d_outboards, d_slices);
   if (rows.small) hipLaunchKernelGGL(b3w_bao_range_slice_kernel<64>, dim3((uint32_t)rows.small), dim3(64), 0, st, d_ranges, d_small, group_log, d_arena, d_outboards, d_slices);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(ctx, e, "bao range slice arena launch");
-  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
-  return B3W_OK;
-}
-
-uint64_t b3w_bao_range_slice_ingest_scratch_bytes(const uint64_t *host_lens, uint32_t n_files, const uint32_t *host_files, const uint64_t *host_first,
-                                                  const uint64_t *host_count, uint32_t n_ranges) {
-  if (!host_lens || !host_files || !host_first || !host_count) return 0;
-  uint64_t rows = 0;
-  for (uint32_t i = 0; i < n_ranges; ++i) {
-    if (host_files[i] >= n_files || !b3w_bao_range_slice_size(host_lens[host_files[i]], host_first[i], host_count[i])) return 0;
-    const uint64_t a = host_first[i], k = host_count[i], B = k <= RS_SHORT ? 64 : B3W_TILE;
-    rows += (a + k - 1) / B - a / B + 1;
-  }
-  return rows * 16;                                       // a row's status and first bad chunk
+  return batch_launched(ctx, st, "bao range slice arena launch");
 }
 
 int32_t b3w_bao_range_slice_ingest_device(b3w_ctx *ctx, uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
@@ -4854,32 +3844,23 @@ int32_t b3w_bao_range_slice_ingest_device(b3w_ctx *ctx, uint8_t *d_arena, uint64
                                           const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, const uint8_t *d_slices,
                                           int32_t *d_range_status, uint64_t *d_range_first_bad, uint64_t *d_have, void *d_scratch, uint64_t scratch_bytes,
                                           void *stream) {
+  const char *call = "bao range slice ingest";
   if (!ctx) return B3W_E_BAD_ARGUMENT;
-  if (group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "bao range slice ingest: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
-  if ((uintptr_t)d_have & 7) { ctx->last_error = "bao range slice ingest: d_have is not 8-byte aligned"; return B3W_E_BAD_ARGUMENT; }
+  B3W_TRY(group_log_ok(ctx, call, group_log));
+  if ((uintptr_t)d_have & 7) return refuse(ctx, call, "d_have is not 8-byte aligned");
   if (!n_ranges) return B3W_OK;
-  if (!host_offsets || !host_lens || !d_outboards || !d_roots || !host_files || !host_first || !host_count || !d_slices || !d_range_status || !d_range_first_bad) {
-    ctx->last_error = "bao range slice ingest: a null pointer"; return B3W_E_BAD_ARGUMENT;
-  }
-  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) {
-    ctx->last_error = "bao range slice ingest: d_outboards is not 8-byte or d_slices not 16-byte aligned"; return B3W_E_BAD_ARGUMENT;
-  }
-  if (((uintptr_t)d_range_status & 3) || ((uintptr_t)d_range_first_bad & 7)) {
-    ctx->last_error = "bao range slice ingest: d_range_status is not 4-byte or d_range_first_bad not 8-byte aligned"; return B3W_E_BAD_ARGUMENT;
-  }
+  if (!host_offsets || !host_lens || !d_outboards || !d_roots || !host_files || !host_first || !host_count || !d_slices || !d_range_status || !d_range_first_bad) return refuse(ctx, call, "a null pointer");
+  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) return refuse(ctx, call, "d_outboards is not 8-byte or d_slices not 16-byte aligned");
+  if (((uintptr_t)d_range_status & 3) || ((uintptr_t)d_range_first_bad & 7)) return refuse(ctx, call, "d_range_status is not 4-byte or d_range_first_bad not 8-byte aligned");
   RangeRows rows;
-  int32_t rc = range_list_ok(ctx, "bao range slice ingest", d_arena, arena_bytes, host_offsets, host_lens, n_files, host_files, host_first, host_count, n_ranges, rows);
-  if (rc) return rc;
-  if (scratch_bytes < (rows.big + rows.small) * 16) {
-    ctx->last_error = "bao range slice ingest: the scratch is smaller than b3w_bao_range_slice_ingest_scratch_bytes says"; return B3W_E_BAD_ARGUMENT;
-  }
-  if (!d_scratch || ((uintptr_t)d_scratch & 15)) { ctx->last_error = "bao range slice ingest: the scratch is null or not 16-byte aligned"; return B3W_E_BAD_ARGUMENT; }
+  B3W_TRY(range_list_ok(ctx, call, d_arena, arena_bytes, host_offsets, host_lens, n_files, host_files, host_first, host_count, n_ranges, rows));
+  if (scratch_bytes < (rows.big + rows.small) * 16) return refuse(ctx, call, "the scratch is smaller than b3w_bao_range_slice_ingest_scratch_bytes says");
+  if (!d_scratch || ((uintptr_t)d_scratch & 15)) return refuse(ctx, call, "the scratch is null or not 16-byte aligned");
   ON_DEVICE(ctx);
   hipStream_t st = (hipStream_t)stream;
   const RsRange *d_ranges = nullptr;
   const RsRow *d_big = nullptr, *d_small = nullptr;
-  rc = range_table(ctx, host_offsets, host_lens, n_files, group_log, host_files, host_first, host_count, n_ranges, rows, st, d_ranges, d_big, d_small);
-  if (rc) return rc;
+  B3W_TRY(range_table(ctx, host_offsets, host_lens, n_files, group_log, host_files, host_first, host_count, n_ranges, rows, st, d_ranges, d_big, d_small));
   uint4 *res = reinterpret_cast<uint4 *>(d_scratch);
   unsigned long long *have = reinterpret_cast<unsigned long long *>(d_have);
   if (rows.big)
@@ -4890,10 +3871,7 @@ int32_t b3w_bao_range_slice_ingest_device(b3w_ctx *ctx, uint8_t *d_arena, uint64
                        have, res + rows.big);
   hipLaunchKernelGGL(b3w_bao_range_reduce_kernel, dim3((n_ranges + 3) / 4), dim3(256), 0, st, d_ranges, n_ranges, res, d_range_status,
                      reinterpret_cast<unsigned long long *>(d_range_first_bad));
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(ctx, e, "bao range slice ingest launch");
-  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
-  return B3W_OK;
+  return batch_launched(ctx, st, "bao range slice ingest launch");
 }
 
 }  // extern "C"

@@ -20,13 +20,12 @@
 // selected bit whose predecessor (the previous word's top bit, inside one file) is not selected, and ends likewise; the runs that ended
 // before a word are the runs that started before it, less the one that comes in through bit 0, so one scan numbers both.
 #include "b3w_internal.h"
+#include "b3w_bao_tree.h"
 
 namespace {
 
 constexpr uint32_t HAVE_WG = 1024;                       // words a workgroup of the run kernels (a lane each)
 constexpr uint64_t HAVE_MAX_WORDS = 1ull << 26;
-
-uint64_t num_chunks(uint64_t len) { return len ? (len + 1023) / 1024 : 1; }
 
 // the tables behind each other in the staging: word_first [n_files + 1], n_chunks [n_files], unit_first [n_files] (the pack call's)
 struct HaveTables { const uint64_t *word_first, *n_chunks, *unit_first; };
@@ -189,14 +188,13 @@ __global__ __launch_bounds__(256) void b3w_bao_have_pack_kernel(const uint8_t *_
 // the tables into the staging and on their way to the device -> their device addresses
 int32_t have_tables(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, bool units, uint32_t group_log, hipStream_t st, const uint64_t *&t) {
   const uint64_t words = (uint64_t)n_files * (units ? 3 : 2) + 1;
-  const int32_t rc = b3w_int_batch_staging(ctx, words * 8);
-  if (rc) return rc;
+  B3W_TRY(b3w_int_batch_staging(ctx, words * 8));
   uint64_t *h = reinterpret_cast<uint64_t *>(ctx->h_batch);
   (void)b3w_bao_have_layout(host_lens, n_files, h);
   for (uint32_t f = 0; f < n_files; ++f) h[(uint64_t)n_files + 1 + f] = num_chunks(host_lens[f]);
   if (units) {
     uint64_t at = 0;                                      // b3w_bao_verify_layout without its last entry
-    for (uint32_t f = 0; f < n_files; ++f) { h[2 * (uint64_t)n_files + 1 + f] = at; at += (num_chunks(host_lens[f]) + (1ull << group_log) - 1) >> group_log; }
+    for (uint32_t f = 0; f < n_files; ++f) { h[2 * (uint64_t)n_files + 1 + f] = at; at += n_units(host_lens[f], group_log); }
   }
   HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)(words * 8), hipMemcpyHostToDevice, st));
   t = reinterpret_cast<const uint64_t *>(ctx->d_batch);
@@ -213,14 +211,6 @@ uint64_t have_words(const uint64_t *lens, uint32_t n_files) {
 
 extern "C" {
 
-uint64_t b3w_bao_have_layout(const uint64_t *host_lens, uint32_t n_files, uint64_t *word_first) {
-  if (!word_first || (!host_lens && n_files)) return 0;
-  uint64_t at = 0;
-  for (uint32_t f = 0; f < n_files; ++f) { word_first[f] = at; at += (num_chunks(host_lens[f]) + 63) / 64; }
-  word_first[n_files] = at;
-  return at;
-}
-
 uint64_t b3w_bao_have_runs_scratch_bytes(const uint64_t *host_lens, uint32_t n_files) {
   if (!host_lens) return 0;
   const uint64_t wgs = (have_words(host_lens, n_files) + HAVE_WG - 1) / HAVE_WG;
@@ -230,32 +220,30 @@ uint64_t b3w_bao_have_runs_scratch_bytes(const uint64_t *host_lens, uint32_t n_f
 int32_t b3w_bao_have_runs_device(b3w_ctx *ctx, const uint64_t *d_have, const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, uint32_t kind,
                                  uint64_t capacity, uint32_t *d_run_file, uint64_t *d_run_first, uint64_t *d_run_count, uint64_t *d_n_runs,
                                  uint64_t *d_file_have, void *d_scratch, uint64_t scratch_bytes, void *stream) {
+  const char *call = "bao have runs";
   if (!ctx) return B3W_E_BAD_ARGUMENT;
-  if (group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "bao have runs: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
-  if (kind != B3W_BAO_HAVE_MISSING && kind != B3W_BAO_HAVE_PRESENT) { ctx->last_error = "bao have runs: kind is neither B3W_BAO_HAVE_MISSING nor B3W_BAO_HAVE_PRESENT"; return B3W_E_BAD_ARGUMENT; }
-  if (!d_n_runs || ((uintptr_t)d_n_runs & 7)) { ctx->last_error = "bao have runs: d_n_runs is null or not 8-byte aligned"; return B3W_E_BAD_ARGUMENT; }
-  if (capacity && (!d_run_file || !d_run_first || !d_run_count)) { ctx->last_error = "bao have runs: a null row array with a capacity above 0"; return B3W_E_BAD_ARGUMENT; }
-  if (((uintptr_t)d_run_file & 3) || ((uintptr_t)d_run_first & 7) || ((uintptr_t)d_run_count & 7) || ((uintptr_t)d_file_have & 7)) {
-    ctx->last_error = "bao have runs: d_run_file is not 4-byte aligned, or d_run_first, d_run_count or d_file_have not 8-byte aligned"; return B3W_E_BAD_ARGUMENT;
-  }
+  B3W_TRY(group_log_ok(ctx, call, group_log));
+  if (kind != B3W_BAO_HAVE_MISSING && kind != B3W_BAO_HAVE_PRESENT) return refuse(ctx, call, "kind is neither B3W_BAO_HAVE_MISSING nor B3W_BAO_HAVE_PRESENT");
+  if (!d_n_runs || ((uintptr_t)d_n_runs & 7)) return refuse(ctx, call, "d_n_runs is null or not 8-byte aligned");
+  if (capacity && (!d_run_file || !d_run_first || !d_run_count)) return refuse(ctx, call, "a null row array with a capacity above 0");
+  if (((uintptr_t)d_run_file & 3) || ((uintptr_t)d_run_first & 7) || ((uintptr_t)d_run_count & 7) || ((uintptr_t)d_file_have & 7)) return refuse(ctx, call, "d_run_file is not 4-byte aligned, or d_run_first, d_run_count or d_file_have not 8-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   if (!n_files) {
     ON_DEVICE(ctx);
     HIP_TRY(ctx, hipMemsetAsync(d_n_runs, 0, 8, st));
     return B3W_OK;
   }
-  if (!host_lens || !d_have || ((uintptr_t)d_have & 7)) { ctx->last_error = "bao have runs: host_lens or d_have is null, or d_have not 8-byte aligned"; return B3W_E_BAD_ARGUMENT; }
+  if (!host_lens || !d_have || ((uintptr_t)d_have & 7)) return refuse(ctx, call, "host_lens or d_have is null, or d_have not 8-byte aligned");
   const uint64_t n_words = have_words(host_lens, n_files);
-  if (n_words > HAVE_MAX_WORDS) { ctx->last_error = "bao have runs: more than 2^26 bitmap words"; return B3W_E_BAD_ARGUMENT; }
+  if (n_words > HAVE_MAX_WORDS) return refuse(ctx, call, "more than 2^26 bitmap words");
   const uint32_t wgs = (uint32_t)((n_words + HAVE_WG - 1) / HAVE_WG);
-  if (scratch_bytes < (((uint64_t)wgs * 8 + 15) & ~15ull)) { ctx->last_error = "bao have runs: the scratch is smaller than b3w_bao_have_runs_scratch_bytes says"; return B3W_E_BAD_ARGUMENT; }
-  if (!d_scratch || ((uintptr_t)d_scratch & 7)) { ctx->last_error = "bao have runs: the scratch is null or not 8-byte aligned"; return B3W_E_BAD_ARGUMENT; }
+  if (scratch_bytes < (((uint64_t)wgs * 8 + 15) & ~15ull)) return refuse(ctx, call, "the scratch is smaller than b3w_bao_have_runs_scratch_bytes says");
+  if (!d_scratch || ((uintptr_t)d_scratch & 7)) return refuse(ctx, call, "the scratch is null or not 8-byte aligned");
   uint64_t most = 0;                                      // the rows there can be: ceil(units / 2) a file
-  for (uint32_t f = 0; f < n_files; ++f) most += (((num_chunks(host_lens[f]) + (1ull << group_log) - 1) >> group_log) + 1) / 2;
+  for (uint32_t f = 0; f < n_files; ++f) most += (n_units(host_lens[f], group_log) + 1) / 2;
   ON_DEVICE(ctx);
   const uint64_t *t = nullptr;
-  const int32_t rc = have_tables(ctx, host_lens, n_files, false, 0, st, t);
-  if (rc) return rc;
+  B3W_TRY(have_tables(ctx, host_lens, n_files, false, 0, st, t));
   uint64_t *wg = reinterpret_cast<uint64_t *>(d_scratch);
   hipLaunchKernelGGL(b3w_bao_have_count_kernel, dim3(wgs), dim3(HAVE_WG), 0, st, d_have, t, n_files, n_words, group_log, kind, wg, d_file_have);
   hipLaunchKernelGGL(b3w_bao_have_scan_kernel, dim3(1), dim3(HAVE_WG), 0, st, wg, wgs, d_n_runs);
@@ -264,69 +252,24 @@ int32_t b3w_bao_have_runs_device(b3w_ctx *ctx, const uint64_t *d_have, const uin
                        d_run_count, reinterpret_cast<unsigned long long *>(d_file_have));
   const uint64_t rows = capacity < most ? capacity : most;
   if (rows) hipLaunchKernelGGL(b3w_bao_have_sub_kernel, dim3((uint32_t)((rows + 255) / 256)), dim3(256), 0, st, d_n_runs, capacity, d_run_first, d_run_count);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(ctx, e, "bao have runs launch");
-  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
-  return B3W_OK;
+  return b3w_int_batch_launched(ctx, st, "bao have runs launch");
 }
 
 int32_t b3w_bao_have_from_status_device(b3w_ctx *ctx, const uint8_t *d_unit_status, const uint64_t *host_lens, uint32_t n_files, uint32_t group_log,
                                         uint64_t *d_have, void *stream) {
+  const char *call = "bao have from status";
   if (!ctx) return B3W_E_BAD_ARGUMENT;
-  if (group_log > B3W_BAO_MAX_GROUP_LOG) { ctx->last_error = "bao have from status: group_log is above B3W_BAO_MAX_GROUP_LOG (6)"; return B3W_E_BAD_ARGUMENT; }
+  B3W_TRY(group_log_ok(ctx, call, group_log));
   if (!n_files) return B3W_OK;
-  if (!d_unit_status || !host_lens || !d_have || ((uintptr_t)d_have & 7)) {
-    ctx->last_error = "bao have from status: a null pointer, or d_have not 8-byte aligned"; return B3W_E_BAD_ARGUMENT;
-  }
+  if (!d_unit_status || !host_lens || !d_have || ((uintptr_t)d_have & 7)) return refuse(ctx, call, "a null pointer, or d_have not 8-byte aligned");
   const uint64_t n_words = have_words(host_lens, n_files);
-  if (n_words > HAVE_MAX_WORDS) { ctx->last_error = "bao have from status: more than 2^26 bitmap words"; return B3W_E_BAD_ARGUMENT; }
+  if (n_words > HAVE_MAX_WORDS) return refuse(ctx, call, "more than 2^26 bitmap words");
   ON_DEVICE(ctx);
   hipStream_t st = (hipStream_t)stream;
   const uint64_t *t = nullptr;
-  const int32_t rc = have_tables(ctx, host_lens, n_files, true, group_log, st, t);
-  if (rc) return rc;
+  B3W_TRY(have_tables(ctx, host_lens, n_files, true, group_log, st, t));
   hipLaunchKernelGGL(b3w_bao_have_pack_kernel, dim3((uint32_t)((n_words + 255) / 256)), dim3(256), 0, st, d_unit_status, t, n_files, n_words, group_log, d_have);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(ctx, e, "bao have from status launch");
-  HIP_TRY(ctx, hipEventRecord(ctx->batch_done, st));
-  return B3W_OK;
-}
-
-// ---- the host mirrors: one file, unit by unit ---------------------------------------------------------------------------
-int32_t b3w_bao_have_runs(const uint64_t *have, uint64_t len, uint32_t group_log, uint32_t kind, uint64_t capacity, uint64_t *run_first,
-                          uint64_t *run_count, uint64_t *n_runs, uint64_t *n_have) {
-  if (!have || !n_runs || group_log > B3W_BAO_MAX_GROUP_LOG || (kind != B3W_BAO_HAVE_MISSING && kind != B3W_BAO_HAVE_PRESENT) ||
-      (capacity && (!run_first || !run_count)))
-    return B3W_E_BAD_ARGUMENT;
-  const uint64_t n = num_chunks(len), F = 1ull << group_log;
-  uint64_t runs = 0, set = 0, open_at = 0;
-  bool open = false;
-  for (uint64_t c = 0; c < n; c += F) {
-    const uint64_t end = c + F < n ? c + F : n;
-    uint64_t got = 0;
-    for (uint64_t k = c; k < end; ++k) got += (have[k >> 6] >> (k & 63)) & 1;
-    set += got;
-    const bool sel = (kind == B3W_BAO_HAVE_PRESENT) == (got == end - c);
-    if (sel && !open) { open = true; open_at = c; }
-    if (open && (!sel || end == n)) {
-      const uint64_t stop = sel ? end : c;
-      if (runs < capacity) { run_first[runs] = open_at; run_count[runs] = stop - open_at; }
-      ++runs;
-      open = false;
-    }
-  }
-  *n_runs = runs;
-  if (n_have) *n_have = set;
-  return B3W_OK;
-}
-
-int32_t b3w_bao_have_from_status(const uint8_t *status, uint64_t len, uint32_t group_log, uint64_t *have) {
-  if (!status || !have || group_log > B3W_BAO_MAX_GROUP_LOG) return B3W_E_BAD_ARGUMENT;
-  const uint64_t n = num_chunks(len);
-  for (uint64_t w = 0; w < (n + 63) / 64; ++w) have[w] = 0;
-  for (uint64_t c = 0; c < n; ++c)
-    if (status[c >> group_log] == 0) have[c >> 6] |= 1ull << (c & 63);
-  return B3W_OK;
+  return b3w_int_batch_launched(ctx, st, "bao have from status launch");
 }
 
 }  // extern "C"

@@ -1,0 +1,19 @@
+// b3w_bao_plan.h — the plan of the sparse bao calls (update, ranged verification): defined in b3w_bao_host.cpp, where the scratch sizes
+// use it; the two device entry points of b3w_bao.hip build their tables from it.  Not installed.
+#pragma once
+#include <vector>
+
+#include "b3w_bao_tree.h"
+
+struct UpdRange { uint32_t file; uint64_t first, end; };              // chunks [first, end) of the file
+// a workgroup of the plan: the file, the tile / span within it, its own scratch slot and the slot of its first dirty input item
+struct UpdWg { uint32_t file, idx; uint64_t out, in; uint32_t mask[B3W_TILE / 32]; };
+struct UpdPlan {
+  std::vector<uint32_t> small;                                        // the dirty files of at most 64 chunks, ascending, each once
+  std::vector<UpdWg> tiles, spans, tops;                              // the three storeys, sorted by (file, idx)
+  uint64_t tile_slots = 0, span_slots = 0;                            // scratch: the dirty tiles of files of more than one tile, then the dirty spans past 1 GiB
+};
+// the ranges that are not empty, sorted by (file, first chunk), overlapping and adjoining ones of a file merged; ends clamped to the file
+std::vector<UpdRange> b3w_int_update_ranges(const uint64_t *lens, const uint32_t *files, const uint64_t *first, const uint64_t *count, uint32_t n_ranges);
+// what a call over these (sorted, merged) ranges launches; the chunk masks are expanded to whole groups of 1 << gl chunks
+UpdPlan b3w_int_update_plan(const uint64_t *lens, const std::vector<UpdRange> &ranges, uint32_t gl);

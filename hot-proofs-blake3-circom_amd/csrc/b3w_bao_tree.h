@@ -1,0 +1,188 @@
+// b3w_bao_tree.h — the bao arithmetic that the host calls (b3w_bao_host.cpp), the device entry points and the kernels (b3w_bao.hip,
+// b3w_bao_have.hip) share: chunk and unit counts, sizes, places in the pre-order outboard and in a range slice, the packing of small
+// files into waves, what a batch launches, and a chunk's and a subtree's CV on the host.  One definition each; compiles as HIP and as
+// plain C++ (b3w_blake3_cv.h).  Not installed.  The inline pieces live in an anonymous namespace, a copy a file, as b3w_blake3_dev.h's.
+#pragma once
+#include <stdint.h>
+#include <string.h>
+
+#include "b3w_blake3_cv.h"
+
+namespace {
+
+constexpr uint32_t B3W_TILE = 1024;                      // chunks per tile = items per merge group
+constexpr uint64_t RES_TB = (uint64_t)B3W_TILE * 1024;   // a tile's bytes
+constexpr uint64_t RS_SHORT = 64;                        // range slices: ranges of at most this many chunks take rows of 64 chunks
+
+inline uint64_t num_chunks(uint64_t len) { return len ? (len + 1023) / 1024 : 1; }
+inline uint64_t chunk_bytes(uint64_t len, uint64_t c) { return len - c * 1024 < 1024 ? len - c * 1024 : 1024; }
+inline uint32_t chunk_blocks(uint64_t len, uint64_t c) {
+  const uint64_t bytes = chunk_bytes(len, c);
+  return bytes ? (uint32_t)((bytes + 63) / 64) : 1;
+}
+// the units of a group outboard (groups of 1 << gl chunks, the last one ragged) and its bytes (b3w_bao_group_outboard_size; gl = 0:
+// b3w_bao_outboard_size)
+inline uint64_t n_units(uint64_t len, uint32_t gl) { return (num_chunks(len) + ((1ull << gl) - 1)) >> gl; }
+inline uint64_t group_outboard_bytes(uint64_t len, uint32_t gl) { return 8 + 64 * (n_units(len, gl) - 1); }
+inline uint64_t tiles_of(uint64_t len) { return (num_chunks(len) + B3W_TILE - 1) / B3W_TILE; }
+
+// the chunks of the left subtree of a subtree over m >= 2 chunks: the largest power of two strictly below m
+B3W_HD_INLINE uint64_t left_of(uint64_t m) { return 1ull << (63 - __builtin_clzll(m - 1)); }
+
+// path_len with the split from a bit scan: the parent nodes above chunk c of a subtree over m chunks, its root included
+B3W_HD_INLINE uint32_t depth_in(uint64_t c, uint64_t m) {
+  uint32_t p = 0;
+  for (; m > 1; ++p) {
+    const uint64_t k = left_of(m);
+    if (c < k) m = k; else { c -= k; m -= k; }
+  }
+  return p;
+}
+
+// the slice of chunk c, whose path has P nodes (b3w_bao_slice_size); the next slice start at or behind byte `end`: 8 modulo 16
+inline uint64_t slice_bytes(uint64_t len, uint64_t c, uint32_t P) { return 8 + 64ull * P + chunk_bytes(len, c); }
+inline uint64_t slice_start(uint64_t end) { return ((end + 7) & ~15ull) + 8; }
+
+// pre-order position, relative to the root of a tree over `total` chunks, of its node over chunks [a, a + size); the host walks use it too
+B3W_HD_INLINE uint64_t preorder_pos(uint64_t total, uint64_t a, uint64_t size) {
+  uint64_t p = 0, lo = 0, cnt = total;
+  while (cnt > 1 && !(lo == a && cnt == size)) {
+#ifdef __HIP_DEVICE_COMPILE__
+    const uint64_t k = 1ull << (63 - __clzll((long long)(cnt - 1)));
+#else
+    const uint64_t k = left_of(cnt);
+#endif
+    if (a < lo + k) { p += 1; cnt = k; } else { p += k; lo += k; cnt -= k; }
+  }
+  return p;
+}
+
+// ---- range slices: places (the format is described at the range kernels in b3w_bao.hip) ------------------------------------------------
+// U(a, c), a <= c < n
+B3W_HD inline uint64_t range_nodes(uint64_t n, uint64_t a, uint64_t c) {
+  uint64_t u = 0, lo = 0, m = n;
+  while (m > 1) {                                          // the nodes above the split: both ends go the same way
+    const uint64_t k = left_of(m);
+    if (c < lo + k) m = k;
+    else if (a >= lo + k) { lo += k; m -= k; }
+    else break;
+    ++u;
+  }
+  if (m <= 1) return u;                                    // (a == c: the chunk's path)
+  const uint64_t k = left_of(m);
+  ++u;                                                     // the split node: a on its left, c on its right
+  for (uint64_t l = lo, s = k; s > 1;) {                   // a's path below it: what lies right of a is inside
+    const uint64_t kk = left_of(s);
+    ++u;
+    if (a < l + kk) { u += s - kk - 1; s = kk; } else { l += kk; s -= kk; }
+  }
+  for (uint64_t l = lo + k, s = m - k; s > 1;) {           // c's path below it: what lies left of c is inside
+    const uint64_t kk = left_of(s);
+    ++u;
+    if (c >= l + kk) { u += kk - 1; l += kk; s -= kk; } else s = kk;
+  }
+  return u;
+}
+
+// the place within the slice of chunks [a, ..) of a file of n chunks of chunk c >= a, and of the node over [lo, lo + size) that meets it
+B3W_HD_INLINE uint64_t range_chunk_at(uint64_t n, uint64_t a, uint64_t c) { return 8 + 64 * range_nodes(n, a, c) + 1024 * (c - a); }
+B3W_HD_INLINE uint64_t range_node_at(uint64_t n, uint64_t a, uint64_t lo, uint64_t size) {
+  const uint64_t c0 = lo > a ? lo : a;
+  return range_chunk_at(n, a, c0) - 64ull * depth_in(c0 - lo, size);
+}
+
+inline uint64_t range_slice_bytes(uint64_t len, uint64_t n, uint64_t a, uint64_t k) {     // (a + k <= n, k >= 1)
+  const uint64_t end = (a + k) * 1024 < len ? (a + k) * 1024 : len;
+  return 8 + 64 * range_nodes(n, a, a + k - 1) + (end - a * 1024);
+}
+// the rows of a range: the blocks of 64 (short ranges) or 1 024 chunks it touches
+inline uint64_t range_rows(uint64_t a, uint64_t k) {
+  const uint64_t B = k <= RS_SHORT ? 64 : B3W_TILE;
+  return (a + k - 1) / B - a / B + 1;
+}
+
+// ---- files of at most 64 chunks share waves, in file order, as many as fit ----------------------------------------------------------
+// add(n): the first lane of a file of n chunks in its wave; `first` (may be null: counting) takes every wave's first file, and
+// close() the end of the last wave
+struct SmallPack {
+  uint64_t files = 0, waves = 0, fill = 64;              // fill: lanes taken in the current wave (none open yet)
+  uint32_t *first = nullptr;
+  uint32_t add(uint64_t n) {
+    if (fill + n > 64) { if (first) first[waves] = (uint32_t)files; waves++; fill = 0; }
+    const uint32_t lane = (uint32_t)fill;
+    fill += n;
+    files++;
+    return lane;
+  }
+  void close() { if (first && files) first[waves] = (uint32_t)files; }
+  uint64_t first_bytes() const { return files ? (waves + 1) * 4 : 0; }
+};
+
+// what a batch of these lengths launches: the small files' waves; the others take a workgroup per tile (big); files of more than one
+// tile a merge workgroup per 1 024 tiles (groups), files of more than 1 024 tiles one more over those (tops)
+struct BatchCounts { uint64_t small, waves, big, big_wgs, merged, groups, tops; bool too_long; };
+inline BatchCounts batch_counts(const uint64_t *lens, uint32_t n_files) {
+  BatchCounts k{};
+  SmallPack pack;
+  for (uint32_t f = 0; f < n_files; ++f) {
+    const uint64_t n = num_chunks(lens[f]);
+    if (n <= 64) { (void)pack.add(n); continue; }
+    const uint64_t tiles = (n + B3W_TILE - 1) / B3W_TILE, groups = (tiles + B3W_TILE - 1) / B3W_TILE;
+    k.big++; k.big_wgs += tiles;
+    if (tiles > 1) { k.merged++; k.groups += groups; }
+    if (groups > 1) k.tops++;
+    if (groups > B3W_TILE) k.too_long = true;
+  }
+  k.small = pack.files; k.waves = pack.waves;
+  return k;
+}
+
+// verification's scratch entries: one per tile of the files of more than one tile, one per group of 1 024 tiles of the files of more
+// than one group
+inline uint64_t verify_entries(const uint64_t *lens, uint32_t n_files, uint64_t *tile_ents) {
+  uint64_t tiles_sum = 0, groups_sum = 0;
+  for (uint32_t f = 0; f < n_files; ++f) {
+    const uint64_t tiles = tiles_of(lens[f]), groups = (tiles + B3W_TILE - 1) / B3W_TILE;
+    if (tiles > 1) tiles_sum += tiles;
+    if (groups > 1) groups_sum += groups;
+  }
+  if (tile_ents) *tile_ents = tiles_sum;
+  return tiles_sum + groups_sum;
+}
+
+// resize: scratch slots of a listed file at its new length: its tiles' CVs, then its spans' past 1 GiB; none for a file of one tile
+inline uint64_t resize_slots(uint64_t new_len) {
+  const uint64_t tiles = tiles_of(new_len);
+  return tiles > 1 ? tiles + (tiles > B3W_TILE ? (tiles + B3W_TILE - 1) / B3W_TILE : 0) : 0;
+}
+
+// ---- hashing on the host ------------------------------------------------------------------------------------------------------------
+// the CV of a chunk (the kernels' chunk_cv loop over blake3_cv)
+inline void host_chunk_cv(const uint8_t *src, uint32_t bytes, uint64_t c, uint32_t root, uint32_t h[8]) {
+  const uint32_t nb = bytes ? (bytes + 63) / 64 : 1;
+  iv(h);
+  for (uint32_t j = 0; j < nb; ++j) {
+    const uint32_t bb = bytes - j * 64 < 64 ? bytes - j * 64 : 64;
+    uint32_t m[16] = {}, o[8];
+    for (uint32_t q = 0; q < bb; ++q) m[q / 4] |= (uint32_t)src[j * 64 + q] << (8 * (q & 3));
+    blake3_cv(h, m, (uint32_t)c, (uint32_t)(c >> 32), bb, (j == 0 ? 1u : 0u) | (j == nb - 1 ? 2u | root : 0u), o);
+    for (int k = 0; k < 8; ++k) h[k] = o[k];
+  }
+}
+
+// BLAKE3's tree over the chunks [first, first + cnt) of a file of `len` bytes whose chunk base_chunk lies at `base` (root: they are
+// the whole file)
+inline void host_subtree_cv(const uint8_t *base, uint64_t base_chunk, uint64_t len, uint64_t first, uint64_t cnt, bool root, uint32_t h[8]) {
+  if (cnt == 1) {
+    host_chunk_cv(base + (first - base_chunk) * 1024, (uint32_t)chunk_bytes(len, first), first, root ? 8u : 0u, h);
+    return;
+  }
+  const uint64_t k = left_of(cnt);
+  uint32_t m[16], ivv[8];
+  host_subtree_cv(base, base_chunk, len, first, k, false, m);
+  host_subtree_cv(base, base_chunk, len, first + k, cnt - k, false, m + 8);
+  iv(ivv);
+  blake3_cv(ivv, m, 0, 0, 64, 4u | (root ? 8u : 0u), h);
+}
+
+}  // namespace

@@ -106,10 +106,25 @@ inline int32_t hip_fail(b3w_ctx *ctx, hipError_t e, const char *what) {
   if (ctx) ctx->last_error = std::string(what) + ": " + hipGetErrorString(e);
   return B3W_E_HIP;
 }
+// a bad argument: "<call>: <why>" (call null: the reason alone) for b3w_last_error
+inline int32_t refuse(b3w_ctx *ctx, const char *call, const std::string &why) {
+  ctx->last_error = call ? std::string(call) + ": " + why : why;
+  return B3W_E_BAD_ARGUMENT;
+}
+inline int32_t group_log_ok(b3w_ctx *ctx, const char *call, uint32_t group_log) {
+  return group_log > B3W_BAO_MAX_GROUP_LOG ? refuse(ctx, call, "group_log is above B3W_BAO_MAX_GROUP_LOG (6)") : B3W_OK;
+}
 #define HIP_TRY(ctx, call)                                  \
   do {                                                      \
     hipError_t _e = (call);                                 \
     if (_e != hipSuccess) return hip_fail(ctx, _e, #call);  \
+  } while (0)
+
+// a step of an entry point that returns a B3W_* code: anything but B3W_OK is the entry point's answer
+#define B3W_TRY(...)                  \
+  do {                                \
+    const int32_t _rc = (__VA_ARGS__);\
+    if (_rc) return _rc;              \
   } while (0)
 
 // Every entry point that touches the device runs with ctx->device current and puts the caller's device back on the
@@ -149,6 +164,8 @@ int32_t b3w_int_commit_records(b3w_ctx *ctx, const b3w_commit_key *key, const ui
                                int32_t *d_status, void *stream, uint32_t *d_sums_out, void *trace_stream = nullptr, hipEvent_t trace_done = nullptr);
 int32_t b3w_int_commit_normalize(b3w_ctx *ctx, const b3w_commit_key *key, const uint32_t *d_sums, uint64_t n, uint8_t *d_points, void *stream);
 b3w_ctx *b3w_int_r1cs_ctx(const b3w_r1cs *r1cs);
-// b3w_bao.hip: the context's staging for the batch calls' tables (h_batch / d_batch) — waits for the previous batch call, grows both to `bytes`
+// b3w_bao.hip: the context's staging for the batch calls' tables (h_batch / d_batch) — waits for the previous batch call, grows both to `bytes` —
+// and what follows the launches that read it: the launch error as `what`, else batch_done recorded on the stream
 int32_t b3w_int_batch_staging(b3w_ctx *ctx, uint64_t bytes);
+int32_t b3w_int_batch_launched(b3w_ctx *ctx, hipStream_t st, const char *what);
 constexpr uint64_t B3W_RING_SPARE_CAP = 26ull << 30;    // ring buffers a context keeps between chains: two 16 384-step nova buffers

@@ -1,15 +1,14 @@
 // bao_range_host_check.cpp — the host calls of the range slices (b3w_bao_range_slice_size, _batch_layout, b3w_bao_range_slice, _decode,
 // _ingest) run stand-alone over the files and range kinds of tests/test_bao_range_cpu.py, for a sanitizer build of host code that is never
 // loaded into Python:
-//   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -I include \
-//         hot-proofs-blake3-circom_amd/csrc/b3w_bao.hip hot-proofs-blake3-circom_amd/csrc/b3w_bao_have.hip tools/bao_range_host_check.cpp \
-//         -o bao_range_host_check && ./bao_range_host_check
+//   g++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -I include hot-proofs-blake3-circom_amd/csrc/b3w_bao_host.cpp
+//       tools/bao_range_host_check.cpp -o bao_range_host_check && ./bao_range_host_check          (one command line)
 // Every buffer is exactly as large as the contract says (the slice its size, range_bytes the touched groups clipped to the file, the
 // decoder's output the range's payload, the bitmap ceil(n / 64) words), so a read or write past one is the sanitizer's to report.  The
 // results are held against each other and against the library's older host calls: the slice from the full outboard equals the one from
 // every group outboard, a range of one chunk equals b3w_bao_slice, what is decoded is the file, every range taken in leaves the file
-// and the provider's outboard, which b3w_bao_verify accepts; a flipped byte is reported and keeps its chunk out.  No device call is made:
-// the functions of other object files that b3w_bao.hip names are stubs here.
+// and the provider's outboard, which b3w_bao_verify accepts; a flipped byte is reported and keeps its chunk out.  No device call is made
+// and no kernel compiled: b3w_bao_host.cpp is plain C++ and names nothing of another object file.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -19,13 +18,7 @@
 #include <utility>
 #include <vector>
 
-#include <hip/hip_runtime_api.h>
-
 #include "b3wit.h"
-
-// what b3w_bao.hip names of object files that are not linked here (device plumbing: never reached by the host calls)
-int32_t b3w_chain_tree_device(b3w_ctx *, uint32_t *, uint64_t, uint32_t *, void *) { abort(); }
-extern "C" uint32_t b3w_plan_path_len(uint64_t, uint64_t) { abort(); }
 
 static long checks = 0;
 #define CHECK(cond, ...)                                              \
