@@ -231,8 +231,10 @@ bool reference_trace(int circuit, uint32_t site, std::string &text) {
   return false;
 }
 
-// VERIFY mode: record word j of a witness is read back from slot in_slots[j] of its body (the slot the
-// layout gives the whole input atom: compression atoms 1..28, nova atoms NV+0..31 in record order)
+// VERIFY mode: record word j of a witness is read back from slot in_slots[j] of its body (the FIRST whole-word slot, in
+// file order, the layout gives the input atom: compression atoms 1..28, nova atoms NV+0..31 in record order — for nova
+// words 0 and 10..13 that is a public output sharing the atom; every other copy is compared like any slot.  DESIGN.md
+// section 5 has the table, tests/test_verify_ref_cpu.py pins it by value)
 bool build_input_slots(const CircuitDesc &c, std::vector<uint32_t> &slots) {
   slots.assign(c.nin, 0xFFFFFFFFu);
   const uint32_t first = c.kind == B3W_KIND_COMP ? B3W_A_H : B3W_A_NV;

@@ -258,7 +258,11 @@ void b3w_r1cs_consumer(void *user, const uint8_t *d_bodies, uint64_t pitch, uint
  * slots; the kernel reads each body once (HBM-read bound) and compares every 16-byte unit.
  * d_mismatch[i] = number of differing units of body i: 0 = valid witness; 0xFFFFFFFF = the body's inputs are
  * rejected by the circuit, are not plain 32-bit values, or make a record that b3w_batch_run_device answers with 103
- * (outside this path's domain: DESIGN.md "Input domain" has the closed-form rule).  Stands where the
+ * (outside this path's domain: DESIGN.md "Input domain" has the closed-form rule).
+ * The record is read from the FIRST slot the layout gives each input atom — compression: slots 17..44; nova: word 0 from slot 1,
+ * words 1..9 from 17..25, 10..13 from 13, 14, 15, 11, words 14..31 from 28..45, i.e. for words 0 and 10..13 from the public OUTPUTS
+ * that share the input's atom (n_blocks_out, chunk_idx_low_out, chunk_idx_high_out, leaf_depth_out, total_depth_out).  Every other
+ * copy of an input atom (nova slots 16, 26, 27) is compared like any slot: tampered alone it counts as one differing unit.  Stands where the
  * reference's consumers check a witness against the R1CS (circom_tester expectPass, test/blake3_hash.test.ts:36;
  * synthesize_with_vec's constraints, rust_fold/src/utils.rs:17-88). */
 int32_t b3w_batch_verify_device(b3w_ctx *ctx, const uint8_t *d_bodies, uint32_t n, uint64_t pitch, uint32_t *d_mismatch,
