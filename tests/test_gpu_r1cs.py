@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import b3w_testlib as T
+import r1cs_cases as C
 import r1cs_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -81,10 +82,9 @@ def test_kernel_witnesses_pass_and_1000_single_slot_corruptions_fail(env):
         changed.append((s, new))
     viol, first = _check(env, torch.from_numpy(host).to(env["dev"]))
     assert (viol > 0).all(), np.nonzero(viol == 0)[0][:10]
-    for i in range(0, n, 9):                          # every 9th body against the integer evaluation of the rows that read the slot
+    for i in range(n):                                # every body against the integer evaluation of the rows that read the slot
         s, new = changed[i]
-        z = R.body_to_ints(host[i])
-        want = R.violated(sys_, z, by_wire[s])
+        want = C.changed_violated(sys_, C.BodyView(host[i]), s, by_wire)
         assert viol[i] == len(want) and first[i] == min(want), (i, s)
 
 
@@ -199,8 +199,8 @@ def test_nova_o1_build_on_the_device():
         host[i, 32 * s:32 * s + 32] = np.frombuffer(new.to_bytes(32, "little"), dtype=np.uint8)
     viol, first = check(torch.from_numpy(host).to(dev))
     assert (viol > 0).all(), np.nonzero(viol == 0)[0][:10]
-    for i in range(0, n, 7):
-        want = R.violated(sys_, R.body_to_ints(host[i]), by_wire[slots[i]])
+    for i in range(n):
+        want = C.changed_violated(sys_, C.BodyView(host[i]), slots[i], by_wire)
         assert viol[i] == len(want) and first[i] == min(want), (i, slots[i])
     g = T.golden("nova_bn254_o1")
     wild = [c for c in g["cases"] if "error" not in c and not T.is_canonical_u32("nova_bn254_o1", c["input"])][:5]
@@ -254,8 +254,8 @@ def test_nova_o2_builds_on_the_device(circuit):
         host[i, 32 * s:32 * s + 32] = np.frombuffer(new.to_bytes(32, "little"), dtype=np.uint8)
     viol, first = check(torch.from_numpy(host).to(dev))
     assert (viol > 0).all(), np.nonzero(viol == 0)[0][:10]
-    for i in range(0, n, 7):
-        want = R.violated(sys_, R.body_to_ints(host[i]), by_wire[slots[i]])
+    for i in range(n):
+        want = C.changed_violated(sys_, C.BodyView(host[i]), slots[i], by_wire)
         assert viol[i] == len(want) and first[i] == min(want), (i, slots[i])
     g = T.golden(circuit)
     wild = [c for c in g["cases"] if "error" not in c and not T.is_canonical_u32(circuit, c["input"])][:5]
