@@ -795,6 +795,67 @@ def ingest_range_slices(ctx, d_arena, offsets, lens, d_outboards, d_roots, files
     return dict(range_status=st, range_first_bad=fb)
 
 
+def sample_rows_ranges(lens, files, first_chunks, n_chunks):
+    """-> (range_row_first uint64 [n_ranges + 1], chunk_row_first uint64 [total chunks + 1], provable bool [total chunks]): the record
+    rows of ranges (files[r], first_chunks[r], n_chunks[r]) — exactly sample_rows_batch over runs_chunks of the same ranges, the
+    per-range firsts from a closed form — and b3w_chain_path_provable of every chunk, in runs_chunks' order"""
+    ln = _u64(lens)
+    fi = np.ascontiguousarray(files, dtype=np.uint32)
+    fc, nc = _ranges(first_chunks, n_chunks)
+    if fi.size != fc.size:
+        raise B3WError(100, f"sample_rows_ranges: {fi.size} files and {fc.size} ranges")
+    rrf = np.zeros(fc.size + 1, dtype=np.uint64)
+    args = (ln.ctypes.data, ln.size, fi.ctypes.data, fc.ctypes.data, nc.ctypes.data, fc.size, rrf.ctypes.data)
+    if lib().b3w_sample_rows_ranges(*args, None, None) < 0:               # (the ranges are checked before the per-chunk arrays are sized by them)
+        raise B3WError(100, "b3w_sample_rows_ranges: a file index is not below the file count, or a range is empty or reaches past its file's chunk count")
+    total = int(nc.sum(dtype=np.uint64))
+    crf = np.zeros(total + 1, dtype=np.uint64)
+    prov = np.zeros(max(total, 1), dtype=np.uint8)
+    lib().b3w_sample_rows_ranges(*args, crf.ctypes.data, prov.ctypes.data)
+    return rrf, crf, prov[:total].astype(bool)
+
+
+def plan_samples_range_slices(ctx, lens, d_roots, files, first_chunks, n_chunks, d_slices, stream=0):
+    """The prover's side for challenged RUNS of chunks: plan_samples_slices from range slices (range_slices_arena's tensor, or slices
+    received and packed as range_slice_layout says) and the files' roots on the device — no outboard, no arena.  Every chunk gets the
+    status and, word for word, the records plan_samples_slices gives its own one-chunk slice (the projection of the range slice onto
+    it); a bad node spoils the chunks below it and no other; ranges may overlap, repeat and come in any order.  At most three
+    launches.  When not to (MI355X, DESIGN.md §8g, against a build of the commit before planning one-chunk slices of the same chunks
+    with b3w_sample_plan_slices_device): 64 runs of 1 024 chunks of a 1 GiB file 0.43 ms against 1.71, 4 096 runs of 16 0.53 against
+    1.72 — but a range takes at least a wave, so 65 536 runs of ONE chunk take 7.9 ms against 1.7 and the 262 507 runs of a
+    half-missing bitmap 23.4 against 13.4: runs of one or two chunks are faster to plan through runs_chunks and plan_samples_slices;
+    where between 2 and 16 chunks a run the two cross was not measured.  This wrapper makes its outputs and scratch on every call.
+    Returns the dict plan_samples_slices returns, keyed per chunk in runs_chunks order (records, row_first, sample_status, provable),
+    plus range_row_first (uint64 [n_ranges + 1]), range_status (int32 CUDA) and range_first_bad (int64 CUDA, -1 for none)."""
+    L = lib()
+    ln = _u64(lens)
+    fi = np.ascontiguousarray(files, dtype=np.uint32)
+    fc, nc = _ranges(first_chunks, n_chunks)
+    rrf, crf, provable = sample_rows_ranges(ln, fi, fc, nc)
+    sf = range_slice_layout(ln, fi, fc, nc)
+    dev = d_slices.device
+    assert d_roots.is_cuda and d_roots.is_contiguous() and d_roots.numel() >= ln.size * 8
+    assert d_slices.is_cuda and d_slices.dtype == torch.uint8 and d_slices.is_contiguous() and d_slices.numel() >= int(sf[-1])
+    recs = torch.empty((int(rrf[-1]), 32), dtype=torch.int32, device=dev)
+    st = torch.full((provable.size,), -1, dtype=torch.int32, device=dev)
+    rst = torch.full((fc.size,), -1, dtype=torch.int32, device=dev)
+    rfb = torch.full((fc.size,), -2, dtype=torch.int64, device=dev)
+    need = L.b3w_bao_range_slice_ingest_scratch_bytes(ln.ctypes.data, ln.size, fi.ctypes.data, fc.ctypes.data, nc.ctypes.data, fc.size)
+    scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    _chk(ctx, L.b3w_sample_plan_range_slices_device(ctx.handle, ln.ctypes.data, ln.size, d_roots.data_ptr(), fi.ctypes.data, fc.ctypes.data, nc.ctypes.data,
+                                                    fc.size, d_slices.data_ptr(), recs.data_ptr(), st.data_ptr(), rst.data_ptr(), rfb.data_ptr(),
+                                                    scratch.data_ptr(), scratch.numel(), _stream(stream)), "b3w_sample_plan_range_slices_device")
+    return dict(records=recs, row_first=crf, sample_status=st.cpu().numpy(), provable=provable, range_row_first=rrf, range_status=rst, range_first_bad=rfb)
+
+
+def prove_samples_range_slices(ctx, lens, d_roots, files, first_chunks, n_chunks, d_slices, batch_steps=4096, consumer=None, commit_key=None, r1cs=None,
+                               stream=0):
+    """prove_samples_slices over plan_samples_range_slices' plan"""
+    s = _stream(stream)
+    out = plan_samples_range_slices(ctx, lens, d_roots, files, first_chunks, n_chunks, d_slices, stream=s)
+    return _prove_planned(ctx, out, batch_steps, consumer, commit_key, r1cs, s)
+
+
 def range_slice_host(outboard, length, first_chunk, n_chunks, range_bytes, group_log=0):
     """The slice of one range on the host (no GPU) from the file's outboard of this group_log and range_bytes: the bytes of the
     range's chunks (group_log 0) or of the whole groups it touches (above 0) -> bytes"""

@@ -39,6 +39,8 @@
 //                            (b3w_bao_stream_open_relocate_many_kernel: the blocks of many sessions moved in one grid)
 //   b3w_bao_range_*_kernel   the slice of a RUN of chunks (bao's general slice, every shared node once) extracted from the arena and the
 //                            outboards and taken in again, a row per (range, block of 64 or 1 024 chunks) ("range slices", at the end)
+//   b3w_sample_plan_range_kernel  the step records of a RUN of challenged chunks planned from its range slice alone, on the same rows:
+//                            b3w_sample_plan_slices_kernel's records and statuses for every chunk's projection (behind the range kernels)
 //
 // The routes (batch table, one streamed file by value, a table of sessions, update / ranges / resize rows) differ only in where a file's
 // entry comes from.  Each kernel, or its *_body wrapper, finds its entry and calls one of the bodies every route shares:
@@ -3532,7 +3534,7 @@ int32_t b3w_bao_outboard_resize_batch_device(b3w_ctx *ctx, const uint8_t *d_aren
 //   b3w_bao_range_reduce_kernel      a wave per range: the largest status and the first bad chunk over the range's rows.
 namespace {
 
-// a range's entry and a workgroup's row of the two device calls' table
+// a range's entry and a workgroup's row of the two device calls' table (the planner's entry: `off` is the range's first chunk status)
 struct RsRange { uint64_t len, off, ob, slice, first, count, have; uint32_t file, row0; };   // have: the file's first bitmap word; row0: its first row
 struct RsRow { uint32_t range, block; };
 
@@ -3758,20 +3760,148 @@ __global__ __launch_bounds__(256) void b3w_bao_range_reduce_kernel(const RsRange
   if (lane == 0) { range_status[i] = (int32_t)w; range_first_bad[i] = f; }
 }
 
+// ---- step records from range slices: the prover's side -----------------------------------------------------------------------------------
+// b3w_sample_plan_slices_kernel's records and statuses for the projection of the range slice onto every chunk of the range, on the row
+// shape of the receiver (b3w_bao_range_ingest_kernel<B>: lane = chunk, every node of the block hashed once):
+//   0. where a lane's rows start: the row's base (a 64-bit field of its table entry, from the host's closed form rows_before) plus the
+//      prefix sum over the block's lanes of blocks + path nodes (a wave's by shuffles, the waves' totals through LDS)
+//   1. the range's lanes run plan_leaf_chunk on their chunk's bytes in the slice: the leaf records in place, the chunk's CV to LDS
+//   2. - 4. the receiver's verdicts: the block's tree with ranges_pair<true>, the nodes above the block side by side (their places kept in
+//      LDS for step 5), the verdicts down through the flags (path_bad); the chunk's status out, the row's result to the scratch
+//   5. the parent records, bottom up, each from the slice's own node: a verified chunk with a provable path gets parent_record from the
+//      on-path and sibling halves; any other the plan_parent_step chain on its lane.
+// Every row of 128 bytes is written by the lane that owns the chunk.  `off` of the range's entry is its first chunk status.
+struct RpRow { uint32_t range, block; uint64_t row; };    // row: the first record row of the block's first chunk of the range
+
+template <int B>
+__global__ __launch_bounds__(B) void b3w_sample_plan_range_kernel(const RsRange *__restrict__ ranges, const RpRow *__restrict__ rows,
+                                                                  const uint8_t *__restrict__ slices, const uint32_t *__restrict__ roots,
+                                                                  uint32_t *__restrict__ recs, int32_t *__restrict__ chunk_status,
+                                                                  uint4 *__restrict__ results) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B * 8];
+  __shared__ uint32_t flags[B], listed[B], before[B];
+  __shared__ uint64_t above_at[64];
+  __shared__ uint32_t wave_rows[B / 64], worst, first, above;
+  const RpRow row = rows[blockIdx.x];
+  const RsRange r = ranges[row.range];
+  const RsBlock b = range_block<B>(r, row.block);
+  const uint32_t t = threadIdx.x;
+  const bool mine = t >= b.lo && t < b.hi;
+  const uint8_t *__restrict__ sl = slices + r.slice;
+  const uint32_t *__restrict__ root = roots + (uint64_t)r.file * 8;
+  const uint64_t c = b.a0 + t;
+  const uint32_t P = mine ? depth_in(c, b.n) : 0, bytes = mine ? range_chunk_bytes(b.len, c) : 0, n_blocks = bytes ? (bytes + 63) / 64 : 1;
+  listed[t] = mine ? 1u : 0u;
+  flags[t] = 0;
+  if (t == 0) { worst = 0; first = ~0u; above = 0; }
+  // 0. the lane's first row
+  const uint32_t own = mine ? n_blocks + P : 0;
+  uint32_t upto = own;
+#pragma unroll
+  for (int d = 1; d < 64; d *= 2) {
+    const uint32_t o = __shfl_up(upto, d);
+    if ((t & 63) >= (uint32_t)d) upto += o;
+  }
+  if ((t & 63) == 63) wave_rows[t >> 6] = upto;
+  __syncthreads();
+  uint32_t ahead = upto - own;
+  for (uint32_t w = 0; w < (t >> 6); ++w) ahead += wave_rows[w];
+  uint32_t *__restrict__ rec = recs + (row.row + ahead) * 32;
+  // 1. the leaf records and the chunks' CVs
+  uint32_t h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (mine) {
+    const uint64_t u = range_nodes(b.n, b.a, c);
+    before[t] = (uint32_t)u;
+    plan_leaf_chunk(sl + 8 + 64 * u + 1024 * (c - b.a), bytes, c, P, rec, h);   // (16-byte aligned; P == 0: the ROOT-flagged output)
+    put_cv(cv, t, h);
+  }
+  // 2. - 4. the verdicts, as the receiver reaches them
+  const RsAbove up = range_above(b.n, b.a0, b.m, t);
+  if (t < up.depth) {
+    uint32_t mw[16], ivv[8], o[8];
+    const uint64_t at = range_node_at(b.n, b.a, up.lo, up.cnt);
+    above_at[t] = at;
+    load_node(sl + at, mw);
+    iv(ivv);
+    blake3_cv(ivv, mw, 0, 0, 64, 4u | (t == 0 ? 8u : 0u), o);
+    const uint32_t *want = t == 0 ? root : reinterpret_cast<const uint32_t *>(sl + range_node_at(b.n, b.a, up.plo, up.pcnt) + (up.left ? 0 : 32));
+    if (!eq8(o, want)) atomicOr(&above, 1u);
+  }
+  for (uint32_t l = 0; (1u << l) < b.m; ++l) {
+    lds_barrier();
+    const uint32_t i0 = (2 * t) << l, i1 = i0 + (1u << l);
+    if (i1 >= b.m) continue;
+    const bool d0 = listed[i0] != 0, d1 = listed[i1] != 0;
+    if (!d0 && !d1) continue;
+    const uint32_t end = i0 + (2u << l), size = (end < b.m ? end : b.m) - i0;
+    ranges_pair<true>(cv, flags, nullptr, i0, i1, d0, d1, l, sl + range_block_node_at(b, before, i0, size), 4u | (b.sole && (2u << l) >= b.m ? 8u : 0u),
+                      1ull << l, size - (1u << l), 1, nullptr);
+    listed[i0] = 1;
+  }
+  lds_barrier();
+  if (t == 0) {
+    const uint32_t *want = up.depth ? reinterpret_cast<const uint32_t *>(sl + range_node_at(b.n, b.a, up.last_lo, up.last_cnt) + (up.last_left ? 0 : 32)) : root;
+    if (!eq8(cv, want)) flags[0] |= b.m == 1 ? VER_UNIT : VER_TOP;
+  }
+  lds_barrier();
+  const uint2 hd = *reinterpret_cast<const uint2 *>(sl);
+  const bool hdr = ((uint64_t)hd.x | ((uint64_t)hd.y << 32)) != b.len;
+  uint32_t st = 0;
+  if (mine) {
+    st = hdr ? 3u : above || path_bad(flags, t) ? 2u : (flags[t] & VER_UNIT) ? 1u : 0u;
+    chunk_status[r.off + (c - b.a)] = (int32_t)st;
+    if (st) { atomicMax(&worst, st); atomicMin(&first, t); }
+  }
+  __syncthreads();
+  if (t == 0) results[blockIdx.x] = make_uint4(worst, 0, first == ~0u ? ~0u : (uint32_t)(b.a0 + first), first == ~0u ? ~0u : (uint32_t)((b.a0 + first) >> 32));
+  if (!mine) return;
+  // 5. the parent records: the block's nodes on the lane's path bottom up, then the nodes above the block
+  const bool chain = st != 0 || !path_provable(c, b.n);
+  uint32_t g = 0;
+  rec += (uint64_t)n_blocks * 32;
+  const auto step = [&](uint64_t at) {
+    uint32_t mw[16], on[8], sib[8];
+    load_node(sl + at, mw);
+    const bool bit_left = ((c >> g) & 1) == 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { on[k] = bit_left ? mw[k] : mw[8 + k]; sib[k] = bit_left ? mw[8 + k] : mw[k]; }
+    if (chain) plan_parent_step(rec, h, sib, bit_left, c, n_blocks, P, P - 1 - g);
+    else {
+      if (g) {                                             // (every node hashed to its half of the node above: h at height g is that half)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) h[k] = on[k];
+      }
+      parent_record(rec, h, sib, c, n_blocks, P, P - 1 - g);
+    }
+    rec += 32; ++g;
+  };
+  for (uint32_t l = 0; (1u << l) < b.m; ++l) {
+    const uint32_t i0 = (t >> (l + 1)) << (l + 1), i1 = i0 + (1u << l);
+    if (i1 >= b.m) continue;
+    const uint32_t end = i0 + (2u << l), size = (end < b.m ? end : b.m) - i0;
+    step(range_block_node_at(b, before, i0, size));
+  }
+  for (uint32_t j = up.depth; j-- > 0;) step(above_at[j]);
+}
+
 struct RangeRows { uint64_t big, small; };                // rows of 1 024 chunks, rows of 64
 
-// every refusal the two calls share that concerns the ranges; counts the rows
+// every refusal the range calls share that concerns the ranges; counts the rows.  The planner has no arena (null host_offsets: the arena
+// is not looked at) and a longest file (most_chunks; 0: none).
 int32_t range_list_ok(b3w_ctx *ctx, const char *what, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
-                      uint32_t n_files, const uint32_t *host_files, const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, RangeRows &rows) {
+                      uint32_t n_files, const uint32_t *host_files, const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, RangeRows &rows,
+                      uint64_t most_chunks = 0) {
   rows = RangeRows{};
   for (uint32_t i = 0; i < n_ranges; ++i) {
     const char *why = nullptr;
     const uint32_t f = host_files[i];
     if (f >= n_files) why = "its file index is not below the file count";
     else {
-      const uint64_t n = num_chunks(host_lens[f]), off = host_offsets[f], len = host_lens[f];
+      const uint64_t n = num_chunks(host_lens[f]), off = host_offsets ? host_offsets[f] : 0, len = host_lens[f];
       if (host_count[i] == 0) why = "it has no chunk";
       else if (host_first[i] >= n || host_count[i] > n - host_first[i]) why = "it reaches past its file's chunk count";
+      else if (most_chunks && n > most_chunks) why = "its file has more than 2^30 chunks";
+      else if (!host_offsets) why = nullptr;
       else if (len && !d_arena) why = "a null arena with a file that is not empty";
       else if (off > arena_bytes || len > arena_bytes - off) why = "its file reaches past arena_bytes";
     }
@@ -3783,14 +3913,16 @@ int32_t range_list_ok(b3w_ctx *ctx, const char *what, const uint8_t *d_arena, ui
 }
 
 // the table into the staging and on its way: the ranges' entries, the rows of 1 024 chunks, the rows of 64 (behind them, host only, the
-// files' outboard offsets and bitmap words)
-int32_t range_table(b3w_ctx *ctx, const uint64_t *host_offsets, const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint32_t *host_files,
+// files' outboard offsets and bitmap words).  The call says what a range's `off` is (off_of(i, file), asked once a range, in order, before
+// the range's rows) and makes its own kind of row (make_row(i, block, B)).
+template <class Row, class Off, class Make>
+int32_t range_table(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint32_t *host_files,
                     const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, RangeRows rows, hipStream_t st, const RsRange *&d_ranges,
-                    const RsRow *&d_big, const RsRow *&d_small) {
-  const uint64_t up_bytes = (uint64_t)n_ranges * sizeof(RsRange) + (rows.big + rows.small) * sizeof(RsRow);
+                    const Row *&d_big, const Row *&d_small, Off off_of, Make make_row) {
+  const uint64_t up_bytes = (uint64_t)n_ranges * sizeof(RsRange) + (rows.big + rows.small) * sizeof(Row);
   B3W_TRY(batch_staging(ctx, up_bytes + 2 * ((uint64_t)n_files + 1) * 8));
   RsRange *rg = reinterpret_cast<RsRange *>(ctx->h_batch);
-  RsRow *big = reinterpret_cast<RsRow *>(rg + n_ranges), *small = big + rows.big;
+  Row *big = reinterpret_cast<Row *>(rg + n_ranges), *small = big + rows.big;
   uint64_t *ob_first = reinterpret_cast<uint64_t *>(small + rows.small), *word_first = ob_first + n_files + 1;
   (void)b3w_bao_group_batch_layout(host_lens, n_files, group_log, ob_first);        // (group_log 0: b3w_bao_batch_layout's)
   (void)b3w_bao_have_layout(host_lens, n_files, word_first);
@@ -3800,17 +3932,24 @@ int32_t range_table(b3w_ctx *ctx, const uint64_t *host_offsets, const uint64_t *
     const uint64_t len = host_lens[f], a = host_first[i], k = host_count[i];
     const bool shrt = k <= RS_SHORT;
     const uint64_t B = shrt ? 64 : B3W_TILE, b0 = a / B, b1 = (a + k - 1) / B;
-    rg[i] = RsRange{len, host_offsets[f], ob_first[f], at, a, k, word_first[f], f, (uint32_t)(shrt ? rows.big + ns : nb)};
-    RsRow *out = shrt ? small + ns : big + nb;
-    for (uint64_t blk = b0; blk <= b1; ++blk) *out++ = RsRow{i, (uint32_t)blk};
+    rg[i] = RsRange{len, off_of(i, f), ob_first[f], at, a, k, word_first[f], f, (uint32_t)(shrt ? rows.big + ns : nb)};
+    Row *out = shrt ? small + ns : big + nb;
+    for (uint64_t blk = b0; blk <= b1; ++blk) *out++ = make_row(i, blk, B);
     (shrt ? ns : nb) += b1 - b0 + 1;
     at = slice_start(at + range_slice_bytes(len, num_chunks(len), a, k));
   }
   HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)up_bytes, hipMemcpyHostToDevice, st));
   d_ranges = reinterpret_cast<const RsRange *>(ctx->d_batch);
-  d_big = reinterpret_cast<const RsRow *>(d_ranges + n_ranges);
+  d_big = reinterpret_cast<const Row *>(d_ranges + n_ranges);
   d_small = d_big + rows.big;
   return B3W_OK;
+}
+// the provider's and the receiver's table: `off` is the file's place in the arena, a row its range and block
+int32_t range_table(b3w_ctx *ctx, const uint64_t *host_offsets, const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint32_t *host_files,
+                    const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, RangeRows rows, hipStream_t st, const RsRange *&d_ranges,
+                    const RsRow *&d_big, const RsRow *&d_small) {
+  return range_table<RsRow>(ctx, host_lens, n_files, group_log, host_files, host_first, host_count, n_ranges, rows, st, d_ranges, d_big, d_small,
+                            [&](uint32_t, uint32_t f) { return host_offsets[f]; }, [](uint32_t i, uint64_t blk, uint64_t) { return RsRow{i, (uint32_t)blk}; });
 }
 
 }  // namespace
@@ -3872,6 +4011,54 @@ int32_t b3w_bao_range_slice_ingest_device(b3w_ctx *ctx, uint8_t *d_arena, uint64
   hipLaunchKernelGGL(b3w_bao_range_reduce_kernel, dim3((n_ranges + 3) / 4), dim3(256), 0, st, d_ranges, n_ranges, res, d_range_status,
                      reinterpret_cast<unsigned long long *>(d_range_first_bad));
   return batch_launched(ctx, st, "bao range slice ingest launch");
+}
+
+// ---- step records of challenged chunk runs from range slices --------------------------------------------------------------------------
+int32_t b3w_sample_plan_range_slices_device(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, const uint32_t *d_roots, const uint32_t *host_files,
+                                            const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, const uint8_t *d_slices,
+                                            uint32_t *d_records, int32_t *d_chunk_status, int32_t *d_range_status, uint64_t *d_range_first_bad,
+                                            void *d_scratch, uint64_t scratch_bytes, void *stream) {
+  const char *call = "sample plan range slices";
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  B3W_TRY(nova_ok(ctx));
+  if (!n_ranges) return B3W_OK;
+  if (!host_lens || !d_roots || !host_files || !host_first || !host_count || !d_slices || !d_records || !d_chunk_status || !d_range_status || !d_range_first_bad)
+    return refuse(ctx, call, "a null pointer");
+  if (((uintptr_t)d_slices & 15) || ((uintptr_t)d_roots & 3)) return refuse(ctx, call, "d_slices is not 16-byte or d_roots not 4-byte aligned");
+  if (((uintptr_t)d_records & 3) || ((uintptr_t)d_chunk_status & 3)) return refuse(ctx, call, "d_records or d_chunk_status is not 4-byte aligned");
+  if (((uintptr_t)d_range_status & 3) || ((uintptr_t)d_range_first_bad & 7)) return refuse(ctx, call, "d_range_status is not 4-byte or d_range_first_bad not 8-byte aligned");
+  RangeRows rows;
+  B3W_TRY(range_list_ok(ctx, call, nullptr, 0, nullptr, host_lens, n_files, host_files, host_first, host_count, n_ranges, rows, 1ull << 30));
+  if (scratch_bytes < (rows.big + rows.small) * 16) return refuse(ctx, call, "the scratch is smaller than b3w_bao_range_slice_ingest_scratch_bytes says");
+  if (!d_scratch || ((uintptr_t)d_scratch & 15)) return refuse(ctx, call, "the scratch is null or not 16-byte aligned");
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  const RsRange *d_ranges = nullptr;
+  const RpRow *d_big = nullptr, *d_small = nullptr;
+  // a range's `off` is its first chunk status; a row carries the first record row of its first chunk of the range (rows_before: O(depth))
+  uint64_t next_row = 0, next_chunk = 0, range_row = 0;
+  B3W_TRY(range_table<RpRow>(ctx, host_lens, n_files, 0, host_files, host_first, host_count, n_ranges, rows, st, d_ranges, d_big, d_small,
+                             [&](uint32_t i, uint32_t f) {
+                               const uint64_t len = host_lens[f], n = num_chunks(len), chunk0 = next_chunk;
+                               range_row = next_row;
+                               next_row += rows_before(len, n, host_first[i] + host_count[i]) - rows_before(len, n, host_first[i]);
+                               next_chunk += host_count[i];
+                               return chunk0;
+                             },
+                             [&](uint32_t i, uint64_t blk, uint64_t B) {
+                               const uint64_t len = host_lens[host_files[i]], n = num_chunks(len), a = host_first[i], c0 = blk * B > a ? blk * B : a;
+                               return RpRow{i, (uint32_t)blk, range_row + rows_before(len, n, c0) - rows_before(len, n, a)};
+                             }));
+  uint4 *res = reinterpret_cast<uint4 *>(d_scratch);
+  if (rows.big)
+    hipLaunchKernelGGL(b3w_sample_plan_range_kernel<(int)B3W_TILE>, dim3((uint32_t)rows.big), dim3(B3W_TILE), 0, st, d_ranges, d_big, d_slices, d_roots, d_records,
+                       d_chunk_status, res);
+  if (rows.small)
+    hipLaunchKernelGGL(b3w_sample_plan_range_kernel<64>, dim3((uint32_t)rows.small), dim3(64), 0, st, d_ranges, d_small, d_slices, d_roots, d_records, d_chunk_status,
+                       res + rows.big);
+  hipLaunchKernelGGL(b3w_bao_range_reduce_kernel, dim3((n_ranges + 3) / 4), dim3(256), 0, st, d_ranges, n_ranges, res, d_range_status,
+                     reinterpret_cast<unsigned long long *>(d_range_first_bad));
+  return batch_launched(ctx, st, "sample plan range slices launch");
 }
 
 }  // extern "C"

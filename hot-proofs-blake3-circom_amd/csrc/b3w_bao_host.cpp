@@ -552,6 +552,31 @@ uint64_t b3w_bao_range_slice_ingest_scratch_bytes(const uint64_t *host_lens, uin
   return rows * 16;                                       // a row's status and first bad chunk
 }
 
+int64_t b3w_sample_rows_ranges(const uint64_t *host_lens, uint32_t n_files, const uint32_t *host_files, const uint64_t *host_first,
+                               const uint64_t *host_count, uint32_t n_ranges, uint64_t *range_row_first, uint64_t *chunk_row_first,
+                               uint8_t *chunk_provable) {
+  if (!range_row_first || (n_ranges && (!host_lens || !host_files || !host_first || !host_count))) return -B3W_E_BAD_ARGUMENT;
+  for (uint32_t i = 0; i < n_ranges; ++i)
+    if (host_files[i] >= n_files || !b3w_bao_range_slice_size(host_lens[host_files[i]], host_first[i], host_count[i])) return -B3W_E_BAD_ARGUMENT;
+  uint64_t row = 0, at = 0;
+  for (uint32_t i = 0; i < n_ranges; ++i) {
+    const uint64_t len = host_lens[host_files[i]], n = num_chunks(len), a = host_first[i], k = host_count[i];
+    range_row_first[i] = row;
+    if (chunk_row_first || chunk_provable) {               // (asked for: the one loop over chunks)
+      uint64_t r = row;
+      for (uint64_t c = a; c < a + k; ++c, ++at) {
+        if (chunk_row_first) chunk_row_first[at] = r;
+        if (chunk_provable) chunk_provable[at] = path_provable(c, n) ? 1 : 0;
+        r += chunk_blocks(len, c) + depth_in(c, n);
+      }
+    }
+    row += rows_before(len, n, a + k) - rows_before(len, n, a);
+  }
+  range_row_first[n_ranges] = row;
+  if (chunk_row_first) chunk_row_first[at] = row;
+  return (int64_t)row;
+}
+
 int64_t b3w_bao_range_slice(const uint8_t *outboard, uint64_t len, uint32_t group_log, uint64_t first_chunk, uint64_t n_chunks, const uint8_t *range_bytes,
                             uint8_t *out, uint64_t out_len) {
   const uint64_t size = b3w_bao_range_slice_size(len, first_chunk, n_chunks);

@@ -101,6 +101,38 @@ inline uint64_t range_rows(uint64_t a, uint64_t k) {
   return (a + k - 1) / B - a / B + 1;
 }
 
+// ---- step records of a run of chunks: where a chunk's rows start (b3w_sample_rows_ranges, the range planner's table) ------------------
+// the sum of depth_in(i, n) over the chunks i < c of a tree over n chunks, c <= n, in the manner of range_nodes: the walk follows chunk
+// c's path, and a left subtree of k = 2^j chunks that lies wholly in front of c gives k (d + 1 + j), d the nodes above it: O(depth)
+inline uint64_t path_sum(uint64_t n, uint64_t c) {
+  uint64_t s = 0;
+  for (uint64_t d = 0; c; ++d) {
+    if (n == 1) return s + d;                              // (c == 1: the subtree's only chunk)
+    const uint64_t k = left_of(n), each = d + 1 + (uint64_t)__builtin_ctzll(k);
+    if (c <= k) return s + c * each;
+    s += k * each;
+    c -= k; n -= k;
+  }
+  return s;
+}
+// the record rows of the chunks in front of chunk c <= n of a file of len bytes, n chunks: a row a block (every chunk but the last has
+// sixteen) and one a path node, as b3w_sample_rows_batch counts them chunk by chunk
+inline uint64_t rows_before(uint64_t len, uint64_t n, uint64_t c) {
+  return 16 * (c < n ? c : n - 1) + (c == n ? chunk_blocks(len, n - 1) : 0) + path_sum(n, c);
+}
+// do the low bits of chunk c's index spell its path through the tree over n chunks (b3w_plan_path_provable, with the split from a bit scan)?
+B3W_HD_INLINE bool path_provable(uint64_t c, uint64_t n) {
+  const uint32_t P = depth_in(c, n);
+  uint64_t cc = c, m = n;
+  for (uint32_t j = 0; j < P; ++j) {
+    const uint64_t k = left_of(m);
+    const bool left = cc < k;
+    if (left) m = k; else { cc -= k; m -= k; }
+    if (left != (((c >> (P - 1 - j)) & 1) == 0)) return false;
+  }
+  return true;
+}
+
 // ---- files of at most 64 chunks share waves, in file order, as many as fit ----------------------------------------------------------
 // add(n): the first lane of a file of n chunks in its wave; `first` (may be null: counting) takes every wave's first file, and
 // close() the end of the last wave

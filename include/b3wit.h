@@ -1127,6 +1127,50 @@ int32_t b3w_bao_range_slice_ingest_device(b3w_ctx *ctx, uint8_t *d_arena, uint64
                                           const uint64_t *host_count, uint32_t n_ranges, const uint8_t *d_slices, int32_t *d_range_status,
                                           uint64_t *d_range_first_bad, uint64_t *d_have /* may be NULL */, void *d_scratch,
                                           uint64_t scratch_bytes, void *stream);
+/* THE PROVER: step records of challenged chunk RUNS planned from range slices alone, b3w_sample_plan_slices_device's twin.  DEFINED BY
+ * PROJECTION like the receiver: for every chunk c of every range, the status is the one b3w_sample_plan_slices_device gives the
+ * projection of the range slice onto c (3 header, 2 a path node or the root, 1 the chunk's bytes, 0 verified; 3 over 2 over 1; a
+ * one-chunk file's wrong root is 1), and the records are word for word the rows that call writes for the projection: the leaf
+ * blocks, then the parent steps bottom up - the chained words where the chunk failed or its path is not provable
+ * (b3w_chain_path_provable), the words straight from the nodes otherwise.  Records are written for failing chunks too; a bad node
+ * spoils the chunks below it and no other.  Ranges may overlap, repeat and come in any order; each writes its own rows.
+ * ROWS.  Range r owns rows [range_row_first[r], range_row_first[r + 1]), its chunks in ascending order, each chunk's rows as
+ * b3w_sample_rows_batch lays out one sample: the rows are exactly b3w_sample_rows_batch's over the ranges broken into chunks.  The
+ * per-chunk outputs are packed the same way: range r's chunks at [chunk_first[r], chunk_first[r] + host_count[r]), chunk_first the
+ * running sum of the counts. */
+/* Host only.  range_row_first [n_ranges + 1]; chunk_row_first (NULL, or the total chunk count + 1: every chunk's first row, the total
+ * behind them) and chunk_provable (NULL, or the total chunk count: b3w_chain_path_provable of every chunk) are filled only when asked
+ * for.  -> the total rows, or -B3W_E_BAD_ARGUMENT for what b3w_bao_range_slice_batch_layout refuses.  The per-range totals are a
+ * closed form (the sum of the path lengths over a prefix of the tree, O(depth) a range); only the two optional arrays cost a step
+ * a chunk. */
+int64_t b3w_sample_rows_ranges(const uint64_t *host_lens, uint32_t n_files, const uint32_t *host_files, const uint64_t *host_first,
+                               const uint64_t *host_count, uint32_t n_ranges, uint64_t *range_row_first /* n_ranges + 1 */,
+                               uint64_t *chunk_row_first /* NULL, or total chunks + 1 */, uint8_t *chunk_provable /* NULL, or total chunks */);
+/* d_slices: the packed range slices (16-byte aligned, b3w_bao_range_slice_batch_layout); d_records: 32 words a row,
+ * b3w_sample_rows_ranges' total; d_chunk_status: an int32 a chunk; d_range_status / d_range_first_bad: what
+ * b3w_bao_range_slice_ingest_device gives (the largest chunk status; the first chunk of the file whose status is not 0, UINT64_MAX
+ * for none; 8-byte aligned).  THE SCRATCH is 16 bytes a row of the table (16-byte aligned): the rows are the receiver's, so its size
+ * is what b3w_bao_range_slice_ingest_scratch_bytes says for the same ranges.  A row is (range, block of 64 or 1 024 aligned chunks) as
+ * in the receiver: lane = chunk; the chunk's leaf records written in place while its CV goes to LDS; the block's nodes hashed once in
+ * LDS and the nodes above it side by side; then every lane writes its parent records from the slice's own nodes.  At most THREE
+ * launches (short rows, tile rows, the per-range reduce); one table (64 bytes a range, 16 a row) through the context's staging and
+ * nothing else allocated; asynchronous on `stream`; nova contexts only.  Every byte and row count is 64 bits wide: a whole 1 GiB file
+ * as one range is 37 748 736 rows, 4.8 GB of records.  n_ranges == 0: a no-op.  REFUSALS ARE ATOMIC (B3W_E_BAD_ARGUMENT before
+ * anything is launched or written - records, statuses, range outputs and scratch untouched; b3w_last_error names the range): a null
+ * or misaligned pointer, a scratch that is too small, a file index >= n_files, a range with count 0 or that reaches past its file's
+ * chunk count, a file of more than 2^30 chunks, more than 2^31 - 1 rows of one kind, a context that is not a nova circuit's.
+ * WHEN NOT TO (MI355X, one 1 GiB file; the yardstick is a build of the commit before this call planning the same chunks
+ * from one-chunk slices with b3w_sample_plan_slices_device).  64 runs of 1 024 chunks at starts that are not tile-aligned: 0.432 ms
+ * against 1.714 (the yardstick's spread 0.0008), 302 MB of records at 700 GB/s; 4 096 runs of 16: 0.525 against 1.715.  SHORT RUNS LOSE
+ * as in the receiver: a range takes at least a wave, and its one busy lane writes the parent rows the one-chunk kernel spreads over
+ * sixteen lanes - 65 536 runs of ONE chunk 7.93 ms against 1.72, the 262 507 runs of a half-missing bitmap 23.4 against 13.4.  So:
+ * runs of one or two chunks through bao.runs_chunks and b3w_sample_plan_slices_device, longer ones through this call; where between
+ * 2 and 16 chunks a run the two cross was not measured, nor were files past 1 GiB. */
+int32_t b3w_sample_plan_range_slices_device(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, const uint32_t *d_roots,
+                                            const uint32_t *host_files, const uint64_t *host_first, const uint64_t *host_count,
+                                            uint32_t n_ranges, const uint8_t *d_slices, uint32_t *d_records, int32_t *d_chunk_status,
+                                            int32_t *d_range_status, uint64_t *d_range_first_bad, void *d_scratch, uint64_t scratch_bytes,
+                                            void *stream);
 
 /* ---- updates in place after writes to resident files (still ABI 1.4: new names only) --------------------------------
  * Every call above treats a file as immutable: after one rewritten block the only way to a correct outboard and root is the batch
