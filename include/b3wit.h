@@ -276,8 +276,21 @@ int32_t b3w_batch_verify_device(b3w_ctx *ctx, const uint8_t *d_bodies, uint32_t 
  * x then y, 32-byte little-endian each, standard (non-Montgomery) form, one per committed slot.
  * b3w_commit_key_create precomputes 2^k * G for the slots that hold more than one bit, so committing a witness is
  * "add the points of its set bits" (no doublings).  Output: n affine points (x, y as above; all zero = the point
- * at infinity); d_status (may be NULL): 0 ok, 103 = a bit slot of that body does not hold 0 or 1 (not a body of the
- * batch kernels: commitment not meaningful). */
+ * at infinity); d_status (may be NULL): 0 ok, 103 = the body is outside the key's DOMAIN (not a body of the batch kernels).
+ * The domain is a rule about the committed slots' values, each slot's 32 bytes taken as a little-endian 256-bit integer, by the
+ * slot's class under the key (b3w_slot_widths and, for a folded key, folded[]):
+ *   a bit slot (width 1)                          holds 0 or 1;
+ *   a 32-bit slot, also one cut down to one bit
+ *   of its word by folded[] = 0x80 | i            holds a value below 2^32 (the key then commits bit i of it);
+ *   a 64-bit slot                                 holds a value below 2^64;
+ *   a 256-bit slot (the IsZero inverses too)      holds anything, values >= p included: the integer is committed as it stands,
+ *                                                 which is the commitment of its residue on the curve whose order is the prime;
+ *   a slot folded away (folded[] = 1)             holds anything: it is not read and commits nothing;
+ *   a slot below first_slot                       never matters.
+ * A body inside the domain gets exactly sum_s committed[s] * G[s - first_slot]; it need not be a witness of the circuit.  A body
+ * outside it gets status 103 and an UNSPECIFIED point (with d_status NULL there is no telling which points those are); the other
+ * bodies of the launch are not affected.  b3w_commit_key_counts counts a flagged body as well: the non-zero windows of the low bits
+ * its slots' classes keep.  tests/commit_domain_ref.py states this rule in plain integers. */
 #define B3W_CURVE_BN254_G1 0 /* y^2 = x^3 + 3 over q = 0x30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47 */
 #define B3W_CURVE_PALLAS   1 /* y^2 = x^3 + 5 over 0x40000000000000000000000000000000224698fc094cf91b992d30ed00000001: the Pallas curve
                                * (pasta_curves; generator (-1, 2)), whose SCALAR field is the prime circom calls "vesta" — the group

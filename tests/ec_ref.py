@@ -93,6 +93,25 @@ def random_points(curve, n, seed=b"b3wit-test-generators"):
     return list(out[:n])
 
 
+_RELATED = {}
+
+
+def related_points(curve, n):
+    """n generators A + i B from two points of random_points: commitments are compared as group elements, for which any generators
+    do, and a witness's worth of independent ones is 10 s of square roots in Python.  The commitment of a vector v is then
+    (sum v_i) A + (sum i v_i) B — two scalar multiplications, and the index weight shows a point taken from the wrong slot."""
+    if curve not in _RELATED:
+        p, _ = CURVES[curve]
+        A, B = random_points(curve, 2)
+        out = [A]
+        for _i in range(1, 24700):
+            out.append(add(out[-1], B, p))
+        assert len({P for P in out}) == len(out) and None not in out
+        _RELATED[curve] = out
+    assert n <= len(_RELATED[curve])
+    return _RELATED[curve][:n]
+
+
 def on_curve(P, curve):
     p, b = CURVES[curve]
     return P is None or (P[1] * P[1] - P[0] ** 3 - b) % p == 0

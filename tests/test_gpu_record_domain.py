@@ -206,23 +206,6 @@ def test_constraint_check_on_the_oracles_bodies(circuit):
     r1cs.close(); ctx.close()
 
 
-_gens = {}
-
-
-def _generators(curve, n):
-    """n generators A + i B from two points of ec_ref.random_points: the commitments below are compared as group elements, for which any
-    generators do, and a witness's worth of independent ones is 10 s of square roots in Python."""
-    if curve not in _gens:
-        p, _ = E.CURVES[curve]
-        A, B = E.random_points(curve, 2)
-        out = [A]
-        for _i in range(1, 24700):
-            out.append(E.add(out[-1], B, p))
-        assert len({P for P in out}) == len(out) and None not in out
-        _gens[curve] = out
-    return _gens[curve][:n]
-
-
 @pytest.mark.parametrize("circuit,window", [(c, w) for c in T.CIRCUITS for w in (12, 16)])
 def test_commitments_from_records_at_the_edges(circuit, window):
     """commit_records_device over the whole table against commit_device on the uploaded oracle bodies: the statuses are run_device's
@@ -234,7 +217,7 @@ def test_commitments_from_records_at_the_edges(circuit, window):
     n, acc = t["n"], t["acc"]
     ctx = _ctx(circuit)
     curve, first_slot = CURVE[circuit], 3
-    gens = _generators(curve, ctx.witness_size - first_slot)
+    gens = E.related_points(curve, ctx.witness_size - first_slot)
     key = m.CommitKey(ctx, curve, E.points_to_bytes(gens), first_slot, window)
     s = torch.cuda.current_stream().cuda_stream
     d_recs = torch.from_numpy(t["recs"].view(np.int32)).cuda()
