@@ -235,6 +235,10 @@ def lib():
         "b3w_bao_range_slice_ingest_device": (i32, [vp, vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, u64, vp]),
         "b3w_sample_rows_ranges": (ctypes.c_int64, [vp, u32, vp, vp, vp, u32, vp, vp, vp]),
         "b3w_sample_plan_range_slices_device": (i32, [vp, vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, u64, vp]),
+        "b3w_bao_packed_layout": (i32, [vp, u32, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp]),
+        "b3w_bao_outboard_update_packed_device": (i32, [vp, vp, u64, vp, u32, u32, vp, vp, vp, vp, vp, vp, u32, vp, u64, vp]),
+        "b3w_bao_verify_ranges_packed_device": (i32, [vp, vp, u64, vp, u32, u32, vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, u64, vp]),
+        "b3w_bao_range_slice_packed_device": (i32, [vp, vp, u64, vp, u32, u32, vp, vp, vp, vp, u32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -275,7 +279,9 @@ EXPORTED_SYMBOLS = ("b3w_abi_version", "b3w_identify_wasm", "b3w_create", "b3w_d
                     "b3w_bao_have_from_status_device", "b3w_bao_have_runs", "b3w_bao_have_from_status",
                     "b3w_bao_range_slice_size", "b3w_bao_range_slice_batch_layout", "b3w_bao_range_slice", "b3w_bao_range_slice_decode",
                     "b3w_bao_range_slice_ingest", "b3w_bao_range_slice_arena_device", "b3w_bao_range_slice_ingest_scratch_bytes",
-                    "b3w_bao_range_slice_ingest_device", "b3w_sample_rows_ranges", "b3w_sample_plan_range_slices_device")
+                    "b3w_bao_range_slice_ingest_device", "b3w_sample_rows_ranges", "b3w_sample_plan_range_slices_device",
+                    "b3w_bao_packed_layout", "b3w_bao_outboard_update_packed_device", "b3w_bao_verify_ranges_packed_device",
+                    "b3w_bao_range_slice_packed_device")
 
 
 class graph_capture:

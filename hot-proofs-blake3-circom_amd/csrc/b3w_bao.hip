@@ -41,6 +41,10 @@
 //                            outboards and taken in again, a row per (range, block of 64 or 1 024 chunks) ("range slices", at the end)
 //   b3w_sample_plan_range_kernel  the step records of a RUN of challenged chunks planned from its range slice alone, on the same rows:
 //                            b3w_sample_plan_slices_kernel's records and statuses for every chunk's projection (behind the range kernels)
+//   b3w_bao_*_packed_kernel  the update's and the ranged verification's tile kernels and the range-slice provider for files that are NOT
+//                            resident: the same bodies, the listed chunks read slot by slot from a packed buffer that holds them alone,
+//                            a lane's place its rank among the listed chunks, its counter and length its chunk's ("sparse calls from
+//                            packed chunk bytes" in b3wit.h)
 //
 // The routes (batch table, one streamed file by value, a table of sessions, update / ranges / resize rows) differ only in where a file's
 // entry comes from.  Each kernel, or its *_body wrapper, finds its entry and calls one of the bodies every route shares:
@@ -1538,7 +1542,7 @@ __global__ __launch_bounds__(B3W_TILE) void b3w_bao_stream_verify_many_kernel(co
 // file) is dirty; the host expands chunk masks to whole groups, so inside a dirty group every chunk is hashed and nothing is loaded.
 struct UpdRow {
   uint64_t len;
-  const uint8_t *data;                                   // the file's first byte (tile rows)
+  const uint8_t *data;                                   // the file's first byte (tile rows; packed: the slot of the tile's first dirty chunk)
   uint8_t *ob;                                           // the file's outboard, header first
   uint32_t *root;
   uint32_t *in;                                          // merge rows: the scratch slot of the workgroup's first dirty item
@@ -1597,7 +1601,16 @@ __device__ __forceinline__ void update_in_lds(uint32_t *cv, uint32_t *dirty, uin
   lds_barrier();
 }
 
-template <bool GRP>
+// the items of a row's mask below item t: where the rows are sorted, the place of item t among the workgroup's listed ones
+__device__ __forceinline__ uint32_t mask_rank(const uint32_t *mask, uint32_t t) {
+  uint32_t below = __popc(mask[t >> 5] & ((1u << (t & 31)) - 1));
+  for (uint32_t k = 0; k < (t >> 5); ++k) below += __popc(mask[k]);
+  return below;
+}
+
+// PACKED (b3w_bao_outboard_update_packed_device): r->data is the slot of the tile's first dirty chunk in the packed buffer and a dirty
+// chunk lies behind the tile's dirty chunks below it; its counter and its length stay those of chunk a0 + t
+template <bool GRP, bool PACKED>
 __device__ __forceinline__ void update_tile_body(const UpdRow *__restrict__ rows) {
   __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
   __shared__ uint32_t dirty[B3W_TILE];
@@ -1609,13 +1622,15 @@ __device__ __forceinline__ void update_tile_body(const UpdRow *__restrict__ rows
   const bool sole = n <= B3W_TILE;
   const bool mine = t < m && ((r->mask[t >> 5] >> (t & 31)) & 1u);
   dirty[t] = mine ? 1u : 0u;
-  if (mine) lane_chunk_cv(cv, as_global(r->data), a0 + t, len, n, a0 + t, false);
+  if (mine) lane_chunk_cv(cv, as_global(r->data), PACKED ? mask_rank(r->mask, t) : a0 + t, len, n, a0 + t, false);
   update_in_lds<B3W_TILE, GRP>(cv, dirty, m, 1, m, as_global(r->ob) + 8 + node_pos<GRP>(n, a0, m, gl) * 64, sole, gl);   // (a tile starts at a multiple of every group size)
   if (t < 8) as_global(sole ? r->root : r->out)[t] = cv[t];            // (the row's mask is not empty: slot 0 holds the tile's CV)
 }
 
-__global__ __launch_bounds__(B3W_TILE) void b3w_bao_update_tile_kernel(const UpdRow *__restrict__ rows) { update_tile_body<false>(rows); }
-__global__ __launch_bounds__(B3W_TILE) void b3w_bao_update_tile_group_kernel(const UpdRow *__restrict__ rows) { update_tile_body<true>(rows); }
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_update_tile_kernel(const UpdRow *__restrict__ rows) { update_tile_body<false, false>(rows); }
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_update_tile_group_kernel(const UpdRow *__restrict__ rows) { update_tile_body<true, false>(rows); }
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_update_tile_packed_kernel(const UpdRow *__restrict__ rows) { update_tile_body<false, true>(rows); }
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_update_tile_packed_group_kernel(const UpdRow *__restrict__ rows) { update_tile_body<true, true>(rows); }
 
 // unit = chunks per input item, as in merge_storey; the workgroup's items are [1 024 idx, ...) of the file's
 template <bool GRP>
@@ -1668,7 +1683,7 @@ __global__ __launch_bounds__(256) void b3w_bao_update_merge_group_kernel(const U
 // workgroup; a one-tile file's tile reads it itself).
 struct VrRow {
   uint64_t len;
-  const uint8_t *data;                                   // the file's first byte (tile rows)
+  const uint8_t *data;                                   // the file's first byte (tile rows; packed: the slot of the tile's first listed chunk)
   const uint8_t *ob;                                     // the file's outboard, header first
   const uint32_t *root;
   const uint32_t *want;                                  // the workgroup's own scratch entry: 8 words of CV ... (unused by a file's top workgroup)
@@ -1774,7 +1789,9 @@ __global__ __launch_bounds__(256) void b3w_bao_verify_ranges_upper_kernel(const 
     if ((r->mask[t >> 5] >> (t & 31)) & 1u) out_word[rank[t]] = above | (path_bad(flags, t) ? VR_PATH : 0u);
 }
 
-__global__ __launch_bounds__(B3W_TILE) void b3w_bao_verify_ranges_tile_kernel(const VrRow *__restrict__ rows) {
+// PACKED (b3w_bao_verify_ranges_packed_device): as in update_tile_body
+template <bool PACKED>
+__device__ __forceinline__ void verify_ranges_tile_body(const VrRow *__restrict__ rows) {
   __shared__ __attribute__((aligned(16))) uint32_t cv[B3W_TILE * 8];
   __shared__ uint32_t flags[B3W_TILE], listed[B3W_TILE];
   const VrRow *__restrict__ r = rows + blockIdx.x;
@@ -1787,7 +1804,7 @@ __global__ __launch_bounds__(B3W_TILE) void b3w_bao_verify_ranges_tile_kernel(co
   const uint8_t *__restrict__ ob = as_global(r->ob);
   listed[t] = mine ? 1u : 0u;
   flags[t] = 0;
-  if (mine) lane_chunk_cv(cv, as_global(r->data), a0 + t, len, n, a0 + t, false);
+  if (mine) lane_chunk_cv(cv, as_global(r->data), PACKED ? mask_rank(r->mask, t) : a0 + t, len, n, a0 + t, false);
   const uint32_t above = sole ? (header_is(ob, len) ? 0u : VR_HDR) : *as_global(r->above);
   ranges_in_lds<B3W_TILE, true>(cv, flags, listed, nullptr, m, 1, m, ob + 8 + node_pos<true>(n, a0, m, gl) * 64, sole, gl, nullptr);
   // (the row's mask is not empty: slot 0 holds what the tile's stored root node hashes to, or the CV of a tile that is one unit)
@@ -1798,6 +1815,8 @@ __global__ __launch_bounds__(B3W_TILE) void b3w_bao_verify_ranges_tile_kernel(co
     as_global(r->unit_status)[(a0 + t) >> gl] = (uint8_t)st;
   }
 }
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_verify_ranges_tile_kernel(const VrRow *__restrict__ rows) { verify_ranges_tile_body<false>(rows); }
+__global__ __launch_bounds__(B3W_TILE) void b3w_bao_verify_ranges_tile_packed_kernel(const VrRow *__restrict__ rows) { verify_ranges_tile_body<true>(rows); }
 
 // b3w_bao_verify_small_kernel with a row per file: wave w takes the rows [wave_first[w], wave_first[w + 1]), r.first = the lane of the
 // file's chunk 0; every unit byte of the file is written, with the whole-file call's value; no per-file outputs
@@ -3200,7 +3219,27 @@ namespace {
 std::string update_range_text(uint32_t i, uint32_t file, uint64_t first, uint64_t count) {
   return "range " + std::to_string(i) + " (file " + std::to_string(file) + ", chunks " + std::to_string(first) + " + " + std::to_string(count) + ")";
 }
-// the update and ranged-verification calls: every range is checked before anything is launched or written
+// Where a sparse call finds its chunks: file f's bytes at base + offsets[f] of an arena of `bytes` bytes, or (null offsets) the listed
+// chunks alone, slot by slot, in a packed buffer of `bytes` bytes (b3wit.h "sparse calls from packed chunk bytes")
+struct SparseSrc {
+  const uint8_t *base; uint64_t bytes; const uint64_t *offsets;
+  bool packed() const { return !offsets; }
+};
+// the packed calls' own two refusals
+int32_t packed_ok(b3w_ctx *ctx, const char *call, const SparseSrc &src, const PkLayout &pk) {
+  if (pk.bytes && !src.base) return refuse(ctx, call, "a null d_packed with " + std::to_string(pk.bytes) + " bytes of listed chunks (b3w_bao_packed_layout's total_bytes)");
+  if (src.bytes < pk.bytes)
+    return refuse(ctx, call, "packed_bytes is " + std::to_string(src.bytes) + ", the listed chunks take " + std::to_string(pk.bytes) + " (b3w_bao_packed_layout's total_bytes)");
+  return B3W_OK;
+}
+// the first item of a row's mask (not empty)
+uint32_t mask_first(const uint32_t *mask) {
+  uint32_t w = 0;
+  while (!mask[w]) ++w;
+  return w * 32 + (uint32_t)__builtin_ctz(mask[w]);
+}
+// the update and ranged-verification calls: every range is checked before anything is launched or written (null host_offsets: a packed
+// call, which has no arena to look at)
 int32_t sparse_ranges_ok(b3w_ctx *ctx, const char *call, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
                          uint32_t n_files, const uint64_t *host_ob_first, const uint32_t *host_files, const uint64_t *host_first_chunk, const uint64_t *host_n_chunks,
                          uint32_t n_ranges, const char *null_arena) {
@@ -3211,8 +3250,8 @@ int32_t sparse_ranges_ok(b3w_ctx *ctx, const char *call, const uint8_t *d_arena,
     const uint64_t len = host_lens[f], n = num_chunks(len);
     if (n > (1ull << 30)) return refuse(ctx, call, update_range_text(i, f, a, c) + ": a file of more than 2^30 chunks");
     if (a > n || c > n - a) return refuse(ctx, call, update_range_text(i, f, a, c) + " reaches past the file's " + std::to_string(n) + " chunks");
-    if (host_offsets[f] > arena_bytes || len > arena_bytes - host_offsets[f]) return refuse(ctx, call, update_range_text(i, f, a, c) + ": the file reaches past arena_bytes");
-    if (len && !d_arena) return refuse(ctx, call, update_range_text(i, f, a, c) + null_arena);
+    if (host_offsets && (host_offsets[f] > arena_bytes || len > arena_bytes - host_offsets[f])) return refuse(ctx, call, update_range_text(i, f, a, c) + ": the file reaches past arena_bytes");
+    if (host_offsets && len && !d_arena) return refuse(ctx, call, update_range_text(i, f, a, c) + null_arena);
     if (host_ob_first[f] & 7) return refuse(ctx, call, update_range_text(i, f, a, c) + ": the file's outboard offset is not a multiple of 8");
   }
   return B3W_OK;
@@ -3229,21 +3268,27 @@ std::string resize_entry_text(uint32_t i, uint32_t file) { return "entry " + std
 
 extern "C" {
 
+}  // extern "C"
+
+namespace {
+
 // ---- updates in place, ranged verification, appends and truncations (b3wit.h) -----------------------------------------------------------
-int32_t b3w_bao_outboard_update_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets,
-                                             const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint64_t *host_ob_first,
-                                             uint8_t *d_outboards, uint32_t *d_roots, const uint32_t *host_files, const uint64_t *host_first_chunk,
-                                             const uint64_t *host_n_chunks, uint32_t n_ranges, void *d_scratch, uint64_t scratch_bytes, void *stream) {
-  const char *call = "bao update";
-  if (!ctx) return B3W_E_BAD_ARGUMENT;
-  B3W_TRY(group_log_ok(ctx, call, group_log));
-  if (!n_ranges) return B3W_OK;
-  if (!host_offsets || !host_lens || !host_ob_first || !d_outboards || !d_roots || !host_files || !host_first_chunk || !host_n_chunks)
+// b3w_bao_outboard_update_batch_device and b3w_bao_outboard_update_packed_device: one plan, one table, the same launches; the two differ in
+// where a tile row's and a small file's bytes lie and in the tile kernel that reads them
+int32_t update_call(b3w_ctx *ctx, const char *call, const SparseSrc src, const uint64_t *host_lens, uint32_t n_files, uint32_t group_log,
+                    const uint64_t *host_ob_first, uint8_t *d_outboards, uint32_t *d_roots, const uint32_t *host_files, const uint64_t *host_first_chunk,
+                    const uint64_t *host_n_chunks, uint32_t n_ranges, void *d_scratch, uint64_t scratch_bytes, void *stream) {
+  const uint8_t *const d_arena = src.base;
+  const uint64_t *const host_offsets = src.offsets;
+  if (!host_lens || !host_ob_first || !d_outboards || !d_roots || !host_files || !host_first_chunk || !host_n_chunks)
     return refuse(ctx, call, "a null pointer (offsets, lengths, outboard offsets, outboards, roots or a range array)");
   if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_roots & 3)) return refuse(ctx, call, "d_outboards is not 8-byte aligned, or d_roots not 4-byte aligned");
-  B3W_TRY(sparse_ranges_ok(ctx, call, d_arena, arena_bytes, host_offsets, host_lens, n_files, host_ob_first, host_files, host_first_chunk, host_n_chunks, n_ranges,
+  B3W_TRY(sparse_ranges_ok(ctx, call, d_arena, src.bytes, host_offsets, host_lens, n_files, host_ob_first, host_files, host_first_chunk, host_n_chunks, n_ranges,
                            ": a null arena with a dirty file that is not empty"));
-  const UpdPlan p = b3w_int_update_plan(host_lens, b3w_int_update_ranges(host_lens, host_files, host_first_chunk, host_n_chunks, n_ranges), group_log);
+  const std::vector<UpdRange> merged = b3w_int_update_ranges(host_lens, host_files, host_first_chunk, host_n_chunks, n_ranges);
+  const UpdPlan p = b3w_int_update_plan(host_lens, merged, group_log);
+  PkLayout pk;
+  if (src.packed()) { pk = b3w_int_packed_layout(host_lens, merged, group_log); B3W_TRY(packed_ok(ctx, call, src, pk)); }
   const uint64_t need = (p.tile_slots + p.span_slots) * 32;
   if (scratch_bytes < need) return refuse(ctx, call, "the scratch is smaller than b3w_bao_update_scratch_bytes says (" + std::to_string(need) + " bytes)");
   if (need && (!d_scratch || ((uintptr_t)d_scratch & 15))) return refuse(ctx, call, "the scratch is null or not 16-byte aligned");
@@ -3264,20 +3309,24 @@ int32_t b3w_bao_outboard_update_batch_device(b3w_ctx *ctx, const uint8_t *d_aren
   auto row = [&](const UpdWg &w, uint32_t *in, uint32_t *out) {
     UpdRow r{};
     const uint32_t f = w.file;
-    r.len = host_lens[f]; r.data = d_arena + host_offsets[f]; r.ob = d_outboards + host_ob_first[f]; r.root = d_roots + (uint64_t)f * 8;
+    r.len = host_lens[f]; r.ob = d_outboards + host_ob_first[f]; r.root = d_roots + (uint64_t)f * 8;
     r.in = in; r.out = out; r.idx = w.idx; r.gl = group_log;
     memcpy(r.mask, w.mask, sizeof r.mask);
     return r;
   };
   UpdRow *at = h_rows;
-  for (const UpdWg &w : p.tiles) *at++ = row(w, nullptr, scratch + w.out * 8);
+  for (const UpdWg &w : p.tiles) {
+    UpdRow r = row(w, nullptr, scratch + w.out * 8);
+    r.data = src.packed() ? d_arena + 1024 * pk.slot_of(w.file, (uint64_t)w.idx * B3W_TILE + mask_first(w.mask)) : d_arena + host_offsets[w.file];
+    *at++ = r;
+  }
   for (const UpdWg &w : p.spans) *at++ = row(w, scratch + w.in * 8, span_cv + w.out * 8);
   for (const UpdWg &w : p.tops) *at++ = row(w, span_cv + w.in * 8, nullptr);
   SmallPack pack;
   pack.first = h_waves;
   for (uint32_t f : p.small) {
     const uint32_t lane = pack.add(num_chunks(host_lens[f]));
-    h_small[pack.files - 1] = BatchEnt{host_offsets[f], host_lens[f], host_ob_first[f], lane, f};
+    h_small[pack.files - 1] = BatchEnt{src.packed() ? 1024 * pk.slot_of(f, 0) : host_offsets[f], host_lens[f], host_ob_first[f], lane, f};
   }
   pack.close();
   const hipError_t ec = hipMemcpyAsync(slot->d, slot->h, (size_t)bytes, hipMemcpyHostToDevice, st);
@@ -3287,35 +3336,37 @@ int32_t b3w_bao_outboard_update_batch_device(b3w_ctx *ctx, const uint8_t *d_aren
   const uint32_t *d_waves = reinterpret_cast<const uint32_t *>(d_small + p.small.size());
   const uint64_t U = B3W_TILE;
   const bool grp = group_log != 0;
-  const auto tile_kernel = grp ? b3w_bao_update_tile_group_kernel : b3w_bao_update_tile_kernel;
+  const auto tile_kernel = src.packed() ? (grp ? b3w_bao_update_tile_packed_group_kernel : b3w_bao_update_tile_packed_kernel)
+                                        : (grp ? b3w_bao_update_tile_group_kernel : b3w_bao_update_tile_kernel);
   const auto merge_kernel = grp ? b3w_bao_update_merge_group_kernel : b3w_bao_update_merge_kernel;
   if (pack.files) launch_pair(grp, b3w_bao_small_kernel, b3w_bao_small_group_kernel, group_log, dim3((uint32_t)waves), dim3(64), st, d_arena, d_small, d_waves, d_outboards, d_roots);
   if (!p.tiles.empty()) hipLaunchKernelGGL(tile_kernel, dim3((uint32_t)p.tiles.size()), dim3(B3W_TILE), 0, st, d_tiles);
   if (!p.spans.empty()) hipLaunchKernelGGL(merge_kernel, dim3((uint32_t)p.spans.size()), dim3(256), 0, st, d_spans, U);
   if (!p.tops.empty()) hipLaunchKernelGGL(merge_kernel, dim3((uint32_t)p.tops.size()), dim3(256), 0, st, d_tops, U * U);
-  return many_launched(ctx, slot, st, "bao update launch");
+  return many_launched(ctx, slot, st, (std::string(call) + " launch").c_str());
 }
 
-int32_t b3w_bao_verify_ranges_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets,
-                                           const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint64_t *host_ob_first,
-                                           const uint8_t *d_outboards, const uint32_t *d_roots, const uint32_t *host_files,
-                                           const uint64_t *host_first_chunk, const uint64_t *host_n_chunks, uint32_t n_ranges,
-                                           const uint64_t *host_unit_first, uint8_t *d_unit_status, int32_t *d_range_status,
-                                           uint64_t *d_range_first_bad, void *d_scratch, uint64_t scratch_bytes, void *stream) {
-  const char *call = "bao verify ranges";
-  if (!ctx) return B3W_E_BAD_ARGUMENT;
-  B3W_TRY(group_log_ok(ctx, call, group_log));
-  if (!n_ranges) return B3W_OK;
-  if (!host_offsets || !host_lens || !host_ob_first || !d_outboards || !d_roots || !host_files || !host_first_chunk || !host_n_chunks || !host_unit_first)
+// b3w_bao_verify_ranges_batch_device and b3w_bao_verify_ranges_packed_device, as update_call
+int32_t verify_ranges_call(b3w_ctx *ctx, const char *call, const SparseSrc src, const uint64_t *host_lens, uint32_t n_files, uint32_t group_log,
+                           const uint64_t *host_ob_first, const uint8_t *d_outboards, const uint32_t *d_roots, const uint32_t *host_files,
+                           const uint64_t *host_first_chunk, const uint64_t *host_n_chunks, uint32_t n_ranges, const uint64_t *host_unit_first,
+                           uint8_t *d_unit_status, int32_t *d_range_status, uint64_t *d_range_first_bad, void *d_scratch, uint64_t scratch_bytes,
+                           void *stream) {
+  const uint8_t *const d_arena = src.base;
+  const uint64_t *const host_offsets = src.offsets;
+  if (!host_lens || !host_ob_first || !d_outboards || !d_roots || !host_files || !host_first_chunk || !host_n_chunks || !host_unit_first)
     return refuse(ctx, call, "a null pointer (offsets, lengths, outboard offsets, unit offsets, outboards, roots or a range array)");
   if (!d_unit_status || !d_range_status || !d_range_first_bad) return refuse(ctx, call, "a null output pointer (unit statuses, range statuses or first bad units)");
   if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_roots & 3)) return refuse(ctx, call, "d_outboards is not 8-byte aligned, or d_roots not 4-byte aligned");
   if (((uintptr_t)d_range_first_bad & 7) || ((uintptr_t)d_range_status & 3))
     return refuse(ctx, call, "d_range_first_bad is not 8-byte aligned, or d_range_status not 4-byte aligned");
   if (n_ranges > 0x7fffffffu) return refuse(ctx, call, "more than 2^31 - 1 ranges in one call");
-  B3W_TRY(sparse_ranges_ok(ctx, call, d_arena, arena_bytes, host_offsets, host_lens, n_files, host_ob_first, host_files, host_first_chunk, host_n_chunks, n_ranges,
+  B3W_TRY(sparse_ranges_ok(ctx, call, d_arena, src.bytes, host_offsets, host_lens, n_files, host_ob_first, host_files, host_first_chunk, host_n_chunks, n_ranges,
                            ": a null arena with a listed file that is not empty"));
-  const UpdPlan p = b3w_int_update_plan(host_lens, b3w_int_update_ranges(host_lens, host_files, host_first_chunk, host_n_chunks, n_ranges), group_log);
+  const std::vector<UpdRange> merged = b3w_int_update_ranges(host_lens, host_files, host_first_chunk, host_n_chunks, n_ranges);
+  const UpdPlan p = b3w_int_update_plan(host_lens, merged, group_log);
+  PkLayout pk;
+  if (src.packed()) { pk = b3w_int_packed_layout(host_lens, merged, group_log); B3W_TRY(packed_ok(ctx, call, src, pk)); }
   const uint64_t n_scr = p.tile_slots + p.span_slots, need = (n_scr * 36 + 15) & ~15ull;
   if (scratch_bytes < need) return refuse(ctx, call, "the scratch is smaller than b3w_bao_verify_ranges_scratch_bytes says (" + std::to_string(need) + " bytes)");
   if (need && (!d_scratch || ((uintptr_t)d_scratch & 15))) return refuse(ctx, call, "the scratch is null or not 16-byte aligned");
@@ -3338,14 +3389,19 @@ int32_t b3w_bao_verify_ranges_batch_device(b3w_ctx *ctx, const uint8_t *d_arena,
   auto row = [&](const UpdWg &w) {
     VrRow r{};
     const uint32_t f = w.file;
-    r.len = host_lens[f]; r.data = d_arena + host_offsets[f]; r.ob = d_outboards + host_ob_first[f]; r.root = d_roots + (uint64_t)f * 8;
+    r.len = host_lens[f]; r.ob = d_outboards + host_ob_first[f]; r.root = d_roots + (uint64_t)f * 8;
     r.unit_status = d_unit_status + host_unit_first[f];
     r.idx = w.idx; r.gl = group_log;
     memcpy(r.mask, w.mask, sizeof r.mask);
     return r;
   };
   VrRow *at = h_rows;
-  for (const UpdWg &w : p.tiles) { VrRow r = row(w); r.want = tile_cv + w.out * 8; r.above = tile_word + w.out; *at++ = r; }
+  for (const UpdWg &w : p.tiles) {
+    VrRow r = row(w);
+    r.data = src.packed() ? d_arena + 1024 * pk.slot_of(w.file, (uint64_t)w.idx * B3W_TILE + mask_first(w.mask)) : d_arena + host_offsets[w.file];
+    r.want = tile_cv + w.out * 8; r.above = tile_word + w.out;
+    *at++ = r;
+  }
   for (const UpdWg &w : p.spans) {
     VrRow r = row(w);
     r.want = span_cv + w.out * 8; r.above = span_word + w.out; r.out_cv = tile_cv + w.in * 8; r.out_word = tile_word + w.in;
@@ -3360,7 +3416,7 @@ int32_t b3w_bao_verify_ranges_batch_device(b3w_ctx *ctx, const uint8_t *d_arena,
   pack.first = h_waves;
   for (uint32_t f : p.small) {
     const uint32_t lane = pack.add(num_chunks(host_lens[f]));
-    h_small[pack.files - 1] = VrSmall{host_offsets[f], host_lens[f], d_outboards + host_ob_first[f], d_roots + (uint64_t)f * 8, d_unit_status + host_unit_first[f], lane, 0};
+    h_small[pack.files - 1] = VrSmall{src.packed() ? 1024 * pk.slot_of(f, 0) : host_offsets[f], host_lens[f], d_outboards + host_ob_first[f], d_roots + (uint64_t)f * 8, d_unit_status + host_unit_first[f], lane, 0};
   }
   pack.close();
   const hipError_t ec = hipMemcpyAsync(slot->d, slot->h, (size_t)bytes, hipMemcpyHostToDevice, st);
@@ -3374,10 +3430,71 @@ int32_t b3w_bao_verify_ranges_batch_device(b3w_ctx *ctx, const uint8_t *d_arena,
   if (pack.files) hipLaunchKernelGGL(b3w_bao_verify_ranges_small_kernel, dim3((uint32_t)waves), dim3(64), 0, st, d_arena, d_small, d_waves, group_log);
   if (!p.tops.empty()) hipLaunchKernelGGL(b3w_bao_verify_ranges_upper_kernel, dim3((uint32_t)p.tops.size()), dim3(256), 0, st, d_tops, U * U);
   if (!p.spans.empty()) hipLaunchKernelGGL(b3w_bao_verify_ranges_upper_kernel, dim3((uint32_t)p.spans.size()), dim3(256), 0, st, d_spans, U);
-  if (!p.tiles.empty()) hipLaunchKernelGGL(b3w_bao_verify_ranges_tile_kernel, dim3((uint32_t)p.tiles.size()), dim3(B3W_TILE), 0, st, d_tiles);
+  if (!p.tiles.empty())
+    hipLaunchKernelGGL(src.packed() ? b3w_bao_verify_ranges_tile_packed_kernel : b3w_bao_verify_ranges_tile_kernel, dim3((uint32_t)p.tiles.size()), dim3(B3W_TILE), 0, st,
+                       d_tiles);
   hipLaunchKernelGGL(b3w_bao_verify_ranges_reduce_kernel, dim3(n_ranges), dim3(256), 0, st, d_ranges, d_range_status,
                      reinterpret_cast<unsigned long long *>(d_range_first_bad));
-  return many_launched(ctx, slot, st, "bao verify ranges launch");
+  return many_launched(ctx, slot, st, (std::string(call) + " launch").c_str());
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t b3w_bao_outboard_update_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets,
+                                             const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint64_t *host_ob_first,
+                                             uint8_t *d_outboards, uint32_t *d_roots, const uint32_t *host_files, const uint64_t *host_first_chunk,
+                                             const uint64_t *host_n_chunks, uint32_t n_ranges, void *d_scratch, uint64_t scratch_bytes, void *stream) {
+  const char *call = "bao update";
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  B3W_TRY(group_log_ok(ctx, call, group_log));
+  if (!n_ranges) return B3W_OK;
+  if (!host_offsets) return refuse(ctx, call, "a null pointer (offsets, lengths, outboard offsets, outboards, roots or a range array)");
+  return update_call(ctx, call, SparseSrc{d_arena, arena_bytes, host_offsets}, host_lens, n_files, group_log, host_ob_first, d_outboards, d_roots, host_files,
+                     host_first_chunk, host_n_chunks, n_ranges, d_scratch, scratch_bytes, stream);
+}
+
+int32_t b3w_bao_outboard_update_packed_device(b3w_ctx *ctx, const uint8_t *d_packed, uint64_t packed_bytes, const uint64_t *host_lens, uint32_t n_files,
+                                              uint32_t group_log, const uint64_t *host_ob_first, uint8_t *d_outboards, uint32_t *d_roots,
+                                              const uint32_t *host_files, const uint64_t *host_first_chunk, const uint64_t *host_n_chunks, uint32_t n_ranges,
+                                              void *d_scratch, uint64_t scratch_bytes, void *stream) {
+  const char *call = "bao update packed";
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  B3W_TRY(group_log_ok(ctx, call, group_log));
+  if (!n_ranges) return B3W_OK;
+  return update_call(ctx, call, SparseSrc{d_packed, packed_bytes, nullptr}, host_lens, n_files, group_log, host_ob_first, d_outboards, d_roots, host_files,
+                     host_first_chunk, host_n_chunks, n_ranges, d_scratch, scratch_bytes, stream);
+}
+
+int32_t b3w_bao_verify_ranges_batch_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets,
+                                           const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint64_t *host_ob_first,
+                                           const uint8_t *d_outboards, const uint32_t *d_roots, const uint32_t *host_files,
+                                           const uint64_t *host_first_chunk, const uint64_t *host_n_chunks, uint32_t n_ranges,
+                                           const uint64_t *host_unit_first, uint8_t *d_unit_status, int32_t *d_range_status,
+                                           uint64_t *d_range_first_bad, void *d_scratch, uint64_t scratch_bytes, void *stream) {
+  const char *call = "bao verify ranges";
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  B3W_TRY(group_log_ok(ctx, call, group_log));
+  if (!n_ranges) return B3W_OK;
+  if (!host_offsets) return refuse(ctx, call, "a null pointer (offsets, lengths, outboard offsets, unit offsets, outboards, roots or a range array)");
+  return verify_ranges_call(ctx, call, SparseSrc{d_arena, arena_bytes, host_offsets}, host_lens, n_files, group_log, host_ob_first, d_outboards, d_roots, host_files,
+                            host_first_chunk, host_n_chunks, n_ranges, host_unit_first, d_unit_status, d_range_status, d_range_first_bad, d_scratch, scratch_bytes,
+                            stream);
+}
+
+int32_t b3w_bao_verify_ranges_packed_device(b3w_ctx *ctx, const uint8_t *d_packed, uint64_t packed_bytes, const uint64_t *host_lens, uint32_t n_files,
+                                            uint32_t group_log, const uint64_t *host_ob_first, const uint8_t *d_outboards, const uint32_t *d_roots,
+                                            const uint32_t *host_files, const uint64_t *host_first_chunk, const uint64_t *host_n_chunks, uint32_t n_ranges,
+                                            const uint64_t *host_unit_first, uint8_t *d_unit_status, int32_t *d_range_status, uint64_t *d_range_first_bad,
+                                            void *d_scratch, uint64_t scratch_bytes, void *stream) {
+  const char *call = "bao verify ranges packed";
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  B3W_TRY(group_log_ok(ctx, call, group_log));
+  if (!n_ranges) return B3W_OK;
+  return verify_ranges_call(ctx, call, SparseSrc{d_packed, packed_bytes, nullptr}, host_lens, n_files, group_log, host_ob_first, d_outboards, d_roots, host_files,
+                            host_first_chunk, host_n_chunks, n_ranges, host_unit_first, d_unit_status, d_range_status, d_range_first_bad, d_scratch, scratch_bytes,
+                            stream);
 }
 
 // At most five launches: one table through the staging ring in runs of rows, each run the rows of one grid (the tiles behind the kept
@@ -3584,10 +3701,12 @@ __device__ __forceinline__ uint64_t range_block_node_at(const RsBlock &b, const 
   return 8 + 64ull * before[c0] + 1024 * (b.a0 + c0 - b.a) - 64ull * depth_in(c0 - i0, size);
 }
 
-template <int B>
-__global__ __launch_bounds__(B) void b3w_bao_range_slice_kernel(const RsRange *__restrict__ ranges, const RsRow *__restrict__ rows, uint32_t gl,
-                                                                const uint8_t *__restrict__ arena, const uint8_t *__restrict__ obs,
-                                                                uint8_t *__restrict__ slices) {
+// PACKED (b3w_bao_range_slice_packed_device): `arena` is the packed buffer and r.off the place of the range's first LISTED chunk in it —
+// the first chunk of the group that holds chunk a, or chunk 0 of a file of at most 64 chunks (b3w_bao_packed_layout's range_first) —
+// and the chunks the range lists follow it slot by slot
+template <int B, bool PACKED>
+__device__ __forceinline__ void range_slice_body(const RsRange *__restrict__ ranges, const RsRow *__restrict__ rows, uint32_t gl,
+                                                 const uint8_t *__restrict__ arena, const uint8_t *__restrict__ obs, uint8_t *__restrict__ slices) {
   __shared__ __attribute__((aligned(16))) uint32_t cv[B * 8];
   __shared__ uint32_t before[B];
   const RsRow row = rows[blockIdx.x];
@@ -3595,12 +3714,13 @@ __global__ __launch_bounds__(B) void b3w_bao_range_slice_kernel(const RsRange *_
   const RsBlock b = range_block<B>(r, row.block);
   const uint32_t t = threadIdx.x, G = 1u << gl;
   const uint8_t *__restrict__ data = arena + r.off, *__restrict__ ob = obs + r.ob;
+  const uint64_t base = !PACKED || b.n <= 64 ? 0 : b.a & ~(uint64_t)(G - 1);   // the chunk of the file that lies at `data`
   uint8_t *__restrict__ sl = slices + r.slice;
   if (t >= b.lo && t < b.hi) before[t] = (uint32_t)range_nodes(b.n, b.a, b.a0 + t);
   // group outboards: the chunks of the touched groups, hashed (no byte behind the file's last one is read)
   const uint32_t gs = t & ~(G - 1);
   const bool touched = gl != 0 && t < b.m && gs < b.hi && gs + G > b.lo;
-  if (touched) lane_chunk_cv(cv, data, b.a0 + t, b.len, b.n, b.a0 + t, true);
+  if (touched) lane_chunk_cv(cv, data, b.a0 + t - base, b.len, b.n, b.a0 + t, true);
   for (uint32_t l = 0; (1u << l) < b.m; ++l) {
     if (l <= gl) lds_barrier();                            // (before[] and the level below inside a group; above the groups nothing is handed on)
     const uint32_t i0 = (2 * t) << l, i1 = i0 + (1u << l);
@@ -3628,10 +3748,22 @@ __global__ __launch_bounds__(B) void b3w_bao_range_slice_kernel(const RsRange *_
     const uint64_t c = b.a0 + ch;
     const uint32_t bytes = range_chunk_bytes(b.len, c);
     uint8_t *dst = sl + 8 + 64ull * before[ch] + 1024 * (c - b.a);
-    const uint8_t *src = data + c * 1024;
+    const uint8_t *src = data + (c - base) * 1024;
     if (q + 16 <= bytes) move16<true>(dst + q, src + q);
     else for (uint32_t o = q; o < bytes; ++o) dst[o] = src[o];
   }
+}
+template <int B>
+__global__ __launch_bounds__(B) void b3w_bao_range_slice_kernel(const RsRange *__restrict__ ranges, const RsRow *__restrict__ rows, uint32_t gl,
+                                                                const uint8_t *__restrict__ arena, const uint8_t *__restrict__ obs,
+                                                                uint8_t *__restrict__ slices) {
+  range_slice_body<B, false>(ranges, rows, gl, arena, obs, slices);
+}
+template <int B>
+__global__ __launch_bounds__(B) void b3w_bao_range_slice_packed_kernel(const RsRange *__restrict__ ranges, const RsRow *__restrict__ rows, uint32_t gl,
+                                                                       const uint8_t *__restrict__ packed, const uint8_t *__restrict__ obs,
+                                                                       uint8_t *__restrict__ slices) {
+  range_slice_body<B, true>(ranges, rows, gl, packed, obs, slices);
 }
 
 template <int B>
@@ -3976,6 +4108,36 @@ int32_t b3w_bao_range_slice_arena_device(b3w_ctx *ctx, const uint8_t *d_arena, u
   if (rows.big) hipLaunchKernelGGL(b3w_bao_range_slice_kernel<(int)B3W_TILE>, dim3((uint32_t)rows.big), dim3(B3W_TILE), 0, st, d_ranges, d_big, group_log, d_arena, d_outboards, d_slices);
   if (rows.small) hipLaunchKernelGGL(b3w_bao_range_slice_kernel<64>, dim3((uint32_t)rows.small), dim3(64), 0, st, d_ranges, d_small, group_log, d_arena, d_outboards, d_slices);
   return batch_launched(ctx, st, "bao range slice arena launch");
+}
+
+// the same table and grids; a range's `off` is the place of its first listed chunk in the packed buffer
+int32_t b3w_bao_range_slice_packed_device(b3w_ctx *ctx, const uint8_t *d_packed, uint64_t packed_bytes, const uint64_t *host_lens, uint32_t n_files,
+                                          uint32_t group_log, const uint8_t *d_outboards, const uint32_t *host_files, const uint64_t *host_first,
+                                          const uint64_t *host_count, uint32_t n_ranges, uint8_t *d_slices, void *stream) {
+  const char *call = "bao range slice packed";
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  B3W_TRY(group_log_ok(ctx, call, group_log));
+  if (!n_ranges) return B3W_OK;
+  if (!host_lens || !d_outboards || !host_files || !host_first || !host_count || !d_slices) return refuse(ctx, call, "a null pointer");
+  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) return refuse(ctx, call, "d_outboards is not 8-byte or d_slices not 16-byte aligned");
+  RangeRows rows;
+  B3W_TRY(range_list_ok(ctx, call, nullptr, 0, nullptr, host_lens, n_files, host_files, host_first, host_count, n_ranges, rows));
+  const PkLayout pk = b3w_int_packed_layout(host_lens, b3w_int_update_ranges(host_lens, host_files, host_first, host_count, n_ranges), group_log);
+  B3W_TRY(packed_ok(ctx, call, SparseSrc{d_packed, packed_bytes, nullptr}, pk));
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  const RsRange *d_ranges = nullptr;
+  const RsRow *d_big = nullptr, *d_small = nullptr;
+  B3W_TRY(range_table<RsRow>(ctx, host_lens, n_files, group_log, host_files, host_first, host_count, n_ranges, rows, st, d_ranges, d_big, d_small,
+                             [&](uint32_t i, uint32_t f) {
+                               uint64_t first, count;
+                               b3w_int_packed_range(host_lens[f], group_log, host_first[i], host_count[i], &first, &count);
+                               return 1024 * pk.slot_of(f, first);
+                             },
+                             [](uint32_t i, uint64_t blk, uint64_t) { return RsRow{i, (uint32_t)blk}; }));
+  if (rows.big) hipLaunchKernelGGL(b3w_bao_range_slice_packed_kernel<(int)B3W_TILE>, dim3((uint32_t)rows.big), dim3(B3W_TILE), 0, st, d_ranges, d_big, group_log, d_packed, d_outboards, d_slices);
+  if (rows.small) hipLaunchKernelGGL(b3w_bao_range_slice_packed_kernel<64>, dim3((uint32_t)rows.small), dim3(64), 0, st, d_ranges, d_small, group_log, d_packed, d_outboards, d_slices);
+  return batch_launched(ctx, st, "bao range slice packed launch");
 }
 
 int32_t b3w_bao_range_slice_ingest_device(b3w_ctx *ctx, uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,

@@ -1,7 +1,7 @@
 // b3w_bao_host.cpp — the bao calls of include/b3wit.h that never touch a device: the sizes and layouts, and the host mirrors that
 // extract, decode and take in slices (UNTRUSTED input), verify, update and resize one file node by node.  Plain C++, no kernel and no
-// HIP runtime call: tools/bao_range_host_check.cpp and tools/bao_have_host_check.cpp compile this file alone with AddressSanitizer +
-// UBSan.  The formats are described where the kernels are (b3w_bao.hip, b3w_bao_have.hip); the arithmetic both sides share is
+// HIP runtime call: tools/bao_range_host_check.cpp, tools/bao_have_host_check.cpp and tools/bao_packed_host_check.cpp compile this file
+// alone with AddressSanitizer + UBSan.  The formats are described where the kernels are (b3w_bao.hip, b3w_bao_have.hip); the arithmetic both sides share is
 // b3w_bao_tree.h.  The device entry points stay in the .hip files, and b3w_sample_rows* beside them (they need b3w_plan_path_len).
 #include "b3w_bao_plan.h"
 
@@ -257,6 +257,36 @@ UpdPlan b3w_int_update_plan(const uint64_t *lens, const std::vector<UpdRange> &r
   return p;
 }
 
+void b3w_int_packed_range(uint64_t len, uint32_t gl, uint64_t a, uint64_t c, uint64_t *first, uint64_t *count) {
+  const uint64_t n = num_chunks(len), G1 = (1ull << gl) - 1;
+  if (n <= 64) { *first = 0; *count = n; return; }
+  const uint64_t lo = a & ~G1, hi = (a + c + G1) & ~G1;
+  *first = lo; *count = (hi < n ? hi : n) - lo;
+}
+
+PkLayout b3w_int_packed_layout(const uint64_t *lens, const std::vector<UpdRange> &ranges, uint32_t gl) {
+  PkLayout p;
+  for (const UpdRange &r : ranges) {
+    uint64_t lo, cnt;
+    b3w_int_packed_range(lens[r.file], gl, r.first, r.end - r.first, &lo, &cnt);
+    if (!p.runs.empty() && p.runs.back().file == r.file && lo <= p.runs.back().end) {   // (whole groups of two ranges may meet where the ranges do not)
+      PkRun &b = p.runs.back();
+      if (lo + cnt > b.end) { p.slots += lo + cnt - b.end; b.end = lo + cnt; }
+      continue;
+    }
+    p.runs.push_back(PkRun{r.file, lo, lo + cnt, p.slots});
+    p.slots += cnt;
+  }
+  if (p.slots) p.bytes = 1024 * (p.slots - 1) + chunk_bytes(lens[p.runs.back().file], p.runs.back().end - 1);
+  return p;
+}
+
+uint64_t PkLayout::slot_of(uint32_t file, uint64_t chunk) const {
+  auto it = std::upper_bound(runs.begin(), runs.end(), chunk, [file](uint64_t c, const PkRun &r) { return file != r.file ? file < r.file : c < r.first; });
+  const PkRun &r = *(it - 1);                                          // (a listed chunk: the last run that starts at or before it holds it)
+  return r.slot + (chunk - r.first);
+}
+
 extern "C" {
 
 // ---- sizes and layouts ----------------------------------------------------------------------------------------------------------------
@@ -323,6 +353,29 @@ uint64_t b3w_bao_verify_ranges_scratch_bytes(const uint64_t *host_lens, const ui
   if (!n_ranges || !host_lens || !host_files || !host_first_chunk || !host_n_chunks) return 0;
   const UpdPlan p = b3w_int_update_plan(host_lens, b3w_int_update_ranges(host_lens, host_files, host_first_chunk, host_n_chunks, n_ranges), 0);
   return ((p.tile_slots + p.span_slots) * 36 + 15) & ~15ull;          // the expected CV (32) and the word (4) of every entry
+}
+
+int32_t b3w_bao_packed_layout(const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint32_t *host_files,
+                              const uint64_t *host_first_chunk, const uint64_t *host_n_chunks, uint32_t n_ranges, uint64_t *range_slot,
+                              uint64_t *range_first, uint64_t *range_chunks, uint64_t *total_slots, uint64_t *total_bytes) {
+  if (!total_slots || !total_bytes || group_log > B3W_BAO_MAX_GROUP_LOG) return B3W_E_BAD_ARGUMENT;
+  if (n_ranges && (!host_lens || !host_files || !host_first_chunk || !host_n_chunks)) return B3W_E_BAD_ARGUMENT;
+  for (uint32_t i = 0; i < n_ranges; ++i) {                           // (the sparse calls' own refusals)
+    if (host_files[i] >= n_files) return B3W_E_BAD_ARGUMENT;
+    const uint64_t n = num_chunks(host_lens[host_files[i]]);
+    if (n > (1ull << 30) || host_first_chunk[i] > n || host_n_chunks[i] > n - host_first_chunk[i]) return B3W_E_BAD_ARGUMENT;
+  }
+  const PkLayout p = b3w_int_packed_layout(host_lens, b3w_int_update_ranges(host_lens, host_files, host_first_chunk, host_n_chunks, n_ranges), group_log);
+  for (uint32_t i = 0; i < n_ranges; ++i) {
+    uint64_t first = 0, count = 0;
+    if (host_n_chunks[i]) b3w_int_packed_range(host_lens[host_files[i]], group_log, host_first_chunk[i], host_n_chunks[i], &first, &count);
+    if (range_slot) range_slot[i] = count ? p.slot_of(host_files[i], first) : 0;
+    if (range_first) range_first[i] = first;
+    if (range_chunks) range_chunks[i] = count;
+  }
+  *total_slots = p.slots;
+  *total_bytes = p.bytes;
+  return B3W_OK;
 }
 
 uint64_t b3w_bao_resize_kept_tiles(uint64_t old_len, uint64_t new_len) { return (old_len < new_len ? old_len : new_len) / RES_TB; }

@@ -1,5 +1,6 @@
 // b3w_bao_plan.h — the plan of the sparse bao calls (update, ranged verification): defined in b3w_bao_host.cpp, where the scratch sizes
-// use it; the two device entry points of b3w_bao.hip build their tables from it.  Not installed.
+// use it; the device entry points of b3w_bao.hip build their tables from it, and their packed twins find their chunks' slots with the
+// packed layout below.  Not installed.
 #pragma once
 #include <vector>
 
@@ -17,3 +18,17 @@ struct UpdPlan {
 std::vector<UpdRange> b3w_int_update_ranges(const uint64_t *lens, const uint32_t *files, const uint64_t *first, const uint64_t *count, uint32_t n_ranges);
 // what a call over these (sorted, merged) ranges launches; the chunk masks are expanded to whole groups of 1 << gl chunks
 UpdPlan b3w_int_update_plan(const uint64_t *lens, const std::vector<UpdRange> &ranges, uint32_t gl);
+
+// The packed layout (b3wit.h "sparse calls from packed chunk bytes"): the chunks b3w_int_update_plan has hashed, as runs of consecutive
+// chunks of one file in consecutive slots of 1 024 bytes, sorted by (file, first chunk); no two runs of a file touch.
+struct PkRun { uint32_t file; uint64_t first, end, slot; };           // chunks [first, end) of the file lie from slot `slot` on
+struct PkLayout {
+  std::vector<PkRun> runs;
+  uint64_t slots = 0, bytes = 0;                                      // bytes: the end of the last listed chunk's last byte
+  uint64_t slot_of(uint32_t file, uint64_t chunk) const;              // of a LISTED chunk
+};
+// over the (sorted, merged) ranges of b3w_int_update_ranges: a file of at most 64 chunks lists all its chunks, any other one the
+// whole groups of 1 << gl chunks its ranges touch, clamped to the file
+PkLayout b3w_int_packed_layout(const uint64_t *lens, const std::vector<UpdRange> &ranges, uint32_t gl);
+// the chunks [*first, *first + *count) that range (file, a, c) of a call lists, c > 0: its groups, or all of a file of at most 64 chunks
+void b3w_int_packed_range(uint64_t len, uint32_t gl, uint64_t a, uint64_t c, uint64_t *first, uint64_t *count);

@@ -1303,6 +1303,63 @@ int32_t b3w_bao_verify_ranges(const uint8_t *data, uint64_t len, const uint8_t *
                               const uint64_t *host_first_chunk, const uint64_t *host_n_chunks, uint32_t n_ranges, uint8_t *unit_status,
                               int32_t *range_status, uint64_t *range_first_bad);
 
+/* ---- sparse calls from packed chunk bytes: files that are NOT resident (still ABI 1.4: new names only) ------------------
+ * The update call, the ranged verification and the range-slice provider read only the chunks their ranges list, yet they take the
+ * arena: the whole file has to be in device memory for them to find those chunks at offset + 1024 c.  A provider whose file is on
+ * disk (the streamed sessions above are for it) gathers the listed chunks alone into a PACKED buffer and calls the twins below.
+ * THE LISTED CHUNKS of a call with (host_lens, group_log, ranges (file, first_chunk, n_chunks)):
+ *   a file of at most 64 chunks with a range that is not empty lists ALL its chunks (the small kernels rehash and verify it whole);
+ *   any other file lists every chunk of every unit of 2^group_log chunks that a range touches, clamped to the file
+ * — the chunks the arena calls hash.  Every listed chunk takes one SLOT of 1 024 bytes: listed files in ascending index, within a
+ * file its distinct listed chunks in ascending order, slots numbered from 0 across the call; a file's short last chunk fills the
+ * front of its slot and the rest of that slot is never read.  Chunk c lies at d_packed + 1024 slot(c), and the chunks an input range
+ * lists are consecutive slots whatever the order, overlap or repetition of the ranges. */
+/* Host only.  The layout: the listed chunks of range i are the file's chunks [range_first[i], range_first[i] + range_chunks[i]), to
+ * be copied to slot range_slot[i] onwards (ranges that share a chunk name the same slot for it); an empty range gets range_chunks[i]
+ * = 0 (and slot and first 0).  The three arrays (n_ranges entries each) may be NULL.  *total_slots: the slots of the call;
+ * *total_bytes: the end of the last byte any call reads, 1024 (total_slots - 1) + the bytes of the chunk in the last slot, 0 with
+ * nothing listed.  B3W_E_BAD_ARGUMENT, nothing written, for what the sparse calls refuse: a null pointer (the totals; the inputs
+ * where n_ranges > 0), group_log above the maximum, a file index >= n_files, a range that reaches past its file's chunk count, a
+ * listed file of more than 2^30 chunks.  O(n_ranges log n_ranges); host_lens is read at listed files only. */
+int32_t b3w_bao_packed_layout(const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint32_t *host_files,
+                              const uint64_t *host_first_chunk, const uint64_t *host_n_chunks, uint32_t n_ranges, uint64_t *range_slot,
+                              uint64_t *range_first, uint64_t *range_chunks, uint64_t *total_slots, uint64_t *total_bytes);
+/* The three twins: the arguments of b3w_bao_outboard_update_batch_device, b3w_bao_verify_ranges_batch_device and
+ * b3w_bao_range_slice_arena_device with (d_packed, packed_bytes) for (d_arena, arena_bytes, host_offsets).  d_packed holds the listed
+ * chunks of THIS call's ranges and group_log as b3w_bao_packed_layout places them, at any byte alignment (16-byte aligned it is read
+ * in 16-byte pieces, as an arena file at such an offset).  EVERY OUTPUT BYTE IS WHAT THE ARENA COUNTERPART WRITES for an arena that
+ * holds the same file bytes, with the same outboards, roots, ranges and group_log, and every byte it leaves alone stays untouched:
+ * outboard nodes, header, roots; unit statuses, range statuses, first bad units; slices.  The same launch bounds (four, five, two),
+ * the same scratch (b3w_bao_update_scratch_bytes, b3w_bao_verify_ranges_scratch_bytes), the same table through the same staging;
+ * nothing is allocated, the host waits for nothing.  The tile kernels are instantiations that address by rank: a row carries the
+ * slot of its tile's first listed chunk, and lane t reads behind the listed chunks of the tile below t while its counter and its
+ * length stay those of chunk 1 024 tile + t; the small-file launches, the storeys above the tiles and the reduction are the arena
+ * calls' own kernels.  In a range slice the source of chunk c of range r is d_packed + 1024 (range_slot[r] + c - range_first[r]).
+ * REFUSALS ARE ATOMIC and name the range: the arena calls' lists without the arena items (null arena, a file past arena_bytes), and
+ * a null d_packed where total_bytes > 0, and packed_bytes < total_bytes (b3w_last_error gives the number needed).  No byte at or
+ * behind total_bytes, and no byte of a slot behind a short last chunk, is read.
+ * WHEN NOT TO (MI355X; device events round whole calls against the arena call of the same build): a file that IS
+ * resident.  The arena calls read it in place, need no gather and no layout, and are the faster calls on every shape measured: one,
+ * 64 ranges of 4 KiB or 64 runs of 1 024 chunks of a 1 GiB file 1 to 2 us behind; 4 096 ranges of 4 KiB 0.412 ms against 0.388 (update),
+ * 0.422 against 0.400 (ranged verification), 0.431 against 0.262 (range slices: this call sorts the ranges, the arena call does not);
+ * 4 096 listed files of 4 KiB 0.181 against 0.106, 0.199 against 0.127, 0.446 against 0.329.  The difference is the layout on the
+ * host.  What the packed calls save is device memory and upload: total_bytes instead of the files. */
+int32_t b3w_bao_outboard_update_packed_device(b3w_ctx *ctx, const uint8_t *d_packed, uint64_t packed_bytes, const uint64_t *host_lens,
+                                              uint32_t n_files, uint32_t group_log, const uint64_t *host_ob_first, uint8_t *d_outboards,
+                                              uint32_t *d_roots, const uint32_t *host_files, const uint64_t *host_first_chunk,
+                                              const uint64_t *host_n_chunks, uint32_t n_ranges, void *d_scratch, uint64_t scratch_bytes,
+                                              void *stream);
+int32_t b3w_bao_verify_ranges_packed_device(b3w_ctx *ctx, const uint8_t *d_packed, uint64_t packed_bytes, const uint64_t *host_lens,
+                                            uint32_t n_files, uint32_t group_log, const uint64_t *host_ob_first, const uint8_t *d_outboards,
+                                            const uint32_t *d_roots, const uint32_t *host_files, const uint64_t *host_first_chunk,
+                                            const uint64_t *host_n_chunks, uint32_t n_ranges, const uint64_t *host_unit_first,
+                                            uint8_t *d_unit_status, int32_t *d_range_status, uint64_t *d_range_first_bad, void *d_scratch,
+                                            uint64_t scratch_bytes, void *stream);
+int32_t b3w_bao_range_slice_packed_device(b3w_ctx *ctx, const uint8_t *d_packed, uint64_t packed_bytes, const uint64_t *host_lens,
+                                          uint32_t n_files, uint32_t group_log, const uint8_t *d_outboards, const uint32_t *host_files,
+                                          const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, uint8_t *d_slices,
+                                          void *stream);
+
 /* ---- resident files after appends and truncations (still ABI 1.4: new names only) -------------------------------------
  * The update call above follows writes that keep a file's length.  These calls follow a CHANGE of length.  In a pre-order outboard
  * the PLACE of every node can move when the length changes; the VALUES below a tile of 1 024 chunks that is full before and after
