@@ -239,6 +239,14 @@ def lib():
         "b3w_bao_outboard_update_packed_device": (i32, [vp, vp, u64, vp, u32, u32, vp, vp, vp, vp, vp, vp, u32, vp, u64, vp]),
         "b3w_bao_verify_ranges_packed_device": (i32, [vp, vp, u64, vp, u32, u32, vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, u64, vp]),
         "b3w_bao_range_slice_packed_device": (i32, [vp, vp, u64, vp, u32, u32, vp, vp, vp, vp, u32, vp, vp]),
+        "b3w_bao_set_slice_size": (u64, [u64, vp, vp, u32]),
+        "b3w_bao_set_slice_batch_layout": (ctypes.c_int64, [vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, ctypes.POINTER(u32)]),
+        "b3w_bao_set_slice": (ctypes.c_int64, [vp, u64, u32, vp, vp, u32, vp, vp, u64]),
+        "b3w_bao_set_slice_decode": (i32, [vp, u64, u64, vp, vp, u32, vp, vp, vp, ctypes.POINTER(i32), ctypes.POINTER(u64)]),
+        "b3w_bao_set_slice_ingest": (i32, [vp, u64, u64, vp, vp, u32, vp, u32, vp, vp, vp, vp, ctypes.POINTER(i32), ctypes.POINTER(u64)]),
+        "b3w_bao_set_slice_arena_device": (i32, [vp, vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, u32, vp, vp]),
+        "b3w_bao_set_slice_ingest_scratch_bytes": (u64, [vp, u32, vp, vp, vp, u32]),
+        "b3w_bao_set_slice_ingest_device": (i32, [vp, vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, u64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -281,7 +289,10 @@ EXPORTED_SYMBOLS = ("b3w_abi_version", "b3w_identify_wasm", "b3w_create", "b3w_d
                     "b3w_bao_range_slice_ingest", "b3w_bao_range_slice_arena_device", "b3w_bao_range_slice_ingest_scratch_bytes",
                     "b3w_bao_range_slice_ingest_device", "b3w_sample_rows_ranges", "b3w_sample_plan_range_slices_device",
                     "b3w_bao_packed_layout", "b3w_bao_outboard_update_packed_device", "b3w_bao_verify_ranges_packed_device",
-                    "b3w_bao_range_slice_packed_device")
+                    "b3w_bao_range_slice_packed_device",
+                    "b3w_bao_set_slice_size", "b3w_bao_set_slice_batch_layout", "b3w_bao_set_slice", "b3w_bao_set_slice_decode",
+                    "b3w_bao_set_slice_ingest", "b3w_bao_set_slice_arena_device", "b3w_bao_set_slice_ingest_scratch_bytes",
+                    "b3w_bao_set_slice_ingest_device")
 
 
 class graph_capture:

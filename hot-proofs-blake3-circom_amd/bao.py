@@ -910,6 +910,149 @@ def ingest_range_slice_host(data, outboard, length, first_chunk, n_chunks, root,
     return st.value, (None if fb.value == 2 ** 64 - 1 else fb.value)
 
 
+# ---- set slices: one slice for all the wanted runs of a file --------------------------------------------------------------
+def set_slice_size(length, first_chunks, n_chunks):
+    """8 + 64 U_S + the bytes of S: the bao slice of the union S of one file's runs (ascending and disjoint, touching allowed), every
+    shared node once"""
+    fc, nc = _ranges(first_chunks, n_chunks)
+    size = lib().b3w_bao_set_slice_size(length, fc.ctypes.data, nc.ctypes.data, fc.size)
+    if not size:
+        raise B3WError(100, "b3w_bao_set_slice_size: the list is empty, a run is empty or reaches past the chunk count, or the runs are not ascending and disjoint")
+    return size
+
+
+def set_slice_layout(lens, files, first_chunks, n_chunks):
+    """The sets of a range list (ascending by (file, first chunk), disjoint: have_runs' rows as they come) -> dict(set_file uint32
+    [n_sets], set_range_first uint32 [n_sets + 1], set_chunk_first uint64 [n_sets + 1], slice_first uint64 [n_sets + 1]): set s is the
+    ranges [set_range_first[s], set_range_first[s + 1]) of file set_file[s], its per-chunk statuses lie from set_chunk_first[s], its
+    slice from slice_first[s] of the packed slices (every start 8 modulo 16); the last entries are the totals"""
+    ln = _u64(lens)
+    fi = np.ascontiguousarray(files, dtype=np.uint32)
+    fc, nc = _ranges(first_chunks, n_chunks)
+    if fi.size != fc.size:
+        raise B3WError(100, f"set_slice_layout: {fi.size} files and {fc.size} ranges")
+    sfile = np.zeros(fc.size + 1, dtype=np.uint32)
+    srf = np.zeros(fc.size + 1, dtype=np.uint32)
+    scf = np.zeros(fc.size + 1, dtype=np.uint64)
+    sf = np.zeros(fc.size + 1, dtype=np.uint64)
+    k = ctypes.c_uint32()
+    total = lib().b3w_bao_set_slice_batch_layout(ln.ctypes.data, ln.size, fi.ctypes.data, fc.ctypes.data, nc.ctypes.data, fc.size, sfile.ctypes.data,
+                                                 srf.ctypes.data, scf.ctypes.data, sf.ctypes.data, ctypes.byref(k))
+    if total < 0:
+        raise B3WError(-total, "b3w_bao_set_slice_batch_layout: a file index is not below the file count, a range is empty or reaches past its file's "
+                               "chunk count, or the list is not ascending by (file, first chunk) and disjoint")
+    k = k.value
+    return dict(set_file=sfile[:k].copy(), set_range_first=srf[:k + 1].copy(), set_chunk_first=scf[:k + 1].copy(), slice_first=sf[:k + 1].copy())
+
+
+def set_slices_arena(ctx, d_arena, offsets, lens, d_outboards, files, first_chunks, n_chunks, group_log=0, stream=0):
+    """The provider's side for ALL the wanted runs of a file in one slice: range_slices_arena's arguments, the ranges ascending by
+    (file, first chunk) and disjoint - have_runs' rows as they come.  A file's runs make one set slice that carries every node they
+    share once; a tile's lanes are busy with every wanted chunk of the tile however the chunks are cut into runs.  At most two
+    launches; nothing is verified.  Measured (MI355X, DESIGN.md §8g, against a build of the commit before): the 262 507 runs of a
+    half-missing 1 GiB file 3.20 ms against range_slices_arena's 13.22, for 593 MB against 892; but 4 096 scattered runs of 16 take
+    0.35 ms against 0.25 and 64 runs of 1 024 0.110 against 0.081 — few long or sparse medium runs stay with the range call.  Returns dict(slices: uint8 CUDA tensor, packed; **set_slice_layout)."""
+    off, ln, fi, fc, nc = _range_args("set_slices_arena", d_arena, offsets, lens, d_outboards, files, first_chunks, n_chunks, group_log)
+    lay = set_slice_layout(ln, fi, fc, nc)
+    d_slices = torch.zeros(int(lay["slice_first"][-1]) if fc.size else 0, dtype=torch.uint8, device=d_outboards.device)
+    _chk(ctx, lib().b3w_bao_set_slice_arena_device(ctx.handle, d_arena.data_ptr() if d_arena.numel() else None, d_arena.numel(), off.ctypes.data,
+                                                   ln.ctypes.data, ln.size, group_log, d_outboards.data_ptr(), fi.ctypes.data, fc.ctypes.data,
+                                                   nc.ctypes.data, fc.size, d_slices.data_ptr(), _stream(stream)), "b3w_bao_set_slice_arena_device")
+    return dict(slices=d_slices, **lay)
+
+
+def ingest_set_slices(ctx, d_arena, offsets, lens, d_outboards, d_roots, files, first_chunks, n_chunks, d_slices, group_log=0, stream=0, d_have=None):
+    """The receiver's side for set slices, set_slices_arena's mirror image: every wanted chunk gets the status its own one-chunk slice
+    would get, and the chunks of status 0 write what ingest_slices writes for them - bytes, stored path nodes, header, and their bit
+    in d_have where one is given.  A bad node keeps out the chunks below it and no other.  At most three launches.  When not to
+    (MI355X, DESIGN.md §8g, against a build of the commit before): the 262 507 runs of a half-missing 1 GiB file take 3.70 ms against
+    20.86 for ingest_range_slices and 16.85 for ingest_slices over runs_chunks, 65 536 runs of one chunk 1.30 against 5.45 and 2.17 —
+    but a set takes a workgroup per touched tile, so 4 096 scattered runs of 16 take 0.78 ms against ingest_range_slices' 0.39, and
+    64 runs of 1 024 chunks 0.237 against 0.214: a few long runs or a sparse scatter of medium ones stay with the range call.  This
+    wrapper makes its outputs and its scratch on every call; a loop that matters keeps them and calls b3w_bao_set_slice_ingest_device.
+    Returns dict(set_status: int32 CUDA, the largest chunk status of each set; set_first_bad: int64 CUDA, the first chunk of the file
+    whose status is not 0, -1 for none; chunk_status: int32 CUDA, a wanted chunk each, set s's from set_chunk_first[s];
+    **set_slice_layout)."""
+    L = lib()
+    off, ln, fi, fc, nc = _range_args("ingest_set_slices", d_arena, offsets, lens, d_outboards, files, first_chunks, n_chunks, group_log)
+    lay = set_slice_layout(ln, fi, fc, nc)
+    dev = d_slices.device
+    n_sets = lay["set_file"].size
+    assert d_roots.is_cuda and d_roots.is_contiguous() and d_roots.numel() >= ln.size * 8
+    assert d_slices.is_cuda and d_slices.dtype == torch.uint8 and d_slices.is_contiguous() and d_slices.numel() >= (int(lay["slice_first"][-1]) if fc.size else 0)
+    if d_have is not None:
+        _have_tensor("ingest_set_slices", d_have, ln)
+    st = torch.full((n_sets,), -1, dtype=torch.int32, device=dev)
+    fb = torch.full((n_sets,), -2, dtype=torch.int64, device=dev)
+    cs = torch.full((int(lay["set_chunk_first"][-1]),), -1, dtype=torch.int32, device=dev)
+    need = L.b3w_bao_set_slice_ingest_scratch_bytes(ln.ctypes.data, ln.size, fi.ctypes.data, fc.ctypes.data, nc.ctypes.data, fc.size)
+    scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    _chk(ctx, L.b3w_bao_set_slice_ingest_device(ctx.handle, d_arena.data_ptr() if d_arena.numel() else None, d_arena.numel(), off.ctypes.data,
+                                                ln.ctypes.data, ln.size, group_log, d_outboards.data_ptr(), d_roots.data_ptr(), fi.ctypes.data,
+                                                fc.ctypes.data, nc.ctypes.data, fc.size, d_slices.data_ptr(), st.data_ptr(), fb.data_ptr(),
+                                                cs.data_ptr() if cs.numel() else None, d_have.data_ptr() if d_have is not None else None,
+                                                scratch.data_ptr(), scratch.numel(), _stream(stream)), "b3w_bao_set_slice_ingest_device")
+    return dict(set_status=st, set_first_bad=fb, chunk_status=cs, **lay)
+
+
+def set_slice_host(outboard, length, first_chunks, n_chunks, data, group_log=0):
+    """The set slice of one file on the host (no GPU) from its outboard of this group_log and the file's bytes -> bytes"""
+    if not 0 <= group_log <= MAX_GROUP_LOG:
+        raise B3WError(100, f"group_log {group_log} is not in 0 .. {MAX_GROUP_LOG}")
+    fc, nc = _ranges(first_chunks, n_chunks)
+    size = set_slice_size(length, fc, nc)
+    ob, d = bytes(outboard), bytes(data)
+    if len(ob) != group_outboard_size(length, group_log) or len(d) != length:
+        raise B3WError(100, "set_slice_host: the outboard is not that of a file of this length, or data not the file's bytes")
+    out = ctypes.create_string_buffer(size)
+    got = lib().b3w_bao_set_slice(ob, length, group_log, fc.ctypes.data, nc.ctypes.data, fc.size, d, out, size)
+    if got != size:
+        raise B3WError(100 if got >= 0 else -got, "b3w_bao_set_slice")
+    return out.raw
+
+
+def decode_set_slice(slice_bytes, length, first_chunks, n_chunks, root):
+    """The sequential decoder for one set slice on the host -> (set status as STATUS, first bad chunk or None, chunk status int32 a
+    wanted chunk, the wanted chunks' bytes at 1024 rank with the chunks that did not verify left zero)"""
+    sl = bytes(slice_bytes)
+    fc, nc = _ranges(first_chunks, n_chunks)
+    rw = np.ascontiguousarray(root, dtype=np.uint32)
+    total = int(nc.sum(dtype=np.uint64))
+    out = np.zeros(max(1, total) * 1024, dtype=np.uint8)
+    cs = np.full(max(1, total), -1, dtype=np.int32)
+    st, fb = ctypes.c_int32(), ctypes.c_uint64()
+    _chk(None, lib().b3w_bao_set_slice_decode(sl, len(sl), length, fc.ctypes.data, nc.ctypes.data, fc.size, rw.ctypes.data, out.ctypes.data, cs.ctypes.data,
+                                              ctypes.byref(st), ctypes.byref(fb)), "b3w_bao_set_slice_decode")
+    last = int(fc[-1] + nc[-1])
+    end = total * 1024 - (1024 - (length - (last - 1) * 1024) if last == num_chunks(length) else 0)
+    return st.value, (None if fb.value == 2 ** 64 - 1 else fb.value), cs[:total].copy(), out[:end].tobytes()
+
+
+def ingest_set_slice_host(data, outboard, length, first_chunks, n_chunks, root, slice_bytes, group_log=0, have=None):
+    """ingest_set_slices for one file on the host (no GPU): data, outboard (and have: the file's bitmap words, numpy uint64, or None)
+    are written in place where chunks verify -> (set status as STATUS, first bad chunk or None, chunk status int32 a wanted chunk)"""
+    if not 0 <= group_log <= MAX_GROUP_LOG:
+        raise B3WError(100, f"group_log {group_log} is not in 0 .. {MAX_GROUP_LOG}")
+    d, ob = _writable(data, "data"), _writable(outboard, "outboard")
+    if d.size != length or ob.size != group_outboard_size(length, group_log):
+        raise B3WError(100, "ingest_set_slice_host: data is not of this length or the outboard not that of a file of this length")
+    if have is not None and not (isinstance(have, np.ndarray) and have.dtype == np.uint64 and have.flags.c_contiguous and have.flags.writeable
+                                 and have.size == (num_chunks(length) + 63) // 64):
+        raise B3WError(100, "ingest_set_slice_host: have is not the writable uint64 bitmap of a file of this length")
+    sl = bytes(slice_bytes)
+    fc, nc = _ranges(first_chunks, n_chunks)
+    rw = np.ascontiguousarray(root, dtype=np.uint32)
+    if rw.size != 8:
+        raise B3WError(100, "ingest_set_slice_host: the root is 8 words")
+    total = int(nc.sum(dtype=np.uint64))
+    cs = np.full(max(1, total), -1, dtype=np.int32)
+    st, fb = ctypes.c_int32(), ctypes.c_uint64()
+    _chk(None, lib().b3w_bao_set_slice_ingest(sl, len(sl), length, fc.ctypes.data, nc.ctypes.data, fc.size, rw.ctypes.data, group_log,
+                                              d.ctypes.data if d.size else None, ob.ctypes.data, have.ctypes.data if have is not None else None,
+                                              cs.ctypes.data, ctypes.byref(st), ctypes.byref(fb)), "b3w_bao_set_slice_ingest")
+    return st.value, (None if fb.value == 2 ** 64 - 1 else fb.value), cs[:total].copy()
+
+
 # ---- verification: whole files against their outboards ------------------------------------------------------------------
 def verify_layout(lens, group_log=0):
     """-> unit_first (numpy uint64 [n_files + 1]): file f's unit statuses are entries [unit_first[f], unit_first[f + 1]) of the packed

@@ -4224,3 +4224,420 @@ int32_t b3w_sample_plan_range_slices_device(b3w_ctx *ctx, const uint64_t *host_l
 }
 
 }  // extern "C"
+
+// ---- set slices: one slice for the union S of a file's runs, extracted and taken in (still ABI 1.4: new names only) ----------------------
+// The format and the places are b3wit.h's "set slices"; the arithmetic the host shares is b3w_bao_tree.h's.  The kernels are the range
+// kernels' siblings: a ROW is (set, block of B aligned chunks with a wanted chunk), `mine` is the row's mask bit where the range kernels
+// ask t in [lo, hi), and a node's place follows from the first wanted chunk at or behind its first lane.  The device never sees the runs:
+//   lv[0]      the row's mask, 64 lanes a word
+//   lv[l]      the mask OR-folded by 2^l: bit j says that S meets lanes [j << l, (j + 1) << l) - the `meets` of the node of that span
+//   rel[t]     of a wanted lane: 64 (U_S(c) - U_S(cf)) + 1024 (the wanted lanes below t), cf the row's first wanted lane; the node of
+//              level l over index j is a parent iff (j << l) + 2^(l-1) < m, so U_S(c) - U_S(cf) = the sum over l of the set bits of
+//              lv[l] at the parents of index <= t >> l, less the nodes of cf's own path (full tile: popcount(L_l[0 .. c >> l]) - 1 a level)
+//   lane_of[r] the r-th wanted lane: the byte movers walk the wanted chunks alone
+// The table carries, a row, the place and rank of cf and the places of the nodes above the block (SET_UP of them at most); the row that
+// holds the first wanted chunk below such a node finds its place equal to place(cf) - 64 (the nodes of cf's path at or below it).
+namespace {
+
+constexpr uint32_t SET_UP = 24;                           // nodes above a block of 64 chunks of a file of at most 2^30 chunks
+struct SetDev { uint64_t len, off, ob, slice, have, chunk_first; uint32_t file, row0, n_rows, pad; };   // row0: its first row's result
+template <int B>
+struct SetRow { uint32_t set, block; uint64_t place0, rank0, up[SET_UP]; uint32_t mask[B / 32]; };
+template <int B>
+struct SetLds { unsigned long long lv[B == 64 ? 7 : 11][B / 64]; uint32_t rel[B]; uint16_t lane_of[B]; };
+struct SetLanes { uint32_t cf, cnt, rank; bool mine; };   // the first wanted lane, their number; this lane's rank among them
+
+__device__ __forceinline__ bool set_bit(const unsigned long long *w, uint32_t i) { return (w[i >> 6] >> (i & 63)) & 1ull; }
+// the set bits of w at indices 0 .. idx
+__device__ __forceinline__ uint32_t set_prefix(const unsigned long long *w, uint32_t idx) {
+  uint32_t r = 0;
+  for (uint32_t k = 0; k < (idx >> 6); ++k) r += (uint32_t)__popcll(w[k]);
+  return r + (uint32_t)__popcll(w[idx >> 6] & ((2ull << (idx & 63)) - 1));
+}
+// the first set bit at or behind i0 (the caller knows there is one below the words' end)
+template <int B>
+__device__ __forceinline__ uint32_t set_first_at(const unsigned long long *w, uint32_t i0) {
+  uint32_t k = i0 >> 6;
+  unsigned long long x = w[k] & (~0ull << (i0 & 63));
+  while (!x && k + 1 < B / 64) x = w[++k];
+  return x ? k * 64 + (uint32_t)__ffsll((long long)x) - 1 : B - 1;
+}
+
+// the row's masks, rel[] and lane_of[] into LDS (ends with a barrier); m: the block's chunks
+template <int B>
+__device__ __forceinline__ SetLanes set_lanes(const SetRow<B> *__restrict__ row, uint32_t m, uint32_t t, SetLds<B> &s) {
+  constexpr uint32_t LOG = B == 64 ? 6 : 10;
+  if (t < B / 64) s.lv[0][t] = (unsigned long long)row->mask[2 * t] | ((unsigned long long)row->mask[2 * t + 1] << 32);
+  lds_barrier();
+#pragma unroll
+  for (uint32_t l = 1; l <= LOG; ++l) {
+    bool bit = false;
+    if (t < (B >> l)) {
+      if (l <= 6) {
+        const unsigned long long word = s.lv[0][(t << l) >> 6] >> ((t << l) & 63);
+        bit = (l == 6 ? word : word & ((1ull << (1u << l)) - 1)) != 0;
+      } else {
+        for (uint32_t k = 0; k < (1u << (l - 6)); ++k) bit |= s.lv[0][(t << (l - 6)) + k] != 0;
+      }
+    }
+    const unsigned long long b = __ballot(bit);
+    if ((t & 63) == 0 && t < (B >> l)) s.lv[l][t >> 6] = b;
+  }
+  lds_barrier();
+  SetLanes w;
+  w.cf = set_first_at<B>(s.lv[0], 0);
+  w.cnt = set_prefix(s.lv[0], B - 1);
+  w.mine = set_bit(s.lv[0], t);
+  w.rank = 0;
+  if (w.mine) {
+    w.rank = set_prefix(s.lv[0], t) - 1;
+    uint32_t u = 0;
+#pragma unroll
+    for (uint32_t l = 1; l <= LOG; ++l) {
+      const uint32_t half = 1u << (l - 1);
+      if (m <= half) break;
+      const uint32_t parents = (m - half + (1u << l) - 1) >> l, idx = t >> l;
+      u += set_prefix(s.lv[l], idx < parents ? idx : parents - 1);
+    }
+    s.rel[t] = 64 * (u - depth_in(w.cf, m)) + 1024 * w.rank;
+    s.lane_of[w.rank] = (uint16_t)t;
+  }
+  lds_barrier();
+  return w;
+}
+// the node over the block's lanes [i0, i0 + size), which meets S: its place in the slice behind the row's place0
+template <int B>
+__device__ __forceinline__ uint64_t set_block_node_at(const SetRow<B> *__restrict__ row, const SetLds<B> &s, uint32_t i0, uint32_t size) {
+  const uint32_t c0 = set_first_at<B>(s.lv[0], i0);
+  return row->place0 + s.rel[c0] - 64ull * depth_in(c0 - i0, size);
+}
+
+// THE PROVIDER (range_slice_body with the mask for the interval)
+template <int B>
+__global__ __launch_bounds__(B) void b3w_bao_set_slice_kernel(const SetDev *__restrict__ sets, const SetRow<B> *__restrict__ rows, uint32_t gl,
+                                                              const uint8_t *__restrict__ arena, const uint8_t *__restrict__ obs,
+                                                              uint8_t *__restrict__ slices) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B * 8];
+  __shared__ SetLds<B> s;
+  const SetRow<B> *__restrict__ row = rows + blockIdx.x;
+  const SetDev r = sets[row->set];
+  const uint32_t t = threadIdx.x;
+  const uint64_t n = r.len ? (r.len + 1023) / 1024 : 1, a0 = (uint64_t)row->block * B;
+  const uint32_t m = (uint32_t)(n - a0 < B ? n - a0 : B);
+  const bool sole = n <= B;
+  const uint8_t *__restrict__ data = arena + r.off, *__restrict__ ob = obs + r.ob;
+  uint8_t *__restrict__ sl = slices + r.slice;
+  const SetLanes w = set_lanes<B>(row, m, t, s);
+  // group outboards: the chunks of the touched groups, hashed (no byte behind the file's last one is read)
+  if (gl != 0 && t < m && set_bit(s.lv[gl], t >> gl)) lane_chunk_cv(cv, data, a0 + t, r.len, n, a0 + t, true);
+  for (uint32_t l = 0; (1u << l) < m; ++l) {
+    if (l <= gl) lds_barrier();                            // (the level below inside a group; above the groups nothing is handed on)
+    const uint32_t i0 = (2 * t) << l, i1 = i0 + (1u << l);
+    if (i1 >= m) continue;
+    const uint32_t end = i0 + (2u << l), size = (end < m ? end : m) - i0;
+    const bool meets = set_bit(s.lv[l + 1], t);
+    uint8_t *place = meets ? sl + set_block_node_at<B>(row, s, i0, size) : nullptr;
+    if (l < gl) {                                          // inside a group: computed, and stored where the set wants it
+      if (set_bit(s.lv[gl], i0 >> gl)) merge_pair<true>(cv, i0, i1, place, 4u | (sole && (2u << l) >= m ? 8u : 0u));
+    } else if (meets) {
+      copy_node(place, ob + 8 + node_pos<true>(n, a0 + i0, size, gl) * 64);
+    }
+  }
+  // the nodes above the block whose first wanted chunk lies in it, and the header in front of min S
+  const RsAbove up = range_above(n, a0, m, t);
+  const uint64_t own = row->place0 - 64ull * (up.depth + depth_in(w.cf, m));     // the place of the root, if this row holds min S
+  if (t < up.depth && row->up[t] == own + 64ull * t) copy_node(sl + row->up[t], ob + 8 + node_pos<true>(n, up.lo, up.cnt, gl) * 64);
+  if (t == 0 && own == 8) *reinterpret_cast<uint2 *>(sl) = *reinterpret_cast<const uint2 *>(ob);
+  for (uint32_t p = t; p < w.cnt * 64; p += B) {
+    const uint32_t ch = s.lane_of[p >> 6], q = (p & 63) * 16;
+    const uint64_t c = a0 + ch;
+    const uint32_t bytes = range_chunk_bytes(r.len, c);
+    uint8_t *dst = sl + row->place0 + s.rel[ch];
+    const uint8_t *src = data + c * 1024;
+    if (q + 16 <= bytes) move16<true>(dst + q, src + q);
+    else for (uint32_t o = q; o < bytes; ++o) dst[o] = src[o];
+  }
+}
+
+// THE RECEIVER (b3w_bao_range_ingest_kernel with the mask for the interval, and a status a wanted chunk)
+template <int B>
+__global__ __launch_bounds__(B) void b3w_bao_set_ingest_kernel(const SetDev *__restrict__ sets, const SetRow<B> *__restrict__ rows, uint32_t gl,
+                                                               const uint8_t *__restrict__ slices, const uint32_t *__restrict__ roots,
+                                                               uint8_t *__restrict__ arena, uint8_t *__restrict__ obs, int32_t *__restrict__ chunk_status,
+                                                               unsigned long long *__restrict__ have, uint4 *__restrict__ results) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B * 8];
+  __shared__ uint32_t flags[B], listed[B];
+  __shared__ SetLds<B> s;
+  __shared__ uint32_t worst, first, above;
+  const SetRow<B> *__restrict__ row = rows + blockIdx.x;
+  const SetDev r = sets[row->set];
+  const uint32_t t = threadIdx.x;
+  const uint64_t n = r.len ? (r.len + 1023) / 1024 : 1, a0 = (uint64_t)row->block * B;
+  const uint32_t m = (uint32_t)(n - a0 < B ? n - a0 : B);
+  const bool sole = n <= B;
+  const uint8_t *__restrict__ sl = slices + r.slice;
+  const uint32_t *__restrict__ root = roots + (uint64_t)r.file * 8;
+  flags[t] = 0;
+  if (t == 0) { worst = 0; first = ~0u; above = 0; }
+  const SetLanes w = set_lanes<B>(row, m, t, s);
+  const bool mine = w.mine;
+  listed[t] = mine ? 1u : 0u;
+  // 1. the verdicts: the wanted chunks, the block's nodes bottom up, the nodes above the block side by side
+  if (mine) {
+    const uint64_t c = a0 + t;
+    uint32_t h[8];
+    chunk_cv(sl + row->place0 + s.rel[t], range_chunk_bytes(r.len, c), c, n == 1 ? 8u : 0u, h);   // (16-byte aligned)
+    put_cv(cv, t, h);
+  }
+  const RsAbove up = range_above(n, a0, m, t);
+  if (t < up.depth) {
+    uint32_t mw[16], ivv[8], o[8];
+    load_node(sl + row->up[t], mw);
+    iv(ivv);
+    blake3_cv(ivv, mw, 0, 0, 64, 4u | (t == 0 ? 8u : 0u), o);
+    const uint32_t *want = t == 0 ? root : reinterpret_cast<const uint32_t *>(sl + row->up[t - 1] + (up.left ? 0 : 32));
+    if (!eq8(o, want)) atomicOr(&above, 1u);
+  }
+  for (uint32_t l = 0; (1u << l) < m; ++l) {
+    lds_barrier();
+    const uint32_t i0 = (2 * t) << l, i1 = i0 + (1u << l);
+    if (i1 >= m) continue;
+    const bool d0 = listed[i0] != 0, d1 = listed[i1] != 0;
+    if (!d0 && !d1) continue;
+    const uint32_t end = i0 + (2u << l), size = (end < m ? end : m) - i0;
+    ranges_pair<true>(cv, flags, nullptr, i0, i1, d0, d1, l, sl + set_block_node_at<B>(row, s, i0, size), 4u | (sole && (2u << l) >= m ? 8u : 0u), 1ull << l,
+                      size - (1u << l), 1, nullptr);
+    listed[i0] = 1;
+  }
+  lds_barrier();
+  if (t == 0) {                                            // slot 0: what the block's stored root node hashes to, or the CV of a block of one chunk
+    const uint32_t *want = up.depth ? reinterpret_cast<const uint32_t *>(sl + row->up[up.depth - 1] + (up.last_left ? 0 : 32)) : root;
+    if (!eq8(cv, want)) flags[0] |= m == 1 ? VER_UNIT : VER_TOP;
+  }
+  lds_barrier();
+  const uint2 hd = *reinterpret_cast<const uint2 *>(sl);
+  const bool hdr = ((uint64_t)hd.x | ((uint64_t)hd.y << 32)) != r.len;
+  uint32_t st = 0;
+  if (mine) {
+    st = hdr ? 3u : above || path_bad(flags, t) ? 2u : (flags[t] & VER_UNIT) ? 1u : 0u;
+    if (st) { atomicMax(&worst, st); atomicMin(&first, t); }          // (LDS; a clean row issues none)
+    if (chunk_status) chunk_status[r.chunk_first + row->rank0 + w.rank] = (int32_t)st;
+  }
+  const bool ok = mine && st == 0;
+  __syncthreads();
+  listed[t] = ok ? 1u : 0u;                                // from here on: a verified chunk (below this slot)
+  __syncthreads();
+  if (t == 0) results[blockIdx.x] = make_uint4(worst, 0, first == ~0u ? ~0u : (uint32_t)(a0 + first), first == ~0u ? ~0u : (uint32_t)((a0 + first) >> 32));
+  // 2. the places: nothing unverified is written
+  uint8_t *__restrict__ data = arena + r.off, *__restrict__ ob = obs + r.ob;
+  for (uint32_t p = t; p < w.cnt * 64; p += B) {
+    const uint32_t ch = s.lane_of[p >> 6], q = (p & 63) * 16;
+    if (!listed[ch]) continue;
+    const uint64_t c = a0 + ch;
+    const uint32_t bytes = range_chunk_bytes(r.len, c);
+    const uint8_t *src = sl + row->place0 + s.rel[ch];
+    uint8_t *dst = data + c * 1024;
+    if (q + 16 <= bytes) put16(dst + q, src + q);
+    else for (uint32_t o = q; o < bytes; ++o) dst[o] = src[o];
+  }
+  for (uint32_t l = 0; (1u << l) < m; ++l) {               // the stored nodes with a verified chunk below them
+    lds_barrier();
+    const uint32_t i0 = (2 * t) << l, i1 = i0 + (1u << l);
+    if (i1 >= m || !(listed[i0] | listed[i1])) continue;
+    const uint32_t end = i0 + (2u << l), size = (end < m ? end : m) - i0;
+    uint8_t *node = node_at<true>(ob + 8, n, a0 + i0, size, gl);
+    if (node) copy_node(node, sl + set_block_node_at<B>(row, s, i0, size));
+    listed[i0] = 1;
+  }
+  lds_barrier();
+  if (listed[0]) {                                         // (every row with a verified chunk stores the nodes above it: the same verified bytes)
+    if (t < up.depth) {
+      uint8_t *node = node_at<true>(ob + 8, n, up.lo, up.cnt, gl);
+      if (node) copy_node(node, sl + row->up[t]);
+    }
+    if (t == 0) *reinterpret_cast<uint2 *>(ob) = hd;       // the header (it is the length: just checked)
+  }
+  if (have) {                                              // a wave's lanes are the chunks of one word (a block starts at a multiple of 64)
+    const unsigned long long mask = __ballot(ok);
+    if ((t & 63) == 0 && mask) atomicOr(have + r.have + ((a0 + t) >> 6), mask);
+  }
+}
+
+// a wave per set: b3w_bao_range_reduce_kernel's body over the set's rows
+__global__ __launch_bounds__(256) void b3w_bao_set_reduce_kernel(const SetDev *__restrict__ sets, uint32_t n_sets, const uint4 *__restrict__ results,
+                                                                 int32_t *__restrict__ set_status, unsigned long long *__restrict__ set_first_bad) {
+  const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (i >= n_sets) return;
+  const uint32_t n_rows = sets[i].n_rows;
+  const uint4 *__restrict__ res = results + sets[i].row0;
+  uint32_t w = 0;
+  unsigned long long f = ~0ull;
+  for (uint32_t j = lane; j < n_rows; j += 64) {
+    const uint4 v = res[j];
+    const unsigned long long at = (unsigned long long)v.z | ((unsigned long long)v.w << 32);
+    w = w > v.x ? w : v.x;
+    f = f < at ? f : at;
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d /= 2) {
+    const uint32_t ow = __shfl_xor(w, d);
+    const unsigned long long of = __shfl_xor(f, d);
+    w = w > ow ? w : ow;
+    f = f < of ? f : of;
+  }
+  if (lane == 0) { set_status[i] = (int32_t)w; set_first_bad[i] = f; }
+}
+
+// what both set calls refuse about the list and the arena; the sets, their rows and the slices' places
+int32_t set_list_ok(b3w_ctx *ctx, const char *what, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
+                    uint32_t n_files, const uint32_t *host_files, const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, SetList &list) {
+  if (!b3w_int_set_list(host_lens, n_files, host_files, host_first, host_count, n_ranges, list)) return refuse(ctx, what, list.why);
+  for (const SetEnt &e : list.sets) {
+    const uint64_t len = host_lens[e.file], off = host_offsets[e.file];
+    const char *why = nullptr;
+    if (num_chunks(len) > (1ull << 30)) why = "its file has more than 2^30 chunks";
+    else if (len && !d_arena) why = "a null arena with a file that is not empty";
+    else if (off > arena_bytes || len > arena_bytes - off) why = "its file reaches past arena_bytes";
+    if (why) return refuse(ctx, what, "range " + std::to_string(e.range_first) + ": " + why);
+  }
+  if (list.big > 0x7fffffffull || list.small > 0x7fffffffull) return refuse(ctx, what, "more than 2^31 - 1 rows of one kind");
+  return B3W_OK;
+}
+
+// one row of the table: its block's mask from the runs [i0, i1) of the set that touch it, the place and rank of its first wanted chunk,
+// the places of the nodes above the block.  ufirst[] / rank[]: SetRuns' state at every run of the set
+template <int B>
+bool set_make_row(SetRow<B> &row, uint32_t set, uint64_t blk, uint64_t len, const uint64_t *first, const uint64_t *count, uint64_t k,
+                  const uint64_t *ufirst, const uint64_t *rank) {
+  const uint64_t n = num_chunks(len), a0 = blk * B, m = n - a0 < B ? n - a0 : B;
+  memset(&row, 0, sizeof row);
+  row.set = set; row.block = (uint32_t)blk;
+  auto place = [&](uint64_t i, uint64_t c) { return 8 + 64 * set_nodes(n, ufirst[i], first[i], c) + 1024 * (rank[i] + (c - first[i])); };
+  uint64_t i = set_run_behind(first, count, k, a0);       // the first run that reaches into the block
+  const uint64_t cf = first[i] > a0 ? first[i] : a0;
+  row.place0 = place(i, cf);
+  row.rank0 = rank[i] + (cf - first[i]);
+  for (; i < k && first[i] < a0 + m; ++i) {
+    const uint64_t lo = (first[i] > a0 ? first[i] : a0) - a0, hi = (first[i] + count[i] < a0 + m ? first[i] + count[i] : a0 + m) - a0;
+    for (uint64_t wd = lo >> 5; wd <= (hi - 1) >> 5; ++wd) {
+      const uint32_t from = wd == lo >> 5 ? (uint32_t)lo & 31 : 0, to = wd == (hi - 1) >> 5 ? (uint32_t)((hi - 1) & 31) + 1 : 32;
+      row.mask[wd] |= (to == 32 ? ~0u : (1u << to) - 1) & ~((1u << from) - 1);
+    }
+  }
+  uint64_t lo = 0, cnt = n;
+  for (uint32_t j = 0; cnt > 1 && !(lo == a0 && cnt == m); ++j) {
+    if (j == SET_UP) return false;                         // (never with at most 2^30 chunks: the kernels read up[] as far as the block lies deep)
+    const uint64_t r = set_run_behind(first, count, k, lo), c0 = first[r] > lo ? first[r] : lo;
+    row.up[j] = place(r, c0) - 64ull * depth_in(c0 - lo, cnt);
+    const uint64_t half = left_of(cnt);
+    if (a0 < lo + half) cnt = half; else { lo += half; cnt -= half; }
+  }
+  return true;
+}
+
+// the table into the staging and on its way: the sets' entries, the rows of 1 024 chunks, the rows of 64
+int32_t set_table(b3w_ctx *ctx, const uint64_t *host_offsets, const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint64_t *host_first,
+                  const uint64_t *host_count, const SetList &list, hipStream_t st, const SetDev *&d_sets, const SetRow<(int)B3W_TILE> *&d_big,
+                  const SetRow<64> *&d_small) {
+  using Big = SetRow<(int)B3W_TILE>;
+  using Small = SetRow<64>;
+  const uint64_t n_sets = list.sets.size();
+  const uint64_t up_bytes = n_sets * sizeof(SetDev) + list.big * sizeof(Big) + list.small * sizeof(Small);
+  B3W_TRY(batch_staging(ctx, up_bytes + 2 * ((uint64_t)n_files + 1) * 8));
+  SetDev *sd = reinterpret_cast<SetDev *>(ctx->h_batch);
+  Big *big = reinterpret_cast<Big *>(sd + n_sets);
+  Small *small = reinterpret_cast<Small *>(big + list.big);
+  uint64_t *ob_first = reinterpret_cast<uint64_t *>(small + list.small), *word_first = ob_first + n_files + 1;
+  (void)b3w_bao_group_batch_layout(host_lens, n_files, group_log, ob_first);
+  (void)b3w_bao_have_layout(host_lens, n_files, word_first);
+  uint64_t nb = 0, ns = 0;
+  for (uint64_t s = 0; s < n_sets; ++s) {
+    const SetEnt &e = list.sets[s];
+    const uint64_t len = host_lens[e.file], k = e.range_end - e.range_first;
+    const uint64_t *first = host_first + e.range_first, *count = host_count + e.range_first;
+    sd[s] = SetDev{len, host_offsets[e.file], ob_first[e.file], e.slice, word_first[e.file], e.chunk_first, e.file,
+                   (uint32_t)(e.shrt ? list.big + ns : nb), (uint32_t)e.rows, 0};
+    const uint64_t *ufirst = list.ufirst.data() + e.range_first, *rank = list.rank.data() + e.range_first;
+    const uint64_t B = e.shrt ? 64 : B3W_TILE;
+    uint64_t last = ~0ull, made = 0;
+    for (uint64_t i = 0; i < k; ++i)
+      for (uint64_t blk = first[i] / B; blk <= (first[i] + count[i] - 1) / B; ++blk) {
+        if (blk == last) continue;
+        last = blk;
+        if (made++ == e.rows) return refuse(ctx, "bao set slice table", "the rows do not add up");   // (never: b3w_int_set_list counted them)
+        if (!(e.shrt ? set_make_row<64>(small[ns++], (uint32_t)s, blk, len, first, count, k, ufirst, rank)
+                     : set_make_row<(int)B3W_TILE>(big[nb++], (uint32_t)s, blk, len, first, count, k, ufirst, rank)))
+          return refuse(ctx, "bao set slice table", "a block lies deeper than the table's places");
+      }
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)up_bytes, hipMemcpyHostToDevice, st));
+  d_sets = reinterpret_cast<const SetDev *>(ctx->d_batch);
+  d_big = reinterpret_cast<const Big *>(d_sets + n_sets);
+  d_small = reinterpret_cast<const Small *>(d_big + list.big);
+  return B3W_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t b3w_bao_set_slice_arena_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
+                                       uint32_t n_files, uint32_t group_log, const uint8_t *d_outboards, const uint32_t *host_files,
+                                       const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, uint8_t *d_slices, void *stream) {
+  const char *call = "bao set slice arena";
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  B3W_TRY(group_log_ok(ctx, call, group_log));
+  if (!n_ranges) return B3W_OK;
+  if (!host_offsets || !host_lens || !d_outboards || !host_files || !host_first || !host_count || !d_slices) return refuse(ctx, call, "a null pointer");
+  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) return refuse(ctx, call, "d_outboards is not 8-byte or d_slices not 16-byte aligned");
+  SetList list;
+  B3W_TRY(set_list_ok(ctx, call, d_arena, arena_bytes, host_offsets, host_lens, n_files, host_files, host_first, host_count, n_ranges, list));
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  const SetDev *d_sets = nullptr;
+  const SetRow<(int)B3W_TILE> *d_big = nullptr;
+  const SetRow<64> *d_small = nullptr;
+  B3W_TRY(set_table(ctx, host_offsets, host_lens, n_files, group_log, host_first, host_count, list, st, d_sets, d_big, d_small));
+  if (list.big) hipLaunchKernelGGL(b3w_bao_set_slice_kernel<(int)B3W_TILE>, dim3((uint32_t)list.big), dim3(B3W_TILE), 0, st, d_sets, d_big, group_log, d_arena, d_outboards, d_slices);
+  if (list.small) hipLaunchKernelGGL(b3w_bao_set_slice_kernel<64>, dim3((uint32_t)list.small), dim3(64), 0, st, d_sets, d_small, group_log, d_arena, d_outboards, d_slices);
+  return batch_launched(ctx, st, "bao set slice arena launch");
+}
+
+int32_t b3w_bao_set_slice_ingest_device(b3w_ctx *ctx, uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
+                                        uint32_t n_files, uint32_t group_log, uint8_t *d_outboards, const uint32_t *d_roots, const uint32_t *host_files,
+                                        const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, const uint8_t *d_slices,
+                                        int32_t *d_set_status, uint64_t *d_set_first_bad, int32_t *d_chunk_status, uint64_t *d_have, void *d_scratch,
+                                        uint64_t scratch_bytes, void *stream) {
+  const char *call = "bao set slice ingest";
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  B3W_TRY(group_log_ok(ctx, call, group_log));
+  if (((uintptr_t)d_have & 7) || ((uintptr_t)d_chunk_status & 3)) return refuse(ctx, call, "d_have is not 8-byte or d_chunk_status not 4-byte aligned");
+  if (!n_ranges) return B3W_OK;
+  if (!host_offsets || !host_lens || !d_outboards || !d_roots || !host_files || !host_first || !host_count || !d_slices || !d_set_status || !d_set_first_bad) return refuse(ctx, call, "a null pointer");
+  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) return refuse(ctx, call, "d_outboards is not 8-byte or d_slices not 16-byte aligned");
+  if (((uintptr_t)d_set_status & 3) || ((uintptr_t)d_set_first_bad & 7)) return refuse(ctx, call, "d_set_status is not 4-byte or d_set_first_bad not 8-byte aligned");
+  SetList list;
+  B3W_TRY(set_list_ok(ctx, call, d_arena, arena_bytes, host_offsets, host_lens, n_files, host_files, host_first, host_count, n_ranges, list));
+  if (scratch_bytes < (list.big + list.small) * 16) return refuse(ctx, call, "the scratch is smaller than b3w_bao_set_slice_ingest_scratch_bytes says");
+  if (!d_scratch || ((uintptr_t)d_scratch & 15)) return refuse(ctx, call, "the scratch is null or not 16-byte aligned");
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  const SetDev *d_sets = nullptr;
+  const SetRow<(int)B3W_TILE> *d_big = nullptr;
+  const SetRow<64> *d_small = nullptr;
+  B3W_TRY(set_table(ctx, host_offsets, host_lens, n_files, group_log, host_first, host_count, list, st, d_sets, d_big, d_small));
+  uint4 *res = reinterpret_cast<uint4 *>(d_scratch);
+  unsigned long long *have = reinterpret_cast<unsigned long long *>(d_have);
+  const uint32_t n_sets = (uint32_t)list.sets.size();
+  if (list.big)
+    hipLaunchKernelGGL(b3w_bao_set_ingest_kernel<(int)B3W_TILE>, dim3((uint32_t)list.big), dim3(B3W_TILE), 0, st, d_sets, d_big, group_log, d_slices, d_roots, d_arena,
+                       d_outboards, d_chunk_status, have, res);
+  if (list.small)
+    hipLaunchKernelGGL(b3w_bao_set_ingest_kernel<64>, dim3((uint32_t)list.small), dim3(64), 0, st, d_sets, d_small, group_log, d_slices, d_roots, d_arena, d_outboards,
+                       d_chunk_status, have, res + list.big);
+  hipLaunchKernelGGL(b3w_bao_set_reduce_kernel, dim3((n_sets + 3) / 4), dim3(256), 0, st, d_sets, n_sets, res, d_set_status,
+                     reinterpret_cast<unsigned long long *>(d_set_first_bad));
+  return batch_launched(ctx, st, "bao set slice ingest launch");
+}
+
+}  // extern "C"

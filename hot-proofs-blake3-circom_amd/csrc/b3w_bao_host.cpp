@@ -1,6 +1,6 @@
 // b3w_bao_host.cpp — the bao calls of include/b3wit.h that never touch a device: the sizes and layouts, and the host mirrors that
 // extract, decode and take in slices (UNTRUSTED input), verify, update and resize one file node by node.  Plain C++, no kernel and no
-// HIP runtime call: tools/bao_range_host_check.cpp, tools/bao_have_host_check.cpp and tools/bao_packed_host_check.cpp compile this file
+// HIP runtime call: tools/bao_range_host_check.cpp, bao_set_host_check.cpp, bao_have_host_check.cpp and bao_packed_host_check.cpp compile this file
 // alone with AddressSanitizer + UBSan.  The formats are described where the kernels are (b3w_bao.hip, b3w_bao_have.hip); the arithmetic both sides share is
 // b3w_bao_tree.h.  The device entry points stay in the .hip files, and b3w_sample_rows* beside them (they need b3w_plan_path_len).
 #include "b3w_bao_plan.h"
@@ -193,6 +193,81 @@ int32_t range_decode_run(const uint8_t *slice, uint64_t slice_len, uint64_t len,
   return B3W_OK;
 }
 
+// ---- set slices: one file's runs, node by node (the range walks with "meets S" for "meets the range") ------------------------------------
+struct SetEnc { const uint8_t *ob, *data; uint64_t len, n; const uint64_t *first, *count; uint64_t k; uint32_t gl; uint8_t *out; uint64_t at; };
+void set_encode(SetEnc &w, uint64_t lo, uint64_t size) {
+  if (size == 1) {
+    const uint64_t bytes = chunk_bytes(w.len, lo);
+    if (bytes) memcpy(w.out + w.at, w.data + lo * 1024, bytes);
+    w.at += bytes;
+    return;
+  }
+  const uint64_t k = left_of(size), G = 1ull << w.gl;
+  if (size > G) memcpy(w.out + w.at, w.ob + 8 + 64 * preorder_pos((w.n + G - 1) >> w.gl, lo >> w.gl, (size + G - 1) >> w.gl), 64);
+  else {                                                  // inside a group: from the group's bytes
+    uint32_t m[16];
+    host_subtree_cv(w.data, 0, w.len, lo, k, false, m);
+    host_subtree_cv(w.data, 0, w.len, lo + k, size - k, false, m + 8);
+    put_words(w.out + w.at, m, 16);
+  }
+  w.at += 64;
+  if (set_meets(w.first, w.count, w.k, lo, lo + k)) set_encode(w, lo, k);
+  if (set_meets(w.first, w.count, w.k, lo + k, lo + size)) set_encode(w, lo + k, size - k);
+}
+
+// the decoder's walk; chunks come in ascending order, so a chunk's rank is a running count
+struct SetDec {
+  const uint8_t *sl; uint64_t len, n; const uint64_t *first, *count; uint64_t k, at, rank; bool hdr; uint32_t gl;
+  uint8_t *out_bytes, *data, *ob; uint64_t *have; int32_t *chunk_status;
+  int32_t worst; uint64_t first_bad;
+};
+bool set_decode(SetDec &w, uint64_t lo, uint64_t size, const uint32_t want[8], bool bad_above, bool root) {
+  if (size == 1) {
+    const uint64_t bytes = chunk_bytes(w.len, lo), rank = w.rank++;
+    const uint8_t *src = w.sl + w.at;
+    w.at += bytes;
+    uint32_t h[8];
+    host_chunk_cv(src, (uint32_t)bytes, lo, root ? 8u : 0u, h);
+    const int32_t st = w.hdr ? 3 : bad_above ? 2 : memcmp(h, want, 32) != 0 ? 1 : 0;
+    if (w.chunk_status) w.chunk_status[rank] = st;
+    if (st) {
+      if (st > w.worst) w.worst = st;
+      if (lo < w.first_bad) w.first_bad = lo;
+      return false;
+    }
+    if (bytes && w.out_bytes) memcpy(w.out_bytes + rank * 1024, src, bytes);
+    if (bytes && w.data) memcpy(w.data + lo * 1024, src, bytes);
+    if (w.have) w.have[lo >> 6] |= 1ull << (lo & 63);
+    return true;
+  }
+  const uint8_t *node = w.sl + w.at;
+  w.at += 64;
+  uint32_t mw[16], o[8];
+  load_node(node, mw);
+  parent_cv(mw, root, o);
+  const bool bad = bad_above || memcmp(o, want, 32) != 0;
+  const uint64_t k = left_of(size), G = 1ull << w.gl;
+  bool any = false;
+  if (set_meets(w.first, w.count, w.k, lo, lo + k)) any |= set_decode(w, lo, k, mw, bad, false);
+  if (set_meets(w.first, w.count, w.k, lo + k, lo + size)) any |= set_decode(w, lo + k, size - k, mw + 8, bad, false);
+  if (any && w.ob && size > G) memcpy(w.ob + 8 + 64 * preorder_pos((w.n + G - 1) >> w.gl, lo >> w.gl, (size + G - 1) >> w.gl), node, 64);
+  return any;
+}
+
+int32_t set_decode_run(const uint8_t *slice, uint64_t slice_len, uint64_t len, const uint64_t *first, const uint64_t *count, uint32_t n_ranges,
+                       const uint32_t *root, SetDec &w) {
+  const uint64_t n = num_chunks(len);
+  uint64_t bad;
+  if (!slice || !root || !n_ranges || !first || !count || set_runs_wrong(n, first, count, n_ranges, &bad) ||
+      slice_len != set_slice_bytes(len, first, count, n_ranges))
+    return B3W_E_BAD_ARGUMENT;
+  w.sl = slice; w.len = len; w.n = n; w.first = first; w.count = count; w.k = n_ranges; w.at = 8; w.rank = 0; w.hdr = read_header(slice) != len;
+  w.worst = 0; w.first_bad = ~0ull;
+  const bool any = set_decode(w, 0, n, root, false, true);
+  if (any && w.ob) memcpy(w.ob, slice, 8);
+  return B3W_OK;
+}
+
 }  // namespace
 
 std::vector<UpdRange> b3w_int_update_ranges(const uint64_t *lens, const uint32_t *files, const uint64_t *first, const uint64_t *count, uint32_t n_ranges) {
@@ -255,6 +330,47 @@ UpdPlan b3w_int_update_plan(const uint64_t *lens, const std::vector<UpdRange> &r
     }
   }
   return p;
+}
+
+bool b3w_int_set_list(const uint64_t *lens, uint32_t n_files, const uint32_t *files, const uint64_t *first, const uint64_t *count, uint32_t n_ranges,
+                      SetList &out) {
+  out = SetList{};
+  out.ufirst.resize(n_ranges);
+  out.rank.resize(n_ranges);
+  uint64_t at = slice_start(0);
+  for (uint32_t i = 0; i < n_ranges;) {
+    const uint32_t f = files[i];
+    const char *why = nullptr;
+    uint64_t bad = 0;
+    uint32_t e = i;
+    if (f >= n_files) why = "its file index is not below the file count";
+    else {
+      if (i && f < files[i - 1]) why = "the list is not ascending by (file, first chunk)";
+      while (e < n_ranges && files[e] == f) ++e;
+      if (!why) why = set_runs_wrong(num_chunks(lens[f]), first + i, count + i, e - i, &bad);
+    }
+    if (why) { out.why = "range " + std::to_string(i + bad) + ": " + why; return false; }
+    SetEnt s{};
+    s.file = f; s.range_first = i; s.range_end = e; s.chunk_first = out.chunks; s.slice = at;
+    const uint64_t c0 = first[i], c1 = first[e - 1] + count[e - 1] - 1;
+    s.shrt = set_is_short(c0, c1);
+    if (s.shrt) s.rows = c1 / 64 - c0 / 64 + 1;
+    else {
+      uint64_t last = ~0ull;                               // the touched tiles: the runs ascend
+      for (uint32_t r = i; r < e; ++r) {
+        const uint64_t t0 = first[r] / B3W_TILE, t1 = (first[r] + count[r] - 1) / B3W_TILE;
+        s.rows += t1 - t0 + (t0 == last ? 0 : 1);
+        last = t1;
+      }
+    }
+    for (uint32_t r = i; r < e; ++r) out.chunks += count[r];
+    (s.shrt ? out.small : out.big) += s.rows;
+    at = slice_start(at + set_slice_bytes(lens[f], first + i, count + i, e - i, out.ufirst.data() + i, out.rank.data() + i));
+    out.sets.push_back(s);
+    i = e;
+  }
+  out.bytes = at;
+  return true;
 }
 
 void b3w_int_packed_range(uint64_t len, uint32_t gl, uint64_t a, uint64_t c, uint64_t *first, uint64_t *count) {
@@ -660,6 +776,79 @@ int32_t b3w_bao_range_slice_ingest(const uint8_t *slice, uint64_t slice_len, uin
   RangeDec w{};
   w.gl = group_log; w.data = data; w.ob = outboard; w.have = have;
   const int32_t rc = range_decode_run(slice, slice_len, len, first_chunk, n_chunks, root, w);
+  if (rc) return rc;
+  *out_status = w.worst;
+  if (out_first_bad) *out_first_bad = w.first_bad;
+  return B3W_OK;
+}
+
+// ---- set slices -----------------------------------------------------------------------------------------------------------------------
+uint64_t b3w_bao_set_slice_size(uint64_t len, const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges) {
+  uint64_t bad;
+  if (!n_ranges || !host_first || !host_count || set_runs_wrong(num_chunks(len), host_first, host_count, n_ranges, &bad)) return 0;
+  return set_slice_bytes(len, host_first, host_count, n_ranges);
+}
+
+int64_t b3w_bao_set_slice_batch_layout(const uint64_t *host_lens, uint32_t n_files, const uint32_t *host_files, const uint64_t *host_first,
+                                       const uint64_t *host_count, uint32_t n_ranges, uint32_t *set_file, uint32_t *set_range_first,
+                                       uint64_t *set_chunk_first, uint64_t *slice_first, uint32_t *n_sets) {
+  if (n_ranges && (!host_lens || !host_files || !host_first || !host_count)) return -B3W_E_BAD_ARGUMENT;
+  SetList l;
+  if (!b3w_int_set_list(host_lens, n_files, host_files, host_first, host_count, n_ranges, l)) return -B3W_E_BAD_ARGUMENT;
+  const size_t k = l.sets.size();
+  for (size_t s = 0; s < k; ++s) {
+    if (set_file) set_file[s] = l.sets[s].file;
+    if (set_range_first) set_range_first[s] = l.sets[s].range_first;
+    if (set_chunk_first) set_chunk_first[s] = l.sets[s].chunk_first;
+    if (slice_first) slice_first[s] = l.sets[s].slice;
+  }
+  if (set_range_first) set_range_first[k] = n_ranges;
+  if (set_chunk_first) set_chunk_first[k] = l.chunks;
+  if (slice_first) slice_first[k] = l.bytes;
+  if (n_sets) *n_sets = (uint32_t)k;
+  return (int64_t)l.bytes;
+}
+
+uint64_t b3w_bao_set_slice_ingest_scratch_bytes(const uint64_t *host_lens, uint32_t n_files, const uint32_t *host_files, const uint64_t *host_first,
+                                                const uint64_t *host_count, uint32_t n_ranges) {
+  if (!host_lens || !host_files || !host_first || !host_count) return 0;
+  SetList l;
+  if (!b3w_int_set_list(host_lens, n_files, host_files, host_first, host_count, n_ranges, l)) return 0;
+  return (l.big + l.small) * 16;                          // a row's status and first bad chunk
+}
+
+int64_t b3w_bao_set_slice(const uint8_t *outboard, uint64_t len, uint32_t group_log, const uint64_t *host_first, const uint64_t *host_count,
+                          uint32_t n_ranges, const uint8_t *data, uint8_t *out, uint64_t out_len) {
+  const uint64_t size = b3w_bao_set_slice_size(len, host_first, host_count, n_ranges);
+  if (!size || group_log > B3W_BAO_MAX_GROUP_LOG) return -B3W_E_BAD_ARGUMENT;
+  if (!out) return (int64_t)size;
+  if (!outboard || (!data && len) || out_len < size) return -B3W_E_BAD_ARGUMENT;
+  memcpy(out, outboard, 8);
+  SetEnc w{outboard, data, len, num_chunks(len), host_first, host_count, n_ranges, group_log, out, 8};
+  set_encode(w, 0, w.n);
+  return (int64_t)w.at;
+}
+
+int32_t b3w_bao_set_slice_decode(const uint8_t *slice, uint64_t slice_len, uint64_t len, const uint64_t *host_first, const uint64_t *host_count,
+                                 uint32_t n_ranges, const uint32_t *root, uint8_t *out_bytes, int32_t *chunk_status, int32_t *out_status,
+                                 uint64_t *out_first_bad) {
+  if (!out_status) return B3W_E_BAD_ARGUMENT;
+  SetDec w{};
+  w.out_bytes = out_bytes; w.chunk_status = chunk_status;
+  const int32_t rc = set_decode_run(slice, slice_len, len, host_first, host_count, n_ranges, root, w);
+  if (rc) return rc;
+  *out_status = w.worst;
+  if (out_first_bad) *out_first_bad = w.first_bad;
+  return B3W_OK;
+}
+
+int32_t b3w_bao_set_slice_ingest(const uint8_t *slice, uint64_t slice_len, uint64_t len, const uint64_t *host_first, const uint64_t *host_count,
+                                 uint32_t n_ranges, const uint32_t *root, uint32_t group_log, uint8_t *data, uint8_t *outboard, uint64_t *have,
+                                 int32_t *chunk_status, int32_t *out_status, uint64_t *out_first_bad) {
+  if (group_log > B3W_BAO_MAX_GROUP_LOG || !outboard || (!data && len) || !out_status) return B3W_E_BAD_ARGUMENT;
+  SetDec w{};
+  w.gl = group_log; w.data = data; w.ob = outboard; w.have = have; w.chunk_status = chunk_status;
+  const int32_t rc = set_decode_run(slice, slice_len, len, host_first, host_count, n_ranges, root, w);
   if (rc) return rc;
   *out_status = w.worst;
   if (out_first_bad) *out_first_bad = w.first_bad;

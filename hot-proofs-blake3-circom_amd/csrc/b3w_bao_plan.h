@@ -2,6 +2,7 @@
 // use it; the device entry points of b3w_bao.hip build their tables from it, and their packed twins find their chunks' slots with the
 // packed layout below.  Not installed.
 #pragma once
+#include <string>
 #include <vector>
 
 #include "b3w_bao_tree.h"
@@ -18,6 +19,20 @@ struct UpdPlan {
 std::vector<UpdRange> b3w_int_update_ranges(const uint64_t *lens, const uint32_t *files, const uint64_t *first, const uint64_t *count, uint32_t n_ranges);
 // what a call over these (sorted, merged) ranges launches; the chunk masks are expanded to whole groups of 1 << gl chunks
 UpdPlan b3w_int_update_plan(const uint64_t *lens, const std::vector<UpdRange> &ranges, uint32_t gl);
+
+// The sets of a set-slice call (b3wit.h "set slices"): a set is the maximal stretch of consecutive ranges of one file; its rows are one
+// or two blocks of 64 chunks (shrt) or its touched tiles.
+struct SetEnt { uint32_t file, range_first, range_end; uint64_t chunk_first, slice, rows; bool shrt; };
+struct SetList {
+  std::vector<SetEnt> sets;
+  std::vector<uint64_t> ufirst, rank;                                 // a range: U_S of its first chunk, the set's wanted chunks in front of it (SetRuns)
+  uint64_t big = 0, small = 0, chunks = 0, bytes = 0;                  // rows of 1 024 and of 64 chunks; the wanted chunks; the packed slices' bytes
+  std::string why;                                                    // a refusal: "range i: ..."
+};
+// false for a list the set calls refuse (why names the range): a file index >= n_files, an empty range or one past its file, a list
+// that is not ascending by (file, first chunk) or not disjoint
+bool b3w_int_set_list(const uint64_t *lens, uint32_t n_files, const uint32_t *files, const uint64_t *first, const uint64_t *count, uint32_t n_ranges,
+                      SetList &out);
 
 // The packed layout (b3wit.h "sparse calls from packed chunk bytes"): the chunks b3w_int_update_plan has hashed, as runs of consecutive
 // chunks of one file in consecutive slots of 1 024 bytes, sorted by (file, first chunk); no two runs of a file touch.

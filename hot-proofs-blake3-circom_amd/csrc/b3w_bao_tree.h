@@ -101,6 +101,76 @@ inline uint64_t range_rows(uint64_t a, uint64_t k) {
   return (a + k - 1) / B - a / B + 1;
 }
 
+// ---- set slices: one slice for the union S of a file's ascending, disjoint runs (the format: b3wit.h "set slices") -------------------
+// The nodes a chunk adds to the slice are those of its path that do not hold the wanted chunk p before it: the path below the node where
+// the two part.  j = the highest bit in which p < a differ: a's side of that node is the aligned 2^j chunks from s = (a >> j) << j, cut
+// off at n, and a's path inside it has j nodes where it is whole.  O(1) but for the cut-off subtrees on the file's right edge.
+inline uint32_t new_nodes(uint64_t n, uint64_t p, uint64_t a) {
+  const uint32_t j = 63 - (uint32_t)__builtin_clzll(p ^ a);
+  const uint64_t s = (a >> j) << j;
+  return s + (1ull << j) <= n ? j : depth_in(a - s, n - s);
+}
+// what the chunks a + 1 .. a + k - 1 of a run add: U(a, a + k - 1) - depth(a).  Chunk c adds ctz(c) nodes behind c - 1 wherever its
+// aligned 2^ctz(c) chunks are whole - everywhere in front of the largest power of two at or below n - and the sum of ctz over (a, p] is
+// (p - popcount p) - (a - popcount a); a run that reaches further takes the walk.
+inline uint64_t run_inner(uint64_t n, uint64_t a, uint64_t k) {
+  if (k == 1) return 0;
+  const uint64_t p = a + k - 1;
+  if (p < (1ull << (63 - __builtin_clzll(n)))) return (p - (uint64_t)__builtin_popcountll(p)) - (a - (uint64_t)__builtin_popcountll(a));
+  return range_nodes(n, a, p) - depth_in(a, n);
+}
+// SetRuns walks one file's runs in order: ufirst = U_S of the run's first chunk, rank = the wanted chunks in front of the run, so
+//   U_S(c) = ufirst + run_inner(a, c - a + 1) for c in the run from a;   the next run's ufirst = U_S(p) + new_nodes(p, its first chunk).
+// No step a chunk, and O(1) a run away from the file's ragged right edge.
+inline uint64_t set_nodes(uint64_t n, uint64_t ufirst, uint64_t a, uint64_t c) { return ufirst + run_inner(n, a, c - a + 1); }
+struct SetRuns {
+  uint64_t n, ufirst, rank = 0;
+  SetRuns(uint64_t n_, uint64_t a0) : n(n_), ufirst(depth_in(a0, n_)) {}
+  void next(uint64_t a, uint64_t k, uint64_t a_next) {
+    ufirst += run_inner(n, a, k) + new_nodes(n, a + k - 1, a_next);
+    rank += k;
+  }
+};
+// is (first, count)[0 .. k) the list of one file of n chunks: no empty run, none past the file, ascending and disjoint (touching allowed)?
+// -> null, or what is wrong with run *bad
+inline const char *set_runs_wrong(uint64_t n, const uint64_t *first, const uint64_t *count, uint64_t k, uint64_t *bad) {
+  for (uint64_t i = 0; i < k; ++i) {
+    *bad = i;
+    if (count[i] == 0) return "it has no chunk";
+    if (first[i] >= n || count[i] > n - first[i]) return "it reaches past its file's chunk count";
+    if (i && first[i] < first[i - 1] + count[i - 1]) return first[i] < first[i - 1] ? "the list is not ascending by (file, first chunk)" : "it overlaps the range before it: the list is not disjoint";
+  }
+  return nullptr;
+}
+// the bytes of the set slice of these (valid) runs of a file of len bytes; ufirst / rank (may be null): SetRuns' state at every run
+inline uint64_t set_slice_bytes(uint64_t len, const uint64_t *first, const uint64_t *count, uint64_t k, uint64_t *ufirst = nullptr, uint64_t *rank = nullptr) {
+  const uint64_t n = num_chunks(len);
+  SetRuns w(n, first[0]);
+  for (uint64_t i = 0;; ++i) {
+    if (ufirst) { ufirst[i] = w.ufirst; rank[i] = w.rank; }
+    if (i + 1 == k) break;
+    w.next(first[i], count[i], first[i + 1]);
+  }
+  const uint64_t a = first[k - 1], e = a + count[k - 1], chunks = w.rank + count[k - 1];
+  return 8 + 64 * set_nodes(n, w.ufirst, a, e - 1) + 1024 * chunks - (e == n ? 1024 - chunk_bytes(len, n - 1) : 0);
+}
+// the first run of the (valid) list that ends behind chunk c, k for none; S meets [lo, hi) iff that run starts before hi
+inline uint64_t set_run_behind(const uint64_t *first, const uint64_t *count, uint64_t k, uint64_t c) {
+  uint64_t a = 0, b = k;
+  while (a < b) {
+    const uint64_t mid = (a + b) / 2;
+    if (first[mid] + count[mid] > c) b = mid; else a = mid + 1;
+  }
+  return a;
+}
+inline bool set_meets(const uint64_t *first, const uint64_t *count, uint64_t k, uint64_t lo, uint64_t hi) {
+  const uint64_t i = set_run_behind(first, count, k, lo);
+  return i < k && first[i] < hi;
+}
+// the rows of a set whose first and last wanted chunks are c0 and c1: one or two of 64 chunks where the two lie in the same or in
+// adjacent aligned 64-chunk blocks, else a row of 1 024 per touched tile (counted by the caller: it needs the runs)
+inline bool set_is_short(uint64_t c0, uint64_t c1) { return c1 / 64 - c0 / 64 <= 1; }
+
 // ---- step records of a run of chunks: where a chunk's rows start (b3w_sample_rows_ranges, the range planner's table) ------------------
 // the sum of depth_in(i, n) over the chunks i < c of a tree over n chunks, c <= n, in the manner of range_nodes: the walk follows chunk
 // c's path, and a left subtree of k = 2^j chunks that lies wholly in front of c gives k (d + 1 + j), d the nodes above it: O(depth)

@@ -1185,6 +1185,113 @@ int32_t b3w_sample_plan_range_slices_device(b3w_ctx *ctx, const uint64_t *host_l
                                             int32_t *d_range_status, uint64_t *d_range_first_bad, void *d_scratch, uint64_t scratch_bytes,
                                             void *stream);
 
+/* ---- set slices: ONE slice for all the wanted runs of a file, extracted and taken in (still ABI 1.4: new names only) -
+ * A range slice carries one run, and every run repeats its whole path down from the root: the 262 507 runs of a half-arrived 1 GiB file
+ * are 892 MB of range slices for 537 MB of payload, and a run of one or two chunks keeps one or two lanes of its wave busy.  A SET SLICE
+ * carries the union of a file's runs, every shared node once - the response to a multi-range bao request.
+ * THE RANGE LIST.  The calls take the range calls' (host_files, host_first, host_count, n_ranges) with one more condition: the ranges
+ * come ascending by (file, first chunk) and disjoint - within a file first[i] >= first[i-1] + count[i-1]; touching runs are allowed.
+ * This is what b3w_bao_have_runs_device emits.  A SET is the maximal stretch of consecutive ranges of one file, so a file appears in at
+ * most one set; sets are numbered in order of appearance; S is the union of a set's ranges.
+ * THE SET SLICE is the 8-byte little-endian length, then the tree in pre-order restricted to S: a parent node whose span meets S gives
+ * its 64 bytes, then its left subtree if that meets S, then its right one likewise; a chunk c of S gives its min(1024, len - 1024 c)
+ * bytes.  With one run it is the range slice byte for byte; with every chunk the whole-file range slice.
+ * PLACES.  U_S(c) = the parent nodes whose span meets S n [0, c]; rank_S(c) = the chunks of S below c.  Chunk c of S lies at
+ * 8 + 64 U_S(c) + 1024 rank_S(c) (only the file's last chunk is short, and nothing follows it).  A node X over [lo, lo + size) that
+ * meets S, c0 = min(S n span), lies at place(c0) - 64 (the nodes of c0's path at or below X): between X and c0 the slice holds c0's
+ * path alone.  The size is 8 + 64 U_S(max S) + the bytes of S: never more than the sum of the runs' range slices, and less whenever a
+ * file of more than one chunk has more than one run.
+ * PACKING.  Set s starts at slice_first[s], 8 modulo 16, as b3w_bao_range_slice_batch_layout does it.
+ * THE RECEIVER IS DEFINED BY PROJECTION, as the range receiver with "range" read as "set": the projection of a set slice onto one of its
+ * chunks is that chunk's one-chunk slice; chunk status = b3w_bao_slice_decode's status of the projection (3 over 2 over 1; a one-chunk
+ * file's wrong root is 1); writes = the union over the chunks of status 0 of what b3w_bao_slice_ingest writes for the projection (the
+ * chunk's bytes, the stored nodes of its path at this group_log, the header, the chunk's bit where a bitmap is given).  Nothing
+ * unverified is written; a bad node keeps out the chunks below it and no other.  Set status = the largest chunk status; set first bad =
+ * the first chunk of the file whose status is not 0, UINT64_MAX for none.  Per-chunk statuses are packed set by set: set s's wanted
+ * chunks, ascending, at [set_chunk_first[s], set_chunk_first[s + 1]). */
+/* The host calls below take files of any length; the DEVICE calls refuse a file of more than 2^30 chunks (1 TiB), whose blocks lie
+ * deeper than the 24 places a row of their table carries. */
+/* Host only.  The bytes of one file's set slice, O(ranges x depth), no step a chunk; 0 for an empty list or a refused one (an empty
+ * run, one past the file's chunk count, a list that is not ascending or not disjoint). */
+uint64_t b3w_bao_set_slice_size(uint64_t preimage_len, const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges);
+/* Host only.  The sets of a range list and where their slices lie -> the total bytes, or -B3W_E_BAD_ARGUMENT (a null list, a file
+ * index >= n_files, a list b3w_bao_set_slice_size refuses, files that do not ascend).  Every output may be NULL: set_file (room for
+ * n_ranges), set_range_first (n_ranges + 1: set s is ranges [set_range_first[s], set_range_first[s + 1])), set_chunk_first
+ * (n_ranges + 1: the running sum of the sets' wanted chunks, the index base of the per-chunk status), slice_first (n_ranges + 1),
+ * *n_sets.  Only the first *n_sets (+ 1) entries are written. */
+int64_t b3w_bao_set_slice_batch_layout(const uint64_t *host_lens, uint32_t n_files, const uint32_t *host_files, const uint64_t *host_first,
+                                       const uint64_t *host_count, uint32_t n_ranges, uint32_t *set_file, uint32_t *set_range_first,
+                                       uint64_t *set_chunk_first, uint64_t *slice_first, uint32_t *n_sets);
+/* Host only.  The set slice of one file from its outboard of this group_log and the FILE's bytes (`data`: the whole file's place; at
+ * group_log 0 only the chunks of S are read, above 0 the chunks of every group S touches, and the nodes inside those groups are
+ * recomputed).  out == NULL: -> the size.  Otherwise -> the bytes written, or -B3W_E_BAD_ARGUMENT for a refused list, a group_log
+ * above the maximum, a null pointer (data may be NULL for an empty file) or out_len below the size. */
+int64_t b3w_bao_set_slice(const uint8_t *outboard, uint64_t preimage_len, uint32_t group_log, const uint64_t *host_first,
+                          const uint64_t *host_count, uint32_t n_ranges, const uint8_t *data, uint8_t *out, uint64_t out_len);
+/* Host only.  The sequential top-down decoder.  out_bytes (may be NULL; room for 1024 |S|) gets the bytes of the chunks of status 0 at
+ * 1024 rank_S(c), the others' places are left alone; chunk_status (may be NULL) one int32 a wanted chunk, ascending; *out_first_bad may
+ * be NULL.  B3W_E_BAD_ARGUMENT for a null slice, root or out_status, a refused list, or a slice_len that is not
+ * b3w_bao_set_slice_size. */
+int32_t b3w_bao_set_slice_decode(const uint8_t *slice, uint64_t slice_len, uint64_t preimage_len, const uint64_t *host_first,
+                                 const uint64_t *host_count, uint32_t n_ranges, const uint32_t *root /* 8 u32 */, uint8_t *out_bytes,
+                                 int32_t *chunk_status, int32_t *out_status, uint64_t *out_first_bad);
+/* Host only.  The receiver for ONE file: the decoder's verdicts and the writes defined above into `data` (the file), `outboard` (its
+ * outboard of this group_log) and `have` (may be NULL; the file's bitmap from its word 0).  Refuses what the decoder refuses, a
+ * group_log above the maximum and a null outboard (data may be NULL only for an empty file). */
+int32_t b3w_bao_set_slice_ingest(const uint8_t *slice, uint64_t slice_len, uint64_t preimage_len, const uint64_t *host_first,
+                                 const uint64_t *host_count, uint32_t n_ranges, const uint32_t *root /* 8 u32 */, uint32_t group_log,
+                                 uint8_t *data, uint8_t *outboard, uint64_t *have, int32_t *chunk_status, int32_t *out_status,
+                                 uint64_t *out_first_bad);
+/* THE PROVIDER.  The set slices of the list's sets into d_slices (16-byte aligned, packed as b3w_bao_set_slice_batch_layout says); the
+ * other arguments are b3w_bao_range_slice_arena_device's.  Nothing is verified; every byte of a slice has one writer; no byte outside
+ * a set's own file is read; padding is not written.  group_log > 0: the chunks of every touched group are hashed and the nodes inside
+ * the groups come from that, as the range provider does.
+ * Both device calls: a ROW is (set, block of B aligned chunks with at least one wanted chunk).  A set whose first and last wanted
+ * chunks lie in the same or in adjacent aligned 64-chunk blocks takes one or two rows of B = 64, a wave each (every file of at most 64
+ * chunks); any other set a workgroup of 1 024 lanes per touched tile - the 262 507 runs of a half-arrived 1 GiB file are 1 024
+ * workgroups with every wanted lane busy.  The device never sees the run list: a row carries the mask of its wanted chunks.  At most
+ * TWO launches here and THREE in the receiver (the rows of each kind, and a wave per set that reduces its rows' results); no workgroup
+ * waits for another.  THE TABLE grows with sets and rows, never with ranges or chunks: 64 bytes a set, and a row of 64 chunks 224
+ * bytes, one of 1 024 chunks 344: set and block (8), the place of the row's first wanted chunk and its rank (16), the places of the
+ * D <= 24 nodes above the block in the slice (192: files of up to 2^30 chunks; a longer file is refused), the mask (8 or 128); a
+ * node above a block is moved by the row that holds the first wanted chunk below it, which the row reads off the places (the
+ * receiver stores it from every row with a verified chunk: the same verified bytes).  It goes through the context's staging
+ * and nothing else is allocated; asynchronous on `stream`; the host waits for nothing but this context's previous batch call; every
+ * byte count and place is 64 bits wide.  REFUSALS ARE ATOMIC (B3W_E_BAD_ARGUMENT before anything is launched or written;
+ * b3w_last_error names the range): what the range twins refuse, a list that is not ascending or not disjoint (named as such), a file
+ * of more than 2^30 chunks, more than 2^31 - 1 rows of one kind.  n_ranges == 0: a no-op. */
+int32_t b3w_bao_set_slice_arena_device(b3w_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets,
+                                       const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint8_t *d_outboards,
+                                       const uint32_t *host_files, const uint64_t *host_first, const uint64_t *host_count,
+                                       uint32_t n_ranges, uint8_t *d_slices, void *stream);
+/* Host only.  Bytes of scratch the receiver needs: 16 per row (0 for a null pointer or a list the layout call refuses). */
+uint64_t b3w_bao_set_slice_ingest_scratch_bytes(const uint64_t *host_lens, uint32_t n_files, const uint32_t *host_files,
+                                                const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges);
+/* THE RECEIVER, with the semantics above; b3w_bao_range_slice_ingest_device's arguments with the two outputs a SET (int32, and uint64
+ * 8-byte aligned, in set order) and d_chunk_status (may be NULL; an int32 a wanted chunk at set_chunk_first[s] + rank).  Also refused:
+ * a scratch that is too small, null or misaligned, a misaligned d_have or d_chunk_status, a null or misaligned output.
+ * WHEN NOT TO (MI355X, one 1 GiB file; the yardsticks are a build of the commit before these calls doing the same job by
+ * both existing routes, its range calls and bao.runs_chunks + its one-chunk calls; device events round whole calls; no profiler run).
+ * The 262 507 runs of a bitmap with half its chunks missing (593 MB of set slice, 892 of range slices, 1 213 of one-chunk slices): the
+ * provider 3.20 ms against 13.22 (range) and 16.18 (one-chunk), the receiver 3.70 against 20.86 and 16.85, the yardsticks' spreads
+ * below 0.23; 65 536 runs of ONE chunk: 0.78 against 3.51 and 1.73, 1.30 against 5.45 and 2.17.  FEW WANTED CHUNKS IN MANY TILES LOSE
+ * TO THE RANGE CALLS: a set takes a workgroup of 1 024 lanes per touched tile, and 4 096 runs of 16 scattered over the file keep 64
+ * lanes of each of 1 009 tiles busy - the provider 0.35 ms against the range call's 0.25, the receiver 0.78 against 0.39 (the one-chunk
+ * route 1.50 and 2.16).  LONG RUNS GAIN NOTHING: 64 runs of 1 024 chunks 0.110 against the range provider's 0.081 and 0.237 against
+ * the range receiver's 0.214 (at group_log 4: 0.190 / 0.158 and 0.226 / 0.202), for 0.03 % fewer bytes.  One cause that is known and
+ * was not measured apart: the tile kernels take 92 and 76 VGPRs, so ONE workgroup of 1 024 lanes is resident a CU where the range
+ * tile kernels (52 / 53) fit two.  So: set slices for the many
+ * short runs of a half-arrived file, the range calls for a few long runs or a sparse scatter of medium ones; the one-chunk calls win
+ * none of these shapes against the better of the two.  The list must be ascending and disjoint and a file is in one set a call, which
+ * the range calls do not ask.  Not measured: where between 64 and 512 wanted chunks a tile the two cross, files past 1 GiB, many files
+ * a call, the kernels one by one. */
+int32_t b3w_bao_set_slice_ingest_device(b3w_ctx *ctx, uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets,
+                                        const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, uint8_t *d_outboards,
+                                        const uint32_t *d_roots, const uint32_t *host_files, const uint64_t *host_first,
+                                        const uint64_t *host_count, uint32_t n_ranges, const uint8_t *d_slices, int32_t *d_set_status,
+                                        uint64_t *d_set_first_bad, int32_t *d_chunk_status /* may be NULL */,
+                                        uint64_t *d_have /* may be NULL */, void *d_scratch, uint64_t scratch_bytes, void *stream);
+
 /* ---- updates in place after writes to resident files (still ABI 1.4: new names only) --------------------------------
  * Every call above treats a file as immutable: after one rewritten block the only way to a correct outboard and root is the batch
  * call over the whole file again.  These calls make the cost follow the bytes written.  GIVEN an arena with its offsets and
