@@ -995,6 +995,53 @@ def ingest_set_slices(ctx, d_arena, offsets, lens, d_outboards, d_roots, files, 
     return dict(set_status=st, set_first_bad=fb, chunk_status=cs, **lay)
 
 
+def plan_samples_set_slices(ctx, lens, d_roots, files, first_chunks, n_chunks, d_slices, stream=0):
+    """The prover's side for set slices: plan_samples_range_slices from SET slices (set_slices_arena's or set_slices_packed's tensor,
+    or slices received and packed as set_slice_layout says) and the files' roots on the device - no outboard, no arena.  The list is
+    the set calls' (ascending by (file, first chunk), disjoint, touching allowed).  Every wanted chunk gets the status and, word for
+    word, the records plan_samples_slices gives the projection of its set slice onto it; a bad node spoils the wanted chunks below it,
+    in every row under it, and no other.  For such a list a set's wanted chunks in ascending order are the list's chunks in
+    runs_chunks order, so the layout is sample_rows_ranges' over the same list: untampered, records and sample_status are byte for
+    byte what plan_samples_range_slices writes from range slices of the same list.  At most three launches.  When not to (MI355X, one 1 GiB file, DESIGN.md §8g, against a
+    build of the commit before planning the same chunks from range slices and, through runs_chunks, from one-chunk slices): the
+    262 507 runs of a half-missing bitmap 5.08 ms against 23.10 and 18.38, 65 536 runs of one chunk 1.53 against 5.95 and 2.01 - but a
+    set takes a workgroup per touched tile, so 4 096 scattered runs of 16 take 0.73 ms against plan_samples_range_slices' 0.45, and 64
+    runs of 1 024 chunks 0.454 against 0.431: a few long runs or a sparse scatter of medium ones stay with the range planner.  This
+    wrapper makes its outputs and scratch on every call.
+    Returns the dict plan_samples_range_slices returns with set_status (int32 CUDA, a set each) and set_first_bad (int64 CUDA, the
+    first chunk of the file whose status is not 0, -1 for none) for the range pair, plus range_row_first: set s owns the rows
+    [range_row_first[set_range_first[s]], range_row_first[set_range_first[s + 1]]) and the statuses from set_chunk_first[s]
+    (**set_slice_layout is in the dict)."""
+    L = lib()
+    ln = _u64(lens)
+    fi = np.ascontiguousarray(files, dtype=np.uint32)
+    fc, nc = _ranges(first_chunks, n_chunks)
+    lay = set_slice_layout(ln, fi, fc, nc)
+    rrf, crf, provable = sample_rows_ranges(ln, fi, fc, nc)
+    dev = d_slices.device
+    n_sets = lay["set_file"].size
+    assert d_roots.is_cuda and d_roots.is_contiguous() and d_roots.numel() >= ln.size * 8
+    assert d_slices.is_cuda and d_slices.dtype == torch.uint8 and d_slices.is_contiguous() and d_slices.numel() >= (int(lay["slice_first"][-1]) if fc.size else 0)
+    recs = torch.empty((int(rrf[-1]), 32), dtype=torch.int32, device=dev)
+    st = torch.full((provable.size,), -1, dtype=torch.int32, device=dev)
+    sst = torch.full((n_sets,), -1, dtype=torch.int32, device=dev)
+    sfb = torch.full((n_sets,), -2, dtype=torch.int64, device=dev)
+    need = L.b3w_bao_set_slice_ingest_scratch_bytes(ln.ctypes.data, ln.size, fi.ctypes.data, fc.ctypes.data, nc.ctypes.data, fc.size)
+    scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    _chk(ctx, L.b3w_sample_plan_set_slices_device(ctx.handle, ln.ctypes.data, ln.size, d_roots.data_ptr(), fi.ctypes.data, fc.ctypes.data, nc.ctypes.data,
+                                                  fc.size, d_slices.data_ptr(), recs.data_ptr(), st.data_ptr(), sst.data_ptr(), sfb.data_ptr(),
+                                                  scratch.data_ptr(), scratch.numel(), _stream(stream)), "b3w_sample_plan_set_slices_device")
+    return dict(records=recs, row_first=crf, sample_status=st.cpu().numpy(), provable=provable, range_row_first=rrf, set_status=sst, set_first_bad=sfb, **lay)
+
+
+def prove_samples_set_slices(ctx, lens, d_roots, files, first_chunks, n_chunks, d_slices, batch_steps=4096, consumer=None, commit_key=None, r1cs=None,
+                             stream=0):
+    """prove_samples_slices over plan_samples_set_slices' plan"""
+    s = _stream(stream)
+    out = plan_samples_set_slices(ctx, lens, d_roots, files, first_chunks, n_chunks, d_slices, stream=s)
+    return _prove_planned(ctx, out, batch_steps, consumer, commit_key, r1cs, s)
+
+
 def set_slice_host(outboard, length, first_chunks, n_chunks, data, group_log=0):
     """The set slice of one file on the host (no GPU) from its outboard of this group_log and the file's bytes -> bytes"""
     if not 0 <= group_log <= MAX_GROUP_LOG:
@@ -1397,6 +1444,27 @@ def range_slices_packed(ctx, d_packed, lens, d_outboards, files, first_chunks, n
                                                       group_log, d_outboards.data_ptr(), fi.ctypes.data, fc.ctypes.data, nc.ctypes.data, fc.size,
                                                       d_slices.data_ptr(), _stream(stream)), "b3w_bao_range_slice_packed_device")
     return dict(slices=d_slices, slice_first=sf)
+
+
+def set_slices_packed(ctx, d_packed, lens, d_outboards, files, first_chunks, n_chunks, group_log=0, stream=0):
+    """set_slices_arena for files that are NOT resident - the multi-range request have_runs produces, answered by a provider whose file
+    is on disk: d_packed (uint8 CUDA, any alignment; pack_ranges makes it) holds the listed chunks of these ranges alone, placed as
+    packed_layout says (at group_log > 0 the whole groups the set touches, which are hashed; all of a file of at most 64 chunks), in
+    place of d_arena and offsets.  The same dict, byte for byte.  At most two launches.  When not to (MI355X, DESIGN.md §8g, against the
+    commit before's set_slices_arena over the resident 1 GiB file): a file that IS resident - never faster, and far behind with many
+    runs (the layout over the run list on the host): the half-missing shape 7.04 ms against 3.18, 65 536 runs of one chunk 1.80
+    against 0.79, 64 runs of 1 024 chunks 0.134 against 0.113; what it saves is the memory and the upload."""
+    ln, fi, fc, nc = _packed_args("set_slices_packed", lens, files, first_chunks, n_chunks, group_log)
+    lay = set_slice_layout(ln, fi, fc, nc)
+    ob_first = group_batch_layout(ln, group_log)
+    assert d_outboards.is_cuda and d_outboards.dtype == torch.uint8 and d_outboards.is_contiguous() and d_outboards.numel() >= int(ob_first[-1])
+    if fc.size:
+        _packed_tensor("set_slices_packed", d_packed, packed_layout(ln, fi, fc, nc, group_log))
+    d_slices = torch.zeros(int(lay["slice_first"][-1]) if fc.size else 0, dtype=torch.uint8, device=d_outboards.device)
+    _chk(ctx, lib().b3w_bao_set_slice_packed_device(ctx.handle, d_packed.data_ptr() if d_packed.numel() else None, d_packed.numel(), ln.ctypes.data, ln.size,
+                                                    group_log, d_outboards.data_ptr(), fi.ctypes.data, fc.ctypes.data, nc.ctypes.data, fc.size,
+                                                    d_slices.data_ptr(), _stream(stream)), "b3w_bao_set_slice_packed_device")
+    return dict(slices=d_slices, **lay)
 
 
 # ---- resident files after appends and truncations ---------------------------------------------------------------------------

@@ -45,6 +45,9 @@
 //                            resident: the same bodies, the listed chunks read slot by slot from a packed buffer that holds them alone,
 //                            a lane's place its rank among the listed chunks, its counter and length its chunk's ("sparse calls from
 //                            packed chunk bytes" in b3wit.h)
+//   b3w_bao_set_*_kernel     the slice of the union of a file's runs, served (from the arena, or packed: b3w_bao_set_slice_packed_kernel)
+//                            and taken in, a row per (set, block with a wanted chunk) carrying the mask ("set slices", the last section)
+//   b3w_sample_plan_set_kernel    the step records of every wanted chunk planned from the set slice alone, on the set receiver's rows
 //
 // The routes (batch table, one streamed file by value, a table of sessions, update / ranges / resize rows) differ only in where a file's
 // entry comes from.  Each kernel, or its *_body wrapper, finds its entry and calls one of the bodies every route shares:
@@ -4312,6 +4315,14 @@ __device__ __forceinline__ uint64_t set_block_node_at(const SetRow<B> *__restric
   return row->place0 + s.rel[c0] - 64ull * depth_in(c0 - i0, size);
 }
 
+// PACKED (b3w_bao_set_slice_packed_device): slot[row] is the slot of the block's first LISTED chunk in the packed buffer, and the
+// block's listed lanes follow it slot by slot.  Listed are all lanes of a file of at most 64 chunks, else the lanes of the groups
+// the set touches (lv[gl]; at gl 0 the mask itself): a lane reads at its rank among them and keeps c = a0 + t for counter and length.
+template <int B>
+__device__ __forceinline__ uint32_t set_listed_rank(const SetLds<B> &s, uint32_t gl, bool all, uint32_t t) {
+  return all ? t : ((set_prefix(s.lv[gl], t >> gl) - 1) << gl) + (t & ((1u << gl) - 1));
+}
+
 // THE PROVIDER (range_slice_body with the mask for the interval)
 template <int B>
 __global__ __launch_bounds__(B) void b3w_bao_set_slice_kernel(const SetDev *__restrict__ sets, const SetRow<B> *__restrict__ rows, uint32_t gl,
@@ -4354,6 +4365,53 @@ __global__ __launch_bounds__(B) void b3w_bao_set_slice_kernel(const SetDev *__re
     const uint32_t bytes = range_chunk_bytes(r.len, c);
     uint8_t *dst = sl + row->place0 + s.rel[ch];
     const uint8_t *src = data + c * 1024;
+    if (q + 16 <= bytes) move16<true>(dst + q, src + q);
+    else for (uint32_t o = q; o < bytes; ++o) dst[o] = src[o];
+  }
+}
+
+// THE PROVIDER FROM PACKED BYTES: b3w_bao_set_slice_kernel with the chunks read at their slots.  A kernel of its own: as two
+// instantiations of one body the arena kernel did not keep its ISA text (two operand pairs swapped), and its text is the yardstick.
+template <int B>
+__global__ __launch_bounds__(B) void b3w_bao_set_slice_packed_kernel(const SetDev *__restrict__ sets, const SetRow<B> *__restrict__ rows,
+                                                                     const uint64_t *__restrict__ slot, uint32_t gl, const uint8_t *__restrict__ packed,
+                                                                     const uint8_t *__restrict__ obs, uint8_t *__restrict__ slices) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B * 8];
+  __shared__ SetLds<B> s;
+  const SetRow<B> *__restrict__ row = rows + blockIdx.x;
+  const SetDev r = sets[row->set];
+  const uint32_t t = threadIdx.x;
+  const uint64_t n = r.len ? (r.len + 1023) / 1024 : 1, a0 = (uint64_t)row->block * B;
+  const uint32_t m = (uint32_t)(n - a0 < B ? n - a0 : B);
+  const bool sole = n <= B, all = n <= 64;
+  const uint8_t *__restrict__ data = packed + 1024 * slot[blockIdx.x], *__restrict__ ob = obs + r.ob;
+  uint8_t *__restrict__ sl = slices + r.slice;
+  const SetLanes w = set_lanes<B>(row, m, t, s);
+  // group outboards: the chunks of the touched groups, hashed (no byte behind the file's last one is read)
+  if (gl != 0 && t < m && set_bit(s.lv[gl], t >> gl)) lane_chunk_cv(cv, data, set_listed_rank<B>(s, gl, all, t), r.len, n, a0 + t, true);
+  for (uint32_t l = 0; (1u << l) < m; ++l) {
+    if (l <= gl) lds_barrier();                            // (the level below inside a group; above the groups nothing is handed on)
+    const uint32_t i0 = (2 * t) << l, i1 = i0 + (1u << l);
+    if (i1 >= m) continue;
+    const uint32_t end = i0 + (2u << l), size = (end < m ? end : m) - i0;
+    const bool meets = set_bit(s.lv[l + 1], t);
+    uint8_t *place = meets ? sl + set_block_node_at<B>(row, s, i0, size) : nullptr;
+    if (l < gl) {                                          // inside a group: computed, and stored where the set wants it
+      if (set_bit(s.lv[gl], i0 >> gl)) merge_pair<true>(cv, i0, i1, place, 4u | (sole && (2u << l) >= m ? 8u : 0u));
+    } else if (meets) {
+      copy_node(place, ob + 8 + node_pos<true>(n, a0 + i0, size, gl) * 64);
+    }
+  }
+  // the nodes above the block whose first wanted chunk lies in it, and the header in front of min S
+  const RsAbove up = range_above(n, a0, m, t);
+  const uint64_t own = row->place0 - 64ull * (up.depth + depth_in(w.cf, m));     // the place of the root, if this row holds min S
+  if (t < up.depth && row->up[t] == own + 64ull * t) copy_node(sl + row->up[t], ob + 8 + node_pos<true>(n, up.lo, up.cnt, gl) * 64);
+  if (t == 0 && own == 8) *reinterpret_cast<uint2 *>(sl) = *reinterpret_cast<const uint2 *>(ob);
+  for (uint32_t p = t; p < w.cnt * 64; p += B) {
+    const uint32_t ch = s.lane_of[p >> 6], q = (p & 63) * 16;
+    const uint32_t bytes = range_chunk_bytes(r.len, a0 + ch);
+    uint8_t *dst = sl + row->place0 + s.rel[ch];
+    const uint8_t *src = data + set_listed_rank<B>(s, gl, all, ch) * 1024;
     if (q + 16 <= bytes) move16<true>(dst + q, src + q);
     else for (uint32_t o = q; o < bytes; ++o) dst[o] = src[o];
   }
@@ -4488,14 +4546,133 @@ __global__ __launch_bounds__(256) void b3w_bao_set_reduce_kernel(const SetDev *_
   if (lane == 0) { set_status[i] = (int32_t)w; set_first_bad[i] = f; }
 }
 
-// what both set calls refuse about the list and the arena; the sets, their rows and the slices' places
+// THE PLANNER (b3w_sample_plan_range_kernel on the set receiver's rows): b3w_sample_plan_slices_kernel's records and statuses for the
+// projection of the set slice onto every wanted chunk.  The range planner's steps with the mask for the interval:
+//   0. where a lane's rows start: the row's base (row_base[], 8 bytes a row beside the table: the host's closed form over the set's runs,
+//      b3w_int_set_row_base) plus the prefix sum over the WANTED lanes of blocks + path nodes
+//   1. plan_leaf_chunk on the chunk where it lies in the slice (place0 + rel[t]): the leaf records in place, the chunk's CV to LDS
+//   2. - 4. the set receiver's verdicts as they stand; the chunk's status at chunk_first + rank0 + rank, the row's result to the scratch
+//   5. the parent records bottom up: the block's nodes at set_block_node_at, the nodes above it at row->up[]
+// Every row of 128 bytes is written by the lane that owns the chunk.
+template <int B>
+__global__ __launch_bounds__(B) void b3w_sample_plan_set_kernel(const SetDev *__restrict__ sets, const SetRow<B> *__restrict__ rows,
+                                                                const uint64_t *__restrict__ row_base, const uint8_t *__restrict__ slices,
+                                                                const uint32_t *__restrict__ roots, uint32_t *__restrict__ recs,
+                                                                int32_t *__restrict__ chunk_status, uint4 *__restrict__ results) {
+  __shared__ __attribute__((aligned(16))) uint32_t cv[B * 8];
+  __shared__ uint32_t flags[B], listed[B];
+  __shared__ SetLds<B> s;
+  __shared__ uint32_t wave_rows[B / 64], worst, first, above;
+  const SetRow<B> *__restrict__ row = rows + blockIdx.x;
+  const SetDev r = sets[row->set];
+  const uint32_t t = threadIdx.x;
+  const uint64_t n = r.len ? (r.len + 1023) / 1024 : 1, a0 = (uint64_t)row->block * B, c = a0 + t;
+  const uint32_t m = (uint32_t)(n - a0 < B ? n - a0 : B);
+  const bool sole = n <= B;
+  const uint8_t *__restrict__ sl = slices + r.slice;
+  const uint32_t *__restrict__ root = roots + (uint64_t)r.file * 8;
+  flags[t] = 0;
+  if (t == 0) { worst = 0; first = ~0u; above = 0; }
+  const SetLanes w = set_lanes<B>(row, m, t, s);
+  const bool mine = w.mine;
+  listed[t] = mine ? 1u : 0u;
+  const uint32_t P = mine ? depth_in(c, n) : 0, bytes = mine ? range_chunk_bytes(r.len, c) : 0, n_blocks = bytes ? (bytes + 63) / 64 : 1;
+  // 0. the lane's first row
+  const uint32_t own = mine ? n_blocks + P : 0;
+  uint32_t upto = own;
+#pragma unroll
+  for (int d = 1; d < 64; d *= 2) {
+    const uint32_t o = __shfl_up(upto, d);
+    if ((t & 63) >= (uint32_t)d) upto += o;
+  }
+  if ((t & 63) == 63) wave_rows[t >> 6] = upto;
+  __syncthreads();
+  uint32_t ahead = upto - own;
+  for (uint32_t wv = 0; wv < (t >> 6); ++wv) ahead += wave_rows[wv];
+  uint32_t *__restrict__ rec = recs + (row_base[blockIdx.x] + ahead) * 32;
+  // 1. the leaf records and the chunks' CVs
+  uint32_t h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (mine) {
+    plan_leaf_chunk(sl + row->place0 + s.rel[t], bytes, c, P, rec, h);   // (16-byte aligned; P == 0: the ROOT-flagged output)
+    put_cv(cv, t, h);
+  }
+  // 2. - 4. the verdicts, as the set receiver reaches them
+  const RsAbove up = range_above(n, a0, m, t);
+  if (t < up.depth) {
+    uint32_t mw[16], ivv[8], o[8];
+    load_node(sl + row->up[t], mw);
+    iv(ivv);
+    blake3_cv(ivv, mw, 0, 0, 64, 4u | (t == 0 ? 8u : 0u), o);
+    const uint32_t *want = t == 0 ? root : reinterpret_cast<const uint32_t *>(sl + row->up[t - 1] + (up.left ? 0 : 32));
+    if (!eq8(o, want)) atomicOr(&above, 1u);
+  }
+  for (uint32_t l = 0; (1u << l) < m; ++l) {
+    lds_barrier();
+    const uint32_t i0 = (2 * t) << l, i1 = i0 + (1u << l);
+    if (i1 >= m) continue;
+    const bool d0 = listed[i0] != 0, d1 = listed[i1] != 0;
+    if (!d0 && !d1) continue;
+    const uint32_t end = i0 + (2u << l), size = (end < m ? end : m) - i0;
+    ranges_pair<true>(cv, flags, nullptr, i0, i1, d0, d1, l, sl + set_block_node_at<B>(row, s, i0, size), 4u | (sole && (2u << l) >= m ? 8u : 0u), 1ull << l,
+                      size - (1u << l), 1, nullptr);
+    listed[i0] = 1;
+  }
+  lds_barrier();
+  if (t == 0) {
+    const uint32_t *want = up.depth ? reinterpret_cast<const uint32_t *>(sl + row->up[up.depth - 1] + (up.last_left ? 0 : 32)) : root;
+    if (!eq8(cv, want)) flags[0] |= m == 1 ? VER_UNIT : VER_TOP;
+  }
+  lds_barrier();
+  const uint2 hd = *reinterpret_cast<const uint2 *>(sl);
+  const bool hdr = ((uint64_t)hd.x | ((uint64_t)hd.y << 32)) != r.len;
+  uint32_t st = 0;
+  if (mine) {
+    st = hdr ? 3u : above || path_bad(flags, t) ? 2u : (flags[t] & VER_UNIT) ? 1u : 0u;
+    chunk_status[r.chunk_first + row->rank0 + w.rank] = (int32_t)st;
+    if (st) { atomicMax(&worst, st); atomicMin(&first, t); }
+  }
+  __syncthreads();
+  if (t == 0) results[blockIdx.x] = make_uint4(worst, 0, first == ~0u ? ~0u : (uint32_t)(a0 + first), first == ~0u ? ~0u : (uint32_t)((a0 + first) >> 32));
+  if (!mine) return;
+  // 5. the parent records: the block's nodes on the lane's path bottom up, then the nodes above the block
+  const bool chain = st != 0 || !path_provable(c, n);
+  uint32_t g = 0;
+  rec += (uint64_t)n_blocks * 32;
+  const auto step = [&](uint64_t at) {
+    uint32_t mw[16], on[8], sib[8];
+    load_node(sl + at, mw);
+    const bool bit_left = ((c >> g) & 1) == 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { on[k] = bit_left ? mw[k] : mw[8 + k]; sib[k] = bit_left ? mw[8 + k] : mw[k]; }
+    if (chain) plan_parent_step(rec, h, sib, bit_left, c, n_blocks, P, P - 1 - g);
+    else {
+      if (g) {                                             // (every node hashed to its half of the node above: h at height g is that half)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) h[k] = on[k];
+      }
+      parent_record(rec, h, sib, c, n_blocks, P, P - 1 - g);
+    }
+    rec += 32; ++g;
+  };
+  for (uint32_t l = 0; (1u << l) < m; ++l) {
+    const uint32_t i0 = (t >> (l + 1)) << (l + 1), i1 = i0 + (1u << l);
+    if (i1 >= m) continue;
+    const uint32_t end = i0 + (2u << l), size = (end < m ? end : m) - i0;
+    step(set_block_node_at<B>(row, s, i0, size));
+  }
+  for (uint32_t j = up.depth; j-- > 0;) step(row->up[j]);
+}
+
+// what the set calls refuse about the list and the arena (null host_offsets: the arena is not looked at); the sets, their rows and the
+// slices' places
 int32_t set_list_ok(b3w_ctx *ctx, const char *what, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
                     uint32_t n_files, const uint32_t *host_files, const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, SetList &list) {
   if (!b3w_int_set_list(host_lens, n_files, host_files, host_first, host_count, n_ranges, list)) return refuse(ctx, what, list.why);
   for (const SetEnt &e : list.sets) {
-    const uint64_t len = host_lens[e.file], off = host_offsets[e.file];
+    const uint64_t len = host_lens[e.file], off = host_offsets ? host_offsets[e.file] : 0;
     const char *why = nullptr;
     if (num_chunks(len) > (1ull << 30)) why = "its file has more than 2^30 chunks";
+    else if (!host_offsets) why = nullptr;
     else if (len && !d_arena) why = "a null arena with a file that is not empty";
     else if (off > arena_bytes || len > arena_bytes - off) why = "its file reaches past arena_bytes";
     if (why) return refuse(ctx, what, "range " + std::to_string(e.range_first) + ": " + why);
@@ -4535,19 +4712,23 @@ bool set_make_row(SetRow<B> &row, uint32_t set, uint64_t blk, uint64_t len, cons
   return true;
 }
 
-// the table into the staging and on its way: the sets' entries, the rows of 1 024 chunks, the rows of 64
-int32_t set_table(b3w_ctx *ctx, const uint64_t *host_offsets, const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint64_t *host_first,
-                  const uint64_t *host_count, const SetList &list, hipStream_t st, const SetDev *&d_sets, const SetRow<(int)B3W_TILE> *&d_big,
-                  const SetRow<64> *&d_small) {
+// the table into the staging and on its way: the sets' entries, the rows of 1 024 chunks, the rows of 64 and, where the call has one
+// (AUX), a 64-bit value a row in the rows' order behind them: d_aux for the tile rows, d_aux + list.big for the rows of 64.  The call
+// says what a set's `off` is (off_of(file)) and what a row carries beside the table (aux_of(set, block, B)).
+template <bool AUX, class Off, class Aux>
+int32_t set_table(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint64_t *host_first, const uint64_t *host_count,
+                  const SetList &list, hipStream_t st, const SetDev *&d_sets, const SetRow<(int)B3W_TILE> *&d_big, const SetRow<64> *&d_small,
+                  const uint64_t *&d_aux, Off off_of, Aux aux_of) {
   using Big = SetRow<(int)B3W_TILE>;
   using Small = SetRow<64>;
   const uint64_t n_sets = list.sets.size();
-  const uint64_t up_bytes = n_sets * sizeof(SetDev) + list.big * sizeof(Big) + list.small * sizeof(Small);
+  const uint64_t up_bytes = n_sets * sizeof(SetDev) + list.big * sizeof(Big) + list.small * sizeof(Small) + (AUX ? (list.big + list.small) * 8 : 0);
   B3W_TRY(batch_staging(ctx, up_bytes + 2 * ((uint64_t)n_files + 1) * 8));
   SetDev *sd = reinterpret_cast<SetDev *>(ctx->h_batch);
   Big *big = reinterpret_cast<Big *>(sd + n_sets);
   Small *small = reinterpret_cast<Small *>(big + list.big);
-  uint64_t *ob_first = reinterpret_cast<uint64_t *>(small + list.small), *word_first = ob_first + n_files + 1;
+  uint64_t *aux = reinterpret_cast<uint64_t *>(small + list.small);
+  uint64_t *ob_first = aux + (AUX ? list.big + list.small : 0), *word_first = ob_first + n_files + 1;
   (void)b3w_bao_group_batch_layout(host_lens, n_files, group_log, ob_first);
   (void)b3w_bao_have_layout(host_lens, n_files, word_first);
   uint64_t nb = 0, ns = 0;
@@ -4555,7 +4736,7 @@ int32_t set_table(b3w_ctx *ctx, const uint64_t *host_offsets, const uint64_t *ho
     const SetEnt &e = list.sets[s];
     const uint64_t len = host_lens[e.file], k = e.range_end - e.range_first;
     const uint64_t *first = host_first + e.range_first, *count = host_count + e.range_first;
-    sd[s] = SetDev{len, host_offsets[e.file], ob_first[e.file], e.slice, word_first[e.file], e.chunk_first, e.file,
+    sd[s] = SetDev{len, off_of(e.file), ob_first[e.file], e.slice, word_first[e.file], e.chunk_first, e.file,
                    (uint32_t)(e.shrt ? list.big + ns : nb), (uint32_t)e.rows, 0};
     const uint64_t *ufirst = list.ufirst.data() + e.range_first, *rank = list.rank.data() + e.range_first;
     const uint64_t B = e.shrt ? 64 : B3W_TILE;
@@ -4565,6 +4746,7 @@ int32_t set_table(b3w_ctx *ctx, const uint64_t *host_offsets, const uint64_t *ho
         if (blk == last) continue;
         last = blk;
         if (made++ == e.rows) return refuse(ctx, "bao set slice table", "the rows do not add up");   // (never: b3w_int_set_list counted them)
+        if (AUX) aux[e.shrt ? list.big + ns : nb] = aux_of(s, blk, B);
         if (!(e.shrt ? set_make_row<64>(small[ns++], (uint32_t)s, blk, len, first, count, k, ufirst, rank)
                      : set_make_row<(int)B3W_TILE>(big[nb++], (uint32_t)s, blk, len, first, count, k, ufirst, rank)))
           return refuse(ctx, "bao set slice table", "a block lies deeper than the table's places");
@@ -4574,7 +4756,16 @@ int32_t set_table(b3w_ctx *ctx, const uint64_t *host_offsets, const uint64_t *ho
   d_sets = reinterpret_cast<const SetDev *>(ctx->d_batch);
   d_big = reinterpret_cast<const Big *>(d_sets + n_sets);
   d_small = reinterpret_cast<const Small *>(d_big + list.big);
+  d_aux = reinterpret_cast<const uint64_t *>(d_small + list.small);
   return B3W_OK;
+}
+// the arena provider's and the receiver's table: `off` is the file's place in the arena, nothing beside the rows
+int32_t set_table(b3w_ctx *ctx, const uint64_t *host_offsets, const uint64_t *host_lens, uint32_t n_files, uint32_t group_log, const uint64_t *host_first,
+                  const uint64_t *host_count, const SetList &list, hipStream_t st, const SetDev *&d_sets, const SetRow<(int)B3W_TILE> *&d_big,
+                  const SetRow<64> *&d_small) {
+  const uint64_t *none = nullptr;
+  return set_table<false>(ctx, host_lens, n_files, group_log, host_first, host_count, list, st, d_sets, d_big, d_small, none,
+                          [&](uint32_t f) { return host_offsets[f]; }, [](uint64_t, uint64_t, uint64_t) { return 0ull; });
 }
 
 }  // namespace
@@ -4638,6 +4829,88 @@ int32_t b3w_bao_set_slice_ingest_device(b3w_ctx *ctx, uint8_t *d_arena, uint64_t
   hipLaunchKernelGGL(b3w_bao_set_reduce_kernel, dim3((n_sets + 3) / 4), dim3(256), 0, st, d_sets, n_sets, res, d_set_status,
                      reinterpret_cast<unsigned long long *>(d_set_first_bad));
   return batch_launched(ctx, st, "bao set slice ingest launch");
+}
+
+// the arena call's table and grids; a row's slot (beside the table) is that of its block's first listed chunk in the packed buffer
+int32_t b3w_bao_set_slice_packed_device(b3w_ctx *ctx, const uint8_t *d_packed, uint64_t packed_bytes, const uint64_t *host_lens, uint32_t n_files,
+                                        uint32_t group_log, const uint8_t *d_outboards, const uint32_t *host_files, const uint64_t *host_first,
+                                        const uint64_t *host_count, uint32_t n_ranges, uint8_t *d_slices, void *stream) {
+  const char *call = "bao set slice packed";
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  B3W_TRY(group_log_ok(ctx, call, group_log));
+  if (!n_ranges) return B3W_OK;
+  if (!host_lens || !d_outboards || !host_files || !host_first || !host_count || !d_slices) return refuse(ctx, call, "a null pointer");
+  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) return refuse(ctx, call, "d_outboards is not 8-byte or d_slices not 16-byte aligned");
+  SetList list;
+  B3W_TRY(set_list_ok(ctx, call, nullptr, 0, nullptr, host_lens, n_files, host_files, host_first, host_count, n_ranges, list));
+  const PkLayout pk = b3w_int_packed_layout(host_lens, b3w_int_update_ranges(host_lens, host_files, host_first, host_count, n_ranges), group_log);
+  B3W_TRY(packed_ok(ctx, call, SparseSrc{d_packed, packed_bytes, nullptr}, pk));
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  const SetDev *d_sets = nullptr;
+  const SetRow<(int)B3W_TILE> *d_big = nullptr;
+  const SetRow<64> *d_small = nullptr;
+  const uint64_t *d_slot = nullptr;
+  B3W_TRY(set_table<true>(ctx, host_lens, n_files, group_log, host_first, host_count, list, st, d_sets, d_big, d_small, d_slot,
+                          [](uint32_t) { return 0ull; },
+                          [&](uint64_t s, uint64_t blk, uint64_t B) {
+                            const SetEnt &e = list.sets[s];
+                            return b3w_int_set_row_slot(pk, e.file, host_lens[e.file], group_log, host_first + e.range_first, host_count + e.range_first,
+                                                        e.range_end - e.range_first, blk * B);
+                          }));
+  if (list.big)
+    hipLaunchKernelGGL(b3w_bao_set_slice_packed_kernel<(int)B3W_TILE>, dim3((uint32_t)list.big), dim3(B3W_TILE), 0, st, d_sets, d_big, d_slot, group_log, d_packed,
+                       d_outboards, d_slices);
+  if (list.small)
+    hipLaunchKernelGGL(b3w_bao_set_slice_packed_kernel<64>, dim3((uint32_t)list.small), dim3(64), 0, st, d_sets, d_small, d_slot + list.big, group_log, d_packed,
+                       d_outboards, d_slices);
+  return batch_launched(ctx, st, "bao set slice packed launch");
+}
+
+// ---- step records of the wanted chunks of set slices ----------------------------------------------------------------------------------
+int32_t b3w_sample_plan_set_slices_device(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, const uint32_t *d_roots, const uint32_t *host_files,
+                                          const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, const uint8_t *d_slices,
+                                          uint32_t *d_records, int32_t *d_chunk_status, int32_t *d_set_status, uint64_t *d_set_first_bad, void *d_scratch,
+                                          uint64_t scratch_bytes, void *stream) {
+  const char *call = "sample plan set slices";
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  B3W_TRY(nova_ok(ctx));
+  if (!n_ranges) return B3W_OK;
+  if (!host_lens || !d_roots || !host_files || !host_first || !host_count || !d_slices || !d_records || !d_chunk_status || !d_set_status || !d_set_first_bad)
+    return refuse(ctx, call, "a null pointer");
+  if (((uintptr_t)d_slices & 15) || ((uintptr_t)d_roots & 3)) return refuse(ctx, call, "d_slices is not 16-byte or d_roots not 4-byte aligned");
+  if (((uintptr_t)d_records & 3) || ((uintptr_t)d_chunk_status & 3)) return refuse(ctx, call, "d_records or d_chunk_status is not 4-byte aligned");
+  if (((uintptr_t)d_set_status & 3) || ((uintptr_t)d_set_first_bad & 7)) return refuse(ctx, call, "d_set_status is not 4-byte or d_set_first_bad not 8-byte aligned");
+  SetList list;
+  B3W_TRY(set_list_ok(ctx, call, nullptr, 0, nullptr, host_lens, n_files, host_files, host_first, host_count, n_ranges, list));
+  if (scratch_bytes < (list.big + list.small) * 16) return refuse(ctx, call, "the scratch is smaller than b3w_bao_set_slice_ingest_scratch_bytes says");
+  if (!d_scratch || ((uintptr_t)d_scratch & 15)) return refuse(ctx, call, "the scratch is null or not 16-byte aligned");
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  const SetDev *d_sets = nullptr;
+  const SetRow<(int)B3W_TILE> *d_big = nullptr;
+  const SetRow<64> *d_small = nullptr;
+  const uint64_t *d_base = nullptr;
+  // a row carries the first record row of its first wanted chunk: the runs' first rows (O(depth) a run), then O(depth) a row
+  const std::vector<uint64_t> run_row = b3w_int_range_row_first(host_lens, host_files, host_first, host_count, n_ranges);
+  B3W_TRY(set_table<true>(ctx, host_lens, n_files, 0, host_first, host_count, list, st, d_sets, d_big, d_small, d_base,
+                          [](uint32_t) { return 0ull; },
+                          [&](uint64_t s, uint64_t blk, uint64_t B) {
+                            const SetEnt &e = list.sets[s];
+                            return b3w_int_set_row_base(host_lens[e.file], host_first + e.range_first, host_count + e.range_first, e.range_end - e.range_first,
+                                                        run_row.data() + e.range_first, blk * B);
+                          }));
+  uint4 *res = reinterpret_cast<uint4 *>(d_scratch);
+  const uint32_t n_sets = (uint32_t)list.sets.size();
+  if (list.big)
+    hipLaunchKernelGGL(b3w_sample_plan_set_kernel<(int)B3W_TILE>, dim3((uint32_t)list.big), dim3(B3W_TILE), 0, st, d_sets, d_big, d_base, d_slices, d_roots, d_records,
+                       d_chunk_status, res);
+  if (list.small)
+    hipLaunchKernelGGL(b3w_sample_plan_set_kernel<64>, dim3((uint32_t)list.small), dim3(64), 0, st, d_sets, d_small, d_base + list.big, d_slices, d_roots, d_records,
+                       d_chunk_status, res + list.big);
+  hipLaunchKernelGGL(b3w_bao_set_reduce_kernel, dim3((n_sets + 3) / 4), dim3(256), 0, st, d_sets, n_sets, res, d_set_status,
+                     reinterpret_cast<unsigned long long *>(d_set_first_bad));
+  return batch_launched(ctx, st, "sample plan set slices launch");
 }
 
 }  // extern "C"

@@ -403,6 +403,31 @@ uint64_t PkLayout::slot_of(uint32_t file, uint64_t chunk) const {
   return r.slot + (chunk - r.first);
 }
 
+// ---- the set planner's and the packed set provider's row values (8 bytes a row beside the set table) ---------------------------------------
+std::vector<uint64_t> b3w_int_range_row_first(const uint64_t *lens, const uint32_t *files, const uint64_t *first, const uint64_t *count, uint32_t n_ranges) {
+  std::vector<uint64_t> row((size_t)n_ranges + 1);
+  uint64_t at = 0;
+  for (uint32_t i = 0; i < n_ranges; ++i) {
+    const uint64_t len = lens[files[i]], n = num_chunks(len);
+    row[i] = at;
+    at += rows_before(len, n, first[i] + count[i]) - rows_before(len, n, first[i]);
+  }
+  row[n_ranges] = at;
+  return row;
+}
+
+uint64_t b3w_int_set_row_base(uint64_t len, const uint64_t *first, const uint64_t *count, uint64_t k, const uint64_t *run_row, uint64_t a0) {
+  const uint64_t n = num_chunks(len), i = set_run_behind(first, count, k, a0), cf = first[i] > a0 ? first[i] : a0;
+  return run_row[i] + (rows_before(len, n, cf) - rows_before(len, n, first[i]));
+}
+
+uint64_t b3w_int_set_row_slot(const PkLayout &pk, uint32_t file, uint64_t len, uint32_t gl, const uint64_t *first, const uint64_t *count, uint64_t k,
+                              uint64_t a0) {
+  if (num_chunks(len) <= 64) return pk.slot_of(file, 0);
+  const uint64_t i = set_run_behind(first, count, k, a0), cf = first[i] > a0 ? first[i] : a0;
+  return pk.slot_of(file, cf & ~((1ull << gl) - 1));
+}
+
 extern "C" {
 
 // ---- sizes and layouts ----------------------------------------------------------------------------------------------------------------

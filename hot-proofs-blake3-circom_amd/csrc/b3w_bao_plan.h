@@ -34,6 +34,14 @@ struct SetList {
 bool b3w_int_set_list(const uint64_t *lens, uint32_t n_files, const uint32_t *files, const uint64_t *first, const uint64_t *count, uint32_t n_ranges,
                       SetList &out);
 
+// The set planner's rows (b3w_sample_plan_set_slices_device).  For an ascending disjoint list a set's wanted chunks in ascending order are
+// the list's chunks in order, so the record rows are b3w_sample_rows_ranges': run_row = its range_row_first (n_ranges + 1 values, from
+// rows_before: O(depth) a range), and a table row's base is the first record row of the first wanted chunk at or behind chunk a0 (the
+// block's start) of the set whose runs are (first, count)[0 .. k), run_row[] their first rows: the run that straddles or follows a0 and
+// the part of it in front of the block.  64 bits; no step a chunk.
+std::vector<uint64_t> b3w_int_range_row_first(const uint64_t *lens, const uint32_t *files, const uint64_t *first, const uint64_t *count, uint32_t n_ranges);
+uint64_t b3w_int_set_row_base(uint64_t len, const uint64_t *first, const uint64_t *count, uint64_t k, const uint64_t *run_row, uint64_t a0);
+
 // The packed layout (b3wit.h "sparse calls from packed chunk bytes"): the chunks b3w_int_update_plan has hashed, as runs of consecutive
 // chunks of one file in consecutive slots of 1 024 bytes, sorted by (file, first chunk); no two runs of a file touch.
 struct PkRun { uint32_t file; uint64_t first, end, slot; };           // chunks [first, end) of the file lie from slot `slot` on
@@ -47,3 +55,8 @@ struct PkLayout {
 PkLayout b3w_int_packed_layout(const uint64_t *lens, const std::vector<UpdRange> &ranges, uint32_t gl);
 // the chunks [*first, *first + *count) that range (file, a, c) of a call lists, c > 0: its groups, or all of a file of at most 64 chunks
 void b3w_int_packed_range(uint64_t len, uint32_t gl, uint64_t a, uint64_t c, uint64_t *first, uint64_t *count);
+// the packed set provider's row (b3w_bao_set_slice_packed_device): the slot of the first LISTED chunk of the block from chunk a0 on of
+// the set whose runs are (first, count)[0 .. k) - chunk 0 of a file of at most 64 chunks, else the start of the group that holds the
+// block's first wanted chunk; the block's listed chunks follow it slot by slot
+uint64_t b3w_int_set_row_slot(const PkLayout &pk, uint32_t file, uint64_t len, uint32_t gl, const uint64_t *first, const uint64_t *count, uint64_t k,
+                              uint64_t a0);

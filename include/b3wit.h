@@ -1291,6 +1291,67 @@ int32_t b3w_bao_set_slice_ingest_device(b3w_ctx *ctx, uint8_t *d_arena, uint64_t
                                         const uint64_t *host_count, uint32_t n_ranges, const uint8_t *d_slices, int32_t *d_set_status,
                                         uint64_t *d_set_first_bad, int32_t *d_chunk_status /* may be NULL */,
                                         uint64_t *d_have /* may be NULL */, void *d_scratch, uint64_t scratch_bytes, void *stream);
+/* THE PLANNER: the prover's side of set slices, the twin of b3w_sample_plan_range_slices_device.  The list is the set calls' list
+ * (ascending by (file, first chunk), disjoint, touching runs allowed); d_slices is packed as b3w_bao_set_slice_batch_layout says.
+ * SEMANTICS, BY PROJECTION: every wanted chunk c of every set gets the status b3w_sample_plan_slices_device gives the projection of
+ * the set slice onto c (3 over 2 over 1; a one-chunk file's wrong root is 1) and, word for word, the rows that call writes for the
+ * projection - leaf blocks first, then parent steps bottom up; the chained words where the chunk failed or b3w_chain_path_provable
+ * says no, the words straight from the nodes otherwise.  Records are written for failing chunks too.  A bad node spoils the wanted
+ * chunks below it, in every row under it, and no other.  d_set_status / d_set_first_bad are what b3w_bao_set_slice_ingest_device
+ * reports.
+ * THE OUTPUT LAYOUT NEEDS NO NEW HOST CALL.  For an ascending disjoint list a set's wanted chunks in ascending order are the list's
+ * chunks in order, so the rows are exactly b3w_sample_rows_ranges' over the same list: set s owns rows
+ * [range_row_first[set_range_first[s]], range_row_first[set_range_first[s + 1]]), and its chunk statuses lie at set_chunk_first[s] +
+ * rank, which is the running sum of the counts.  UNTAMPERED, d_records AND d_chunk_status ARE BYTE FOR BYTE WHAT
+ * b3w_sample_plan_range_slices_device WRITES FOR THE SAME LIST FROM RANGE SLICES.
+ * The kernel runs on the set receiver's rows and table (lane = chunk, `mine` the row's mask bit, so every wanted lane of a tile is
+ * busy); beside the table a row carries the 64-bit number of its first record row, 8 bytes, from a closed form on the host (O(depth)
+ * a run and a row, no step a chunk).  At most THREE launches (tile rows, rows of 64, b3w_bao_set_slice_ingest_device's reduce); one
+ * table through the context's staging and nothing else allocated; asynchronous on `stream`; nova contexts only.  THE SCRATCH is 16
+ * bytes a row: b3w_bao_set_slice_ingest_scratch_bytes for the same list.  Rows, places and byte counts are 64 bits wide.
+ * n_ranges == 0: a no-op.  REFUSALS ARE ATOMIC (B3W_E_BAD_ARGUMENT before anything is launched or written - records, statuses, set
+ * outputs and scratch untouched; b3w_last_error names the range): what the set calls refuse about the list (an unsorted or overlapping
+ * one is named as such), a null or misaligned pointer, a scratch that is too small, a file of more than 2^30 chunks, more than
+ * 2^31 - 1 rows of one kind, a context that is not a nova circuit's.
+ * WHEN NOT TO (MI355X, one 1 GiB file; the yardsticks are a build of the commit before this call planning the same chunks,
+ * b3w_sample_plan_range_slices_device over range slices and bao.runs_chunks + b3w_sample_plan_slices_device over one-chunk slices;
+ * device events round whole calls, the three routes' records compared word for word before timing; no profiler run).  The 262 507 runs
+ * of a bitmap with half its chunks missing, 2.4 GB of records: 5.08 ms against 18.38 (one-chunk, the faster; spread 0.03) and 23.10
+ * (range; 0.08), from 593 MB of slices where the yardsticks read 1 213 and 892; 65 536 runs of ONE chunk: 1.53 against 2.01 (0.0005) and
+ * 5.95 (0.06).  FEW WANTED CHUNKS IN MANY TILES LOSE TO THE RANGE PLANNER, as in the receiver: 4 096 runs of 16 scattered over the file
+ * keep 64 lanes of each of 1 009 workgroups of 1 024 busy - 0.733 ms against the range planner's 0.447 (spread 0.001; one-chunk 1.80).
+ * LONG RUNS GAIN NOTHING: 64 runs of 1 024 chunks 0.454 against 0.431 (0.0001), for 0.03 % fewer bytes.  So: this call for the many
+ * short runs of a half-arrived file, the range planner for a few long runs or a sparse scatter of medium ones; the one-chunk planner
+ * wins none of these shapes against the better of the two.  The list must be ascending and disjoint and a file is in one set a call,
+ * which the range planner does not ask.  Not measured: where between 64 and 512 wanted chunks a tile the two cross, files past 1 GiB,
+ * many files a call, the kernels one by one.  Not tested on the device: records past 2^32 bytes (4.8 GB of output; the host side of
+ * it is held by tools/bao_set_plan_host_check.cpp). */
+int32_t b3w_sample_plan_set_slices_device(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, const uint32_t *d_roots,
+                                          const uint32_t *host_files, const uint64_t *host_first, const uint64_t *host_count,
+                                          uint32_t n_ranges, const uint8_t *d_slices, uint32_t *d_records, int32_t *d_chunk_status,
+                                          int32_t *d_set_status, uint64_t *d_set_first_bad, void *d_scratch, uint64_t scratch_bytes,
+                                          void *stream);
+/* THE PROVIDER FROM PACKED CHUNK BYTES ("sparse calls from packed chunk bytes" below): b3w_bao_set_slice_arena_device for files that
+ * are not resident, (d_packed, packed_bytes) in place of (d_arena, arena_bytes, host_offsets).  EVERY OUTPUT BYTE IS WHAT THE ARENA
+ * CALL WRITES for an arena with the same file bytes, outboards, list and group_log, and every byte it leaves alone stays.  The layout
+ * is b3w_bao_packed_layout's over the same list: a file of at most 64 chunks lists all its chunks, any other file every chunk of
+ * every group of 2^group_log chunks the set touches.  Beside the table a row carries the slot of its block's first listed chunk (8
+ * bytes, looked up in the layout's runs on the host); a lane reads at its rank among the block's LISTED lanes - the mask bits at
+ * group_log 0, the lanes of the touched groups above 0, every lane in a file of at most 64 chunks - and keeps its chunk index for the
+ * counter and the length.  At most TWO launches, the same table, nothing allocated, any byte alignment of d_packed; no byte behind
+ * total_bytes is read.  Refused, atomically: what the arena call refuses without the arena items, a null d_packed with
+ * total_bytes > 0, packed_bytes < total_bytes (the message says how many are needed).
+ * WHEN NOT TO (the same run; the yardstick is the parent's b3w_bao_set_slice_arena_device over the resident file, the two calls' slices
+ * compared byte for byte before timing): a file that IS resident.  The packed call is never faster, and with many runs it is FAR
+ * behind: the half-missing shape 7.04 ms against 3.18 (spread 0.001), 65 536 runs of one chunk 1.80 against 0.79, 4 096 runs of 16
+ * 0.516 against 0.349; 64 runs of 1 024 chunks 0.134 against 0.113 (0.190 / 0.187 at group_log 4).  The kernels read the same bytes;
+ * what the call adds is the packed layout over the run list on the host (the merged ranges, the layout's runs, a lookup a row), about
+ * 15 ns a run - supposed from the shapes, not measured apart.  What it saves is the memory and the upload: 536 MB of listed chunks on
+ * the device where the arena call needs the 1 GiB file.  Not timed: the gather into the packed buffer, files past 1 GiB. */
+int32_t b3w_bao_set_slice_packed_device(b3w_ctx *ctx, const uint8_t *d_packed, uint64_t packed_bytes, const uint64_t *host_lens,
+                                        uint32_t n_files, uint32_t group_log, const uint8_t *d_outboards, const uint32_t *host_files,
+                                        const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, uint8_t *d_slices,
+                                        void *stream);
 
 /* ---- updates in place after writes to resident files (still ABI 1.4: new names only) --------------------------------
  * Every call above treats a file as immutable: after one rewritten block the only way to a correct outboard and root is the batch
