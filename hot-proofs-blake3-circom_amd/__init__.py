@@ -249,6 +249,9 @@ def lib():
         "b3w_bao_set_slice_ingest_device": (i32, [vp, vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, u64, vp]),
         "b3w_sample_plan_set_slices_device": (i32, [vp, vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, u64, vp]),
         "b3w_bao_set_slice_packed_device": (i32, [vp, vp, u64, vp, u32, u32, vp, vp, vp, vp, u32, vp, vp]),
+        "b3w_bao_slice_ingest_packed_device": (i32, [vp, vp, u64, vp, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp]),
+        "b3w_bao_range_slice_ingest_packed_device": (i32, [vp, vp, u64, vp, u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, u64, vp]),
+        "b3w_bao_set_slice_ingest_packed_device": (i32, [vp, vp, u64, vp, u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, u64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -294,7 +297,8 @@ EXPORTED_SYMBOLS = ("b3w_abi_version", "b3w_identify_wasm", "b3w_create", "b3w_d
                     "b3w_bao_range_slice_packed_device",
                     "b3w_bao_set_slice_size", "b3w_bao_set_slice_batch_layout", "b3w_bao_set_slice", "b3w_bao_set_slice_decode",
                     "b3w_bao_set_slice_ingest", "b3w_bao_set_slice_arena_device", "b3w_bao_set_slice_ingest_scratch_bytes",
-                    "b3w_bao_set_slice_ingest_device", "b3w_sample_plan_set_slices_device", "b3w_bao_set_slice_packed_device")
+                    "b3w_bao_set_slice_ingest_device", "b3w_sample_plan_set_slices_device", "b3w_bao_set_slice_packed_device",
+                    "b3w_bao_slice_ingest_packed_device", "b3w_bao_range_slice_ingest_packed_device", "b3w_bao_set_slice_ingest_packed_device")
 
 
 class graph_capture:

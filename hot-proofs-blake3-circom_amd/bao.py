@@ -25,6 +25,10 @@ their places in the arena and their path nodes at their places in the outboards 
 have_new() / ingest_slices(d_have=) keep a bitmap of the chunks that have arrived on the device, have_runs() turns it into the
 missing (or present) chunk runs of every file and have_from_status() rebuilds it from verify_batch's statuses after a restart
 (have_runs_host(), have_from_status_host(): one file on the host; runs_chunks(): the runs as sample lists).
+ingest_slices_packed() / ingest_range_slices_packed() / ingest_set_slices_packed() are the receivers for files that are NOT resident:
+the verified chunks go to one 1 024-byte slot each, in the order of the statuses (chunk_slots(): where each slot belongs in its file;
+scatter_chunks(): the verified slots written there after the copy to the host), with the arena receivers' statuses, outboards and
+bitmap - or, with d_outboards=None, nothing but the verified bytes: bao's decode on the device.
 The records are
 word for word those the chain planner writes for the same chunks (ChainPlanner.plan), so every step is the reference's
 prove_chunk_hash step (rust_fold/src/main.rs:41-203 over hash_with_path's slice, rust_fold/src/blake3_hash.rs:17-93)."""
@@ -1465,6 +1469,156 @@ def set_slices_packed(ctx, d_packed, lens, d_outboards, files, first_chunks, n_c
                                                     group_log, d_outboards.data_ptr(), fi.ctypes.data, fc.ctypes.data, nc.ctypes.data, fc.size,
                                                     d_slices.data_ptr(), _stream(stream)), "b3w_bao_set_slice_packed_device")
     return dict(slices=d_slices, **lay)
+
+
+# ---- slices taken into packed chunk slots: the receiver's side for files that are not resident ------------------------------
+def chunk_slots(lens, files, first_chunks, n_chunks):
+    """The slots of a packed receiver, one per listed chunk in the order of the per-chunk statuses: the ranges (files[r],
+    first_chunks[r], n_chunks[r]) as given, a range's chunks ascending (one-chunk samples: n_chunks all 1).  -> (file uint32, chunk
+    uint64, byte_offset uint64, nbytes uint32), arrays over the slots: slot k holds chunk[k] of file[k], whose nbytes[k] =
+    min(1024, len - 1024 chunk) bytes belong at byte_offset[k] = 1024 chunk[k] of the file.  Host only."""
+    ln = _u64(lens)
+    fi = np.ascontiguousarray(np.atleast_1d(files), dtype=np.uint32)
+    fc, nc = _ranges(first_chunks, n_chunks)
+    if fi.size != fc.size:
+        raise B3WError(100, f"chunk_slots: {fi.size} files and {fc.size} ranges")
+    if fi.size and int(fi.max()) >= ln.size:
+        raise B3WError(100, "chunk_slots: a file index is not below the file count")
+    n = np.maximum((ln[fi] + np.uint64(1023)) // np.uint64(1024), np.uint64(1))
+    if fi.size and ((fc >= n) | (nc > n - np.minimum(fc, n))).any():
+        raise B3WError(100, "chunk_slots: a range reaches past its file's chunk count")
+    f, c = runs_chunks(fi, fc, nc)
+    off = c * np.uint64(1024)
+    left = ln[f] - np.minimum(off, ln[f])
+    return f, c, off, np.minimum(left, np.uint64(1024)).astype(np.uint32)
+
+
+def scatter_chunks(dest, chunks_host, chunk_status, slots):
+    """What a receiver does after the copy to the host: the VERIFIED chunks of a slot buffer to their places in the files.
+    chunks_host: the slot buffer on the host (numpy uint8 or a CPU tensor, 1 024 bytes a slot); chunk_status: a status per slot (None:
+    every slot verified), only those of status 0 are written; slots: chunk_slots' tuple for the call's list; dest: one entry per file,
+    a writable buffer of the file's length (bytearray, numpy uint8, memoryview) or an object with seek(offset) and write(bytes).
+    Verified chunks that touch - neighbouring slots, neighbouring chunks of one file - go out in ONE write.  -> the bytes written."""
+    f, c, off, nb = slots
+    buf = chunks_host.numpy() if isinstance(chunks_host, torch.Tensor) else np.asarray(chunks_host)
+    buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+    if buf.size < 1024 * f.size:
+        raise B3WError(100, f"scatter_chunks: the slot buffer has {buf.size} bytes, {f.size} slots take {1024 * f.size}")
+    ok = nb > 0
+    if chunk_status is not None:
+        st = chunk_status.cpu().numpy() if isinstance(chunk_status, torch.Tensor) else np.asarray(chunk_status)
+        if st.size != f.size:
+            raise B3WError(100, f"scatter_chunks: {st.size} statuses for {f.size} slots")
+        ok &= st.reshape(-1) == 0
+    at = np.flatnonzero(ok)
+    if not at.size:
+        return 0
+    # slot k + 1 goes on where slot k ended: the next slot, the next chunk of the same file, behind a whole chunk
+    joins = (np.diff(at) == 1) & (f[at[1:]] == f[at[:-1]]) & (c[at[1:]] == c[at[:-1]] + np.uint64(1)) & (nb[at[:-1]] == 1024)
+    heads = np.flatnonzero(np.concatenate([[True], ~joins]))
+    tails = np.concatenate([heads[1:], [at.size]]) - 1
+    total = 0
+    for h, t in zip(heads, tails):                                       # a step a WRITE, not a chunk
+        k0, k1 = int(at[h]), int(at[t])
+        nbytes = 1024 * (k1 - k0) + int(nb[k1])
+        src, d, o = buf[1024 * k0:1024 * k0 + nbytes], dest[int(f[k0])], int(off[k0])
+        if hasattr(d, "write"):
+            d.seek(o)
+            d.write(src.tobytes())
+        else:
+            a = _writable(d, "a destination")
+            if o + nbytes > a.size:
+                raise B3WError(100, f"scatter_chunks: file {int(f[k0])}'s buffer has {a.size} bytes, the write ends at {o + nbytes}")
+            a[o:o + nbytes] = src
+        total += nbytes
+    return total
+
+
+def _receive_args(what, lens, d_outboards, d_roots, files, d_slices, slices_bytes, group_log, d_have, d_chunks, n_slots):
+    """the checks the three packed receivers share -> (the slot buffer, its pointer or None)"""
+    ln = _u64(lens)
+    assert d_slices.is_cuda and d_slices.dtype == torch.uint8 and d_slices.is_contiguous() and d_slices.numel() >= slices_bytes, what
+    assert d_roots.is_cuda and d_roots.is_contiguous() and d_roots.numel() >= ln.size * 8, what
+    if d_outboards is not None:
+        ob_first = group_batch_layout(ln, group_log)
+        assert d_outboards.is_cuda and d_outboards.dtype == torch.uint8 and d_outboards.is_contiguous() and d_outboards.numel() >= int(ob_first[-1]), what
+    if d_have is not None:
+        _have_tensor(what, d_have, ln)
+    if d_chunks is None:
+        d_chunks = torch.zeros((n_slots, 1024), dtype=torch.uint8, device=d_slices.device)
+    assert d_chunks.is_cuda and d_chunks.dtype == torch.uint8 and d_chunks.is_contiguous(), what
+    return d_chunks, (d_chunks.data_ptr() if d_chunks.numel() else None)
+
+
+def ingest_slices_packed(ctx, lens, d_outboards, d_roots, files, chunks, d_slices, group_log=0, stream=0, d_have=None, d_chunks=None):
+    """ingest_slices for files that are NOT resident: the verified chunks go to a SLOT BUFFER, sample i to d_chunks[1024 i : ] (uint8
+    CUDA, 16-byte aligned; None: made here, zeroed), in place of d_arena and offsets.  Every status, outboard byte and bitmap bit is
+    what ingest_slices gives for the same slices; a slice that does not verify leaves its slot alone, a short last chunk the rest of
+    its slot.  d_outboards=None: DECODE - nothing but slots, statuses and the bitmap is written.  One launch.  Returns
+    ingest_slices' dict plus chunks (the slot buffer) and slot_first (numpy uint64 [n_samples + 1]: sample i's slot, the total)."""
+    ln, fi, fc, nc = _packed_args("ingest_slices_packed", lens, files, chunks, np.ones(np.size(chunks), dtype=np.uint64), group_log)
+    sf = slice_layout(ln, fi, fc)
+    d_chunks, p_chunks = _receive_args("ingest_slices_packed", ln, d_outboards, d_roots, fi, d_slices, int(sf[-1]), group_log, d_have, d_chunks, fc.size)
+    st = torch.full((fc.size,), -1, dtype=torch.int32, device=d_slices.device)
+    _chk(ctx, lib().b3w_bao_slice_ingest_packed_device(ctx.handle, p_chunks, d_chunks.numel(), ln.ctypes.data, ln.size, group_log,
+                                                       d_outboards.data_ptr() if d_outboards is not None else None, d_roots.data_ptr(), fi.ctypes.data,
+                                                       fc.ctypes.data, fc.size, d_slices.data_ptr(), st.data_ptr(),
+                                                       d_have.data_ptr() if d_have is not None else None, _stream(stream)), "b3w_bao_slice_ingest_packed_device")
+    return dict(sample_status=st, chunks=d_chunks, slot_first=np.arange(fc.size + 1, dtype=np.uint64))
+
+
+def ingest_range_slices_packed(ctx, lens, d_outboards, d_roots, files, first_chunks, n_chunks, d_slices, group_log=0, stream=0, d_have=None, d_chunks=None):
+    """ingest_range_slices for files that are NOT resident: range r's chunk c goes to slot slot_first[r] + (c - first_chunks[r]) of
+    d_chunks, slot_first the running sum of the counts (chunk_slots gives every slot's file position) - overlapping ranges each have
+    their own slots.  Statuses, outboards and bitmap as ingest_range_slices; d_outboards=None: decode.  At most three launches.
+    Returns ingest_range_slices' dict plus chunks and slot_first (numpy uint64 [n_ranges + 1])."""
+    L = lib()
+    ln, fi, fc, nc = _packed_args("ingest_range_slices_packed", lens, files, first_chunks, n_chunks, group_log)
+    sf = range_slice_layout(ln, fi, fc, nc)
+    slot_first = np.concatenate([[0], np.cumsum(nc)]).astype(np.uint64)
+    d_chunks, p_chunks = _receive_args("ingest_range_slices_packed", ln, d_outboards, d_roots, fi, d_slices, int(sf[-1]), group_log, d_have, d_chunks,
+                                       int(slot_first[-1]))
+    dev = d_slices.device
+    st = torch.full((fc.size,), -1, dtype=torch.int32, device=dev)
+    fb = torch.full((fc.size,), -2, dtype=torch.int64, device=dev)
+    need = L.b3w_bao_range_slice_ingest_scratch_bytes(ln.ctypes.data, ln.size, fi.ctypes.data, fc.ctypes.data, nc.ctypes.data, fc.size)
+    scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    _chk(ctx, L.b3w_bao_range_slice_ingest_packed_device(ctx.handle, p_chunks, d_chunks.numel(), ln.ctypes.data, ln.size, group_log,
+                                                         d_outboards.data_ptr() if d_outboards is not None else None, d_roots.data_ptr(), fi.ctypes.data,
+                                                         fc.ctypes.data, nc.ctypes.data, fc.size, d_slices.data_ptr(), st.data_ptr(), fb.data_ptr(),
+                                                         d_have.data_ptr() if d_have is not None else None, scratch.data_ptr(), scratch.numel(),
+                                                         _stream(stream)), "b3w_bao_range_slice_ingest_packed_device")
+    return dict(range_status=st, range_first_bad=fb, chunks=d_chunks, slot_first=slot_first)
+
+
+def ingest_set_slices_packed(ctx, lens, d_outboards, d_roots, files, first_chunks, n_chunks, d_slices, group_log=0, stream=0, d_have=None, d_chunks=None):
+    """ingest_set_slices for files that are NOT resident - the download of the missing half of a file into 537 MB of slots where the
+    arena call needs the resident GiB: set s's wanted chunk of rank k goes to slot set_chunk_first[s] + k of d_chunks, which is
+    chunk_status' index (chunk_slots gives every slot's file position, scatter_chunks writes the verified ones out).  Statuses,
+    outboards and bitmap as ingest_set_slices; d_outboards=None: decode.  At most three launches.  When not to (MI355X, DESIGN.md §8g,
+    against the commit before's arena receivers over the same slices of a 1 GiB file): a file that IS resident.  The packed receivers
+    are level with their twins or just below - that shape 3.34 ms against 3.41, 65 536 single chunks 1.24 against 1.26 as set slices
+    and 1.46 against 1.52 as one-chunk slices, 4 096 runs of 16 as range slices 0.395 against 0.400, 64 runs of 1 024 0.2120 against
+    0.2113 (the one shape behind, by 0.3 %) - so what they save is the memory, not time.  Returns ingest_set_slices' dict plus chunks
+    and slot_first (= set_chunk_first)."""
+    L = lib()
+    ln, fi, fc, nc = _packed_args("ingest_set_slices_packed", lens, files, first_chunks, n_chunks, group_log)
+    lay = set_slice_layout(ln, fi, fc, nc)
+    n_sets, total = lay["set_file"].size, int(lay["set_chunk_first"][-1]) if fc.size else 0
+    d_chunks, p_chunks = _receive_args("ingest_set_slices_packed", ln, d_outboards, d_roots, fi, d_slices, int(lay["slice_first"][-1]) if fc.size else 0,
+                                       group_log, d_have, d_chunks, total)
+    dev = d_slices.device
+    st = torch.full((n_sets,), -1, dtype=torch.int32, device=dev)
+    fb = torch.full((n_sets,), -2, dtype=torch.int64, device=dev)
+    cs = torch.full((total,), -1, dtype=torch.int32, device=dev)
+    need = L.b3w_bao_set_slice_ingest_scratch_bytes(ln.ctypes.data, ln.size, fi.ctypes.data, fc.ctypes.data, nc.ctypes.data, fc.size)
+    scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    _chk(ctx, L.b3w_bao_set_slice_ingest_packed_device(ctx.handle, p_chunks, d_chunks.numel(), ln.ctypes.data, ln.size, group_log,
+                                                       d_outboards.data_ptr() if d_outboards is not None else None, d_roots.data_ptr(), fi.ctypes.data,
+                                                       fc.ctypes.data, nc.ctypes.data, fc.size, d_slices.data_ptr(), st.data_ptr(), fb.data_ptr(),
+                                                       cs.data_ptr() if cs.numel() else None, d_have.data_ptr() if d_have is not None else None,
+                                                       scratch.data_ptr(), scratch.numel(), _stream(stream)), "b3w_bao_set_slice_ingest_packed_device")
+    return dict(set_status=st, set_first_bad=fb, chunk_status=cs, chunks=d_chunks, slot_first=lay["set_chunk_first"], **lay)
 
 
 # ---- resident files after appends and truncations ---------------------------------------------------------------------------

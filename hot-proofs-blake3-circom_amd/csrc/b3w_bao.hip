@@ -1045,7 +1045,10 @@ __device__ __forceinline__ void put16(uint8_t *__restrict__ dst, const uint8_t *
 
 // HAVE: a verified sample also ORs its chunk's bit into the arrival bitmap (b3w_bao_have_layout: chunk c of file f is bit c & 63 of word
 // word_first[f] + (c >> 6)), one atomicOr by the sample's leader behind its stores; the word offsets lie behind the rows of `desc`.
-template <int K, bool HAVE = false>
+// PACKED (b3w_bao_slice_ingest_packed_device): `arena` is a slot buffer and sample s's chunk goes to slot s of 1 024 bytes (16-byte
+// aligned: put16 takes its widest store); a row has no arena offset (five words); `obs` may be null: nothing but the slot, the status
+// and the bit is written (decode).
+template <int K, bool HAVE = false, bool PACKED = false>
 __global__ __launch_bounds__(64) void b3w_bao_slice_ingest_kernel(const uint8_t *__restrict__ slices, const uint32_t *__restrict__ roots,
                                                                   const uint64_t *__restrict__ desc, uint32_t n_samples, uint32_t gl,
                                                                   uint8_t *__restrict__ arena, uint8_t *__restrict__ obs, int32_t *__restrict__ status,
@@ -1053,7 +1056,8 @@ __global__ __launch_bounds__(64) void b3w_bao_slice_ingest_kernel(const uint8_t 
   const uint32_t lane = threadIdx.x, t = lane & (K - 1), base = lane - t;
   const uint32_t s = blockIdx.x * (64u / K) + lane / K;
   const bool valid = s < n_samples, leader = valid && t == 0;
-  const uint64_t *d = desc + 6 * (uint64_t)(valid ? s : 0);              // (lanes past the last sample read sample 0's row and write nothing)
+  constexpr uint32_t W = PACKED ? 5 : 6;                                  // the words of a row
+  const uint64_t *d = desc + W * (uint64_t)(valid ? s : 0);              // (lanes past the last sample read sample 0's row and write nothing)
   const uint64_t c = d[0], len = d[2], n = len ? (len + 1023) / 1024 : 1;
   const uint8_t *sl = slices + d[1];
   const uint32_t *nodes = reinterpret_cast<const uint32_t *>(sl + 8);     // (16-byte aligned)
@@ -1100,29 +1104,32 @@ __global__ __launch_bounds__(64) void b3w_bao_slice_ingest_kernel(const uint8_t 
   if (K > 1) st = __shfl(st, (int)base);
   if (!valid || st != 0) return;                                          // nothing unverified is written
   // 2. the places
-  uint8_t *ob = obs + d[3];
-  if (t == 0) *reinterpret_cast<uint2 *>(ob) = *reinterpret_cast<const uint2 *>(sl);          // the header (it is the length: just checked)
-  const uint64_t n_groups = (n + (1ull << gl) - 1) >> gl;
-  const uint32_t U = path_len(c >> gl, n_groups);                         // (gl = 0: P)
-  uint64_t p = 0, cc = c >> gl, m = n_groups;
-  for (uint32_t j = 0; j < U; ++j) {
+  if (!PACKED || obs) {
+    uint8_t *ob = obs + d[3];
+    if (t == 0) *reinterpret_cast<uint2 *>(ob) = *reinterpret_cast<const uint2 *>(sl);          // the header (it is the length: just checked)
+    const uint64_t n_groups = (n + (1ull << gl) - 1) >> gl;
+    const uint32_t U = path_len(c >> gl, n_groups);                         // (gl = 0: P)
+    uint64_t p = 0, cc = c >> gl, m = n_groups;
+    for (uint32_t j = 0; j < U; ++j) {
 #pragma unroll
-    for (uint32_t q = 0; q < 4; ++q)
-      if (((j * 4 + q) & (K - 1)) == t) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(sl + 8 + 64 * (uint64_t)j + q * 16);
-        uint2 *node = reinterpret_cast<uint2 *>(ob + 8 + p * 64 + q * 16);
-        node[0] = make_uint2(v.x, v.y);
-        node[1] = make_uint2(v.z, v.w);
-      }
-    uint64_t k2 = 1;
-    while (k2 * 2 < m) k2 *= 2;
-    if (cc < k2) { p += 1; m = k2; } else { p += k2; cc -= k2; m -= k2; }
+      for (uint32_t q = 0; q < 4; ++q)
+        if (((j * 4 + q) & (K - 1)) == t) {
+          const uint4 v = *reinterpret_cast<const uint4 *>(sl + 8 + 64 * (uint64_t)j + q * 16);
+          uint2 *node = reinterpret_cast<uint2 *>(ob + 8 + p * 64 + q * 16);
+          node[0] = make_uint2(v.x, v.y);
+          node[1] = make_uint2(v.z, v.w);
+        }
+      uint64_t k2 = 1;
+      while (k2 * 2 < m) k2 *= 2;
+      if (cc < k2) { p += 1; m = k2; } else { p += k2; cc -= k2; m -= k2; }
+    }
   }
-  uint8_t *dst = arena + d[5] + off;
+  uint8_t *dst;
+  if constexpr (PACKED) dst = arena + 1024 * (uint64_t)s; else dst = arena + d[5] + off;
   const uint32_t whole = bytes & ~15u;
   for (uint32_t o = t * 16; o < whole; o += K * 16) put16(dst + o, body + o);
   for (uint32_t o = whole + t; o < bytes; o += K) dst[o] = body[o];
-  if (HAVE && t == 0) atomicOr(have + desc[6 * (uint64_t)n_samples + d[4]] + (c >> 6), 1ull << (c & 63));
+  if (HAVE && t == 0) atomicOr(have + desc[W * (uint64_t)n_samples + d[4]] + (c >> 6), 1ull << (c & 63));
 }
 
 // ---- verification: whole files against their outboards ---------------------------------------------------------------------
@@ -2313,24 +2320,36 @@ void launch_slices(uint32_t group_log, uint32_t n_samples, hipStream_t st, const
   else hipLaunchKernelGGL(b3w_bao_slice_group_kernel<ARENA>, dim3((n_samples + per_wave - 1) / per_wave), dim3(64), 0, st, d_outboards, d_desc, n_samples, group_log, d_bytes, d_slices);
 }
 
-// b3w_bao_slice_ingest_device (HAVE false: d_have is not looked at) and b3w_bao_slice_ingest_have_device
-template <bool HAVE>
+// the slot buffer of the packed receivers (1 024 bytes a listed chunk): b3w_int_slots_wrong's refusal through the one refusal path
+int32_t slots_ok(b3w_ctx *ctx, const char *call, const uint8_t *d_chunks, uint64_t chunks_bytes, uint64_t listed) {
+  const std::string why = b3w_int_slots_wrong(d_chunks, chunks_bytes, listed);
+  return why.empty() ? B3W_OK : refuse(ctx, call, why);
+}
+
+// b3w_bao_slice_ingest_device (HAVE false: d_have is not looked at) and b3w_bao_slice_ingest_have_device; PACKED:
+// b3w_bao_slice_ingest_packed_device, (d_arena, arena_bytes) its slot buffer, no offsets, d_outboards may be null
+template <bool HAVE, bool PACKED = false>
 int32_t slice_ingest(b3w_ctx *ctx, uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens,
                             uint32_t n_files, uint32_t group_log, uint8_t *d_outboards, const uint32_t *d_roots, const uint32_t *host_files,
                             const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_slices, int32_t *d_sample_status, uint64_t *d_have, void *stream) {
-  const char *call = "bao slice ingest";
+  const char *call = PACKED ? "bao slice ingest packed" : "bao slice ingest";
   if (!ctx) return B3W_E_BAD_ARGUMENT;
   B3W_TRY(group_log_ok(ctx, call, group_log));
   if (HAVE && (!d_have || ((uintptr_t)d_have & 7))) return refuse(ctx, call, "d_have is null or not 8-byte aligned");
   if (!n_samples) return B3W_OK;
-  if (!host_offsets || !host_lens || !d_outboards || !d_roots || !host_files || !host_chunks || !d_slices || !d_sample_status) return refuse(ctx, call, "a null pointer");
+  if ((!PACKED && (!host_offsets || !d_outboards)) || !host_lens || !d_roots || !host_files || !host_chunks || !d_slices || !d_sample_status) return refuse(ctx, call, "a null pointer");
   if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) return refuse(ctx, call, "d_outboards is not 8-byte or d_slices not 16-byte aligned");
-  B3W_TRY(arena_samples_ok(ctx, d_arena, arena_bytes, host_offsets, host_lens, n_files, host_files, host_chunks, n_samples));
+  if (PACKED) {
+    B3W_TRY(samples_ok(ctx, host_lens, n_files, host_files, host_chunks, n_samples));
+    B3W_TRY(slots_ok(ctx, call, d_arena, arena_bytes, n_samples));
+  } else {
+    B3W_TRY(arena_samples_ok(ctx, d_arena, arena_bytes, host_offsets, host_lens, n_files, host_files, host_chunks, n_samples));
+  }
   ON_DEVICE(ctx);
   hipStream_t st = (hipStream_t)stream;
   const uint64_t *d_desc = nullptr;
   uint32_t longest = 0;
-  B3W_TRY(sample_table<6, true, false, HAVE>(ctx, host_offsets, host_lens, n_files, group_log, host_files, host_chunks, n_samples, st, &d_desc, &longest));
+  B3W_TRY((sample_table<PACKED ? 5 : 6, true, false, HAVE>(ctx, host_offsets, host_lens, n_files, group_log, host_files, host_chunks, n_samples, st, &d_desc, &longest)));
   // lanes a sample, from the batch's longest path P: node j is checked by lane j mod K, ceil(P / K) rounds beside the chunk's sixteen blocks,
   // and every lane fewer a sample is a leader more a wave in the stretch only leaders run.  Measured at P = 20: four lanes
   // (five rounds) beat sixteen (two) at 4 096 and at 65 536 slices, so four up to six rounds; sixteen for the longer paths (files past
@@ -2339,10 +2358,10 @@ int32_t slice_ingest(b3w_ctx *ctx, uint8_t *d_arena, uint64_t arena_bytes, const
   unsigned long long *have = HAVE ? reinterpret_cast<unsigned long long *>(d_have) : nullptr;
   with_lanes(env ? atoi(env) : (longest <= 24 ? 4 : 16), [&](auto K) {
     constexpr int LANES = decltype(K)::value;
-    hipLaunchKernelGGL((b3w_bao_slice_ingest_kernel<LANES, HAVE>), lanes_grid<LANES>(n_samples), dim3(64), 0, st, d_slices, d_roots, d_desc, n_samples, group_log, d_arena,
+    hipLaunchKernelGGL((b3w_bao_slice_ingest_kernel<LANES, HAVE, PACKED>), lanes_grid<LANES>(n_samples), dim3(64), 0, st, d_slices, d_roots, d_desc, n_samples, group_log, d_arena,
                        d_outboards, d_sample_status, have);
   });
-  return batch_launched(ctx, st, "bao slice ingest launch");
+  return batch_launched(ctx, st, PACKED ? "bao slice ingest packed launch" : "bao slice ingest launch");
 }
 
 }  // namespace
@@ -2605,6 +2624,18 @@ int32_t b3w_bao_slice_ingest_have_device(b3w_ctx *ctx, uint8_t *d_arena, uint64_
                                          uint64_t *d_have, void *stream) {
   return slice_ingest<true>(ctx, d_arena, arena_bytes, host_offsets, host_lens, n_files, group_log, d_outboards, d_roots, host_files, host_chunks, n_samples,
                             d_slices, d_sample_status, d_have, stream);
+}
+
+// the same body with the slot buffer for the arena; the bitmap is optional, so one name serves both
+int32_t b3w_bao_slice_ingest_packed_device(b3w_ctx *ctx, uint8_t *d_chunks, uint64_t chunks_bytes, const uint64_t *host_lens, uint32_t n_files,
+                                           uint32_t group_log, uint8_t *d_outboards, const uint32_t *d_roots, const uint32_t *host_files,
+                                           const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_slices, int32_t *d_sample_status,
+                                           uint64_t *d_have, void *stream) {
+  if (d_have)
+    return slice_ingest<true, true>(ctx, d_chunks, chunks_bytes, nullptr, host_lens, n_files, group_log, d_outboards, d_roots, host_files, host_chunks, n_samples,
+                                    d_slices, d_sample_status, d_have, stream);
+  return slice_ingest<false, true>(ctx, d_chunks, chunks_bytes, nullptr, host_lens, n_files, group_log, d_outboards, d_roots, host_files, host_chunks, n_samples,
+                                   d_slices, d_sample_status, nullptr, stream);
 }
 
 }  // extern "C"
@@ -3769,7 +3800,10 @@ __global__ __launch_bounds__(B) void b3w_bao_range_slice_packed_kernel(const RsR
   range_slice_body<B, true>(ranges, rows, gl, packed, obs, slices);
 }
 
-template <int B>
+// PACKED (b3w_bao_range_slice_ingest_packed_device): `arena` is a slot buffer and r.off the place of the range's first slot in it
+// (1 024 bytes a listed chunk, the ranges one behind the other as given: chunk c of the range at r.off + 1024 (c - a)); `obs` may be
+// null: no node and no header is stored (decode).
+template <int B, bool PACKED = false>
 __global__ __launch_bounds__(B) void b3w_bao_range_ingest_kernel(const RsRange *__restrict__ ranges, const RsRow *__restrict__ rows, uint32_t gl,
                                                                  const uint8_t *__restrict__ slices, const uint32_t *__restrict__ roots,
                                                                  uint8_t *__restrict__ arena, uint8_t *__restrict__ obs,
@@ -3842,26 +3876,29 @@ __global__ __launch_bounds__(B) void b3w_bao_range_ingest_kernel(const RsRange *
     const uint64_t c = b.a0 + ch;
     const uint32_t bytes = range_chunk_bytes(b.len, c);
     const uint8_t *src = sl + 8 + 64ull * before[ch] + 1024 * (c - b.a);
-    uint8_t *dst = data + c * 1024;
+    uint8_t *dst;
+    if constexpr (PACKED) dst = data + (c - b.a) * 1024; else dst = data + c * 1024;
     if (q + 16 <= bytes) put16(dst + q, src + q);
     else for (uint32_t o = q; o < bytes; ++o) dst[o] = src[o];
   }
-  for (uint32_t l = 0; (1u << l) < b.m; ++l) {             // the stored nodes with a verified chunk below them
-    lds_barrier();
-    const uint32_t i0 = (2 * t) << l, i1 = i0 + (1u << l);
-    if (i1 >= b.m || !(listed[i0] | listed[i1])) continue;
-    const uint32_t end = i0 + (2u << l), size = (end < b.m ? end : b.m) - i0;
-    uint8_t *node = node_at<true>(ob + 8, b.n, b.a0 + i0, size, gl);
-    if (node) copy_node(node, sl + range_block_node_at(b, before, i0, size));
-    listed[i0] = 1;
-  }
-  lds_barrier();
-  if (listed[0]) {
-    if (t < up.depth) {
-      uint8_t *node = node_at<true>(ob + 8, b.n, up.lo, up.cnt, gl);
-      if (node) copy_node(node, sl + range_node_at(b.n, b.a, up.lo, up.cnt));
+  if (!PACKED || obs) {
+    for (uint32_t l = 0; (1u << l) < b.m; ++l) {             // the stored nodes with a verified chunk below them
+      lds_barrier();
+      const uint32_t i0 = (2 * t) << l, i1 = i0 + (1u << l);
+      if (i1 >= b.m || !(listed[i0] | listed[i1])) continue;
+      const uint32_t end = i0 + (2u << l), size = (end < b.m ? end : b.m) - i0;
+      uint8_t *node = node_at<true>(ob + 8, b.n, b.a0 + i0, size, gl);
+      if (node) copy_node(node, sl + range_block_node_at(b, before, i0, size));
+      listed[i0] = 1;
     }
-    if (t == 0) *reinterpret_cast<uint2 *>(ob) = hd;       // the header (it is the length: just checked)
+    lds_barrier();
+    if (listed[0]) {
+      if (t < up.depth) {
+        uint8_t *node = node_at<true>(ob + 8, b.n, up.lo, up.cnt, gl);
+        if (node) copy_node(node, sl + range_node_at(b.n, b.a, up.lo, up.cnt));
+      }
+      if (t == 0) *reinterpret_cast<uint2 *>(ob) = hd;       // the header (it is the length: just checked)
+    }
   }
   if (have) {                                              // a wave's lanes are the chunks of one word (a block starts at a multiple of 64)
     const unsigned long long mask = __ballot(ok);
@@ -4087,6 +4124,52 @@ int32_t range_table(b3w_ctx *ctx, const uint64_t *host_offsets, const uint64_t *
                             [&](uint32_t, uint32_t f) { return host_offsets[f]; }, [](uint32_t i, uint64_t blk, uint64_t) { return RsRow{i, (uint32_t)blk}; });
 }
 
+// b3w_bao_range_slice_ingest_device, and PACKED: b3w_bao_range_slice_ingest_packed_device - (d_arena, arena_bytes) its slot buffer, no
+// offsets, d_outboards may be null; a range's `off` is the place of its first slot, 1 024 bytes times the running sum of the counts
+template <bool PACKED>
+int32_t range_slice_ingest(b3w_ctx *ctx, uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens, uint32_t n_files,
+                           uint32_t group_log, uint8_t *d_outboards, const uint32_t *d_roots, const uint32_t *host_files, const uint64_t *host_first,
+                           const uint64_t *host_count, uint32_t n_ranges, const uint8_t *d_slices, int32_t *d_range_status, uint64_t *d_range_first_bad,
+                           uint64_t *d_have, void *d_scratch, uint64_t scratch_bytes, void *stream) {
+  const char *call = PACKED ? "bao range slice ingest packed" : "bao range slice ingest";
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  B3W_TRY(group_log_ok(ctx, call, group_log));
+  if ((uintptr_t)d_have & 7) return refuse(ctx, call, "d_have is not 8-byte aligned");
+  if (!n_ranges) return B3W_OK;
+  if ((!PACKED && (!host_offsets || !d_outboards)) || !host_lens || !d_roots || !host_files || !host_first || !host_count || !d_slices || !d_range_status || !d_range_first_bad) return refuse(ctx, call, "a null pointer");
+  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) return refuse(ctx, call, "d_outboards is not 8-byte or d_slices not 16-byte aligned");
+  if (((uintptr_t)d_range_status & 3) || ((uintptr_t)d_range_first_bad & 7)) return refuse(ctx, call, "d_range_status is not 4-byte or d_range_first_bad not 8-byte aligned");
+  RangeRows rows;
+  B3W_TRY(range_list_ok(ctx, call, d_arena, arena_bytes, host_offsets, host_lens, n_files, host_files, host_first, host_count, n_ranges, rows));
+  if (PACKED) B3W_TRY(slots_ok(ctx, call, d_arena, arena_bytes, b3w_int_listed_chunks(host_count, n_ranges)));
+  if (scratch_bytes < (rows.big + rows.small) * 16) return refuse(ctx, call, "the scratch is smaller than b3w_bao_range_slice_ingest_scratch_bytes says");
+  if (!d_scratch || ((uintptr_t)d_scratch & 15)) return refuse(ctx, call, "the scratch is null or not 16-byte aligned");
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  const RsRange *d_ranges = nullptr;
+  const RsRow *d_big = nullptr, *d_small = nullptr;
+  uint64_t next_slot = 0;
+  B3W_TRY(range_table<RsRow>(ctx, host_lens, n_files, group_log, host_files, host_first, host_count, n_ranges, rows, st, d_ranges, d_big, d_small,
+                             [&](uint32_t i, uint32_t f) {
+                               if (!PACKED) return host_offsets[f];
+                               const uint64_t slot = next_slot;
+                               next_slot += host_count[i];
+                               return 1024 * slot;
+                             },
+                             [](uint32_t i, uint64_t blk, uint64_t) { return RsRow{i, (uint32_t)blk}; }));
+  uint4 *res = reinterpret_cast<uint4 *>(d_scratch);
+  unsigned long long *have = reinterpret_cast<unsigned long long *>(d_have);
+  if (rows.big)
+    hipLaunchKernelGGL((b3w_bao_range_ingest_kernel<(int)B3W_TILE, PACKED>), dim3((uint32_t)rows.big), dim3(B3W_TILE), 0, st, d_ranges, d_big, group_log, d_slices, d_roots,
+                       d_arena, d_outboards, have, res);
+  if (rows.small)
+    hipLaunchKernelGGL((b3w_bao_range_ingest_kernel<64, PACKED>), dim3((uint32_t)rows.small), dim3(64), 0, st, d_ranges, d_small, group_log, d_slices, d_roots, d_arena,
+                       d_outboards, have, res + rows.big);
+  hipLaunchKernelGGL(b3w_bao_range_reduce_kernel, dim3((n_ranges + 3) / 4), dim3(256), 0, st, d_ranges, n_ranges, res, d_range_status,
+                     reinterpret_cast<unsigned long long *>(d_range_first_bad));
+  return batch_launched(ctx, st, PACKED ? "bao range slice ingest packed launch" : "bao range slice ingest launch");
+}
+
 }  // namespace
 
 extern "C" {
@@ -4148,34 +4231,17 @@ int32_t b3w_bao_range_slice_ingest_device(b3w_ctx *ctx, uint8_t *d_arena, uint64
                                           const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, const uint8_t *d_slices,
                                           int32_t *d_range_status, uint64_t *d_range_first_bad, uint64_t *d_have, void *d_scratch, uint64_t scratch_bytes,
                                           void *stream) {
-  const char *call = "bao range slice ingest";
-  if (!ctx) return B3W_E_BAD_ARGUMENT;
-  B3W_TRY(group_log_ok(ctx, call, group_log));
-  if ((uintptr_t)d_have & 7) return refuse(ctx, call, "d_have is not 8-byte aligned");
-  if (!n_ranges) return B3W_OK;
-  if (!host_offsets || !host_lens || !d_outboards || !d_roots || !host_files || !host_first || !host_count || !d_slices || !d_range_status || !d_range_first_bad) return refuse(ctx, call, "a null pointer");
-  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) return refuse(ctx, call, "d_outboards is not 8-byte or d_slices not 16-byte aligned");
-  if (((uintptr_t)d_range_status & 3) || ((uintptr_t)d_range_first_bad & 7)) return refuse(ctx, call, "d_range_status is not 4-byte or d_range_first_bad not 8-byte aligned");
-  RangeRows rows;
-  B3W_TRY(range_list_ok(ctx, call, d_arena, arena_bytes, host_offsets, host_lens, n_files, host_files, host_first, host_count, n_ranges, rows));
-  if (scratch_bytes < (rows.big + rows.small) * 16) return refuse(ctx, call, "the scratch is smaller than b3w_bao_range_slice_ingest_scratch_bytes says");
-  if (!d_scratch || ((uintptr_t)d_scratch & 15)) return refuse(ctx, call, "the scratch is null or not 16-byte aligned");
-  ON_DEVICE(ctx);
-  hipStream_t st = (hipStream_t)stream;
-  const RsRange *d_ranges = nullptr;
-  const RsRow *d_big = nullptr, *d_small = nullptr;
-  B3W_TRY(range_table(ctx, host_offsets, host_lens, n_files, group_log, host_files, host_first, host_count, n_ranges, rows, st, d_ranges, d_big, d_small));
-  uint4 *res = reinterpret_cast<uint4 *>(d_scratch);
-  unsigned long long *have = reinterpret_cast<unsigned long long *>(d_have);
-  if (rows.big)
-    hipLaunchKernelGGL(b3w_bao_range_ingest_kernel<(int)B3W_TILE>, dim3((uint32_t)rows.big), dim3(B3W_TILE), 0, st, d_ranges, d_big, group_log, d_slices, d_roots, d_arena,
-                       d_outboards, have, res);
-  if (rows.small)
-    hipLaunchKernelGGL(b3w_bao_range_ingest_kernel<64>, dim3((uint32_t)rows.small), dim3(64), 0, st, d_ranges, d_small, group_log, d_slices, d_roots, d_arena, d_outboards,
-                       have, res + rows.big);
-  hipLaunchKernelGGL(b3w_bao_range_reduce_kernel, dim3((n_ranges + 3) / 4), dim3(256), 0, st, d_ranges, n_ranges, res, d_range_status,
-                     reinterpret_cast<unsigned long long *>(d_range_first_bad));
-  return batch_launched(ctx, st, "bao range slice ingest launch");
+  return range_slice_ingest<false>(ctx, d_arena, arena_bytes, host_offsets, host_lens, n_files, group_log, d_outboards, d_roots, host_files, host_first, host_count,
+                                   n_ranges, d_slices, d_range_status, d_range_first_bad, d_have, d_scratch, scratch_bytes, stream);
+}
+
+int32_t b3w_bao_range_slice_ingest_packed_device(b3w_ctx *ctx, uint8_t *d_chunks, uint64_t chunks_bytes, const uint64_t *host_lens, uint32_t n_files,
+                                                 uint32_t group_log, uint8_t *d_outboards, const uint32_t *d_roots, const uint32_t *host_files,
+                                                 const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, const uint8_t *d_slices,
+                                                 int32_t *d_range_status, uint64_t *d_range_first_bad, uint64_t *d_have, void *d_scratch,
+                                                 uint64_t scratch_bytes, void *stream) {
+  return range_slice_ingest<true>(ctx, d_chunks, chunks_bytes, nullptr, host_lens, n_files, group_log, d_outboards, d_roots, host_files, host_first, host_count,
+                                  n_ranges, d_slices, d_range_status, d_range_first_bad, d_have, d_scratch, scratch_bytes, stream);
 }
 
 // ---- step records of challenged chunk runs from range slices --------------------------------------------------------------------------
@@ -4418,7 +4484,10 @@ __global__ __launch_bounds__(B) void b3w_bao_set_slice_packed_kernel(const SetDe
 }
 
 // THE RECEIVER (b3w_bao_range_ingest_kernel with the mask for the interval, and a status a wanted chunk)
-template <int B>
+// PACKED (b3w_bao_set_slice_ingest_packed_device): `arena` is a slot buffer, 1 024 bytes a wanted chunk in the order of chunk_status:
+// the copy loop's lane group p >> 6 is the wanted lane's rank in the row, so its slot is r.chunk_first + row->rank0 + (p >> 6); `obs`
+// may be null: no node and no header is stored (decode).
+template <int B, bool PACKED = false>
 __global__ __launch_bounds__(B) void b3w_bao_set_ingest_kernel(const SetDev *__restrict__ sets, const SetRow<B> *__restrict__ rows, uint32_t gl,
                                                                const uint8_t *__restrict__ slices, const uint32_t *__restrict__ roots,
                                                                uint8_t *__restrict__ arena, uint8_t *__restrict__ obs, int32_t *__restrict__ chunk_status,
@@ -4494,26 +4563,29 @@ __global__ __launch_bounds__(B) void b3w_bao_set_ingest_kernel(const SetDev *__r
     const uint64_t c = a0 + ch;
     const uint32_t bytes = range_chunk_bytes(r.len, c);
     const uint8_t *src = sl + row->place0 + s.rel[ch];
-    uint8_t *dst = data + c * 1024;
+    uint8_t *dst;
+    if constexpr (PACKED) dst = arena + (r.chunk_first + row->rank0 + (p >> 6)) * 1024; else dst = data + c * 1024;
     if (q + 16 <= bytes) put16(dst + q, src + q);
     else for (uint32_t o = q; o < bytes; ++o) dst[o] = src[o];
   }
-  for (uint32_t l = 0; (1u << l) < m; ++l) {               // the stored nodes with a verified chunk below them
-    lds_barrier();
-    const uint32_t i0 = (2 * t) << l, i1 = i0 + (1u << l);
-    if (i1 >= m || !(listed[i0] | listed[i1])) continue;
-    const uint32_t end = i0 + (2u << l), size = (end < m ? end : m) - i0;
-    uint8_t *node = node_at<true>(ob + 8, n, a0 + i0, size, gl);
-    if (node) copy_node(node, sl + set_block_node_at<B>(row, s, i0, size));
-    listed[i0] = 1;
-  }
-  lds_barrier();
-  if (listed[0]) {                                         // (every row with a verified chunk stores the nodes above it: the same verified bytes)
-    if (t < up.depth) {
-      uint8_t *node = node_at<true>(ob + 8, n, up.lo, up.cnt, gl);
-      if (node) copy_node(node, sl + row->up[t]);
+  if (!PACKED || obs) {
+    for (uint32_t l = 0; (1u << l) < m; ++l) {               // the stored nodes with a verified chunk below them
+      lds_barrier();
+      const uint32_t i0 = (2 * t) << l, i1 = i0 + (1u << l);
+      if (i1 >= m || !(listed[i0] | listed[i1])) continue;
+      const uint32_t end = i0 + (2u << l), size = (end < m ? end : m) - i0;
+      uint8_t *node = node_at<true>(ob + 8, n, a0 + i0, size, gl);
+      if (node) copy_node(node, sl + set_block_node_at<B>(row, s, i0, size));
+      listed[i0] = 1;
     }
-    if (t == 0) *reinterpret_cast<uint2 *>(ob) = hd;       // the header (it is the length: just checked)
+    lds_barrier();
+    if (listed[0]) {                                         // (every row with a verified chunk stores the nodes above it: the same verified bytes)
+      if (t < up.depth) {
+        uint8_t *node = node_at<true>(ob + 8, n, up.lo, up.cnt, gl);
+        if (node) copy_node(node, sl + row->up[t]);
+      }
+      if (t == 0) *reinterpret_cast<uint2 *>(ob) = hd;       // the header (it is the length: just checked)
+    }
   }
   if (have) {                                              // a wave's lanes are the chunks of one word (a block starts at a multiple of 64)
     const unsigned long long mask = __ballot(ok);
@@ -4765,7 +4837,47 @@ int32_t set_table(b3w_ctx *ctx, const uint64_t *host_offsets, const uint64_t *ho
                   const SetRow<64> *&d_small) {
   const uint64_t *none = nullptr;
   return set_table<false>(ctx, host_lens, n_files, group_log, host_first, host_count, list, st, d_sets, d_big, d_small, none,
-                          [&](uint32_t f) { return host_offsets[f]; }, [](uint64_t, uint64_t, uint64_t) { return 0ull; });
+                          [&](uint32_t f) { return host_offsets ? host_offsets[f] : 0; }, [](uint64_t, uint64_t, uint64_t) { return 0ull; });
+}
+
+// b3w_bao_set_slice_ingest_device, and PACKED: b3w_bao_set_slice_ingest_packed_device - (d_arena, arena_bytes) its slot buffer, no
+// offsets, d_outboards may be null; the table is the arena call's (a set's `off` 0): the kernel finds a slot from chunk_first and rank0
+template <bool PACKED>
+int32_t set_slice_ingest(b3w_ctx *ctx, uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *host_offsets, const uint64_t *host_lens, uint32_t n_files,
+                         uint32_t group_log, uint8_t *d_outboards, const uint32_t *d_roots, const uint32_t *host_files, const uint64_t *host_first,
+                         const uint64_t *host_count, uint32_t n_ranges, const uint8_t *d_slices, int32_t *d_set_status, uint64_t *d_set_first_bad,
+                         int32_t *d_chunk_status, uint64_t *d_have, void *d_scratch, uint64_t scratch_bytes, void *stream) {
+  const char *call = PACKED ? "bao set slice ingest packed" : "bao set slice ingest";
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  B3W_TRY(group_log_ok(ctx, call, group_log));
+  if (((uintptr_t)d_have & 7) || ((uintptr_t)d_chunk_status & 3)) return refuse(ctx, call, "d_have is not 8-byte or d_chunk_status not 4-byte aligned");
+  if (!n_ranges) return B3W_OK;
+  if ((!PACKED && (!host_offsets || !d_outboards)) || !host_lens || !d_roots || !host_files || !host_first || !host_count || !d_slices || !d_set_status || !d_set_first_bad) return refuse(ctx, call, "a null pointer");
+  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) return refuse(ctx, call, "d_outboards is not 8-byte or d_slices not 16-byte aligned");
+  if (((uintptr_t)d_set_status & 3) || ((uintptr_t)d_set_first_bad & 7)) return refuse(ctx, call, "d_set_status is not 4-byte or d_set_first_bad not 8-byte aligned");
+  SetList list;
+  B3W_TRY(set_list_ok(ctx, call, d_arena, arena_bytes, host_offsets, host_lens, n_files, host_files, host_first, host_count, n_ranges, list));
+  if (PACKED) B3W_TRY(slots_ok(ctx, call, d_arena, arena_bytes, list.chunks));
+  if (scratch_bytes < (list.big + list.small) * 16) return refuse(ctx, call, "the scratch is smaller than b3w_bao_set_slice_ingest_scratch_bytes says");
+  if (!d_scratch || ((uintptr_t)d_scratch & 15)) return refuse(ctx, call, "the scratch is null or not 16-byte aligned");
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  const SetDev *d_sets = nullptr;
+  const SetRow<(int)B3W_TILE> *d_big = nullptr;
+  const SetRow<64> *d_small = nullptr;
+  B3W_TRY(set_table(ctx, host_offsets, host_lens, n_files, group_log, host_first, host_count, list, st, d_sets, d_big, d_small));
+  uint4 *res = reinterpret_cast<uint4 *>(d_scratch);
+  unsigned long long *have = reinterpret_cast<unsigned long long *>(d_have);
+  const uint32_t n_sets = (uint32_t)list.sets.size();
+  if (list.big)
+    hipLaunchKernelGGL((b3w_bao_set_ingest_kernel<(int)B3W_TILE, PACKED>), dim3((uint32_t)list.big), dim3(B3W_TILE), 0, st, d_sets, d_big, group_log, d_slices, d_roots, d_arena,
+                       d_outboards, d_chunk_status, have, res);
+  if (list.small)
+    hipLaunchKernelGGL((b3w_bao_set_ingest_kernel<64, PACKED>), dim3((uint32_t)list.small), dim3(64), 0, st, d_sets, d_small, group_log, d_slices, d_roots, d_arena, d_outboards,
+                       d_chunk_status, have, res + list.big);
+  hipLaunchKernelGGL(b3w_bao_set_reduce_kernel, dim3((n_sets + 3) / 4), dim3(256), 0, st, d_sets, n_sets, res, d_set_status,
+                     reinterpret_cast<unsigned long long *>(d_set_first_bad));
+  return batch_launched(ctx, st, PACKED ? "bao set slice ingest packed launch" : "bao set slice ingest launch");
 }
 
 }  // namespace
@@ -4799,36 +4911,17 @@ int32_t b3w_bao_set_slice_ingest_device(b3w_ctx *ctx, uint8_t *d_arena, uint64_t
                                         const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, const uint8_t *d_slices,
                                         int32_t *d_set_status, uint64_t *d_set_first_bad, int32_t *d_chunk_status, uint64_t *d_have, void *d_scratch,
                                         uint64_t scratch_bytes, void *stream) {
-  const char *call = "bao set slice ingest";
-  if (!ctx) return B3W_E_BAD_ARGUMENT;
-  B3W_TRY(group_log_ok(ctx, call, group_log));
-  if (((uintptr_t)d_have & 7) || ((uintptr_t)d_chunk_status & 3)) return refuse(ctx, call, "d_have is not 8-byte or d_chunk_status not 4-byte aligned");
-  if (!n_ranges) return B3W_OK;
-  if (!host_offsets || !host_lens || !d_outboards || !d_roots || !host_files || !host_first || !host_count || !d_slices || !d_set_status || !d_set_first_bad) return refuse(ctx, call, "a null pointer");
-  if (((uintptr_t)d_outboards & 7) || ((uintptr_t)d_slices & 15)) return refuse(ctx, call, "d_outboards is not 8-byte or d_slices not 16-byte aligned");
-  if (((uintptr_t)d_set_status & 3) || ((uintptr_t)d_set_first_bad & 7)) return refuse(ctx, call, "d_set_status is not 4-byte or d_set_first_bad not 8-byte aligned");
-  SetList list;
-  B3W_TRY(set_list_ok(ctx, call, d_arena, arena_bytes, host_offsets, host_lens, n_files, host_files, host_first, host_count, n_ranges, list));
-  if (scratch_bytes < (list.big + list.small) * 16) return refuse(ctx, call, "the scratch is smaller than b3w_bao_set_slice_ingest_scratch_bytes says");
-  if (!d_scratch || ((uintptr_t)d_scratch & 15)) return refuse(ctx, call, "the scratch is null or not 16-byte aligned");
-  ON_DEVICE(ctx);
-  hipStream_t st = (hipStream_t)stream;
-  const SetDev *d_sets = nullptr;
-  const SetRow<(int)B3W_TILE> *d_big = nullptr;
-  const SetRow<64> *d_small = nullptr;
-  B3W_TRY(set_table(ctx, host_offsets, host_lens, n_files, group_log, host_first, host_count, list, st, d_sets, d_big, d_small));
-  uint4 *res = reinterpret_cast<uint4 *>(d_scratch);
-  unsigned long long *have = reinterpret_cast<unsigned long long *>(d_have);
-  const uint32_t n_sets = (uint32_t)list.sets.size();
-  if (list.big)
-    hipLaunchKernelGGL(b3w_bao_set_ingest_kernel<(int)B3W_TILE>, dim3((uint32_t)list.big), dim3(B3W_TILE), 0, st, d_sets, d_big, group_log, d_slices, d_roots, d_arena,
-                       d_outboards, d_chunk_status, have, res);
-  if (list.small)
-    hipLaunchKernelGGL(b3w_bao_set_ingest_kernel<64>, dim3((uint32_t)list.small), dim3(64), 0, st, d_sets, d_small, group_log, d_slices, d_roots, d_arena, d_outboards,
-                       d_chunk_status, have, res + list.big);
-  hipLaunchKernelGGL(b3w_bao_set_reduce_kernel, dim3((n_sets + 3) / 4), dim3(256), 0, st, d_sets, n_sets, res, d_set_status,
-                     reinterpret_cast<unsigned long long *>(d_set_first_bad));
-  return batch_launched(ctx, st, "bao set slice ingest launch");
+  return set_slice_ingest<false>(ctx, d_arena, arena_bytes, host_offsets, host_lens, n_files, group_log, d_outboards, d_roots, host_files, host_first, host_count,
+                                 n_ranges, d_slices, d_set_status, d_set_first_bad, d_chunk_status, d_have, d_scratch, scratch_bytes, stream);
+}
+
+int32_t b3w_bao_set_slice_ingest_packed_device(b3w_ctx *ctx, uint8_t *d_chunks, uint64_t chunks_bytes, const uint64_t *host_lens, uint32_t n_files,
+                                               uint32_t group_log, uint8_t *d_outboards, const uint32_t *d_roots, const uint32_t *host_files,
+                                               const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, const uint8_t *d_slices,
+                                               int32_t *d_set_status, uint64_t *d_set_first_bad, int32_t *d_chunk_status, uint64_t *d_have,
+                                               void *d_scratch, uint64_t scratch_bytes, void *stream) {
+  return set_slice_ingest<true>(ctx, d_chunks, chunks_bytes, nullptr, host_lens, n_files, group_log, d_outboards, d_roots, host_files, host_first, host_count,
+                                n_ranges, d_slices, d_set_status, d_set_first_bad, d_chunk_status, d_have, d_scratch, scratch_bytes, stream);
 }
 
 // the arena call's table and grids; a row's slot (beside the table) is that of its block's first listed chunk in the packed buffer

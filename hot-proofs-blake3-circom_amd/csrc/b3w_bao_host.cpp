@@ -428,6 +428,25 @@ uint64_t b3w_int_set_row_slot(const PkLayout &pk, uint32_t file, uint64_t len, u
   return pk.slot_of(file, cf & ~((1ull << gl) - 1));
 }
 
+// ---- the slot buffer of the packed receivers --------------------------------------------------------------------------------------------
+uint64_t b3w_int_listed_chunks(const uint64_t *count, uint32_t n_ranges) {
+  uint64_t sum = 0;
+  for (uint32_t i = 0; i < n_ranges; ++i) {
+    if (count[i] > ~0ull - sum) return ~0ull;
+    sum += count[i];
+  }
+  return sum;
+}
+
+std::string b3w_int_slots_wrong(const void *d_chunks, uint64_t chunks_bytes, uint64_t listed) {
+  if (listed > (~0ull >> 10)) return "the listed chunks' slots do not fit 64 bits of bytes";
+  const std::string need = std::to_string(1024 * listed) + " bytes (1024 a listed chunk, " + std::to_string(listed) + " chunks)";
+  if (listed && !d_chunks) return "a null d_chunks with a list that needs " + need;
+  if ((uintptr_t)d_chunks & 15) return "d_chunks is not 16-byte aligned";
+  if (chunks_bytes < 1024 * listed) return "chunks_bytes is " + std::to_string(chunks_bytes) + ", the slots take " + need;
+  return std::string();
+}
+
 extern "C" {
 
 // ---- sizes and layouts ----------------------------------------------------------------------------------------------------------------

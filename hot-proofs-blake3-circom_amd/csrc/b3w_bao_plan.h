@@ -60,3 +60,12 @@ void b3w_int_packed_range(uint64_t len, uint32_t gl, uint64_t a, uint64_t c, uin
 // block's first wanted chunk; the block's listed chunks follow it slot by slot
 uint64_t b3w_int_set_row_slot(const PkLayout &pk, uint32_t file, uint64_t len, uint32_t gl, const uint64_t *first, const uint64_t *count, uint64_t k,
                               uint64_t a0);
+
+// The slot buffer of the packed RECEIVERS (b3wit.h "slices taken into packed chunk slots"): 1 024 bytes a listed chunk, in the order of
+// the per-chunk statuses - sample i at slot i; range r's chunk c at slot chunk_first[r] + (c - first[r]), chunk_first the running sum of
+// the counts; set s's wanted chunk of rank k at slot set_chunk_first[s] + k (SetEnt::chunk_first).
+// the chunks a range list lists: the sum of the counts, UINT64_MAX where that does not fit
+uint64_t b3w_int_listed_chunks(const uint64_t *count, uint32_t n_ranges);
+// empty, or why a call over `listed` chunks refuses (d_chunks, chunks_bytes): null with a list that is not empty, not 16-byte aligned,
+// too few bytes (the message names the bytes needed)
+std::string b3w_int_slots_wrong(const void *d_chunks, uint64_t chunks_bytes, uint64_t listed);

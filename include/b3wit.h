@@ -1353,6 +1353,60 @@ int32_t b3w_bao_set_slice_packed_device(b3w_ctx *ctx, const uint8_t *d_packed, u
                                         const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, uint8_t *d_slices,
                                         void *stream);
 
+/* ---- slices taken into packed chunk slots: the receiver's side for files that are not resident (still ABI 1.4: new names only) ---
+ * The three receivers above write a chunk at d_arena + host_offsets[f] + 1024 c, so a node that fetches the missing half of a 1 GiB file
+ * holds the whole GiB on the device to take in 537 MB, and a client that only wants verified bytes (bao's decode) has no device route.
+ * These calls take their arena twin's arguments with a SLOT BUFFER (d_chunks, chunks_bytes) in place of (d_arena, arena_bytes,
+ * host_offsets): one slot of 1 024 bytes per listed chunk, in the order of the per-chunk statuses.
+ * SEMANTICS, BY PROJECTION.  Every status - per chunk / sample, per range / set, first bad - is what the arena twin reports for the
+ * same slices, roots, list and group_log.  A chunk of status 0 gets its min(1024, len - 1024 c) bytes at d_chunks + 1024 slot; the
+ * rest of a short last chunk's slot is not written; a chunk of any other status has its whole slot left alone: nothing unverified is
+ * written.  The slot of a chunk:
+ *   one-chunk slices   slot = i, the sample's index (repeated samples each have their own slot);
+ *   range slices       slot = chunk_first[r] + (c - first[r]), chunk_first the running sum of the counts (the index of
+ *                      b3w_sample_plan_range_slices_device's d_chunk_status; overlapping ranges each list their own slots);
+ *   set slices         slot = set_chunk_first[s] + rank_S(c): d_chunk_status's index, the device form of b3w_bao_set_slice_decode's
+ *                      out_bytes.
+ * d_outboards != NULL: the header and the stored nodes of every verified chunk's path at this group_log go to their pre-order places,
+ * byte for byte what the arena twin writes, and every other byte stays.  d_outboards == NULL: nothing but slots, statuses and the
+ * optional bitmap is written - DECODE on the device.  d_have (may be NULL in all three) gets the arena calls' bits.
+ * The same launches as the twins (1, <= 3, <= 3), the same table through the context's staging, the same scratch size calls; nothing
+ * is allocated; asynchronous on `stream`.  d_chunks, d_outboards and d_slices must not overlap (not checked).  REFUSALS ARE ATOMIC
+ * (B3W_E_BAD_ARGUMENT before anything is launched or written; b3w_last_error says what was wrong): what the twin refuses without the
+ * arena items and without the null d_outboards, a null d_chunks with a list that is not empty, a d_chunks that is not 16-byte
+ * aligned, chunks_bytes < 1024 x the listed chunks (the message says how many bytes are needed).  An empty list is a no-op.
+ * WHEN NOT TO (MI355X, one 1 GiB file; the yardstick is the parent commit's arena receiver over the same slices into a
+ * resident arena, the slots compared with the arena's chunks one by one before timing; device events round whole calls, alternating
+ * medians; no profiler run): the packed calls read and write the same bytes as
+ * their twins and their stores are denser, and they land at or just below them - the 262 507 runs of a half-missing bitmap as set slices
+ * 3.34 ms against 3.41 (the yardstick's spread 0.001), 65 536 runs of ONE chunk 1.457 against 1.515 as one-chunk slices (0.0004) and 1.242
+ * against 1.261 as set slices (0.0008), 4 096 runs of 16 as range slices 0.395 against 0.400 (0.0009).  LONG RUNS GAIN NOTHING AND LOSE A
+ * HAIR: 64 runs of 1 024 chunks as range slices 0.2120 against 0.2113, 0.3 % and more than the spread of 0.00002 (cause not found: the
+ * kernels take the same registers as their twins - 66 to 73 VGPRs the one-chunk kernel, 53 / 54 the range kernels, 76 / 60 the set kernels -
+ * and the host does the same work); at group_log 4 0.1984 against 0.1985, inside the spread of 0.00004.  With d_outboards null the same
+ * calls take 3.21, 1.415, 1.123, 0.357 and 0.176 ms.  What the calls save is the memory: 536 MB of slots where the arena receiver needs
+ * the 1 GiB file resident for the half-missing shape (538 MB less), 67 MB against 1 GiB for 65 536 chunks.  So: a file that IS resident
+ * keeps the arena calls (the chunks are then where every other call reads them); the choice between the three slice kinds is the arena
+ * calls' (set slices for many short runs, range slices for a few long ones).  Not measured: the copy of the slots to the host and
+ * bao.scatter_chunks, files past 1 GiB, many files a call, the kernels one by one.  Not tested on the device: slots past 2^32 bytes
+ * (the slot arithmetic is 64 bits wide; tools/bao_receive_packed_host_check.cpp holds the host side of it). */
+int32_t b3w_bao_slice_ingest_packed_device(b3w_ctx *ctx, uint8_t *d_chunks, uint64_t chunks_bytes, const uint64_t *host_lens, uint32_t n_files,
+                                           uint32_t group_log, uint8_t *d_outboards /* may be NULL */, const uint32_t *d_roots,
+                                           const uint32_t *host_files, const uint64_t *host_chunks, uint32_t n_samples, const uint8_t *d_slices,
+                                           int32_t *d_sample_status, uint64_t *d_have /* may be NULL */, void *stream);
+int32_t b3w_bao_range_slice_ingest_packed_device(b3w_ctx *ctx, uint8_t *d_chunks, uint64_t chunks_bytes, const uint64_t *host_lens, uint32_t n_files,
+                                                 uint32_t group_log, uint8_t *d_outboards /* may be NULL */, const uint32_t *d_roots,
+                                                 const uint32_t *host_files, const uint64_t *host_first, const uint64_t *host_count,
+                                                 uint32_t n_ranges, const uint8_t *d_slices, int32_t *d_range_status,
+                                                 uint64_t *d_range_first_bad, uint64_t *d_have /* may be NULL */, void *d_scratch,
+                                                 uint64_t scratch_bytes, void *stream);
+int32_t b3w_bao_set_slice_ingest_packed_device(b3w_ctx *ctx, uint8_t *d_chunks, uint64_t chunks_bytes, const uint64_t *host_lens, uint32_t n_files,
+                                               uint32_t group_log, uint8_t *d_outboards /* may be NULL */, const uint32_t *d_roots,
+                                               const uint32_t *host_files, const uint64_t *host_first, const uint64_t *host_count,
+                                               uint32_t n_ranges, const uint8_t *d_slices, int32_t *d_set_status, uint64_t *d_set_first_bad,
+                                               int32_t *d_chunk_status /* may be NULL */, uint64_t *d_have /* may be NULL */, void *d_scratch,
+                                               uint64_t scratch_bytes, void *stream);
+
 /* ---- updates in place after writes to resident files (still ABI 1.4: new names only) --------------------------------
  * Every call above treats a file as immutable: after one rewritten block the only way to a correct outboard and root is the batch
  * call over the whole file again.  These calls make the cost follow the bytes written.  GIVEN an arena with its offsets and
