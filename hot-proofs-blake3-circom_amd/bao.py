@@ -29,6 +29,8 @@ ingest_slices_packed() / ingest_range_slices_packed() / ingest_set_slices_packed
 the verified chunks go to one 1 024-byte slot each, in the order of the statuses (chunk_slots(): where each slot belongs in its file;
 scatter_chunks(): the verified slots written there after the copy to the host), with the arena receivers' statuses, outboards and
 bitmap - or, with d_outboards=None, nothing but the verified bytes: bao's decode on the device.
+outboard_diff() names the chunks two versions of a file share from their outboards alone, as a bitmap in the arrival bitmap's layout:
+a replica with a stale copy fetches only what have_runs() then lists as missing (diff_host(): one pair on the host).
 The records are
 word for word those the chain planner writes for the same chunks (ChainPlanner.plan), so every step is the reference's
 prove_chunk_hash step (rust_fold/src/main.rs:41-203 over hash_with_path's slice, rust_fold/src/blake3_hash.rs:17-93)."""
@@ -720,6 +722,98 @@ def runs_chunks(files, first_chunks, n_chunks):
     starts = np.cumsum(cnt) - cnt
     within = np.arange(int(cnt.sum()), dtype=np.int64) - np.repeat(starts, cnt)
     return np.repeat(fi, cnt), (np.repeat(fc, cnt).astype(np.int64) + within).astype(np.uint64)
+
+
+# ---- outboard diff: the chunks two versions of a file share, from their outboards alone -----------------------------------
+def _diff_side(what, side, lens, d_outboards, d_roots, group_log, ob_first):
+    if not 0 <= group_log <= MAX_GROUP_LOG:
+        raise B3WError(100, f"{what}: group_log_{side} {group_log} is not in 0 .. {MAX_GROUP_LOG}")
+    ln = _u64(lens)
+    obf = group_batch_layout(ln, group_log) if ob_first is None else _u64(ob_first)
+    if obf.size < ln.size:
+        raise B3WError(100, f"{what}: {obf.size} outboard places for {ln.size} files of side {side}")
+    if not (isinstance(d_outboards, torch.Tensor) and d_outboards.is_cuda and d_outboards.dtype == torch.uint8 and d_outboards.is_contiguous()):
+        raise B3WError(100, f"{what}: d_outboards_{side} is not a contiguous uint8 CUDA tensor")
+    if not (isinstance(d_roots, torch.Tensor) and d_roots.is_cuda and d_roots.is_contiguous() and d_roots.element_size() == 4 and d_roots.numel() >= ln.size * 8):
+        raise B3WError(100, f"{what}: d_roots_{side} is not a contiguous CUDA tensor of 8 words a file")
+    return ln, obf
+
+
+def outboard_diff(ctx, lens_a, d_outboards_a, d_roots_a, lens_b, d_outboards_b, d_roots_b, pairs_a=None, pairs_b=None, group_log_a=0, group_log_b=0,
+                  ob_first_a=None, ob_first_b=None, d_same=None, stream=0):
+    """Which chunks of version b of a file does a holder of version a already have?  Answered on the device from the two outboards
+    alone: pair i is (file pairs_a[i] of side a, file pairs_b[i] of side b; no lists: file i of both), a side its lengths, its
+    outboards as outboard_batch (group_log 0) / outboard_groups_batch made them (at ob_first, any 8-byte-aligned places; None: the
+    batch layout of its lens) and its roots.  The sides may be the same tensors and a file may be in many pairs.  With
+    G = max(group_log_a, group_log_b) a unit is 2^G chunks (the last one ragged); its CV is stored in its parent's node (the finer
+    outboard read at the coarser level), or is the root where the unit is the whole file, and unit u of b is SAME iff it exists in a,
+    covers the same chunks, is the whole file in both or in neither, and the stored CVs are equal.  Returns dict(same: int64 CUDA, the
+    bitmap in have_layout(pair_lens)'s layout, every word written whole, pad bits zero; word_first: numpy uint64 [n_pairs + 1];
+    pair_lens: numpy uint64, the b lengths of the pairs — what have_runs, have_runs_bound and runs_chunks take as lens, the rows' file
+    column then being the pair index).  A set bit means equal bytes; a clear bit "differs or not known": a chunk with equal bytes is
+    still clear where another chunk of its unit differs or where its unit is the whole file on one side only.  Nothing is hashed and
+    no file byte read; one launch.
+    Sync from a stale replica, EQUAL LENGTHS: diff = outboard_diff(old side, new side); runs = have_runs(ctx, diff["same"],
+    diff["pair_lens"], "missing"); the provider answers set_slices_arena over those runs; the replica calls ingest_set_slices(its own
+    arena, its own OLD outboards, d_roots = the NEW roots, d_have = diff["same"]).  Nodes over unchanged chunks are right already and
+    every node above a changed chunk arrives verified in the slice, so the replica ends with the provider's bytes and outboard byte
+    for byte.  CHANGED LENGTH: first outboard_resize_batch over the replica's arena as it is at the new length (the bytes behind the
+    old end are whatever lies there): an outboard consistent with what the replica holds; then the recipe above against it.
+    When not to (MI355X): the C call never takes less than about 0.02 ms.  One 1 GiB file with 1 % of its chunks rewritten
+    takes 0.033 ms (full outboards; copying the two outboards device to device takes 0.046) or 0.021 (group_log 4), where
+    verify_batch of b's resident bytes against a's outboard followed by have_from_status takes 0.457 and 0.440; 262 144 files of 4
+    chunks take 1.17 ms against 1.99, most of it the host's table (about 4 ns and 40 uploaded bytes a pair).  A caller who already
+    holds b's bytes and must verify them anyway gets the same bitmap from that route, verified: this call verifies nothing and
+    believes both outboards (verify_batch over the finished file is what catches a lying outboard).  This wrapper also makes the
+    layouts and, with d_same=None, the bitmap on every call; a loop that matters keeps them and calls b3w_bao_outboard_diff_device."""
+    what = "outboard_diff"
+    la, ofa = _diff_side(what, "a", lens_a, d_outboards_a, d_roots_a, group_log_a, ob_first_a)
+    lb, ofb = _diff_side(what, "b", lens_b, d_outboards_b, d_roots_b, group_log_b, ob_first_b)
+    if (pairs_a is None) != (pairs_b is None):
+        raise B3WError(100, f"{what}: one pair list without the other")
+    if pairs_a is None:
+        if la.size != lb.size:
+            raise B3WError(100, f"{what}: no pair lists and {la.size} files against {lb.size}")
+        pa = pb = np.arange(la.size, dtype=np.uint32)
+    else:
+        pa = np.ascontiguousarray(np.atleast_1d(pairs_a), dtype=np.uint32)
+        pb = np.ascontiguousarray(np.atleast_1d(pairs_b), dtype=np.uint32)
+        if pa.size != pb.size:
+            raise B3WError(100, f"{what}: {pa.size} files of side a paired with {pb.size} of side b")
+        if pa.size and (int(pa.max()) >= la.size or int(pb.max()) >= lb.size):
+            raise B3WError(100, f"{what}: a pair names a file that is not below its side's file count")
+    pair_lens = lb[pb] if pb.size else np.zeros(0, dtype=np.uint64)
+    word_first = have_layout(pair_lens)
+    if d_same is None:
+        d_same = torch.empty(int(word_first[-1]), dtype=torch.int64, device=d_outboards_b.device)
+    _have_tensor(what, d_same, pair_lens)
+    _chk(ctx, lib().b3w_bao_outboard_diff_device(ctx.handle, la.ctypes.data, ofa.ctypes.data, d_outboards_a.data_ptr(), d_outboards_a.numel(), d_roots_a.data_ptr(),
+                                                 la.size, group_log_a, lb.ctypes.data, ofb.ctypes.data, d_outboards_b.data_ptr(), d_outboards_b.numel(),
+                                                 d_roots_b.data_ptr(), lb.size, group_log_b, pa.ctypes.data, pb.ctypes.data, pa.size, word_first.ctypes.data,
+                                                 d_same.data_ptr(), _stream(stream)), "b3w_bao_outboard_diff_device")
+    return dict(same=d_same, word_first=word_first, pair_lens=pair_lens)
+
+
+def diff_host(outboard_a, len_a, root_a, outboard_b, len_b, root_b, group_log_a=0, group_log_b=0):
+    """outboard_diff for one pair on the host (no GPU): the outboards as bytes (or tensors) of group_outboard_size(len, group_log), the
+    roots as 8 words -> the pair's words (numpy uint64 [ceil(num_chunks(len_b) / 64)])"""
+    sides = []
+    for side, ob, ln, root, g in (("a", outboard_a, len_a, root_a, group_log_a), ("b", outboard_b, len_b, root_b, group_log_b)):
+        if not 0 <= g <= MAX_GROUP_LOG:
+            raise B3WError(100, f"diff_host: group_log_{side} {g} is not in 0 .. {MAX_GROUP_LOG}")
+        if ln < 0:
+            raise B3WError(100, f"diff_host: len_{side} is negative")
+        ob = ob.cpu().numpy().tobytes() if isinstance(ob, torch.Tensor) else bytes(ob)
+        if len(ob) != group_outboard_size(ln, g):
+            raise B3WError(100, f"diff_host: outboard_{side}'s size is not that of a file of len_{side} bytes")
+        rw = np.ascontiguousarray(np.asarray(root.cpu() if isinstance(root, torch.Tensor) else root).reshape(-1).astype(np.uint32))
+        if rw.size != 8:
+            raise B3WError(100, f"diff_host: root_{side} is not 8 words")
+        sides.append((ob, rw))
+    same = np.zeros((num_chunks(len_b) + 63) // 64, dtype=np.uint64)
+    _chk(None, lib().b3w_bao_outboard_diff(sides[0][0], len_a, sides[0][1].ctypes.data, group_log_a, sides[1][0], len_b, sides[1][1].ctypes.data, group_log_b,
+                                           same.ctypes.data), "b3w_bao_outboard_diff")
+    return same
 
 
 # ---- range slices: the slice of a run of chunks, extracted and taken in ---------------------------------------------------

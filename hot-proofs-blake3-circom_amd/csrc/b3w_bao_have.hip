@@ -11,6 +11,8 @@
 //                                the count's place; the set bits of every file counted into d_file_have
 //   b3w_bao_have_sub_kernel      count = (the chunk behind the run) - first, for the rows written
 //   b3w_bao_have_pack_kernel     a bitmap from packed unit statuses, a lane per word, every word written whole
+//   b3w_bao_diff_kernel          a bitmap of the chunks two versions of a file share, from the CVs their outboards store (described
+//                                where it stands), a wave per word, every word written whole
 // No workgroup waits for another: each level of the scan is a launch.
 //
 // The selected mask of a word at chunk granularity: a unit is a field of F = 1 << group_log bits, and for group_log <= 6 no field
@@ -185,6 +187,55 @@ __global__ __launch_bounds__(256) void b3w_bao_have_pack_kernel(const uint8_t *_
   have[w] = bits & have_valid(i, n);
 }
 
+// ---- the chunks two versions of a file share, from their outboards alone (b3wit.h "outboard diff") ---------------------------------
+// A wave is a word of the bitmap and a lane a chunk of it.  A unit is 2^G chunks, G the larger of the two group_logs, so a word holds
+// whole units: the lane of a unit's first chunk finds where each outboard stores the unit's CV (diff_cv_at: a half of its parent's
+// node, read at the coarser level in the finer outboard; the root where the unit is the whole file) and compares the 32 bytes, the
+// ballot is the word at the units' lowest bits, one multiplication fills the fields as have_selected does, lane 0 stores the word
+// whole.  The pair of a word is found in SGPRs (the wave index is made uniform).  Nothing is hashed; a half node is 8-byte aligned and
+// a root 4-byte, and no load assumes more.
+// the staging: word_first [n_pairs + 1], then four words a pair: chunk counts (a low, b high), a's and b's outboard's first byte, the
+// files (a low, b high)
+constexpr uint32_t DIFF_WG = 256;
+
+__device__ __forceinline__ bool cv_equal(const uint8_t *a, const uint8_t *b, bool roots) {
+  if (roots) {
+    const uint32_t *x = reinterpret_cast<const uint32_t *>(a), *y = reinterpret_cast<const uint32_t *>(b);
+    uint32_t d = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) d |= x[k] ^ y[k];
+    return d == 0;
+  }
+  const uint64_t *x = reinterpret_cast<const uint64_t *>(a), *y = reinterpret_cast<const uint64_t *>(b);
+  uint64_t d = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) d |= x[k] ^ y[k];
+  return d == 0;
+}
+
+__global__ __launch_bounds__(DIFF_WG) void b3w_bao_diff_kernel(const uint64_t *__restrict__ tab, uint32_t n_pairs, uint64_t n_words, const uint8_t *obs_a,
+                                                               const uint32_t *roots_a, uint32_t gl_a, const uint8_t *obs_b, const uint32_t *roots_b,
+                                                               uint32_t gl_b, uint64_t *__restrict__ same) {
+  const uint64_t w = (uint64_t)blockIdx.x * (DIFF_WG / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (w >= n_words) return;
+  const uint32_t lane = threadIdx.x & 63, G = gl_a > gl_b ? gl_a : gl_b, F = 1u << G;
+  const uint32_t p = have_file_of(tab, n_pairs, w);
+  const uint64_t *rec = tab + (uint64_t)n_pairs + 1 + 4ull * p;
+  const uint64_t i = w - tab[p], c = i * 64 + lane;
+  const uint32_t na = (uint32_t)rec[0], nb = (uint32_t)(rec[0] >> 32);
+  bool eq = false;
+  if (c < nb && !(lane & (F - 1)) && diff_unit_comparable(na, nb, (uint32_t)(c >> G), G)) {
+    const uint32_t u = (uint32_t)(c >> G);
+    const bool whole = nb <= F;
+    const uint8_t *cv_a = whole ? reinterpret_cast<const uint8_t *>(roots_a + 8ull * (uint32_t)rec[3]) : obs_a + rec[1] + diff_cv_at(na, gl_a, u, G);
+    const uint8_t *cv_b = whole ? reinterpret_cast<const uint8_t *>(roots_b + 8ull * (uint32_t)(rec[3] >> 32)) : obs_b + rec[2] + diff_cv_at(nb, gl_b, u, G);
+    eq = cv_equal(cv_a, cv_b, whole);
+  }
+  const uint64_t low = __ballot(eq);
+  const uint64_t bits = G == 6 ? 0ull - (low & 1) : low * ((1ull << F) - 1);
+  if (lane == 0) same[w] = bits & have_valid(i, nb);
+}
+
 // the tables into the staging and on their way to the device -> their device addresses
 int32_t have_tables(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, bool units, uint32_t group_log, hipStream_t st, const uint64_t *&t) {
   const uint64_t words = (uint64_t)n_files * (units ? 3 : 2) + 1;
@@ -270,6 +321,59 @@ int32_t b3w_bao_have_from_status_device(b3w_ctx *ctx, const uint8_t *d_unit_stat
   B3W_TRY(have_tables(ctx, host_lens, n_files, true, group_log, st, t));
   hipLaunchKernelGGL(b3w_bao_have_pack_kernel, dim3((uint32_t)((n_words + 255) / 256)), dim3(256), 0, st, d_unit_status, t, n_files, n_words, group_log, d_have);
   return b3w_int_batch_launched(ctx, st, "bao have from status launch");
+}
+
+int32_t b3w_bao_outboard_diff_device(b3w_ctx *ctx, const uint64_t *host_lens_a, const uint64_t *host_ob_first_a, const uint8_t *d_outboards_a,
+                                     uint64_t outboards_a_bytes, const uint32_t *d_roots_a, uint32_t n_files_a, uint32_t group_log_a,
+                                     const uint64_t *host_lens_b, const uint64_t *host_ob_first_b, const uint8_t *d_outboards_b,
+                                     uint64_t outboards_b_bytes, const uint32_t *d_roots_b, uint32_t n_files_b, uint32_t group_log_b,
+                                     const uint32_t *host_pair_a, const uint32_t *host_pair_b, uint32_t n_pairs, const uint64_t *host_word_first,
+                                     uint64_t *d_same, void *stream) {
+  const char *call = "bao outboard diff";
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  B3W_TRY(group_log_ok(ctx, call, group_log_a));
+  B3W_TRY(group_log_ok(ctx, call, group_log_b));
+  if (!n_pairs) return B3W_OK;
+  if (!host_lens_a || !host_ob_first_a || !d_outboards_a || !d_roots_a || !host_lens_b || !host_ob_first_b || !d_outboards_b || !d_roots_b || !host_pair_a ||
+      !host_pair_b || !host_word_first || !d_same)
+    return refuse(ctx, call, "a null pointer");
+  if (((uintptr_t)d_outboards_a & 7) || ((uintptr_t)d_outboards_b & 7) || ((uintptr_t)d_roots_a & 3) || ((uintptr_t)d_roots_b & 3) || ((uintptr_t)d_same & 7))
+    return refuse(ctx, call, "d_outboards_a, d_outboards_b or d_same is not 8-byte aligned, or d_roots_a or d_roots_b not 4-byte aligned");
+  if (n_pairs > HAVE_MAX_WORDS) return refuse(ctx, call, "more than 2^26 bitmap words");      // (a pair has a word at least)
+  ON_DEVICE(ctx);
+  const uint64_t words = 5ull * n_pairs + 1;
+  B3W_TRY(b3w_int_batch_staging(ctx, words * 8));
+  uint64_t *h = reinterpret_cast<uint64_t *>(ctx->h_batch);
+  uint64_t n_words = 0;                                   // one pass checks a pair and writes its record; a refusal launches nothing
+  for (uint32_t i = 0; i < n_pairs; ++i) {
+    const uint32_t fa = host_pair_a[i], fb = host_pair_b[i];
+    const auto pair = [i] { return "pair " + std::to_string(i); };
+    if (fa >= n_files_a || fb >= n_files_b) return refuse(ctx, call, pair() + " names a file that is not below its side's file count");
+    const uint64_t na = num_chunks(host_lens_a[fa]), nb = num_chunks(host_lens_b[fb]);
+    if (na > DIFF_MAX_CHUNKS || nb > DIFF_MAX_CHUNKS) return refuse(ctx, call, pair() + " has a file of more than 2^30 chunks");
+    const uint64_t oa = host_ob_first_a[fa], ob = host_ob_first_b[fb];
+    if ((oa & 7) || (ob & 7)) return refuse(ctx, call, pair() + ": an outboard's place is not 8-byte aligned");
+    const uint64_t sa = group_outboard_bytes(host_lens_a[fa], group_log_a), sb = group_outboard_bytes(host_lens_b[fb], group_log_b);
+    if (oa > outboards_a_bytes || sa > outboards_a_bytes - oa || ob > outboards_b_bytes || sb > outboards_b_bytes - ob)
+      return refuse(ctx, call, pair() + ": an outboard reaches past its buffer's bytes");
+    if (host_word_first[i] != n_words) return refuse(ctx, call, "host_word_first is not b3w_bao_have_layout of the pairs' b lengths at " + pair());
+    h[i] = n_words;
+    uint64_t *rec = h + (uint64_t)n_pairs + 1 + 4ull * i;
+    rec[0] = na | nb << 32;
+    rec[1] = oa;
+    rec[2] = ob;
+    rec[3] = fa | (uint64_t)fb << 32;
+    n_words += (nb + 63) / 64;
+    if (n_words > HAVE_MAX_WORDS) return refuse(ctx, call, "more than 2^26 bitmap words");
+  }
+  if (host_word_first[n_pairs] != n_words) return refuse(ctx, call, "host_word_first is not b3w_bao_have_layout of the pairs' b lengths at its last entry");
+  h[n_pairs] = n_words;
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)(words * 8), hipMemcpyHostToDevice, st));
+  const uint32_t per = DIFF_WG / 64;
+  hipLaunchKernelGGL(b3w_bao_diff_kernel, dim3((uint32_t)((n_words + per - 1) / per)), dim3(DIFF_WG), 0, st, reinterpret_cast<const uint64_t *>(ctx->d_batch), n_pairs,
+                     n_words, d_outboards_a, d_roots_a, group_log_a, d_outboards_b, d_roots_b, group_log_b, d_same);
+  return b3w_int_batch_launched(ctx, st, "bao outboard diff launch");
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // b3w_bao_host.cpp — the bao calls of include/b3wit.h that never touch a device: the sizes and layouts, and the host mirrors that
 // extract, decode and take in slices (UNTRUSTED input), verify, update and resize one file node by node.  Plain C++, no kernel and no
-// HIP runtime call: tools/bao_range_host_check.cpp, bao_set_host_check.cpp, bao_have_host_check.cpp and bao_packed_host_check.cpp compile this file
+// HIP runtime call: tools/bao_range_host_check.cpp, bao_set_host_check.cpp, bao_have_host_check.cpp, bao_packed_host_check.cpp and bao_diff_host_check.cpp compile this file
 // alone with AddressSanitizer + UBSan.  The formats are described where the kernels are (b3w_bao.hip, b3w_bao_have.hip); the arithmetic both sides share is
 // b3w_bao_tree.h.  The device entry points stay in the .hip files, and b3w_sample_rows* beside them (they need b3w_plan_path_len).
 #include "b3w_bao_plan.h"
@@ -933,6 +933,26 @@ int32_t b3w_bao_have_from_status(const uint8_t *status, uint64_t len, uint32_t g
   for (uint64_t w = 0; w < (n + 63) / 64; ++w) have[w] = 0;
   for (uint64_t c = 0; c < n; ++c)
     if (status[c >> group_log] == 0) have[c >> 6] |= 1ull << (c & 63);
+  return B3W_OK;
+}
+
+// ---- the chunks two versions of one file share, from their outboards alone (the device side: the diff kernel in b3w_bao_have.hip) ------
+int32_t b3w_bao_outboard_diff(const uint8_t *outboard_a, uint64_t len_a, const uint32_t *root_a, uint32_t group_log_a, const uint8_t *outboard_b,
+                              uint64_t len_b, const uint32_t *root_b, uint32_t group_log_b, uint64_t *same_words) {
+  if (!outboard_a || !root_a || !outboard_b || !root_b || !same_words || group_log_a > B3W_BAO_MAX_GROUP_LOG || group_log_b > B3W_BAO_MAX_GROUP_LOG)
+    return B3W_E_BAD_ARGUMENT;
+  const uint64_t na = num_chunks(len_a), nb = num_chunks(len_b);
+  if (na > DIFF_MAX_CHUNKS || nb > DIFF_MAX_CHUNKS) return B3W_E_BAD_ARGUMENT;
+  const uint32_t G = group_log_a > group_log_b ? group_log_a : group_log_b;
+  for (uint64_t w = 0; w < (nb + 63) / 64; ++w) same_words[w] = 0;
+  for (uint64_t u = 0; u < n_units(len_b, G); ++u) {
+    if (!diff_unit_comparable((uint32_t)na, (uint32_t)nb, (uint32_t)u, G)) continue;
+    const bool whole = nb <= (1ull << G);
+    const void *cv_a = whole ? (const void *)root_a : outboard_a + diff_cv_at((uint32_t)na, group_log_a, (uint32_t)u, G);
+    const void *cv_b = whole ? (const void *)root_b : outboard_b + diff_cv_at((uint32_t)nb, group_log_b, (uint32_t)u, G);
+    if (memcmp(cv_a, cv_b, 32)) continue;
+    for (uint64_t c = u << G; c < nb && c < (u + 1) << G; ++c) same_words[c >> 6] |= 1ull << (c & 63);
+  }
   return B3W_OK;
 }
 

@@ -57,6 +57,41 @@ B3W_HD_INLINE uint64_t preorder_pos(uint64_t total, uint64_t a, uint64_t size) {
   return p;
 }
 
+// ---- outboard diff: where the CV of a block of leaves is STORED (b3w_bao_outboard_diff, the diff kernel in b3w_bao_have.hip) ----------
+// Leaves [a, a + size) of a tree over total > size leaves (a leaf: a unit of the outboard's own group_log), a a multiple of the power
+// of two `full` >= size, size < full only where the block ends the tree: such a block is a subtree, and its CV is one half of its
+// parent's node -> 2 * (that node's pre-order position) + (1: the right half).  The walk goes down from the root; from a complete
+// subtree of 2^j leaves on the rest is arithmetic: going right from a node of height h skips the 2^(h-1) - 1 nodes of its left
+// subtree, so the bits of the local index from the block's height + 1 up add themselves and every zero among them adds one.  32-bit:
+// a file has at most 2^30 chunks here.
+B3W_HD_INLINE uint32_t stored_half(uint32_t total, uint32_t a, uint32_t size, uint32_t full) {
+  uint32_t p = 0, lo = 0, cnt = total;
+  for (;;) {
+    if (size == full && !(cnt & (cnt - 1)) && cnt > full) {
+      const uint32_t t1 = (uint32_t)__builtin_ctz(full) + 1, j = (uint32_t)__builtin_ctz(cnt), up = (a - lo) >> t1;
+      return 2 * (p + (up << t1) + (j - t1) - (uint32_t)__builtin_popcount(up)) + (((a - lo) >> (t1 - 1)) & 1);
+    }
+    const uint32_t k = 1u << (31 - __builtin_clz(cnt - 1));
+    const bool left = a < lo + k;
+    const uint32_t clo = left ? lo : lo + k, ccnt = left ? k : cnt - k;
+    if (clo == a && ccnt == size) return 2 * p + (left ? 0 : 1);
+    p += left ? 1 : k;
+    lo = clo; cnt = ccnt;
+  }
+}
+// is unit u (2^G chunks, the last one ragged) of a file of nb chunks SAME in a file of na chunks, as far as the counts say: it exists
+// there, covers the same chunks, and is the whole file in both or in neither
+B3W_HD_INLINE bool diff_unit_comparable(uint32_t na, uint32_t nb, uint32_t u, uint32_t G) {
+  const uint64_t s = (uint64_t)u << G, e = s + (1ull << G);
+  return s < na && (e < na ? e : na) == (e < nb ? e : nb) && (na <= (1u << G)) == (nb <= (1u << G));
+}
+// the byte of the outboard (of group_log gl <= G) of a file of n > 2^G chunks at which the CV of its unit u of 2^G chunks is stored
+B3W_HD_INLINE uint64_t diff_cv_at(uint32_t n, uint32_t gl, uint32_t u, uint32_t G) {
+  const uint32_t total = (n + ((1u << gl) - 1)) >> gl, full = 1u << (G - gl), a = u << (G - gl);
+  return 8 + 32ull * stored_half(total, a, total - a < full ? total - a : full, full);
+}
+constexpr uint64_t DIFF_MAX_CHUNKS = 1ull << 30;         // a file of the diff: its node positions fit 32 bits
+
 // ---- range slices: places (the format is described at the range kernels in b3w_bao.hip) ------------------------------------------------
 // U(a, c), a <= c < n
 B3W_HD inline uint64_t range_nodes(uint64_t n, uint64_t a, uint64_t c) {

@@ -1048,6 +1048,50 @@ int32_t b3w_bao_have_runs(const uint64_t *have, uint64_t preimage_len, uint32_t 
                           uint64_t *run_first, uint64_t *run_count, uint64_t *n_runs, uint64_t *n_have);
 int32_t b3w_bao_have_from_status(const uint8_t *unit_status, uint64_t preimage_len, uint32_t group_log, uint64_t *have);
 
+/* ---- outboard diff: the chunks two versions of a file share, from their outboards alone (still ABI 1.4: new names only) ----
+ * A replica that holds a stale version `a` of a file and its outboard wants version `b`, of which it has only the outboard and the
+ * root.  Every unit's chaining value is stored in its parent's node, and two equal CVs mean equal bytes: comparing them names the
+ * chunks a already has.  The result is a bitmap in the arrival-bitmap layout of the b lengths, so b3w_bao_have_runs_device, the set
+ * slice calls and b3w_bao_set_slice_ingest_device (with this bitmap as d_have) follow unchanged.  Nothing is hashed and no file byte read.
+ * A PAIR i is (file host_pair_a[i] of side a, file host_pair_b[i] of side b).  A side is its lengths, its outboards as
+ * b3w_bao_outboard_batch_device (group_log 0) / b3w_bao_group_outboard_batch_device make them, each at byte host_ob_first[f] of
+ * d_outboards (any 8-byte-aligned places, read at paired files only), its group_log and its roots (8 words a file).  The two sides
+ * may be the same buffers, and a file may appear in many pairs.
+ * With G = max(group_log_a, group_log_b) a UNIT is 2^G chunks, the last one of a file possibly ragged.  Its STORED CV is the file's
+ * root where the unit is the whole file, else the left or right half of the node over the unit's parent subtree, which every
+ * outboard of group_log <= G holds (the finer outboard is read at the coarser level).  Unit u of b is SAME iff it exists in a, covers
+ * the same chunks in both, is the whole file in both or in neither, and the two stored CVs are equal.  Pair i owns
+ * ceil(num_chunks(len_b) / 64) words from word host_word_first[i] of d_same (host_word_first = b3w_bao_have_layout of the pairs' b
+ * lengths, n_pairs + 1 entries); bit c is set iff chunk c's unit is same.  Every word of every pair is written whole with its pad bits
+ * zero and nothing else is written.  A set bit means equal bytes.  A clear bit means "differs or not known": a chunk with equal bytes
+ * still gets a clear bit where another chunk of its unit differs, and where its unit is the whole file on one side only.
+ * One launch, a wave per word; the table of pairs (40 bytes a pair) rides the context's staging; asynchronous on `stream`; the host
+ * waits for nothing but this context's previous batch call.  n_pairs == 0 is a no-op.  B3W_E_BAD_ARGUMENT before anything is written
+ * for a null or misaligned pointer (outboards and d_same 8-byte, roots 4-byte, every paired outboard's place 8-byte), a group_log
+ * above B3W_BAO_MAX_GROUP_LOG, a pair index not below its side's file count, a file of more than 2^30 chunks, an outboard that
+ * reaches past its buffer's bytes, a host_word_first that is not that layout, or more than 2^26 words.
+ * When not to (MI355X): no call takes less than about 0.02 ms (the table's upload and one launch).  One 1 GiB file, 1 % of its
+ * chunks rewritten: 0.033 ms with full outboards, where copying the two outboards' 134 MB device to device takes 0.046 (spread
+ * 0.00004) and the route without this call - b3w_bao_verify_batch_device of b's RESIDENT bytes against a's outboard, then
+ * b3w_bao_have_from_status_device - 0.457; with group outboards of 16 chunks 0.021 against 0.0096 for the copy of 8 MB (the fixed
+ * cost shows) and 0.440 for that route.  262 144 files of 4 chunks: 1.17 ms against 0.034 for the copy and 1.99 for that route - the
+ * host's table costs about 4 ns a pair and is 40 bytes a pair to upload, the one cost that follows the pair count.  So: not for a
+ * caller who already holds b's bytes and has to verify them anyway (that route's statuses are the same bitmap and a verification
+ * besides; this call verifies NOTHING and believes both outboards - a replica that does not trust b's outboard learns of a lie only
+ * when b3w_bao_verify_batch_device runs over the finished file), and with very many tiny files the gain over that route shrinks to
+ * 1.7 times. */
+int32_t b3w_bao_outboard_diff_device(b3w_ctx *ctx, const uint64_t *host_lens_a, const uint64_t *host_ob_first_a, const uint8_t *d_outboards_a,
+                                     uint64_t outboards_a_bytes, const uint32_t *d_roots_a, uint32_t n_files_a, uint32_t group_log_a,
+                                     const uint64_t *host_lens_b, const uint64_t *host_ob_first_b, const uint8_t *d_outboards_b,
+                                     uint64_t outboards_b_bytes, const uint32_t *d_roots_b, uint32_t n_files_b, uint32_t group_log_b,
+                                     const uint32_t *host_pair_a, const uint32_t *host_pair_b, uint32_t n_pairs,
+                                     const uint64_t *host_word_first /* n_pairs + 1 */, uint64_t *d_same, void *stream);
+/* Host only, ONE pair: same_words [ceil(num_chunks(len_b) / 64)] receives the words the device call leaves for it.
+ * B3W_E_BAD_ARGUMENT for a null pointer, a group_log above the maximum or a file of more than 2^30 chunks. */
+int32_t b3w_bao_outboard_diff(const uint8_t *outboard_a, uint64_t len_a, const uint32_t *root_a /* 8 u32 */, uint32_t group_log_a,
+                              const uint8_t *outboard_b, uint64_t len_b, const uint32_t *root_b /* 8 u32 */, uint32_t group_log_b,
+                              uint64_t *same_words);
+
 /* ---- range slices: the slice of a run of chunks, extracted and taken in (still ABI 1.4: new names only) -------------
  * The run lists above name what is missing as rows (file, first chunk, chunks); the slice calls above carry ONE chunk a slice, so a
  * run of k chunks costs k slices and k whole paths (2 312 bytes for 1 024 of payload in a file of 2^20 chunks).  A RANGE SLICE carries
