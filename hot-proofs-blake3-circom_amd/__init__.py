@@ -217,6 +217,13 @@ def lib():
         "b3w_bao_have_from_status": (i32, [vp, u64, u32, vp]),
         "b3w_bao_outboard_diff_device": (i32, [vp, vp, vp, vp, u64, vp, u32, u32, vp, vp, vp, u64, vp, u32, u32, vp, vp, u32, vp, vp, vp]),
         "b3w_bao_outboard_diff": (i32, [vp, u64, vp, u32, vp, u64, vp, u32, vp]),
+        "b3w_bao_outboard_delta_bound": (u64, [u64, u32]),
+        "b3w_bao_outboard_delta_layout": (u64, [vp, u32, vp, u32, u32, vp]),
+        "b3w_bao_outboard_delta_scratch_bytes": (u64, [vp, u32, vp, u32, u32]),
+        "b3w_bao_outboard_delta_device": (i32, [vp, vp, vp, vp, u64, vp, u32, vp, vp, vp, u64, vp, u32, u32, u32, vp, vp, u32, vp, vp, u64, vp, vp, u64, vp]),
+        "b3w_bao_outboard_delta_apply_device": (i32, [vp, vp, vp, vp, u64, vp, u32, vp, vp, u32, u32, vp, vp, u32, vp, vp, u64, vp, vp, u64, vp, vp, vp, u64, vp]),
+        "b3w_bao_outboard_delta": (i32, [vp, u64, vp, vp, u64, vp, u32, vp, u64, vp]),
+        "b3w_bao_outboard_delta_apply": (i32, [vp, u64, vp, u64, vp, u32, vp, u64, vp, vp, vp]),
         "b3w_bao_update_scratch_bytes": (u64, [vp, vp, vp, vp, u32]),
         "b3w_bao_outboard_update_batch_device": (i32, [vp, vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, u32, vp, u64, vp]),
         "b3w_bao_outboard_update": (i32, [vp, u64, vp, u32, vp, vp, u32, vp]),
@@ -293,6 +300,8 @@ EXPORTED_SYMBOLS = ("b3w_abi_version", "b3w_identify_wasm", "b3w_create", "b3w_d
                     "b3w_bao_have_layout", "b3w_bao_slice_ingest_have_device", "b3w_bao_have_runs_scratch_bytes", "b3w_bao_have_runs_device",
                     "b3w_bao_have_from_status_device", "b3w_bao_have_runs", "b3w_bao_have_from_status",
                     "b3w_bao_outboard_diff_device", "b3w_bao_outboard_diff",
+                    "b3w_bao_outboard_delta_bound", "b3w_bao_outboard_delta_layout", "b3w_bao_outboard_delta_scratch_bytes", "b3w_bao_outboard_delta_device",
+                    "b3w_bao_outboard_delta_apply_device", "b3w_bao_outboard_delta", "b3w_bao_outboard_delta_apply",
                     "b3w_bao_range_slice_size", "b3w_bao_range_slice_batch_layout", "b3w_bao_range_slice", "b3w_bao_range_slice_decode",
                     "b3w_bao_range_slice_ingest", "b3w_bao_range_slice_arena_device", "b3w_bao_range_slice_ingest_scratch_bytes",
                     "b3w_bao_range_slice_ingest_device", "b3w_sample_rows_ranges", "b3w_sample_plan_range_slices_device",

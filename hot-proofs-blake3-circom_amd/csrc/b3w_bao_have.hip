@@ -13,6 +13,8 @@
 //   b3w_bao_have_pack_kernel     a bitmap from packed unit statuses, a lane per word, every word written whole
 //   b3w_bao_diff_kernel          a bitmap of the chunks two versions of a file share, from the CVs their outboards store (described
 //                                where it stands), a wave per word, every word written whole
+//   b3w_bao_delta_*_kernel       outboard deltas (described where they stand): mark and compact (the provider), check and write (the
+//                                replica), count for both; the scan between them is b3w_bao_have_scan_kernel
 // No workgroup waits for another: each level of the scan is a launch.
 //
 // The selected mask of a word at chunk granularity: a unit is a field of F = 1 << group_log bits, and for group_log <= 6 no field
@@ -236,6 +238,168 @@ __global__ __launch_bounds__(DIFF_WG) void b3w_bao_diff_kernel(const uint64_t *_
   if (lane == 0) same[w] = bits & have_valid(i, nb);
 }
 
+// ---- outboard deltas: b's parent nodes that a does not hold, served and verified on arrival (b3wit.h "outboard delta") --------------
+// Both calls keep the diff kernel's shape: a wave is a word of a pair's bitmap (bit p: b's node p is in the blob), a lane a node.  What
+// a lane decides about its node is b3w_bao_tree.h's (delta_node_same, delta_check_node, delta_copy_from), shared with the host mirrors;
+// a node's span and the places of the stored CVs come from walks down from the root, at most 30 steps each.  A node's rank in the blob
+// is (the set bits of the pair's words in front of its word) + (those below it in its word): the first from the have_runs scan over
+// ALL pairs' words - a lane per word counts, the workgroups' totals are scanned by b3w_bao_have_scan_kernel, and a word's prefix is
+// its workgroup's first plus its own place in the workgroup (delta_prefix).
+//   provider  mark (the ballot of "not SAME" is the word, stored whole into the blob), count, scan, compact (a lane copies its node to
+//             its rank while the rank is below the extent's capacity; a thread per pair writes the header and k as found)
+//   replica   count (over the blob's own bitmap; the pairs' keys reset), scan, check (a thread per pair the header; a lane its node:
+//             one parent compression per present node; the least key of a pair by atomicMin), write (gated on the pair's key: present
+//             nodes from the blob, absent ones from a's outboard; a thread per pair the status, the first bad node and the length)
+// The staging: word_first [n_pairs + 1], then eight words a pair: chunk counts (a low, b high), a's outboard's first byte (~0: the
+// replica holds nothing), b's outboard's (provider), the files (a low, b high), the blob's first byte, the nodes its extent holds,
+// len_b, the output outboard's first byte (replica).  A blob is UNTRUSTED: every node read is behind a rank below the capacity.
+constexpr uint32_t DELTA_WG = 256, DELTA_REC = 8;
+static_assert(DELTA_MALFORMED == B3W_BAO_DELTA_MALFORMED && DELTA_BAD_HASH == B3W_BAO_DELTA_BAD_HASH && DELTA_NOT_HELD == B3W_BAO_DELTA_NOT_HELD, "b3wit.h");
+
+__device__ __forceinline__ DeltaSides delta_sides(const uint64_t *rec, const uint8_t *obs_a, const uint32_t *roots_a, const uint32_t *roots_b, uint32_t g) {
+  DeltaSides s;
+  const bool has_a = rec[1] != ~0ull;
+  const uint32_t F1 = (1u << g) - 1;
+  s.ob_a = has_a ? obs_a + rec[1] : nullptr;
+  s.root_a = has_a && roots_a ? reinterpret_cast<const uint8_t *>(roots_a + 8ull * (uint32_t)rec[3]) : nullptr;
+  s.root_b = roots_b ? reinterpret_cast<const uint8_t *>(roots_b + 8ull * (uint32_t)(rec[3] >> 32)) : nullptr;
+  s.na = (uint32_t)rec[0]; s.nb = (uint32_t)(rec[0] >> 32);
+  s.ua = (s.na + F1) >> g; s.ub = (s.nb + F1) >> g;
+  s.g = g;
+  return s;
+}
+// the set bits in front of word w of all pairs' words (w = n_words: all of them)
+__device__ __forceinline__ uint64_t delta_prefix(const uint64_t *__restrict__ wg_first, const uint32_t *__restrict__ word_rank, uint64_t n_words, uint64_t w) {
+  return w < n_words ? wg_first[w / HAVE_WG] + word_rank[w] : wg_first[-1];      // (the grand total lies in front of the workgroups' firsts)
+}
+__device__ __forceinline__ void copy_node(uint8_t *dst, const uint8_t *src) {
+  uint64_t v[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) v[k] = reinterpret_cast<const uint64_t *>(src)[k];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) reinterpret_cast<uint64_t *>(dst)[k] = v[k];
+}
+
+__global__ __launch_bounds__(DELTA_WG) void b3w_bao_delta_mark_kernel(const uint64_t *__restrict__ tab, uint32_t n_pairs, uint64_t n_words, const uint8_t *obs_a,
+                                                                      const uint32_t *roots_a, const uint8_t *obs_b, const uint32_t *roots_b, uint32_t g,
+                                                                      uint8_t *__restrict__ delta) {
+  const uint64_t w = (uint64_t)blockIdx.x * (DELTA_WG / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (w >= n_words) return;
+  const uint32_t lane = threadIdx.x & 63, i = have_file_of(tab, n_pairs, w);
+  const uint64_t *rec = tab + (uint64_t)n_pairs + 1 + (uint64_t)DELTA_REC * i;
+  const uint64_t j = w - tab[i];
+  const uint32_t p = (uint32_t)(j * 64 + lane);
+  const DeltaSides s = delta_sides(rec, obs_a, roots_a, roots_b, g);
+  const bool differs = p < s.ub - 1 && !delta_node_same(s, obs_b + rec[2], p);
+  const uint64_t word = __ballot(differs);
+  if (lane == 0) *reinterpret_cast<uint64_t *>(delta + rec[4] + 16 + 8 * j) = word;
+}
+
+// a lane per word of the blobs' bitmaps: its count's place in the workgroup to word_rank, the workgroup's total to wg_totals; keys
+// (the replica's): reset for every pair (the grid covers the pairs)
+__global__ __launch_bounds__(HAVE_WG) void b3w_bao_delta_count_kernel(const uint64_t *__restrict__ tab, uint32_t n_pairs, uint64_t n_words, const uint8_t *__restrict__ delta,
+                                                                      uint64_t *__restrict__ wg_totals, uint32_t *__restrict__ word_rank, uint64_t *__restrict__ keys) {
+  __shared__ uint32_t lds[HAVE_WG / 64 + 1];
+  const uint64_t w = (uint64_t)blockIdx.x * HAVE_WG + threadIdx.x;
+  if (keys && w < n_pairs) keys[w] = DELTA_OK;
+  uint32_t pop = 0;
+  if (w < n_words) {
+    const uint32_t i = have_file_of(tab, n_pairs, w);
+    const uint64_t *rec = tab + (uint64_t)n_pairs + 1 + (uint64_t)DELTA_REC * i;
+    pop = (uint32_t)__popcll(*reinterpret_cast<const uint64_t *>(delta + rec[4] + 16 + 8 * (w - tab[i])));
+  }
+  uint32_t total;
+  const uint32_t before = block_scan(pop, lds, total);
+  if (w < n_words) word_rank[w] = before;
+  if (threadIdx.x == 0) wg_totals[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(DELTA_WG) void b3w_bao_delta_compact_kernel(const uint64_t *__restrict__ tab, uint32_t n_pairs, uint64_t n_words, const uint8_t *__restrict__ obs_b,
+                                                                         const uint64_t *__restrict__ wg_first, const uint32_t *__restrict__ word_rank,
+                                                                         uint8_t *__restrict__ delta, uint64_t *__restrict__ n_nodes) {
+  const uint64_t t = (uint64_t)blockIdx.x * DELTA_WG + threadIdx.x;
+  if (t < n_pairs) {                                       // the pair's header: len_b, k as found
+    const uint64_t *rec = tab + (uint64_t)n_pairs + 1 + (uint64_t)DELTA_REC * t;
+    const uint64_t k = delta_prefix(wg_first, word_rank, n_words, tab[t + 1]) - delta_prefix(wg_first, word_rank, n_words, tab[t]);
+    uint64_t *head = reinterpret_cast<uint64_t *>(delta + rec[4]);
+    head[0] = rec[6];
+    head[1] = k;
+    n_nodes[t] = k;
+  }
+  const uint64_t w = (uint64_t)blockIdx.x * (DELTA_WG / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (w >= n_words) return;
+  const uint32_t lane = threadIdx.x & 63, i = have_file_of(tab, n_pairs, w);
+  const uint64_t *rec = tab + (uint64_t)n_pairs + 1 + (uint64_t)DELTA_REC * i;
+  const uint64_t j = w - tab[i], W = tab[i + 1] - tab[i];
+  uint8_t *blob = delta + rec[4];
+  const uint64_t word = *reinterpret_cast<const uint64_t *>(blob + 16 + 8 * j);
+  if (!((word >> lane) & 1)) return;
+  const uint64_t r = delta_prefix(wg_first, word_rank, n_words, w) - delta_prefix(wg_first, word_rank, n_words, tab[i]) + (uint64_t)__popcll(word & ((1ull << lane) - 1));
+  if (r >= rec[5]) return;                                 // behind the extent: counted, not written
+  copy_node(blob + 16 + 8 * W + 64 * r, obs_b + rec[2] + 8 + 64 * (j * 64 + lane));
+}
+
+__global__ __launch_bounds__(DELTA_WG) void b3w_bao_delta_check_kernel(const uint64_t *__restrict__ tab, uint32_t n_pairs, uint64_t n_words, const uint8_t *obs_a,
+                                                                       const uint32_t *roots_a, const uint32_t *roots_b, uint32_t g, const uint8_t *__restrict__ delta,
+                                                                       const uint64_t *__restrict__ wg_first, const uint32_t *__restrict__ word_rank,
+                                                                       unsigned long long *__restrict__ keys) {
+  const uint64_t t = (uint64_t)blockIdx.x * DELTA_WG + threadIdx.x;
+  if (t < n_pairs) {
+    const uint64_t *rec = tab + (uint64_t)n_pairs + 1 + (uint64_t)DELTA_REC * t;
+    const uint64_t count = delta_prefix(wg_first, word_rank, n_words, tab[t + 1]) - delta_prefix(wg_first, word_rank, n_words, tab[t]);
+    const uint64_t key = delta_check_head(delta + rec[4], rec[6], rec[5], count);
+    if (key != DELTA_OK) atomicMin(keys + t, (unsigned long long)key);
+  }
+  const uint64_t w = (uint64_t)blockIdx.x * (DELTA_WG / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (w >= n_words) return;
+  const uint32_t lane = threadIdx.x & 63, i = have_file_of(tab, n_pairs, w);
+  const uint64_t *rec = tab + (uint64_t)n_pairs + 1 + (uint64_t)DELTA_REC * i;
+  const uint64_t first = tab[i], base = delta_prefix(wg_first, word_rank, n_words, first);
+  const uint8_t *blob = delta + rec[4];
+  const DeltaSides s = delta_sides(rec, obs_a, roots_a, roots_b, g);
+  const auto rank = [&](uint32_t q) {
+    const uint64_t word = *reinterpret_cast<const uint64_t *>(blob + 16 + 8 * (uint64_t)(q >> 6));
+    return delta_prefix(wg_first, word_rank, n_words, first + (q >> 6)) - base + (uint64_t)__popcll(word & ((1ull << (q & 63)) - 1));
+  };
+  const uint64_t key = delta_check_node(s, blob, rec[5], (uint32_t)((w - first) * 64 + lane), rank);
+  if (key != DELTA_OK) atomicMin(keys + i, (unsigned long long)key);
+}
+
+__global__ __launch_bounds__(DELTA_WG) void b3w_bao_delta_write_kernel(const uint64_t *__restrict__ tab, uint32_t n_pairs, uint64_t n_words, const uint8_t *obs_a, uint32_t g,
+                                                                       const uint8_t *delta, const uint64_t *__restrict__ wg_first, const uint32_t *__restrict__ word_rank,
+                                                                       const uint64_t *__restrict__ keys, uint8_t *out, int32_t *__restrict__ status,
+                                                                       uint64_t *__restrict__ first_bad) {
+  const uint64_t t = (uint64_t)blockIdx.x * DELTA_WG + threadIdx.x;
+  if (t < n_pairs) {
+    const uint64_t *rec = tab + (uint64_t)n_pairs + 1 + (uint64_t)DELTA_REC * t;
+    const uint64_t key = keys[t];
+    status[t] = key == DELTA_OK ? 0 : (int32_t)(key & 3);
+    first_bad[t] = key == DELTA_OK ? ~0ull : key >> 2;
+    if (key == DELTA_OK) *reinterpret_cast<uint64_t *>(out + rec[7]) = rec[6];
+  }
+  const uint64_t w = (uint64_t)blockIdx.x * (DELTA_WG / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (w >= n_words) return;
+  const uint32_t lane = threadIdx.x & 63, i = have_file_of(tab, n_pairs, w);
+  if (keys[i] != DELTA_OK) return;                         // a pair with a status keeps its output as it was
+  const uint64_t *rec = tab + (uint64_t)n_pairs + 1 + (uint64_t)DELTA_REC * i;
+  const uint64_t first = tab[i], j = w - first, W = tab[i + 1] - first;
+  const DeltaSides s = delta_sides(rec, obs_a, nullptr, nullptr, g);
+  const uint32_t p = (uint32_t)(j * 64 + lane);
+  if (p >= s.ub - 1) return;
+  const uint8_t *blob = delta + rec[4], *src;
+  const uint64_t word = *reinterpret_cast<const uint64_t *>(blob + 16 + 8 * j);
+  if ((word >> lane) & 1) {
+    const uint64_t r = delta_prefix(wg_first, word_rank, n_words, w) - delta_prefix(wg_first, word_rank, n_words, first) + (uint64_t)__popcll(word & ((1ull << lane) - 1));
+    src = blob + 16 + 8 * W + 64 * r;                      // (r < k <= the capacity: the pair passed)
+  } else {
+    const uint64_t at = delta_copy_from(s, p);
+    if (!at) return;
+    src = s.ob_a + at;
+  }
+  uint8_t *dst = out + rec[7] + 8 + 64ull * p;
+  if (src != dst) copy_node(dst, src);                     // (in place: a's own node stays where it is)
+}
+
 // the tables into the staging and on their way to the device -> their device addresses
 int32_t have_tables(b3w_ctx *ctx, const uint64_t *host_lens, uint32_t n_files, bool units, uint32_t group_log, hipStream_t st, const uint64_t *&t) {
   const uint64_t words = (uint64_t)n_files * (units ? 3 : 2) + 1;
@@ -374,6 +538,194 @@ int32_t b3w_bao_outboard_diff_device(b3w_ctx *ctx, const uint64_t *host_lens_a, 
   hipLaunchKernelGGL(b3w_bao_diff_kernel, dim3((uint32_t)((n_words + per - 1) / per)), dim3(DIFF_WG), 0, st, reinterpret_cast<const uint64_t *>(ctx->d_batch), n_pairs,
                      n_words, d_outboards_a, d_roots_a, group_log_a, d_outboards_b, d_roots_b, group_log_b, d_same);
   return b3w_int_batch_launched(ctx, st, "bao outboard diff launch");
+}
+
+}  // extern "C"
+
+// ---- outboard deltas: what both entry points check and prepare, then the entry points ------------------------------------------------
+namespace {
+
+bool ranges_meet(const void *p, uint64_t n, const void *q, uint64_t m) {
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return n && m && a < b + m && b < a + n;
+}
+uint64_t delta_pair_words(const uint64_t *lens_b, const uint32_t *pair_b, uint32_t n_pairs, uint32_t n_files_b, uint32_t g, bool &ok) {
+  uint64_t at = 0;
+  ok = true;
+  for (uint32_t i = 0; i < n_pairs; ++i) {
+    const uint32_t fb = pair_b ? pair_b[i] : i;
+    if (fb >= n_files_b) { ok = false; return 0; }
+    at += delta_words(n_units(lens_b[fb], g));
+  }
+  return at;
+}
+uint64_t delta_scratch(uint64_t n_words, uint32_t n_pairs) {
+  const uint64_t most = n_words > n_pairs ? n_words : n_pairs, wgs = most ? (most + HAVE_WG - 1) / HAVE_WG : 1;
+  return (8 * (1 + wgs + (uint64_t)n_pairs) + 4 * n_words + 15) & ~15ull;      // the total, the workgroups' firsts, the pairs' keys, the words' ranks
+}
+
+struct DeltaPlan { uint64_t n_words; uint32_t wgs; const uint64_t *tab; uint64_t *total, *wg, *keys; uint32_t *word_rank; };
+
+// the checks both calls share and the table of pairs into the staging; nothing is launched or written to the device before it returns.
+// The provider passes ob_first_b and no out_first, the replica the other way round.
+int32_t delta_prepare(b3w_ctx *ctx, const char *call, const uint64_t *lens_a, const uint64_t *ob_first_a, const uint8_t *d_a, uint64_t a_bytes, uint32_t n_files_a,
+                      const uint64_t *lens_b, const uint64_t *ob_first_b, uint64_t b_bytes, uint32_t n_files_b, uint32_t g, const uint32_t *pair_a,
+                      const uint32_t *pair_b, uint32_t n_pairs, const uint64_t *delta_first, uint64_t delta_bytes, const uint64_t *out_first, const uint8_t *d_out,
+                      uint64_t out_bytes, bool in_place, void *d_scratch, uint64_t scratch_bytes, hipStream_t st, DeltaPlan &plan) {
+  if (n_pairs > HAVE_MAX_WORDS) return refuse(ctx, call, "more than 2^26 pairs");
+  const uint64_t words = (uint64_t)n_pairs * (1 + DELTA_REC) + 1;
+  B3W_TRY(b3w_int_batch_staging(ctx, words * 8));
+  uint64_t *h = reinterpret_cast<uint64_t *>(ctx->h_batch);
+  uint64_t n_words = 0, out_end = 0;
+  for (uint32_t i = 0; i < n_pairs; ++i) {
+    const uint32_t fa = pair_a[i], fb = pair_b[i];
+    const auto pair = [i] { return "pair " + std::to_string(i); };
+    const bool has_a = fa != B3W_BAO_DELTA_NO_A;
+    if ((has_a && fa >= n_files_a) || fb >= n_files_b) return refuse(ctx, call, pair() + " names a file that is not below its side's file count");
+    const uint64_t na = has_a ? num_chunks(lens_a[fa]) : 0, nb = num_chunks(lens_b[fb]);
+    if (na > DIFF_MAX_CHUNKS || nb > DIFF_MAX_CHUNKS) return refuse(ctx, call, pair() + " has a file of more than 2^30 chunks");
+    const uint64_t ub = n_units(lens_b[fb], g), W = delta_words(ub);
+    uint64_t oa = ~0ull;
+    if (has_a) {
+      oa = ob_first_a[fa];
+      if (oa & 7) return refuse(ctx, call, pair() + ": an outboard's place is not 8-byte aligned");
+      const uint64_t sa = group_outboard_bytes(lens_a[fa], g);
+      if (oa > a_bytes || sa > a_bytes - oa) return refuse(ctx, call, pair() + ": an outboard reaches past its buffer's bytes");
+    }
+    uint64_t ob = 0;
+    if (ob_first_b) {
+      ob = ob_first_b[fb];
+      if (ob & 7) return refuse(ctx, call, pair() + ": an outboard's place is not 8-byte aligned");
+      const uint64_t sb = group_outboard_bytes(lens_b[fb], g);
+      if (ob > b_bytes || sb > b_bytes - ob) return refuse(ctx, call, pair() + ": an outboard reaches past its buffer's bytes");
+    }
+    const uint64_t d0 = delta_first[i], d1 = delta_first[i + 1];
+    if ((d0 & 7) || (d1 & 7)) return refuse(ctx, call, "host_delta_first is not 8-byte aligned at " + pair());
+    if (d1 < d0) return refuse(ctx, call, "host_delta_first does not rise at " + pair() + ": the extents overlap");
+    if (d1 > delta_bytes) return refuse(ctx, call, pair() + ": the blob's extent reaches past delta_bytes");
+    if (d1 - d0 < 16 + 8 * W) return refuse(ctx, call, pair() + ": the blob's extent is too small for its header and bitmap");
+    uint64_t oo = 0;
+    if (out_first) {
+      oo = out_first[i];
+      const uint64_t so = group_outboard_bytes(lens_b[fb], g);
+      if (oo & 7) return refuse(ctx, call, pair() + ": the output outboard's place is not 8-byte aligned");
+      if (oo > out_bytes || so > out_bytes - oo) return refuse(ctx, call, pair() + ": the output outboard reaches past its buffer's bytes");
+      if (i && oo < out_end) return refuse(ctx, call, pair() + ": the output outboards do not lie in rising order, or two of them overlap");
+      out_end = oo + so;
+      if (in_place && !(has_a && n_units(lens_a[fa], g) == ub && d_out + oo == d_a + oa))
+        return refuse(ctx, call, pair() + ": the output buffer overlaps a's outboards, and this pair's output is not a's outboard of the same unit count at the same place");
+    }
+    h[i] = n_words;
+    uint64_t *rec = h + (uint64_t)n_pairs + 1 + (uint64_t)DELTA_REC * i;
+    rec[0] = na | nb << 32;
+    rec[1] = oa;
+    rec[2] = ob;
+    rec[3] = (has_a ? fa : 0) | (uint64_t)fb << 32;
+    rec[4] = d0;
+    rec[5] = (d1 - d0 - 16 - 8 * W) / 64;
+    rec[6] = lens_b[fb];
+    rec[7] = oo;
+    n_words += W;
+    if (n_words > HAVE_MAX_WORDS) return refuse(ctx, call, "more than 2^26 bitmap words");
+  }
+  h[n_pairs] = n_words;
+  if (scratch_bytes < delta_scratch(n_words, n_pairs)) return refuse(ctx, call, "the scratch is smaller than b3w_bao_outboard_delta_scratch_bytes says");
+  if (!d_scratch || ((uintptr_t)d_scratch & 7)) return refuse(ctx, call, "the scratch is null or not 8-byte aligned");
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, ctx->h_batch, (size_t)(words * 8), hipMemcpyHostToDevice, st));
+  const uint64_t most = n_words > n_pairs ? n_words : n_pairs;
+  plan.n_words = n_words;
+  plan.wgs = (uint32_t)((most + HAVE_WG - 1) / HAVE_WG);
+  plan.tab = reinterpret_cast<const uint64_t *>(ctx->d_batch);
+  plan.total = reinterpret_cast<uint64_t *>(d_scratch);
+  plan.wg = plan.total + 1;
+  plan.keys = plan.wg + plan.wgs;
+  plan.word_rank = reinterpret_cast<uint32_t *>(plan.keys + n_pairs);
+  return B3W_OK;
+}
+// the grid of the kernels that give a wave to a word and a thread to a pair
+uint32_t delta_grid(const DeltaPlan &p, uint32_t n_pairs) {
+  const uint64_t a = (p.n_words + DELTA_WG / 64 - 1) / (DELTA_WG / 64), b = ((uint64_t)n_pairs + DELTA_WG - 1) / DELTA_WG;
+  return (uint32_t)(a > b ? a : b);
+}
+
+}  // namespace
+extern "C" {
+
+uint64_t b3w_bao_outboard_delta_scratch_bytes(const uint64_t *host_lens_b, uint32_t n_files_b, const uint32_t *host_pair_b, uint32_t n_pairs, uint32_t group_log) {
+  if (!host_lens_b || group_log > B3W_BAO_MAX_GROUP_LOG) return 0;
+  bool ok;
+  const uint64_t n_words = delta_pair_words(host_lens_b, host_pair_b, n_pairs, n_files_b, group_log, ok);
+  return ok ? delta_scratch(n_words, n_pairs) : 0;
+}
+
+int32_t b3w_bao_outboard_delta_device(b3w_ctx *ctx, const uint64_t *host_lens_a, const uint64_t *host_ob_first_a, const uint8_t *d_outboards_a,
+                                      uint64_t outboards_a_bytes, const uint32_t *d_roots_a, uint32_t n_files_a, const uint64_t *host_lens_b,
+                                      const uint64_t *host_ob_first_b, const uint8_t *d_outboards_b, uint64_t outboards_b_bytes, const uint32_t *d_roots_b,
+                                      uint32_t n_files_b, uint32_t group_log_a, uint32_t group_log_b, const uint32_t *host_pair_a, const uint32_t *host_pair_b,
+                                      uint32_t n_pairs, const uint64_t *host_delta_first, uint8_t *d_delta, uint64_t delta_bytes, uint64_t *d_n_nodes,
+                                      void *d_scratch, uint64_t scratch_bytes, void *stream) {
+  const char *call = "bao outboard delta";
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  B3W_TRY(group_log_ok(ctx, call, group_log_a));
+  B3W_TRY(group_log_ok(ctx, call, group_log_b));
+  if (group_log_a != group_log_b) return refuse(ctx, call, "the two sides have different group_logs (b3w_bao_outboard_diff_device takes those)");
+  if (!n_pairs) return B3W_OK;
+  if (!host_lens_b || !host_ob_first_b || !d_outboards_b || !d_roots_b || !host_pair_a || !host_pair_b || !host_delta_first || !d_delta || !d_n_nodes)
+    return refuse(ctx, call, "a null pointer");
+  if (n_files_a && (!host_lens_a || !host_ob_first_a || !d_outboards_a || !d_roots_a)) return refuse(ctx, call, "a null pointer");
+  if (((uintptr_t)d_outboards_a & 7) || ((uintptr_t)d_outboards_b & 7) || ((uintptr_t)d_roots_a & 3) || ((uintptr_t)d_roots_b & 3) || ((uintptr_t)d_delta & 7) ||
+      ((uintptr_t)d_n_nodes & 7))
+    return refuse(ctx, call, "d_outboards_a, d_outboards_b, d_delta or d_n_nodes is not 8-byte aligned, or d_roots_a or d_roots_b not 4-byte aligned");
+  if (ranges_meet(d_delta, delta_bytes, d_outboards_a, n_files_a ? outboards_a_bytes : 0) || ranges_meet(d_delta, delta_bytes, d_outboards_b, outboards_b_bytes))
+    return refuse(ctx, call, "the blob buffer overlaps an outboard buffer");
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  DeltaPlan p;
+  B3W_TRY(delta_prepare(ctx, call, host_lens_a, host_ob_first_a, d_outboards_a, outboards_a_bytes, n_files_a, host_lens_b, host_ob_first_b, outboards_b_bytes, n_files_b,
+                        group_log_a, host_pair_a, host_pair_b, n_pairs, host_delta_first, delta_bytes, nullptr, nullptr, 0, false, d_scratch, scratch_bytes, st, p));
+  const uint32_t per = DELTA_WG / 64;
+  if (p.n_words)
+    hipLaunchKernelGGL(b3w_bao_delta_mark_kernel, dim3((uint32_t)((p.n_words + per - 1) / per)), dim3(DELTA_WG), 0, st, p.tab, n_pairs, p.n_words, d_outboards_a, d_roots_a,
+                       d_outboards_b, d_roots_b, group_log_a, d_delta);
+  hipLaunchKernelGGL(b3w_bao_delta_count_kernel, dim3(p.wgs), dim3(HAVE_WG), 0, st, p.tab, n_pairs, p.n_words, d_delta, p.wg, p.word_rank, (uint64_t *)nullptr);
+  hipLaunchKernelGGL(b3w_bao_have_scan_kernel, dim3(1), dim3(HAVE_WG), 0, st, p.wg, p.wgs, p.total);
+  hipLaunchKernelGGL(b3w_bao_delta_compact_kernel, dim3(delta_grid(p, n_pairs)), dim3(DELTA_WG), 0, st, p.tab, n_pairs, p.n_words, d_outboards_b, p.wg, p.word_rank, d_delta,
+                     d_n_nodes);
+  return b3w_int_batch_launched(ctx, st, "bao outboard delta launch");
+}
+
+int32_t b3w_bao_outboard_delta_apply_device(b3w_ctx *ctx, const uint64_t *host_lens_a, const uint64_t *host_ob_first_a, const uint8_t *d_outboards_a,
+                                            uint64_t outboards_a_bytes, const uint32_t *d_roots_a, uint32_t n_files_a, const uint64_t *host_lens_b,
+                                            const uint32_t *d_roots_b, uint32_t n_files_b, uint32_t group_log, const uint32_t *host_pair_a,
+                                            const uint32_t *host_pair_b, uint32_t n_pairs, const uint64_t *host_delta_first, const uint8_t *d_delta,
+                                            uint64_t delta_bytes, const uint64_t *host_ob_first_out, uint8_t *d_outboards_out, uint64_t outboards_out_bytes,
+                                            int32_t *d_pair_status, uint64_t *d_first_bad, void *d_scratch, uint64_t scratch_bytes, void *stream) {
+  const char *call = "bao outboard delta apply";
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  B3W_TRY(group_log_ok(ctx, call, group_log));
+  if (!n_pairs) return B3W_OK;
+  if (!host_lens_b || !d_roots_b || !host_pair_a || !host_pair_b || !host_delta_first || !d_delta || !host_ob_first_out || !d_outboards_out || !d_pair_status ||
+      !d_first_bad)
+    return refuse(ctx, call, "a null pointer");
+  if (n_files_a && (!host_lens_a || !host_ob_first_a || !d_outboards_a || !d_roots_a)) return refuse(ctx, call, "a null pointer");
+  if (((uintptr_t)d_outboards_a & 7) || ((uintptr_t)d_outboards_out & 7) || ((uintptr_t)d_roots_a & 3) || ((uintptr_t)d_roots_b & 3) || ((uintptr_t)d_delta & 7) ||
+      ((uintptr_t)d_first_bad & 7) || ((uintptr_t)d_pair_status & 3))
+    return refuse(ctx, call, "d_outboards_a, d_outboards_out, d_delta or d_first_bad is not 8-byte aligned, or d_roots_a, d_roots_b or d_pair_status not 4-byte aligned");
+  if (ranges_meet(d_outboards_out, outboards_out_bytes, d_delta, delta_bytes)) return refuse(ctx, call, "the output buffer overlaps the blob buffer");
+  const bool in_place = ranges_meet(d_outboards_out, outboards_out_bytes, d_outboards_a, n_files_a ? outboards_a_bytes : 0);
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  DeltaPlan p;
+  B3W_TRY(delta_prepare(ctx, call, host_lens_a, host_ob_first_a, d_outboards_a, outboards_a_bytes, n_files_a, host_lens_b, nullptr, 0, n_files_b, group_log, host_pair_a,
+                        host_pair_b, n_pairs, host_delta_first, delta_bytes, host_ob_first_out, d_outboards_out, outboards_out_bytes, in_place, d_scratch, scratch_bytes,
+                        st, p));
+  hipLaunchKernelGGL(b3w_bao_delta_count_kernel, dim3(p.wgs), dim3(HAVE_WG), 0, st, p.tab, n_pairs, p.n_words, d_delta, p.wg, p.word_rank, p.keys);
+  hipLaunchKernelGGL(b3w_bao_have_scan_kernel, dim3(1), dim3(HAVE_WG), 0, st, p.wg, p.wgs, p.total);
+  hipLaunchKernelGGL(b3w_bao_delta_check_kernel, dim3(delta_grid(p, n_pairs)), dim3(DELTA_WG), 0, st, p.tab, n_pairs, p.n_words, d_outboards_a, d_roots_a, d_roots_b,
+                     group_log, d_delta, p.wg, p.word_rank, reinterpret_cast<unsigned long long *>(p.keys));
+  hipLaunchKernelGGL(b3w_bao_delta_write_kernel, dim3(delta_grid(p, n_pairs)), dim3(DELTA_WG), 0, st, p.tab, n_pairs, p.n_words, d_outboards_a, group_log, d_delta, p.wg,
+                     p.word_rank, p.keys, d_outboards_out, d_pair_status, d_first_bad);
+  return b3w_int_batch_launched(ctx, st, "bao outboard delta apply launch");
 }
 
 }  // extern "C"

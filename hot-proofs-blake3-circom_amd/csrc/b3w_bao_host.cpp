@@ -1,6 +1,6 @@
 // b3w_bao_host.cpp — the bao calls of include/b3wit.h that never touch a device: the sizes and layouts, and the host mirrors that
 // extract, decode and take in slices (UNTRUSTED input), verify, update and resize one file node by node.  Plain C++, no kernel and no
-// HIP runtime call: tools/bao_range_host_check.cpp, bao_set_host_check.cpp, bao_have_host_check.cpp, bao_packed_host_check.cpp and bao_diff_host_check.cpp compile this file
+// HIP runtime call: tools/bao_range_host_check.cpp, bao_set_host_check.cpp, bao_have_host_check.cpp, bao_packed_host_check.cpp, bao_diff_host_check.cpp and bao_delta_host_check.cpp compile this file
 // alone with AddressSanitizer + UBSan.  The formats are described where the kernels are (b3w_bao.hip, b3w_bao_have.hip); the arithmetic both sides share is
 // b3w_bao_tree.h.  The device entry points stay in the .hip files, and b3w_sample_rows* beside them (they need b3w_plan_path_len).
 #include "b3w_bao_plan.h"
@@ -952,6 +952,100 @@ int32_t b3w_bao_outboard_diff(const uint8_t *outboard_a, uint64_t len_a, const u
     const void *cv_b = whole ? (const void *)root_b : outboard_b + diff_cv_at((uint32_t)nb, group_log_b, (uint32_t)u, G);
     if (memcmp(cv_a, cv_b, 32)) continue;
     for (uint64_t c = u << G; c < nb && c < (u + 1) << G; ++c) same_words[c >> 6] |= 1ull << (c & 63);
+  }
+  return B3W_OK;
+}
+
+// ---- outboard deltas on the host (the device side: the delta kernels in b3w_bao_have.hip; the verdicts: b3w_bao_tree.h) ------------------
+static_assert(DELTA_MALFORMED == B3W_BAO_DELTA_MALFORMED && DELTA_BAD_HASH == B3W_BAO_DELTA_BAD_HASH && DELTA_NOT_HELD == B3W_BAO_DELTA_NOT_HELD, "b3wit.h");
+
+uint64_t b3w_bao_outboard_delta_bound(uint64_t len_b, uint32_t group_log) {
+  if (group_log > B3W_BAO_MAX_GROUP_LOG) return 0;
+  const uint64_t ub = n_units(len_b, group_log);
+  return 16 + 8 * delta_words(ub) + 64 * (ub - 1);
+}
+
+uint64_t b3w_bao_outboard_delta_layout(const uint64_t *host_lens_b, uint32_t n_files_b, const uint32_t *host_pair_b, uint32_t n_pairs, uint32_t group_log,
+                                       uint64_t *delta_first) {
+  if (!host_lens_b || !delta_first || group_log > B3W_BAO_MAX_GROUP_LOG) return 0;
+  uint64_t at = 0;
+  for (uint32_t i = 0; i < n_pairs; ++i) {
+    const uint32_t fb = host_pair_b ? host_pair_b[i] : i;
+    if (fb >= n_files_b) return 0;
+    delta_first[i] = at;
+    at += b3w_bao_outboard_delta_bound(host_lens_b[fb], group_log);
+  }
+  delta_first[n_pairs] = at;
+  return at;
+}
+
+static bool delta_sides_of(const uint8_t *outboard_a, uint64_t len_a, const uint32_t *root_a, uint64_t len_b, const uint32_t *root_b, uint32_t g, DeltaSides &s) {
+  if (!root_b || (outboard_a && !root_a) || g > B3W_BAO_MAX_GROUP_LOG) return false;
+  const uint64_t na = outboard_a ? num_chunks(len_a) : 0, nb = num_chunks(len_b);
+  if (na > DIFF_MAX_CHUNKS || nb > DIFF_MAX_CHUNKS) return false;
+  s.ob_a = outboard_a;
+  s.root_a = reinterpret_cast<const uint8_t *>(root_a);
+  s.root_b = reinterpret_cast<const uint8_t *>(root_b);
+  s.na = (uint32_t)na; s.nb = (uint32_t)nb;
+  s.ua = outboard_a ? (uint32_t)n_units(len_a, g) : 0; s.ub = (uint32_t)n_units(len_b, g);
+  s.g = g;
+  return true;
+}
+
+int32_t b3w_bao_outboard_delta(const uint8_t *outboard_a, uint64_t len_a, const uint32_t *root_a, const uint8_t *outboard_b, uint64_t len_b,
+                               const uint32_t *root_b, uint32_t group_log, uint8_t *blob, uint64_t blob_bytes, uint64_t *n_nodes) {
+  DeltaSides s;
+  if (!outboard_b || !blob || !n_nodes || !delta_sides_of(outboard_a, len_a, root_a, len_b, root_b, group_log, s)) return B3W_E_BAD_ARGUMENT;
+  const uint64_t W = delta_words(s.ub);
+  if (blob_bytes < 16 + 8 * W) return B3W_E_BAD_ARGUMENT;
+  const uint64_t cap = (blob_bytes - 16 - 8 * W) / 64;
+  uint64_t k = 0;
+  memset(blob + 16, 0, 8 * W);
+  for (uint32_t p = 0; p + 1 < s.ub; ++p) {
+    if (delta_node_same(s, outboard_b, p)) continue;
+    blob[16 + p / 8] |= (uint8_t)(1u << (p & 7));          // (little-endian words: bit p of the bitmap is bit p & 7 of byte p / 8)
+    if (k < cap) memcpy(blob + 16 + 8 * W + 64 * k, outboard_b + 8 + 64ull * p, 64);
+    ++k;
+  }
+  memcpy(blob, &len_b, 8);
+  memcpy(blob + 8, &k, 8);
+  *n_nodes = k;
+  return B3W_OK;
+}
+
+int32_t b3w_bao_outboard_delta_apply(const uint8_t *outboard_a, uint64_t len_a, const uint32_t *root_a, uint64_t len_b, const uint32_t *root_b,
+                                     uint32_t group_log, const uint8_t *blob, uint64_t blob_bytes, uint8_t *outboard_out, int32_t *status,
+                                     uint64_t *first_bad) {
+  DeltaSides s;
+  if (!blob || !outboard_out || !status || !first_bad || !delta_sides_of(outboard_a, len_a, root_a, len_b, root_b, group_log, s)) return B3W_E_BAD_ARGUMENT;
+  const uint64_t W = delta_words(s.ub);
+  if (blob_bytes < 16 + 8 * W) return B3W_E_BAD_ARGUMENT;
+  const uint64_t cap = (blob_bytes - 16 - 8 * W) / 64;
+  std::vector<uint64_t> before(W + 1);                     // the set bits in front of every word
+  before[0] = 0;
+  for (uint64_t j = 0; j < W; ++j) before[j + 1] = before[j] + (uint64_t)__builtin_popcountll(delta_load64(blob + 16 + 8 * j));
+  const auto rank = [&](uint32_t q) {
+    return before[q >> 6] + (uint64_t)__builtin_popcountll(delta_load64(blob + 16 + 8 * (uint64_t)(q >> 6)) & ((1ull << (q & 63)) - 1));
+  };
+  uint64_t key = delta_check_head(blob, len_b, cap, before[W]);
+  for (uint64_t p = 0; p < 64 * W; ++p) {
+    const uint64_t one = delta_check_node(s, blob, cap, (uint32_t)p, rank);
+    if (one < key) key = one;
+  }
+  *status = key == DELTA_OK ? 0 : (int32_t)(key & 3);
+  *first_bad = key == DELTA_OK ? ~0ull : key >> 2;
+  if (key != DELTA_OK) return B3W_OK;
+  memcpy(outboard_out, &len_b, 8);
+  for (uint32_t p = 0; p + 1 < s.ub; ++p) {
+    const uint8_t *src;
+    if ((delta_load64(blob + 16 + 8 * (uint64_t)(p >> 6)) >> (p & 63)) & 1) src = blob + 16 + 8 * W + 64 * rank(p);
+    else {
+      const uint64_t at = delta_copy_from(s, p);
+      if (!at) continue;
+      src = outboard_a + at;
+    }
+    uint8_t *dst = outboard_out + 8 + 64ull * p;
+    if (src != dst) memcpy(dst, src, 64);
   }
   return B3W_OK;
 }

@@ -92,6 +92,162 @@ B3W_HD_INLINE uint64_t diff_cv_at(uint32_t n, uint32_t gl, uint32_t u, uint32_t 
 }
 constexpr uint64_t DIFF_MAX_CHUNKS = 1ull << 30;         // a file of the diff: its node positions fit 32 bits
 
+// ---- outboard delta: b's parent nodes that a does not hold (b3wit.h "outboard delta"; the delta kernels in b3w_bao_have.hip) -----------
+// Both trees are over units of one group_log.  Everything the provider, the replica and their host mirrors decide about a node is
+// decided here, once: the kernels and b3w_bao_host.cpp differ only in how they find a node's rank in the blob.
+constexpr uint64_t DELTA_OK = ~0ull;                     // the key of a pair without a fault; a fault's key: 4 * node + status, the least wins
+constexpr uint32_t DELTA_MALFORMED = 1, DELTA_BAD_HASH = 2, DELTA_NOT_HELD = 3;      // B3W_BAO_DELTA_* of b3wit.h (the entry points assert it)
+B3W_HD_INLINE uint64_t delta_key(uint32_t node, uint32_t status) { return 4ull * node + status; }
+B3W_HD_INLINE uint64_t delta_words(uint64_t units) { return (units - 1 + 63) / 64; }
+B3W_HD_INLINE uint32_t left_of32(uint32_t m) { return 1u << (31 - __builtin_clz(m - 1)); }
+
+B3W_HD_INLINE uint64_t delta_load64(const uint8_t *p) {
+#ifdef __HIP_DEVICE_COMPILE__
+  return *reinterpret_cast<const uint64_t *>(p);         // (every place of a blob and of an outboard is 8-byte aligned)
+#else
+  uint64_t v;
+  memcpy(&v, p, 8);
+  return v;
+#endif
+}
+// 32 bytes as 8 words; words: the place is a root's, 4-byte aligned only
+B3W_HD_INLINE void delta_load_cv(const uint8_t *p, uint32_t w[8], bool words) {
+#ifdef __HIP_DEVICE_COMPILE__
+  if (words) {
+    B3W_UNROLL
+    for (int k = 0; k < 8; ++k) w[k] = reinterpret_cast<const uint32_t *>(p)[k];
+  } else {
+    B3W_UNROLL
+    for (int k = 0; k < 4; ++k) {
+      const uint64_t v = reinterpret_cast<const uint64_t *>(p)[k];
+      w[2 * k] = (uint32_t)v; w[2 * k + 1] = (uint32_t)(v >> 32);
+    }
+  }
+#else
+  (void)words;
+  memcpy(w, p, 32);
+#endif
+}
+B3W_HD_INLINE bool delta_cv_is(const uint32_t a[8], const uint32_t b[8]) {
+  uint32_t d = 0;
+  B3W_UNROLL
+  for (int k = 0; k < 8; ++k) d |= a[k] ^ b[k];
+  return d == 0;
+}
+B3W_HD_INLINE bool delta_cv_equal(const uint8_t *a, const uint8_t *b, bool words) {
+  uint32_t x[8], y[8];
+  delta_load_cv(a, x, words);
+  delta_load_cv(b, y, words);
+  return delta_cv_is(x, y);
+}
+
+// node p < total - 1 of the tree over `total` units: its span [lo, lo + cnt), its parent's position and the half of the parent's node
+// that stores its CV (p = 0: neither)
+struct DeltaNode { uint32_t lo, cnt, parent, side; };
+B3W_HD_INLINE DeltaNode delta_node(uint32_t total, uint32_t p) {
+  DeltaNode r{0, total, 0, 0};
+  uint32_t pos = 0;
+  while (pos != p) {
+    const uint32_t k = left_of32(r.cnt);
+    r.parent = pos;
+    if (p < pos + k) { r.side = 0; pos += 1; r.cnt = k; } else { r.side = 1; pos += k; r.lo += k; r.cnt -= k; }
+  }
+  return r;
+}
+// does the tree over `total` units have a parent node over units [lo, lo + cnt), cnt >= 2?  -> its position, and 2 * (its parent's
+// position) + (1: the right half) where its CV is stored (the root: 0)
+B3W_HD_INLINE bool delta_find(uint32_t total, uint32_t lo, uint32_t cnt, uint32_t &pos, uint32_t &half) {
+  uint32_t p = 0, l = 0, c = total;
+  half = 0;
+  for (;;) {
+    if (l == lo && c == cnt) { pos = p; return true; }
+    if (c <= cnt) return false;                            // (c > cnt >= 2 below)
+    const uint32_t k = left_of32(c);
+    half = 2 * p;
+    if (lo < l + k) {
+      if (lo + cnt > l + k) return false;                  // it straddles the split
+      p += 1; c = k;
+    } else { half += 1; p += k; l += k; c -= k; }
+  }
+}
+// the byte of a's outboard that stores the CV of a's node over units [lo, lo + cnt), where a (na chunks, ua units) has such a node
+// below its root and it covers the same chunks as in b (nb chunks); 0: a holds no such node.  pos_a: the node's position in a.
+B3W_HD_INLINE uint64_t delta_held_at(uint32_t na, uint32_t nb, uint32_t ua, uint32_t g, uint32_t lo, uint32_t cnt, uint32_t &pos_a) {
+  uint32_t half;
+  if (!delta_find(ua, lo, cnt, pos_a, half) || pos_a == 0) return 0;
+  const uint64_t end = (uint64_t)(lo + cnt) << g;
+  if ((end < na ? end : na) != (end < nb ? end : nb)) return 0;
+  return 8 + 32ull * half;
+}
+
+// one pair as both calls see it: a's outboard (null: the replica holds nothing), the two roots, the chunk and unit counts
+struct DeltaSides {
+  const uint8_t *ob_a;
+  const uint8_t *root_a, *root_b;                          // (4-byte aligned)
+  uint32_t na, nb, ua, ub, g;
+};
+// is b's root node SAME: equal chunk counts and equal roots
+B3W_HD_INLINE bool delta_root_same(const DeltaSides &s) { return s.ob_a && s.na == s.nb && delta_cv_equal(s.root_a, s.root_b, true); }
+// the provider's verdict: is node p < ub - 1 of b (outboard ob_b) SAME
+B3W_HD_INLINE bool delta_node_same(const DeltaSides &s, const uint8_t *ob_b, uint32_t p) {
+  if (p == 0) return delta_root_same(s);
+  if (!s.ob_a) return false;
+  const DeltaNode nd = delta_node(s.ub, p);
+  uint32_t pos_a;
+  const uint64_t at_a = delta_held_at(s.na, s.nb, s.ua, s.g, nd.lo, nd.cnt, pos_a);
+  return at_a && delta_cv_equal(s.ob_a + at_a, ob_b + 8 + 64ull * nd.parent + 32 * nd.side, false);
+}
+
+// the replica's verdict on bit p < 64 * W of a blob (its first byte: blob; cap: the nodes its extent holds behind header and bitmap):
+// DELTA_OK or the fault's key.  rank(q): the set bits of the bitmap below bit q.  A node is read only where its rank is below cap;
+// a rank at or above cap means k or the bitmap's count is past the extent, which delta_check_head reports at node 0, the least key.
+template <class Rank>
+B3W_HD_INLINE uint64_t delta_check_node(const DeltaSides &s, const uint8_t *blob, uint64_t cap, uint32_t p, Rank rank) {
+  const uint32_t nodes = s.ub - 1;
+  const uint8_t *bitmap = blob + 16, *base = bitmap + 8 * delta_words(s.ub);
+  const bool present = (delta_load64(bitmap + 8 * (p >> 6)) >> (p & 63)) & 1;
+  if (p >= nodes) return present ? delta_key(p, DELTA_MALFORMED) : DELTA_OK;      // a pad bit
+  if (!present) return p == 0 && !delta_root_same(s) ? delta_key(0, DELTA_MALFORMED) : DELTA_OK;
+  const uint64_t r = rank(p);
+  if (r >= cap) return DELTA_OK;
+  const DeltaNode nd = delta_node(s.ub, p);
+  if (p && !((delta_load64(bitmap + 8 * (nd.parent >> 6)) >> (nd.parent & 63)) & 1)) return delta_key(p, DELTA_MALFORMED);
+  uint32_t m[16], h[8], o[8], want[8];
+  delta_load_cv(base + 64 * r, m, false);
+  delta_load_cv(base + 64 * r + 32, m + 8, false);
+  iv(h);
+  blake3_cv(h, m, 0, 0, 64, 4u | (p ? 0u : 8u), o);
+  if (p) delta_load_cv(base + 64 * rank(nd.parent) + 32 * nd.side, want, false);      // (the parent is present and in front: its rank is below r)
+  else delta_load_cv(s.root_b, want, true);
+  if (!delta_cv_is(o, want)) return delta_key(p, DELTA_BAD_HASH);
+  const uint32_t k = left_of32(nd.cnt);
+  uint64_t key = DELTA_OK;
+  for (uint32_t side = 0; side < 2; ++side) {              // an absent child that is a parent subtree: a must hold it
+    const uint32_t clo = side ? nd.lo + k : nd.lo, ccnt = side ? nd.cnt - k : k, pc = side ? p + k : p + 1;
+    if (ccnt < 2 || ((delta_load64(bitmap + 8 * (pc >> 6)) >> (pc & 63)) & 1)) continue;
+    uint32_t pos_a, cv_a[8];
+    const uint64_t at_a = s.ob_a ? delta_held_at(s.na, s.nb, s.ua, s.g, clo, ccnt, pos_a) : 0;
+    bool held = at_a != 0;
+    if (held) {
+      delta_load_cv(s.ob_a + at_a, cv_a, false);
+      held = delta_cv_is(cv_a, m + 8 * side);
+    }
+    if (!held && delta_key(pc, DELTA_NOT_HELD) < key) key = delta_key(pc, DELTA_NOT_HELD);
+  }
+  return key;
+}
+// the blob's header against the call's len_b, the bitmap's count and the extent
+B3W_HD_INLINE uint64_t delta_check_head(const uint8_t *blob, uint64_t len_b, uint64_t cap, uint64_t count) {
+  const uint64_t k = delta_load64(blob + 8);
+  return delta_load64(blob) != len_b || k != count || k > cap ? delta_key(0, DELTA_MALFORMED) : DELTA_OK;
+}
+// where the replica's outboard takes node p < ub - 1 from when it is absent from the blob: the byte of a's outboard (the pair passed)
+B3W_HD_INLINE uint64_t delta_copy_from(const DeltaSides &s, uint32_t p) {
+  const DeltaNode nd = delta_node(s.ub, p);
+  uint32_t pos_a = 0, half;                                // (a passed pair: every absent node lies in a subtree a holds in the same shape;
+  return s.ob_a && delta_find(s.ua, nd.lo, nd.cnt, pos_a, half) ? 8 + 64ull * pos_a : 0;      // 0: it does not, nothing is copied)
+}
+
 // ---- range slices: places (the format is described at the range kernels in b3w_bao.hip) ------------------------------------------------
 // U(a, c), a <= c < n
 B3W_HD inline uint64_t range_nodes(uint64_t n, uint64_t a, uint64_t c) {

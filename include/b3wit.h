@@ -1092,6 +1092,107 @@ int32_t b3w_bao_outboard_diff(const uint8_t *outboard_a, uint64_t len_a, const u
                               const uint8_t *outboard_b, uint64_t len_b, const uint32_t *root_b /* 8 u32 */, uint32_t group_log_b,
                               uint64_t *same_words);
 
+/* ---- outboard delta: the nodes of a new version that a replica does not hold, served and verified on arrival (still ABI 1.4: new
+ * names only) ----
+ * The diff above needs ALL of b's outboard on the replica (67 MB for 1 GiB) and believes it.  A DELTA carries only the parent nodes
+ * of b that a does not already hold, and the replica checks every one of them against b's root before it writes a byte - by hashing
+ * the nodes alone, no file byte is read on either side.  The outboard the replica ends with is consistent with b's root down to every
+ * unit's chaining value, so the diff -> b3w_bao_have_runs_device -> set slices -> b3w_bao_set_slice_ingest_device chain then runs
+ * against an outboard the replica can trust, and the chunks may come from anybody.
+ * SIDES AND PAIRS as in the diff call, but both sides have ONE group_log g: U = units of 2^g chunks, b's tree has U_b - 1 parent nodes
+ * in pre-order, node p spans units [lo, lo + cnt), cnt >= 2.  host_pair_a[i] == B3W_BAO_DELTA_NO_A: the replica holds nothing, and
+ * nothing is SAME for that pair (side a may then be all null with n_files_a = 0).
+ * SAME.  The root (p = 0) is SAME iff the two files have the same chunk count and equal roots.  Node p > 0 is SAME iff a's tree has a
+ * parent node over the same units, that node covers the same chunks in both files (min((lo + cnt) << g, num_chunks) agrees), it is not
+ * a's root, and the two STORED CVs - the half of the node above that holds the node's CV, in each outboard - are equal.
+ * The DELTA of a pair is b's parent nodes that are not SAME, pointwise, in pre-order.  On two outboards that are each consistent with
+ * their root this is "descend from the two roots and stop at equal nodes" (equal CVs mean equal nodes below); the provider is defined
+ * pointwise so that it is exact on any input.
+ * BLOB of a pair, little-endian, 8-byte aligned: 8 bytes len_b; 8 bytes k, the nodes present; W = ceil((U_b - 1) / 64) bitmap words
+ * (bit p set iff node p is present, pad bits zero); the k present nodes in pre-order, each byte for byte b's outboard node.  A file
+ * of one unit: W = 0, k = 0, 16 bytes.  b3w_bao_outboard_delta_bound = 16 + 8 W + 64 (U_b - 1) always suffices.
+ * WHAT THE APPLY PROVES: the outboard it writes is consistent with b's root GIVEN that the subtrees copied from a were consistent
+ * with the CVs a stores for them (a's outboard is the replica's own).  It proves nothing about file bytes: the chunks still arrive
+ * through the verifying receivers.
+ * When not to (MI355X, tools/bao_delta_measure.py; medians of whole calls, the copy's two series 0.00004 ms apart).
+ * One 1 GiB file, 1 % of its chunks rewritten, full outboards: the blob is 4.7 MB against b's outboard of 67.1 MB (0.07 of it); the
+ * provider takes 0.065 ms where copying the two outboards takes 0.046 and the diff 0.032; the apply takes 0.108 ms where copying
+ * b's outboard - what a trusting replica did - takes 0.022 and b3w_bao_verify_batch_device over b's RESIDENT file, the only check
+ * there was, 0.432.  With group outboards of 16 chunks the same edits touch 47 % of the nodes: 1.96 MB against 4.19, provider 0.039
+ * (copy 0.0096, diff 0.021), apply 0.049 (copy 0.0068, verify 0.421) - at that grain a rewritten 1 % of chunks is half the tree, and
+ * the delta saves half the bytes, no more.  HALF of the chunks rewritten (full outboards): 57.8 MB against 67.1 (0.86), provider 0.083,
+ * apply 0.120 - the delta still costs less than verifying the file, but it saves almost nothing on the wire; send the outboard and
+ * check it (outboard_check's route: 0.150 ms for 1 GiB, 0.35 of the verification, and no file byte needed).  262 144 files of 4
+ * chunks, one chunk rewritten in every tenth: 9.6 MB against 52.4, but the provider takes 1.94 ms (diff 1.13, copy 0.034) and the
+ * apply 2.02 where the verification of the resident files takes 1.52 and the copy 0.018: the host's table (72 bytes a pair to upload,
+ * a few ns a pair to fill) and a workgroup's worth of scan per 1 024 pairs are the cost, and the kernels' share cannot be told apart
+ * from the table's in these figures.  So: not for very many tiny files that are resident anyway, not where most of the tree
+ * changed, and never as a check of file bytes. */
+#define B3W_BAO_DELTA_NO_A 0xFFFFFFFFu
+#define B3W_BAO_DELTA_MALFORMED 1
+#define B3W_BAO_DELTA_BAD_HASH 2
+#define B3W_BAO_DELTA_NOT_HELD 3
+/* Host only.  The bytes that always suffice for one pair's blob (0: a group_log above the maximum); the extents of the pairs' blobs
+ * at their bounds -> the total bytes, delta_first [n_pairs + 1] (host_pair_b NULL: pair i is file i; 0: a null pointer, a group_log
+ * above the maximum or a pair index not below n_files_b); the scratch both device calls want for these pairs (0 likewise). */
+uint64_t b3w_bao_outboard_delta_bound(uint64_t len_b, uint32_t group_log);
+uint64_t b3w_bao_outboard_delta_layout(const uint64_t *host_lens_b, uint32_t n_files_b, const uint32_t *host_pair_b, uint32_t n_pairs, uint32_t group_log,
+                                       uint64_t *delta_first);
+uint64_t b3w_bao_outboard_delta_scratch_bytes(const uint64_t *host_lens_b, uint32_t n_files_b, const uint32_t *host_pair_b, uint32_t n_pairs,
+                                              uint32_t group_log);
+/* THE PROVIDER.  Pair i's blob goes to bytes [host_delta_first[i], host_delta_first[i + 1]) of d_delta: the caller chooses the
+ * capacities, each extent 8-byte aligned and at least 16 + 8 W.  Every pair's header and bitmap are written whole, the nodes
+ * [0, min(k, what the extent holds)); d_n_nodes[i] is k AS FOUND, even above the capacity (the header's k too), and nothing beyond the
+ * extent is written - b3w_bao_have_runs_device's capacity rule.  No file byte is read and nothing is hashed.
+ * At most FOUR launches whatever the pair and node counts: mark (a wave per bitmap word, a lane per node, the ballot the word), count
+ * and scan (have_runs' scan over the words' counts), compact (a lane copies its node to its rank).  Nothing is allocated beyond
+ * d_scratch (b3w_bao_outboard_delta_scratch_bytes) and the context's staging (72 bytes a pair); asynchronous on `stream`; the host
+ * waits for nothing but this context's previous batch call.  n_pairs == 0 is a no-op.  B3W_E_BAD_ARGUMENT before anything is written
+ * for what b3w_bao_outboard_diff_device refuses, two different group_logs, an extent too small for its header and bitmap, a
+ * host_delta_first that is misaligned, does not rise (overlapping extents) or reaches past delta_bytes, a blob buffer that overlaps
+ * either outboard buffer, or a scratch that is null, misaligned or too small. */
+int32_t b3w_bao_outboard_delta_device(b3w_ctx *ctx, const uint64_t *host_lens_a, const uint64_t *host_ob_first_a, const uint8_t *d_outboards_a,
+                                      uint64_t outboards_a_bytes, const uint32_t *d_roots_a, uint32_t n_files_a, const uint64_t *host_lens_b,
+                                      const uint64_t *host_ob_first_b, const uint8_t *d_outboards_b, uint64_t outboards_b_bytes, const uint32_t *d_roots_b,
+                                      uint32_t n_files_b, uint32_t group_log_a, uint32_t group_log_b, const uint32_t *host_pair_a, const uint32_t *host_pair_b,
+                                      uint32_t n_pairs, const uint64_t *host_delta_first /* n_pairs + 1 */, uint8_t *d_delta, uint64_t delta_bytes,
+                                      uint64_t *d_n_nodes, void *d_scratch, uint64_t scratch_bytes, void *stream);
+/* THE REPLICA.  Side a is read only; of side b the call takes the lengths and the roots.  The blobs are UNTRUSTED: every index
+ * derived from a blob is bounded by the extent before it is used, and a hostile blob yields a status, never a read or write outside
+ * the buffers named in the call.  Per pair the status is the first that applies at the lowest node, d_first_bad that node (~0: none):
+ *   B3W_BAO_DELTA_MALFORMED  the header's length is not len_b, k is not the bitmap's popcount or k nodes reach past the extent (all
+ *                            three at node 0); a pad bit is set (at the bit's index); a present node whose parent is absent; the
+ *                            root absent although it is not SAME; the root present although U_b = 1 (k is not 0 then)
+ *   B3W_BAO_DELTA_BAD_HASH   a present node's parent compression (ROOT flag iff p = 0) is not b's root at p = 0, else not the half
+ *                            of its parent's node in the blob
+ *   B3W_BAO_DELTA_NOT_HELD   an absent child of a present node that is itself a parent subtree is not SAME against a's outboard (the
+ *                            CV taken from the present node against a's stored CV); with B3W_BAO_DELTA_NO_A every such child
+ * Status 0, and only then, writes the pair's output outboard whole at byte host_ob_first_out[i] of d_outboards_out: the length,
+ * present nodes at their pre-order places, every absent node from a's outboard at the place of the same span in a's tree.  Any other
+ * status leaves the output extent untouched.  The output extents lie in rising order of i and do not overlap.  Where the output
+ * buffer overlaps a's outboard buffer the call is IN PLACE: every pair's output is then a's own outboard (same place, U_a = U_b); the
+ * copies are no-ops and only present nodes are written - the equal-length recipe.  Any other overlap with a's outboards, and any
+ * overlap with the blob buffer, is refused.
+ * FOUR launches whatever the counts (count, scan, check, write; the write reads the pair's status on the device); no workgroup waits
+ * for another; scratch, staging and stream as the provider.  B3W_E_BAD_ARGUMENT before anything is written for what the provider
+ * refuses on side a, the lengths, the pairs and host_delta_first, and for the outputs as said above. */
+int32_t b3w_bao_outboard_delta_apply_device(b3w_ctx *ctx, const uint64_t *host_lens_a, const uint64_t *host_ob_first_a, const uint8_t *d_outboards_a,
+                                            uint64_t outboards_a_bytes, const uint32_t *d_roots_a, uint32_t n_files_a, const uint64_t *host_lens_b,
+                                            const uint32_t *d_roots_b, uint32_t n_files_b, uint32_t group_log, const uint32_t *host_pair_a,
+                                            const uint32_t *host_pair_b, uint32_t n_pairs, const uint64_t *host_delta_first /* n_pairs + 1 */,
+                                            const uint8_t *d_delta, uint64_t delta_bytes, const uint64_t *host_ob_first_out /* n_pairs */,
+                                            uint8_t *d_outboards_out, uint64_t outboards_out_bytes, int32_t *d_pair_status, uint64_t *d_first_bad,
+                                            void *d_scratch, uint64_t scratch_bytes, void *stream);
+/* Host only, ONE pair, the device calls' bytes and statuses (outboard_a NULL: B3W_BAO_DELTA_NO_A).  The provider writes into
+ * blob [blob_bytes >= 16 + 8 W] by the capacity rule and *n_nodes = k as found.  The replica reads blob [blob_bytes] and, with
+ * *status 0 only, writes outboard_out [8 + 64 (U_b - 1)], which may be outboard_a itself where U_a = U_b.  B3W_E_BAD_ARGUMENT for a
+ * null pointer, a group_log above the maximum, a file of more than 2^30 chunks or a blob_bytes below 16 + 8 W. */
+int32_t b3w_bao_outboard_delta(const uint8_t *outboard_a, uint64_t len_a, const uint32_t *root_a /* 8 u32 */, const uint8_t *outboard_b, uint64_t len_b,
+                               const uint32_t *root_b /* 8 u32 */, uint32_t group_log, uint8_t *blob, uint64_t blob_bytes, uint64_t *n_nodes);
+int32_t b3w_bao_outboard_delta_apply(const uint8_t *outboard_a, uint64_t len_a, const uint32_t *root_a /* 8 u32 */, uint64_t len_b,
+                                     const uint32_t *root_b /* 8 u32 */, uint32_t group_log, const uint8_t *blob, uint64_t blob_bytes,
+                                     uint8_t *outboard_out, int32_t *status, uint64_t *first_bad);
+
 /* ---- range slices: the slice of a run of chunks, extracted and taken in (still ABI 1.4: new names only) -------------
  * The run lists above name what is missing as rows (file, first chunk, chunks); the slice calls above carry ONE chunk a slice, so a
  * run of k chunks costs k slices and k whole paths (2 312 bytes for 1 024 of payload in a file of 2^20 chunks).  A RANGE SLICE carries
