@@ -261,6 +261,12 @@ def lib():
         "b3w_bao_slice_ingest_packed_device": (i32, [vp, vp, u64, vp, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp]),
         "b3w_bao_range_slice_ingest_packed_device": (i32, [vp, vp, u64, vp, u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, u64, vp]),
         "b3w_bao_set_slice_ingest_packed_device": (i32, [vp, vp, u64, vp, u32, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, u64, vp]),
+        "b3w_bao_set_slice_stream_cuts": (ctypes.c_int64, [u64, vp, vp, u32, u64, vp, u64]),
+        "b3w_bao_set_slice_stream_scratch_bytes": (u64, [u64, vp, vp, u32, u64]),
+        "b3w_bao_set_slice_stream_begin": (i32, [vp, u64, u32, vp, vp, u32, vp, u32, vp, u64, vp, vp, vp, vp, vp, vp, u64, vp, ctypes.POINTER(vp)]),
+        "b3w_bao_set_slice_stream_push": (i32, [vp, u64, vp, u64, vp]),
+        "b3w_bao_set_slice_stream_finish": (i32, [vp]),
+        "b3w_bao_set_slice_stream_free": (None, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -310,7 +316,9 @@ EXPORTED_SYMBOLS = ("b3w_abi_version", "b3w_identify_wasm", "b3w_create", "b3w_d
                     "b3w_bao_set_slice_size", "b3w_bao_set_slice_batch_layout", "b3w_bao_set_slice", "b3w_bao_set_slice_decode",
                     "b3w_bao_set_slice_ingest", "b3w_bao_set_slice_arena_device", "b3w_bao_set_slice_ingest_scratch_bytes",
                     "b3w_bao_set_slice_ingest_device", "b3w_sample_plan_set_slices_device", "b3w_bao_set_slice_packed_device",
-                    "b3w_bao_slice_ingest_packed_device", "b3w_bao_range_slice_ingest_packed_device", "b3w_bao_set_slice_ingest_packed_device")
+                    "b3w_bao_slice_ingest_packed_device", "b3w_bao_range_slice_ingest_packed_device", "b3w_bao_set_slice_ingest_packed_device",
+                    "b3w_bao_set_slice_stream_cuts", "b3w_bao_set_slice_stream_scratch_bytes", "b3w_bao_set_slice_stream_begin",
+                    "b3w_bao_set_slice_stream_push", "b3w_bao_set_slice_stream_finish", "b3w_bao_set_slice_stream_free")
 
 
 class graph_capture:

@@ -2197,6 +2197,139 @@ def verify_stream(ctx, source, length, d_outboard, d_root, window_bytes=DEFAULT_
         session.close()
 
 
+# ---- set slices taken in window by window as they arrive -------------------------------------------------------------------------------
+SET_SLICE_STREAM_MIN_WINDOW = 8 + 64 * (24 + 1023) + (1 << 20)   # B3W_BAO_SET_SLICE_STREAM_MIN_WINDOW: no row's segment is longer
+SET_SLICE_STREAM_CARRY_BYTES = 1552                    # B3W_BAO_SET_SLICE_STREAM_CARRY_BYTES
+SET_STREAM_ARENA, SET_STREAM_PACKED = 0, 1
+DEFAULT_SET_SLICE_WINDOW_BYTES = 64 << 20              # the fastest of 1.1, 8 and 64 MiB (a push costs about 0.17 ms whatever it holds)
+
+
+def set_slice_cuts(length, first_chunks, n_chunks, window_bytes):
+    """-> numpy uint64 [windows + 1]: the ascending offsets at which the set slice of these runs (ascending, disjoint) of a file of
+    `length` bytes is cut into windows of at most window_bytes (>= SET_SLICE_STREAM_MIN_WINDOW), each filled greedily with as many
+    whole rows as fit; from 0 to set_slice_size.  Host only; no step a chunk."""
+    fc, nc = _ranges(first_chunks, n_chunks)
+    L = lib()
+    k = L.b3w_bao_set_slice_stream_cuts(length, fc.ctypes.data, nc.ctypes.data, fc.size, window_bytes, None, 0)
+    if k < 0:
+        raise B3WError(-k, "b3w_bao_set_slice_stream_cuts: no run, a run that is empty or reaches past the file's chunk count, a list that is not "
+                           f"ascending and disjoint, a file of more than 2^30 chunks, or window_bytes below {SET_SLICE_STREAM_MIN_WINDOW}")
+    out = np.zeros(k + 1, dtype=np.uint64)
+    assert L.b3w_bao_set_slice_stream_cuts(length, fc.ctypes.data, nc.ctypes.data, fc.size, window_bytes, out.ctypes.data, out.size) == k
+    return out
+
+
+class SetSliceStream:
+    """ingest_set_slices / ingest_set_slices_packed for ONE set (one file) whose slice arrives in windows cut at row boundaries
+    (set_slice_cuts, or any cuts of the rows), pushed in slice order; the outputs are byte for byte the one-shot call's.  packed=False:
+    d_dest is the file's place in an arena (a uint8 CUDA view of at least `length` bytes, any alignment) and d_outboard its outboard;
+    packed=True: d_dest is the slot buffer (made here when None) and d_outboard may be None (decode).  The session makes its own
+    statuses and scratch; window_bytes sizes the scratch: no pushed window may hold more rows than a window of that many bytes can.
+    set_status is final for a window once its push is done on its stream: a bad window shows before the next one arrives.  Each push
+    must be ordered behind the one before (the same stream, or events): the carried nodes are a serial dependency."""
+
+    def __init__(self, ctx, length, first_chunks, n_chunks, d_root, d_dest=None, d_outboard=None, group_log=0, window_bytes=DEFAULT_SET_SLICE_WINDOW_BYTES,
+                 packed=False, d_have=None, stream=0):
+        self._h = ctypes.c_void_p()
+        if not 0 <= group_log <= MAX_GROUP_LOG:
+            raise B3WError(100, f"group_log {group_log} is not in 0 .. {MAX_GROUP_LOG}")
+        L = lib()
+        self.ctx, self.length, self.group_log, self.packed = ctx, int(length), group_log, bool(packed)
+        fc, nc = _ranges(first_chunks, n_chunks)
+        self.layout = set_slice_layout([self.length], np.zeros(fc.size, dtype=np.uint32), fc, nc)
+        total = int(self.layout["set_chunk_first"][-1])
+        need = L.b3w_bao_set_slice_stream_scratch_bytes(self.length, fc.ctypes.data, nc.ctypes.data, fc.size, window_bytes)
+        if not need:
+            raise B3WError(100, f"SetSliceStream: no run, or window_bytes {window_bytes} is below {SET_SLICE_STREAM_MIN_WINDOW}")
+        assert d_root.is_cuda and d_root.is_contiguous() and d_root.element_size() == 4 and d_root.numel() >= 8
+        dev = d_root.device
+        if self.packed and d_dest is None:
+            d_dest = torch.zeros(total * 1024, dtype=torch.uint8, device=dev)
+        if d_dest is None or (not self.packed and d_outboard is None):
+            raise B3WError(100, "SetSliceStream: an arena destination needs d_dest and d_outboard")
+        assert d_dest.is_cuda and d_dest.dtype == torch.uint8 and d_dest.is_contiguous()
+        if d_outboard is not None:
+            assert d_outboard.is_cuda and d_outboard.dtype == torch.uint8 and d_outboard.is_contiguous()
+            assert d_outboard.numel() >= group_outboard_size(self.length, group_log)
+        if d_have is not None:
+            _have_tensor("SetSliceStream", d_have, _u64([self.length]))
+        self.d_dest, self.d_outboard, self.d_root, self.d_have = d_dest, d_outboard, d_root, d_have
+        self.set_status = torch.full((1,), -1, dtype=torch.int32, device=dev)
+        self.set_first_bad = torch.full((1,), -2, dtype=torch.int64, device=dev)
+        self.chunk_status = torch.full((total,), -1, dtype=torch.int32, device=dev)
+        self.scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        _chk(ctx, L.b3w_bao_set_slice_stream_begin(ctx.handle, self.length, group_log, fc.ctypes.data, nc.ctypes.data, fc.size, d_root.data_ptr(),
+                                                   SET_STREAM_PACKED if self.packed else SET_STREAM_ARENA, d_dest.data_ptr() if d_dest.numel() else None,
+                                                   d_dest.numel(), d_outboard.data_ptr() if d_outboard is not None else None,
+                                                   d_have.data_ptr() if d_have is not None else None, self.chunk_status.data_ptr(),
+                                                   self.set_status.data_ptr(), self.set_first_bad.data_ptr(), self.scratch.data_ptr(), need,
+                                                   _stream(stream), ctypes.byref(self._h)), "b3w_bao_set_slice_stream_begin")
+
+    def push(self, offset, d_window, stream=0):
+        """slice bytes [offset, offset + d_window.numel()) lie in d_window (a uint8 CUDA view whose first byte is at 8 modulo 16 for
+        offset 0 and 16-byte aligned otherwise): from a cut to a cut, starting where the last window ended.  At most three launches."""
+        assert d_window.is_cuda and d_window.dtype == torch.uint8 and d_window.is_contiguous()
+        _chk(self.ctx, lib().b3w_bao_set_slice_stream_push(self._h, offset, d_window.data_ptr(), d_window.numel(), _stream(stream)),
+             "b3w_bao_set_slice_stream_push")
+
+    def finish(self):
+        """-> the dict ingest_set_slices (packed: ingest_set_slices_packed) returns for this set as a call of one; no launch"""
+        _chk(self.ctx, lib().b3w_bao_set_slice_stream_finish(self._h), "b3w_bao_set_slice_stream_finish")
+        out = dict(set_status=self.set_status, set_first_bad=self.set_first_bad, chunk_status=self.chunk_status, **self.layout)
+        if self.packed:
+            out.update(chunks=self.d_dest, slot_first=self.layout["set_chunk_first"])
+        return out
+
+    def close(self):
+        if self._h:
+            lib().b3w_bao_set_slice_stream_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        self.close()
+
+
+def ingest_set_slice_stream(ctx, source, length, first_chunks, n_chunks, d_root, d_dest=None, d_outboard=None, group_log=0,
+                            window_bytes=DEFAULT_SET_SLICE_WINDOW_BYTES, packed=False, d_have=None):
+    """ingest_set_slices for one set whose slice is NOT on the device: `source` (bytes-like, a numpy buffer, or an object with readinto,
+    read in order) holds the set slice and goes through a ring of two pinned host buffers and two device windows cut by
+    set_slice_cuts(window_bytes); the copies run on a side stream and are chained to the pushes (on the current stream) with events, so
+    window i + 1 is copied while window i is verified.  Device memory made here is 2 x window_bytes + the statuses + the scratch,
+    whatever the slice's size, where ingest_set_slices needs the whole slice resident.  When not to (MI355X, DESIGN.md §8g, the 593 MB
+    slice of a half-missing 1 GiB file, against a build of the commit before's one-shot receiver over the resident slice): a slice that
+    IS resident - a session of 9 windows of 64 MiB takes 4.66 ms against 3.39, 74 of 8 MiB 15.8, 986 of the least window 171.6 (50
+    times): a push costs about 0.17 ms whatever it holds, so window_bytes defaults to the largest measured.  Returns the dict ingest_set_slices returns for
+    this set as a call of one (packed=True: ingest_set_slices_packed's); the work is enqueued on the current stream."""
+    cuts = [int(x) for x in set_slice_cuts(length, first_chunks, n_chunks, window_bytes)]
+    session = SetSliceStream(ctx, length, first_chunks, n_chunks, d_root, d_dest, d_outboard, group_log, window_bytes, packed, d_have,
+                             stream=torch.cuda.current_stream().cuda_stream)
+    try:
+        size = max(b - a for a, b in zip(cuts, cuts[1:]))
+        fill = _reader(source, cuts[-1])
+        cur, side = torch.cuda.current_stream(), torch.cuda.Stream()
+        ring = min(2, len(cuts) - 1)
+        host = [torch.empty(size + 16, dtype=torch.uint8, pin_memory=True) for _ in range(ring)]
+        dev = [torch.empty(size + 16, dtype=torch.uint8, device=d_root.device) for _ in range(ring)]
+        copied, pushed = [torch.cuda.Event() for _ in range(ring)], [torch.cuda.Event() for _ in range(ring)]
+        side.wait_stream(cur)                                 # (the windows are the current stream's memory: what the caller enqueued before may still read a block they reuse)
+        for i, (a, b) in enumerate(zip(cuts, cuts[1:])):
+            k, lead = i % ring, 0 if a else 8                 # (the header's window starts at 8 modulo 16, as a packed slice does)
+            if i >= ring:
+                copied[k].synchronize()                       # the pinned buffer's last copy is through
+            fill(host[k].numpy()[lead:lead + b - a], a)
+            with torch.cuda.stream(side):
+                if i >= ring:
+                    side.wait_event(pushed[k])                # the device window's last push is through
+                dev[k][lead:lead + b - a].copy_(host[k][lead:lead + b - a], non_blocking=True)
+                copied[k].record(side)
+            cur.wait_event(copied[k])
+            session.push(a, dev[k][lead:lead + b - a], stream=cur.cuda_stream)
+            pushed[k].record(cur)
+        return session.finish()
+    finally:
+        session.close()
+
+
 # ---- files whose length is not known up front -----------------------------------------------------------------------------------------
 STREAM_OPEN = 2
 OPEN_STAGING_PAD = 16                                  # B3W_BAO_STREAM_OPEN_STAGING_PAD

@@ -4487,11 +4487,23 @@ __global__ __launch_bounds__(B) void b3w_bao_set_slice_packed_kernel(const SetDe
 // PACKED (b3w_bao_set_slice_ingest_packed_device): `arena` is a slot buffer, 1 024 bytes a wanted chunk in the order of chunk_status:
 // the copy loop's lane group p >> 6 is the wanted lane's rank in the row, so its slot is r.chunk_first + row->rank0 + (p >> 6); `obs`
 // may be null: no node and no header is stored (decode).
-template <int B, bool PACKED = false>
+// STREAM (b3w_bao_set_slice_stream_push): `slices` is a WINDOW of the set's slice that starts at slice offset r.slice, a cut, so the
+// row's places keep their values and every chunk and block node is read where the one-shot kernel reads it.  The only places in front of
+// the cut are the header (r.pad says so) and nodes above the block: the host marks those up[] entries SET_CARRIED | the node's offset in
+// `carry`, the session's carried area - one select a node load, none a chunk byte.  Nothing carried is trusted: it is hashed as a slice
+// node is.
+constexpr uint64_t SET_CARRIED = 1ull << 63;
+template <bool STREAM>
+__device__ __forceinline__ const uint8_t *set_up_at(const uint8_t *__restrict__ sl, const uint8_t *__restrict__ carry, uint64_t up) {
+  if constexpr (STREAM) return (up & SET_CARRIED) ? carry + (up & ~SET_CARRIED) : sl + up;
+  else return sl + up;
+}
+template <int B, bool PACKED = false, bool STREAM = false>
 __global__ __launch_bounds__(B) void b3w_bao_set_ingest_kernel(const SetDev *__restrict__ sets, const SetRow<B> *__restrict__ rows, uint32_t gl,
                                                                const uint8_t *__restrict__ slices, const uint32_t *__restrict__ roots,
                                                                uint8_t *__restrict__ arena, uint8_t *__restrict__ obs, int32_t *__restrict__ chunk_status,
-                                                               unsigned long long *__restrict__ have, uint4 *__restrict__ results) {
+                                                               unsigned long long *__restrict__ have, uint4 *__restrict__ results,
+                                                               const uint8_t *__restrict__ carry = nullptr) {
   __shared__ __attribute__((aligned(16))) uint32_t cv[B * 8];
   __shared__ uint32_t flags[B], listed[B];
   __shared__ SetLds<B> s;
@@ -4502,7 +4514,7 @@ __global__ __launch_bounds__(B) void b3w_bao_set_ingest_kernel(const SetDev *__r
   const uint64_t n = r.len ? (r.len + 1023) / 1024 : 1, a0 = (uint64_t)row->block * B;
   const uint32_t m = (uint32_t)(n - a0 < B ? n - a0 : B);
   const bool sole = n <= B;
-  const uint8_t *__restrict__ sl = slices + r.slice;
+  const uint8_t *__restrict__ sl = STREAM ? slices - r.slice : slices + r.slice;
   const uint32_t *__restrict__ root = roots + (uint64_t)r.file * 8;
   flags[t] = 0;
   if (t == 0) { worst = 0; first = ~0u; above = 0; }
@@ -4519,10 +4531,10 @@ __global__ __launch_bounds__(B) void b3w_bao_set_ingest_kernel(const SetDev *__r
   const RsAbove up = range_above(n, a0, m, t);
   if (t < up.depth) {
     uint32_t mw[16], ivv[8], o[8];
-    load_node(sl + row->up[t], mw);
+    load_node(set_up_at<STREAM>(sl, carry, row->up[t]), mw);
     iv(ivv);
     blake3_cv(ivv, mw, 0, 0, 64, 4u | (t == 0 ? 8u : 0u), o);
-    const uint32_t *want = t == 0 ? root : reinterpret_cast<const uint32_t *>(sl + row->up[t - 1] + (up.left ? 0 : 32));
+    const uint32_t *want = t == 0 ? root : reinterpret_cast<const uint32_t *>(set_up_at<STREAM>(sl, carry, row->up[t - 1]) + (up.left ? 0 : 32));
     if (!eq8(o, want)) atomicOr(&above, 1u);
   }
   for (uint32_t l = 0; (1u << l) < m; ++l) {
@@ -4538,11 +4550,11 @@ __global__ __launch_bounds__(B) void b3w_bao_set_ingest_kernel(const SetDev *__r
   }
   lds_barrier();
   if (t == 0) {                                            // slot 0: what the block's stored root node hashes to, or the CV of a block of one chunk
-    const uint32_t *want = up.depth ? reinterpret_cast<const uint32_t *>(sl + row->up[up.depth - 1] + (up.last_left ? 0 : 32)) : root;
+    const uint32_t *want = up.depth ? reinterpret_cast<const uint32_t *>(set_up_at<STREAM>(sl, carry, row->up[up.depth - 1]) + (up.last_left ? 0 : 32)) : root;
     if (!eq8(cv, want)) flags[0] |= m == 1 ? VER_UNIT : VER_TOP;
   }
   lds_barrier();
-  const uint2 hd = *reinterpret_cast<const uint2 *>(sl);
+  const uint2 hd = *reinterpret_cast<const uint2 *>(STREAM && r.pad ? carry : sl);
   const bool hdr = ((uint64_t)hd.x | ((uint64_t)hd.y << 32)) != r.len;
   uint32_t st = 0;
   if (mine) {
@@ -4582,7 +4594,7 @@ __global__ __launch_bounds__(B) void b3w_bao_set_ingest_kernel(const SetDev *__r
     if (listed[0]) {                                         // (every row with a verified chunk stores the nodes above it: the same verified bytes)
       if (t < up.depth) {
         uint8_t *node = node_at<true>(ob + 8, n, up.lo, up.cnt, gl);
-        if (node) copy_node(node, sl + row->up[t]);
+        if (node) copy_node(node, set_up_at<STREAM>(sl, carry, row->up[t]));
       }
       if (t == 0) *reinterpret_cast<uint2 *>(ob) = hd;       // the header (it is the length: just checked)
     }
@@ -4616,6 +4628,46 @@ __global__ __launch_bounds__(256) void b3w_bao_set_reduce_kernel(const SetDev *_
     f = f < of ? f : of;
   }
   if (lane == 0) { set_status[i] = (int32_t)w; set_first_bad[i] = f; }
+}
+
+// the tail of a streamed push, one workgroup: wave 0 folds the window's rows' results INTO the set's two outputs (the largest status,
+// the least first bad chunk; the pushes of a session are ordered, so a plain read and write), waves 1 .. 2 move what later windows
+// need into the carried area - behind the window's rows, which read it: the node at src[t] of the window to depth slot t (16 bytes a
+// lane), and the header if the window holds it.  Vector loads and stores only.
+struct SetStreamFold { uint64_t src[SET_UP]; uint32_t n_rows, header; };   // src[t]: the node's offset in the window, ~0: keep what is carried
+__global__ __launch_bounds__(256) void b3w_bao_set_stream_fold_kernel(const SetStreamFold f, const uint8_t *__restrict__ window,
+                                                                      const uint4 *__restrict__ results, int32_t *__restrict__ set_status,
+                                                                      unsigned long long *__restrict__ set_first_bad, uint8_t *__restrict__ carry) {
+  const uint32_t t = threadIdx.x;
+  if (t < 64) {
+    uint32_t w = 0;
+    unsigned long long fb = ~0ull;
+    for (uint32_t j = t; j < f.n_rows; j += 64) {
+      const uint4 v = results[j];
+      const unsigned long long at = (unsigned long long)v.z | ((unsigned long long)v.w << 32);
+      w = w > v.x ? w : v.x;
+      fb = fb < at ? fb : at;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d /= 2) {
+      const uint32_t ow = __shfl_xor(w, d);
+      const unsigned long long of = __shfl_xor(fb, d);
+      w = w > ow ? w : ow;
+      fb = fb < of ? fb : of;
+    }
+    if (t == 0) {
+      const int32_t was = *set_status;
+      const unsigned long long first = *set_first_bad;
+      if ((int32_t)w > was) *set_status = (int32_t)w;
+      if (fb < first) *set_first_bad = fb;
+    }
+  } else if (t < 64 + SET_UP * 4) {
+    const uint32_t q = t - 64, depth = q >> 2, part = q & 3;
+    const uint64_t src = f.src[depth];
+    if (src != ~0ull) reinterpret_cast<uint4 *>(carry + 16)[q] = *reinterpret_cast<const uint4 *>(window + src + 16 * part);
+  } else if (t == 64 + SET_UP * 4 && f.header) {
+    *reinterpret_cast<uint2 *>(carry) = *reinterpret_cast<const uint2 *>(window);
+  }
 }
 
 // THE PLANNER (b3w_sample_plan_range_kernel on the set receiver's rows): b3w_sample_plan_slices_kernel's records and statuses for the
@@ -5005,5 +5057,170 @@ int32_t b3w_sample_plan_set_slices_device(b3w_ctx *ctx, const uint64_t *host_len
                      reinterpret_cast<unsigned long long *>(d_set_first_bad));
   return batch_launched(ctx, st, "sample plan set slices launch");
 }
+
+}  // extern "C"
+
+// ---- set slices in windows: one set's slice taken in as it arrives (b3wit.h "set slices in windows") ----------------------------------
+// A host object: the set's row table (built once, the one-shot call's rows), the rows' cuts, the caller's device pointers and how far
+// the slice has come.  No device memory and no event of its own: the carried area and the rows' results lie in the caller's scratch.
+struct b3w_bao_set_stream {
+  b3w_ctx *ctx = nullptr;
+  uint64_t len = 0;
+  uint32_t gl = 0;
+  bool packed = false, shrt = false, finished = false;
+  uint8_t *dest = nullptr, *ob = nullptr, *carry = nullptr;
+  const uint32_t *root = nullptr;
+  unsigned long long *have = nullptr, *first_bad = nullptr;
+  int32_t *chunk_status = nullptr, *set_status = nullptr;
+  uint4 *res = nullptr;
+  uint64_t row_cap = 0, row_bytes = 0, next = 0;           // the rows a window may have; a table row's bytes; the first row not pushed
+  std::vector<uint64_t> cut;                               // n_rows + 1
+  std::vector<uint8_t> rows;                               // SetRow<64> or SetRow<B3W_TILE>, in the table's order
+};
+
+namespace {
+
+// the session's rows [i, j) into the staging behind their SetDev: the places in front of the window's cut marked as carried, and what
+// the push's tail must carry on - a depth's last node above a block that lies in this window
+template <int B>
+void set_stream_rows(const b3w_bao_set_stream *s, uint64_t i, uint64_t j, uint8_t *staging, SetStreamFold &fold) {
+  const uint64_t at = s->cut[i];
+  SetRow<B> *out = reinterpret_cast<SetRow<B> *>(staging);
+  memcpy(out, s->rows.data() + i * sizeof(SetRow<B>), (size_t)((j - i) * sizeof(SetRow<B>)));
+  for (uint64_t r = 0; r < j - i; ++r)
+    for (uint32_t t = 0; t < SET_UP && out[r].up[t]; ++t) {
+      if (out[r].up[t] < at) out[r].up[t] = SET_CARRIED | (16 + 64ull * t);
+      else fold.src[t] = out[r].up[t] - at;
+    }
+}
+
+template <int B, bool PACKED>
+void set_stream_launch(const b3w_bao_set_stream *s, uint32_t n, const uint8_t *d_table, const uint8_t *d_window, hipStream_t st) {
+  hipLaunchKernelGGL((b3w_bao_set_ingest_kernel<B, PACKED, true>), dim3(n), dim3(B), 0, st, reinterpret_cast<const SetDev *>(d_table),
+                     reinterpret_cast<const SetRow<B> *>(d_table + sizeof(SetDev)), s->gl, d_window, s->root, s->dest, s->ob, s->chunk_status, s->have, s->res,
+                     (const uint8_t *)s->carry);
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t b3w_bao_set_slice_stream_begin(b3w_ctx *ctx, uint64_t len, uint32_t group_log, const uint64_t *host_first, const uint64_t *host_count,
+                                       uint32_t n_ranges, const uint32_t *d_root, uint32_t dest_kind, uint8_t *d_dest, uint64_t dest_bytes,
+                                       uint8_t *d_outboard, uint64_t *d_have, int32_t *d_chunk_status, int32_t *d_set_status, uint64_t *d_set_first_bad,
+                                       void *d_scratch, uint64_t scratch_bytes, void *stream, b3w_bao_set_stream **out_session) {
+  const char *call = "bao set slice stream begin";
+  if (!ctx) return B3W_E_BAD_ARGUMENT;
+  if (!out_session) return refuse(ctx, call, "a null session pointer");
+  *out_session = nullptr;
+  B3W_TRY(group_log_ok(ctx, call, group_log));
+  if (dest_kind != B3W_BAO_SET_STREAM_ARENA && dest_kind != B3W_BAO_SET_STREAM_PACKED) return refuse(ctx, call, "an unknown destination kind");
+  const bool packed = dest_kind == B3W_BAO_SET_STREAM_PACKED;
+  if (((uintptr_t)d_have & 7) || ((uintptr_t)d_chunk_status & 3)) return refuse(ctx, call, "d_have is not 8-byte or d_chunk_status not 4-byte aligned");
+  if (!n_ranges) return refuse(ctx, call, "a set has at least one run");
+  if ((!packed && !d_outboard) || !d_root || !host_first || !host_count || !d_set_status || !d_set_first_bad) return refuse(ctx, call, "a null pointer");
+  if ((uintptr_t)d_outboard & 7) return refuse(ctx, call, "d_outboard is not 8-byte aligned");
+  if (((uintptr_t)d_set_status & 3) || ((uintptr_t)d_set_first_bad & 7)) return refuse(ctx, call, "d_set_status is not 4-byte or d_set_first_bad not 8-byte aligned");
+  const std::vector<uint32_t> files(n_ranges, 0);
+  const uint64_t off0 = 0;
+  SetList list;
+  B3W_TRY(set_list_ok(ctx, call, d_dest, dest_bytes, packed ? nullptr : &off0, &len, 1, files.data(), host_first, host_count, n_ranges, list));
+  if (packed) B3W_TRY(slots_ok(ctx, call, d_dest, dest_bytes, list.chunks));
+  if (scratch_bytes < B3W_BAO_SET_SLICE_STREAM_CARRY_BYTES + 16) return refuse(ctx, call, "the scratch is smaller than b3w_bao_set_slice_stream_scratch_bytes says for the least window");
+  if (!d_scratch || ((uintptr_t)d_scratch & 15)) return refuse(ctx, call, "the scratch is null or not 16-byte aligned");
+  ON_DEVICE(ctx);
+  b3w_bao_set_stream *s = new b3w_bao_set_stream;
+  const SetEnt &e = list.sets[0];
+  b3w_int_set_stream_cuts(len, host_first, host_count, n_ranges, list, s->cut);
+  s->shrt = e.shrt;
+  const uint64_t n_rows = s->cut.size() - 1, B = s->shrt ? 64 : B3W_TILE;
+  s->ctx = ctx; s->len = len; s->gl = group_log; s->packed = packed;
+  s->dest = d_dest; s->ob = d_outboard; s->root = d_root;
+  s->have = reinterpret_cast<unsigned long long *>(d_have); s->first_bad = reinterpret_cast<unsigned long long *>(d_set_first_bad);
+  s->chunk_status = d_chunk_status; s->set_status = d_set_status;
+  s->carry = reinterpret_cast<uint8_t *>(d_scratch);
+  s->res = reinterpret_cast<uint4 *>(s->carry + B3W_BAO_SET_SLICE_STREAM_CARRY_BYTES);
+  s->row_cap = (scratch_bytes - B3W_BAO_SET_SLICE_STREAM_CARRY_BYTES) / 16;
+  if (s->row_cap > n_rows) s->row_cap = n_rows;
+  s->row_bytes = s->shrt ? sizeof(SetRow<64>) : sizeof(SetRow<(int)B3W_TILE>);
+  s->rows.resize((size_t)(n_rows * s->row_bytes));
+  uint64_t last = ~0ull, made = 0;
+  bool fits = e.rows == n_rows && e.shrt == s->shrt;
+  for (uint64_t i = 0; i < n_ranges && fits; ++i)
+    for (uint64_t blk = host_first[i] / B; blk <= (host_first[i] + host_count[i] - 1) / B && fits; ++blk) {
+      if (blk == last) continue;
+      last = blk;
+      uint8_t *at = s->rows.data() + made++ * s->row_bytes;
+      fits = s->shrt ? set_make_row<64>(*reinterpret_cast<SetRow<64> *>(at), 0, blk, len, host_first, host_count, n_ranges, list.ufirst.data(), list.rank.data())
+                     : set_make_row<(int)B3W_TILE>(*reinterpret_cast<SetRow<(int)B3W_TILE> *>(at), 0, blk, len, host_first, host_count, n_ranges, list.ufirst.data(), list.rank.data());
+    }
+  if (!fits) { delete s; return refuse(ctx, call, "the rows do not add up");   /* (never: the cuts and the list count the same rows) */ }
+  int32_t rc = B3W_OK;
+  hipStream_t st = (hipStream_t)stream;
+  // the ring's slots grown now, so that a push allocates nothing (a slot in flight keeps its size until a push needs it)
+  for (uint32_t k = 0; k < b3w_ctx::B3W_MANY_SLOTS && rc == B3W_OK; ++k) {
+    b3w_ctx::ManySlot *slot = nullptr;
+    rc = many_staging(ctx, sizeof(SetDev) + s->row_cap * s->row_bytes, &slot);
+  }
+  if (rc == B3W_OK) {
+    hipError_t err = hipMemsetAsync(d_set_status, 0, 4, st);
+    if (err == hipSuccess) err = hipMemsetAsync(d_set_first_bad, 0xff, 8, st);
+    if (err != hipSuccess) rc = hip_fail(ctx, err, "bao set slice stream begin: hipMemsetAsync");
+  }
+  if (rc != B3W_OK) { delete s; return rc; }
+  *out_session = s;
+  return B3W_OK;
+}
+
+int32_t b3w_bao_set_slice_stream_push(b3w_bao_set_stream *s, uint64_t offset, const uint8_t *d_window, uint64_t bytes, void *stream) {
+  const char *call = "bao set slice stream push";
+  if (!s) return B3W_E_BAD_ARGUMENT;
+  b3w_ctx *ctx = s->ctx;
+  const uint64_t n_rows = s->cut.size() - 1, i = s->next;
+  if (s->finished) return refuse(ctx, call, "the session is finished");
+  if (i == n_rows) return refuse(ctx, call, "the slice has been pushed to its end");
+  if (!d_window || !bytes) return refuse(ctx, call, "a null window or no bytes");
+  if (offset != s->cut[i]) return refuse(ctx, call, "out of order: the window starts at slice byte " + std::to_string(offset) + ", the last one ended at " + std::to_string(s->cut[i]));
+  if (bytes > s->cut[n_rows] - offset) return refuse(ctx, call, "the window reaches past the slice's end (" + std::to_string(s->cut[n_rows]) + " bytes)");
+  const uint64_t j = (uint64_t)(std::lower_bound(s->cut.begin() + (size_t)i + 1, s->cut.end(), offset + bytes) - s->cut.begin());
+  if (s->cut[j] != offset + bytes) return refuse(ctx, call, "the window does not end on a cut: slice byte " + std::to_string(offset + bytes) + " lies inside row " + std::to_string(j - 1) + ", which ends at " + std::to_string(s->cut[j]));
+  if (((uintptr_t)d_window & 15) != (i ? 0u : 8u)) return refuse(ctx, call, i ? "the window's first byte is not 16-byte aligned" : "the first window's first byte does not lie at 8 modulo 16");
+  if (j - i > s->row_cap) return refuse(ctx, call, "the window has " + std::to_string(j - i) + " rows, the scratch holds the results of " + std::to_string(s->row_cap));
+  ON_DEVICE(ctx);
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t up_bytes = sizeof(SetDev) + (j - i) * s->row_bytes;
+  b3w_ctx::ManySlot *slot = nullptr;
+  B3W_TRY(many_staging(ctx, up_bytes, &slot));
+  // the set as this window sees it: its slice "starts" a cut in front of the window; pad: the header is carried
+  *reinterpret_cast<SetDev *>(slot->h) = SetDev{s->len, 0, 0, offset, 0, 0, 0, 0, (uint32_t)(j - i), i ? 1u : 0u};
+  SetStreamFold fold;
+  for (uint32_t t = 0; t < SET_UP; ++t) fold.src[t] = ~0ull;
+  fold.n_rows = (uint32_t)(j - i); fold.header = i ? 0u : 1u;
+  if (s->shrt) set_stream_rows<64>(s, i, j, slot->h + sizeof(SetDev), fold);
+  else set_stream_rows<(int)B3W_TILE>(s, i, j, slot->h + sizeof(SetDev), fold);
+  // (as many_upload: a copy that was not enqueued reads nothing, so the slot stays free; once it is enqueued many_launched releases it)
+  HIP_TRY(ctx, hipMemcpyAsync(slot->d, slot->h, (size_t)up_bytes, hipMemcpyHostToDevice, st));
+  const uint32_t n = (uint32_t)(j - i);
+  if (s->shrt) {
+    if (s->packed) set_stream_launch<64, true>(s, n, slot->d, d_window, st); else set_stream_launch<64, false>(s, n, slot->d, d_window, st);
+  } else {
+    if (s->packed) set_stream_launch<(int)B3W_TILE, true>(s, n, slot->d, d_window, st); else set_stream_launch<(int)B3W_TILE, false>(s, n, slot->d, d_window, st);
+  }
+  hipLaunchKernelGGL(b3w_bao_set_stream_fold_kernel, dim3(1), dim3(256), 0, st, fold, d_window, (const uint4 *)s->res, s->set_status, s->first_bad, s->carry);
+  B3W_TRY(many_launched(ctx, slot, st, "bao set slice stream push launch"));
+  s->next = j;
+  return B3W_OK;
+}
+
+int32_t b3w_bao_set_slice_stream_finish(b3w_bao_set_stream *s) {
+  if (!s) return B3W_E_BAD_ARGUMENT;
+  const uint64_t n_rows = s->cut.size() - 1;
+  if (s->finished) return refuse(s->ctx, "bao set slice stream finish", "the session is finished");
+  if (s->next != n_rows) return refuse(s->ctx, "bao set slice stream finish", std::to_string(n_rows - s->next) + " of " + std::to_string(n_rows) + " rows have not been pushed: the slice is at byte " + std::to_string(s->cut[s->next]) + " of " + std::to_string(s->cut[n_rows]));
+  s->finished = true;
+  return B3W_OK;
+}
+
+void b3w_bao_set_slice_stream_free(b3w_bao_set_stream *s) { delete s; }
 
 }  // extern "C"

@@ -447,6 +447,43 @@ std::string b3w_int_slots_wrong(const void *d_chunks, uint64_t chunks_bytes, uin
   return std::string();
 }
 
+// ---- set slices taken in window by window: the cuts (b3wit.h "set slices in windows") ---------------------------------------------------
+// cut[r], r > 0, is the end of the last wanted chunk in front of row r's block: the elements between that chunk and the row's first wanted
+// chunk cf are the nodes of cf's path that do not hold the chunk before - every one has c0 = cf.  The rows are walked with the runs (the
+// run that first reaches into a new block is the one being walked), a place is SetRuns' closed form: O(rows + runs), O(depth) a run on
+// the file's ragged right edge, no step a chunk.
+void b3w_int_set_stream_cuts(uint64_t len, const uint64_t *first, const uint64_t *count, uint32_t n_ranges, const SetList &l, std::vector<uint64_t> &cut) {
+  const SetEnt &e = l.sets[0];
+  const uint64_t n = num_chunks(len), B = e.shrt ? 64 : B3W_TILE;
+  auto at = [&](uint64_t i, uint64_t c) { return 8 + 64 * set_nodes(n, l.ufirst[i], first[i], c) + 1024 * (l.rank[i] + (c - first[i])); };
+  cut.clear();
+  cut.reserve((size_t)e.rows + 1);
+  uint64_t last = ~0ull;
+  for (uint64_t i = 0; i < n_ranges; ++i)
+    for (uint64_t blk = first[i] / B; blk <= (first[i] + count[i] - 1) / B; ++blk) {
+      if (blk == last) continue;
+      last = blk;
+      const uint64_t a0 = blk * B;
+      if (cut.empty()) cut.push_back(0);                  // (the header rides with row 0)
+      else cut.push_back(1024 + (a0 > first[i] ? at(i, a0 - 1) : at(i - 1, first[i - 1] + count[i - 1] - 1)));
+    }
+  const uint64_t c_last = first[n_ranges - 1] + count[n_ranges - 1] - 1;
+  cut.push_back(at(n_ranges - 1, c_last) + chunk_bytes(len, c_last));   // (set_slice_bytes, from the list's state)
+}
+
+bool b3w_int_set_stream_cuts(uint64_t len, const uint64_t *first, const uint64_t *count, uint32_t n_ranges, std::vector<uint64_t> &cut, bool *shrt,
+                             std::string &why) {
+  cut.clear();
+  if (!n_ranges || !first || !count) { why = "a set has at least one run"; return false; }
+  if (num_chunks(len) > (1ull << 30)) { why = "its file has more than 2^30 chunks"; return false; }
+  const std::vector<uint32_t> files(n_ranges, 0);
+  SetList l;
+  if (!b3w_int_set_list(&len, 1, files.data(), first, count, n_ranges, l)) { why = l.why; return false; }
+  b3w_int_set_stream_cuts(len, first, count, n_ranges, l, cut);
+  if (shrt) *shrt = l.sets[0].shrt;
+  return true;
+}
+
 extern "C" {
 
 // ---- sizes and layouts ----------------------------------------------------------------------------------------------------------------
@@ -859,6 +896,45 @@ uint64_t b3w_bao_set_slice_ingest_scratch_bytes(const uint64_t *host_lens, uint3
   SetList l;
   if (!b3w_int_set_list(host_lens, n_files, host_files, host_first, host_count, n_ranges, l)) return 0;
   return (l.big + l.small) * 16;                          // a row's status and first bad chunk
+}
+
+int64_t b3w_bao_set_slice_stream_cuts(uint64_t len, const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges, uint64_t max_window_bytes,
+                                      uint64_t *cuts_out, uint64_t cap) {
+  std::vector<uint64_t> cut;
+  std::string why;
+  if (max_window_bytes < B3W_BAO_SET_SLICE_STREAM_MIN_WINDOW || !b3w_int_set_stream_cuts(len, host_first, host_count, n_ranges, cut, nullptr, why))
+    return -B3W_E_BAD_ARGUMENT;
+  // greedy: a window takes whole rows while they fit (a row always fits: it is never longer than the least window)
+  const size_t rows = cut.size() - 1;
+  uint64_t windows = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    windows = 0;
+    for (size_t i = 0; i < rows;) {
+      size_t j = i + 1;
+      while (j < rows && cut[j + 1] - cut[i] <= max_window_bytes) ++j;
+      if (pass) cuts_out[windows] = cut[i];
+      ++windows;
+      i = j;
+    }
+    if (pass) cuts_out[windows] = cut[rows];
+    if (!cuts_out || cap < windows + 1) break;             // (the count alone: nothing is written into a list that is too short)
+  }
+  return (int64_t)windows;
+}
+
+uint64_t b3w_bao_set_slice_stream_scratch_bytes(uint64_t len, const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges,
+                                                uint64_t max_window_bytes) {
+  std::vector<uint64_t> cut;
+  std::string why;
+  if (max_window_bytes < B3W_BAO_SET_SLICE_STREAM_MIN_WINDOW || !b3w_int_set_stream_cuts(len, host_first, host_count, n_ranges, cut, nullptr, why)) return 0;
+  const size_t rows = cut.size() - 1;
+  uint64_t most = 0;
+  for (size_t i = 0, j = 0; i < rows; ++i) {               // the most rows any window of that many bytes can hold, wherever it starts
+    if (j < i + 1) j = i + 1;
+    while (j < rows && cut[j + 1] - cut[i] <= max_window_bytes) ++j;
+    if (j - i > most) most = j - i;
+  }
+  return B3W_BAO_SET_SLICE_STREAM_CARRY_BYTES + 16 * most;
 }
 
 int64_t b3w_bao_set_slice(const uint8_t *outboard, uint64_t len, uint32_t group_log, const uint64_t *host_first, const uint64_t *host_count,

@@ -34,6 +34,14 @@ struct SetList {
 bool b3w_int_set_list(const uint64_t *lens, uint32_t n_files, const uint32_t *files, const uint64_t *first, const uint64_t *count, uint32_t n_ranges,
                       SetList &out);
 
+// The cuts of ONE set's slice (b3wit.h "set slices in windows"): cut[r] the offset of the first element whose least wanted chunk lies in
+// row r's block, rows in the table's order, cut[0] = 0 and cut[rows] the slice's size; *shrt (may be null): rows of 64.  false with why
+// for a list the set calls refuse, no run at all, or a file of more than 2^30 chunks.
+bool b3w_int_set_stream_cuts(uint64_t len, const uint64_t *first, const uint64_t *count, uint32_t n_ranges, std::vector<uint64_t> &cut, bool *shrt,
+                             std::string &why);
+// the same from the list b3w_int_set_list has made of these runs as the one file of a call (l.sets[0]): no second walk over the runs
+void b3w_int_set_stream_cuts(uint64_t len, const uint64_t *first, const uint64_t *count, uint32_t n_ranges, const SetList &l, std::vector<uint64_t> &cut);
+
 // The set planner's rows (b3w_sample_plan_set_slices_device).  For an ascending disjoint list a set's wanted chunks in ascending order are
 // the list's chunks in order, so the record rows are b3w_sample_rows_ranges': run_row = its range_row_first (n_ranges + 1 values, from
 // rows_before: O(depth) a range), and a table row's base is the first record row of the first wanted chunk at or behind chunk a0 (the

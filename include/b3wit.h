@@ -1552,6 +1552,83 @@ int32_t b3w_bao_set_slice_ingest_packed_device(b3w_ctx *ctx, uint8_t *d_chunks, 
                                                int32_t *d_chunk_status /* may be NULL */, uint64_t *d_have /* may be NULL */, void *d_scratch,
                                                uint64_t scratch_bytes, void *stream);
 
+/* ---- set slices in windows: ONE set's slice taken in as it arrives (still ABI 1.4: new names only) ------------------------------------
+ * The two set receivers above need the whole slice on the device before they verify a byte: the missing half of a 1 GiB file is one
+ * slice of 593 MB.  A SESSION takes the slice of one set (one file) in WINDOWS cut at row boundaries, in slice order, and its outputs
+ * are byte for byte those of the one-shot receiver over the whole slice.
+ * DEFINITIONS.  The set is the set calls' list for one file: ascending, disjoint, touching runs allowed.  Its ROWS and their kind (64 or
+ * 1 024 chunks) are b3w_bao_set_slice_ingest_device's.  Every element of the slice - a parent node or a chunk - has c0, the least wanted
+ * chunk under it; the slice is pre-order, so c0 never falls along it and the rows cut it into consecutive SEGMENTS: cut[r] is the offset
+ * of the first element whose c0 lies in row r's block, cut[0] = 0 (the header rides with row 0), cut[n_rows] the slice's size.  For
+ * r > 0, cut[r] is the end of the last wanted chunk in front of the block.  A WINDOW is slice bytes [cut[i], cut[j]), i < j, and a
+ * session's next window starts where the last one ended.  A segment is never longer than B3W_BAO_SET_SLICE_STREAM_MIN_WINDOW = 8 + 64 x
+ * (24 + 1 023) + 1 048 576 bytes.  Slices start at 8 modulo 16 in the one-shot layout, so every cut but 0 is 16-byte aligned there:
+ * a window's first byte must lie at 8 modulo 16 for cut 0 and at 0 modulo 16 for any other cut.
+ * WHAT IS CARRIED from window to window is the header and, a depth t < 24, the last node of that depth above a block seen so far: 16 +
+ * 64 x 24 bytes at the front of the scratch.  The ancestor at depth t of any later row is that node (DESIGN.md 8g has the proof).
+ * NOTHING CARRIED IS TRUSTED: a row hashes its carried nodes against the root exactly as it hashes slice nodes, so the statuses are the
+ * one-shot call's by construction.  The carry is written by the push's last launch, after the window's rows have read it: PUSHES ARE A
+ * SERIAL DEPENDENCY, and the caller orders each push behind the previous one (the same stream, or events). */
+#define B3W_BAO_SET_SLICE_STREAM_MIN_WINDOW 1115592ull
+#define B3W_BAO_SET_SLICE_STREAM_CARRY_BYTES 1552ull
+#define B3W_BAO_SET_STREAM_ARENA  0 /* d_dest is the file's place in an arena: chunk c at d_dest + 1024 c, any byte alignment */
+#define B3W_BAO_SET_STREAM_PACKED 1 /* d_dest is a slot buffer: the wanted chunk of rank k at d_dest + 1024 k, 16-byte aligned */
+typedef struct b3w_bao_set_stream b3w_bao_set_stream;
+/* Host only.  The windows of at most max_window_bytes, filled greedily with as many whole rows as fit: their ascending cut offsets,
+ * windows + 1 values from 0 to the slice's size, into cuts_out when cap >= windows + 1 (nothing is written otherwise).  Returns the
+ * number of windows either way; -B3W_E_BAD_ARGUMENT for a list the set calls refuse, no run, a file of more than 2^30 chunks or
+ * max_window_bytes < B3W_BAO_SET_SLICE_STREAM_MIN_WINDOW.  O(rows + runs), O(depth) a run on the file's ragged right edge; no step a
+ * chunk. */
+int64_t b3w_bao_set_slice_stream_cuts(uint64_t preimage_len, const uint64_t *host_first, const uint64_t *host_count, uint32_t n_ranges,
+                                      uint64_t max_window_bytes, uint64_t *cuts_out, uint64_t cap);
+/* Host only.  The session's scratch: B3W_BAO_SET_SLICE_STREAM_CARRY_BYTES, then 16 bytes a row of the window with the most rows among
+ * all windows of at most max_window_bytes, wherever they start.  0 where the cuts call refuses. */
+uint64_t b3w_bao_set_slice_stream_scratch_bytes(uint64_t preimage_len, const uint64_t *host_first, const uint64_t *host_count,
+                                                uint32_t n_ranges, uint64_t max_window_bytes);
+/* Begins a session.  dest_kind B3W_BAO_SET_STREAM_ARENA: (d_dest, dest_bytes) is the file's place in an arena and d_outboard its
+ * outboard at this group_log, with the meanings, alignments and nullabilities of b3w_bao_set_slice_ingest_device for one file at
+ * offset 0.  B3W_BAO_SET_STREAM_PACKED: (d_dest, dest_bytes) is b3w_bao_set_slice_ingest_packed_device's slot buffer and d_outboard may
+ * be NULL (decode only).  d_root: the file's 8 root words.  d_have, d_chunk_status may be NULL; d_have is the file's bitmap.  The row
+ * table is built here, once, on the host (344 or 224 bytes a row) and the context's staging ring is grown to the largest window the
+ * scratch allows; d_set_status and d_set_first_bad are set to 0 and UINT64_MAX ("none") on `stream`.  Refused, atomically (nothing
+ * launched or written, *out_session NULL): what the one-shot call of that kind refuses, no run, an unknown kind, a scratch smaller than
+ * B3W_BAO_SET_SLICE_STREAM_CARRY_BYTES + 16, null or not 16-byte aligned. */
+int32_t b3w_bao_set_slice_stream_begin(b3w_ctx *ctx, uint64_t preimage_len, uint32_t group_log, const uint64_t *host_first,
+                                       const uint64_t *host_count, uint32_t n_ranges, const uint32_t *d_root, uint32_t dest_kind,
+                                       uint8_t *d_dest, uint64_t dest_bytes, uint8_t *d_outboard, uint64_t *d_have /* may be NULL */,
+                                       int32_t *d_chunk_status /* may be NULL */, int32_t *d_set_status, uint64_t *d_set_first_bad,
+                                       void *d_scratch, uint64_t scratch_bytes, void *stream, b3w_bao_set_stream **out_session);
+/* Takes in the window of `bytes` bytes at d_window, slice bytes [offset, offset + bytes): verifies its rows, writes their chunks, nodes,
+ * bitmap bits and per-chunk statuses as the one-shot call does, folds the rows' results into d_set_status (the largest) and
+ * d_set_first_bad (the least) - a bad window is known when its push is done - and carries the header and the nodes later rows need.  At
+ * most THREE launches (in fact two: a set's rows are of one kind; then the fold, which also writes the carry); only this window's rows
+ * go up, through a slot of the context's staging ring of eight.  TWO LIMITS: begin grows the slots that are free at that moment, so a
+ * push that lands on a slot which was in flight then and is still too small frees and allocates it (hipHostMalloc / hipMalloc, which
+ * wait for the device) - otherwise a push allocates nothing; and the host waits for nothing only while fewer than eight uploads of
+ * this context are in flight: with every slot busy a push waits for the oldest (a session of many small windows does).  No byte
+ * outside the window is read but the carry.  REFUSALS ARE ATOMIC and each names its reason: a finished
+ * session or one whose slice is all pushed, a null window or no bytes, an offset that is not where the last window ended (out of
+ * order), an end that is not on a cut, a first byte that is not at 8 (offset 0) or 0 modulo 16, more rows than the scratch holds.
+ * Nothing is launched or written and the session stays usable.
+ * WHEN NOT TO (MI355X, one 1 GiB file with half its chunks missing, 262 507 runs, 593 MB of slice in 1 024 rows; the
+ * yardstick is a build of the parent commit's b3w_bao_set_slice_ingest_device loaded beside this library, over the same RESIDENT slice;
+ * device events round whole calls - a whole session: begin, every push, finish, free -, the routes alternating, medians, every output
+ * compared byte for byte before timing; no profiler run): A SLICE THAT IS ALREADY RESIDENT.  The one-shot call takes 3.39 ms (spread
+ * 0.01).  A session costs begin - the one-shot call's host work, 2.8 ms with these runs - and then 0.17 ms a push (0.21 at 64 MiB) whatever the
+ * window holds, because a push waits for the one before it and a window of a few rows leaves most of the device idle: 9 windows of
+ * 64 MiB 4.66 ms (1.37 times the one-shot call), 74 of 8 MiB 15.8 ms (4.7 times), 986 of the least window 171.6 ms (50 times).  What
+ * a session buys is the memory and the first verdict: two windows of 64 MiB are 134 MB on the device where the one-shot call holds
+ * 593 MB, two of the least one 2.2 MB; and a tampered header is reported 2.95 ms after begin (begin and the first push) where the
+ * one-shot call reports it 3.1 ms after the LAST byte has arrived.  So: windows as large as memory allows, never the least one for
+ * throughput.  Not measured: the arrival itself (the copies that a session overlaps and the one-shot call must wait for), the packed
+ * destination, files past 1 GiB, the kernels one by one. */
+int32_t b3w_bao_set_slice_stream_push(b3w_bao_set_stream *session, uint64_t offset, const uint8_t *d_window, uint64_t bytes, void *stream);
+/* Host only; no launch.  Refuses a session whose slice was not pushed to its end (or that is finished); afterwards every push is
+ * refused.  The outputs are final when the last push is done. */
+int32_t b3w_bao_set_slice_stream_finish(b3w_bao_set_stream *session);
+/* Frees the host object (a session owns no device memory and no event); safe during an open graph capture.  NULL is a no-op. */
+void b3w_bao_set_slice_stream_free(b3w_bao_set_stream *session);
+
 /* ---- updates in place after writes to resident files (still ABI 1.4: new names only) --------------------------------
  * Every call above treats a file as immutable: after one rewritten block the only way to a correct outboard and root is the batch
  * call over the whole file again.  These calls make the cost follow the bytes written.  GIVEN an arena with its offsets and

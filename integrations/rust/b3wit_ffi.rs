@@ -131,7 +131,7 @@ extern "C" {
     // bao slices taken into packed chunk slots (the file need not be resident; d_outboards null: decode only)
     pub fn b3w_bao_slice_ingest_packed_device(ctx: *mut c_void, d_chunks: *mut u8, chunks_bytes: u64, host_lens: *const u64, n_files: u32, group_log: u32, d_outboards: *mut u8, d_roots: *const u32, host_files: *const u32, host_chunks: *const u64, n_samples: u32, d_slices: *const u8, d_sample_status: *mut i32, d_have: *mut u64, stream: *mut c_void) -> i32;
     pub fn b3w_bao_range_slice_ingest_packed_device(ctx: *mut c_void, d_chunks: *mut u8, chunks_bytes: u64, host_lens: *const u64, n_files: u32, group_log: u32, d_outboards: *mut u8, d_roots: *const u32, host_files: *const u32, host_first: *const u64, host_count: *const u64, n_ranges: u32, d_slices: *const u8, d_range_status: *mut i32, d_range_first_bad: *mut u64, d_have: *mut u64, d_scratch: *mut c_void, scratch_bytes: u64, stream: *mut c_void) -> i32;
-    pub fn b3w_bao_set_slice_ingest_packed_device(ctx: *mut c_void, d_chunks: *mut u8, chunks_bytes: u64, host_lens: *const u64, n_files: u32, group_log: u32, d_outboards: *mut u8, d_roots: *const u32, host_files: *const u32, host_first: *const u64, host_count: *const u64, n_ranges: u32, d_slices: *const u8, d_set_status: *mut i32, d_set_first_bad: *mut u64, d_chunk_status: *mut i32, d_have: *mut u64, d_scratch: *mut c_void, scratch_bytes: u64, stream: *mut c_void) -> i32;
+    pub fn b3w_bao_set_slice_ingest_packed_device(ctx: *mut c_void, d_chunks: *mut u8, chunks_bytes: u64, host_lens: *const u64, n_files: u32, group_log: u32, d_outboards: *mut u8, d_roots: *const u32, host_files: *const u32, host_first: *const u64, host_count: *const u64, n_ranges: u32, d_slices: *const u8, d_set_status: *mut i32, d_set_first_bad: *mut u64, d_chunk_status: *mut i32, d_have: *mut u64, d_scratch: *mut c_void, scratch_bytes: u64, stream: *mut c_void) -> i32; pub fn b3w_bao_set_slice_stream_cuts(preimage_len: u64, host_first: *const u64, host_count: *const u64, n_ranges: u32, max_window_bytes: u64, cuts_out: *mut u64, cap: u64) -> i64; pub fn b3w_bao_set_slice_stream_scratch_bytes(preimage_len: u64, host_first: *const u64, host_count: *const u64, n_ranges: u32, max_window_bytes: u64) -> u64; pub fn b3w_bao_set_slice_stream_begin(ctx: *mut c_void, preimage_len: u64, group_log: u32, host_first: *const u64, host_count: *const u64, n_ranges: u32, d_root: *const u32, dest_kind: u32, d_dest: *mut u8, dest_bytes: u64, d_outboard: *mut u8, d_have: *mut u64, d_chunk_status: *mut i32, d_set_status: *mut i32, d_set_first_bad: *mut u64, d_scratch: *mut c_void, scratch_bytes: u64, stream: *mut c_void, out_session: *mut *mut c_void) -> i32; pub fn b3w_bao_set_slice_stream_push(session: *mut c_void, offset: u64, d_window: *const u8, bytes: u64, stream: *mut c_void) -> i32; pub fn b3w_bao_set_slice_stream_finish(session: *mut c_void) -> i32; pub fn b3w_bao_set_slice_stream_free(session: *mut c_void); // one set's slice taken in window by window as it arrives (windows cut at row boundaries, pushed in slice order; dest_kind 0: the file's place in an arena, 1: packed slots, d_outboard may then be null)
     // the chunks two versions of a file share, from their outboards alone (a bitmap in the arrival-bitmap layout of the b lengths); then outboard deltas: b's nodes that a does not hold, served (provider) and verified against b's root before they are written (replica)
     pub fn b3w_bao_outboard_diff_device(ctx: *mut c_void, host_lens_a: *const u64, host_ob_first_a: *const u64, d_outboards_a: *const u8, outboards_a_bytes: u64, d_roots_a: *const u32, n_files_a: u32, group_log_a: u32, host_lens_b: *const u64, host_ob_first_b: *const u64, d_outboards_b: *const u8, outboards_b_bytes: u64, d_roots_b: *const u32, n_files_b: u32, group_log_b: u32, host_pair_a: *const u32, host_pair_b: *const u32, n_pairs: u32, host_word_first: *const u64, d_same: *mut u64, stream: *mut c_void) -> i32; pub fn b3w_bao_outboard_diff(outboard_a: *const u8, len_a: u64, root_a: *const u32, group_log_a: u32, outboard_b: *const u8, len_b: u64, root_b: *const u32, group_log_b: u32, same_words: *mut u64) -> i32;
     pub fn b3w_bao_outboard_delta_bound(len_b: u64, group_log: u32) -> u64; pub fn b3w_bao_outboard_delta_layout(host_lens_b: *const u64, n_files_b: u32, host_pair_b: *const u32, n_pairs: u32, group_log: u32, delta_first: *mut u64) -> u64; pub fn b3w_bao_outboard_delta_scratch_bytes(host_lens_b: *const u64, n_files_b: u32, host_pair_b: *const u32, n_pairs: u32, group_log: u32) -> u64; pub fn b3w_bao_outboard_delta_device(ctx: *mut c_void, host_lens_a: *const u64, host_ob_first_a: *const u64, d_outboards_a: *const u8, outboards_a_bytes: u64, d_roots_a: *const u32, n_files_a: u32, host_lens_b: *const u64, host_ob_first_b: *const u64, d_outboards_b: *const u8, outboards_b_bytes: u64, d_roots_b: *const u32, n_files_b: u32, group_log_a: u32, group_log_b: u32, host_pair_a: *const u32, host_pair_b: *const u32, n_pairs: u32, host_delta_first: *const u64, d_delta: *mut u8, delta_bytes: u64, d_n_nodes: *mut u64, d_scratch: *mut c_void, scratch_bytes: u64, stream: *mut c_void) -> i32; pub fn b3w_bao_outboard_delta_apply_device(ctx: *mut c_void, host_lens_a: *const u64, host_ob_first_a: *const u64, d_outboards_a: *const u8, outboards_a_bytes: u64, d_roots_a: *const u32, n_files_a: u32, host_lens_b: *const u64, d_roots_b: *const u32, n_files_b: u32, group_log: u32, host_pair_a: *const u32, host_pair_b: *const u32, n_pairs: u32, host_delta_first: *const u64, d_delta: *const u8, delta_bytes: u64, host_ob_first_out: *const u64, d_outboards_out: *mut u8, outboards_out_bytes: u64, d_pair_status: *mut i32, d_first_bad: *mut u64, d_scratch: *mut c_void, scratch_bytes: u64, stream: *mut c_void) -> i32; pub fn b3w_bao_outboard_delta(outboard_a: *const u8, len_a: u64, root_a: *const u32, outboard_b: *const u8, len_b: u64, root_b: *const u32, group_log: u32, blob: *mut u8, blob_bytes: u64, n_nodes: *mut u64) -> i32; pub fn b3w_bao_outboard_delta_apply(outboard_a: *const u8, len_a: u64, root_a: *const u32, len_b: u64, root_b: *const u32, group_log: u32, blob: *const u8, blob_bytes: u64, outboard_out: *mut u8, status: *mut i32, first_bad: *mut u64) -> i32;
